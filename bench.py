@@ -4,12 +4,17 @@
 A "step" is one pass of the hot path over one batch of B synthetic frame pairs (front 1280x720 +
 bird 512x512, BASELINE.json configs[2]: HIP ORB extract + Hamming match + PoseOptimizationWithBird
 with ~2k front + ~1k bird edges).  All inputs are resident in HBM before the timed region.
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 For N>1 the driver launches one rank per GPU with torch.distributed.run; every rank processes its
 own batch (independent sequences -> weak scaling, no data-path collective).
 Prints ONE JSON line on rank 0.
 
-What the line carries besides the contract fields:
+A plain run sets up, runs W warm-up steps, times K steps and prints the headline (value = frames/s over the K steps,
+ms_per_step = milliseconds per timed step) with workload_check (key point / match / inlier means of the last step).
+--dump-outputs DIR writes what the last timed step computed, as its caller receives it, to DIR/<name>.npy (dump_outputs).
+
+--full adds everything else the line can carry; in a --full run only the dominant kernel carries
+HIP events inside the timed region:
   roofline      the dominant kernel of the SINGLE-STREAM pass (every kernel bracketed by HIP events on its launch stream,
                 no overlap: the same ranking `rocprofv3 --kernel-trace --stats` gives), its SURVEY 8(d) algorithmic bytes
                 per launch over its average launch duration inside the timed region; + the whole step against the roof
@@ -19,6 +24,8 @@ What the line carries besides the contract fields:
   cpu_baseline  the oracle on 1 core (per-stage medians over >= 50 frames after 5 warm-ups) and as
                 N independent sequences on N cores
   single_sequence  ms per frame pair at B = 1 and B = 8 (config 5's sequence count) with the same pipeline
+  + match, host_fed, config5_replicas, local_ba, track_chain, host_abi (--no-ba / --no-single / --no-chain / --cpu-sample
+    leave legs out)
 """
 import argparse
 import ctypes as C
@@ -64,10 +71,55 @@ def algorithmic_bytes_per_pair():
 
 
 def make_images(batch, rank):
+    """Every image from its own seed: the same bytes on every run whatever thread synthesises it."""
+    from concurrent.futures import ThreadPoolExecutor
     from fishbirdeyevisualslam_amd import synth
-    f = np.stack([synth.synth_image(1000 + rank * 10000 + i, *FRONT_WH) for i in range(batch)])
-    b = np.stack([synth.synth_image(1500 + rank * 10000 + i, *BIRD_WH) for i in range(batch)])
+    with ThreadPoolExecutor(max_workers=8) as ex:
+        f = np.stack(list(ex.map(lambda i: synth.synth_image(1000 + rank * 10000 + i, *FRONT_WH), range(batch))))
+        b = np.stack(list(ex.map(lambda i: synth.synth_image(1500 + rank * 10000 + i, *BIRD_WH), range(batch))))
     return f, b
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SEED = 20260
+DUMP_KP_FRAMES = 256     # frames whose per-key-point arrays are written (all of them up to this batch size)
+DUMP_DESC_FRAMES = 32    # frames whose descriptors are written (all B would pass the size cap: 2 x B x ~2000 x 32 values)
+
+
+def _dump_sample(B, k):
+    """A fixed, seeded choice of k of the B frames (ascending), all of them when B <= k."""
+    if B <= k:
+        return np.arange(B)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(B, k, replace=False))
+
+
+def dump_outputs(pipe, res, out_dir):
+    """What the last timed step computed, as a caller of FramePipeline receives it (results_host + keypoints_host), written
+    as out_dir/<name>.npy in float32 / float64 (every value exact: indices, counts, flags and descriptor bytes are small
+    integers).  Per-frame arrays cover the whole batch; per-key-point arrays hold each frame's first n entries (n_front /
+    n_bird), concatenated in frame order over the frames in kp_frames (desc_frames for the descriptors, one row of 32
+    byte values per key point)."""
+    B = pipe.B
+    kp_frames, desc_frames = _dump_sample(B, DUMP_KP_FRAMES), _dump_sample(B, DUMP_DESC_FRAMES)
+    arrays = {"n_front": res["n_front"].astype(np.float64), "n_bird": res["n_bird"].astype(np.float64),
+              "nm_front": res["nm_front"].astype(np.float64), "nm_bird": res["nm_bird"].astype(np.float64),
+              "ninliers": res["ninliers"].astype(np.float64), "Tcw": res["Tcw"].astype(np.float32),
+              "kp_frames": kp_frames.astype(np.float64), "desc_frames": desc_frames.astype(np.float64)}
+    for side in ("front", "bird"):
+        kps, desc = pipe.keypoints_host(side)
+        n = res["n_" + side]
+        for field in kps[0].dtype.names:
+            arrays["%s_kp_%s" % (side, field)] = np.concatenate([kps[b][field] for b in kp_frames]).astype(np.float32)
+        arrays[side + "_match"] = np.concatenate([res["m_" + side][b, :n[b]] for b in kp_frames]).astype(np.float32)
+        arrays[side + "_outlier"] = np.concatenate([res[side + "_outlier"][b, :n[b]] for b in kp_frames]).astype(np.float32)
+        arrays[side + "_desc"] = np.concatenate([desc[b].reshape(-1, 32) for b in desc_frames]).astype(np.float32)
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte cap" % (total, DUMP_MAX_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+    return total
 
 
 STAGES = ("extract_front", "extract_bird", "match_front", "match_bird", "pose_opt")
@@ -674,7 +726,15 @@ def main():
     ap.add_argument("--no-single", action="store_true", help="skip the B=1 / B=8 single-sequence sub-results")
     ap.add_argument("--no-chain", action="store_true", help="skip the tracking-chain and host-ABI sub-results")
     ap.add_argument("--serial", action="store_true", help="single-stream steps (kernels do not overlap; for profiling)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: the single-stream kernel pass (roofline, per-kernel tables), cpu_baseline "
+                         "+ parity_check against the oracle, config5_replicas, local_ba, single_sequence, track_chain, host_abi, "
+                         "match, host_fed (the --no-* / --cpu-sample options apply to these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, at most 64 MB)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -724,88 +784,96 @@ def main():
     step = step_serial_on_pose_stream if a.serial else pipe.step
     for _ in range(a.warmup):
         step()
-    ents = (cabi.ProfEntry * 48)()
+    kern_serial, kern, dom = None, None, None   # --full: the single-stream kernel table, the timed table, the dominant kernel
+    if a.full:
+        ents = (cabi.ProfEntry * 48)()
 
-    def prof_pass(fn, nsteps):
-        """nsteps untimed steps with every kernel bracketed by HIP events on its launch stream -> {kernel: (launches, total ms)}"""
-        torch.cuda.synchronize()
-        L.fb_prof_only(None)
-        L.fb_prof_reset()
-        L.fb_prof_enable(1)
-        for _ in range(nsteps):
-            fn()
-        torch.cuda.synchronize()
-        L.fb_prof_enable(0)
-        n_ = L.fb_prof_report(ents, 48)
-        return {ents[i].name.decode(): (ents[i].launches, ents[i].total_ms) for i in range(n_)}
+        def prof_pass(fn, nsteps):
+            """nsteps untimed steps with every kernel bracketed by HIP events on its launch stream -> {kernel: (launches, total ms)}"""
+            torch.cuda.synchronize()
+            L.fb_prof_only(None)
+            L.fb_prof_reset()
+            L.fb_prof_enable(1)
+            for _ in range(nsteps):
+                fn()
+            torch.cuda.synchronize()
+            L.fb_prof_enable(0)
+            n_ = L.fb_prof_report(ents, 48)
+            return {ents[i].name.decode(): (ents[i].launches, ents[i].total_ms) for i in range(n_)}
 
-    # untimed: single-stream steps with every kernel bracketed -> each kernel's own speed; the dominant kernel is the one
-    # with the largest total there (with three overlapped streams the event times of a kernel include its neighbours)
-    PROBE = 3
-    kern_serial = prof_pass(step_serial_on_pose_stream, PROBE)
-    # ranking by kernel: the instantiations of one kernel (k_fast<44> for the front levels, k_fast<56> / <72> for other cell
-    # sizes) count together; of the winning kernel the instantiation with the largest total is the one bracketed and reported
-    def family(name):
-        return name.split("<")[0]
-    fam_total = {}
-    for k_, (n_, ms_) in kern_serial.items():
-        fam_total[family(k_)] = fam_total.get(family(k_), 0.0) + ms_
-    dom_family = max(fam_total, key=fam_total.get)
-    dom = max((k_ for k_ in kern_serial if family(k_) == dom_family), key=lambda k_: kern_serial[k_][1])
-    for _ in range(2):
+        # untimed: single-stream steps with every kernel bracketed -> each kernel's own speed; the dominant kernel is the one
+        # with the largest total there (with three overlapped streams the event times of a kernel include its neighbours)
+        PROBE = 3
+        kern_serial = prof_pass(step_serial_on_pose_stream, PROBE)
+        # ranking by kernel: the instantiations of one kernel (k_fast<44> for the front levels, k_fast<56> / <72> for other cell
+        # sizes) count together; of the winning kernel the instantiation with the largest total is the one bracketed and reported
+        def family(name):
+            return name.split("<")[0]
+        fam_total = {}
+        for k_, (n_, ms_) in kern_serial.items():
+            fam_total[family(k_)] = fam_total.get(family(k_), 0.0) + ms_
+        dom_family = max(fam_total, key=fam_total.get)
+        dom = max((k_ for k_ in kern_serial if family(k_) == dom_family), key=lambda k_: kern_serial[k_][1])
+    for _ in range(2):   # the timed region starts right behind two untimed steps of its own kind, with or without --full
         step()
     barrier()
-    # timed region: only the dominant kernel stays bracketed (two events per launch cost ~8 us of stream bubble each)
-    L.fb_prof_only(dom.encode())
-    L.fb_prof_reset()
-    L.fb_prof_enable(1)
+    if a.full:
+        # timed region: only the dominant kernel stays bracketed (two events per launch cost ~8 us of stream bubble each)
+        L.fb_prof_only(dom.encode())
+        L.fb_prof_reset()
+        L.fb_prof_enable(1)
     t0 = time.perf_counter()
     for _ in range(a.steps):
         step()
     torch.cuda.synchronize()
     barrier()
     elapsed = time.perf_counter() - t0
-    L.fb_prof_enable(0)
-    L.fb_prof_only(None)
+    if a.full:
+        L.fb_prof_enable(0)
+        L.fb_prof_only(None)
     if world_size > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if rehearsal else "cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    n = L.fb_prof_report(ents, 48)
-    kern = {ents[i].name.decode(): (ents[i].launches, ents[i].total_ms) for i in range(n)}
+    if a.full:
+        n = L.fb_prof_report(ents, 48)
+        kern = {ents[i].name.decode(): (ents[i].launches, ents[i].total_ms) for i in range(n)}
     res = pipe.results_host()
-    # BASELINE configs[4], the replica form SURVEY 8e recommends: 8 sequences per GPU, every GPU its own 8 (weak scaling)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(pipe, res, a.dump_outputs)
     config5 = None
-    try:
-        if a.no_single:
-            raise RuntimeError("skipped (--no-single)")
-        f8, b8 = make_images(8, rank)
-        p8 = FramePipeline(8, FRONT_WH, BIRD_WH, device="cuda:%d" % local_rank)
-        p8.set_images(f8, b8)
-        p8.build_world(seed=5000 + rank * 10000)
-        for _ in range(10):
-            p8.step()
-        barrier()
-        t8 = time.perf_counter()
-        for _ in range(100):
-            p8.step()
-        torch.cuda.synchronize()
-        barrier()
-        e8 = time.perf_counter() - t8
-        if world_size > 1:
-            tt = torch.tensor([e8], dtype=torch.float64, device="cpu" if rehearsal else "cuda")
-            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-            e8 = float(tt.item())
-        config5 = {"workload": "configs[4] as replicas: 8 sequences per GPU (independent frame pairs, no data-path collective)",
-                   "frame_pairs_per_step_per_gpu": 8, "steps": 100, "ms_per_step": e8 / 100 * 1e3, "frames_per_s": world_size * 8 * 100 / e8,
-                   "n_gpus": world_size, "note": "the landmark-sharded BA of the same config is local_ba (mode names the transport)"}
-        p8.close()
-    except Exception as e:  # noqa: BLE001
-        config5 = {"error": str(e)[:200]}
+    if a.full:
+        # BASELINE configs[4], the replica form SURVEY 8e recommends: 8 sequences per GPU, every GPU its own 8 (weak scaling)
+        try:
+            if a.no_single:
+                raise RuntimeError("skipped (--no-single)")
+            f8, b8 = make_images(8, rank)
+            p8 = FramePipeline(8, FRONT_WH, BIRD_WH, device="cuda:%d" % local_rank)
+            p8.set_images(f8, b8)
+            p8.build_world(seed=5000 + rank * 10000)
+            for _ in range(10):
+                p8.step()
+            barrier()
+            t8 = time.perf_counter()
+            for _ in range(100):
+                p8.step()
+            torch.cuda.synchronize()
+            barrier()
+            e8 = time.perf_counter() - t8
+            if world_size > 1:
+                tt = torch.tensor([e8], dtype=torch.float64, device="cpu" if rehearsal else "cuda")
+                dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+                e8 = float(tt.item())
+            config5 = {"workload": "configs[4] as replicas: 8 sequences per GPU (independent frame pairs, no data-path collective)",
+                       "frame_pairs_per_step_per_gpu": 8, "steps": 100, "ms_per_step": e8 / 100 * 1e3, "frames_per_s": world_size * 8 * 100 / e8,
+                       "n_gpus": world_size, "note": "the landmark-sharded BA of the same config is local_ba (mode names the transport)"}
+            p8.close()
+        except Exception as e:  # noqa: BLE001
+            config5 = {"error": str(e)[:200]}
     ba = None
     ba_hung = False
-    if not a.no_ba:
+    if a.full and not a.no_ba:
         # the secondary leg must never take the headline line down: exceptions are caught, and with several ranks (collectives
         # inside the BA) it runs under a deadline -- a rank stuck in an exchange is reported instead of waited for
         box = {}
@@ -836,55 +904,7 @@ def main():
 
     rc = 0
     if rank == 0:
-        alg = algorithmic_bytes_per_pair()
-
-        def alg_key(k):  # the byte model lists blur and describe together
-            return "k_blur+k_describe" if k in ("k_blur", "k_describe") else k
-
-        def ser(k):      # (launches, total ms) of a byte-model entry in the single-stream pass
-            if k == "k_blur+k_describe":
-                kb, kd = kern_serial.get("k_blur", (0, 0.0)), kern_serial.get("k_describe", (0, 0.0))
-                return (max(kb[0], kd[0]), kb[1] + kd[1])
-            return kern_serial.get(k)
-        launches, ms = kern[dom]
-        per_launch_ms = ms / launches
-        # bytes ONE launch of the dominant kernel must move = per-pair bytes x B pairs x steps / launches in the timed region
-        alg_per_launch = alg.get(alg_key(dom), 0) * B * a.steps / launches
-        if alg_key(dom) == "k_blur+k_describe":  # the pair shares P: charge the launch with the pair's time
-            other = "k_describe" if dom == "k_blur" else "k_blur"
-            per_launch_model_ms = per_launch_ms + kern_serial[other][1] / kern_serial[other][0]
-        else:
-            per_launch_model_ms = per_launch_ms
-        achieved = alg_per_launch / (per_launch_model_ms * 1e-3) / 1e9 if per_launch_model_ms > 0 else 0.0
-        traffic, traffic_src = None, None
-        try:  # PMC counters cannot be read inside this process: per-launch means of separate rocprofv3 --pmc passes
-            tj = os.path.join(ROOT, "profiles", "r03_pmc_traffic.json")
-            if not os.path.exists(tj):
-                tj = os.path.join(ROOT, "profiles", "r02_pmc_traffic.json")
-            with open(tj) as f:
-                pt = json.load(f)
-            if pt.get("batch") == B and dom in pt["kernels"]:
-                traffic = pt["kernels"][dom]["hbm_bytes_per_launch"]
-                traffic_src = "profiles/" + os.path.basename(tj) + ": " + pt.get("method", "")
-        except (OSError, ValueError, KeyError):
-            pass
         ms_step = elapsed / a.steps * 1e3
-        runner_up = None
-        try:  # the second throughput bottleneck: blur + describe on their shared byte model (they move P once between them)
-            bd_ms = (kern_serial["k_blur"][1] + kern_serial["k_describe"][1]) / PROBE
-            bd_alg = alg["k_blur+k_describe"] * B
-            runner_up = {"kernel": "k_blur+k_describe", "bound": "hbm", "achieved": bd_alg / (bd_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": bd_alg / (bd_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "ms_per_step_single_stream": bd_ms,
-                         "algorithmic_bytes_per_step": bd_alg, "traffic": None}
-            with open(os.path.join(ROOT, "profiles", "r03_pmc_traffic.json")) as f:
-                pt = json.load(f)
-            if pt.get("batch") == B:
-                # two launches of each per step (front images, bird images); the json holds the mean over both kinds
-                tb = sum(pt["kernels"][k]["hbm_bytes_per_launch"] * 2 for k in ("k_blur", "k_describe") if k in pt["kernels"])
-                runner_up["traffic"] = tb
-                runner_up["traffic_over_algorithmic"] = tb / bd_alg
-        except (OSError, ValueError, KeyError, ZeroDivisionError):
-            pass
         out = {
             "metric": "frames/s (extract+match+pose-opt), 1280x720+512x512 pair",
             "value": world_size * B * a.steps / elapsed,
@@ -901,74 +921,127 @@ def main():
             "config": {"workload": "configs[2]: 1280x720 front + 512x512 bird pair, HIP ORB extract + M3/M9 Hamming match + "
                                    "PoseOptimizationWithBird (~2k front + ~1k bird edges)",
                        "frame_pairs_per_step_per_gpu": B, "nfeatures": 2000, "parallelism": "replicas x%d" % world_size},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                         "avg_launch_ms": per_launch_ms, "launches_timed": launches, "algorithmic_bytes_per_launch": alg_per_launch,
-                         "avg_launch_ms_single_stream": kern_serial[dom][1] / kern_serial[dom][0],
-                         "byte_model": "SURVEY 8(d): FAST reads every level once (P); blur + describe share P; resize (P-px7)+(P-px0)",
-                         "note": "dominant kernel = largest total in the untimed single-stream pass (every kernel bracketed by HIP "
-                                 "events on its launch stream); achieved = its algorithmic bytes per launch / its average launch "
-                                 "duration in the timed region, where only this kernel carries events",
-                         "step": {"algorithmic_bytes_per_pair": PAIR_BYTES, "achieved": PAIR_BYTES * B / (ms_step * 1e-3) / 1e9,
-                                  "frac": PAIR_BYTES * B / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS, "unit": "GB/s",
-                                  "note": "whole step: extract bytes of B pairs / ms_per_step"}},
-            "roofline_runner_up": runner_up,
-            "kernels_ms_per_step_single_stream": {k: v[1] / PROBE for k, v in sorted(kern_serial.items(), key=lambda kv: -kv[1][1])},
-            "kernel_ms_sum_single_stream": sum(v[1] for v in kern_serial.values()) / PROBE,
-            # north_star: "HBM GB/s for matching" -- algorithmic bytes / single-stream kernel time for every byte-model entry
-            "hbm_gbs_single_stream": {k: {"gbs": alg[k] * B * PROBE / (ser(k)[1] * 1e-3) / 1e9,
-                                          "frac": alg[k] * B * PROBE / (ser(k)[1] * 1e-3) / 1e9 / HBM_PEAK_GBS}
-                                      for k in alg if ser(k) and ser(k)[1] > 0},
-            "workload_check": {"kps_front": float(res["n_front"].mean()), "kps_bird": float(res["n_bird"].mean()),
-                               "front_matches": float(res["nm_front"].mean()), "bird_matches": float(res["nm_bird"].mean()),
-                               "pose_inliers": float(res["ninliers"].mean())},
         }
-        try:
-            out["match"] = match_pair_rate(pipe, world, kern_serial, PROBE, B)
-        except Exception as e:  # a reporting extra must never cost the bench line
-            out["match"] = {"error": str(e)[:200]}
-        try:
-            out["host_fed"] = host_fed_leg(pipe, front, bird, B)
-        except Exception as e:  # noqa: BLE001
-            out["host_fed"] = {"error": str(e)[:200]}
-        out["local_ba"] = ba
-        out["config5_replicas"] = config5
-        # the CPU legs run on rank 0 of the single-GPU run only (N > 1 would stall the other ranks)
-        out["cpu_baseline"], out["parity_check"] = None, None
-        if a.cpu_sample > 0 and world_size == 1:
-            ns = min(a.cpu_sample, B)
-            fk, fd = pipe.keypoints_host("front")
-            bk, bd = pipe.keypoints_host("bird")
-            refs = []
-            out["cpu_baseline"] = cpu_baseline(world, ns, rank, refs)
-            out["parity_check"] = parity_check(refs, fk, fd, bk, bd, res)
-            if out["parity_check"]["mismatches"]:
-                rc = 3
-        if not a.no_single and world_size == 1:
+        if a.full:
+            alg = algorithmic_bytes_per_pair()
+
+            def alg_key(k):  # the byte model lists blur and describe together
+                return "k_blur+k_describe" if k in ("k_blur", "k_describe") else k
+
+            def ser(k):      # (launches, total ms) of a byte-model entry in the single-stream pass
+                if k == "k_blur+k_describe":
+                    kb, kd = kern_serial.get("k_blur", (0, 0.0)), kern_serial.get("k_describe", (0, 0.0))
+                    return (max(kb[0], kd[0]), kb[1] + kd[1])
+                return kern_serial.get(k)
+            launches, ms = kern[dom]
+            per_launch_ms = ms / launches
+            # bytes ONE launch of the dominant kernel must move = per-pair bytes x B pairs x steps / launches in the timed region
+            alg_per_launch = alg.get(alg_key(dom), 0) * B * a.steps / launches
+            if alg_key(dom) == "k_blur+k_describe":  # the pair shares P: charge the launch with the pair's time
+                other = "k_describe" if dom == "k_blur" else "k_blur"
+                per_launch_model_ms = per_launch_ms + kern_serial[other][1] / kern_serial[other][0]
+            else:
+                per_launch_model_ms = per_launch_ms
+            achieved = alg_per_launch / (per_launch_model_ms * 1e-3) / 1e9 if per_launch_model_ms > 0 else 0.0
+            traffic, traffic_src = None, None
+            try:  # PMC counters cannot be read inside this process: per-launch means of separate rocprofv3 --pmc passes
+                tj = os.path.join(ROOT, "profiles", "r03_pmc_traffic.json")
+                if not os.path.exists(tj):
+                    tj = os.path.join(ROOT, "profiles", "r02_pmc_traffic.json")
+                with open(tj) as f:
+                    pt = json.load(f)
+                if pt.get("batch") == B and dom in pt["kernels"]:
+                    traffic = pt["kernels"][dom]["hbm_bytes_per_launch"]
+                    traffic_src = "profiles/" + os.path.basename(tj) + ": " + pt.get("method", "")
+            except (OSError, ValueError, KeyError):
+                pass
+            runner_up = None
+            try:  # the second throughput bottleneck: blur + describe on their shared byte model (they move P once between them)
+                bd_ms = (kern_serial["k_blur"][1] + kern_serial["k_describe"][1]) / PROBE
+                bd_alg = alg["k_blur+k_describe"] * B
+                runner_up = {"kernel": "k_blur+k_describe", "bound": "hbm", "achieved": bd_alg / (bd_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS,
+                             "unit": "GB/s", "frac": bd_alg / (bd_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "ms_per_step_single_stream": bd_ms,
+                             "algorithmic_bytes_per_step": bd_alg, "traffic": None}
+                with open(os.path.join(ROOT, "profiles", "r03_pmc_traffic.json")) as f:
+                    pt = json.load(f)
+                if pt.get("batch") == B:
+                    # two launches of each per step (front images, bird images); the json holds the mean over both kinds
+                    tb = sum(pt["kernels"][k]["hbm_bytes_per_launch"] * 2 for k in ("k_blur", "k_describe") if k in pt["kernels"])
+                    runner_up["traffic"] = tb
+                    runner_up["traffic_over_algorithmic"] = tb / bd_alg
+            except (OSError, ValueError, KeyError, ZeroDivisionError):
+                pass
+            out.update({
+                "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+                             "avg_launch_ms": per_launch_ms, "launches_timed": launches, "algorithmic_bytes_per_launch": alg_per_launch,
+                             "avg_launch_ms_single_stream": kern_serial[dom][1] / kern_serial[dom][0],
+                             "byte_model": "SURVEY 8(d): FAST reads every level once (P); blur + describe share P; resize (P-px7)+(P-px0)",
+                             "note": "dominant kernel = largest total in the untimed single-stream pass (every kernel bracketed by HIP "
+                                     "events on its launch stream); achieved = its algorithmic bytes per launch / its average launch "
+                                     "duration in the timed region, where only this kernel carries events",
+                             "step": {"algorithmic_bytes_per_pair": PAIR_BYTES, "achieved": PAIR_BYTES * B / (ms_step * 1e-3) / 1e9,
+                                      "frac": PAIR_BYTES * B / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS, "unit": "GB/s",
+                                      "note": "whole step: extract bytes of B pairs / ms_per_step"}},
+                "roofline_runner_up": runner_up,
+                "kernels_ms_per_step_single_stream": {k: v[1] / PROBE for k, v in sorted(kern_serial.items(), key=lambda kv: -kv[1][1])},
+                "kernel_ms_sum_single_stream": sum(v[1] for v in kern_serial.values()) / PROBE,
+                # north_star: "HBM GB/s for matching" -- algorithmic bytes / single-stream kernel time for every byte-model entry
+                "hbm_gbs_single_stream": {k: {"gbs": alg[k] * B * PROBE / (ser(k)[1] * 1e-3) / 1e9,
+                                              "frac": alg[k] * B * PROBE / (ser(k)[1] * 1e-3) / 1e9 / HBM_PEAK_GBS}
+                                          for k in alg if ser(k) and ser(k)[1] > 0},
+            })
+        # the means of the timed step's own outputs (read back above): what the headline's workload was
+        out["workload_check"] = {"kps_front": float(res["n_front"].mean()), "kps_bird": float(res["n_bird"].mean()),
+                                 "front_matches": float(res["nm_front"].mean()), "bird_matches": float(res["nm_bird"].mean()),
+                                 "pose_inliers": float(res["ninliers"].mean())}
+        if a.full:
             try:
-                out["single_sequence"] = {"independent_frames": single_sequence_leg(FramePipeline, rank, local_rank),
-                                          "note": "independent_frames = the configs[2] step at B = 1 / 8 with NO data dependency between "
-                                                  "consecutive steps (throughput of unrelated frame pairs); dependent = the tracking chain below, "
-                                                  "frame k+1 predicted from frame k's optimised pose: THAT is a single sequence"}
-            except Exception as e:
-                out["single_sequence"] = {"error": str(e)[:200]}
-        if not a.no_chain and world_size == 1:
+                out["match"] = match_pair_rate(pipe, world, kern_serial, PROBE, B)
+            except Exception as e:  # a reporting extra must never cost the bench line
+                out["match"] = {"error": str(e)[:200]}
             try:
-                tcl = track_chain_leg(rank, local_rank)
-                out["track_chain"] = tcl
-                if isinstance(out.get("single_sequence"), dict):
-                    out["single_sequence"]["dependent"] = {k: {"serial": tcl[k]["dependent"], "pipelined_frame_construction": tcl[k]["dependent_pipelined"]}
-                                                           for k in ("b1", "b8") if k in tcl}
-                if tcl.get("parity_check", {}).get("mismatches"):
+                out["host_fed"] = host_fed_leg(pipe, front, bird, B)
+            except Exception as e:  # noqa: BLE001
+                out["host_fed"] = {"error": str(e)[:200]}
+            out["local_ba"] = ba
+            out["config5_replicas"] = config5
+            # the CPU legs run on rank 0 of the single-GPU run only (N > 1 would stall the other ranks)
+            out["cpu_baseline"], out["parity_check"] = None, None
+            if a.cpu_sample > 0 and world_size == 1:
+                ns = min(a.cpu_sample, B)
+                fk, fd = pipe.keypoints_host("front")
+                bk, bd = pipe.keypoints_host("bird")
+                refs = []
+                out["cpu_baseline"] = cpu_baseline(world, ns, rank, refs)
+                out["parity_check"] = parity_check(refs, fk, fd, bk, bd, res)
+                if out["parity_check"]["mismatches"]:
                     rc = 3
-            except Exception as e:
-                out["track_chain"] = {"error": str(e)[:300]}
-            try:
-                out["host_abi"] = host_abi_leg(rank)
-                if out.get("cpu_baseline"):
-                    out["host_abi"]["cpu_oracle_stage_ms_median"] = out["cpu_baseline"]["one_core"]["stage_ms_median"]
-            except Exception as e:
-                out["host_abi"] = {"error": str(e)[:300]}
+            if not a.no_single and world_size == 1:
+                try:
+                    out["single_sequence"] = {"independent_frames": single_sequence_leg(FramePipeline, rank, local_rank),
+                                              "note": "independent_frames = the configs[2] step at B = 1 / 8 with NO data dependency between "
+                                                      "consecutive steps (throughput of unrelated frame pairs); dependent = the tracking chain below, "
+                                                      "frame k+1 predicted from frame k's optimised pose: THAT is a single sequence"}
+                except Exception as e:
+                    out["single_sequence"] = {"error": str(e)[:200]}
+            if not a.no_chain and world_size == 1:
+                try:
+                    tcl = track_chain_leg(rank, local_rank)
+                    out["track_chain"] = tcl
+                    if isinstance(out.get("single_sequence"), dict):
+                        out["single_sequence"]["dependent"] = {k: {"serial": tcl[k]["dependent"], "pipelined_frame_construction": tcl[k]["dependent_pipelined"]}
+                                                               for k in ("b1", "b8") if k in tcl}
+                    if tcl.get("parity_check", {}).get("mismatches"):
+                        rc = 3
+                except Exception as e:
+                    out["track_chain"] = {"error": str(e)[:300]}
+                try:
+                    out["host_abi"] = host_abi_leg(rank)
+                    if out.get("cpu_baseline"):
+                        out["host_abi"]["cpu_oracle_stage_ms_median"] = out["cpu_baseline"]["one_core"]["stage_ms_median"]
+                except Exception as e:
+                    out["host_abi"] = {"error": str(e)[:300]}
         print(json.dumps(out), flush=True)
         if rc:
             print("bench.py: GPU results differ from the oracle: %s" % out["parity_check"]["details"], file=sys.stderr, flush=True)

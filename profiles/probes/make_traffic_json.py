@@ -1,5 +1,5 @@
 """profiles/r02_pmc_traffic.json from two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE; rocpd databases) of
-`bench.py --serial --no-ba --cpu-sample 0 --no-single --batch B`.
+`bench.py --full --serial --no-ba --cpu-sample 0 --no-single --batch B`.
 
 Corrections (MI355X_MICROARCH.md, HBM section): rocprofv3 reports both counters in KB.  WRITE_SIZE is exact for streaming
 stores.  FETCH_SIZE under-reports reads on gfx950: exactly 1/2 for 16-byte-per-lane streams; other widths must be

@@ -1,9 +1,8 @@
 """ctypes loader of oracle/_ref/libref_dbow2.so = the reference's own DBoW2 FeatureVector.cpp / BowVector.cpp compiled
-where they lie (oracle/Makefile, target `ref`).  Test infrastructure; absent when neither the prebuilt .so nor
-/root/reference is there."""
+where they lie (oracle/Makefile, target `ref`, which build() runs where the reference tree is present).  Test
+infrastructure; absent elsewhere."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
@@ -13,14 +12,12 @@ _LIB = None
 
 
 def available():
-    return os.path.exists(SO) or os.path.isdir("/root/reference/Thirdparty/DBoW2/DBoW2")
+    return os.path.exists(SO)
 
 
 def lib():
     global _LIB
     if _LIB is None:
-        if not os.path.exists(SO):
-            subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "ref"])
         _LIB = C.CDLL(SO)
     return _LIB
 

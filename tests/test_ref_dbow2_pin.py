@@ -1,9 +1,11 @@
 """Pins oracle/bow_oracle.cpp (and the synthetic FeatureVector of bow_problem.py) against the one piece of the reference that
-builds here: DBoW2's own FeatureVector.cpp / BowVector.cpp, compiled from /root/reference into oracle/_ref (tests/ref_dbow2.py),
-plus the committed fixture those produced (tests/golden/dbow2_ref.npz).  What is pinned: the container order of
-FeatureVector::addFeature (FeatureVector.cpp:31-45), the accumulation order of BowVector::addWeight (BowVector.cpp:30-43) and
-the L1 normalisation (:58-84) -- bit for bit, doubles included.  What stays unpinned: the tree descent itself
-(TemplatedVocabulary.h needs OpenCV) and the vocabulary (no file in the reference)."""
+builds with plain g++: DBoW2's own FeatureVector.cpp / BowVector.cpp, compiled from the reference tree into oracle/_ref by
+`make -C oracle ref` (tests/ref_dbow2.py), through the committed fixtures those produced: tests/golden/dbow2_ref.npz (random
+id / weight streams) and tests/golden/dbow2_ref_pin.npz (the exact streams the first two tests below feed the containers).
+What is pinned: the container order of FeatureVector::addFeature (FeatureVector.cpp:31-45), the accumulation order of
+BowVector::addWeight (BowVector.cpp:30-43) and the L1 normalisation (:58-84) -- bit for bit, doubles included.  What stays
+unpinned: the tree descent itself (TemplatedVocabulary.h needs OpenCV) and the vocabulary (no file in the reference).
+Where the reference build is present, the last fixture test checks that it still reproduces both fixtures."""
 import ctypes as C
 import os
 
@@ -16,6 +18,35 @@ from fishbirdeyevisualslam_amd import bow_problem, synth
 from test_bow_transform import _descs, make_args, make_vocabulary
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "dbow2_ref.npz")
+PIN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "dbow2_ref_pin.npz")
+NO_REF_BUILD = "oracle/_ref/libref_dbow2.so (the reference's DBoW2 containers, `make -C oracle ref`) is not present"
+
+
+class Recorded:
+    """The reference containers of every stream this module feeds them, as the reference build returned them (PIN).
+    A stream the fixture does not hold is an error, not a pass: the fixture and these tests must be regenerated together
+    (tests/golden/make_dbow2_ref_golden.py)."""
+
+    def __init__(self, path=PIN):
+        z = np.load(path)
+        self.fv = [tuple(z["fv%d_%s" % (i, k)] for k in ("node", "ids", "start", "items")) for i in range(int(z["n_fv"]))]
+        self.bow = [tuple(z["bow%d_%s" % (i, k)] for k in ("word", "w", "ids", "vals")) for i in range(int(z["n_bow"]))]
+
+    def feature_vector(self, node_ids):
+        node_ids = np.ascontiguousarray(node_ids, np.uint32)
+        for node, ids, start, items in self.fv:
+            if node.shape == node_ids.shape and np.array_equal(node, node_ids):
+                return ids, start, items
+        raise AssertionError("tests/golden/dbow2_ref_pin.npz holds no FeatureVector of this node-id stream (n = %d)" % len(node_ids))
+
+    def bow_vector(self, word_ids, weights, normalize=True):
+        assert normalize, "the fixture holds normalised BowVectors only"
+        word_ids = np.ascontiguousarray(word_ids, np.uint32)
+        weights = np.ascontiguousarray(weights, np.float64)
+        for word, w, ids, vals in self.bow:
+            if word.shape == word_ids.shape and np.array_equal(word, word_ids) and w.tobytes() == weights.tobytes():
+                return ids, vals
+        raise AssertionError("tests/golden/dbow2_ref_pin.npz holds no BowVector of this (word id, weight) stream (n = %d)" % len(word_ids))
 
 
 def _leaf_stream(vk, first_leaf, d, k, L, levelsup):
@@ -63,26 +94,31 @@ def _check_against(fv_fn, bow_fn, label):
             np.testing.assert_array_equal(out["fv_items"][b, :start[-1]], items, err_msg=label)
 
 
-@pytest.mark.skipif(not ref_dbow2.available(), reason="neither oracle/_ref/libref_dbow2.so nor /root/reference is present")
-def test_bow_oracle_matches_the_reference_containers():
-    _check_against(ref_dbow2.feature_vector, lambda ids, w: ref_dbow2.bow_vector(ids, w, True), "oracle/_ref")
-
-
-@pytest.mark.skipif(not ref_dbow2.available(), reason="neither oracle/_ref/libref_dbow2.so nor /root/reference is present")
-def test_synthetic_feature_vector_is_what_addFeature_builds():
-    """bow_problem.feature_vector (SURVEY 8d config 1: NodeId from two descriptor bytes) == DBoW2::FeatureVector::addFeature."""
+def _check_synthetic(fv_fn):
     g = synth.rng(8810)
     for n in (1, 17, 2000):
         desc = synth.random_descriptors(g, n)
         ids, start, items = bow_problem.feature_vector(desc)
         node = ((desc[:, 0].astype(np.int64) % 10) * 10 + desc[:, 1].astype(np.int64) % 10).astype(np.uint32)
-        rid, rstart, ritems = ref_dbow2.feature_vector(node)
+        rid, rstart, ritems = fv_fn(node)
         np.testing.assert_array_equal(ids, rid)
         np.testing.assert_array_equal(start, rstart)
         np.testing.assert_array_equal(items, ritems)
 
 
-@pytest.mark.skipif(not ref_dbow2.available(), reason="neither oracle/_ref/libref_dbow2.so nor /root/reference is present")
+def test_bow_oracle_matches_the_reference_containers():
+    """The reference containers of these streams come from PIN (what oracle/_ref returned for them when the fixture was made)."""
+    r = Recorded()
+    _check_against(r.feature_vector, lambda ids, w: r.bow_vector(ids, w, True), "oracle/_ref (recorded)")
+
+
+def test_synthetic_feature_vector_is_what_addFeature_builds():
+    """bow_problem.feature_vector (SURVEY 8d config 1: NodeId from two descriptor bytes) == DBoW2::FeatureVector::addFeature
+    (recorded in PIN)."""
+    _check_synthetic(Recorded().feature_vector)
+
+
+@pytest.mark.skipif(not ref_dbow2.available(), reason=NO_REF_BUILD)
 def test_fixture_is_reproduced_by_the_reference_build():
     z = np.load(GOLD)
     for c in range(4):
@@ -91,6 +127,17 @@ def test_fixture_is_reproduced_by_the_reference_build():
         np.testing.assert_array_equal(ids, z["c%d_fv_ids" % c])
         np.testing.assert_array_equal(items, z["c%d_fv_items" % c])
         assert bval.tobytes() == z["c%d_bow_vals" % c].tobytes()
+    # ... and the streams the first two tests take from PIN
+    r = Recorded()
+    for node, ids, start, items in r.fv:
+        rid, rstart, ritems = ref_dbow2.feature_vector(node)
+        np.testing.assert_array_equal(rid, ids)
+        np.testing.assert_array_equal(rstart, start)
+        np.testing.assert_array_equal(ritems, items)
+    for word, w, ids, vals in r.bow:
+        rid, rval = ref_dbow2.bow_vector(word, w, True)
+        np.testing.assert_array_equal(rid, ids)
+        assert rval.tobytes() == vals.tobytes()
 
 
 def test_restated_containers_match_the_reference_fixture():
