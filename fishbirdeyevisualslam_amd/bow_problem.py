@@ -164,3 +164,190 @@ def make_vocabulary(seed, k=10, L=3, stop_frac=0.05):
     v = cabi.Vocabulary()
     fill(v, n_nodes=n_nodes, L=L, **keep)
     return v, keep, first_leaf
+
+
+# ---- LocalMapping::CreateNewMapPoints -------------------------------------------------------------------------------
+def _project(T, X, fx, fy, cx, cy):
+    Xc = X @ T[:3, :3].T + T[:3, 3]
+    return np.stack([fx * Xc[:, 0] / Xc[:, 2] + cx, fy * Xc[:, 1] / Xc[:, 2] + cy], 1), Xc[:, 2]
+
+
+def make_new_points_problem(seed, n_nb=20, n1=2000, n2=2000, w=640, h=480, fx=400.0, fy=400.0, pixel_noise=0.5, plants=True):
+    """One static scene, a current key frame (KF1) and n_nb covisible neighbours that see overlapping subsets of it, with pixel
+    noise, outliers, existing map points (has_mp*) and synthetic feature vectors (feature_vector()).  KF1 feature i observes
+    scene point i (truth["xw"][i]; NaN for outliers).  With plants=True it also holds (indices in truth["plants"]):
+      short   a neighbour whose baseline / median depth is below 0.01 (n_nb >= 3)
+      far     points thousands of metres away (cos parallax > 0.9998)
+      behind  points in front of KF1 but behind neighbour `behind_nb` (which moved forward past them)
+      chi2    KF1 octave 0 / neighbour 0 octave 7, the neighbour-0 copy 6 px off the epipolar line (inside M7's 7 px band)
+      scale   KF1 octave 0 / neighbour 0 octave 7 on the exact projection (ratioOctave ~ 0.28)
+      chi2 and scale points are also seen, correctly, by neighbour `second_nb`
+      dup     pairs of KF1 features on one scene point: both match the same neighbour slot (many-to-one)"""
+    g = synth.rng(seed)
+    cx, cy = w / 2.0, h / 2.0
+    K = np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1.0]])
+    sf, _, _, _ = synth.scale_tables()
+    T1 = synth.random_pose(g)
+    R1, t1 = T1[:3, :3], T1[:3, 3]
+    Ow1 = -R1.T @ t1
+    kps1 = synth.random_keypoints(g, n1, w, h, margin=20)
+    # scene point of every KF1 feature (noiseless pixel, depth)
+    z = g.uniform(3.0, 25.0, n1)
+    n_plant = min(n1 // 10, 200) if plants else 0
+    npl = n_plant // 5
+    sl = dict(far=np.arange(0, npl), behind=np.arange(npl, 2 * npl), chi2=np.arange(2 * npl, 3 * npl), scale=np.arange(3 * npl, 4 * npl),
+              dup=np.arange(4 * npl, 5 * npl))
+    base = n1 - n_plant
+    for k in sl:
+        sl[k] = sl[k] + base
+    z[sl["far"]] = g.uniform(3000.0, 6000.0, npl)
+    # behind: neighbour `behind_nb` sits 3 m ahead of KF1; the points lie 1-2 m in front of KF1
+    z[sl["behind"]] = g.uniform(1.0, 2.0, npl)
+    kps1["octave"][sl["chi2"]] = 0
+    kps1["octave"][sl["scale"]] = 0
+    uv_true = np.stack([kps1["x"].astype(np.float64), kps1["y"].astype(np.float64)], 1)
+    Xc1 = np.stack([(uv_true[:, 0] - cx) / fx * z, (uv_true[:, 1] - cy) / fy * z, z], 1)
+    Xw = (R1.T @ (Xc1 - t1).T).T
+    # dup: the second feature of a pair re-observes the scene point of the first (features base+4npl.. pair with ..+npl/2)
+    half = npl // 2
+    d0, d1 = sl["dup"][:half], sl["dup"][half:2 * half]
+    Xw[d1] = Xw[d0]
+    uv1 = _project(T1, Xw, fx, fy, cx, cy)[0]
+    n1_noise = g.normal(0, pixel_noise, (n1, 2)) if pixel_noise > 0 else np.zeros((n1, 2))
+    kps1["x"] = (uv1[:, 0] + n1_noise[:, 0]).astype(np.float32)
+    kps1["y"] = (uv1[:, 1] + n1_noise[:, 1]).astype(np.float32)
+    kps1["octave"][d1] = kps1["octave"][d0]
+    scene_desc = synth.random_descriptors(g, n1)
+    scene_desc[d1] = scene_desc[d0]
+    desc1 = synth.flip_bits(g, scene_desc, p=0.03)
+    desc1[:, :2] = scene_desc[:, :2]
+    outlier1 = g.random(n1) < 0.12
+    outlier1[base:] = False
+    desc1[outlier1] = synth.random_descriptors(g, int(outlier1.sum()))
+    has_mp1 = (g.random(n1) < 0.3).astype(np.uint8)
+    has_mp1[base:] = 0
+    truth_xw = Xw.copy()
+    truth_xw[outlier1] = np.nan
+    short_nb = 2 if (plants and n_nb >= 3) else -1
+    behind_nb = 1 if (plants and n_nb >= 2) else -1
+    second_nb = 3 if n_nb > 3 else n_nb - 1
+    nbs = []
+    for b in range(n_nb):
+        D = np.eye(4)
+        D[:3, :3] = synth.so3_exp(g.normal(0, 0.04, 3))
+        dirn = g.normal(0, 1, 3)
+        dirn[2] *= 0.3
+        D[:3, 3] = dirn / np.linalg.norm(dirn) * g.uniform(0.4, 1.6)
+        if b == short_nb:
+            D[:3, :3] = np.eye(3)
+            D[:3, 3] = [0.02, 0.0, 0.0]
+        if b == behind_nb:
+            D[:3, :3] = np.eye(3)
+            D[:3, 3] = [-0.5, 0.1, -3.0]  # camera centre 3 m ahead of KF1 (tcw2 = tcw1 - c)
+        T2 = D @ T1
+        uv2, z2 = _project(T2, Xw, fx, fy, cx, cy)
+        inside = (uv2[:, 0] > 10) & (uv2[:, 0] < w - 10) & (uv2[:, 1] > 10) & (uv2[:, 1] < h - 10)
+        vis = inside & (z2 > 0) & (g.random(n1) < 0.5)
+        if plants:
+            vis[base:] = False
+            vis[sl["far"]] = inside[sl["far"]] & (z2[sl["far"]] > 0)
+            vis[d0] = inside[d0] & (z2[d0] > 0) & (b % 2 == 0)
+            if b == behind_nb:
+                vis[sl["behind"]] = inside[sl["behind"]]
+            if b in (0, second_nb):
+                vis[sl["chi2"]] = inside[sl["chi2"]] & (z2[sl["chi2"]] > 0)
+                vis[sl["scale"]] = inside[sl["scale"]] & (z2[sl["scale"]] > 0)
+        src = np.nonzero(vis)[0]
+        n_copy = min(len(src), int(0.75 * n2))
+        keep_plant = src[src >= base]
+        rest = src[src < base]
+        src = np.concatenate([keep_plant, g.permutation(rest)[: max(n_copy - len(keep_plant), 0)]])
+        n_copy = len(src)
+        k2 = synth.random_keypoints(g, n2, w, h, margin=20)
+        d2 = synth.random_descriptors(g, n2)
+        slot = g.permutation(n2)[:n_copy]
+        noise2 = g.normal(0, pixel_noise, (n_copy, 2)) if pixel_noise > 0 else np.zeros((n_copy, 2))
+        px = uv2[src] + noise2
+        oc = kps1["octave"][src].copy()
+        if plants and b == 0:
+            # chi2 / scale plants: octave 7 here; chi2 ones 6 px off the epipolar line of the KF1 feature
+            R2, t2 = T2[:3, :3], T2[:3, 3]
+            R12 = R1 @ R2.T
+            t12 = -R1 @ R2.T @ t2 + t1
+            tx = np.array([[0, -t12[2], t12[1]], [t12[2], 0, -t12[0]], [-t12[1], t12[0], 0]])
+            F12 = np.linalg.inv(K).T @ tx @ R12 @ np.linalg.inv(K)
+            for j, s_ in enumerate(src):
+                if s_ in set(sl["chi2"]) or s_ in set(sl["scale"]):
+                    oc[j] = 7
+                    px[j] = uv2[s_]
+                if s_ in set(sl["chi2"]):
+                    l = np.array([kps1["x"][s_], kps1["y"][s_], 1.0]) @ F12
+                    nrm = l[:2] / np.linalg.norm(l[:2])
+                    px[j] = px[j] + 6.0 * nrm
+        k2["x"][slot] = px[:, 0].astype(np.float32)
+        k2["y"][slot] = px[:, 1].astype(np.float32)
+        k2["octave"][slot] = oc
+        cp = synth.flip_bits(g, scene_desc[src], p=0.03)
+        cp[:, :2] = scene_desc[src, :2]
+        d2[slot] = cp
+        has2 = (g.random(n2) < 0.3).astype(np.uint8)
+        is_plant_slot = np.zeros(n2, bool)
+        is_plant_slot[slot[src >= base]] = True
+        has2[is_plant_slot] = 0
+        # the neighbour's map points (ComputeSceneMedianDepth input): the scene point of a copy slot, else a point in front
+        owner = np.full(n2, -1)
+        owner[slot] = src
+        mps = []
+        for s_ in np.nonzero(has2)[0]:
+            if owner[s_] >= 0:
+                mps.append(Xw[owner[s_]])
+            else:
+                zz = g.uniform(3.0, 25.0)
+                xc = np.array([(k2["x"][s_] - cx) / fx * zz, (k2["y"][s_] - cy) / fy * zz, zz])
+                mps.append(T2[:3, :3].T @ (xc - T2[:3, 3]))
+        if not mps:
+            mps.append(Xw[0])
+        nbs.append(dict(kps=k2, desc=d2, has_mp=has2, T=T2, mp_xw=np.asarray(mps, np.float32).reshape(-1, 3),
+                        before=np.uint8(g.random() < 0.5), owner=owner))
+    sf_, _, sig2, _ = synth.scale_tables()
+    return dict(kps1=kps1, desc1=desc1, has_mp1=has_mp1, Tcw1=synth.to12(T1), nbs=nbs, fx=fx, fy=fy, cx=cx, cy=cy,
+                scale_factors=sf_, level_sigma2=sig2, n_levels=8, scale_factor=1.2,
+                truth=dict(xw=truth_xw, T1=T1, plants=dict(sl, dup_pairs=np.stack([d0, d1], 1)), short_nb=short_nb, behind_nb=behind_nb,
+                           second_nb=second_nb))
+
+
+def new_points_args(prob, n_nb=None, kf1_stride=None, kf2_stride=None):
+    """-> (cabi.NewPointsArgs with host pointers, out dict, keepalive).  n_nb: use the first n_nb neighbours only."""
+    nbs = prob["nbs"][: (len(prob["nbs"]) if n_nb is None else n_nb)]
+    B = len(nbs)
+    n1 = len(prob["kps1"])
+    s1 = kf1_stride or max(n1, 1)
+    s2 = kf2_stride or max([len(x["kps"]) for x in nbs] + [1])
+    pad = lambda a, n, tail=(), dt=None: np.concatenate([a, np.zeros((n - len(a),) + tail, dt or a.dtype)])
+    kps2 = np.stack([pad(x["kps"], s2) for x in nbs]) if B else np.zeros((1, s2), cabi.KP_DTYPE)
+    desc2 = np.stack([pad(x["desc"], s2, (32,)) for x in nbs]) if B else np.zeros((1, s2, 32), np.uint8)
+    has2 = np.stack([pad(x["has_mp"], s2) for x in nbs]) if B else np.zeros((1, s2), np.uint8)
+    starts = np.concatenate([[0], np.cumsum([len(x["mp_xw"]) for x in nbs])]).astype(np.int32)
+    mp_xw = np.concatenate([x["mp_xw"] for x in nbs]) if B else np.zeros((1, 3), np.float32)
+    keep = dict(n1=np.array([n1], np.int32), kps1=pad(prob["kps1"], s1), desc1=pad(prob["desc1"], s1, (32,)),
+                Tcw1=np.ascontiguousarray(prob["Tcw1"], np.float32),
+                n2=np.array([len(x["kps"]) for x in nbs] or [0], np.int32), kps2=kps2, desc2=desc2,
+                Tcw2=np.stack([synth.to12(x["T"]) for x in nbs]) if B else np.zeros((1, 12), np.float32),
+                nb_mp_start=starts, nb_mp_xw=np.ascontiguousarray(mp_xw, np.float32),
+                nb_before_kf1=np.array([x["before"] for x in nbs] or [0], np.uint8))
+    out = dict(has_mp1=pad(prob["has_mp1"], s1).copy(), has_mp2=has2.copy(), n_new=np.full(1, -7, np.int32),
+               xw=np.zeros((s1, 3), np.float32), normal=np.zeros((s1, 3), np.float32), max_dist=np.zeros(s1, np.float32),
+               min_dist=np.zeros(s1, np.float32), desc=np.zeros((s1, 32), np.uint8), idx1=np.full(s1, -7, np.int32),
+               nb=np.full(s1, -7, np.int32), idx2=np.full(s1, -7, np.int32), kf1_new=np.full(s1, -7, np.int32),
+               kf2_new=np.full((max(B, 1), s2), -7, np.int32), nb_matches=np.full(max(B, 1), -7, np.int32),
+               nb_new=np.full(max(B, 1), -7, np.int32), nb_skipped=np.full(max(B, 1), -7, np.int32))
+    fv1, k1 = _fv_struct([feature_vector(prob["desc1"])], 100, s1)
+    fv2, k2 = _fv_struct([feature_vector(x["desc"]) for x in nbs] or [feature_vector(np.zeros((1, 32), np.uint8))], 100, s2)
+    a = cabi.NewPointsArgs()
+    fill(a, n_nb=B, kf1_stride=s1, kf2_stride=s2, fx=prob["fx"], fy=prob["fy"], cx=prob["cx"], cy=prob["cy"],
+         scale_factors=[float(x) for x in prob["scale_factors"]] + [1.0] * (cabi.FB_MAX_LEVELS - len(prob["scale_factors"])),
+         level_sigma2=[float(x) for x in prob["level_sigma2"]] + [1.0] * (cabi.FB_MAX_LEVELS - len(prob["level_sigma2"])),
+         n_levels=prob["n_levels"], scale_factor=prob["scale_factor"], **keep, **out)
+    a.fv1, a.fv2 = fv1, fv2
+    fill(a.matcher, nnratio=0.6, check_orientation=0)
+    return a, out, (keep, k1, k2)

@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 
 FB_MAX_LEVELS = 16
+FB_NEW_POINTS_MAX_NB = 64
 FB_OK, FB_ERR_ARG, FB_ERR_HIP, FB_ERR_CAPACITY, FB_ERR_NODEVICE = 0, -1, -2, -3, -4
 FB_POSE_FRONT, FB_POSE_FRONT_BIRD, FB_POSE_BIRD = 0, 1, 2
 
@@ -148,6 +149,19 @@ class BowKfArgs(C.Structure):
                 ("n1", _vp), ("kps1", _vp), ("desc1", _vp), ("has_mp1", _vp), ("fv1", FeatureVector),
                 ("n2", _vp), ("kps2", _vp), ("desc2", _vp), ("has_mp2", _vp), ("fv2", FeatureVector),
                 ("matcher", MatcherParams), ("matches12", _vp), ("nmatches", _vp)]
+
+
+class NewPointsArgs(C.Structure):
+    _fields_ = [("n_nb", _i32), ("kf1_stride", _i32), ("kf2_stride", _i32),
+                ("n1", _vp), ("kps1", _vp), ("desc1", _vp), ("fv1", FeatureVector), ("Tcw1", _vp), ("has_mp1", _vp),
+                ("n2", _vp), ("kps2", _vp), ("desc2", _vp), ("fv2", FeatureVector), ("Tcw2", _vp), ("has_mp2", _vp),
+                ("nb_mp_start", _vp), ("nb_mp_xw", _vp), ("nb_before_kf1", _vp),
+                ("fx", _f32), ("fy", _f32), ("cx", _f32), ("cy", _f32),
+                ("scale_factors", _f32 * FB_MAX_LEVELS), ("level_sigma2", _f32 * FB_MAX_LEVELS), ("n_levels", _i32),
+                ("scale_factor", _f32), ("matcher", MatcherParams),
+                ("n_new", _vp), ("xw", _vp), ("normal", _vp), ("max_dist", _vp), ("min_dist", _vp), ("desc", _vp),
+                ("idx1", _vp), ("nb", _vp), ("idx2", _vp), ("kf1_new", _vp), ("kf2_new", _vp),
+                ("nb_matches", _vp), ("nb_new", _vp), ("nb_skipped", _vp), ("workspace", _vp), ("workspace_bytes", C.c_size_t)]
 
 
 class KfTarget(C.Structure):
@@ -298,6 +312,7 @@ EXPORTS = [
     "fb_match_projection_sim3_dev", "fb_match_projection_sim3", "fb_match_sim3_dev", "fb_match_sim3",
     "fb_match_initialization_dev", "fb_match_initialization",
     "fb_distinctive_descriptors_dev", "fb_distinctive_descriptors",
+    "fb_create_new_map_points_workspace", "fb_create_new_map_points_dev", "fb_create_new_map_points",
     "fb_bird_filter_matches_dev", "fb_bird_filter_matches", "fb_bow_transform_dev", "fb_bow_transform",
     "fb_in_frustum_dev", "fb_in_frustum", "fb_undistort_keypoints_dev", "fb_undistort_keypoints", "fb_image_bounds",
     "fb_pose_opt_batch_dev", "fb_pose_opt", "fb_pose_gather_front_dev", "fb_pose_gather_bird_dev",

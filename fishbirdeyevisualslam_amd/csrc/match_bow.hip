@@ -230,12 +230,16 @@ __global__ __launch_bounds__(BOW_THREADS) void k_match_bow_t(fb_bow_args A, cons
 }
 
 // ---------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(BOW_THREADS) void k_match_triangulation(fb_triangulation_args A, int descInLds) {
+// shared1 = 1 (CreateNewMapPoints, mapping.hip): one KF1 for every batch entry -- its arrays (n1, kps1, desc1, has_mp1, fv1)
+// are read at batch index 0, matches12 is still written per entry; entries with skip[b] != 0 (the baseline gate) exit at once.
+__global__ __launch_bounds__(BOW_THREADS) void k_match_triangulation(fb_triangulation_args A, int descInLds, int shared1, const int32_t *skip) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
-  const size_t o1 = (size_t)b * A.kf1_stride, o2 = (size_t)b * A.kf2_stride;
-  const int n1 = A.n1[b], n2 = A.n2[b];
-  const FVd V1 = fv_of(A.fv1, b), V2 = fv_of(A.fv2, b);
+  if (skip && skip[b]) return;
+  const int b1 = shared1 ? 0 : b;
+  const size_t o1 = (size_t)b1 * A.kf1_stride, o2 = (size_t)b * A.kf2_stride, om = (size_t)b * A.kf1_stride;
+  const int n1 = A.n1[b1], n2 = A.n2[b];
+  const FVd V1 = fv_of(A.fv1, b1), V2 = fv_of(A.fv2, b);
   const int nQ = V1.n > 0 ? V1.start[V1.n] : 0;
   const size_t descBytes = descInLds ? (size_t)A.kf2_stride * 32 : 0;
   const uint4 *desc2 = descInLds ? reinterpret_cast<const uint4 *>(smem) : reinterpret_cast<const uint4 *>(A.desc2 + o2 * 32);
@@ -318,7 +322,7 @@ __global__ __launch_bounds__(BOW_THREADS) void k_match_triangulation(fb_triangul
     }
     __syncthreads();
   }
-  for (int i = tid; i < n1; i += nt) A.matches12[o1 + i] = m12[i];
+  for (int i = tid; i < n1; i += nt) A.matches12[om + i] = m12[i];
   if (tid == 0) A.nmatches[b] = s_n;
 }
 
@@ -338,6 +342,21 @@ void stage_fv(fb::Stager &st, const fb_feature_vector &h, fb_feature_vector &d, 
 }
 
 }  // namespace
+
+namespace fb {
+// M7 for every neighbour of one key frame in one launch (fb_create_new_map_points_dev): KF1 shared, gated entries skipped
+int match_triangulation_shared(const fb_triangulation_args &A, const int32_t *skip, hipStream_t stream) {
+  size_t lds = (size_t)A.kf2_stride * 48 + (size_t)A.kf1_stride * 8 + 16;
+  const int descInLds = lds <= 160 * 1024 - 512;
+  if (!descInLds) lds -= (size_t)A.kf2_stride * 32;
+  FB_TRY(lds_ok(lds, "fb_create_new_map_points"));
+  FB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_match_triangulation), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  fb::ProfScope prof_(fb::P_NP_M7, stream);
+  k_match_triangulation<<<A.batch, BOW_THREADS, lds, stream>>>(A, descInLds, 1, skip);
+  FB_HIP(hipGetLastError());
+  return FB_OK;
+}
+}  // namespace fb
 
 extern "C" {
 
@@ -387,7 +406,7 @@ int fb_match_triangulation_dev(const fb_triangulation_args *A, void *stream) {
   FB_TRY(lds_ok(lds, "fb_match_triangulation"));
   FB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_match_triangulation), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   fb::ProfScope prof_(fb::P_TRIANG, fb::as_stream(stream));
-  k_match_triangulation<<<A->batch, BOW_THREADS, lds, fb::as_stream(stream)>>>(*A, descInLds);
+  k_match_triangulation<<<A->batch, BOW_THREADS, lds, fb::as_stream(stream)>>>(*A, descInLds, 0, nullptr);
   FB_HIP(hipGetLastError());
   return FB_OK;
 }

@@ -588,6 +588,77 @@ int fb_distinctive_descriptors_dev(const int32_t *d_obs_start, const uint8_t *d_
 int fb_distinctive_descriptors(const int32_t *obs_start, const uint8_t *obs_desc, int n_mp, int32_t *best_obs);
 
 /* ======================================================================== */
+/* LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:231-476)            */
+/* ======================================================================== */
+/* One key frame's new points: for each neighbour in GetBestCovisibilityKeyFrames(20) order the baseline / median-depth
+ * gate, ComputeF12, SearchForTriangulation (M7, ORBmatcher(0.6,false)), and per match in ascending idx1 the parallax test,
+ * the linear triangulation, the cheirality, chi2(2) and scale checks; then the point as MapPoint's constructor,
+ * ComputeDistinctiveDescriptors and UpdateNormalAndDepth (pKF1 = reference key frame) leave it.
+ * MONOCULAR ONLY: mvuRight = -1 for every key point (Frame.cc:252,323,799); the stereo / RGB-D branches
+ * (LocalMapping.cc:270-274,325-346,368-375,396-436) are not built.  `if(i>0 && CheckNewKeyFrames()) return;` is not polled:
+ * a caller that stops early passes fewer neighbours; the output of the first k neighbours is exactly the prefix of the
+ * output of all of them.
+ * Output rows: row k is the k-th `new MapPoint` of the reference (by neighbour, then ascending idx1); each KF1 feature
+ * gets at most one point, so kf1_stride rows always suffice.  Two KF1 features may match the same neighbour slot
+ * (vbMatched2 is never set): both become points and the slot holds the later one (kf2_new, has_mp2).
+ * Pointers are DEVICE pointers for _dev, except nb_mp_start, which is a HOST array in both entry points (the caller
+ * gathered the neighbours' points; the call validates it).  Errors: FB_ERR_ARG when matcher.check_orientation != 0
+ * (the per-feature claim below needs M7 without the rotation histogram), when a neighbour has no map point (the
+ * reference indexes an empty vector, KeyFrame.cc:994), when n_nb > FB_NEW_POINTS_MAX_NB, or when the workspace is
+ * missing / too small (_dev).  n_nb = 0 writes n_new = 0 and kf1_new = -1.                                          */
+#define FB_NEW_POINTS_MAX_NB 64
+typedef struct fb_new_points_args {
+  int32_t n_nb;                   /* neighbours, in covisibility order                                  */
+  int32_t kf1_stride, kf2_stride;
+  /* current key frame pKF1 */
+  const int32_t *n1;              /* [1] pKF1->N                                                        */
+  const fb_keypoint *kps1;        /* [kf1_stride] mvKeysUn                                              */
+  const uint8_t *desc1;           /* [kf1_stride][32]                                                   */
+  fb_feature_vector fv1;          /* batch 1                                                            */
+  const float *Tcw1;              /* [12] GetRotation | GetTranslation, row-major 3x4                   */
+  uint8_t *has_mp1;               /* in/out [kf1_stride]: GetMapPoint(i) != NULL                        */
+  /* neighbours pKF2, strided like the KF2 side of fb_triangulation_args */
+  const int32_t *n2;              /* [n_nb]                                                             */
+  const fb_keypoint *kps2;        /* [n_nb][kf2_stride]                                                 */
+  const uint8_t *desc2;           /* [n_nb][kf2_stride][32]                                             */
+  fb_feature_vector fv2;          /* batch n_nb                                                         */
+  const float *Tcw2;              /* [n_nb][12]                                                         */
+  uint8_t *has_mp2;               /* in/out [n_nb][kf2_stride]                                          */
+  const int32_t *nb_mp_start;     /* HOST [n_nb+1]: CSR over nb_mp_xw, every neighbour non-empty       */
+  const float *nb_mp_xw;          /* [nb_mp_start[n_nb]][3]: non-NULL mvpMapPoints' GetWorldPos()      */
+  const uint8_t *nb_before_kf1;   /* [n_nb]: (pKF2 < mpCurrentKeyFrame), the mObservations order       */
+  /* camera (both key frames) and extractor tables */
+  float fx, fy, cx, cy;
+  float scale_factors[FB_MAX_LEVELS];
+  float level_sigma2[FB_MAX_LEVELS];
+  int32_t n_levels;               /* mnScaleLevels                                                      */
+  float scale_factor;             /* mfScaleFactor                                                      */
+  fb_matcher_params matcher;      /* ORBmatcher(0.6,false) at LocalMapping.cc:239                       */
+  /* outputs, kf1_stride rows */
+  int32_t *n_new;                 /* [1]                                                                */
+  float *xw;                      /* [kf1_stride][3] GetWorldPos()      (fb_mp_list.mp_xw layout)       */
+  float *normal;                  /* [kf1_stride][3] GetNormal()                                        */
+  float *max_dist;                /* [kf1_stride] mfMaxDistance                                         */
+  float *min_dist;                /* [kf1_stride] mfMinDistance                                         */
+  uint8_t *desc;                  /* [kf1_stride][32] GetDescriptor()                                   */
+  int32_t *idx1;                  /* [kf1_stride] observation in pKF1                                   */
+  int32_t *nb;                    /* [kf1_stride] neighbour of the second observation                   */
+  int32_t *idx2;                  /* [kf1_stride] its index in that neighbour                           */
+  int32_t *kf1_new;               /* [kf1_stride] row of the point now in KF1 slot i, or -1             */
+  int32_t *kf2_new;               /* [n_nb][kf2_stride] row of the point now in the slot (last writer), or -1 */
+  int32_t *nb_matches;            /* [n_nb] SearchForTriangulation's return value for that neighbour    */
+  int32_t *nb_new;                /* [n_nb] points created with that neighbour                          */
+  int32_t *nb_skipped;            /* [n_nb] 1 = the baseline / median-depth gate skipped it             */
+  /* device scratch of fb_create_new_map_points_workspace(n_nb, kf1_stride) bytes, 16-byte aligned, private to the
+   * call until it has finished on `stream` (_dev only; the host drop-in allocates its own)                           */
+  void *workspace;
+  size_t workspace_bytes;
+} fb_new_points_args;
+size_t fb_create_new_map_points_workspace(int n_nb, int kf1_stride);
+int fb_create_new_map_points_dev(const fb_new_points_args *args, void *stream);
+int fb_create_new_map_points(const fb_new_points_args *args);
+
+/* ======================================================================== */
 /* DBoW2 vocabulary transform (Frame::ComputeBoW, src/Frame.cc:628-635)       */
 /* ======================================================================== */
 /* DBoW2::TemplatedVocabulary<FORB::TDescriptor, FORB> as flat arrays
