@@ -240,30 +240,22 @@ int fb_bow_transform(const fb_vocabulary *HV, const fb_bow_transform_args *H) {
   fb_vocabulary V = *HV;
   fb_bow_transform_args D = *H;
   const size_t B = H->batch, fs = H->f_stride, nn = HV->n_nodes;
-  fb::DevBuf v0, v1, v2, v3, v4, b0, b1, o0, o1, o2, o3, o4, o5, o6;
-  FB_TRY(v0.upload(HV->child_start, (nn + 1) * 4)); V.child_start = v0.as<int32_t>();
-  FB_TRY(v1.upload(HV->children, (size_t)HV->child_start[nn] * 4)); V.children = v1.as<int32_t>();
-  FB_TRY(v2.upload(HV->descriptors, nn * 32)); V.descriptors = v2.as<uint8_t>();
-  FB_TRY(v3.upload(HV->weights, nn * 8)); V.weights = v3.as<double>();
-  FB_TRY(v4.upload(HV->word_ids, nn * 4)); V.word_ids = v4.as<int32_t>();
-  FB_TRY(b0.upload(H->n_f, B * 4)); D.n_f = b0.as<int32_t>();
-  FB_TRY(b1.upload(H->desc, B * fs * 32)); D.desc = b1.as<uint8_t>();
-  FB_TRY(o0.alloc(B * 4)); D.n_words = o0.as<int32_t>();
-  FB_TRY(o1.upload(H->bow_ids, B * fs * 4)); D.bow_ids = o1.as<uint32_t>();  // copy-in: entries past n_f keep the caller's contents (those in [count, n_f) are scratch)
-  FB_TRY(o2.upload(H->bow_vals, B * fs * 8)); D.bow_vals = o2.as<double>();
-  FB_TRY(o3.alloc(B * 4)); D.fv_n_nodes = o3.as<int32_t>();
-  FB_TRY(o4.upload(H->fv_node_ids, B * fs * 4)); D.fv_node_ids = o4.as<uint32_t>();
-  FB_TRY(o5.upload(H->fv_node_start, B * (fs + 1) * 4)); D.fv_node_start = o5.as<int32_t>();
-  FB_TRY(o6.upload(H->fv_items, B * fs * 4)); D.fv_items = o6.as<int32_t>();
+  FB_ARG(HV->child_start && HV->children && HV->descriptors && HV->weights && HV->word_ids);
+  FB_ARG(H->n_f && H->desc && H->n_words && H->bow_ids && H->bow_vals && H->fv_n_nodes && H->fv_node_ids && H->fv_node_start && H->fv_items);
+  fb::Stager st;
+  st.in(V.child_start, (nn + 1) * 4); st.in(V.children, (size_t)HV->child_start[nn] * 4); st.in(V.descriptors, nn * 32);
+  st.in(V.weights, nn * 8); st.in(V.word_ids, nn * 4);
+  st.in(D.n_f, B * 4); st.in(D.desc, B * fs * 32);
+  st.out(D.n_words, B * 4, false);
+  st.out(D.bow_ids, B * fs * 4, true);  // copy-in: entries past n_f keep the caller's contents (those in [count, n_f) are scratch)
+  st.out(D.bow_vals, B * fs * 8, true);
+  st.out(D.fv_n_nodes, B * 4, false);
+  st.out(D.fv_node_ids, B * fs * 4, true);
+  st.out(D.fv_node_start, B * (fs + 1) * 4, true);
+  st.out(D.fv_items, B * fs * 4, true);
+  FB_TRY(st.commit(nullptr));
   FB_TRY(fb_bow_transform_dev(&V, &D, nullptr));
-  FB_HIP(hipDeviceSynchronize());
-  FB_TRY(o0.download(H->n_words, B * 4));
-  FB_TRY(o1.download(H->bow_ids, B * fs * 4));
-  FB_TRY(o2.download(H->bow_vals, B * fs * 8));
-  FB_TRY(o3.download(H->fv_n_nodes, B * 4));
-  FB_TRY(o4.download(H->fv_node_ids, B * fs * 4));
-  FB_TRY(o5.download(H->fv_node_start, B * (fs + 1) * 4));
-  return o6.download(H->fv_items, B * fs * 4);
+  return st.fetch(nullptr);
 }
 
 }  // extern "C"

@@ -105,8 +105,22 @@ struct DevBuf {
 // One staged transfer per host-pointer call.  The drop-in entry points used to upload every argument array with its own
 // synchronous hipMemcpy (16 of them for SearchByProjection: ~0.2 ms of a 0.33 ms call, `host_abi` in bench.py): the arrays of a
 // call are now packed into one page-locked block (per host thread, grows on demand), travel with ONE copy into one device
-// block, and the outputs come back with one copy.  in() = input only; out() = output, optionally uploaded first (in/out
-// arrays: entries the kernel does not write keep the caller's contents).
+// block, and the outputs come back with one copy.  The shape of every host drop-in:
+//   fb_x_args D = *H;                  // every pointer field of D still holds the caller's host address
+//   fb::Stager st;
+//   st.in(D.n, B * 4);                 // input only
+//   st.out(D.match, B * s * 4, true);  // in/out: uploaded first, entries the kernel skips keep the caller's contents
+//   st.out(D.count, B * 4, false);     // output only
+//   FB_TRY(st.commit(nullptr));        // re-points each staged field at its slice of the device block
+//   FB_TRY(fb_x_dev(&D, nullptr));
+//   return st.fetch(nullptr);          // one stream synchronisation, then the outputs land in the caller's arrays
+// A field whose host pointer is null stays null.  A required array is checked (FB_ARG) before commit.
+// Invariants:
+//  - at most one live Stager (or other pinned_scratch user) per host thread: a host wrapper does not call another host
+//    wrapper while its own Stager is live (calling one after the other is fine);
+//  - after staging, no pointer field of D holds a host address: each one is staged or explicitly set to nullptr.
+// If commit enqueued work and fetch did not wait for it (an error in between), the destructor synchronises the stream
+// before the device block goes back to the pool and the pinned block can be refilled by the thread's next call.
 void *pinned_scratch(size_t bytes);  // per-thread page-locked block of at least `bytes` (nullptr on failure, error set)
 struct Stager {
   struct Item { void **field; const void *src; void *dst; size_t bytes, off; };
@@ -114,9 +128,21 @@ struct Stager {
   DevBuf dev;
   uint8_t *pin = nullptr;
   size_t inBytes = 0, total = 0;
+  hipStream_t stream = nullptr;
+  bool pending = false;  // work that reads the blocks may be in flight on `stream`
+  Stager() {}
+  Stager(const Stager &) = delete;
+  Stager &operator=(const Stager &) = delete;
+  ~Stager() {
+    if (pending) { (void)hipStreamSynchronize(stream); (void)hipGetLastError(); }
+  }
   static size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-  void in(void **field, const void *src, size_t bytes) { if (src) ins.push_back({field, src, nullptr, bytes, 0}); }
-  void out(void **field, void *host, size_t bytes, bool copy_in) { if (host) outs.push_back({field, copy_in ? host : nullptr, host, bytes, 0}); }
+  template <typename T> void in(const T *&field, size_t bytes) {
+    if (field) ins.push_back({reinterpret_cast<void **>(const_cast<T **>(&field)), field, nullptr, bytes, 0});
+  }
+  template <typename T> void out(T *&field, size_t bytes, bool copy_in) {
+    if (field) outs.push_back({reinterpret_cast<void **>(&field), copy_in ? field : nullptr, field, bytes, 0});
+  }
   int commit(hipStream_t s) {
     size_t off = 0;
     for (auto &it : ins) { it.off = off; off += up256(it.bytes ? it.bytes : 1); }
@@ -130,6 +156,8 @@ struct Stager {
     for (auto &it : ins) if (it.bytes) memcpy(pin + it.off, it.src, it.bytes);
     for (auto &it : outs) if (it.src && it.bytes) { memcpy(pin + it.off, it.src, it.bytes); anyOutIn = true; }
     const size_t upBytes = anyOutIn ? total : inBytes;
+    stream = s;
+    pending = true;
     if (upBytes) FB_HIP(hipMemcpyAsync(dev.p, pin, upBytes, hipMemcpyHostToDevice, s));
     for (auto &it : ins) *it.field = dev.as<uint8_t>() + it.off;
     for (auto &it : outs) *it.field = dev.as<uint8_t>() + it.off;
@@ -138,10 +166,19 @@ struct Stager {
   int fetch(hipStream_t s) {  // waits for the stream, then hands the outputs to the caller's arrays
     if (total > inBytes) FB_HIP(hipMemcpyAsync(pin + inBytes, dev.as<uint8_t>() + inBytes, total - inBytes, hipMemcpyDeviceToHost, s));
     FB_HIP(hipStreamSynchronize(s));
+    pending = false;
     for (auto &it : outs) if (it.bytes) memcpy(it.dst, pin + it.off, it.bytes);
     return FB_OK;
   }
 };
+
+// a DBoW2::FeatureVector's four arrays (n problems) join the call's staged upload
+inline void stage(Stager &st, fb_feature_vector &d, size_t n) {
+  st.in(d.n_nodes, n * 4);
+  st.in(d.node_ids, n * (size_t)d.node_stride * 4);
+  st.in(d.node_start, n * (size_t)(d.node_stride + 1) * 4);
+  st.in(d.items, n * (size_t)d.item_stride * 4);
+}
 
 // Column sums of up to 32 per-lane values over the 64 lanes as a reduce-scatter butterfly: at the step with mask m a
 // lane sends one half of its values to lane^m, keeps the other half and adds what it receives, so the value count halves

@@ -332,37 +332,29 @@ int fb_bird_guidance(const fb_bird_guidance_args *H) {
   for (int b = 0; b < H->batch; b++) FB_ARG(H->n_in[b] >= 0 && H->n_in[b] <= H->kp_stride);
   fb_bird_guidance_args D = *H;
   const size_t B = H->batch, ks = H->kp_stride, img = (size_t)H->rows * H->pitch, ec = H->edge_cap;
-  fb::DevBuf c, m, ni, ki, di, no, ko, dout, kp, ns, nf, es, ef;
-  FB_TRY(c.upload(H->contour, B * img)); D.contour = c.as<uint8_t>();
-  if (H->mask) { FB_TRY(m.upload(H->mask, B * img)); D.mask = m.as<uint8_t>(); }
-  FB_TRY(ni.upload(H->n_in, B * 4)); D.n_in = ni.as<int32_t>();
-  FB_TRY(ki.upload(H->kps_in, B * ks * sizeof(fb_keypoint))); D.kps_in = ki.as<fb_keypoint>();
-  if (H->desc_in) { FB_TRY(di.upload(H->desc_in, B * ks * 32)); D.desc_in = di.as<uint8_t>(); }
-  FB_TRY(no.alloc(B * 4)); D.n_out = no.as<int32_t>();
+  fb::Stager st;
+  st.in(D.contour, B * img); st.in(D.mask, B * img); st.in(D.n_in, B * 4); st.in(D.kps_in, B * ks * sizeof(fb_keypoint));
+  st.out(D.n_out, B * 4, false);
   // outputs are in/out: entries past n_out keep their previous content
-  FB_TRY(ko.upload(H->kps_out, B * ks * sizeof(fb_keypoint))); D.kps_out = ko.as<fb_keypoint>();
-  if (H->desc_in) { FB_TRY(dout.upload(H->desc_out, B * ks * 32)); D.desc_out = dout.as<uint8_t>(); }
-  if (H->keep) { FB_TRY(kp.upload(H->keep, B * ks)); D.keep = kp.as<uint8_t>(); }
+  st.out(D.kps_out, B * ks * sizeof(fb_keypoint), true);
+  st.out(D.keep, B * ks, true);
+  if (H->desc_in) {
+    st.in(D.desc_in, B * ks * 32);
+    st.out(D.desc_out, B * ks * 32, true);
+  } else {
+    D.desc_out = nullptr;
+  }
   if (ec) {
     FB_ARG(H->n_edge_sign && H->n_edge_free && H->edge_sign && H->edge_free);
-    FB_TRY(ns.alloc(B * 4)); D.n_edge_sign = ns.as<int32_t>();
-    FB_TRY(nf.alloc(B * 4)); D.n_edge_free = nf.as<int32_t>();
-    FB_TRY(es.upload(H->edge_sign, B * ec * 8)); D.edge_sign = es.as<float>();
-    FB_TRY(ef.upload(H->edge_free, B * ec * 8)); D.edge_free = ef.as<float>();
+    st.out(D.n_edge_sign, B * 4, false); st.out(D.n_edge_free, B * 4, false);
+    st.out(D.edge_sign, B * ec * 8, true); st.out(D.edge_free, B * ec * 8, true);
+  } else {
+    D.n_edge_sign = D.n_edge_free = nullptr;
+    D.edge_sign = D.edge_free = nullptr;
   }
+  FB_TRY(st.commit(nullptr));
   FB_TRY(fb_bird_guidance_dev(&D, nullptr));
-  FB_HIP(hipDeviceSynchronize());
-  FB_TRY(no.download(H->n_out, B * 4));
-  FB_TRY(ko.download(H->kps_out, B * ks * sizeof(fb_keypoint)));
-  if (H->desc_in) FB_TRY(dout.download(H->desc_out, B * ks * 32));
-  if (H->keep) FB_TRY(kp.download(H->keep, B * ks));
-  if (ec) {
-    FB_TRY(ns.download(H->n_edge_sign, B * 4));
-    FB_TRY(nf.download(H->n_edge_free, B * 4));
-    FB_TRY(es.download(H->edge_sign, B * ec * 8));
-    FB_TRY(ef.download(H->edge_free, B * ec * 8));
-  }
-  return FB_OK;
+  return st.fetch(nullptr);
 }
 
 int fb_in_frustum_dev(const fb_frustum_args *A, void *stream) {
@@ -387,14 +379,14 @@ int fb_in_frustum(const fb_frustum_args *H) {
   if (B == 0 || ms == 0) return FB_OK;
   FB_ARG(H->in_view && H->proj && H->level && H->view_cos);
   fb::Stager st;  // one staged upload / download
-  st.in((void **)&D.Tcw, H->Tcw, B * 48); st.in((void **)&D.Ow, H->Ow, B * 12); st.in((void **)&D.n_mp, H->n_mp, B * 4);
-  st.in((void **)&D.mp_valid, H->mp_valid, B * ms); st.in((void **)&D.mp_xw, H->mp_xw, B * ms * 12);
-  st.in((void **)&D.mp_normal, H->mp_normal, B * ms * 12); st.in((void **)&D.mp_max_dist, H->mp_max_dist, B * ms * 4);
-  st.in((void **)&D.mp_min_dist, H->mp_min_dist, B * ms * 4);
+  st.in(D.Tcw, B * 48); st.in(D.Ow, B * 12); st.in(D.n_mp, B * 4);
+  st.in(D.mp_valid, B * ms); st.in(D.mp_xw, B * ms * 12);
+  st.in(D.mp_normal, B * ms * 12); st.in(D.mp_max_dist, B * ms * 4);
+  st.in(D.mp_min_dist, B * ms * 4);
   // outputs are in/out (entries that are not in view keep their previous content)
-  st.out((void **)&D.in_view, H->in_view, B * ms, true); st.out((void **)&D.proj, H->proj, B * ms * 8, true);
-  st.out((void **)&D.proj_xr, H->proj_xr, B * ms * 4, true); st.out((void **)&D.level, H->level, B * ms * 4, true);
-  st.out((void **)&D.view_cos, H->view_cos, B * ms * 4, true);
+  st.out(D.in_view, B * ms, true); st.out(D.proj, B * ms * 8, true);
+  st.out(D.proj_xr, B * ms * 4, true); st.out(D.level, B * ms * 4, true);
+  st.out(D.view_cos, B * ms * 4, true);
   FB_TRY(st.commit(nullptr));
   FB_TRY(fb_in_frustum_dev(&D, nullptr));
   return st.fetch(nullptr);
@@ -421,11 +413,11 @@ int fb_bird_filter_matches(const fb_bird_filter_args *H) {
   if (B == 0 || ms == 0) return FB_OK;
   FB_ARG(H->keep && H->pt_world);
   fb::Stager st;
-  st.in((void **)&D.n_matches, H->n_matches, B * 4); st.in((void **)&D.query_idx, H->query_idx, B * ms * 4);
-  st.in((void **)&D.train_idx, H->train_idx, B * ms * 4); st.in((void **)&D.cam_xyz1, H->cam_xyz1, B * s1 * 12);
-  st.in((void **)&D.cam_xyz2, H->cam_xyz2, B * s2 * 12); st.in((void **)&D.Tcw1, H->Tcw1, B * 48); st.in((void **)&D.Tcw2, H->Tcw2, B * 48);
-  st.in((void **)&D.occupied2, H->occupied2, B * s2);
-  st.out((void **)&D.keep, H->keep, B * ms, true); st.out((void **)&D.pt_world, H->pt_world, B * ms * 12, true);
+  st.in(D.n_matches, B * 4); st.in(D.query_idx, B * ms * 4);
+  st.in(D.train_idx, B * ms * 4); st.in(D.cam_xyz1, B * s1 * 12);
+  st.in(D.cam_xyz2, B * s2 * 12); st.in(D.Tcw1, B * 48); st.in(D.Tcw2, B * 48);
+  st.in(D.occupied2, B * s2);
+  st.out(D.keep, B * ms, true); st.out(D.pt_world, B * ms * 12, true);
   FB_TRY(st.commit(nullptr));
   FB_TRY(fb_bird_filter_matches_dev(&D, nullptr));
   return st.fetch(nullptr);
@@ -451,14 +443,14 @@ int fb_undistort_keypoints(const fb_keypoint *kps, int n, const float *K4, const
   FB_ARG(n >= 0 && K4 && D4);
   if (n == 0) return FB_OK;
   FB_ARG(kps && kps_un);
-  fb::DevBuf k, c, o;
   const int32_t n32 = n;
-  FB_TRY(k.upload(kps, (size_t)n * sizeof(fb_keypoint)));
-  FB_TRY(c.upload(&n32, 4));
-  FB_TRY(o.alloc((size_t)n * sizeof(fb_keypoint)));
-  FB_TRY(fb_undistort_keypoints_dev(k.as<fb_keypoint>(), c.as<int32_t>(), 1, n, K4, D4, o.as<fb_keypoint>(), nullptr));
-  FB_HIP(hipDeviceSynchronize());
-  return o.download(kps_un, (size_t)n * sizeof(fb_keypoint));
+  const int32_t *cnt = &n32;
+  fb::Stager st;
+  st.in(kps, (size_t)n * sizeof(fb_keypoint)); st.in(cnt, 4);
+  st.out(kps_un, (size_t)n * sizeof(fb_keypoint), false);
+  FB_TRY(st.commit(nullptr));
+  FB_TRY(fb_undistort_keypoints_dev(kps, cnt, 1, n, K4, D4, kps_un, nullptr));
+  return st.fetch(nullptr);
 }
 
 int fb_image_bounds(int cols, int rows, const float *K4, const float *D4, float *bounds) {

@@ -474,39 +474,30 @@ int fb_create_new_map_points(const fb_new_points_args *H) {
   fb_new_points_args D = *H;
   const size_t B = H->n_nb, s1 = H->kf1_stride, s2 = H->kf2_stride;
   const size_t nmp = B ? (size_t)H->nb_mp_start[B] : 0;
+  fb::DevBuf ws;  // the call's workspace (declared first: it goes back to the pool after the Stager has waited)
   fb::Stager st;
-#define UPF(field, bytes) st.in((void **)&D.field, H->field, (bytes));
-  UPF(n1, 4) UPF(kps1, s1 * sizeof(fb_keypoint)) UPF(desc1, s1 * 32) UPF(Tcw1, 48)
-  UPF(n2, B * 4) UPF(kps2, B * s2 * sizeof(fb_keypoint)) UPF(desc2, B * s2 * 32) UPF(Tcw2, B * 48)
-  UPF(nb_mp_xw, nmp * 12) UPF(nb_before_kf1, B)
-#undef UPF
-  auto fv = [&](const fb_feature_vector &h, fb_feature_vector &d, size_t nb) {
-    d = h;
-    st.in((void **)&d.n_nodes, h.n_nodes, nb * 4);
-    st.in((void **)&d.node_ids, h.node_ids, nb * (size_t)h.node_stride * 4);
-    st.in((void **)&d.node_start, h.node_start, nb * (size_t)(h.node_stride + 1) * 4);
-    st.in((void **)&d.items, h.items, nb * (size_t)h.item_stride * 4);
-  };
-  fv(H->fv1, D.fv1, 1);
-  fv(H->fv2, D.fv2, B);
-  st.out((void **)&D.has_mp1, H->has_mp1, s1, true);
-  st.out((void **)&D.has_mp2, H->has_mp2, B * s2, true);
-  st.out((void **)&D.n_new, H->n_new, 4, false);
-  st.out((void **)&D.xw, H->xw, s1 * 12, true);  // copy-in: rows past n_new keep the caller's contents
-  st.out((void **)&D.normal, H->normal, s1 * 12, true);
-  st.out((void **)&D.max_dist, H->max_dist, s1 * 4, true);
-  st.out((void **)&D.min_dist, H->min_dist, s1 * 4, true);
-  st.out((void **)&D.desc, H->desc, s1 * 32, true);
-  st.out((void **)&D.idx1, H->idx1, s1 * 4, true);
-  st.out((void **)&D.nb, H->nb, s1 * 4, true);
-  st.out((void **)&D.idx2, H->idx2, s1 * 4, true);
-  st.out((void **)&D.kf1_new, H->kf1_new, s1 * 4, false);
-  st.out((void **)&D.kf2_new, H->kf2_new, B * s2 * 4, false);
-  st.out((void **)&D.nb_matches, H->nb_matches, B * 4, false);
-  st.out((void **)&D.nb_new, H->nb_new, B * 4, false);
-  st.out((void **)&D.nb_skipped, H->nb_skipped, B * 4, false);
+  st.in(D.n1, 4); st.in(D.kps1, s1 * sizeof(fb_keypoint)); st.in(D.desc1, s1 * 32); st.in(D.Tcw1, 48);
+  st.in(D.n2, B * 4); st.in(D.kps2, B * s2 * sizeof(fb_keypoint)); st.in(D.desc2, B * s2 * 32); st.in(D.Tcw2, B * 48);
+  st.in(D.nb_mp_xw, nmp * 12); st.in(D.nb_before_kf1, B);  // (nb_mp_start is a host array in both entry points)
+  fb::stage(st, D.fv1, 1);
+  fb::stage(st, D.fv2, B);
+  st.out(D.has_mp1, s1, true);
+  st.out(D.has_mp2, B * s2, true);
+  st.out(D.n_new, 4, false);
+  st.out(D.xw, s1 * 12, true);  // copy-in: rows past n_new keep the caller's contents
+  st.out(D.normal, s1 * 12, true);
+  st.out(D.max_dist, s1 * 4, true);
+  st.out(D.min_dist, s1 * 4, true);
+  st.out(D.desc, s1 * 32, true);
+  st.out(D.idx1, s1 * 4, true);
+  st.out(D.nb, s1 * 4, true);
+  st.out(D.idx2, s1 * 4, true);
+  st.out(D.kf1_new, s1 * 4, false);
+  st.out(D.kf2_new, B * s2 * 4, false);
+  st.out(D.nb_matches, B * 4, false);
+  st.out(D.nb_new, B * 4, false);
+  st.out(D.nb_skipped, B * 4, false);
   FB_TRY(st.commit(nullptr));
-  fb::DevBuf ws;  // this call is synchronous, so a pooled block is safe as its workspace
   D.workspace_bytes = fb_create_new_map_points_workspace((int)B, (int)s1);
   FB_TRY(ws.alloc(D.workspace_bytes));
   D.workspace = ws.p;

@@ -1083,13 +1083,14 @@ int fb_descriptor_distance_dev(const uint8_t *d_a, const uint8_t *d_b, int n, in
 int fb_descriptor_distance(const uint8_t *a, const uint8_t *b, int n, int32_t *out) {
   FB_TRY(fb::check_device());
   FB_ARG(n >= 0);
-  fb::DevBuf da, db, dout;
-  FB_TRY(da.upload(a, (size_t)n * 32));
-  FB_TRY(db.upload(b, (size_t)n * 32));
-  FB_TRY(dout.alloc((size_t)n * 4));
-  FB_TRY(fb_descriptor_distance_dev(da.as<uint8_t>(), db.as<uint8_t>(), n, dout.as<int32_t>(), nullptr));
-  FB_HIP(hipDeviceSynchronize());
-  return dout.download(out, (size_t)n * 4);
+  const size_t bytes = (size_t)n * 32;
+  if (n) FB_ARG(a && b && out);
+  fb::Stager st;
+  st.in(a, bytes); st.in(b, bytes);
+  st.out(out, (size_t)n * 4, false);
+  FB_TRY(st.commit(nullptr));
+  FB_TRY(fb_descriptor_distance_dev(a, b, n, out, nullptr));
+  return st.fetch(nullptr);
 }
 
 int fb_grid_build_batch_dev(const fb_keypoint *d_keypoints, const int32_t *d_n, int batch, int kp_stride,
@@ -1246,8 +1247,6 @@ int fb_match_birdview_dev(const fb_birdview_args *A, void *stream) {
 }
 
 // ---- host-pointer drop-ins: ONE staged upload, the same kernels, one staged download (fb::Stager) --------------
-#define UP(buf, field, bytes) st.in((void **)&D.field, H->field, (bytes));
-#define OUT(field, bytes, copy_in) st.out((void **)&D.field, H->field, (bytes), (copy_in));
 
 int fb_match_projection_frame(const fb_proj_frame_args *H) {
   FB_TRY(fb::check_device());
@@ -1255,14 +1254,14 @@ int fb_match_projection_frame(const fb_proj_frame_args *H) {
   fb_proj_frame_args D = *H;
   const size_t B = H->batch, cs = H->cur_stride, ls = H->last_stride, ncell = (size_t)H->grid.cols * H->grid.rows;
   fb::Stager st;
-  UP(b0, n_cur, B * 4) UP(b1, cur_kps, B * cs * sizeof(fb_keypoint)) UP(b2, cur_desc, B * cs * 32)
-  UP(b3, cur_cell_start, B * (ncell + 1) * 4) UP(b4, cur_cell_items, B * cs * 4) UP(b5, cur_blocked, B * cs)
-  UP(b6, cur_Tcw, B * 48) UP(b7, n_last, B * 4) UP(b8, last_valid, B * ls) UP(b9, last_obs_pos, B * ls)
-  UP(b10, last_xw, B * ls * 12) UP(b11, last_desc, B * ls * 32) UP(b12, last_octave, B * ls * 4)
-  UP(b13, last_angle, B * ls * 4)
-  OUT(match_cur_to_last, B * cs * 4, true)  // copy-in: entries past n keep the caller's contents
-  OUT(nmatches, B * 4, false)
-  if (H->retried) { OUT(retried, B * 4, false) } else D.retried = nullptr;
+  st.in(D.n_cur, B * 4); st.in(D.cur_kps, B * cs * sizeof(fb_keypoint)); st.in(D.cur_desc, B * cs * 32);
+  st.in(D.cur_cell_start, B * (ncell + 1) * 4); st.in(D.cur_cell_items, B * cs * 4); st.in(D.cur_blocked, B * cs);
+  st.in(D.cur_Tcw, B * 48); st.in(D.n_last, B * 4); st.in(D.last_valid, B * ls); st.in(D.last_obs_pos, B * ls);
+  st.in(D.last_xw, B * ls * 12); st.in(D.last_desc, B * ls * 32); st.in(D.last_octave, B * ls * 4);
+  st.in(D.last_angle, B * ls * 4);
+  st.out(D.match_cur_to_last, B * cs * 4, true);  // copy-in: entries past n keep the caller's contents
+  st.out(D.nmatches, B * 4, false);
+  st.out(D.retried, B * 4, false);
   FB_ARG(H->match_cur_to_last && H->nmatches);
   FB_TRY(st.commit(nullptr));
   FB_TRY(fb_match_projection_frame_dev(&D, nullptr));
@@ -1275,13 +1274,13 @@ int fb_match_projection_keyframe(const fb_proj_kf_args *H) {
   fb_proj_kf_args D = *H;
   const size_t B = H->batch, cs = H->cur_stride, ks = H->kf_stride, ncell = (size_t)H->grid.cols * H->grid.rows;
   fb::Stager st;
-  UP(b0, n_cur, B * 4) UP(b1, cur_kps, B * cs * sizeof(fb_keypoint)) UP(b2, cur_desc, B * cs * 32)
-  UP(b3, cur_cell_start, B * (ncell + 1) * 4) UP(b4, cur_cell_items, B * cs * 4) UP(b5, cur_blocked, B * cs)
-  UP(b6, cur_Tcw, B * 48) UP(b7, n_kf, B * 4) UP(b8, kf_valid, B * ks) UP(b9, kf_xw, B * ks * 12)
-  UP(b10, kf_desc, B * ks * 32) UP(b11, kf_max_dist, B * ks * 4) UP(b12, kf_min_dist, B * ks * 4)
-  UP(b13, kf_angle, B * ks * 4)
-  OUT(match_cur_to_kf, B * cs * 4, true)
-  OUT(nmatches, B * 4, false)
+  st.in(D.n_cur, B * 4); st.in(D.cur_kps, B * cs * sizeof(fb_keypoint)); st.in(D.cur_desc, B * cs * 32);
+  st.in(D.cur_cell_start, B * (ncell + 1) * 4); st.in(D.cur_cell_items, B * cs * 4); st.in(D.cur_blocked, B * cs);
+  st.in(D.cur_Tcw, B * 48); st.in(D.n_kf, B * 4); st.in(D.kf_valid, B * ks); st.in(D.kf_xw, B * ks * 12);
+  st.in(D.kf_desc, B * ks * 32); st.in(D.kf_max_dist, B * ks * 4); st.in(D.kf_min_dist, B * ks * 4);
+  st.in(D.kf_angle, B * ks * 4);
+  st.out(D.match_cur_to_kf, B * cs * 4, true);
+  st.out(D.nmatches, B * 4, false);
   FB_ARG(H->match_cur_to_kf && H->nmatches);
   FB_TRY(st.commit(nullptr));
   FB_TRY(fb_match_projection_keyframe_dev(&D, nullptr));
@@ -1293,15 +1292,15 @@ int fb_match_projection_points(const fb_proj_points_args *H) {
   FB_ARG(H && H->batch >= 0);
   fb_proj_points_args D = *H;
   const size_t B = H->batch, cs = H->cur_stride, ms = H->mp_stride, ncell = (size_t)H->grid.cols * H->grid.rows;
+  fb::DevBuf ws;  // the two-phase matcher's workspace (declared first: it goes back to the pool after the Stager has waited)
   fb::Stager st;
-  UP(b0, n_cur, B * 4) UP(b1, cur_kps, B * cs * sizeof(fb_keypoint)) UP(b2, cur_desc, B * cs * 32)
-  UP(b3, cur_cell_start, B * (ncell + 1) * 4) UP(b4, cur_cell_items, B * cs * 4) UP(b5, cur_blocked, B * cs)
-  UP(b6, n_mp, B * 4) UP(b7, mp_track, B * ms) UP(b8, mp_obs_pos, B * ms) UP(b9, mp_proj, B * ms * 8)
-  UP(b10, mp_level, B * ms * 4) UP(b11, mp_view_cos, B * ms * 4) UP(b12, mp_desc, B * ms * 32)
-  OUT(match_cur_to_mp, B * cs * 4, true)
-  OUT(nmatches, B * 4, false)
+  st.in(D.n_cur, B * 4); st.in(D.cur_kps, B * cs * sizeof(fb_keypoint)); st.in(D.cur_desc, B * cs * 32);
+  st.in(D.cur_cell_start, B * (ncell + 1) * 4); st.in(D.cur_cell_items, B * cs * 4); st.in(D.cur_blocked, B * cs);
+  st.in(D.n_mp, B * 4); st.in(D.mp_track, B * ms); st.in(D.mp_obs_pos, B * ms); st.in(D.mp_proj, B * ms * 8);
+  st.in(D.mp_level, B * ms * 4); st.in(D.mp_view_cos, B * ms * 4); st.in(D.mp_desc, B * ms * 32);
+  st.out(D.match_cur_to_mp, B * cs * 4, true);
+  st.out(D.nmatches, B * 4, false);
   FB_ARG(H->match_cur_to_mp && H->nmatches);
-  fb::DevBuf ws;  // the two-phase matcher (this call is synchronous, so a pooled block is safe as its workspace)
   static const bool onePhase = getenv("FB_M2_ONE_KERNEL") != nullptr;  // measurements / tests of the one-kernel version
   D.workspace = nullptr; D.workspace_bytes = 0;
   if (!onePhase && B * ms > 0) {
@@ -1320,12 +1319,12 @@ int fb_match_bird_mappoints(const fb_bird_mp_args *H) {
   fb_bird_mp_args D = *H;
   const size_t B = H->batch, cs = H->cur_stride, rs = H->ref_stride, ncell = (size_t)H->grid.cols * H->grid.rows;
   fb::Stager st;
-  UP(b0, n_cur, B * 4) UP(b1, cur_kps, B * cs * sizeof(fb_keypoint)) UP(b2, cur_desc, B * cs * 32)
-  UP(b3, cur_cam_xyz, B * cs * 12) UP(b4, cur_cell_start, B * (ncell + 1) * 4) UP(b5, cur_cell_items, B * cs * 4)
-  UP(b6, cur_Tcw, B * 48) UP(b7, n_ref, B * 4) UP(b8, ref_valid, B * rs) UP(b9, ref_xw, B * rs * 12)
-  UP(b10, ref_desc, B * rs * 32)
-  OUT(match_cur_to_ref, B * cs * 4, true)  // in/out
-  OUT(ninliers, B * 4, false)
+  st.in(D.n_cur, B * 4); st.in(D.cur_kps, B * cs * sizeof(fb_keypoint)); st.in(D.cur_desc, B * cs * 32);
+  st.in(D.cur_cam_xyz, B * cs * 12); st.in(D.cur_cell_start, B * (ncell + 1) * 4); st.in(D.cur_cell_items, B * cs * 4);
+  st.in(D.cur_Tcw, B * 48); st.in(D.n_ref, B * 4); st.in(D.ref_valid, B * rs); st.in(D.ref_xw, B * rs * 12);
+  st.in(D.ref_desc, B * rs * 32);
+  st.out(D.match_cur_to_ref, B * cs * 4, true);  // in/out
+  st.out(D.ninliers, B * 4, false);
   FB_ARG(H->match_cur_to_ref && H->ninliers);
   FB_TRY(st.commit(nullptr));
   FB_TRY(fb_match_bird_mappoints_dev(&D, nullptr));
@@ -1338,24 +1337,18 @@ int fb_match_birdview(const fb_birdview_args *H) {
   fb_birdview_args D = *H;
   const size_t B = H->batch, cs = H->cur_stride, rs = H->ref_stride, ncell = (size_t)H->grid.cols * H->grid.rows;
   fb::Stager st;
-  UP(b0, n_cur, B * 4) UP(b1, cur_kps, B * cs * sizeof(fb_keypoint)) UP(b2, cur_desc, B * cs * 32)
-  UP(b3, cur_cell_start, B * (ncell + 1) * 4) UP(b4, cur_cell_items, B * cs * 4) UP(b5, n_ref, B * 4)
-  UP(b6, ref_kps, B * rs * sizeof(fb_keypoint)) UP(b7, ref_desc, B * rs * 32)
-  OUT(match_ref_to_cur, B * rs * 4, true)
-  OUT(match_dist, B * rs * 4, true)
-  OUT(nmatches, B * 4, false)
-  OUT(n_dmatches, B * 4, false)
+  st.in(D.n_cur, B * 4); st.in(D.cur_kps, B * cs * sizeof(fb_keypoint)); st.in(D.cur_desc, B * cs * 32);
+  st.in(D.cur_cell_start, B * (ncell + 1) * 4); st.in(D.cur_cell_items, B * cs * 4); st.in(D.n_ref, B * 4);
+  st.in(D.ref_kps, B * rs * sizeof(fb_keypoint)); st.in(D.ref_desc, B * rs * 32);
+  st.out(D.match_ref_to_cur, B * rs * 4, true);
+  st.out(D.match_dist, B * rs * 4, true);
+  st.out(D.nmatches, B * 4, false);
+  st.out(D.n_dmatches, B * 4, false);
   FB_ARG(H->match_ref_to_cur && H->match_dist && H->nmatches && H->n_dmatches);
   FB_TRY(st.commit(nullptr));
   FB_TRY(fb_match_birdview_dev(&D, nullptr));
   return st.fetch(nullptr);
 }
-#undef OUT
-#undef UP
-// (match_kf.inc's wrappers -- loop closing / initialisation, not per-frame -- keep one pooled buffer per argument)
-#define UP(buf, field, bytes)                                        \
-  fb::DevBuf buf;                                                    \
-  if (H->field) { FB_TRY(buf.upload(H->field, (bytes))); D.field = buf.as<std::remove_pointer<decltype(D.field)>::type>(); }
 
 }  // extern "C"
 

@@ -331,16 +331,6 @@ int lds_ok(size_t bytes, const char *what) {
   return FB_OK;
 }
 
-// host-pointer upload helper for a feature vector
-// a DBoW2::FeatureVector's four arrays join the call's staged upload (fb::Stager)
-void stage_fv(fb::Stager &st, const fb_feature_vector &h, fb_feature_vector &d, size_t B) {
-  d = h;
-  st.in((void **)&d.n_nodes, h.n_nodes, B * 4);
-  st.in((void **)&d.node_ids, h.node_ids, B * (size_t)h.node_stride * 4);
-  st.in((void **)&d.node_start, h.node_start, B * (size_t)(h.node_stride + 1) * 4);
-  st.in((void **)&d.items, h.items, B * (size_t)h.item_stride * 4);
-}
-
 }  // namespace
 
 namespace fb {
@@ -412,7 +402,6 @@ int fb_match_triangulation_dev(const fb_triangulation_args *A, void *stream) {
 }
 
 // host-pointer drop-ins: one staged upload, the same kernels, one staged download (fb::Stager, fb_common.h)
-#define UPF(buf, field, bytes) st.in((void **)&D.field, H->field, (bytes));
 
 int fb_match_bow(const fb_bow_args *H) {
   FB_TRY(fb::check_device());
@@ -420,12 +409,12 @@ int fb_match_bow(const fb_bow_args *H) {
   fb_bow_args D = *H;
   const size_t B = H->batch, ks = H->kf_stride, fs = H->f_stride;
   fb::Stager st;
-  UPF(b0, n_kf, B * 4) UPF(b1, kf_kps, B * ks * sizeof(fb_keypoint)) UPF(b2, kf_desc, B * ks * 32) UPF(b3, kf_has_mp, B * ks)
-  UPF(b4, n_f, B * 4) UPF(b5, f_kps, B * fs * sizeof(fb_keypoint)) UPF(b6, f_desc, B * fs * 32)
-  stage_fv(st, H->kf_fv, D.kf_fv, B);
-  stage_fv(st, H->f_fv, D.f_fv, B);
-  st.out((void **)&D.match_f_to_kf, H->match_f_to_kf, B * fs * 4, true);  // copy-in: entries past n keep the caller's contents
-  st.out((void **)&D.nmatches, H->nmatches, B * 4, false);
+  st.in(D.n_kf, B * 4); st.in(D.kf_kps, B * ks * sizeof(fb_keypoint)); st.in(D.kf_desc, B * ks * 32); st.in(D.kf_has_mp, B * ks);
+  st.in(D.n_f, B * 4); st.in(D.f_kps, B * fs * sizeof(fb_keypoint)); st.in(D.f_desc, B * fs * 32);
+  fb::stage(st, D.kf_fv, B);
+  fb::stage(st, D.f_fv, B);
+  st.out(D.match_f_to_kf, B * fs * 4, true);  // copy-in: entries past n keep the caller's contents
+  st.out(D.nmatches, B * 4, false);
   FB_TRY(st.commit(nullptr));
   FB_TRY(fb_match_bow_dev(&D, nullptr));
   return st.fetch(nullptr);
@@ -437,12 +426,12 @@ int fb_match_bow_kf(const fb_bow_kf_args *H) {
   fb_bow_kf_args D = *H;
   const size_t B = H->batch, s1 = H->kf1_stride, s2 = H->kf2_stride;
   fb::Stager st;
-  UPF(b0, n1, B * 4) UPF(b1, kps1, B * s1 * sizeof(fb_keypoint)) UPF(b2, desc1, B * s1 * 32) UPF(b3, has_mp1, B * s1)
-  UPF(b4, n2, B * 4) UPF(b5, kps2, B * s2 * sizeof(fb_keypoint)) UPF(b6, desc2, B * s2 * 32) UPF(b7, has_mp2, B * s2)
-  stage_fv(st, H->fv1, D.fv1, B);
-  stage_fv(st, H->fv2, D.fv2, B);
-  st.out((void **)&D.matches12, H->matches12, B * s1 * 4, true);
-  st.out((void **)&D.nmatches, H->nmatches, B * 4, false);
+  st.in(D.n1, B * 4); st.in(D.kps1, B * s1 * sizeof(fb_keypoint)); st.in(D.desc1, B * s1 * 32); st.in(D.has_mp1, B * s1);
+  st.in(D.n2, B * 4); st.in(D.kps2, B * s2 * sizeof(fb_keypoint)); st.in(D.desc2, B * s2 * 32); st.in(D.has_mp2, B * s2);
+  fb::stage(st, D.fv1, B);
+  fb::stage(st, D.fv2, B);
+  st.out(D.matches12, B * s1 * 4, true);
+  st.out(D.nmatches, B * 4, false);
   FB_TRY(st.commit(nullptr));
   FB_TRY(fb_match_bow_kf_dev(&D, nullptr));
   return st.fetch(nullptr);
@@ -454,17 +443,16 @@ int fb_match_triangulation(const fb_triangulation_args *H) {
   fb_triangulation_args D = *H;
   const size_t B = H->batch, s1 = H->kf1_stride, s2 = H->kf2_stride;
   fb::Stager st;
-  UPF(b0, n1, B * 4) UPF(b1, kps1, B * s1 * sizeof(fb_keypoint)) UPF(b2, desc1, B * s1 * 32) UPF(b3, has_mp1, B * s1)
-  UPF(b4, n2, B * 4) UPF(b5, kps2, B * s2 * sizeof(fb_keypoint)) UPF(b6, desc2, B * s2 * 32) UPF(b7, has_mp2, B * s2)
-  UPF(b8, F12, B * 36) UPF(b9, Cw1, B * 12) UPF(b10, R2w, B * 36) UPF(b11, t2w, B * 12)
-  stage_fv(st, H->fv1, D.fv1, B);
-  stage_fv(st, H->fv2, D.fv2, B);
-  st.out((void **)&D.matches12, H->matches12, B * s1 * 4, true);
-  st.out((void **)&D.nmatches, H->nmatches, B * 4, false);
+  st.in(D.n1, B * 4); st.in(D.kps1, B * s1 * sizeof(fb_keypoint)); st.in(D.desc1, B * s1 * 32); st.in(D.has_mp1, B * s1);
+  st.in(D.n2, B * 4); st.in(D.kps2, B * s2 * sizeof(fb_keypoint)); st.in(D.desc2, B * s2 * 32); st.in(D.has_mp2, B * s2);
+  st.in(D.F12, B * 36); st.in(D.Cw1, B * 12); st.in(D.R2w, B * 36); st.in(D.t2w, B * 12);
+  fb::stage(st, D.fv1, B);
+  fb::stage(st, D.fv2, B);
+  st.out(D.matches12, B * s1 * 4, true);
+  st.out(D.nmatches, B * 4, false);
   FB_TRY(st.commit(nullptr));
   FB_TRY(fb_match_triangulation_dev(&D, nullptr));
   return st.fetch(nullptr);
 }
-#undef UPF
 
 }  // extern "C"

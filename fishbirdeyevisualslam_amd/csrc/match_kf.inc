@@ -436,34 +436,21 @@ int kf_target_ok(const fb_kf_target &K) {
   return K.kf_stride > 0 && K.kf_stride < 65536 && K.n_levels > 0 && K.n_levels <= FB_MAX_LEVELS && K.grid.cols > 0 && K.grid.rows > 0;
 }
 
-struct KfUp {  // host-pointer drop-ins: device copies of a key-frame target / a map-point list
-  fb::DevBuf n, kps, desc, cs, ci;
-  int up(const fb_kf_target &h, fb_kf_target &d, size_t B) {
-    const size_t ks = h.kf_stride, ncell = (size_t)h.grid.cols * h.grid.rows;
-    d = h;
-    FB_TRY(n.upload(h.n_kf, B * 4)); d.n_kf = n.as<int32_t>();
-    FB_TRY(kps.upload(h.kf_kps, B * ks * sizeof(fb_keypoint))); d.kf_kps = kps.as<fb_keypoint>();
-    FB_TRY(desc.upload(h.kf_desc, B * ks * 32)); d.kf_desc = desc.as<uint8_t>();
-    FB_TRY(cs.upload(h.kf_cell_start, B * (ncell + 1) * 4)); d.kf_cell_start = cs.as<int32_t>();
-    FB_TRY(ci.upload(h.kf_cell_items, B * ks * 4)); d.kf_cell_items = ci.as<int32_t>();
-    return FB_OK;
-  }
-};
-struct MpUp {
-  fb::DevBuf n, valid, xw, nrm, mx, mn, desc;
-  int up(const fb_mp_list &h, fb_mp_list &d, size_t B) {
-    const size_t ms = h.mp_stride;
-    d = h;
-    FB_TRY(n.upload(h.n_mp, B * 4)); d.n_mp = n.as<int32_t>();
-    FB_TRY(valid.upload(h.mp_valid, B * ms)); d.mp_valid = valid.as<uint8_t>();
-    FB_TRY(xw.upload(h.mp_xw, B * ms * 12)); d.mp_xw = xw.as<float>();
-    if (h.mp_normal) { FB_TRY(nrm.upload(h.mp_normal, B * ms * 12)); d.mp_normal = nrm.as<float>(); }
-    FB_TRY(mx.upload(h.mp_max_dist, B * ms * 4)); d.mp_max_dist = mx.as<float>();
-    FB_TRY(mn.upload(h.mp_min_dist, B * ms * 4)); d.mp_min_dist = mn.as<float>();
-    FB_TRY(desc.upload(h.mp_desc, B * ms * 32)); d.mp_desc = desc.as<uint8_t>();
-    return FB_OK;
-  }
-};
+// host-pointer drop-ins: a key-frame target / a map-point list (B problems) join the call's staged upload
+int stage(fb::Stager &st, fb_kf_target &d, size_t B) {
+  const size_t ks = d.kf_stride, ncell = (size_t)d.grid.cols * d.grid.rows;
+  FB_ARG(d.n_kf && d.kf_kps && d.kf_desc && d.kf_cell_start && d.kf_cell_items);
+  st.in(d.n_kf, B * 4); st.in(d.kf_kps, B * ks * sizeof(fb_keypoint)); st.in(d.kf_desc, B * ks * 32);
+  st.in(d.kf_cell_start, B * (ncell + 1) * 4); st.in(d.kf_cell_items, B * ks * 4);
+  return FB_OK;
+}
+int stage(fb::Stager &st, fb_mp_list &d, size_t B) {
+  const size_t ms = d.mp_stride;
+  FB_ARG(d.n_mp && (ms == 0 || (d.mp_valid && d.mp_xw && d.mp_max_dist && d.mp_min_dist && d.mp_desc)));
+  st.in(d.n_mp, B * 4); st.in(d.mp_valid, B * ms); st.in(d.mp_xw, B * ms * 12); st.in(d.mp_normal, B * ms * 12);
+  st.in(d.mp_max_dist, B * ms * 4); st.in(d.mp_min_dist, B * ms * 4); st.in(d.mp_desc, B * ms * 32);
+  return FB_OK;
+}
 
 template <int MODE>
 int fuse_dev(const fb_fuse_args *A, void *stream, const char *what) {
@@ -489,16 +476,15 @@ int fuse_host(const fb_fuse_args *H) {
   fb_fuse_args D = *H;
   const size_t B = H->batch, ms = H->mp.mp_stride;
   if (B == 0 || ms == 0) return FB_OK;
-  KfUp ku; MpUp mu;
-  FB_TRY(ku.up(H->kf, D.kf, B));
-  FB_TRY(mu.up(H->mp, D.mp, B));
-  fb::DevBuf p, ow, o0;
-  FB_TRY(p.upload(H->pose, B * 48)); D.pose = p.as<float>();
-  if (H->Ow) { FB_TRY(ow.upload(H->Ow, B * 12)); D.Ow = ow.as<float>(); }
-  FB_TRY(o0.upload(H->best_idx, B * ms * 4)); D.best_idx = o0.as<int32_t>();  // copy-in: entries past n keep the caller's contents
+  FB_ARG(H->pose && H->best_idx);
+  fb::Stager st;
+  FB_TRY(stage(st, D.kf, B));
+  FB_TRY(stage(st, D.mp, B));
+  st.in(D.pose, B * 48); st.in(D.Ow, B * 12);
+  st.out(D.best_idx, B * ms * 4, true);  // copy-in: entries past n keep the caller's contents
+  FB_TRY(st.commit(nullptr));
   FB_TRY((fuse_dev<MODE>(&D, nullptr, "fb_fuse_search")));
-  FB_HIP(hipDeviceSynchronize());
-  return o0.download(H->best_idx, B * ms * 4);
+  return st.fetch(nullptr);
 }
 
 }  // namespace
@@ -531,18 +517,16 @@ int fb_match_projection_sim3(const fb_proj_sim3_args *H) {
   fb_proj_sim3_args D = *H;
   const size_t B = H->batch, ks = H->kf.kf_stride;
   if (B == 0) return FB_OK;
-  KfUp ku; MpUp mu;
-  FB_TRY(ku.up(H->kf, D.kf, B));
-  FB_TRY(mu.up(H->mp, D.mp, B));
-  fb::DevBuf s, km, o0, o1;
-  FB_TRY(s.upload(H->Scw, B * 48)); D.Scw = s.as<float>();
-  if (H->kf_matched) { FB_TRY(km.upload(H->kf_matched, B * ks)); D.kf_matched = km.as<uint8_t>(); }
-  FB_TRY(o0.upload(H->match_kf_to_mp, B * ks * 4)); D.match_kf_to_mp = o0.as<int32_t>();
-  FB_TRY(o1.alloc(B * 4)); D.nmatches = o1.as<int32_t>();
+  FB_ARG(H->Scw && H->match_kf_to_mp && H->nmatches);
+  fb::Stager st;
+  FB_TRY(stage(st, D.kf, B));
+  FB_TRY(stage(st, D.mp, B));
+  st.in(D.Scw, B * 48); st.in(D.kf_matched, B * ks);
+  st.out(D.match_kf_to_mp, B * ks * 4, true);
+  st.out(D.nmatches, B * 4, false);
+  FB_TRY(st.commit(nullptr));
   FB_TRY(fb_match_projection_sim3_dev(&D, nullptr));
-  FB_HIP(hipDeviceSynchronize());
-  FB_TRY(o0.download(H->match_kf_to_mp, B * ks * 4));
-  return o1.download(H->nmatches, B * 4);
+  return st.fetch(nullptr);
 }
 
 int fb_match_sim3_dev(const fb_sim3_args *A, void *stream) {
@@ -568,23 +552,18 @@ int fb_match_sim3(const fb_sim3_args *H) {
   fb_sim3_args D = *H;
   const size_t B = H->batch, s1 = H->mp1.mp_stride;
   if (B == 0) return FB_OK;
-  KfUp k1, k2; MpUp m1, m2;
-  FB_TRY(k1.up(H->kf1, D.kf1, B));
-  FB_TRY(k2.up(H->kf2, D.kf2, B));
-  FB_TRY(m1.up(H->mp1, D.mp1, B));
-  FB_TRY(m2.up(H->mp2, D.mp2, B));
-  fb::DevBuf t1, t2, s, r, t, o0, o1;
-  FB_TRY(t1.upload(H->T1w, B * 48)); D.T1w = t1.as<float>();
-  FB_TRY(t2.upload(H->T2w, B * 48)); D.T2w = t2.as<float>();
-  FB_TRY(s.upload(H->s12, B * 4)); D.s12 = s.as<float>();
-  FB_TRY(r.upload(H->R12, B * 36)); D.R12 = r.as<float>();
-  FB_TRY(t.upload(H->t12, B * 12)); D.t12 = t.as<float>();
-  FB_TRY(o0.upload(H->matches12, B * s1 * 4)); D.matches12 = o0.as<int32_t>();
-  FB_TRY(o1.alloc(B * 4)); D.nfound = o1.as<int32_t>();
+  FB_ARG(H->T1w && H->T2w && H->s12 && H->R12 && H->t12 && H->matches12 && H->nfound);
+  fb::Stager st;
+  FB_TRY(stage(st, D.kf1, B));
+  FB_TRY(stage(st, D.kf2, B));
+  FB_TRY(stage(st, D.mp1, B));
+  FB_TRY(stage(st, D.mp2, B));
+  st.in(D.T1w, B * 48); st.in(D.T2w, B * 48); st.in(D.s12, B * 4); st.in(D.R12, B * 36); st.in(D.t12, B * 12);
+  st.out(D.matches12, B * s1 * 4, true);
+  st.out(D.nfound, B * 4, false);
+  FB_TRY(st.commit(nullptr));
   FB_TRY(fb_match_sim3_dev(&D, nullptr));
-  FB_HIP(hipDeviceSynchronize());
-  FB_TRY(o0.download(H->matches12, B * s1 * 4));
-  return o1.download(H->nfound, B * 4);
+  return st.fetch(nullptr);
 }
 
 int fb_match_initialization_dev(const fb_init_match_args *A, void *stream) {
@@ -611,18 +590,18 @@ int fb_match_initialization(const fb_init_match_args *H) {
   fb_init_match_args D = *H;
   const size_t B = H->batch, s1 = H->f1_stride, s2 = H->f2_stride, ncell = (size_t)H->grid.cols * H->grid.rows;
   if (B == 0) return FB_OK;
-  UP(b0, n1, B * 4) UP(b1, kps1, B * s1 * sizeof(fb_keypoint)) UP(b2, desc1, B * s1 * 32)
-  UP(b3, n2, B * 4) UP(b4, kps2, B * s2 * sizeof(fb_keypoint)) UP(b5, desc2, B * s2 * 32)
-  UP(b6, f2_cell_start, B * (ncell + 1) * 4) UP(b7, f2_cell_items, B * s2 * 4)
-  fb::DevBuf pm, o0, o1;
-  FB_TRY(pm.upload(H->prev_matched, B * s1 * 8)); D.prev_matched = pm.as<float>();
-  FB_TRY(o0.upload(H->matches12, B * s1 * 4)); D.matches12 = o0.as<int32_t>();
-  FB_TRY(o1.alloc(B * 4)); D.nmatches = o1.as<int32_t>();
+  FB_ARG(H->n1 && H->kps1 && H->desc1 && H->n2 && H->kps2 && H->desc2 && H->f2_cell_start && H->f2_cell_items);
+  FB_ARG(H->prev_matched && H->matches12 && H->nmatches);
+  fb::Stager st;
+  st.in(D.n1, B * 4); st.in(D.kps1, B * s1 * sizeof(fb_keypoint)); st.in(D.desc1, B * s1 * 32);
+  st.in(D.n2, B * 4); st.in(D.kps2, B * s2 * sizeof(fb_keypoint)); st.in(D.desc2, B * s2 * 32);
+  st.in(D.f2_cell_start, B * (ncell + 1) * 4); st.in(D.f2_cell_items, B * s2 * 4);
+  st.out(D.prev_matched, B * s1 * 8, true);
+  st.out(D.matches12, B * s1 * 4, true);
+  st.out(D.nmatches, B * 4, false);
+  FB_TRY(st.commit(nullptr));
   FB_TRY(fb_match_initialization_dev(&D, nullptr));
-  FB_HIP(hipDeviceSynchronize());
-  FB_TRY(pm.download(H->prev_matched, B * s1 * 8));
-  FB_TRY(o0.download(H->matches12, B * s1 * 4));
-  return o1.download(H->nmatches, B * 4);
+  return st.fetch(nullptr);
 }
 
 int fb_distinctive_descriptors_dev(const int32_t *d_obs_start, const uint8_t *d_obs_desc, int n_mp, int32_t *d_best_obs,
@@ -651,13 +630,12 @@ int fb_distinctive_descriptors(const int32_t *obs_start, const uint8_t *obs_desc
       return FB_ERR_CAPACITY;
     }
   if (total == 0) { for (int p = 0; p < n_mp; p++) best_obs[p] = -1; return FB_OK; }
-  fb::DevBuf s, d, o;
-  FB_TRY(s.upload(obs_start, (size_t)(n_mp + 1) * 4));
-  FB_TRY(d.upload(obs_desc, total * 32));
-  FB_TRY(o.alloc((size_t)n_mp * 4));
-  FB_TRY(fb_distinctive_descriptors_dev(s.as<int32_t>(), d.as<uint8_t>(), n_mp, o.as<int32_t>(), nullptr));
-  FB_HIP(hipDeviceSynchronize());
-  return o.download(best_obs, (size_t)n_mp * 4);
+  fb::Stager st;
+  st.in(obs_start, (size_t)(n_mp + 1) * 4); st.in(obs_desc, total * 32);
+  st.out(best_obs, (size_t)n_mp * 4, false);
+  FB_TRY(st.commit(nullptr));
+  FB_TRY(fb_distinctive_descriptors_dev(obs_start, obs_desc, n_mp, best_obs, nullptr));
+  return st.fetch(nullptr);
 }
 
 }  // extern "C"

@@ -1810,12 +1810,18 @@ int fb_orb_extract(fb_orb *o, const uint8_t *image, int width, int height, int s
   // asynchronous copy each way and ONE synchronisation (five synchronous copies before)
   const size_t imgBytes = (size_t)stride * height, kpBytes = (size_t)cap * sizeof(fb_keypoint), dBytes = (size_t)cap * 32;
   const size_t oN = 0, oK = 256, oD = oK + ((kpBytes + 255) & ~(size_t)255), oC = oD + ((dBytes + 255) & ~(size_t)255), outBytes = oC + 256;
-  uint8_t *pin = static_cast<uint8_t *>(fb::pinned_scratch(imgBytes + outBytes));
+  const size_t imgArea = fb::Stager::up256(imgBytes);  // the output area starts 256-byte aligned (its level counts are ints)
+  uint8_t *pin = static_cast<uint8_t *>(fb::pinned_scratch(imgArea + outBytes));
   if (!pin) return FB_ERR_HIP;
   fb::DevBuf dout;
   FB_TRY(dout.alloc(outBytes));
   if (o->ownedImg.bytes < imgBytes || !o->ownedImg.p) FB_TRY(o->ownedImg.alloc(imgBytes));
   memcpy(pin, image, imgBytes);
+  // as ~Stager: on an error return after this point the copies and kernels may still use `pin` and `dout`
+  struct SyncOnError {
+    bool armed = true;
+    ~SyncOnError() { if (armed) { (void)hipStreamSynchronize(nullptr); (void)hipGetLastError(); } }
+  } guard;
   FB_HIP(hipMemcpyAsync(o->ownedImg.p, pin, imgBytes, hipMemcpyHostToDevice, nullptr));
   uint8_t *dbase = dout.as<uint8_t>();
   const int keepStride = o->kpStride;
@@ -1824,10 +1830,11 @@ int fb_orb_extract(fb_orb *o, const uint8_t *image, int width, int height, int s
                                           dbase + oD, reinterpret_cast<int32_t *>(dbase + oN), nullptr);
   if (keepStride) (void)fb_orb_set_output_stride(o, keepStride);
   FB_TRY(rc);
-  uint8_t *pout = pin + imgBytes;
+  uint8_t *pout = pin + imgArea;
   FB_HIP(hipMemcpyAsync(pout, dbase, oC, hipMemcpyDeviceToHost, nullptr));
   FB_HIP(hipMemcpyAsync(pout + oC, o->counts.as<int>() + (size_t)o->batchCap * o->p.nlevels, (size_t)o->p.nlevels * 4, hipMemcpyDeviceToHost, nullptr));
   FB_HIP(hipStreamSynchronize(nullptr));
+  guard.armed = false;
   memcpy(n_out, pout + oN, 4);
   {  // n_out is clamped to the capacity on the device; the per-level counts tell whether anything was cut off (the
      // quadtree can end a level with up to 4 x its number of root nodes: very wide strips with a tiny feature budget)

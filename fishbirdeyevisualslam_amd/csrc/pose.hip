@@ -1346,15 +1346,13 @@ int fb_pose_opt(const fb_pose_opt_args *H) {
   const size_t B = H->batch, fs = H->front_stride, bs = H->bird_stride;
   // one staged upload / download (fb::Stager): 13 synchronous copies were a quarter of this call at one frame per call
   fb::Stager st;
-#define UPB(field, bytes) st.in((void **)&D.field, H->field, (bytes));
-  UPB(n_front, B * 4) UPB(front_xw, B * fs * 12) UPB(front_obs, B * fs * 8) UPB(front_inv_sigma2, B * fs * 4)
-  UPB(front_valid, B * fs) UPB(n_bird, B * 4) UPB(bird_xw, B * bs * 12) UPB(bird_xc, B * bs * 12)
-  UPB(bird_inv_sigma2, B * bs * 4) UPB(bird_valid, B * bs)
-#undef UPB
-  st.out((void **)&D.bird_outlier, H->bird_outlier, B * bs, true);   // in/out: mvBirdOutlier
-  st.out((void **)&D.Tcw, H->Tcw, B * 48, true);
-  st.out((void **)&D.front_outlier, H->front_outlier, B * fs, true);
-  st.out((void **)&D.ninliers, H->ninliers, B * 4, false);
+  st.in(D.n_front, B * 4); st.in(D.front_xw, B * fs * 12); st.in(D.front_obs, B * fs * 8); st.in(D.front_inv_sigma2, B * fs * 4);
+  st.in(D.front_valid, B * fs); st.in(D.n_bird, B * 4); st.in(D.bird_xw, B * bs * 12); st.in(D.bird_xc, B * bs * 12);
+  st.in(D.bird_inv_sigma2, B * bs * 4); st.in(D.bird_valid, B * bs);
+  st.out(D.bird_outlier, B * bs, true);   // in/out: mvBirdOutlier
+  st.out(D.Tcw, B * 48, true);
+  st.out(D.front_outlier, B * fs, true);
+  st.out(D.ninliers, B * 4, false);
   // the family a mode ignores may be absent altogether: the kernel never dereferences it (n = 0 for that family)
   FB_TRY(st.commit(nullptr));
   FB_TRY(fb_pose_opt_batch_dev(&D, nullptr));

@@ -11,6 +11,8 @@
  *   passed as void*; they enqueue work and return without synchronising.
  *   Entry points without the suffix take HOST pointers, copy, run the same
  *   kernels and synchronise before returning (drop-in for the reference call).
+ *   A host drop-in synchronises the stream it ran on, not the whole device; a
+ *   null required array is FB_ERR_ARG, reported before anything is enqueued.
  *
  * Threads
  *   Calls that take no handle (matchers, pose optimisation, bundle adjustment)
