@@ -19,6 +19,7 @@
 // OpenCV semantics (not vendored in the reference -> "parity unpinned") are
 // those of oracle/orb_oracle.cpp; this file must agree with it bit for bit.
 #include "fb_common.h"
+#include "fb_fast_score.h"
 
 namespace {
 
@@ -346,33 +347,42 @@ __global__ __launch_bounds__(256) void k_resize_merge(const uint8_t *__restrict_
 // read with an immediate offset (taps at negative offsets from the pixel cost a vector add each).
 template <int TP>
 __device__ __forceinline__ int fast_score16(const uint8_t *__restrict__ corner) {
-  constexpr int tp = TP;
-  const uint8_t *c = corner + 3 * tp + 3;
+  const uint8_t *c = corner + 3 * TP + 3;
   const int v = c[0];
   int d[16];
-  d[0] = v - c[3 * tp];      d[1] = v - c[3 * tp + 1];   d[2] = v - c[2 * tp + 2];   d[3] = v - c[tp + 3];
-  d[4] = v - c[3];           d[5] = v - c[-tp + 3];      d[6] = v - c[-2 * tp + 2];  d[7] = v - c[-3 * tp + 1];
-  d[8] = v - c[-3 * tp];     d[9] = v - c[-3 * tp - 1];  d[10] = v - c[-2 * tp - 2]; d[11] = v - c[-tp - 3];
-  d[12] = v - c[-3];         d[13] = v - c[tp - 3];      d[14] = v - c[2 * tp - 2];  d[15] = v - c[3 * tp - 1];
-  // sliding min / max over the 16 arcs of 9 in three-operand form (v_min3_i32 / v_max3_i32):
-  // arc of 3 -> arc of 9 = three arcs of 3 -> reduction, 40 instructions per polarity
-  int mn3[16], mx3[16];
 #pragma unroll
-  for (int i = 0; i < 16; i++) {
-    mn3[i] = min(min(d[i], d[(i + 1) & 15]), d[(i + 2) & 15]);
-    mx3[i] = max(max(d[i], d[(i + 1) & 15]), d[(i + 2) & 15]);
+  for (int i = 0; i < 16; i++) d[i] = fbscore::IntOps::sub(v, c[fbscore::ring_offset(i, TP)]);
+  return fbscore::score_network<fbscore::IntOps>(d);  // already clamped at 0
+}
+
+// min3 / max3 of the packed form of fb_fast_score.h: the three-operand packed binary16 instructions of gfx950 (no packed
+// INTEGER min3 / max3 exists: two pixels in v_pk_min_i16 form cost what two scalar trips cost).
+struct PkF16MinMax {
+  static __device__ __forceinline__ uint32_t min3(uint32_t a, uint32_t b, uint32_t c) {
+    uint32_t r;
+    asm("v_pk_minimum3_f16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
   }
-  int A = -256, Bm = 256;
+  static __device__ __forceinline__ uint32_t max3(uint32_t a, uint32_t b, uint32_t c) {
+    uint32_t r;
+    asm("v_pk_maximum3_f16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+  }
+};
+
+// Scores of TWO pixels (corners c0 and c1, as for fast_score16): byte 0 of the result is the clamped score of the
+// first, byte 2 that of the second, bytes 1 and 3 are zero.  Per ring position: two LDS byte reads, one v_lshl_or_b32
+// to pair them and one v_pk_sub_u16 (the d16 forms of the LDS byte loads, which would pair for free, clear the other
+// half on this ECC part).
+template <int TP>
+__device__ __forceinline__ uint32_t fast_score16x2(const uint8_t *__restrict__ c0, const uint8_t *__restrict__ c1) {
+  typedef fbscore::PackedOps<PkF16MinMax> Ops;
+  constexpr int ctr = 3 * TP + 3;
+  const uint32_t v = fbscore::pk_centre(c0[ctr], c1[ctr]);
+  uint32_t d[16];
 #pragma unroll
-  for (int i = 0; i < 16; i += 2) {
-    const int a0 = min(min(mn3[i], mn3[(i + 3) & 15]), mn3[(i + 6) & 15]);
-    const int a1 = min(min(mn3[i + 1], mn3[(i + 4) & 15]), mn3[(i + 7) & 15]);
-    const int b0 = max(max(mx3[i], mx3[(i + 3) & 15]), mx3[(i + 6) & 15]);
-    const int b1 = max(max(mx3[i + 1], mx3[(i + 4) & 15]), mx3[(i + 7) & 15]);
-    A = max(max(A, a0), a1);
-    Bm = min(min(Bm, b0), b1);
-  }
-  return max(A, -Bm) - 1;
+  for (int i = 0; i < 16; i++) d[i] = Ops::sub(v, fbscore::pk_pair(c0[ctr + fbscore::ring_offset(i, TP)], c1[ctr + fbscore::ring_offset(i, TP)]));
+  return fbscore::score_network<Ops>(d);
 }
 
 __device__ __forceinline__ int wave_incl_scan(int v) {  // inclusive scan over the 64 lanes
@@ -438,6 +448,14 @@ constexpr int FAST_MAX_TILE = 72;  // cell window <= wCell+6 <= 65 px, +3 alignm
 //     Candidate order is irrelevant downstream (the quadtree breaks response ties with an order key derived from x,y).
 // TP = tile pitch in bytes, a compile-time constant so that every LDS access of the sweep / score / NMS is
 // base + immediate offset (44 covers cells up to 35 px wide, i.e. every level of the usual image sizes).
+#ifdef FB_FAST_LISTHIST
+#define FB_ORB_TIMER_WORDS (16 + 128)  // + the list-length histograms of the probe build (fb_orb_debug_list_hist)
+#else
+#define FB_ORB_TIMER_WORDS 16
+#endif
+#ifndef FB_FAST_PACK_MIN
+#define FB_FAST_PACK_MIN 64  // list entries left from which a score trip runs in the packed two-per-lane form (0: always; 1 << 30: never)
+#endif
 #ifndef FB_FAST_WPE44
 #define FB_FAST_WPE44 6  // register budget of the 44-byte instantiation, in waves per SIMD
 #endif
@@ -654,6 +672,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TP == 44 ? F
     }
     const int nlA = (int)((baseA - listBase) >> 1);
     int nlB = 0;
+#ifdef FB_FAST_LISTHIST  // probe build: list lengths in 64 bins of 8 (bin k: 8k-7 .. 8k entries, bin 0: empty list)
+    if (lane == 0) atomicAdd(&K.timers[16 + min((nlA + 7) >> 3, 63)], 1ull);
+#endif
     __syncthreads();
     FAST_TICK(2)  // sweep
       if (K.dbg == 4) { if (nlA + (int)WB[0] == 123456) cand[0] = 1; return; }
@@ -669,14 +690,35 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TP == 44 ? F
         expand(WB[0], baseB, false, lo0 - (16 - min(16, nIt)) * sstep);
         if (nIt > 16) expand(WB[1], baseB, false, lo0 + 16 * sstep - (16 - min(16, nIt - 16)) * sstep);
         nlB = (int)((listBase + 2u * (uint32_t)(cap - 1) - baseB) >> 1);
+#ifdef FB_FAST_LISTHIST
+        if (lane == 0) atomicAdd(&K.timers[16 + 64 + min((nlB + 7) >> 3, 63)], 1ull);  // cells redone at minThFAST
+#endif
         __syncthreads();
       }
       const int nl = pass == 0 ? nlA : nlA + nlB;  // the NMS of pass 1 visits A then B
-      for (int i = (pass == 0 ? 0 : nlA) + lane; i < nl; i += 64) {
-        const int o = i < nlA ? s_list[i] : s_list[cap - nlB + (i - nlA)];
-        int oc = o - 3 * TP - 3;
-        asm volatile("" : "+v"(oc));  // keeps the compiler from re-basing the taps on the pixel
-        sc[o] = (uint8_t)max(fast_score16<TP>(&tile[oc]), 0);
+      auto listed = [&](int i) { return (int)(i < nlA ? s_list[i] : s_list[cap - nlB + (i - nlA)]); };
+      for (int base = pass == 0 ? 0 : nlA; base < nl;) {
+        const int i = base + lane;
+        if (nl - base > FB_FAST_PACK_MIN) {  // wave-uniform: lane i scores entries i and i + 64 of a 128-entry trip
+          if (i < nl) {
+            const int o0 = listed(i);
+            const int o1 = i + 64 < nl ? listed(i + 64) : o0;  // absent second half: the first pixel again (reads stay inside the carve)
+            int oc0 = o0 - 3 * TP - 3, oc1 = o1 - 3 * TP - 3;
+            asm volatile("" : "+v"(oc0), "+v"(oc1));  // keeps the compiler from re-basing the taps on the pixels
+            const uint32_t r = fast_score16x2<TP>(&tile[oc0], &tile[oc1]);
+            sc[o0] = (uint8_t)r;
+            sc[o1] = (uint8_t)(r >> 16);  // o1 == o0: the same byte again
+          }
+          base += 128;
+        } else {
+          if (i < nl) {
+            const int o = listed(i);
+            int oc = o - 3 * TP - 3;
+            asm volatile("" : "+v"(oc));  // keeps the compiler from re-basing the taps on the pixel
+            sc[o] = (uint8_t)fast_score16<TP>(&tile[oc]);
+          }
+          base += 64;
+        }
       }
       const int Tk = max(T, 1);  // a corner has score >= T and score != 0
       __syncthreads();
@@ -1653,8 +1695,8 @@ int prepare(fb_orb *o, int w, int h, int batch) {
   FB_TRY(o->cellCount.alloc(B * (size_t)K.totalCells * 4 + 16));
   FB_TRY(o->nodeOf.alloc(B * K.candStride * 2 + 16));
   FB_TRY(o->counts.alloc(B * p.nlevels * 4 * 2));  // candCount | lvlCount
-  FB_TRY(o->timers.alloc(16 * 8));
-  FB_HIP(hipMemset(o->timers.p, 0, 16 * 8));
+  FB_TRY(o->timers.alloc(FB_ORB_TIMER_WORDS * 8));
+  FB_HIP(hipMemset(o->timers.p, 0, FB_ORB_TIMER_WORDS * 8));
   K.timers = o->timers.as<unsigned long long>();
   FB_TRY(o->lvlOut.alloc(B * K.outStride * 4 + 16));
   o->w = w; o->h = h; o->batchCap = batch;
@@ -1859,6 +1901,19 @@ int fb_orb_debug_timers(fb_orb *o, uint64_t *dst16) {
   FB_HIP(hipMemset(o->timers.p, 0, 16 * 8));
   return FB_OK;
 }
+
+#ifdef FB_FAST_LISTHIST
+// probe build only (profiles/probes/fast_list_lengths.py): dst128[0..63] = cells by length of the iniThFAST list,
+// dst128[64..127] = redone cells by length of the minThFAST-only list; both in bins of 8, cleared by the call
+extern "C" int fb_orb_debug_list_hist(fb_orb *o, uint64_t *dst128) {
+  FB_TRY(fb::check_device());
+  FB_ARG(o && dst128 && o->timers.p);
+  FB_HIP(hipDeviceSynchronize());
+  FB_HIP(hipMemcpy(dst128, o->timers.as<unsigned long long>() + 16, 128 * 8, hipMemcpyDeviceToHost));
+  FB_HIP(hipMemset(o->timers.as<unsigned long long>() + 16, 0, 128 * 8));
+  return FB_OK;
+}
+#endif
 
 int fb_orb_debug_candidates(fb_orb *o, int b, int level, uint32_t *dst, int cap) {
   FB_TRY(fb::check_device());
