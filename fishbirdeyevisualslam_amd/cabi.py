@@ -210,6 +210,21 @@ class BowTransformArgs(C.Structure):
                 ("fv_node_start", _vp), ("fv_items", _vp)]
 
 
+FB_KFDB_MAX_KEYFRAMES, FB_KFDB_MAX_WORDS, FB_KFDB_COVIS = 4096, 4096, 10
+FB_KFDB_RELOC, FB_KFDB_LOOP = 0, 1
+
+
+class KfdbParams(C.Structure):
+    _fields_ = [("max_keyframes", _i32), ("word_stride", _i32)]
+
+
+class KfdbQueryArgs(C.Structure):
+    _fields_ = [("mode", _i32), ("query_id", C.c_uint64), ("n_words", _vp), ("bow_ids", _vp), ("bow_vals", _vp),
+                ("min_score", _f32), ("n_connected", _i32), ("connected", _vp), ("covis", _vp),
+                ("n_candidates", _vp), ("candidates", _vp), ("n_sharing", _vp), ("max_common_words", _vp), ("n_scored", _vp),
+                ("common_words", _vp), ("scores", _vp)]
+
+
 class BirdFilterArgs(C.Structure):
     _fields_ = [("batch", _i32), ("match_stride", _i32), ("kp1_stride", _i32), ("kp2_stride", _i32),
                 ("n_matches", _vp), ("query_idx", _vp), ("train_idx", _vp), ("cam_xyz1", _vp), ("cam_xyz2", _vp),
@@ -314,6 +329,8 @@ EXPORTS = [
     "fb_distinctive_descriptors_dev", "fb_distinctive_descriptors",
     "fb_create_new_map_points_workspace", "fb_create_new_map_points_dev", "fb_create_new_map_points",
     "fb_bird_filter_matches_dev", "fb_bird_filter_matches", "fb_bow_transform_dev", "fb_bow_transform",
+    "fb_bow_score_dev", "fb_bow_score", "fb_kfdb_create", "fb_kfdb_destroy", "fb_kfdb_clear", "fb_kfdb_add_dev", "fb_kfdb_add",
+    "fb_kfdb_add_frame_dev", "fb_kfdb_erase", "fb_kfdb_query_dev", "fb_kfdb_query", "fb_kfdb_min_score_dev", "fb_kfdb_min_score",
     "fb_in_frustum_dev", "fb_in_frustum", "fb_undistort_keypoints_dev", "fb_undistort_keypoints", "fb_image_bounds",
     "fb_pose_opt_batch_dev", "fb_pose_opt", "fb_pose_gather_front_dev", "fb_pose_gather_bird_dev",
     "fb_frame_create", "fb_frame_destroy", "fb_frame_extract_dev", "fb_frame_extract", "fb_frame_set_pose_dev",

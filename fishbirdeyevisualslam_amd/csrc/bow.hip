@@ -11,6 +11,7 @@
 // weights in feature order (the reference's += order), one lane adds the L1 norm in ascending word order (the std::map
 // iteration order), everyone divides.  Phase 3: the same sort on (node, feature) keys yields the FeatureVector CSR.
 #include "fb_common.h"
+#include "fb_sort_scan.h"
 
 namespace {
 
@@ -19,36 +20,8 @@ constexpr int BOW_MAXF = 4096;
 constexpr int BOW_KMAX = 12;  // children per node handled with batched loads (the ORB vocabulary has 10)
 constexpr unsigned long long KEY_NONE = ~0ull;
 
-__device__ __forceinline__ void bitonic_sort(unsigned long long *key, int n2, int tid, int nt) {
-  for (int k = 2; k <= n2; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = tid; i < n2; i += nt) {
-        const int ixj = i ^ j;
-        if (ixj > i) {
-          const unsigned long long a = key[i], b = key[ixj];
-          const bool up = (i & k) == 0;
-          if ((a > b) == up) { key[i] = b; key[ixj] = a; }
-        }
-      }
-      __syncthreads();
-    }
-}
-
-// exclusive scan of one int per thread over the BOW_T-thread block (s_wv: [BOW_T / 64]); *total = block sum
-__device__ __forceinline__ int bow_excl_scan(int v, int *s_wv, int *total) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  int inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
-  __syncthreads();
-  if (lane == 63) s_wv[wv] = inc;
-  __syncthreads();
-  int base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < BOW_T / 64; w++) { const int x = s_wv[w]; if (w < wv) base += x; tot += x; }
-  *total = tot;
-  return base + inc - v;
-}
+using fb::bitonic_sort;
+__device__ __forceinline__ int bow_excl_scan(int v, int *s_wv, int *total) { return fb::block_excl_scan<BOW_T>(v, s_wv, total); }
 
 // Phase 1 on its own grid: 64 features per workgroup.  One workgroup per image walking all of its features kept the whole
 // descent -- 2000 x 12 x 6 random 32-byte reads -- on ONE compute unit's L1 (the largest part of the kernel at batch 1).

@@ -12,6 +12,7 @@
 #ifndef FISHBIRD_HOST_HPP_
 #define FISHBIRD_HOST_HPP_
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -603,6 +604,81 @@ inline void SearchByBoW(const ORBmatcher &, const DeviceFrame &kf, DeviceFrame &
 inline void PoseOptimizationWithBird(DeviceFrame &f, const DeviceMap &map, float wB = 1.f, float wF = 1.f, int which = 0, void *stream = nullptr) {
   check(fb_frame_pose_optimization_dev(f.handle(), &map.points, &map.birdPoints, FB_POSE_FRONT_BIRD, wB, wF, which, stream));
 }
+
+// ---- KeyFrameDatabase (include/KeyFrameDatabase.h:44-73) on slots ------------------------------------------------
+// A key frame is the host's index for pKF (its slot, as the map tables are indexed).  The BowVectors live on the device;
+// the covisibility rows (GetBestCovisibilityKeyFrames(10) per slot) are kept here and refreshed by the caller where the
+// reference runs UpdateConnections.  Single-threaded, like the reference under KeyFrameDatabase::mMutex.
+class KeyFrameDatabase {
+ public:
+  KeyFrameDatabase(int max_keyframes, int word_stride) : K_(max_keyframes), covis_((size_t)max_keyframes * FB_KFDB_COVIS, -1) {
+    fb_kfdb_params p = {max_keyframes, word_stride};
+    check(fb_kfdb_create(&p, &db_));
+  }
+  ~KeyFrameDatabase() { fb_kfdb_destroy(db_); }
+  KeyFrameDatabase(const KeyFrameDatabase &) = delete;
+  KeyFrameDatabase &operator=(const KeyFrameDatabase &) = delete;
+
+  void add(int slot, const BowVector &bow) {
+    std::vector<uint32_t> ids; std::vector<double> vals;
+    flatten(bow, ids, vals);
+    check(fb_kfdb_add(db_, slot, (int32_t)ids.size(), ids.data(), vals.data()));
+  }
+  void erase(int slot) { check(fb_kfdb_erase(db_, slot, nullptr)); }
+  void clear() { check(fb_kfdb_clear(db_, nullptr)); }
+  // vpNeighs = pKF->GetBestCovisibilityKeyFrames(10) as slots
+  void SetBestCovisibilityKeyFrames(int slot, const std::vector<int> &neighs) {
+    for (int c = 0; c < FB_KFDB_COVIS; c++) covis_[(size_t)slot * FB_KFDB_COVIS + c] = c < (int)neighs.size() ? neighs[c] : -1;
+  }
+  std::vector<int> DetectLoopCandidates(uint64_t mnId, const BowVector &bow, const std::vector<int> &connected, float minScore) {
+    return query(FB_KFDB_LOOP, mnId, bow, connected, minScore);
+  }
+  std::vector<int> DetectRelocalizationCandidates(uint64_t mnId, const BowVector &bow) {
+    return query(FB_KFDB_RELOC, mnId, bow, std::vector<int>(), 0.0f);
+  }
+  // LoopClosing::DetectLoop, LoopClosing.cc:127-141: the lowest score to a connected key frame that is not bad
+  float MinScore(const BowVector &bow, const std::vector<int> &connected, const std::vector<uint8_t> &isBad) {
+    std::vector<uint32_t> ids; std::vector<double> vals;
+    flatten(bow, ids, vals);
+    float m = 1.0f;
+    check(fb_kfdb_min_score(db_, (int32_t)ids.size(), ids.data(), vals.data(), (int32_t)connected.size(), connected.data(),
+                            isBad.empty() ? nullptr : isBad.data(), nullptr, &m));
+    return m;
+  }
+  // ORBVocabulary::score
+  static double score(const BowVector &a, const BowVector &b) {
+    std::vector<uint32_t> ai, bi; std::vector<double> av, bv;
+    flatten(a, ai, av); flatten(b, bi, bv);
+    const int32_t na = (int32_t)ai.size(), nb = (int32_t)bi.size();
+    const size_t stride = std::max<size_t>(1, std::max(ai.size(), bi.size()));
+    ai.resize(stride); av.resize(stride); bi.resize(stride); bv.resize(stride);
+    double s = 0;
+    check(fb_bow_score(1, (int32_t)stride, &na, ai.data(), av.data(), &nb, bi.data(), bv.data(), &s));
+    return s;
+  }
+
+ private:
+  static void flatten(const BowVector &bow, std::vector<uint32_t> &ids, std::vector<double> &vals) {
+    for (const auto &kv : bow) { ids.push_back(kv.first); vals.push_back(kv.second); }
+  }
+  std::vector<int> query(int mode, uint64_t id, const BowVector &bow, const std::vector<int> &connected, float minScore) {
+    std::vector<uint32_t> ids; std::vector<double> vals;
+    flatten(bow, ids, vals);
+    const int32_t nw = (int32_t)ids.size();
+    int32_t n = 0;
+    std::vector<int32_t> cand(K_, -1);
+    fb_kfdb_query_args a;
+    memset(&a, 0, sizeof(a));
+    a.mode = mode; a.query_id = id; a.n_words = &nw; a.bow_ids = ids.data(); a.bow_vals = vals.data(); a.min_score = minScore;
+    a.n_connected = (int32_t)connected.size(); a.connected = connected.data(); a.covis = covis_.data();
+    a.n_candidates = &n; a.candidates = cand.data();
+    check(fb_kfdb_query(db_, &a));
+    return std::vector<int>(cand.begin(), cand.begin() + n);
+  }
+  fb_kfdb *db_ = nullptr;
+  int K_;
+  std::vector<int32_t> covis_;
+};
 
 }  // namespace fishbird
 #endif

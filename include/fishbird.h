@@ -699,6 +699,81 @@ int fb_bow_transform_dev(const fb_vocabulary *voc /* device arrays */, const fb_
 int fb_bow_transform(const fb_vocabulary *voc, const fb_bow_transform_args *args); /* host pointers */
 
 /* ======================================================================== */
+/* KeyFrameDatabase (src/KeyFrameDatabase.cc) and ORBVocabulary::score        */
+/* ======================================================================== */
+/* TemplatedVocabulary::score with L1 scoring (L1Scoring::score, Thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-68) on
+ * explicit pairs: score[i] = score(a_i, b_i) for [batch] BowVectors a and b (ids ascending, `stride` entries per vector).
+ * The double sum runs over the shared words in ascending word order, exactly as the reference adds them.                */
+int fb_bow_score_dev(int32_t batch, int32_t stride, const int32_t *na, const uint32_t *a_ids, const double *a_vals,
+                     const int32_t *nb, const uint32_t *b_ids, const double *b_vals, double *score, void *stream);
+int fb_bow_score(int32_t batch, int32_t stride, const int32_t *na, const uint32_t *a_ids, const double *a_vals,
+                 const int32_t *nb, const uint32_t *b_ids, const double *b_vals, double *score); /* host pointers */
+
+/* The reference's KeyFrameDatabase plus the six query members every KeyFrame carries for it (KeyFrame.h:157-162:
+ * mnLoopQuery, mnLoopWords, mLoopScore, mnRelocQuery, mnRelocWords, mRelocScore).  A key frame is a slot in
+ * [0, max_keyframes): the host's index for pKF, as the map tables of fb_track_args are indexed.  The BowVectors stay on
+ * the device.  The handle is single-threaded, like fb_orb: the reference serialises its users with
+ * KeyFrameDatabase::mMutex, here the caller serialises (or uses one stream).  Calls take effect in the order they are
+ * made; occupancy errors are judged in that order.                                                                      */
+typedef struct fb_kfdb fb_kfdb;
+struct fb_frame;                /* the frame handle of the tracking chain below */
+#define FB_KFDB_MAX_KEYFRAMES 4096
+#define FB_KFDB_MAX_WORDS 4096
+#define FB_KFDB_COVIS 10
+typedef struct fb_kfdb_params {
+  int32_t max_keyframes;        /* 1 .. FB_KFDB_MAX_KEYFRAMES                                          */
+  int32_t word_stride;          /* words kept per BowVector, 1 .. FB_KFDB_MAX_WORDS                    */
+} fb_kfdb_params;
+int fb_kfdb_create(const fb_kfdb_params *p, fb_kfdb **out);
+int fb_kfdb_destroy(fb_kfdb *db);
+/* KeyFrameDatabase::clear (Tracking::Reset): every slot empty, the six members of every slot 0.                         */
+int fb_kfdb_clear(fb_kfdb *db, void *stream);
+/* KeyFrameDatabase::add(pKF).  The six members of the slot become 0 (KeyFrame.cc:35; the two scores, which the reference
+ * leaves uninitialised, are defined as 0.0f).  The _dev variant keeps min(*d_n_words, word_stride) words.               */
+int fb_kfdb_add_dev(fb_kfdb *db, int32_t slot, const int32_t *d_n_words, const uint32_t *d_bow_ids, const double *d_bow_vals,
+                    void *stream);
+int fb_kfdb_add(fb_kfdb *db, int32_t slot, int32_t n_words, const uint32_t *bow_ids, const double *bow_vals); /* host pointers */
+/* add() of sequence 0 of a frame handle after fb_frame_compute_bow_dev (needs kp_stride <= word_stride).                */
+int fb_kfdb_add_frame_dev(fb_kfdb *db, int32_t slot, struct fb_frame *kf, void *stream);
+/* KeyFrameDatabase::erase(pKF) (KeyFrame::SetBadFlag): the slot's six members stay, as they do on the bad KeyFrame.     */
+int fb_kfdb_erase(fb_kfdb *db, int32_t slot, void *stream);
+
+enum { FB_KFDB_RELOC = 0, FB_KFDB_LOOP = 1 };
+typedef struct fb_kfdb_query_args {
+  int32_t mode;                 /* FB_KFDB_RELOC: DetectRelocalizationCandidates(F) (KeyFrameDatabase.cc:199-309);
+                                   FB_KFDB_LOOP: DetectLoopCandidates(pKF, minScore) (:76-197)            */
+  uint64_t query_id;            /* F->mnId / pKF->mnId                                                  */
+  const int32_t *n_words;       /* [1]  the query's mBowVec                                             */
+  const uint32_t *bow_ids;      /* [n_words] ascending                                                  */
+  const double *bow_vals;       /* [n_words]                                                            */
+  float min_score;              /* LOOP                                                                 */
+  int32_t n_connected;          /* LOOP: entries of `connected`                                         */
+  const int32_t *connected;     /* LOOP: slots of pKF->GetConnectedKeyFrames() (may be NULL when n_connected == 0) */
+  const int32_t *covis;         /* [max_keyframes][FB_KFDB_COVIS] slots of GetBestCovisibilityKeyFrames(10) per key
+                                   frame in the vector's order, -1 = no entry                           */
+  int32_t *n_candidates;        /* [1]                                                                  */
+  int32_t *candidates;          /* [max_keyframes] slots, in the order of the returned vector           */
+  /* optional (NULL = not wanted): what the reference computes on the way */
+  int32_t *n_sharing;           /* [1] lKFsSharingWords.size()                                          */
+  int32_t *max_common_words;    /* [1] maxCommonWords (0 when the list is empty)                        */
+  int32_t *n_scored;            /* [1] nscores                                                          */
+  int32_t *common_words;        /* [max_keyframes] mn{Loop,Reloc}Words of every slot after the call     */
+  float *scores;                /* [max_keyframes] m{Loop,Reloc}Score of every slot after the call      */
+} fb_kfdb_query_args;
+int fb_kfdb_query_dev(fb_kfdb *db, const fb_kfdb_query_args *args, void *stream);  /* no synchronisation */
+int fb_kfdb_query(fb_kfdb *db, const fb_kfdb_query_args *args);                    /* host pointers */
+
+/* LoopClosing::DetectLoop's reference score (LoopClosing.cc:127-141): scores[i] = (float)score(query, slots[i]) for a
+ * list of slots, *min_score = the minimum over those with skip[i] == 0 (skip = pKF->isBad(); NULL = none skipped),
+ * starting from 1.  A slot's BowVector outlives erase (the bad KeyFrame keeps its mBowVec) until the slot is added again.
+ * scores may be NULL.                                                                                                   */
+int fb_kfdb_min_score_dev(fb_kfdb *db, const int32_t *d_n_words, const uint32_t *d_bow_ids, const double *d_bow_vals,
+                          int32_t n_list, const int32_t *d_slots, const uint8_t *d_skip, float *d_scores, float *d_min_score,
+                          void *stream);
+int fb_kfdb_min_score(fb_kfdb *db, int32_t n_words, const uint32_t *bow_ids, const double *bow_vals, int32_t n_list,
+                      const int32_t *slots, const uint8_t *skip, float *scores, float *min_score); /* host pointers */
+
+/* ======================================================================== */
 /* Frame geometry either side of the matchers (src/Frame.cc)                 */
 /* ======================================================================== */
 /* --- Frame::isInFrustum(pMP, viewingCosLimit) over a list of map points (Frame.cc:435-491; the loop
