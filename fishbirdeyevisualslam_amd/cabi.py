@@ -192,6 +192,22 @@ class Sim3Args(C.Structure):
                 ("matches12", _vp), ("nfound", _vp)]
 
 
+FB_SIM3_MAX_HYP = 300
+SIM3_CORR_DTYPE = np.dtype([("x3dc1", "<f4", 3), ("x3dc2", "<f4", 3), ("p1im1", "<f4", 2), ("p2im2", "<f4", 2),
+                            ("max_err1", "<i4"), ("max_err2", "<i4")])
+assert SIM3_CORR_DTYPE.itemsize == 48
+
+
+class Sim3SolverArgs(C.Structure):
+    _fields_ = [("n_cand", _i32), ("kf1", KfTarget), ("kf2", KfTarget), ("mp1", MpList), ("mp2", MpList),
+                ("T1w", _vp), ("T2w", _vp), ("kf1_index", _vp), ("kf2_index", _vp), ("matches12", _vp),
+                ("level_sigma2", _f32 * FB_MAX_LEVELS), ("fix_scale", _i32), ("ransac_prob", C.c_double),
+                ("min_inliers", _i32), ("max_iterations", _i32), ("accept_above", _vp), ("rand_idx", _vp),
+                ("N", _vp), ("indices1", _vp), ("corr", _vp), ("max_its", _vp), ("n_hyp_done", _vp), ("first_accept", _vp),
+                ("no_more", _vp), ("s", _vp), ("R", _vp), ("t", _vp), ("n_inliers", _vp), ("accept", _vp),
+                ("inlier_mask", _vp), ("workspace", _vp), ("workspace_bytes", C.c_size_t)]
+
+
 class InitMatchArgs(C.Structure):
     _fields_ = [("batch", _i32), ("f1_stride", _i32), ("f2_stride", _i32), ("n1", _vp), ("kps1", _vp), ("desc1", _vp),
                 ("n2", _vp), ("kps2", _vp), ("desc2", _vp), ("f2_cell_start", _vp), ("f2_cell_items", _vp),
@@ -328,6 +344,7 @@ EXPORTS = [
     "fb_match_initialization_dev", "fb_match_initialization",
     "fb_distinctive_descriptors_dev", "fb_distinctive_descriptors",
     "fb_create_new_map_points_workspace", "fb_create_new_map_points_dev", "fb_create_new_map_points",
+    "fb_sim3_solver_workspace", "fb_sim3_solver_dev", "fb_sim3_solver",
     "fb_bird_filter_matches_dev", "fb_bird_filter_matches", "fb_bow_transform_dev", "fb_bow_transform",
     "fb_bow_score_dev", "fb_bow_score", "fb_kfdb_create", "fb_kfdb_destroy", "fb_kfdb_clear", "fb_kfdb_add_dev", "fb_kfdb_add",
     "fb_kfdb_add_frame_dev", "fb_kfdb_erase", "fb_kfdb_query_dev", "fb_kfdb_query", "fb_kfdb_min_score_dev", "fb_kfdb_min_score",

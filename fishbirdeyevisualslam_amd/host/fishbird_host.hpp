@@ -15,6 +15,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <stdexcept>
@@ -678,6 +679,160 @@ class KeyFrameDatabase {
   fb_kfdb *db_ = nullptr;
   int K_;
   std::vector<int32_t> covis_;
+};
+
+// ---- Sim3Solver (include/Sim3Solver.h) ---------------------------------------------------------------------------------
+// One candidate per object, as in the reference.  The first iterate() runs fb_sim3_solver once: every iteration up to
+// mRansacMaxIts lands in a table, and iterate(n, ...) replays rows (mnIterations, mnIterations + n] of it, so
+// LoopClosing's round-robin iterate(5, ...) and its "go on after a failed OptimizeSim3" behave as in the reference.
+// The 3 x mRansacMaxIts RandomInt values are drawn when the table is filled (INTEGRATION.md 7 on what that means for the
+// random stream).
+struct Sim3KeyFrame {             // what Sim3Solver reads of a KeyFrame
+  int N = 0;                      // features
+  const fb_keypoint *mvKeysUn = nullptr;
+  const uint8_t *mpValid = nullptr;        // [N] GetMapPointMatches()[i] && !isBad()
+  const float *mpWorldPos = nullptr;       // [N][3] GetWorldPos()
+  const int32_t *indexInKeyFrame = nullptr;  // [N] GetIndexInKeyFrame(this key frame), or NULL = i
+  const float *Tcw = nullptr;              // [12] GetRotation | GetTranslation
+  float fx = 0, fy = 0, cx = 0, cy = 0;    // mK
+  long mnFrameId = 0;
+};
+
+class Sim3Solver {
+ public:
+  typedef int (*RandomIntFn)(int min, int max);
+  // DUtils::Random::RandomInt (Thirdparty/DBoW2/DUtils/Random.cpp)
+  static int RandomInt(int min, int max) {
+    const int d = max - min + 1;
+    return int(((double)rand() / ((double)RAND_MAX + 1.0)) * d) + min;
+  }
+  // vnMatches12[i1] = feature of pKF2 whose MapPoint is vpMatched12[i1], or -1 (fb_match_bow_kf's matches12)
+  Sim3Solver(const Sim3KeyFrame &kf1, const Sim3KeyFrame &kf2, const std::vector<int32_t> &vnMatches12, bool bFixScale,
+             const float *mvLevelSigma2, int nLevels, RandomIntFn randomInt = &Sim3Solver::RandomInt)
+      : kf1_(kf1), kf2_(kf2), m12_(vnMatches12), fixScale_(bFixScale), rand_(randomInt) {
+    for (int l = 0; l < FB_MAX_LEVELS; l++) sigma2_[l] = l < nLevels ? mvLevelSigma2[l] : 0.0f;
+    mN1 = (int)m12_.size();
+    if (mN1 != kf1.N || kf1.N < 1 || kf2.N < 1) throw std::runtime_error("Sim3Solver: vpMatched12.size() must equal pKF1->N, and both key frames need features");
+    N = 0;  // the constructor's count (Sim3Solver.cc:62-103) with fb_sim3_solver's skip rule, needed here for the range of the draws
+    for (int i1 = 0; i1 < mN1; i1++) {
+      const int j = m12_[i1];
+      if (j < 0 || j >= kf2.N || !kf1.mpValid[i1] || !kf2.mpValid[j]) continue;
+      const int k1 = kf1.indexInKeyFrame ? kf1.indexInKeyFrame[i1] : i1, k2 = kf2.indexInKeyFrame ? kf2.indexInKeyFrame[j] : j;
+      if (k1 < 0 || k2 < 0 || k1 >= kf1.N || k2 >= kf2.N) continue;
+      const int o1 = kf1.mvKeysUn[k1].octave, o2 = kf2.mvKeysUn[k2].octave;
+      if (o1 < 0 || o1 >= FB_MAX_LEVELS || o2 < 0 || o2 >= FB_MAX_LEVELS) continue;  // (the reference would read out of bounds)
+      N++;
+    }
+    SetRansacParameters();
+  }
+
+  void SetRansacParameters(double probability = 0.99, int minInliers = 6, int maxIterations = 300) {
+    mRansacProb = probability;
+    mRansacMinInliers = minInliers;
+    maxIterations_ = maxIterations;
+    const float epsilon = (float)mRansacMinInliers / N;
+    int nIterations;
+    if (mRansacMinInliers == N) {
+      nIterations = 1;
+    } else {
+      const double x = std::ceil(std::log(1 - mRansacProb) / std::log(1 - std::pow(epsilon, 3)));
+      nIterations = x < (double)maxIterations ? (int)x : maxIterations;
+    }
+    mRansacMaxIts = std::max(1, std::min(nIterations, maxIterations));
+    mnIterations = 0;
+    filled_ = false;
+  }
+
+  // true = the reference returned mBestT12 (GetEstimated* hold it); false = the empty cv::Mat
+  bool iterate(int nIterations, bool &bNoMore, std::vector<bool> &vbInliers, int &nInliers) {
+    bNoMore = false;
+    vbInliers = std::vector<bool>(mN1, false);
+    nInliers = 0;
+    if (N < mRansacMinInliers) {
+      bNoMore = true;
+      return false;
+    }
+    if (!filled_) fill();
+    int nCurrentIterations = 0;
+    while (mnIterations < mRansacMaxIts && nCurrentIterations < nIterations) {
+      nCurrentIterations++;
+      mnIterations++;
+      const int k = mnIterations - 1;
+      if (ninl_[k] >= mnBestInliers) {
+        mnBestInliers = ninl_[k];
+        best_ = k;
+        if (accept_[k]) {
+          nInliers = ninl_[k];
+          for (int i = 0; i < N; i++)
+            if ((mask_[(size_t)k * mw_ + i / 32] >> (i % 32)) & 1u) vbInliers[idx1_[i]] = true;
+          return true;
+        }
+      }
+    }
+    if (mnIterations >= mRansacMaxIts) bNoMore = true;
+    return false;
+  }
+  bool find(std::vector<bool> &vbInliers12, int &nInliers) {
+    bool bFlag;
+    return iterate(mRansacMaxIts, bFlag, vbInliers12, nInliers);
+  }
+  const float *GetEstimatedRotation() const { return &R_[(size_t)best_ * 9]; }     // row-major 3x3
+  const float *GetEstimatedTranslation() const { return &t_[(size_t)best_ * 3]; }
+  float GetEstimatedScale() const { return s_[best_]; }
+  int iterations() const { return mnIterations; }
+  int maxIterations() const { return mRansacMaxIts; }
+  int correspondences() const { return N; }
+
+ private:
+  void fill() {
+    const int s1 = kf1_.N, s2 = kf2_.N;
+    mw_ = (s1 + 31) / 32;
+    std::vector<int32_t> m12(s1, -1), rnd((size_t)FB_SIM3_MAX_HYP * 3, 0);
+    std::copy(m12_.begin(), m12_.end(), m12.begin());
+    for (int k = 0; k < mRansacMaxIts; k++)
+      for (int j = 0; j < 3; j++) rnd[(size_t)k * 3 + j] = rand_(0, N - j - 1);
+    // (Sim3Solver.cc:192: inside the frame-id window more than 15 inliers are enough)
+    int32_t above = mRansacMinInliers;
+    if (kf1_.mnFrameId > 1126 && kf1_.mnFrameId < 1136) above = std::min(mRansacMinInliers, 15);
+    const int32_t n1 = kf1_.N;
+    idx1_.assign(s1, -1);
+    s_.assign(FB_SIM3_MAX_HYP, 0.f); R_.assign((size_t)FB_SIM3_MAX_HYP * 9, 0.f); t_.assign((size_t)FB_SIM3_MAX_HYP * 3, 0.f);
+    ninl_.assign(FB_SIM3_MAX_HYP, 0); accept_.assign(FB_SIM3_MAX_HYP, 0); mask_.assign((size_t)FB_SIM3_MAX_HYP * mw_, 0u);
+    int32_t Ndev = 0, maxIts = 0, done = 0, first = 0, noMore = 0;
+    fb_sim3_solver_args a;
+    memset(&a, 0, sizeof(a));
+    a.n_cand = 1;
+    a.kf1.kf_stride = s1; a.kf1.n_kf = &n1; a.kf1.kf_kps = kf1_.mvKeysUn;
+    a.kf2.kf_stride = s2; a.kf2.kf_kps = kf2_.mvKeysUn;
+    a.kf1.cam.fx = kf1_.fx; a.kf1.cam.fy = kf1_.fy; a.kf1.cam.cx = kf1_.cx; a.kf1.cam.cy = kf1_.cy;
+    a.kf2.cam.fx = kf2_.fx; a.kf2.cam.fy = kf2_.fy; a.kf2.cam.cx = kf2_.cx; a.kf2.cam.cy = kf2_.cy;
+    a.mp1.mp_stride = s1; a.mp1.mp_valid = kf1_.mpValid; a.mp1.mp_xw = kf1_.mpWorldPos;
+    a.mp2.mp_stride = s2; a.mp2.mp_valid = kf2_.mpValid; a.mp2.mp_xw = kf2_.mpWorldPos;
+    a.T1w = kf1_.Tcw; a.T2w = kf2_.Tcw; a.kf1_index = kf1_.indexInKeyFrame; a.kf2_index = kf2_.indexInKeyFrame;
+    a.matches12 = m12.data();
+    for (int l = 0; l < FB_MAX_LEVELS; l++) a.level_sigma2[l] = sigma2_[l];
+    a.fix_scale = fixScale_ ? 1 : 0;
+    a.ransac_prob = mRansacProb; a.min_inliers = mRansacMinInliers; a.max_iterations = maxIterations_;
+    a.accept_above = &above; a.rand_idx = rnd.data();
+    a.N = &Ndev; a.indices1 = idx1_.data(); a.max_its = &maxIts; a.n_hyp_done = &done; a.first_accept = &first; a.no_more = &noMore;
+    a.s = s_.data(); a.R = R_.data(); a.t = t_.data(); a.n_inliers = ninl_.data(); a.accept = accept_.data(); a.inlier_mask = mask_.data();
+    check(fb_sim3_solver(&a));
+    if (Ndev != N || maxIts != mRansacMaxIts) throw std::runtime_error("Sim3Solver: the device's N / mRansacMaxIts differ from the host's");
+    filled_ = true;
+  }
+  Sim3KeyFrame kf1_, kf2_;
+  std::vector<int32_t> m12_;
+  bool fixScale_;
+  RandomIntFn rand_;
+  float sigma2_[FB_MAX_LEVELS];
+  int mN1 = 0, N = 0, mw_ = 0;
+  double mRansacProb = 0.99;
+  int mRansacMinInliers = 6, mRansacMaxIts = 300, maxIterations_ = 300, mnIterations = 0, mnBestInliers = 0, best_ = 0;
+  bool filled_ = false;
+  std::vector<int32_t> idx1_, ninl_;
+  std::vector<float> s_, R_, t_;
+  std::vector<uint8_t> accept_;
+  std::vector<uint32_t> mask_;
 };
 
 }  // namespace fishbird

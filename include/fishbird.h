@@ -661,6 +661,80 @@ int fb_create_new_map_points_dev(const fb_new_points_args *args, void *stream);
 int fb_create_new_map_points(const fb_new_points_args *args);
 
 /* ======================================================================== */
+/* Sim3Solver (src/Sim3Solver.cc; LoopClosing::ComputeSim3, LoopClosing.cc:225-420) */
+/* ======================================================================== */
+/* The RANSAC over Horn's closed form for every loop candidate of one key frame pKF1, in one call: the constructor
+ * (:37-112), SetRansacParameters (:114-138) and ALL mRansacMaxIts iterations of iterate() (:140-231) per candidate, as a
+ * table.  Iteration k of the reference depends on the earlier ones only through the running best count, so the table
+ * holds every hypothesis (s, R, t, inlier count, inlier mask) plus the accept rule evaluated as a scan; a host that
+ * replays iterate(n, ...) reads rows (mnIterations, mnIterations + n] of it (fishbird::Sim3Solver, fishbird_host.hpp).
+ * The draws are an INPUT: rand_idx[c][k][j] is the value DUtils::Random::RandomInt(0, vAvailableIndices.size()-1)
+ * returned for draw j of iteration k (:168), 0 <= rand_idx[c][k][j] <= N[c]-1-j; the swap-with-back removal (:175-176)
+ * is replayed on the device.  Values outside that range are clamped into it (the range is the caller's contract).
+ * MEMORY SAFETY, not in the reference (which would read out of bounds): a correspondence is also skipped, and so not counted
+ * in N, when matches12[i1] >= the KF2 stride, when a GetIndexInKeyFrame value is >= its key frame's stride, or when the key
+ * point it names has an octave outside [0, FB_MAX_LEVELS).  mRansacMaxIts is evaluated on the host with the reference's
+ * expression (Sim3Solver.cc:125-135) for every N up to the KF1 stride and handed to the device as a step table.
+ * MONOCULAR: the key frames' camera matrices are kf1.cam / kf2.cam (fx, fy, cx, cy).
+ * Hypothesis rows are three separate tables so that &s[c][k], &R[c][k][0], &t[c][k][0] are the s12 / R12 / t12 of an
+ * fb_sim3_args with batch 1.  Rows k >= max_its[c] are not written.  Pointers are DEVICE pointers for _dev.        */
+#define FB_SIM3_MAX_HYP 300
+typedef struct fb_sim3_corr {     /* one kept correspondence, compacted in ascending i1                       */
+  float x3dc1[3];                 /* mvX3Dc1 = Rcw1*Xw1 + tcw1                                               */
+  float x3dc2[3];                 /* mvX3Dc2                                                                 */
+  float p1im1[2];                 /* mvP1im1 (FromCameraToImage, mK1)                                        */
+  float p2im2[2];                 /* mvP2im2                                                                 */
+  int32_t max_err1, max_err2;     /* mvnMaxError1/2 = (size_t)(9.210*mvLevelSigma2[octave]): TRUNCATED       */
+} fb_sim3_corr;
+typedef struct fb_sim3_solver_args {
+  int32_t n_cand;                 /* candidates pKF2 of this call (nInitialCandidates), >= 1                 */
+  fb_kf_target kf1;               /* pKF1, batch 1. Read: kf_stride, n_kf (= vpMatched12.size() = pKF1->N), kf_kps
+                                     (mvKeysUn: octave), cam (mK1).  The other fields may be 0 / NULL.           */
+  fb_kf_target kf2;               /* the candidates, batch n_cand ([n_cand][kf_stride] arrays). Same fields; mK2   */
+  fb_mp_list mp1;                 /* per KF1 feature i1 (mp_stride == kf1.kf_stride): mp_valid = pMP1 && !isBad()
+                                     with pMP1 = GetMapPointMatches()[i1]; mp_xw = GetWorldPos().  Rest unread.   */
+  fb_mp_list mp2;                 /* per feature of each candidate ([n_cand][mp_stride], == kf2.kf_stride):
+                                     mp_valid = !pMP2->isBad(); mp_xw                                           */
+  const float *T1w;               /* [12] pKF1 GetRotation | GetTranslation, row-major 3x4                    */
+  const float *T2w;               /* [n_cand][12]                                                            */
+  const int32_t *kf1_index;       /* [kf1 stride] pMP1->GetIndexInKeyFrame(pKF1), or NULL = i1               */
+  const int32_t *kf2_index;       /* [n_cand][kf2 stride] pMP2->GetIndexInKeyFrame(pKF2), or NULL = the slot */
+  const int32_t *matches12;       /* [n_cand][kf1 stride]: KF2 feature whose point is vpMatched12[i1], or -1
+                                     (what fb_match_bow_kf writes)                                           */
+  float level_sigma2[FB_MAX_LEVELS]; /* mvLevelSigma2 (both key frames)                                      */
+  int32_t fix_scale;              /* mbFixScale                                                              */
+  double ransac_prob;             /* SetRansacParameters(probability, minInliers, maxIterations):            */
+  int32_t min_inliers;            /*   (0.99, 20, 300) at LoopClosing.cc:278; min_inliers >= 3, any value    */
+  int32_t max_iterations;         /*   1 .. FB_SIM3_MAX_HYP                                                  */
+  const int32_t *accept_above;    /* [n_cand] or NULL = min_inliers: iterate returns when mnInliersi > this (:192).
+                                     min(min_inliers, 15) restates the frame-id window of that line.          */
+  const int32_t *rand_idx;        /* [n_cand][FB_SIM3_MAX_HYP][3] the RandomInt values, see above            */
+  /* outputs per candidate */
+  int32_t *N;                     /* [n_cand] N = mvpMapPoints1.size()                                       */
+  int32_t *indices1;              /* [n_cand][kf1 stride] mvnIndices1 (rows < N)                             */
+  fb_sim3_corr *corr;             /* [n_cand][kf1 stride] (rows < N), or NULL                                */
+  int32_t *max_its;               /* [n_cand] mRansacMaxIts after SetRansacParameters                        */
+  int32_t *n_hyp_done;            /* [n_cand] rows of the tables that were computed: max_its, 0 when N < min_inliers */
+  int32_t *first_accept;          /* [n_cand] first k with accept, or -1: iterate returns at mnIterations = k+1 */
+  int32_t *no_more;               /* [n_cand] 1 = N < min_inliers, or every iteration ran without a return (find() is empty) */
+  /* outputs per (candidate, hypothesis k) */
+  float *s;                       /* [n_cand][FB_SIM3_MAX_HYP]       ms12i                                    */
+  float *R;                       /* [n_cand][FB_SIM3_MAX_HYP][9]    mR12i                                    */
+  float *t;                       /* [n_cand][FB_SIM3_MAX_HYP][3]    mt12i                                    */
+  int32_t *n_inliers;             /* [n_cand][FB_SIM3_MAX_HYP]       mnInliersi                               */
+  uint8_t *accept;                /* [n_cand][FB_SIM3_MAX_HYP]       mnInliersi >= mnBestInliers && > accept_above */
+  uint32_t *inlier_mask;          /* [n_cand][FB_SIM3_MAX_HYP][(kf1 stride+31)/32] mvbInliersi, bit i%32 of word i/32,
+                                     compacted order (scatter through indices1); words < (N+31)/32 are written */
+  /* device scratch of fb_sim3_solver_workspace(n_cand, kf1 stride) bytes, 16-byte aligned, private to the call until it
+   * has finished on `stream` (_dev only; the host drop-in allocates its own)                                        */
+  void *workspace;
+  size_t workspace_bytes;
+} fb_sim3_solver_args;
+size_t fb_sim3_solver_workspace(int n_cand, int n1_stride);
+int fb_sim3_solver_dev(const fb_sim3_solver_args *args, void *stream);  /* no host synchronisation */
+int fb_sim3_solver(const fb_sim3_solver_args *args);                    /* host pointers */
+
+/* ======================================================================== */
 /* DBoW2 vocabulary transform (Frame::ComputeBoW, src/Frame.cc:628-635)       */
 /* ======================================================================== */
 /* DBoW2::TemplatedVocabulary<FORB::TDescriptor, FORB> as flat arrays
