@@ -23,6 +23,7 @@
 // The accept/reject logic of Levenberg-Marquardt runs on the host between trials (a few scalars
 // are read back per trial); the abort flag (pbStopFlag) is polled there, between iterations.
 #include "fb_common.h"
+#include "fb_primitives.h"
 
 #include <thread>
 #include "fb_se3.h"
@@ -78,21 +79,11 @@ struct State {
   double *pt;    // [npt][3]
 };
 
-// reciprocal from the hardware seed + two Newton steps (relative error < 2^-50) for the pivots of the reduced pose system:
-// the BA is held to 1e-4 on poses and landmarks, and an IEEE division is ~35 dependent instructions on the critical path
-// of every block step of k_ba_solve
-__device__ __forceinline__ double ba_rcp(double x) {
-  double r = __builtin_amdgcn_rcp(x);
-  r = fma(fma(-x, r, 1.0), r, r);
-  r = fma(fma(-x, r, 1.0), r, r);
-  return r;
-}
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
+// fb::rcp_f64_newton serves the pivots of the reduced pose system: the BA is held to 1e-4 on poses and landmarks, and an
+// IEEE division is ~35 dependent instructions on the critical path of every block step of k_ba_solve
+using fb::rcp_f64_newton;
+using fb::wave_sum;
+using fb::dpp_f64;
 
 // residual + Jacobians of one point-pose edge (vertex 0 = point, vertex 1 = pose)
 struct EdgeLin {
@@ -219,14 +210,6 @@ __device__ __forceinline__ void lin_edge(const BADev &D, const LinBuf &B, const 
   }
 }
 
-template <int CTRL>
-__device__ __forceinline__ double ba_dpp_f64(double v) {  // v of the lane selected by the DPP control
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xF, 0xF, true);
-  hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xF, 0xF, true);
-  return __hiloint2double(hi, lo);
-}
-
 // The same with FOUR lanes per landmark (device-resident schedule): lane `sub` of a quad takes the landmark's edges sub,
 // sub + 4, ...; Hll, bl and chi2 are summed over the quad with two DPP quad permutes ((a0 + a1) + (a2 + a3)).  A landmark has
 // 2..10 observers, so one lane per landmark walked them serially with three dependent gathers each: the landmark role was
@@ -263,9 +246,9 @@ __device__ __forceinline__ void linearize_quad_body(const BADev &D, const State 
   }
   // quad sums (every lane of the wave takes part: lanes beyond npt carry zeros)
 #pragma unroll
-  for (int i = 0; i < 9; i++) { H[i] += ba_dpp_f64<0xB1>(H[i]); H[i] += ba_dpp_f64<0x4E>(H[i]); }
+  for (int i = 0; i < 9; i++) { H[i] += dpp_f64<0xB1>(H[i]); H[i] += dpp_f64<0x4E>(H[i]); }
 #pragma unroll
-  for (int i = 0; i < 3; i++) { b3[i] += ba_dpp_f64<0xB1>(b3[i]); b3[i] += ba_dpp_f64<0x4E>(b3[i]); }
+  for (int i = 0; i < 3; i++) { b3[i] += dpp_f64<0xB1>(b3[i]); b3[i] += dpp_f64<0x4E>(b3[i]); }
   if (l < D.npt && sub == 0) {
 #pragma unroll
     for (int i = 0; i < 9; i++) B.Hll[(size_t)9 * l + i] = H[i];
@@ -273,9 +256,8 @@ __device__ __forceinline__ void linearize_quad_body(const BADev &D, const State 
     for (int i = 0; i < 3; i++) B.bl[(size_t)3 * l + i] = b3[i];
     hmax = fmax(fmax(fabs(H[0]), fabs(H[4])), fabs(H[8]));
   }
-  const double ws = wave_sum_d(chi);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) hmax = fmax(hmax, __shfl_xor(hmax, o, 64));
+  const double ws = wave_sum(chi);
+  hmax = fb::wave_max(hmax);
   if ((threadIdx.x & 63) == 0) { s_part[threadIdx.x >> 6] = ws; s_part[TH / 64 + (threadIdx.x >> 6)] = hmax; }
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -326,9 +308,8 @@ __device__ __forceinline__ void linearize_body(const BADev &D, const State &S, c
     for (int i = 0; i < 3; i++) B.bl[(size_t)3 * l + i] = b3[i];
     hmax = fmax(fmax(fabs(H[0]), fabs(H[4])), fabs(H[8]));
   }
-  const double ws = wave_sum_d(chi);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) hmax = fmax(hmax, __shfl_xor(hmax, o, 64));
+  const double ws = wave_sum(chi);
+  hmax = fb::wave_max(hmax);
   if ((threadIdx.x & 63) == 0) { s_part[threadIdx.x >> 6] = ws; s_part[TH / 64 + (threadIdx.x >> 6)] = hmax; }
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -726,7 +707,7 @@ __device__ __forceinline__ void solve_body(const LinBuf &B, double lambda, const
       for (int m = 0; m < c; m++) dc -= Lb[c][m] * Lb[c][m] * d[m];
       if (dc == 0) neg = true;  // SimplicialLDLT: the factorisation fails on a pivot that is exactly 0, negative pivots proceed
       d[c] = dc;
-      const double inv = dc != 0 ? ba_rcp(dc) : 0.0;
+      const double inv = dc != 0 ? rcp_f64_newton(dc) : 0.0;
       dinv[c] = inv;
 #pragma unroll
       for (int r = c + 1; r < 6; r++) {
@@ -801,7 +782,7 @@ __device__ __forceinline__ void solve_body(const LinBuf &B, double lambda, const
   }
   for (int i = tid; i < P6; i += SOLVE_THREADS) {  // D^-1
     const double dd = A[(size_t)i * ld + i];
-    rhs[i] = dd != 0 ? rhs[i] * ba_rcp(dd) : 0.0;
+    rhs[i] = dd != 0 ? rhs[i] * rcp_f64_newton(dd) : 0.0;
   }
   __syncthreads();
   for (int J = nb6 - 1; J >= 0; J--) {  // backward: L^T x = y
@@ -907,7 +888,7 @@ __device__ __forceinline__ void solve_lookahead(const LinBuf &B, double lambda, 
       for (int m = 0; m < c; m++) dc -= Lb[c][m] * Ub[c][m];
       if (dc == 0) neg = true;  // SimplicialLDLT: the factorisation fails on a pivot that is exactly 0, negative pivots proceed
       d[c] = dc;
-      const double inv = dc != 0 ? ba_rcp(dc) : 0.0;
+      const double inv = dc != 0 ? rcp_f64_newton(dc) : 0.0;
       dinv[c] = inv;
 #pragma unroll
       for (int r = c + 1; r < 6; r++) {
@@ -1077,7 +1058,7 @@ __device__ __forceinline__ void update_body(const BADev &D, const LinBuf &B, con
       trial.pose[k] = fb::se3_mul(fb::se3_exp(u), cur.pose[k]);
     }
   }
-  const double ws = wave_sum_d(sc);
+  const double ws = wave_sum(sc);
   if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = ws;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -1349,8 +1330,8 @@ __device__ __forceinline__ void control_body(const BADev &D, const Lb2 &lb, BACt
     // and a few hundred dependent additions on one lane were a third of this kernel)
     for (int i = tid; i < nLin; i += 64) chi += i < 512 ? s_chiP[i] : B.chiPart[i];
     if (!init) for (int i = tid; i < nScale; i += 64) scale += i < 512 ? s_scaleP[i] : scalePart[i];
-    chi = wave_sum_d(chi);
-    scale = wave_sum_d(scale);
+    chi = wave_sum(chi);
+    scale = wave_sum(scale);
   }
   if (tid != 0) return;
   int abortReq;
@@ -1683,8 +1664,7 @@ __global__ __launch_bounds__(1024) void k_bld_scan(int *cnt, int n, int *fill) {
   for (int base = 0; base <= n; base += 1024) {
     const int i = base + tid;
     const int v = i <= n ? cnt[i] : 0;
-    int inc = v;
-    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
+    const int inc = fb::wave_incl_scan(v);
     if (lane == 63) s_w[wv] = inc;
     __syncthreads();
     int off = s_run;
@@ -1728,18 +1708,7 @@ __global__ __launch_bounds__(1024) void k_bld_sort_ps(const int *ps_start, int *
   if (m > cap) { if (tid == 0) atomicOr(bad, 4); return; }  // one key frame with more observations than the LDS sort holds
   for (int i = tid; i < m; i += 1024) s_v[i] = i < n ? ps_edges[a0 + i] : 0x7fffffff;
   __syncthreads();
-  for (int kk = 2; kk <= m; kk <<= 1)
-    for (int j = kk >> 1; j > 0; j >>= 1) {
-      for (int i = tid; i < m; i += 1024) {
-        const int p = i ^ j;
-        if (p > i) {
-          const int a = s_v[i], b = s_v[p];
-          const bool up = (i & kk) == 0;
-          if ((a > b) == up) { s_v[i] = b; s_v[p] = a; }
-        }
-      }
-      __syncthreads();
-    }
+  fb::bitonic_sort(s_v, m, tid, 1024);
   for (int i = tid; i < n; i += 1024) ps_edges[a0 + i] = s_v[i];
 }
 __global__ void k_bld_check(const int *bad, BACtl *c) {

@@ -62,7 +62,7 @@ __global__ __launch_bounds__(256) void k_ba_schur_gather(BADev D, LinBuf B, cons
     }
   }
 #pragma unroll
-  for (int i = 0; i < 36; i++) acc[i] = wave_sum_d(acc[i]);
+  for (int i = 0; i < 36; i++) acc[i] = wave_sum(acc[i]);
   if (lane == 0) {
     const int pr = Lst.blk_pr[blk], pc = Lst.blk_pc[blk];
 #pragma unroll
@@ -88,7 +88,7 @@ __global__ __launch_bounds__(256) void k_ba_rhs_gather(BADev D, LinBuf B, const 
     for (int i = 0; i < 6; i++) acc[i] += W[i * 3] * t0 + W[i * 3 + 1] * t1 + W[i * 3 + 2] * t2;
   }
 #pragma unroll
-  for (int i = 0; i < 6; i++) acc[i] = wave_sum_d(acc[i]);
+  for (int i = 0; i < 6; i++) acc[i] = wave_sum(acc[i]);
   if (lane == 0)
 #pragma unroll
     for (int i = 0; i < 6; i++) r[6 * k + i] = acc[i];

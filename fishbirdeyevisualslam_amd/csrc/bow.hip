@@ -11,7 +11,7 @@
 // weights in feature order (the reference's += order), one lane adds the L1 norm in ascending word order (the std::map
 // iteration order), everyone divides.  Phase 3: the same sort on (node, feature) keys yields the FeatureVector CSR.
 #include "fb_common.h"
-#include "fb_sort_scan.h"
+#include "fb_primitives.h"
 
 namespace {
 
@@ -21,7 +21,6 @@ constexpr int BOW_KMAX = 12;  // children per node handled with batched loads (t
 constexpr unsigned long long KEY_NONE = ~0ull;
 
 using fb::bitonic_sort;
-__device__ __forceinline__ int bow_excl_scan(int v, int *s_wv, int *total) { return fb::block_excl_scan<BOW_T>(v, s_wv, total); }
 
 // Phase 1 on its own grid: 64 features per workgroup.  One workgroup per image walking all of its features kept the whole
 // descent -- 2000 x 12 x 6 random 32-byte reads -- on ONE compute unit's L1 (the largest part of the kernel at batch 1).
@@ -116,7 +115,7 @@ __global__ __launch_bounds__(BOW_T) void k_bow_transform(fb_vocabulary V, fb_bow
   __shared__ double s_sum[BOW_MAXF];   // summed weight per unique word, by rank
   int nw;
   {
-    int rank = bow_excl_scan(heads, s_wv, &nw);
+    int rank = fb::block_excl_scan<BOW_T>(heads, s_wv, &nw);
     for (int i = i0; i < i1; i++) {
       const unsigned long long k = s_key[i];
       if (k == KEY_NONE) break;
@@ -173,7 +172,7 @@ __global__ __launch_bounds__(BOW_T) void k_bow_transform(fb_vocabulary V, fb_bow
   int nNodes;
   int32_t *st = A.fv_node_start + (size_t)b * (A.f_stride + 1);
   {
-    int rank = bow_excl_scan(heads, s_wv, &nNodes);
+    int rank = fb::block_excl_scan<BOW_T>(heads, s_wv, &nNodes);
     for (int i = i0; i < i1; i++) {
       const unsigned long long k = s_key[i];
       if (k == KEY_NONE) break;

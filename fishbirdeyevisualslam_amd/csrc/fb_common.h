@@ -180,6 +180,26 @@ inline void stage(Stager &st, fb_feature_vector &d, size_t n) {
   st.in(d.items, n * (size_t)d.item_stride * 4);
 }
 
+// v of the lane selected by the DPP control, +0.0 where there is none
+template <int CTRL>
+__device__ __forceinline__ double dpp_f64(double v) {
+  int lo = __double2loint(v), hi = __double2hiint(v);
+  lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xF, 0xF, true);
+  hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xF, 0xF, true);
+  return __hiloint2double(hi, lo);
+}
+
+// fp64 reciprocal from the hardware seed (v_rcp_f64) and two Newton steps: 6 instead of the ~35 dependent instructions of
+// the IEEE division sequence, relative error < 2^-50.  Only where the result is held to a tolerance (the LM evaluations of
+// the pose optimisation, the pivots of the BA's reduced pose system: 1e-4), never where a decision needs the true quotient.
+// Written with explicit fma so that the text means the same under every -ffp-contract setting.
+__device__ __forceinline__ double rcp_f64_newton(double x) {
+  double r = __builtin_amdgcn_rcp(x);
+  r = fma(fma(-x, r, 1.0), r, r);
+  r = fma(fma(-x, r, 1.0), r, r);
+  return r;
+}
+
 // Column sums of up to 32 per-lane values over the 64 lanes as a reduce-scatter butterfly: at the step with mask m a
 // lane sends one half of its values to lane^m, keeps the other half and adds what it receives, so the value count halves
 // every step (16 + 8 + 4 + 2 + 1 + 1 = 32 fp64 exchanges instead of 6 per value).  On return v[0] of lane L is the sum
@@ -208,6 +228,13 @@ __device__ __forceinline__ double wave_column_sums32(double (&v)[32], int lane) 
     }
   }
   return v[0] + __shfl_xor(v[0], 1, 64);
+}
+
+// a 32-byte descriptor row (16-byte aligned) as 8 dwords
+__device__ __forceinline__ void load_desc(const uint8_t *p, uint32_t d[8]) {
+  const uint4 *q = reinterpret_cast<const uint4 *>(p);
+  const uint4 a = q[0], b = q[1];
+  d[0] = a.x; d[1] = a.y; d[2] = a.z; d[3] = a.w; d[4] = b.x; d[5] = b.y; d[6] = b.z; d[7] = b.w;
 }
 
 // 256-bit Hamming distance of two 32-byte rows given as 8 dwords each

@@ -10,6 +10,7 @@
 // construction, no LDS needed.  Per-problem constants (pose, camera centre) sit in SGPRs via uniform loads.
 #include "fb_common.h"
 #include "fb_frame_geom.h"
+#include "fb_primitives.h"
 
 namespace {
 
@@ -88,28 +89,6 @@ __global__ __launch_bounds__(FRAME_THREADS) void k_undistort(const fb_keypoint *
 // ---- Frame::GuidenceKeyBirdPts (Frame.cc:671-739) ------------------------------------------------------------------
 constexpr int GUIDE_THREADS = 1024;
 
-__device__ __forceinline__ int wave_incl_scan_i(int v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(v, o, 64);
-    if (lane >= o) v += t;
-  }
-  return v;
-}
-// exclusive scan of one int per thread over the 1024-thread block (s_w: 16 ints); *total = block sum
-__device__ __forceinline__ int block_excl_scan1024(int v, int *s_w, int *total) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int inc = wave_incl_scan_i(v);
-  __syncthreads();
-  if (lane == 63) s_w[wv] = inc;
-  __syncthreads();
-  int base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < GUIDE_THREADS / 64; w++) { const int x = s_w[w]; if (w < wv) base += x; tot += x; }
-  *total = tot;
-  return base + inc - v;
-}
 
 // One workgroup per bird image.  Phase A: 32 lanes per key point, one lane per contour ROW of its box (the box has at
 // most 21 rows: trunc(x-10) .. ceil(x+10)-1), each lane walks its <= 21 contiguous bytes; the verdict is the OR over the
@@ -158,7 +137,7 @@ __global__ __launch_bounds__(GUIDE_THREADS) void k_bird_guidance(fb_bird_guidanc
   int cnt = 0;
   for (int i = i0; i < i1; i++) cnt += s_keep[i];
   int total;
-  int o = block_excl_scan1024(cnt, s_w, &total);
+  int o = fb::block_excl_scan<GUIDE_THREADS>(cnt, s_w, &total);
   for (int i = i0; i < i1; i++) {
     if (!s_keep[i]) continue;
     A.kps_out[ko + o] = A.kps_in[ko + i];
@@ -242,7 +221,7 @@ __global__ __launch_bounds__(GUIDE_THREADS) void k_bird_compact(fb_bird_guidance
   int cnt = 0;
   for (int i = i0; i < i1; i++) cnt += A.keep[ko + i];
   int total;
-  int o = block_excl_scan1024(cnt, s_w, &total);
+  int o = fb::block_excl_scan<GUIDE_THREADS>(cnt, s_w, &total);
   for (int i = i0; i < i1; i++) {
     if (!A.keep[ko + i]) continue;
     A.kps_out[ko + o] = A.kps_in[ko + i];
@@ -276,8 +255,8 @@ __global__ __launch_bounds__(GUIDE_THREADS) void k_bird_edges(fb_bird_guidance_a
     }
   }
   int ts, tf;
-  int os = block_excl_scan1024(ns, s_w, &ts);
-  int of = block_excl_scan1024(nf, s_w, &tf);
+  int os = fb::block_excl_scan<GUIDE_THREADS>(ns, s_w, &ts);
+  int of = fb::block_excl_scan<GUIDE_THREADS>(nf, s_w, &tf);
   float *es = A.edge_sign + (size_t)b * A.edge_cap * 2, *ef = A.edge_free + (size_t)b * A.edge_cap * 2;
   {
     int row = p0 / A.cols, col = p0 - row * A.cols;

@@ -14,7 +14,7 @@
 // the list order, so k_kfdb_score runs between the two on every listed key frame above the common-word threshold.
 // The double sum of a score is added in ascending word order on one accumulator (the order of the additions is the result).
 #include "fb_common.h"
-#include "fb_sort_scan.h"
+#include "fb_primitives.h"
 
 #include <algorithm>
 
@@ -112,8 +112,9 @@ __global__ __launch_bounds__(256) void k_kfdb_count(Db D, int mode, unsigned lon
         const uint32_t wid = row[w];
         if (find_id(s_q, nq, wid) >= 0) { c++; mn = min(mn, wid); }
       }
+      c = fb::wave_sum(c);
 #pragma unroll
-      for (int o = 32; o > 0; o >>= 1) { c += __shfl_xor(c, o, 64); mn = min(mn, (uint32_t)__shfl_xor((int)mn, o, 64)); }
+      for (int o = 32; o > 0; o >>= 1) mn = min(mn, (uint32_t)__shfl_xor((int)mn, o, 64));
       if (c > 0) {
         const bool fresh = D.query[mode][kf] != id;
         bool connected = false;
@@ -203,8 +204,7 @@ __global__ __launch_bounds__(KF_SEL_T) void k_kfdb_select(Db D, fb_kfdb_query_ar
     s_best[p] = best;
   }
   for (int i = tid; i < K; i += nt) __hip_atomic_store(&D.first[i], INT_MAX, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { const float t = __shfl_xor(lmax, o, 64); if (t > lmax) lmax = t; }
+  lmax = fb::wave_max(lmax);
   if ((tid & 63) == 0) s_mx[tid >> 6] = lmax;
   if (nsc) atomicAdd(&s_nscored, nsc);
   __syncthreads();

@@ -26,12 +26,13 @@
 
 #include <type_traits>
 #include "fb_frame_geom.h"
+#include "fb_primitives.h"
+#include "fb_rot_hist.h"
 
 namespace {
 
 constexpr int TH_HIGH = 100;      // ORBmatcher.cc:38
 constexpr int TH_LOW = 50;        // :39
-constexpr int HISTO_LENGTH = 30;  // :40
 constexpr int NONE = 0x7fffffff;
 constexpr int MATCH_THREADS = 1024;
 
@@ -141,27 +142,7 @@ __device__ __forceinline__ void for_area(const fb_grid_geom &g, const TargetLds 
   flush();
 }
 
-__device__ __forceinline__ int rot_bin(float rot) {  // ORBmatcher.cc:1434-1439
-  const float factor = 1.0f / HISTO_LENGTH;
-  if (rot < 0.0f) rot += 360.0f;
-  int bin = (int)roundf(rot * factor);
-  if (bin == HISTO_LENGTH) bin = 0;
-  return bin;
-}
-
-// ComputeThreeMaxima, ORBmatcher.cc:1905-1946
-__device__ void three_maxima(const int *sz, int &ind1, int &ind2, int &ind3) {
-  int max1 = 0, max2 = 0, max3 = 0;
-  ind1 = ind2 = ind3 = -1;
-  for (int i = 0; i < HISTO_LENGTH; i++) {
-    const int s = sz[i];
-    if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-    else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-    else if (s > max3) { max3 = s; ind3 = i; }
-  }
-  if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-  else if (max3 < 0.1f * (float)max1) { ind3 = -1; }
-}
+using fb::rot_bin;
 
 __device__ __forceinline__ void xform(const float *T, const float *X, float *o) {  // rows 0..2 of a 3x4
 #pragma unroll
@@ -260,7 +241,8 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_proj_frame(fb_proj_frame_args
   u16 *assignB = assignA + A.last_stride;                // [last_stride]
   u16 *perm = assignB + A.last_stride;                   // [last_stride] queries sorted by octave (processing order)
   uint8_t *meta = reinterpret_cast<uint8_t *>(perm + A.last_stride);  // [last_stride] cached count | complete << 7
-  __shared__ int s_changed, s_n, s_hist[HISTO_LENGTH], s_ind[3], s_oct[FB_MAX_LEVELS + 1];
+  __shared__ int s_changed, s_n, s_oct[FB_MAX_LEVELS + 1];
+  __shared__ fb::RotHist s_rot;
   __shared__ float s_T[12];
   if (tid < 12) s_T[tid] = A.cur_Tcw[(size_t)b * 12 + tid];
   if (tid <= FB_MAX_LEVELS) s_oct[tid] = 0;
@@ -398,7 +380,7 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_proj_frame(fb_proj_frame_args
   int *matchL = ownerB;  // reuse
   u16 *binQ = assignB;   // reuse: histogram bin of each accepted query
   for (int i = tid; i < ncur; i += nt) matchL[i] = -1;
-  if (tid < HISTO_LENGTH) s_hist[tid] = 0;
+  s_rot.clear();
   if (tid == 0) s_n = 0;
   __syncthreads();
   const bool ori = A.matcher.check_orientation != 0;
@@ -409,19 +391,18 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_proj_frame(fb_proj_frame_args
     atomicAdd(&s_n, 1);
     if (ori) {
       const int bin = rot_bin(A.last_angle[lo + q] - A.cur_kps[co + c].angle);
-      atomicAdd(&s_hist[bin], 1);
+      s_rot.add(bin);
       binQ[q] = (u16)bin;
     }
   }
   __syncthreads();
   if (ori) {
-    if (tid == 0) three_maxima(s_hist, s_ind[0], s_ind[1], s_ind[2]);
-    __syncthreads();
+    s_rot.pick();
     for (int q = tid; q < nlast; q += nt) {
       const int c = assignA[q];
       if (c == NONE16) continue;
       const int bin = binQ[q];
-      if (bin != s_ind[0] && bin != s_ind[1] && bin != s_ind[2]) {
+      if (!s_rot.keeps(bin)) {
         matchL[c] = -1;
         atomicSub(&s_n, 1);
       }
@@ -463,7 +444,8 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_proj_kf(fb_proj_kf_args A, in
   int *ownerB = ownerA + A.cur_stride;                   // [cur_stride]
   u16 *assignA = reinterpret_cast<u16 *>(ownerB + A.cur_stride);  // [kf_stride] chosen slot or NONE16
   u16 *assignB = assignA + A.kf_stride;                  // [kf_stride]
-  __shared__ int s_changed, s_n, s_hist[HISTO_LENGTH], s_ind[3];
+  __shared__ int s_changed, s_n;
+  __shared__ fb::RotHist s_rot;
   __shared__ float s_T[12], s_Ow[3];
   if (tid < 12) s_T[tid] = A.cur_Tcw[(size_t)b * 12 + tid];
   if (tid == 64) fb::camera_centre(A.cur_Tcw + (size_t)b * 12, s_Ow);
@@ -526,7 +508,7 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_proj_kf(fb_proj_kf_args A, in
   int *matchL = ownerB;
   u16 *binQ = assignB;
   for (int i = tid; i < ncur; i += nt) matchL[i] = -1;
-  if (tid < HISTO_LENGTH) s_hist[tid] = 0;
+  s_rot.clear();
   if (tid == 0) s_n = 0;
   __syncthreads();
   const bool ori = A.matcher.check_orientation != 0;
@@ -537,19 +519,18 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_proj_kf(fb_proj_kf_args A, in
     atomicAdd(&s_n, 1);
     if (ori) {
       const int bin = rot_bin(A.kf_angle[ko + q] - A.cur_kps[co + c].angle);
-      atomicAdd(&s_hist[bin], 1);
+      s_rot.add(bin);
       binQ[q] = (u16)bin;
     }
   }
   __syncthreads();
   if (ori) {
-    if (tid == 0) three_maxima(s_hist, s_ind[0], s_ind[1], s_ind[2]);
-    __syncthreads();
+    s_rot.pick();
     for (int q = tid; q < nkf; q += nt) {
       const int c = assignA[q];
       if (c == NONE16) continue;
       const int bin = binQ[q];
-      if (bin != s_ind[0] && bin != s_ind[1] && bin != s_ind[2]) {
+      if (!s_rot.keeps(bin)) {
         matchL[c] = -1;
         atomicSub(&s_n, 1);
       }
@@ -865,8 +846,9 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_birdview(fb_birdview_args A, 
                                    A.cur_cell_start + (size_t)b * (ncell + 1), A.cur_cell_items + co, descInLds != 0);
   int *m12 = reinterpret_cast<int *>(smem + cv.end);  // [ref_stride]
   int *bins = m12 + A.ref_stride;                      // [ref_stride] histogram bin of i1 or -1
-  __shared__ int s_n, s_nd, s_hist[HISTO_LENGTH], s_ind[3];
-  if (tid < HISTO_LENGTH) s_hist[tid] = 0;
+  __shared__ int s_n, s_nd;
+  __shared__ fb::RotHist s_rot;
+  s_rot.clear();
   if (tid == 0) { s_n = 0; s_nd = 0; }
   __syncthreads();
   const bool ori = A.matcher.check_orientation != 0;
@@ -875,9 +857,7 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_birdview(fb_birdview_args A, 
     const fb_keypoint kp1 = A.ref_kps[ro + i1];
     if (!(kp1.octave > 0)) {
       uint32_t d[8];
-      const uint4 *dq = reinterpret_cast<const uint4 *>(A.ref_desc + (ro + i1) * 32);
-      const uint4 d0 = dq[0], d1 = dq[1];
-      d[0] = d0.x; d[1] = d0.y; d[2] = d0.z; d[3] = d0.w; d[4] = d1.x; d[5] = d1.y; d[6] = d1.z; d[7] = d1.w;
+      fb::load_desc(A.ref_desc + (ro + i1) * 32, d);
       int bestDist = INT_MAX, bestDist2 = INT_MAX, bestIdx = -1;
       for_area<true>(A.grid, T, kp1.x, kp1.y, (float)A.window_size, kp1.octave, kp1.octave, [&](int i2) {
         if (i2 >= ncur) return;
@@ -889,7 +869,7 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_birdview(fb_birdview_args A, 
         if (bestDist < (float)bestDist2 * A.matcher.nnratio) { m = bestIdx; md = bestDist; atomicAdd(&s_n, 1); }
         if (ori) {  // pushed even when the ratio test failed, ORBmatcher.cc:1712-1722
           bin = rot_bin(kp1.angle - A.cur_kps[co + bestIdx].angle);
-          atomicAdd(&s_hist[bin], 1);
+          s_rot.add(bin);
         }
       }
     }
@@ -899,11 +879,10 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_birdview(fb_birdview_args A, 
   }
   __syncthreads();
   if (ori) {
-    if (tid == 0) three_maxima(s_hist, s_ind[0], s_ind[1], s_ind[2]);
-    __syncthreads();
+    s_rot.pick();
     for (int i1 = tid; i1 < nref; i1 += nt) {
       const int bin = bins[i1];
-      if (bin < 0 || bin == s_ind[0] || bin == s_ind[1] || bin == s_ind[2]) continue;
+      if (bin < 0 || s_rot.keeps(bin)) continue;
       if (m12[i1] >= 0) { m12[i1] = -1; atomicSub(&s_n, 1); }
     }
     __syncthreads();
@@ -945,7 +924,7 @@ __global__ __launch_bounds__(256) void k_grid_build(const fb_keypoint *__restric
   // the items are scattered, sorted per cell and written out from LDS (itemsInLds): the per-cell insertion sort on the
   // global array was a chain of dependent global accesses per cell, 12 cells per lane -- most of this kernel at batch 1
   int *li = fillp + ncell;                   // [kp_stride] when itemsInLds
-  __shared__ int s_part[256];
+  __shared__ int s_part[256 / 64];
   const fb_keypoint *k = kps + (size_t)b * kp_stride;
   int32_t *cs = cell_start + (size_t)b * (ncell + 1);
   int32_t *cig = cell_items + (size_t)b * kp_stride;
@@ -971,20 +950,10 @@ __global__ __launch_bounds__(256) void k_grid_build(const fb_keypoint *__restric
   for (int c = c0; c < c1; c++) s += cnt[c];
   // exclusive scan of the 256 chunk sums: shuffles inside a wave, four wave totals through LDS (one lane walking the 256
   // partials in LDS was half of this kernel at batch 1)
-  int run;
-  {
-    const int lane = tid & 63, wv = tid >> 6;
-    int inc = s;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
-    if (lane == 63) s_part[wv] = inc;
-    __syncthreads();
-    int base = 0, tot = 0;
-    for (int w = 0; w < (nt >> 6); w++) { const int x = s_part[w]; if (w < wv) base += x; tot += x; }
-    run = base + inc - s;
-    if (tid == 0) cnt[ncell] = tot;
-    __syncthreads();
-  }
+  int tot;
+  int run = fb::block_excl_scan<256>(s, s_part, &tot);
+  if (tid == 0) cnt[ncell] = tot;
+  __syncthreads();
   for (int c = c0; c < c1; c++) { const int v = cnt[c]; cnt[c] = run; fillp[c] = run; run += v; }
   __syncthreads();
   for (int i = tid; i < nk; i += nt) {

@@ -11,11 +11,14 @@
 // M5 is greedy in keyframe-feature order (a frame feature that already received a MapPoint is skipped,
 // :210): resolved with the same fixed-point iteration as M2/M3 (see match.hip), claims here always block.
 #include "fb_common.h"
+#include "fb_rot_hist.h"
 
 namespace {
 
+using fb::load_desc;
+using fb::rot_bin;
+
 constexpr int TH_LOW = 50;        // ORBmatcher.cc:39
-constexpr int HISTO_LENGTH = 30;  // :40
 constexpr int NONE = 0x7fffffff;
 constexpr int BOW_THREADS = 1024;
 
@@ -54,33 +57,6 @@ __device__ __forceinline__ int find_node(const FVd &v, uint32_t id) {  // exact 
   return (lo < v.n && v.ids[lo] == id) ? lo : -1;
 }
 
-__device__ __forceinline__ int rot_bin(float rot) {  // ORBmatcher.cc:237-243
-  const float factor = 1.0f / HISTO_LENGTH;
-  if (rot < 0.0f) rot += 360.0f;
-  int bin = (int)roundf(rot * factor);
-  if (bin == HISTO_LENGTH) bin = 0;
-  return bin;
-}
-
-__device__ void three_maxima(const int *sz, int &ind1, int &ind2, int &ind3) {  // ORBmatcher.cc:1905-1946
-  int max1 = 0, max2 = 0, max3 = 0;
-  ind1 = ind2 = ind3 = -1;
-  for (int i = 0; i < HISTO_LENGTH; i++) {
-    const int s = sz[i];
-    if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-    else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-    else if (s > max3) { max3 = s; ind3 = i; }
-  }
-  if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-  else if (max3 < 0.1f * (float)max1) { ind3 = -1; }
-}
-
-__device__ __forceinline__ void load_desc(const uint8_t *p, uint32_t d[8]) {
-  const uint4 *q = reinterpret_cast<const uint4 *>(p);
-  const uint4 a = q[0], b = q[1];
-  d[0] = a.x; d[1] = a.y; d[2] = a.z; d[3] = a.w; d[4] = b.x; d[5] = b.y; d[6] = b.z; d[7] = b.w;
-}
-
 // ---------------------------------------------------------------------------------------------------------
 // KFKF = false: M5 (keyframe -> frame).  KFKF = true: M6, SearchByBoW(pKF1, pKF2) (ORBmatcher.cc:523-656): the
 // candidate side must carry a good MapPoint (:575-581), the distance test is strict (:598) and the result is
@@ -101,7 +77,8 @@ __global__ __launch_bounds__(BOW_THREADS) void k_match_bow_t(fb_bow_args A, cons
   int *assignA = ownerB + A.f_stride;                                // [kf item_stride]
   int *assignB = assignA + A.kf_fv.item_stride;
   int *fitems = assignB + A.kf_fv.item_stride;                       // [f item_stride] F.mFeatVec's items: walked by every query in every round
-  __shared__ int s_changed, s_n, s_hist[HISTO_LENGTH], s_ind[3];
+  __shared__ int s_changed, s_n;
+  __shared__ fb::RotHist s_rot;
   {
     const int nFi = F.n > 0 ? min(F.start[F.n], A.f_fv.item_stride) : 0;
     for (int i = tid; i < nFi; i += nt) fitems[i] = F.items[i];
@@ -189,7 +166,7 @@ __global__ __launch_bounds__(BOW_THREADS) void k_match_bow_t(fb_bow_args A, cons
   }
   int *matchL = ownerB;
   for (int i = tid; i < nF; i += nt) matchL[i] = -1;
-  if (tid < HISTO_LENGTH) s_hist[tid] = 0;
+  s_rot.clear();
   if (tid == 0) s_n = 0;
   __syncthreads();
   const bool ori = A.matcher.check_orientation != 0;
@@ -201,19 +178,18 @@ __global__ __launch_bounds__(BOW_THREADS) void k_match_bow_t(fb_bow_args A, cons
     atomicAdd(&s_n, 1);
     if (ori) {
       const int bin = rot_bin(A.kf_kps[ko + realIdxKF].angle - A.f_kps[fo + c].angle);
-      atomicAdd(&s_hist[bin], 1);
+      s_rot.add(bin);
       assignB[q] = bin;
     }
   }
   __syncthreads();
   if (ori) {
-    if (tid == 0) three_maxima(s_hist, s_ind[0], s_ind[1], s_ind[2]);
-    __syncthreads();
+    s_rot.pick();
     for (int q = tid; q < nQ; q += nt) {
       const int c = assignA[q];
       if (c == NONE) continue;
       const int bin = assignB[q];
-      if (bin != s_ind[0] && bin != s_ind[1] && bin != s_ind[2]) { matchL[c] = -1; atomicSub(&s_n, 1); }
+      if (!s_rot.keeps(bin)) { matchL[c] = -1; atomicSub(&s_n, 1); }
     }
     __syncthreads();
   }
@@ -246,7 +222,8 @@ __global__ __launch_bounds__(BOW_THREADS) void k_match_triangulation(fb_triangul
   float4 *k2 = reinterpret_cast<float4 *>(smem + descBytes);                         // x, y, angle, octave
   int *m12 = reinterpret_cast<int *>(smem + descBytes + (size_t)A.kf2_stride * 16);  // [kf1_stride]
   int *bins = m12 + A.kf1_stride;                                                    // [kf1_stride]
-  __shared__ int s_n, s_hist[HISTO_LENGTH], s_ind[3];
+  __shared__ int s_n;
+  __shared__ fb::RotHist s_rot;
   __shared__ float s_e[2], s_F[9];
   {
     if (descInLds) {
@@ -260,7 +237,7 @@ __global__ __launch_bounds__(BOW_THREADS) void k_match_triangulation(fb_triangul
     }
   }
   for (int i = tid; i < n1; i += nt) { m12[i] = -1; bins[i] = -1; }
-  if (tid < HISTO_LENGTH) s_hist[tid] = 0;
+  s_rot.clear();
   if (tid < 9) s_F[tid] = A.F12[(size_t)b * 9 + tid];
   if (tid == 0) {
     s_n = 0;
@@ -308,17 +285,16 @@ __global__ __launch_bounds__(BOW_THREADS) void k_match_triangulation(fb_triangul
       if (ori) {
         const int bin = rot_bin(kp1.angle - k2[bestIdx2].z);
         bins[idx1] = bin;
-        atomicAdd(&s_hist[bin], 1);
+        s_rot.add(bin);
       }
     }
   }
   __syncthreads();
   if (ori) {
-    if (tid == 0) three_maxima(s_hist, s_ind[0], s_ind[1], s_ind[2]);
-    __syncthreads();
+    s_rot.pick();
     for (int i = tid; i < n1; i += nt) {
       const int bin = bins[i];
-      if (bin >= 0 && bin != s_ind[0] && bin != s_ind[1] && bin != s_ind[2]) { m12[i] = -1; atomicSub(&s_n, 1); }
+      if (bin >= 0 && !s_rot.keeps(bin)) { m12[i] = -1; atomicSub(&s_n, 1); }
     }
     __syncthreads();
   }

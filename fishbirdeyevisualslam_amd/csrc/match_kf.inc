@@ -46,12 +46,6 @@ __device__ __forceinline__ bool is_in_image(const fb_camera &c, float x, float y
   return x >= c.min_x && x < c.max_x && y >= c.min_y && y < c.max_y;
 }
 
-__device__ __forceinline__ void load_desc8(const uint8_t *p, uint32_t d[8]) {
-  const uint4 *q = reinterpret_cast<const uint4 *>(p);
-  const uint4 a = q[0], b = q[1];
-  d[0] = a.x; d[1] = a.y; d[2] = a.z; d[3] = a.w; d[4] = b.x; d[5] = b.y; d[6] = b.z; d[7] = b.w;
-}
-
 // geometric gates of :843-889 / :1007-1047 / :317-357 for one map point; level < 0 = rejected
 template <int MODE>
 __device__ __forceinline__ int gate_point(const fb_kf_target &K, const float *T, const float *Ow, const fb_mp_list &M,
@@ -83,7 +77,7 @@ __device__ __forceinline__ int search_point(const fb_kf_target &K, const TargetL
                                             int lvl, float th, Blocked blocked) {
   const float radius = th * K.scale_factors[lvl];
   uint32_t d[8];
-  load_desc8(mp_desc, d);
+  fb::load_desc(mp_desc, d);
   int bestDist = MODE == MODE_FUSE_SIM3 ? INT_MAX : 256, best = NONE;
   for_area<false>(K.grid, T, u, v, radius, -1, -1, [&](int idx) {
     if (blocked(idx)) return;
@@ -221,7 +215,7 @@ __device__ __forceinline__ void sim3_direction(const fb_kf_target &Kt, const Tar
             const int lvl = fb::predict_scale(maxD, dist3D, Kt.log_scale_factor, Kt.n_levels);
             const float radius = th * Kt.scale_factors[lvl];
             uint32_t d[8];
-            load_desc8(M.mp_desc + (mo + q) * 32, d);
+            fb::load_desc(M.mp_desc + (mo + q) * 32, d);
             int bestDist = INT_MAX;
             for_area<false>(Kt.grid, T, u, v, radius, -1, -1, [&](int idx) {
               const int oct = T.oct[idx];
@@ -310,7 +304,8 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_init_match(fb_init_match_args
   u16 *assignB = assignA + A.f1_stride;
   u16 *distA = assignB + A.f1_stride;                   // [f1_stride] accepted distance
   u16 *distB = distA + A.f1_stride;
-  __shared__ int s_changed, s_n, s_hist[HISTO_LENGTH], s_ind[3];
+  __shared__ int s_changed, s_n;
+  __shared__ fb::RotHist s_rot;
   for (int i = tid; i < n2; i += nt) headA[i] = -1;
   for (int q = tid; q < n1; q += nt) { assignA[q] = NONE16; distA[q] = 0; nextA[q] = NONE16; }
   __syncthreads();
@@ -324,7 +319,7 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_init_match(fb_init_match_args
       const fb_keypoint kp1 = A.kps1[o1 + q];
       if (!(kp1.octave > 0)) {
         uint32_t d[8];
-        load_desc8(A.desc1 + (o1 + q) * 32, d);
+        fb::load_desc(A.desc1 + (o1 + q) * 32, d);
         for_area<false>(A.grid, T, prev[q * 2], prev[q * 2 + 1], (float)A.window_size, kp1.octave, kp1.octave, [&](int i2) {
           const int dist = target_hamming(T, d, i2);
           // vMatchedDistance[i2] just before q = min accepted distance of earlier queries on i2
@@ -355,7 +350,7 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_init_match(fb_init_match_args
   int *last = headB;  // [n2] largest accepted query
   u16 *bins = nextB;  // [n1] histogram bin, NONE16 = not pushed
   for (int i = tid; i < n2; i += nt) last[i] = -1;
-  if (tid < HISTO_LENGTH) s_hist[tid] = 0;
+  s_rot.clear();
   if (tid == 0) s_n = 0;
   __syncthreads();
   const bool ori = A.matcher.check_orientation != 0;
@@ -366,13 +361,12 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_init_match(fb_init_match_args
     atomicMax(&last[c], q);
     if (ori) {
       const int bin = rot_bin(A.kps1[o1 + q].angle - A.kps2[o2 + c].angle);
-      atomicAdd(&s_hist[bin], 1);
+      s_rot.add(bin);
       bins[q] = (u16)bin;
     }
   }
   __syncthreads();
-  if (ori && tid == 0) three_maxima(s_hist, s_ind[0], s_ind[1], s_ind[2]);
-  __syncthreads();
+  if (ori) s_rot.pick(); else __syncthreads();
   float *prevw = A.prev_matched + o1 * 2;
   for (int q = tid; q < n1; q += nt) {
     const int c = assignA[q];
@@ -381,7 +375,7 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_init_match(fb_init_match_args
       m = c;
       if (ori) {
         const int bin = bins[q];
-        if (bin != s_ind[0] && bin != s_ind[1] && bin != s_ind[2]) m = -1;
+        if (!s_rot.keeps(bin)) m = -1;
       }
     }
     A.matches12[o1 + q] = m;

@@ -20,6 +20,7 @@
 // those of oracle/orb_oracle.cpp; this file must agree with it bit for bit.
 #include "fb_common.h"
 #include "fb_fast_score.h"
+#include "fb_primitives.h"
 
 namespace {
 
@@ -383,43 +384,6 @@ __device__ __forceinline__ uint32_t fast_score16x2(const uint8_t *__restrict__ c
 #pragma unroll
   for (int i = 0; i < 16; i++) d[i] = Ops::sub(v, fbscore::pk_pair(c0[ctr + fbscore::ring_offset(i, TP)], c1[ctr + fbscore::ring_offset(i, TP)]));
   return fbscore::score_network<Ops>(d);
-}
-
-__device__ __forceinline__ int wave_incl_scan(int v) {  // inclusive scan over the 64 lanes
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(v, o, 64);
-    if ((int)(threadIdx.x & 63) >= o) v += t;
-  }
-  return v;
-}
-
-// exclusive scan of one int per thread over an NT-thread block; *total = block sum
-template <int NT>
-__device__ __forceinline__ int block_excl_scan(int v, int *s_w /*[NT / 64]*/, int *total) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int inc = wave_incl_scan(v);
-  __syncthreads();
-  if (lane == 63) s_w[wv] = inc;
-  __syncthreads();
-  int base = 0, tot = 0;
-#pragma unroll
-  for (int i = 0; i < NT / 64; i++) { if (i < wv) base += s_w[i]; tot += s_w[i]; }
-  *total = tot;
-  return base + inc - v;
-}
-
-// exclusive scan of one int per thread over a 256-thread block; *total = block sum
-__device__ __forceinline__ int block_excl_scan256(int v, int *s_w /*[4]*/, int *total) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int inc = wave_incl_scan(v);
-  __syncthreads();
-  if (lane == 63) s_w[wv] = inc;
-  __syncthreads();
-  int base = 0;
-  for (int i = 0; i < wv; i++) base += s_w[i];
-  *total = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-  return base + inc - v;
 }
 
 // inclusive scan over the 64 lanes in the VALU (DPP row shifts, then the row broadcasts of gfx9)
@@ -864,7 +828,7 @@ __global__ __launch_bounds__(NT) void k_octree(OrbK K, const uint32_t *__restric
       const int c = c0 + tid;
       const int v = c < ncell ? cc[c] : 0;
       int tot;
-      const int ex = block_excl_scan<NT>(v, s_w, &tot);
+      const int ex = fb::block_excl_scan<NT>(v, s_w, &tot);
       if (c < ncell) offs[c] = run + ex;
       run += tot;
       __syncthreads();  // s_w is reused by the next chunk
@@ -1009,8 +973,8 @@ __global__ __launch_bounds__(NT) void k_octree(OrbK K, const uint32_t *__restric
       for (int p = a0; p < a1; p++) if (!split[p]) myKeep++;
     }
     int totalKids, totalKeep;
-    const int kidsBefore = block_excl_scan<NT>(myKids, s_w, &totalKids);
-    const int keepBefore = block_excl_scan<NT>(myKeep, s_w, &totalKeep);
+    const int kidsBefore = fb::block_excl_scan<NT>(myKids, s_w, &totalKids);
+    const int keepBefore = fb::block_excl_scan<NT>(myKeep, s_w, &totalKeep);
     // children created before mine: kidsBefore -> my first child has creation index kidsBefore,
     // list position = totalKids-1-creationIndex
     {
@@ -1073,7 +1037,7 @@ __global__ __launch_bounds__(NT) void k_octree(OrbK K, const uint32_t *__restric
       for (int p = n0; p < n1; p++) myExp += (p < totalKids && nxt[p].cnt > 1);
     }
     int nToExpand;
-    block_excl_scan<NT>(myExp, s_w, &nToExpand);
+    fb::block_excl_scan<NT>(myExp, s_w, &nToExpand);
     if (tid == 0) s_nexp = nToExpand;
     __syncthreads();
     ONode *t = cur; cur = nxt; nxt = t;
@@ -1384,8 +1348,8 @@ __global__ __launch_bounds__(64 * DESC_WPB) void k_describe(OrbK K, const uint8_
       m10 = half ? (int)a10 : -(int)a10;
       m01 = __mul24(r - 15, (int)rs);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { m10 += __shfl_xor(m10, o, 64); m01 += __shfl_xor(m01, o, 64); }
+    m10 = fb::wave_sum(m10);
+    m01 = fb::wave_sum(m01);
     if (K.dbg == 12) { if (m10 + m01 == 12345678 && (int)(pp[0].x + pp[1].y + pp[2].z + pp[3].w) == 77777) nOut[0] = 1; continue; }
     const float angle = fb_fast_atan2((float)m01, (float)m10);
     // computeOrbDescriptor (ORBextractor.cc:107-147): lane computes tests 4*lane .. 4*lane+3

@@ -20,6 +20,7 @@
 // like g2o; inputs/outputs are float like the reference's cv::Mat fields.
 #include <type_traits>
 #include "fb_common.h"
+#include "fb_primitives.h"
 #include "fb_se3.h"
 
 namespace {
@@ -48,11 +49,7 @@ struct PoseLds {  // fixed-size shared state
   int ok2;
 };
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
+using fb::wave_sum;
 
 struct EdgeView {  // staged (LDS) or global float arrays of one problem
   const float *fxw, *fobs, *finf;
@@ -447,23 +444,13 @@ __global__ __launch_bounds__(256) void k_pose_opt(fb_pose_opt_args A, int staged
 //    sit in adjacent lanes and are combined with DPP row shifts (VALU moves, no LDS crossbar);
 //  * the update T <- exp(x) T is formed directly on the quaternion (no rotation matrix, one reciprocal square root per
 //    normalisation).
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64(double v) {  // v of the lane selected by the DPP control, +0.0 where there is none
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xF, 0xF, true);
-  hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xF, 0xF, true);
-  return __hiloint2double(hi, lo);
-}
+using fb::dpp_f64;
 
-// fp64 reciprocal / reciprocal square root from the hardware seed (v_rcp_f64 / v_rsq_f64) and two Newton steps: 6 instead
-// of the ~35 dependent instructions of the IEEE division sequence, relative error < 2^-50.  Only for the tolerance-held
-// LM evaluations (pose within 1e-4); the inlier / outlier decision keeps true quotients (chi2_*_vals).
-__device__ __forceinline__ double rcp_fast(double x) {
-  double r = __builtin_amdgcn_rcp(x);
-  r = fma(fma(-x, r, 1.0), r, r);
-  r = fma(fma(-x, r, 1.0), r, r);
-  return r;
-}
+using fb::rcp_f64_newton;
+
+// fp64 reciprocal square root from the hardware seed (v_rsq_f64) and two Newton steps, the companion of rcp_f64_newton.
+// Only for the tolerance-held LM evaluations (pose within 1e-4); the inlier / outlier decision keeps true quotients
+// (chi2_*_vals).
 __device__ __forceinline__ double rsqrt_fast(double x) {
   double r = __builtin_amdgcn_rsq(x);
   r = r * fma(-0.5 * x, r * r, 1.5);
@@ -502,7 +489,7 @@ __device__ __forceinline__ void quat_normalize_fast(fb::Quat &q) {  // normalize
   q.x *= inv; q.y *= inv; q.z *= inv; q.w *= inv;
 }
 
-// fb::ldlt6 with the pivots' reciprocals from rcp_fast (this routine is one lane's serial work inside every LM trial)
+// fb::ldlt6 with the pivots' reciprocals from rcp_f64_newton (this routine is one lane's serial work inside every LM trial)
 __device__ __forceinline__ bool ldlt6_fast(const double H[36], double lambda, const double b[6], double x[6]) {
   double A[36], d[6], dinv[6], y[6];
 #pragma unroll
@@ -517,7 +504,7 @@ __device__ __forceinline__ bool ldlt6_fast(const double H[36], double lambda, co
     for (int k = 0; k < j; k++) dj -= A[j * 6 + k] * A[j * 6 + k] * d[k];
     if (dj < 0) ok = false;
     d[j] = dj;
-    const double inv = dj != 0 ? rcp_fast(dj) : 0.0;
+    const double inv = dj != 0 ? rcp_f64_newton(dj) : 0.0;
     dinv[j] = inv;
 #pragma unroll
     for (int i = j + 1; i < 6; i++) {
@@ -556,7 +543,7 @@ __device__ __forceinline__ fb::SE3 se3_exp_direct(const double u[6]) {
   if (theta < 0.00001) return fb::se3_exp(u);
   double sh, ch;
   sincos_small(0.5 * theta, &sh, &ch);
-  const double it = rcp_fast(theta), it2 = it * it;
+  const double it = rcp_f64_newton(theta), it2 = it * it;
   const double k = sh * it;
   fb::SE3 T;
   T.r.x = wx * k; T.r.y = wy * k; T.r.z = wz * k; T.r.w = ch;
@@ -588,7 +575,7 @@ __device__ __forceinline__ void front_edge_acc(const fb::SE3 &T, float x0, float
   const double Xw[3] = {x0, x1, x2};
   double p[3];
   fb::se3_map(T, Xw, p);
-  const double X = p[0], Y = p[1], invz = rcp_fast(p[2]), invz_2 = invz * invz;
+  const double X = p[0], Y = p[1], invz = rcp_f64_newton(p[2]), invz_2 = invz * invz;
   const double err[2] = {(double)o0 - ((X * invz) * fx + cx), (double)o1 - ((Y * invz) * fy + cy)};
   const double J[2][6] = {{X * Y * invz_2 * fx, -(1 + (X * X * invz_2)) * fx, Y * invz * fx, -invz * fx, 0, X * invz_2 * fx},
                           {(1 + Y * Y * invz_2) * fy, -X * Y * invz_2 * fy, -X * invz * fy, 0, -invz * fy, Y * invz_2 * fy}};

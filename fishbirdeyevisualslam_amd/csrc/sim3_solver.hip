@@ -22,7 +22,7 @@
 // quaternion in double, rounded once to float (the same rotation).  den == 0, |vec| == 0 and z == 0 give
 // inf / NaN as in the reference, and every comparison with them is false.
 #include "fb_common.h"
-#include "fb_sort_scan.h"
+#include "fb_primitives.h"
 
 #include <algorithm>
 #include <atomic>

@@ -16,6 +16,7 @@
 // per frame (17 + the extractor's), so commits ride in the kernel that follows them.
 #include "fb_common.h"
 #include "fb_frame_geom.h"
+#include "fb_primitives.h"
 
 #include <cmath>
 #include <new>
@@ -211,33 +212,6 @@ __global__ __launch_bounds__(TT) void k_edges(FrameDev F, MapDev map, BirdMapDev
   }
 }
 
-__device__ __forceinline__ int block_sum(int v, int *s_w) {  // sum over a WG-thread block; every thread gets it
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
-  __syncthreads();
-  int t = 0;
-  for (int w = 0; w < WG / 64; w++) t += s_w[w];
-  return t;
-}
-__device__ __forceinline__ int wave_incl_scan(int v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(v, o, 64); if (lane >= o) v += t; }
-  return v;
-}
-__device__ __forceinline__ int block_excl_scan(int v, int *s_w, int *total) {  // WG threads
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int inc = wave_incl_scan(v);
-  __syncthreads();
-  if (lane == 63) s_w[wv] = inc;
-  __syncthreads();
-  int base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < WG / 64; w++) { const int x = s_w[w]; if (w < wv) base += x; tot += x; }
-  *total = tot;
-  return base + inc - v;
-}
 
 // "Discard outliers" of TrackWithMotionModel (Tracking.cc:1358-1376): one workgroup per sequence
 // and of TrackReferenceKeyFrame (:1222-1241); src_slot = the matcher count nmatches starts from; gate_min > 0: a sequence
@@ -254,8 +228,8 @@ __global__ __launch_bounds__(WG) void k_discard(FrameDev F, MapDev map, int32_t 
     if (F.outlier[o]) { F.mp[o] = -1; F.outlier[o] = 0; dropped++; }
     else if (map.obs_pos[(size_t)b * map.stride + id]) inmap++;
   }
-  dropped = block_sum(dropped, s_w);
-  inmap = block_sum(inmap, s_w);
+  dropped = fb::block_sum<WG>(dropped, s_w);
+  inmap = fb::block_sum<WG>(inmap, s_w);
   if (threadIdx.x == 0) {
     counts[FB_CNT_MATCHES * B + b] = counts[src_slot * B + b] - dropped;
     counts[FB_CNT_MATCHES_MAP * B + b] = inmap;
@@ -284,7 +258,7 @@ __global__ __launch_bounds__(WG) void k_bird_commit(FrameDev cur, FrameDev ref, 
     int have = 0;
     const int ncur = min(cur.nb[b], cap);
     for (int i = tid; i < ncur; i += WG) have += cur.mpb[fo + i] >= 0;
-    have = block_sum(have, s_w);
+    have = fb::block_sum<WG>(have, s_w);
     if (tid == 0) counts[FB_CNT_BIRD_POINTS * B + b] = have;
     if (have >= only_below) {
       if (tid == 0) counts[FB_CNT_BIRDVIEW_MATCHES * B + b] = 0;
@@ -316,8 +290,8 @@ __global__ __launch_bounds__(WG) void k_bird_commit(FrameDev cur, FrameDev ref, 
     if (ref.mpb[fo + i1] < 0) nnew++;
   }
   int totalNew;
-  int idBase = block_excl_scan(nnew, s_w, &totalNew);
-  const int totalKept = block_sum(nkept, s_w);
+  int idBase = fb::block_excl_scan<WG>(nnew, s_w, &totalNew);
+  const int totalKept = fb::block_sum<WG>(nkept, s_w);
   const int n0 = min(max(mpb.n[b], 0), mpb.stride);
   for (int i1 = i0; i1 < i1e; i1++) {
     const int t = m12[fo + i1];
@@ -351,7 +325,7 @@ __global__ __launch_bounds__(WG) void k_bird_commit(FrameDev cur, FrameDev ref, 
     int have = 0;
     const int ncur = min(cur.nb[b], cap);
     for (int i = tid; i < ncur; i += WG) have += cur.mpb[fo + i] >= 0;
-    have = block_sum(have, s_w);
+    have = fb::block_sum<WG>(have, s_w);
     if (tid == 0) counts[FB_CNT_BIRD_POINTS_FINAL * B + b] = have;
   }
 }
@@ -411,7 +385,7 @@ __global__ __launch_bounds__(WG) void k_local_points(FrameDev F, MapDev map, con
     }
     S.inview[lo + j] = v;
   }
-  toMatch = block_sum(toMatch, s_w);
+  toMatch = fb::block_sum<WG>(toMatch, s_w);
   if (tid == 0) { S.n_eff[b] = nl; counts[FB_CNT_TO_MATCH * B + b] = toMatch; }
 }
 
@@ -432,7 +406,7 @@ __global__ __launch_bounds__(WG) void k_finish(FrameDev F, MapDev map, int32_t *
     if (id < 0) continue;
     if (!F.outlier[o] && map.obs_pos[(size_t)b * map.stride + id] != 0) inl++;
   }
-  inl = block_sum(inl, s_w);
+  inl = fb::block_sum<WG>(inl, s_w);
   if (threadIdx.x == 0) counts[FB_CNT_MATCHES_INLIERS * B + b] = inl;
   if (inl < min_inliers) return;   // bOK = false: mState = LOST, the frame keeps its members (Tracking.cc:668-675)
   for (int i = threadIdx.x; i < n; i += WG) {
