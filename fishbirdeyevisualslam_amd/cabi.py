@@ -241,6 +241,15 @@ class KfdbQueryArgs(C.Structure):
                 ("common_words", _vp), ("scores", _vp)]
 
 
+FB_COVIS_MAX_STRIDE, FB_COVIS_TH = 32767, 15
+
+
+class CovisMap(C.Structure):
+    _fields_ = [("max_keyframes", _i32), ("kp_stride", _i32), ("kf_n", _vp), ("kf_mp", _vp), ("kf_octave", _vp),
+                ("n_mp", _i32), ("mp_bad", _vp), ("n_obs", _i32), ("obs_mp", _vp), ("obs_kf", _vp), ("obs_idx", _vp),
+                ("kf_order", _vp)]
+
+
 class BirdFilterArgs(C.Structure):
     _fields_ = [("batch", _i32), ("match_stride", _i32), ("kp1_stride", _i32), ("kp2_stride", _i32),
                 ("n_matches", _vp), ("query_idx", _vp), ("train_idx", _vp), ("cam_xyz1", _vp), ("cam_xyz2", _vp),
@@ -348,6 +357,11 @@ EXPORTS = [
     "fb_bird_filter_matches_dev", "fb_bird_filter_matches", "fb_bow_transform_dev", "fb_bow_transform",
     "fb_bow_score_dev", "fb_bow_score", "fb_kfdb_create", "fb_kfdb_destroy", "fb_kfdb_clear", "fb_kfdb_add_dev", "fb_kfdb_add",
     "fb_kfdb_add_frame_dev", "fb_kfdb_erase", "fb_kfdb_query_dev", "fb_kfdb_query", "fb_kfdb_min_score_dev", "fb_kfdb_min_score",
+    "fb_covis_create", "fb_covis_destroy", "fb_covis_clear", "fb_covis_reserve", "fb_covis_set_order_dev", "fb_covis_error_count",
+    "fb_covis_update_connections_dev", "fb_covis_update_connections", "fb_covis_add_connection_dev", "fb_covis_erase_connection_dev",
+    "fb_covis_erase_keyframe_dev", "fb_covis_ordered_dev", "fb_covis_ordered", "fb_covis_by_weight_dev", "fb_covis_by_weight",
+    "fb_covis_connected_dev", "fb_covis_connected", "fb_covis_weight_dev", "fb_covis_weight", "fb_covis_kfdb_rows_dev",
+    "fb_covis_kfdb_rows", "fb_covis_keyframe_culling_dev", "fb_covis_keyframe_culling",
     "fb_in_frustum_dev", "fb_in_frustum", "fb_undistort_keypoints_dev", "fb_undistort_keypoints", "fb_image_bounds",
     "fb_pose_opt_batch_dev", "fb_pose_opt", "fb_pose_gather_front_dev", "fb_pose_gather_bird_dev",
     "fb_frame_create", "fb_frame_destroy", "fb_frame_extract_dev", "fb_frame_extract", "fb_frame_set_pose_dev",

@@ -1,0 +1,257 @@
+"""Synthetic maps for the covisibility graph (fb_covis_*): key frames, map points and the observation edge list as the arrays
+of fb_covis_map, with the reference's quirks planted.
+
+    python -m fishbirdeyevisualslam_amd.covis_problem --probe     # times UpdateConnections / KeyFrameCulling at a LocalMapping-like size
+"""
+import numpy as np
+
+
+class MapBuilder:
+    """Grows a map one observation at a time; arrays() gives the fb_covis_map fields as numpy arrays."""
+
+    def __init__(self, K, S, seed):
+        self.K, self.S = K, S
+        self.g = np.random.default_rng(seed)
+        self.kf_mp = np.full((K, S), -1, np.int32)
+        self.kf_octave = np.zeros((K, S), np.uint8)
+        self.kf_n = np.zeros(K, np.int32)
+        self.mp_bad = []
+        self.obs = []          # (mp, kf, idx)
+
+    def new_point(self, bad=False):
+        self.mp_bad.append(1 if bad else 0)
+        return len(self.mp_bad) - 1
+
+    def room(self, kf):
+        return self.S - int(self.kf_n[kf])
+
+    def observe(self, mp, kf, octave=0, hole=False):
+        """mp->AddObservation(kf, idx) + kf->AddMapPoint(mp, idx) at the key frame's next feature (hole: leave a NULL feature first)"""
+        if hole and self.room(kf) >= 2:
+            self.kf_n[kf] += 1
+        idx = int(self.kf_n[kf])
+        assert idx < self.S, "key frame %d is full" % kf
+        self.kf_mp[kf, idx], self.kf_octave[kf, idx] = mp, octave
+        self.kf_n[kf] += 1
+        self.obs.append((mp, kf, idx))
+        return idx
+
+    def hold_again(self, mp, kf, octave=0):
+        """the same point at a second feature of kf (no second observation: mObservations is a std::map)"""
+        idx = int(self.kf_n[kf])
+        assert idx < self.S
+        self.kf_mp[kf, idx], self.kf_octave[kf, idx] = mp, octave
+        self.kf_n[kf] += 1
+
+    def shared(self, n, kfs, octaves=None, bad=False):
+        """n new points, each observed by every key frame of kfs"""
+        pts = []
+        for _ in range(n):
+            p = self.new_point(bad)
+            for j, kf in enumerate(kfs):
+                self.observe(p, kf, 0 if octaves is None else octaves[j])
+            pts.append(p)
+        return pts
+
+    def arrays(self, kf_order, tombstones=0.0, shuffle=True):
+        obs = np.array(self.obs, np.int32).reshape(-1, 3)
+        nt = int(round(len(obs) * tombstones))
+        if nt:   # erased entries: obs_kf < 0, the other two fields keep what they had
+            src = obs[self.g.integers(0, len(obs), nt)].copy()
+            src[:, 1] = -1 - self.g.integers(0, 3, nt)
+            obs = np.concatenate([obs, src])
+        if shuffle:
+            obs = obs[self.g.permutation(len(obs))]
+        return dict(kf_n=self.kf_n.copy(), kf_mp=self.kf_mp.copy(), kf_octave=self.kf_octave.copy(),
+                    mp_bad=np.array(self.mp_bad, np.uint8), obs_mp=np.ascontiguousarray(obs[:, 0]),
+                    obs_kf=np.ascontiguousarray(obs[:, 1]), obs_idx=np.ascontiguousarray(obs[:, 2]),
+                    kf_order=np.asarray(kf_order, np.uint64))
+
+
+def pointer_like_order(g, K, used):
+    """distinct, pointer-like std::map keys in an order unrelated to the slot order; 0 for unused slots"""
+    order = np.zeros(K, np.uint64)
+    perm = g.permutation(len(used))
+    for r, s in zip(perm, used):
+        order[s] = np.uint64(0x7F3A00000000 + int(r) * 0x2D0)
+    return order
+
+
+def make_covis_problem(seed=1, K=70, S=96):
+    """A 70-slot map with every quirk of UpdateConnections and KeyFrameCulling planted.
+
+    Slots 0..7 (E0..E7): pairs that share exactly 14 / 15 / 16 points, ties, a duplicate feature:
+        E0-E1 14, E0-E2 15 (+ one of them held twice by E0: E0 counts 16, E2 counts 15), E0-E3 16, E0-E4 15, E1-E2 15,
+        E5-E6 7, E5-E7 7 (no weight >= 15 and a tie on the maximum).
+    Slots 8..20: the culling block.  cur = 8; X1..X4 = 9..12 observe at octave 3, helpers 13..20 at octave 0 (never redundant):
+        X1 is culled; that turns three 3-observation points bad and flips X2 to culled; that flips X3 to culled; that takes
+        X4's points from 4 to 3 observations and flips X4 to NOT culled.
+    Slots 21..: background places of ten key frames; a few slots stay unused (kf_n = 0), one key frame is filled to the stride.
+    """
+    g = np.random.default_rng(seed)
+    b = MapBuilder(K, S, seed + 1000)
+    E = list(range(8))
+    b.shared(14, [E[0], E[1]])
+    p = b.shared(15, [E[0], E[2]])
+    b.hold_again(p[3], E[0])
+    b.shared(16, [E[0], E[3]])
+    b.shared(15, [E[0], E[4]])
+    b.shared(15, [E[1], E[2]])
+    b.shared(7, [E[5], E[6]])
+    b.shared(7, [E[5], E[7]])
+    cur, X1, X2, X3, X4 = 8, 9, 10, 11, 12
+    Ha, Hb, H3, H4 = [13, 15, 17], [14, 16, 18], 19, 20
+    for k, (X, n_c, n_all) in enumerate(((X1, 20, 50), (X2, 18, 46), (X3, 16, 16))):
+        b.shared(n_c, [cur, X, Ha[k], Hb[k]], [3, 3, 0, 0])                 # C_k seen by cur
+        b.shared(n_all - n_c, [H4, X, Ha[k], Hb[k]], [0, 3, 0, 0])          # C_k seen by H4 instead
+    b.shared(3, [X1, X2, H3], [3, 3, 0])                                    # D_1: 3 observations
+    b.shared(5, [X2, X3, H3], [3, 3, 0])                                    # D_2
+    b.shared(15, [X4, X3, Ha[2], Hb[2]], [3, 3, 0, 0])                      # F: redundant for X4 while X3 is there
+    b.shared(15, [cur, X4, Ha[0], Hb[0]], [3, 3, 0, 0])                     # G
+    used = list(range(21)) + [s for s in range(21, K) if s % 9 != 5]        # unused slots: 23, 32, 41, ...
+    bg = [s for s in used if s >= 21]
+    places = [bg[i:i + 10] for i in range(0, len(bg), 10)]
+    for _ in range(330):
+        place = places[int(g.integers(0, len(places)))]
+        n = int(g.integers(3, 9))
+        kfs = [int(x) for x in g.choice(place, min(n, len(place)), replace=False) if b.room(int(x)) >= 4]
+        if len(kfs) < 2:
+            continue
+        pt = b.new_point(bad=g.random() < 0.05)
+        for kf in kfs:
+            b.observe(pt, kf, int(g.integers(0, 8)), hole=g.random() < 0.05)
+            if g.random() < 0.03 and b.room(kf) >= 3:
+                b.hold_again(pt, kf, int(g.integers(0, 8)))
+    full = bg[0]
+    while b.room(full) > 0:                                                  # one key frame filled to the stride
+        b.observe(b.new_point(), full, int(g.integers(0, 8)))
+    arr = b.arrays(pointer_like_order(g, K, used), tombstones=1.0 / 9.0)
+    arr.update(K=K, S=S, used=used, E=E, cur=cur, X=[X1, X2, X3, X4], batch=[E[0], E[1], E[2], E[5], E[6], cur, X1, bg[3]])
+    return arr
+
+
+def make_hub_problem(seed=2, K=1300, S=1280, n_spokes=1250):
+    """Slot 0 shares exactly one point with each of n_spokes others: after an AddConnection its ordered list is the whole row."""
+    g = np.random.default_rng(seed)
+    b = MapBuilder(K, S, seed)
+    used = list(range(n_spokes + 1))
+    for s in range(1, n_spokes + 1):
+        b.shared(1, [0, s])
+    arr = b.arrays(pointer_like_order(g, K, used))
+    arr.update(K=K, S=S, used=used)
+    return arr
+
+
+def make_sparse_problem(seed=3, K=4096, S=32):
+    """The full slot range with sparse content: clusters at the bottom, in the middle and at the top slot indices."""
+    g = np.random.default_rng(seed)
+    b = MapBuilder(K, S, seed)
+    used = [0, 1, 2, 2047, 2048, 2049, 4093, 4094, 4095]
+    b.shared(16, [0, 4095])
+    b.shared(15, [4095, 4094, 2048])
+    b.shared(3, [4093, 1])
+    b.shared(3, [4093, 2047])
+    b.shared(9, [2, 2049, 4094])
+    arr = b.arrays(pointer_like_order(g, K, used), tombstones=0.1)
+    arr.update(K=K, S=S, used=used)
+    return arr
+
+
+def make_local_mapping_problem(seed=4, K=500, S=2000, n_mp=100000, per_point=6, window=40):
+    """A drive: every point is seen by `per_point` key frames out of a window of neighbouring slots (about 600 k edges)."""
+    g = np.random.default_rng(seed)
+    b = MapBuilder(K, S, seed)
+    for _ in range(n_mp):
+        c = int(g.integers(0, K))
+        lo = max(0, min(c - window // 2, K - window))
+        kfs = [int(x) for x in (lo + g.choice(window, per_point, replace=False)) if b.room(int(x)) > 0]
+        if not kfs:
+            continue
+        p = b.new_point()
+        for kf in kfs:
+            b.observe(p, kf, int(g.integers(0, 8)))
+    arr = b.arrays(pointer_like_order(g, K, list(range(K))))
+    arr.update(K=K, S=S, used=list(range(K)))
+    return arr
+
+
+def _probe():
+    import time
+    import torch
+    from .covis import CovisibilityGraph, DeviceMap
+    p = make_local_mapping_problem()
+    m = DeviceMap(p)
+    G = CovisibilityGraph(p["K"])
+    G.reserve(m.n_mp, m.n_obs, 30)
+    print("map: %d key frames x %d features, %d points, %d edges" % (p["K"], p["S"], m.n_mp, m.n_obs))
+
+    def timed(fn, reps=20):
+        fn()
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        for _ in range(reps):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t) / reps * 1e3
+    G.update_connections(m, list(range(p["K"])))
+    cur = p["K"] // 2
+    print("device update_connections(1 key frame):   %.3f ms" % timed(lambda: G.update_connections(m, [cur])))
+    print("device update_connections(30 key frames): %.3f ms" % timed(lambda: G.update_connections(m, list(range(cur - 15, cur + 15)))))
+    print("device keyframe_culling:                  %.3f ms" % timed(lambda: G.keyframe_culling(m, cur)))
+    print("errors counted: %d" % G.error_count())
+    G.close()
+    _probe_host(p, cur)
+
+
+def _probe_host(p, cur):
+    """The same three operations on one host core, for scale: the std::map restatement tests/cpp/covis_map_ref.cpp and the
+    Python model tests/covis_ref.py (both are test infrastructure; the probe looks for them next to the package's checkout)."""
+    import importlib.util
+    import os
+    import subprocess
+    import tempfile
+    import time
+    tests = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests")
+    src = os.path.join(tests, "cpp", "covis_map_ref.cpp")
+    if not os.path.exists(src):
+        print("host figures: not measured (tests/ is not next to the package)")
+        return
+    d = tempfile.mkdtemp()
+    exe, blob = os.path.join(d, "covis_map_ref"), os.path.join(d, "map.bin")
+    subprocess.check_call(["g++", "-std=c++17", "-O2", src, "-o", exe])
+    with open(blob, "wb") as f:
+        f.write(np.array([p["K"], p["S"], len(p["mp_bad"]), len(p["obs_kf"])], np.int32).tobytes())
+        for k, dt in (("kf_n", np.int32), ("kf_mp", np.int32), ("kf_octave", np.uint8), ("mp_bad", np.uint8), ("obs_mp", np.int32),
+                      ("obs_kf", np.int32), ("obs_idx", np.int32), ("kf_order", np.uint64)):
+            f.write(np.ascontiguousarray(p[k], dt).tobytes())
+    one, thirty, cull, n = subprocess.check_output([exe, blob, str(cur)]).decode().split()
+    print("C++ std::map, one core: update_connections(1) %s ms, (30) %s ms, keyframe_culling %s ms (%s culled)" % (one, thirty, cull, n))
+    spec = importlib.util.spec_from_file_location("covis_ref", os.path.join(tests, "covis_ref.py"))
+    R = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(R)
+    m = R.Map(*[p[k] for k in ("kf_n", "kf_mp", "kf_octave", "mp_bad", "obs_mp", "obs_kf", "obs_idx", "kf_order")])
+    g = R.Graph(p["K"], p["kf_order"])
+    obs = m.observations()
+    m.observations = lambda: obs          # the model rebuilds mObservations per call; here it is built once, outside the timing
+    for a in range(cur - 40, cur + 40):
+        g.update_connections(m, a)
+    t = time.perf_counter()
+    g.update_connections(m, cur)
+    one = (time.perf_counter() - t) * 1e3
+    t = time.perf_counter()
+    for a in range(cur - 15, cur + 15):
+        g.update_connections(m, a)
+    thirty = (time.perf_counter() - t) * 1e3
+    t = time.perf_counter()
+    R.keyframe_culling(g, m, cur)
+    cull = (time.perf_counter() - t) * 1e3
+    print("Python model:           update_connections(1) %.1f ms, (30) %.1f ms, keyframe_culling %.1f ms (culling copies the observations)" % (one, thirty, cull))
+
+
+if __name__ == "__main__":
+    import sys
+    if "--probe" in sys.argv:
+        _probe()
+    else:
+        q = make_covis_problem()
+        print("covis problem: %d points, %d edges (%d erased)" % (len(q["mp_bad"]), len(q["obs_kf"]), int((q["obs_kf"] < 0).sum())))

@@ -681,6 +681,125 @@ class KeyFrameDatabase {
   std::vector<int32_t> covis_;
 };
 
+// ---- the covisibility graph of KeyFrame (KeyFrame.cc:179-270, 564-663, 797-808, 885-899) on slots ----------------------
+// CovisibilityMap is what the graph reads of the caller's Map: per key frame N, mvpMapPoints and mvKeysUn[i].octave, per
+// map point isBad(), and every MapPoint::mObservations entry as one edge list (erase = obs_kf < 0).  The methods carry
+// the reference's names with the key frame's slot as first argument; each one is one call of fb_covis_* with host
+// pointers.  The spanning tree stays with the caller: UpdateConnections returns front() for it.
+struct CovisibilityMap {
+  int maxKeyFrames, kpStride;
+  std::vector<int32_t> kfN, kfMapPoints;            // [K], [K][kpStride] (-1 = NULL)
+  std::vector<uint8_t> kfOctave, mpBad;             // [K][kpStride], [points]
+  std::vector<int32_t> obsMp, obsKf, obsIdx;
+  std::vector<uint64_t> kfOrder;                    // (uintptr_t)pKF
+  CovisibilityMap(int K, int stride)
+      : maxKeyFrames(K), kpStride(stride), kfN(K, 0), kfMapPoints((size_t)K * stride, -1), kfOctave((size_t)K * stride, 0), kfOrder(K, 0) {}
+  int NewMapPoint() { mpBad.push_back(0); return (int)mpBad.size() - 1; }
+  // pKF->AddMapPoint(pMP, idx); pMP->AddObservation(pKF, idx)
+  void AddObservation(int mp, int kf, int idx, int octave) {
+    kfMapPoints[(size_t)kf * kpStride + idx] = mp; kfOctave[(size_t)kf * kpStride + idx] = (uint8_t)octave;
+    kfN[kf] = std::max(kfN[kf], idx + 1);
+    obsMp.push_back(mp); obsKf.push_back(kf); obsIdx.push_back(idx);
+  }
+  fb_covis_map view() const {
+    fb_covis_map m;
+    memset(&m, 0, sizeof(m));
+    m.max_keyframes = maxKeyFrames; m.kp_stride = kpStride; m.kf_n = kfN.data(); m.kf_mp = kfMapPoints.data(); m.kf_octave = kfOctave.data();
+    m.n_mp = (int32_t)mpBad.size(); m.mp_bad = mpBad.data(); m.n_obs = (int32_t)obsKf.size();
+    m.obs_mp = obsMp.data(); m.obs_kf = obsKf.data(); m.obs_idx = obsIdx.data(); m.kf_order = kfOrder.data();
+    return m;
+  }
+};
+
+class CovisibilityGraph {
+ public:
+  explicit CovisibilityGraph(int max_keyframes) : K_(max_keyframes) { check(fb_covis_create(max_keyframes, &g_)); }
+  ~CovisibilityGraph() { fb_covis_destroy(g_); }
+  CovisibilityGraph(const CovisibilityGraph &) = delete;
+  CovisibilityGraph &operator=(const CovisibilityGraph &) = delete;
+  fb_covis *handle() const { return g_; }
+
+  struct Updated { int nCounter, front; };          // KFcounter.size(), mvpOrderedConnectedKeyFrames.front() (-1 = empty)
+  // pKF->UpdateConnections() for each listed key frame, one after the other
+  std::vector<Updated> UpdateConnections(const CovisibilityMap &map, const std::vector<int> &slots) {
+    const fb_covis_map m = map.view();
+    std::vector<int32_t> n(slots.size()), f(slots.size());
+    check(fb_covis_update_connections(g_, &m, (int32_t)slots.size(), slots.data(), n.data(), f.data()));
+    std::vector<Updated> r(slots.size());
+    for (size_t i = 0; i < r.size(); i++) r[i] = {n[i], f[i]};
+    return r;
+  }
+  Updated UpdateConnections(const CovisibilityMap &map, int slot) { return UpdateConnections(map, std::vector<int>(1, slot))[0]; }
+  void AddConnection(int slot, int pKF, int weight) { check(fb_covis_add_connection_dev(g_, slot, pKF, weight, nullptr)); }
+  void EraseConnection(int slot, int pKF) { check(fb_covis_erase_connection_dev(g_, slot, pKF, nullptr)); }
+  void SetBadFlag(int slot) { check(fb_covis_erase_keyframe_dev(g_, slot, nullptr)); }   // the graph part (:797-798, :807-808)
+  void clear() { check(fb_covis_clear(g_, nullptr)); }
+
+  std::vector<int> GetVectorCovisibleKeyFrames(int slot, std::vector<int> *orderedWeights = nullptr) {
+    int32_t n = 0;
+    std::vector<int32_t> s(K_), w(K_);
+    check(fb_covis_ordered(g_, slot, &n, s.data(), w.data()));
+    if (orderedWeights) orderedWeights->assign(w.begin(), w.begin() + n);
+    return std::vector<int>(s.begin(), s.begin() + n);
+  }
+  std::vector<int> GetBestCovisibilityKeyFrames(int slot, int N) {
+    std::vector<int> v = GetVectorCovisibleKeyFrames(slot);
+    if ((int)v.size() > N) v.resize(N);
+    return v;
+  }
+  std::vector<int> GetCovisiblesByWeight(int slot, int w) {
+    int32_t n = 0;
+    std::vector<int32_t> s(K_);
+    check(fb_covis_by_weight(g_, slot, w, &n, s.data()));
+    return std::vector<int>(s.begin(), s.begin() + n);
+  }
+  std::vector<int> GetConnectedKeyFrames(int slot) {   // the std::set's order: ascending kfOrder
+    int32_t n = 0;
+    std::vector<int32_t> s(K_);
+    check(fb_covis_connected(g_, slot, &n, s.data()));
+    return std::vector<int>(s.begin(), s.begin() + n);
+  }
+  int GetWeight(int slot, int pKF) {
+    int32_t w = 0;
+    check(fb_covis_weight(g_, slot, pKF, &w));
+    return w;
+  }
+  // GetBestCovisibilityKeyFrames(10) of every slot, as KeyFrameDatabase::SetBestCovisibilityKeyFrames takes them
+  void UpdateKeyFrameDatabase(KeyFrameDatabase &db) {
+    std::vector<int32_t> rows((size_t)K_ * FB_KFDB_COVIS, -1);
+    check(fb_covis_kfdb_rows(g_, 0, nullptr, rows.data()));
+    for (int s = 0; s < K_; s++) {
+      std::vector<int> v;
+      for (int c = 0; c < FB_KFDB_COVIS && rows[(size_t)s * FB_KFDB_COVIS + c] >= 0; c++) v.push_back(rows[(size_t)s * FB_KFDB_COVIS + c]);
+      db.SetBestCovisibilityKeyFrames(s, v);
+    }
+  }
+
+  struct Culling {                                  // in the order of GetVectorCovisibleKeyFrames() of the current key frame
+    std::vector<int> slots, nRedundantObservations, nMPs;
+    std::vector<uint8_t> culled;                    // SetBadFlag() was called on it
+    std::vector<uint8_t> mpBadAfter;                // isBad() of every map point after the call's SetBadFlag()s
+  };
+  // LocalMapping::KeyFrameCulling (LocalMapping.cc:656-729); the caller then runs the real SetBadFlag per culled slot
+  Culling KeyFrameCulling(const CovisibilityMap &map, int currentKF, int id0Slot, const std::vector<uint8_t> &notErase) {
+    const fb_covis_map m = map.view();
+    int32_t n = 0;
+    std::vector<int32_t> s(K_), r(K_), p(K_);
+    std::vector<uint8_t> c(K_), bad(map.mpBad.size() + 1);
+    check(fb_covis_keyframe_culling(g_, &m, currentKF, id0Slot, notErase.empty() ? nullptr : notErase.data(), &n, s.data(), r.data(),
+                                    p.data(), c.data(), bad.data()));
+    Culling out;
+    out.slots.assign(s.begin(), s.begin() + n); out.nRedundantObservations.assign(r.begin(), r.begin() + n);
+    out.nMPs.assign(p.begin(), p.begin() + n); out.culled.assign(c.begin(), c.begin() + n);
+    out.mpBadAfter.assign(bad.begin(), bad.begin() + map.mpBad.size());
+    return out;
+  }
+
+ private:
+  fb_covis *g_ = nullptr;
+  int K_;
+};
+
 // ---- Sim3Solver (include/Sim3Solver.h) ---------------------------------------------------------------------------------
 // One candidate per object, as in the reference.  The first iterate() runs fb_sim3_solver once: every iteration up to
 // mRansacMaxIts lands in a table, and iterate(n, ...) replays rows (mnIterations, mnIterations + n] of it, so

@@ -848,6 +848,96 @@ int fb_kfdb_min_score(fb_kfdb *db, int32_t n_words, const uint32_t *bow_ids, con
                       const int32_t *slots, const uint8_t *skip, float *scores, float *min_score); /* host pointers */
 
 /* ======================================================================== */
+/* Covisibility graph (src/KeyFrame.cc) and LocalMapping::KeyFrameCulling     */
+/* ======================================================================== */
+/* The caller's map as device arrays; read-only to the library, like fb_map_points.  Preconditions: a (mp, kf) pair occurs
+ * at most once among the live edges (it is a std::map key); kf_order is distinct over the slots in use; the configuration
+ * is monocular, so MapPoint::Observations() is the number of live edges of the point (mvuRight < 0, MapPoint.cc:119-122).
+ * An edge whose obs_kf >= max_keyframes, whose obs_mp or obs_idx is out of range, or a kf_mp entry >= n_mp is skipped on
+ * the device, never used as an index, and counted (fb_covis_error_count).                                               */
+typedef struct fb_covis_map {
+  int32_t max_keyframes;        /* slots, as fb_kfdb: the host's index for pKF; equals the handle's max_keyframes      */
+  int32_t kp_stride;            /* 1 .. FB_COVIS_MAX_STRIDE                                                            */
+  const int32_t *kf_n;          /* [max_keyframes] N (0 for an unused slot)                                            */
+  const int32_t *kf_mp;         /* [max_keyframes][kp_stride] mvpMapPoints[i] as a map point index, -1 = NULL          */
+  const uint8_t *kf_octave;     /* [max_keyframes][kp_stride] mvKeysUn[i].octave                                       */
+  int32_t n_mp;
+  const uint8_t *mp_bad;        /* [n_mp] isBad()                                                                      */
+  int32_t n_obs;                /* all MapPoint::mObservations of the map as one edge list, any order:                 */
+  const int32_t *obs_mp, *obs_kf, *obs_idx;  /* [n_obs]; obs_kf < 0: erased entry (append / tombstone friendly; the same
+                                   shape as fb_local_ba_args.obs_*)                                                    */
+  const uint64_t *kf_order;     /* [max_keyframes] the key std::map<KeyFrame*,..> orders by: (uintptr_t)pKF            */
+} fb_covis_map;
+#define FB_COVIS_MAX_STRIDE 32767 /* a weight is at most kp_stride and is kept in 15 bits                              */
+#define FB_COVIS_TH 15            /* th of KeyFrame::UpdateConnections (KeyFrame.cc:621)                               */
+
+/* mConnectedKeyFrameWeights and the membership of mvpOrderedConnectedKeyFrames of every key frame (slot).  The ordered
+ * vector is always "descending by (weight, kf_order)" over its members (KeyFrame.cc:202-209, :648-655) and is derived on
+ * read.  Until an order is given (fb_covis_set_order_dev, or any call that takes a fb_covis_map) slots order by index.
+ * Every call below enqueues on `stream`, none synchronises, and they take effect in call order; the handle is
+ * single-threaded like fb_kfdb.  The calls that take a fb_covis_map use scratch owned by the handle: it grows on demand
+ * (a growing call waits for the device once), or is sized ahead with fb_covis_reserve.                                   */
+typedef struct fb_covis fb_covis;
+int fb_covis_create(int32_t max_keyframes /* 1 .. FB_KFDB_MAX_KEYFRAMES */, fb_covis **out);
+int fb_covis_destroy(fb_covis *g);
+int fb_covis_clear(fb_covis *g, void *stream);          /* every row empty, the error counter 0                        */
+int fb_covis_reserve(fb_covis *g, int32_t n_mp, int32_t n_obs, int32_t n_q);
+int fb_covis_set_order_dev(fb_covis *g, const uint64_t *d_kf_order /* [max_keyframes] */, void *stream);
+/* entries skipped on the device since creation / clear (see fb_covis_map); waits for `stream`                           */
+int fb_covis_error_count(fb_covis *g, int32_t *count, void *stream);
+
+/* KeyFrame::UpdateConnections (KeyFrame.cc:564-663) for the n_q key frames d_slots[0..n_q), with the result of calling
+ * them one after another in list order.  Row a becomes the counter (entries below FB_COVIS_TH included); the members of
+ * its ordered list are the entries >= FB_COVIS_TH, or pKFmax alone (the smallest kf_order among the maxima, :627-643);
+ * every member b gets AddConnection(a, w).  An empty counter changes nothing (:604-612).  d_n_counter[q] =
+ * KFcounter.size(), d_front[q] = mvpOrderedConnectedKeyFrames.front() afterwards (-1: the vector is empty).  The spanning
+ * tree (mpParent, mbFirstConnection) stays with the host; UpdateBirdConnections is not restated.                       */
+int fb_covis_update_connections_dev(fb_covis *g, const fb_covis_map *map, int32_t n_q, const int32_t *d_slots,
+                                    int32_t *d_n_counter, int32_t *d_front, void *stream);
+int fb_covis_update_connections(fb_covis *g, const fb_covis_map *map, int32_t n_q, const int32_t *slots, int32_t *n_counter,
+                                int32_t *front); /* host pointers, the map's arrays included */
+/* slot->AddConnection(other, weight) (KeyFrame.cc:179-192; weight 1 .. FB_COVIS_MAX_STRIDE) and
+ * slot->EraseConnection(other) (:885-899): the ordered list is rebuilt from every entry only if the row changed.        */
+int fb_covis_add_connection_dev(fb_covis *g, int32_t slot, int32_t other, int32_t weight, void *stream);
+int fb_covis_erase_connection_dev(fb_covis *g, int32_t slot, int32_t other, void *stream);
+/* the graph part of KeyFrame::SetBadFlag (:797-798, :807-808): EraseConnection(slot) on every key frame of its row, then
+ * the row and its ordered list are cleared                                                                              */
+int fb_covis_erase_keyframe_dev(fb_covis *g, int32_t slot, void *stream);
+
+/* Getters.  d_slots / d_weights hold max_keyframes entries; entries past *d_n are left as they are.                     */
+/* GetVectorCovisibleKeyFrames + mvOrderedWeights (d_weights may be NULL); GetBestCovisibilityKeyFrames(N) is the prefix */
+int fb_covis_ordered_dev(fb_covis *g, int32_t slot, int32_t *d_n, int32_t *d_slots, int32_t *d_weights, void *stream);
+int fb_covis_ordered(fb_covis *g, int32_t slot, int32_t *n, int32_t *slots, int32_t *weights);
+/* GetCovisiblesByWeight(w) (:246-261): the prefix with weight >= w, and EMPTY when every weight is >= w (upper_bound
+ * returns end()), as in the reference                                                                                   */
+int fb_covis_by_weight_dev(fb_covis *g, int32_t slot, int32_t w, int32_t *d_n, int32_t *d_slots, void *stream);
+int fb_covis_by_weight(fb_covis *g, int32_t slot, int32_t w, int32_t *n, int32_t *slots);
+/* GetConnectedKeyFrames (a std::set: ascending kf_order); the `connected` argument of fb_kfdb_query_dev                 */
+int fb_covis_connected_dev(fb_covis *g, int32_t slot, int32_t *d_n, int32_t *d_slots, void *stream);
+int fb_covis_connected(fb_covis *g, int32_t slot, int32_t *n, int32_t *slots);
+/* slot->GetWeight(other) (:263-270)                                                                                     */
+int fb_covis_weight_dev(fb_covis *g, int32_t slot, int32_t other, int32_t *d_weight, void *stream);
+int fb_covis_weight(fb_covis *g, int32_t slot, int32_t other, int32_t *weight);
+/* rows [max_keyframes][FB_KFDB_COVIS] of GetBestCovisibilityKeyFrames(10), -1 padded, as fb_kfdb_query_args.covis reads
+ * them: the rows of the n slots listed (d_slots == NULL: every row, n ignored); other rows are left as they are         */
+int fb_covis_kfdb_rows_dev(fb_covis *g, int32_t n, const int32_t *d_slots, int32_t *d_covis, void *stream);
+int fb_covis_kfdb_rows(fb_covis *g, int32_t n, const int32_t *slots, int32_t *covis);
+
+/* LocalMapping::KeyFrameCulling (LocalMapping.cc:656-729) over GetVectorCovisibleKeyFrames() of cur_slot, in that order,
+ * with the effects of each SetBadFlag() on the key frames after it: the culled key frame's observation edges are gone,
+ * every point it observed loses one observation, and a point that drops to <= 2 is bad (MapPoint.cc:129-136).  These
+ * effects live in scratch of the call: the map and the graph are not modified.  id0_slot (mnId == 0, :667; -1 = none)
+ * is skipped with zeros; d_not_erase[slot] (mbNotErase, KeyFrame.cc:790-794; NULL = none) keeps a culled key frame
+ * without effect.  Outputs in list order: d_slots, d_n_redundant, d_n_mps [max_keyframes] int32, d_culled
+ * [max_keyframes] uint8 (nRedundantObservations > 0.9 * nMPs), and d_mp_bad_after [n_mp].                              */
+int fb_covis_keyframe_culling_dev(fb_covis *g, const fb_covis_map *map, int32_t cur_slot, int32_t id0_slot,
+                                  const uint8_t *d_not_erase, int32_t *d_n, int32_t *d_slots, int32_t *d_n_redundant,
+                                  int32_t *d_n_mps, uint8_t *d_culled, uint8_t *d_mp_bad_after, void *stream);
+int fb_covis_keyframe_culling(fb_covis *g, const fb_covis_map *map, int32_t cur_slot, int32_t id0_slot, const uint8_t *not_erase,
+                              int32_t *n, int32_t *slots, int32_t *n_redundant, int32_t *n_mps, uint8_t *culled,
+                              uint8_t *mp_bad_after); /* host pointers, the map's arrays included */
+
+/* ======================================================================== */
 /* Frame geometry either side of the matchers (src/Frame.cc)                 */
 /* ======================================================================== */
 /* --- Frame::isInFrustum(pMP, viewingCosLimit) over a list of map points (Frame.cc:435-491; the loop
