@@ -250,6 +250,26 @@ class CovisMap(C.Structure):
                 ("kf_order", _vp)]
 
 
+class CovisKfTables(C.Structure):
+    _fields_ = [("kf_Tcw", _vp), ("kf_bad", _vp), ("kf_init", _vp), ("kf_keys_un", _vp), ("n_levels", _i32),
+                ("inv_level_sigma2", _vp), ("mp_xw", _vp), ("bird_stride", _i32), ("kf_nb", _vp), ("kf_mpb", _vp),
+                ("kf_bird_octave", _vp), ("kf_bird_xc", _vp), ("n_mpb", _i32), ("mpb_bad", _vp), ("mpb_xw", _vp),
+                ("n_bobs", _i32), ("bobs_mpb", _vp), ("bobs_kf", _vp), ("bobs_idx", _vp)]
+
+
+class CovisWindowHeader(C.Structure):
+    _fields_ = [("n_local", _i32), ("n_fixed", _i32), ("n_mp", _i32), ("n_obs", _i32), ("n_mpb", _i32), ("n_bobs", _i32),
+                ("overflow", _i32)]
+
+
+class CovisWindow(C.Structure):
+    _fields_ = [("cap_kf", _i32), ("cap_mp", _i32), ("cap_obs", _i32), ("cap_mpb", _i32), ("cap_bobs", _i32),
+                ("kf_slot", _vp), ("kf_fixed", _vp), ("kf_Tcw", _vp), ("mp_index", _vp), ("mp_xw", _vp),
+                ("obs_kf", _vp), ("obs_mp", _vp), ("obs_src", _vp), ("obs_uv", _vp), ("obs_inv_sigma2", _vp),
+                ("mpb_index", _vp), ("mpb_xw", _vp), ("bobs_kf", _vp), ("bobs_mpb", _vp), ("bobs_src", _vp),
+                ("bobs_xc", _vp), ("bobs_inv_sigma2", _vp), ("header", _vp)]
+
+
 class BirdFilterArgs(C.Structure):
     _fields_ = [("batch", _i32), ("match_stride", _i32), ("kp1_stride", _i32), ("kp2_stride", _i32),
                 ("n_matches", _vp), ("query_idx", _vp), ("train_idx", _vp), ("cam_xyz1", _vp), ("cam_xyz2", _vp),
@@ -362,6 +382,8 @@ EXPORTS = [
     "fb_covis_erase_keyframe_dev", "fb_covis_ordered_dev", "fb_covis_ordered", "fb_covis_by_weight_dev", "fb_covis_by_weight",
     "fb_covis_connected_dev", "fb_covis_connected", "fb_covis_weight_dev", "fb_covis_weight", "fb_covis_kfdb_rows_dev",
     "fb_covis_kfdb_rows", "fb_covis_keyframe_culling_dev", "fb_covis_keyframe_culling",
+    "fb_covis_reserve_window", "fb_covis_local_window_dev", "fb_covis_local_window_header", "fb_covis_local_window",
+    "fb_covis_window_scatter_dev",
     "fb_in_frustum_dev", "fb_in_frustum", "fb_undistort_keypoints_dev", "fb_undistort_keypoints", "fb_image_bounds",
     "fb_pose_opt_batch_dev", "fb_pose_opt", "fb_pose_gather_front_dev", "fb_pose_gather_bird_dev",
     "fb_frame_create", "fb_frame_destroy", "fb_frame_extract_dev", "fb_frame_extract", "fb_frame_set_pose_dev",

@@ -43,6 +43,41 @@ class DeviceMap:
         return b"".join(self.t[name].cpu().numpy().tobytes() for name, _ in self.FIELDS)
 
 
+class DeviceTables:
+    """fb_covis_kf_tables over device tensors, from the dict of covis_problem.make_window_problem.  The bird side is there when
+    the dict has bobs_kf."""
+    FRONT = (("kf_Tcw", np.float32), ("kf_bad", np.uint8), ("kf_init", np.uint8), ("kf_keys_un", None), ("inv_level_sigma2", np.float32),
+             ("mp_xw", np.float32))
+    BIRD = (("kf_nb", np.int32), ("kf_mpb", np.int32), ("kf_bird_octave", np.uint8), ("kf_bird_xc", np.float32), ("mpb_bad", np.uint8),
+            ("mpb_xw", np.float32), ("bobs_mpb", np.int32), ("bobs_kf", np.int32), ("bobs_idx", np.int32))
+
+    def __init__(self, arrays, device="cuda:0"):
+        self.device = torch.device(device)
+        self.bird = "bobs_kf" in arrays
+        self.t = {}
+        for name, dt in self.FRONT + (self.BIRD if self.bird else ()):
+            a = np.ascontiguousarray(arrays[name]) if dt is None else np.ascontiguousarray(arrays[name], dt)
+            if dt is None:
+                a = a.view(np.uint8).reshape(-1)
+            if a.size == 0:
+                a = np.zeros(4, a.dtype)
+            self.t[name] = torch.from_numpy(a.copy()).to(self.device)
+        self.n_mpb = len(arrays["mpb_bad"]) if self.bird else 0
+        self.n_bobs = len(arrays["bobs_kf"]) if self.bird else 0
+        self.c = cabi.CovisKfTables()
+        cabi.fill(self.c, n_levels=len(arrays["inv_level_sigma2"]), bird_stride=np.asarray(arrays["kf_mpb"]).shape[1] if self.bird else 0,
+                  n_mpb=self.n_mpb, n_bobs=self.n_bobs, **self.t)
+
+
+WINDOW_ARRAYS = (("kf_slot", "cap_kf", 1, torch.int32), ("kf_fixed", "cap_kf", 1, torch.uint8), ("kf_Tcw", "cap_kf", 12, torch.float32),
+                 ("mp_index", "cap_mp", 1, torch.int32), ("mp_xw", "cap_mp", 3, torch.float32), ("obs_kf", "cap_obs", 1, torch.int32),
+                 ("obs_mp", "cap_obs", 1, torch.int32), ("obs_src", "cap_obs", 1, torch.int32), ("obs_uv", "cap_obs", 2, torch.float32),
+                 ("obs_inv_sigma2", "cap_obs", 1, torch.float32), ("mpb_index", "cap_mpb", 1, torch.int32),
+                 ("mpb_xw", "cap_mpb", 3, torch.float32), ("bobs_kf", "cap_bobs", 1, torch.int32), ("bobs_mpb", "cap_bobs", 1, torch.int32),
+                 ("bobs_src", "cap_bobs", 1, torch.int32), ("bobs_xc", "cap_bobs", 3, torch.float32),
+                 ("bobs_inv_sigma2", "cap_bobs", 1, torch.float32))
+
+
 class CovisibilityGraph:
     def __init__(self, max_keyframes, device="cuda:0"):
         self.K = int(max_keyframes)
@@ -140,3 +175,54 @@ class CovisibilityGraph:
                                                   _p(out["mp_bad_after"]), _stream()), "fb_covis_keyframe_culling_dev")
         self._keep = (m, ne)
         return out
+
+    # ---- the local-BA window -------------------------------------------------------------------------------------------------
+    def reserve_window(self, n_mp, n_obs, n_mpb=0, n_bobs=0):
+        check(lib().fb_covis_reserve_window(self.h, int(n_mp), int(n_obs), int(n_mpb), int(n_bobs)), "fb_covis_reserve_window")
+
+    def window_arrays(self, caps, guard=0, fill=-1):
+        """Device arrays of a fb_covis_window with the given capacities (cap_kf, cap_mp, cap_obs, cap_mpb, cap_bobs), each followed
+        by `guard` extra elements the library never sees -> (dict of tensors, cabi.CovisWindow)."""
+        w = {}
+        for name, cap, width, dt in WINDOW_ARRAYS:
+            w[name] = torch.full(((int(caps[cap]) + guard) * width + (0 if guard else 1),), fill if dt != torch.uint8 else 0xEE, dtype=dt,
+                                 device=self.device)
+        w["header"] = torch.full((8,), -1, dtype=torch.int32, device=self.device)
+        c = cabi.CovisWindow()
+        cabi.fill(c, **{k: int(v) for k, v in caps.items()}, **w)
+        return w, c
+
+    def local_window(self, m, t, cur_slot, with_bird=True, caps=None, guard=0):
+        """The window of cur_slot -> dict of device tensors (the fb_covis_window arrays at their capacities, "header" int32[7])
+        with the struct under "c".  Default capacities hold any window of the map.  Nothing synchronises."""
+        bird = bool(with_bird) and t.bird
+        if caps is None:
+            caps = dict(cap_kf=self.K, cap_mp=m.n_mp, cap_obs=m.n_obs, cap_mpb=t.n_mpb if bird else 0, cap_bobs=t.n_bobs if bird else 0)
+        w, c = self.window_arrays(caps, guard)
+        check(lib().fb_covis_local_window_dev(self.h, C.byref(m.c), C.byref(t.c), int(cur_slot), 1 if with_bird else 0, C.byref(c), _stream()),
+              "fb_covis_local_window_dev")
+        w["c"], w["caps"] = c, dict(caps)
+        self._win_cap_kf = int(caps["cap_kf"])
+        self._keep = (m, t, w)
+        return w
+
+    def window_header(self):
+        """The one synchronisation, for the last local_window -> (rc, header fields as a dict, kf_slot, kf_fixed as numpy arrays of
+        n_local + n_fixed entries, or of cap_kf if that is less)"""
+        n = min(self._win_cap_kf, self.K)
+        h = cabi.CovisWindowHeader()
+        slots, fixed = np.full(max(n, 1), -7, np.int32), np.full(max(n, 1), 7, np.uint8)
+        rc = lib().fb_covis_local_window_header(self.h, C.byref(h), C.c_void_p(slots.ctypes.data), C.c_void_p(fixed.ctypes.data), _stream())
+        hd = {k: getattr(h, k) for k, _ in cabi.CovisWindowHeader._fields_}
+        n_kf = min(hd["n_local"] + hd["n_fixed"], n)
+        return rc, hd, slots[:n_kf], fixed[:n_kf]
+
+    def window_scatter(self, m, t, w, obs_outlier=None, bobs_outlier=None):
+        """Optimised poses / points back into the tables of t; -> (n_erase int32[2], erase [cap_obs][4], berase [cap_bobs][4])"""
+        n = torch.zeros(2, dtype=torch.int32, device=self.device)
+        er = torch.full((max(w["caps"]["cap_obs"], 1), 4), -1, dtype=torch.int32, device=self.device)
+        ber = torch.full((max(w["caps"]["cap_bobs"], 1), 4), -1, dtype=torch.int32, device=self.device)
+        check(lib().fb_covis_window_scatter_dev(self.h, C.byref(m.c), C.byref(t.c), C.byref(w["c"]), _p(obs_outlier), _p(bobs_outlier),
+                                                _p(n), _p(er), _p(ber), _stream()), "fb_covis_window_scatter_dev")
+        self._keep = (m, t, w, obs_outlier, bobs_outlier)
+        return n, er, ber

@@ -68,6 +68,133 @@ class MapBuilder:
                     kf_order=np.asarray(kf_order, np.uint64))
 
 
+KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"), ("octave", "<i4")])
+N_LEVELS = 8
+
+
+def window_tables(b, seed, bird=None, kf_bad=(), kf_init=()):
+    """The fb_covis_kf_tables arrays for the map of MapBuilder b (and the bird map of a second builder): poses, key points
+    whose octave is the map's kf_octave, isBad / isInit flags, point positions.  Drawn from a generator of its own, so the
+    builders' streams are as without it."""
+    g = np.random.default_rng(seed)
+    if isinstance(b, dict):   # the arrays of a finished map
+        b = type("Arrays", (), dict(K=b["kf_mp"].shape[0], S=b["kf_mp"].shape[1], kf_octave=b["kf_octave"], mp_bad=b["mp_bad"]))
+    K, S = b.K, b.S
+    keys = np.zeros((K, S), KP_DTYPE)
+    keys["x"], keys["y"] = g.uniform(0, 1280, (K, S)), g.uniform(0, 720, (K, S))
+    keys["octave"] = b.kf_octave
+    t = dict(kf_Tcw=g.normal(0, 1, (K, 12)).astype(np.float32), kf_bad=np.zeros(K, np.uint8), kf_init=np.zeros(K, np.uint8),
+             kf_keys_un=keys, inv_level_sigma2=(1.2 ** (-2.0 * np.arange(N_LEVELS))).astype(np.float32),
+             mp_xw=g.normal(0, 5, (len(b.mp_bad), 3)).astype(np.float32))
+    t["kf_bad"][list(kf_bad)] = 1
+    t["kf_init"][list(kf_init)] = 1
+    if bird is not None:
+        a = bird.arrays(np.zeros(K, np.uint64), tombstones=0.1)
+        t.update(kf_nb=a["kf_n"], kf_mpb=a["kf_mp"], kf_bird_octave=a["kf_octave"], mpb_bad=a["mp_bad"], bobs_mpb=a["obs_mp"],
+                 bobs_kf=a["obs_kf"], bobs_idx=a["obs_idx"], kf_bird_xc=g.normal(0, 3, (K, bird.S, 3)).astype(np.float32),
+                 mpb_xw=g.normal(0, 5, (len(bird.mp_bad), 3)).astype(np.float32))
+    return t
+
+
+def make_window_problem(seed=5, K=70, S=96, BS=24):
+    """A map for the local-BA window of cur = 8 with the reference's quirks planted.
+
+    Neighbours 9..18 share 16 points each with cur, in three groups (ties in the weight: kf_order decides); 13 and 17 are
+    bad, so they are in neither list although they observe local points; 9 is isInit.  Key frames 30..50 see points of the
+    neighbours but none of cur's: the fixed cameras, 32 and 44 of them bad.  Bad points, NULL features, a point at two
+    features, tombstoned edges; bird points continue the fixed list with 53 and 54 (and 52, bad)."""
+    g = np.random.default_rng(seed)
+    b = MapBuilder(K, S, seed + 1000)
+    bird = MapBuilder(K, BS, seed + 2000)
+    cur = 8
+    p0 = b.shared(16, [cur, 9, 10, 11]) + b.shared(16, [cur, 12, 13, 14]) + b.shared(16, [cur, 15, 16, 17, 18])
+    b.hold_again(p0[5], cur)
+    b.hold_again(p0[20], 12)
+    b.shared(2, [cur, 9], bad=True)
+    b.shared(5, [9, 30, 31])
+    b.shared(4, [10, 31, 32, 33])
+    b.shared(3, [14, 34])
+    b.shared(3, [13, 35])                                                   # a bad neighbour's points are not local: 35 stays outside
+    outside = list(range(30, 51))
+    for _ in range(60):
+        n = int(g.integers(9, 19))
+        kfs = [n] + [int(x) for x in g.choice(outside, int(g.integers(1, 4)), replace=False)]
+        kfs = [k for k in kfs if b.room(k) >= 4]
+        if len(kfs) < 2:
+            continue
+        pt = b.new_point(bad=g.random() < 0.08)
+        for kf in kfs:
+            b.observe(pt, kf, int(g.integers(0, N_LEVELS)), hole=g.random() < 0.1)
+            if g.random() < 0.05 and b.room(kf) >= 3:
+                b.hold_again(pt, kf, int(g.integers(0, N_LEVELS)))
+    for _ in range(40):                                                     # the outside key frames among themselves
+        kfs = [int(x) for x in g.choice(outside + [35, 52, 53], 3, replace=False) if b.room(int(x)) >= 2]
+        if len(kfs) >= 2:
+            b.shared(1, kfs)
+    bird.shared(6, [cur, 9, 10], [1, 2, 3])
+    bird.shared(4, [11, 53, 31], [0, 1, 2])
+    bird.shared(3, [12, 52, 54], [2, 2, 2])
+    bird.shared(2, [cur, 13])
+    bird.shared(2, [14, 33], bad=True)
+    pb = bird.shared(3, [15, 16])
+    bird.hold_again(pb[0], 15)
+    used = list(range(8, 19)) + outside + [52, 53, 54]
+    arr = b.arrays(pointer_like_order(g, K, used), tombstones=1.0 / 9.0)
+    arr.update(window_tables(b, seed + 3000, bird, kf_bad=[13, 17, 32, 44, 52], kf_init=[9]))
+    arr.update(K=K, S=S, BS=BS, used=used, cur=cur)
+    return arr
+
+
+def make_window_ba_problem(seed=4200, n_kf=20, n_mp=400, n_mpb=80, K=32, S=256, BS=64):
+    """synth.make_ba_problem as a map: key frame k lies in slot perm[k], its observations become features in edge order, the
+    key points carry the measurements, so the window of the newest key frame is a local BA with consistent geometry.
+    Returns (map and tables, the BA problem, slot of every key frame)."""
+    from . import synth
+    q = synth.make_ba_problem(seed, n_kf=n_kf, n_fixed=1, n_mp=n_mp, n_mpb=n_mpb)
+    g = np.random.default_rng(seed + 1)
+    slot = g.permutation(K)[:n_kf]
+    inv_sig2 = np.asarray(synth.scale_tables()[3], np.float32)[:N_LEVELS]
+    b, bird = MapBuilder(K, S, seed), MapBuilder(K, BS, seed)
+    b.mp_bad, bird.mp_bad = [0] * n_mp, [0] * n_mpb
+    keys = np.zeros((K, S), KP_DTYPE)
+    xc = np.zeros((K, BS, 3), np.float32)
+    for kf, mp, uv, w in zip(q["obs_kf"], q["obs_mp"], q["obs_uv"], q["obs_inv_sigma2"]):
+        o = int(np.argmin(np.abs(inv_sig2 - w)))
+        i = b.observe(int(mp), int(slot[kf]), o)
+        keys[slot[kf], i] = (uv[0], uv[1], 31.0, 0.0, 1.0, o)
+    for kf, mp, x, w in zip(q["bobs_kf"], q["bobs_mpb"], q["bobs_xc"], q["bobs_inv_sigma2"]):
+        i = bird.observe(int(mp), int(slot[kf]), int(np.argmin(np.abs(inv_sig2 - w))))
+        xc[slot[kf], i] = x
+    order = np.zeros(K, np.uint64)
+    order[slot] = 0x7F3A00000000 + g.permutation(n_kf).astype(np.uint64) * np.uint64(0x2D0)
+    arr = b.arrays(order, tombstones=0.05)
+    a = bird.arrays(order, tombstones=0.05)
+    Tcw = np.zeros((K, 12), np.float32)
+    Tcw[slot] = q["kf_Tcw"]
+    init = np.zeros(K, np.uint8)
+    init[slot[0]] = 1
+    arr.update(kf_Tcw=Tcw, kf_bad=np.zeros(K, np.uint8), kf_init=init, kf_keys_un=keys, inv_level_sigma2=inv_sig2,
+               mp_xw=q["mp_xw"].copy(), kf_nb=a["kf_n"], kf_mpb=a["kf_mp"], kf_bird_octave=a["kf_octave"], mpb_bad=a["mp_bad"],
+               bobs_mpb=a["obs_mp"], bobs_kf=a["obs_kf"], bobs_idx=a["obs_idx"], kf_bird_xc=xc, mpb_xw=q["mpb_xw"].copy())
+    arr.update(K=K, S=S, BS=BS, used=[int(x) for x in slot], cur=int(slot[n_kf - 1]))
+    return arr, q, slot
+
+
+def add_point(arr, kfs, octave=0):
+    """One more point in the arrays of a finished map, observed by kfs at each one's next feature -> its index"""
+    mp = len(arr["mp_bad"])
+    arr["mp_bad"] = np.append(arr["mp_bad"], np.uint8(0))
+    idx = [int(arr["kf_n"][kf]) for kf in kfs]
+    for kf, i in zip(kfs, idx):
+        assert i < arr["kf_mp"].shape[1]
+        arr["kf_mp"][kf, i], arr["kf_octave"][kf, i] = mp, octave
+        arr["kf_n"][kf] += 1
+    arr["obs_mp"] = np.append(arr["obs_mp"], np.full(len(kfs), mp, np.int32))
+    arr["obs_kf"] = np.append(arr["obs_kf"], np.asarray(kfs, np.int32))
+    arr["obs_idx"] = np.append(arr["obs_idx"], np.asarray(idx, np.int32))
+    return mp
+
+
 def pointer_like_order(g, K, used):
     """distinct, pointer-like std::map keys in an order unrelated to the slot order; 0 for unused slots"""
     order = np.zeros(K, np.uint64)
@@ -198,6 +325,14 @@ def _probe():
     print("device update_connections(1 key frame):   %.3f ms" % timed(lambda: G.update_connections(m, [cur])))
     print("device update_connections(30 key frames): %.3f ms" % timed(lambda: G.update_connections(m, list(range(cur - 15, cur + 15)))))
     print("device keyframe_culling:                  %.3f ms" % timed(lambda: G.keyframe_culling(m, cur)))
+    from .covis import DeviceTables
+    t = DeviceTables(dict(p, **window_tables(p, 7)))
+    G.reserve_window(m.n_mp, m.n_obs)
+    w = G.local_window(m, t, cur, False)
+    rc, hd, _, _ = G.window_header()
+    print("window of key frame %d: %s" % (cur, hd))
+    print("device local_window (collect, enqueued):  %.3f ms" % timed(lambda: G.local_window(m, t, cur, False)))
+    print("device window_scatter:                    %.3f ms" % timed(lambda: G.window_scatter(m, t, w)))
     print("errors counted: %d" % G.error_count())
     G.close()
     _probe_host(p, cur)
@@ -245,7 +380,41 @@ def _probe_host(p, cur):
     t = time.perf_counter()
     R.keyframe_culling(g, m, cur)
     cull = (time.perf_counter() - t) * 1e3
+    _probe_host_window(p, cur, g.get_vector_covisible_keyframes(cur), tests, d)
     print("Python model:           update_connections(1) %.1f ms, (30) %.1f ms, keyframe_culling %.1f ms (culling copies the observations)" % (one, thirty, cull))
+
+
+def write_window_blob(p, neighbours, path):
+    """the input of tests/cpp/window_map_ref.cpp (the bird side may be missing from p)"""
+    K = p["kf_mp"].shape[0]
+    bird = "bobs_kf" in p
+    q = p if bird else dict(p, kf_nb=np.zeros(K, np.int32), kf_mpb=np.zeros((K, 0), np.int32), mpb_bad=np.zeros(0, np.uint8),
+                            bobs_mpb=np.zeros(0, np.int32), bobs_kf=np.zeros(0, np.int32), bobs_idx=np.zeros(0, np.int32))
+    kf_bad = p["kf_bad"] if "kf_bad" in p else np.zeros(K, np.uint8)
+    with open(path, "wb") as f:
+        f.write(np.array([K, p["kf_mp"].shape[1], len(p["mp_bad"]), len(p["obs_kf"]), q["kf_mpb"].shape[1], len(q["mpb_bad"]),
+                          len(q["bobs_kf"]), len(neighbours)], np.int32).tobytes())
+        for a, dt in ((p["kf_n"], np.int32), (p["kf_mp"], np.int32), (p["mp_bad"], np.uint8), (p["obs_mp"], np.int32), (p["obs_kf"], np.int32),
+                      (p["obs_idx"], np.int32), (p["kf_order"], np.uint64), (kf_bad, np.uint8), (q["kf_nb"], np.int32), (q["kf_mpb"], np.int32),
+                      (q["mpb_bad"], np.uint8), (q["bobs_mpb"], np.int32), (q["bobs_kf"], np.int32), (q["bobs_idx"], np.int32),
+                      (neighbours, np.int32)):
+            f.write(np.ascontiguousarray(a, dt).tobytes())
+
+
+def _probe_host_window(p, cur, neighbours, tests, d):
+    """the literal std::map walk of the window (tests/cpp/window_map_ref.cpp) on one host core"""
+    import os
+    import subprocess
+    src = os.path.join(tests, "cpp", "window_map_ref.cpp")
+    if not os.path.exists(src):
+        print("host window figure: not measured")
+        return
+    exe, blob = os.path.join(d, "window_map_ref"), os.path.join(d, "window.bin")
+    subprocess.check_call(["g++", "-std=c++17", "-O2", src, "-o", exe])
+    write_window_blob(p, neighbours, blob)
+    out = dict(l.split(None, 1) for l in subprocess.check_output([exe, blob, str(cur), "0", "20"]).decode().splitlines() if " " in l)
+    print("C++ std::map, one core: local-BA window %s ms (%d local, %d fixed key frames, %d points, %d edges)" % (
+        out["ms"], len(out["local"].split()), len(out.get("fixed", "").split()), len(out["mp"].split()), len(out["obs_kf"].split())))
 
 
 if __name__ == "__main__":

@@ -398,6 +398,8 @@ struct fb_covis {
   Gr G{};
   void *scr = nullptr;
   size_t scrBytes = 0;
+  bool winValid = false;   // the scratch holds the lists of a fb_covis_local_window_dev (fb_covis_local_window_header reads them)
+  int winCapKf = 0;
   int ensure() {
     FB_TRY(fb::check_device());
     if (block) return FB_OK;
@@ -417,22 +419,23 @@ struct fb_covis {
   }
   int need(size_t bytes) {
     if (bytes <= scrBytes) return FB_OK;
-    if (scr) { FB_HIP(hipDeviceSynchronize()); FB_HIP(hipFree(scr)); scr = nullptr; scrBytes = 0; }
+    if (scr) { FB_HIP(hipDeviceSynchronize()); FB_HIP(hipFree(scr)); scr = nullptr; scrBytes = 0; winValid = false; }
     FB_HIP(hipMalloc(&scr, bytes));
     scrBytes = bytes;
     return FB_OK;
   }
-  // ranks of M.kf_order, then the edge list grouped by point; nothing is kept from an earlier call
-  int index(const fb_covis_map &M, size_t n_q, bool culling, Index *ix, hipStream_t s) {
+  // ranks of M.kf_order, then the edge list grouped by point; nothing is kept from an earlier call.  The index lies `head`
+  // bytes into the scratch (the window calls keep their own arrays, and a second index, in front of it).
+  int index(const fb_covis_map &M, size_t n_q, bool culling, Index *ix, hipStream_t s, size_t head = 0, bool ranks = true) {
     const size_t n_mp = M.n_mp, n_obs = M.n_obs, nb = (n_mp + 1 + CV_SCAN_TILE - 1) / CV_SCAN_TILE;
-    FB_TRY(need(scratch_bytes(n_mp, n_obs, n_q, K)));
-    uint8_t *b = static_cast<uint8_t *>(scr);
+    FB_TRY(need(head + scratch_bytes(n_mp, n_obs, n_q, K)));
+    uint8_t *b = static_cast<uint8_t *>(scr) + head;
     size_t off = 0;
     auto take = [&](size_t bytes) { uint8_t *p = b + off; off += up256(bytes); return p; };
     ix->start = (int32_t *)take((n_mp + 1) * 4); ix->fill = (int32_t *)take(n_mp * 4); ix->nobs = (int32_t *)take(n_mp * 4);
     ix->csr = (int32_t *)take(n_obs * 4); ix->dead = (int32_t *)take(n_obs * 4); ix->bsum = (int32_t *)take(nb * 4);
     ix->counter = (uint16_t *)take(n_q * K * 2);
-    k_cv_rank<<<(K + 255) / 256, 256, 0, s>>>(G, M.kf_order);
+    if (ranks) k_cv_rank<<<(K + 255) / 256, 256, 0, s>>>(G, M.kf_order);
     // start and fill are adjacent: one memset
     FB_HIP(hipMemsetAsync(ix->start, 0, (size_t)((uint8_t *)ix->nobs - (uint8_t *)ix->start), s));
     if (n_obs) k_cv_count<<<(unsigned)((n_obs + 255) / 256), 256, 0, s>>>(M, ix->start, G.err);
@@ -725,3 +728,5 @@ int fb_covis_keyframe_culling(fb_covis *g, const fb_covis_map *H, int32_t cur_sl
 }
 
 }  // extern "C"
+
+#include "covis_window.inc"

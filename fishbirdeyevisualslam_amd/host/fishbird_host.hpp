@@ -800,6 +800,108 @@ class CovisibilityGraph {
   int K_;
 };
 
+// ---- the local-BA window: head and tail of Optimizer::LocalBundleAdjustmentWithOdom (Optimizer.cc:2139-2227, :2574-2669) ----
+// WindowTables is what the window reads of the caller's key frames and points next to CovisibilityMap; the bird side is
+// used when birdStride > 0.  LocalWindow::Run is the whole call with host pointers: collect the window
+// (fb_covis_local_window), the caller's odometry edges between the local key frames (:2419-2495), fb_local_ba, then the
+// write-back and the erase lists.  A caller whose map lies in HBM makes the same four steps with the *_dev calls.
+struct WindowTables {
+  int birdStride = 0;
+  std::vector<float> kfTcw, mpXw, invLevelSigma2;     // [K][12], [points][3], [levels]
+  std::vector<uint8_t> kfBad, kfInit;                 // isBad(), isInit
+  std::vector<fb_keypoint> kfKeysUn;                  // [K][kpStride]
+  std::vector<int32_t> kfNb, kfMapPointsBird;         // [K], [K][birdStride]
+  std::vector<uint8_t> kfBirdOctave, mpbBad;
+  std::vector<float> kfBirdXc, mpbXw;                 // [K][birdStride][3], [bird points][3]
+  std::vector<int32_t> bobsMpb, bobsKf, bobsIdx;
+  WindowTables(const CovisibilityMap &m, int nLevels, int birdStride_ = 0)
+      : birdStride(birdStride_), kfTcw((size_t)m.maxKeyFrames * 12, 0.f), invLevelSigma2(nLevels, 1.f), kfBad(m.maxKeyFrames, 0),
+        kfInit(m.maxKeyFrames, 0), kfKeysUn((size_t)m.maxKeyFrames * m.kpStride), kfNb(m.maxKeyFrames, 0),
+        kfMapPointsBird((size_t)m.maxKeyFrames * birdStride_, -1), kfBirdOctave((size_t)m.maxKeyFrames * birdStride_, 0),
+        kfBirdXc((size_t)m.maxKeyFrames * birdStride_ * 3, 0.f) {}
+  fb_covis_kf_tables view() {
+    fb_covis_kf_tables t;
+    memset(&t, 0, sizeof(t));
+    t.kf_Tcw = kfTcw.data(); t.kf_bad = kfBad.data(); t.kf_init = kfInit.data(); t.kf_keys_un = kfKeysUn.data();
+    t.n_levels = (int32_t)invLevelSigma2.size(); t.inv_level_sigma2 = invLevelSigma2.data(); t.mp_xw = mpXw.data();
+    if (birdStride > 0) {
+      t.bird_stride = birdStride; t.kf_nb = kfNb.data(); t.kf_mpb = kfMapPointsBird.data(); t.kf_bird_octave = kfBirdOctave.data();
+      t.kf_bird_xc = kfBirdXc.data(); t.n_mpb = (int32_t)mpbBad.size(); t.mpb_bad = mpbBad.data(); t.mpb_xw = mpbXw.data();
+      t.n_bobs = (int32_t)bobsKf.size(); t.bobs_mpb = bobsMpb.data(); t.bobs_kf = bobsKf.data(); t.bobs_idx = bobsIdx.data();
+    }
+    return t;
+  }
+};
+
+class LocalWindow {
+ public:
+  struct Erase { int kf, point, idx, edge; };          // pKFi->EraseMapPointMatch(point at idx); point->EraseObservation(pKFi); obs_kf[edge] = -1
+  struct OdomEdge { int i, j; float Tij[12]; double info; };   // i, j: positions in localKeyFrames()
+  int nLocal = 0, nFixed = 0;
+  std::vector<int32_t> kfSlot, mpIndex, mpbIndex, obsKf, obsMp, obsSrc, bobsKf, bobsMpb, bobsSrc;
+  std::vector<uint8_t> kfFixed, obsOutlier, bobsOutlier;
+  std::vector<float> kfTcw, mpXw, mpbXw, obsUv, obsInvSigma2, bobsXc, bobsInvSigma2;
+  std::vector<Erase> toErase, toEraseBird;
+
+  // lLocalKeyFrames, lLocalMapPoints, lFixedCameras and the edges
+  void Collect(CovisibilityGraph &g, const CovisibilityMap &map, WindowTables &tables, int currentKF, bool bHaveBird) {
+    const fb_covis_map m = map.view();
+    const fb_covis_kf_tables t = tables.view();
+    const bool bird = bHaveBird && tables.birdStride > 0;
+    const size_t nKf = map.maxKeyFrames, nMp = map.mpBad.size(), nObs = map.obsKf.size(), nMpb = bird ? tables.mpbBad.size() : 0,
+                 nBobs = bird ? tables.bobsKf.size() : 0;
+    kfSlot.assign(nKf, -1); kfFixed.assign(nKf, 0); kfTcw.assign(nKf * 12, 0.f); mpIndex.assign(nMp + 1, -1); mpXw.assign(nMp * 3 + 1, 0.f);
+    obsKf.assign(nObs + 1, -1); obsMp.assign(nObs + 1, -1); obsSrc.assign(nObs + 1, -1); obsUv.assign(nObs * 2 + 1, 0.f);
+    obsInvSigma2.assign(nObs + 1, 0.f); mpbIndex.assign(nMpb + 1, -1); mpbXw.assign(nMpb * 3 + 1, 0.f); bobsKf.assign(nBobs + 1, -1);
+    bobsMpb.assign(nBobs + 1, -1); bobsSrc.assign(nBobs + 1, -1); bobsXc.assign(nBobs * 3 + 1, 0.f); bobsInvSigma2.assign(nBobs + 1, 0.f);
+    fb_covis_window w;
+    memset(&w, 0, sizeof(w));
+    w.cap_kf = (int32_t)nKf; w.cap_mp = (int32_t)nMp; w.cap_obs = (int32_t)nObs; w.cap_mpb = (int32_t)nMpb; w.cap_bobs = (int32_t)nBobs;
+    w.kf_slot = kfSlot.data(); w.kf_fixed = kfFixed.data(); w.kf_Tcw = kfTcw.data(); w.mp_index = mpIndex.data(); w.mp_xw = mpXw.data();
+    w.obs_kf = obsKf.data(); w.obs_mp = obsMp.data(); w.obs_src = obsSrc.data(); w.obs_uv = obsUv.data(); w.obs_inv_sigma2 = obsInvSigma2.data();
+    w.mpb_index = mpbIndex.data(); w.mpb_xw = mpbXw.data(); w.bobs_kf = bobsKf.data(); w.bobs_mpb = bobsMpb.data(); w.bobs_src = bobsSrc.data();
+    w.bobs_xc = bobsXc.data(); w.bobs_inv_sigma2 = bobsInvSigma2.data();
+    fb_covis_window_header h;
+    w.header = &h;
+    check(fb_covis_local_window(g.handle(), &m, &t, currentKF, bird ? 1 : 0, &w));
+    nLocal = h.n_local; nFixed = h.n_fixed;
+    kfSlot.resize(nLocal + nFixed); kfFixed.resize(nLocal + nFixed); kfTcw.resize((size_t)(nLocal + nFixed) * 12);
+    mpIndex.resize(h.n_mp); mpXw.resize((size_t)h.n_mp * 3); mpbIndex.resize(h.n_mpb); mpbXw.resize((size_t)h.n_mpb * 3);
+    obsKf.resize(h.n_obs); obsMp.resize(h.n_obs); obsSrc.resize(h.n_obs); obsUv.resize((size_t)h.n_obs * 2); obsInvSigma2.resize(h.n_obs);
+    bobsKf.resize(h.n_bobs); bobsMpb.resize(h.n_bobs); bobsSrc.resize(h.n_bobs); bobsXc.resize((size_t)h.n_bobs * 3); bobsInvSigma2.resize(h.n_bobs);
+  }
+  std::vector<int> localKeyFrames() const { return std::vector<int>(kfSlot.begin(), kfSlot.begin() + nLocal); }
+  std::vector<int> fixedCameras() const { return std::vector<int>(kfSlot.begin() + nLocal, kfSlot.end()); }
+
+  // the optimisation on the collected window (fb_local_ba; a defaults to the camera and weights the caller filled in)
+  void Optimize(fb_local_ba_args a, const std::vector<OdomEdge> &odom, const volatile uint8_t *pbStopFlag = nullptr) {
+    std::vector<int32_t> oi, oj;
+    std::vector<float> oT;
+    std::vector<double> oInfo;
+    for (const OdomEdge &e : odom) { oi.push_back(e.i); oj.push_back(e.j); oT.insert(oT.end(), e.Tij, e.Tij + 12); oInfo.push_back(e.info); }
+    obsOutlier.assign(obsKf.size() + 1, 0); bobsOutlier.assign(bobsKf.size() + 1, 0);
+    a.n_kf = nLocal + nFixed; a.kf_Tcw = kfTcw.data(); a.kf_fixed = kfFixed.data(); a.n_mp = (int32_t)mpIndex.size(); a.mp_xw = mpXw.data();
+    a.n_mpb = (int32_t)mpbIndex.size(); a.mpb_xw = mpbXw.data(); a.n_obs = (int32_t)obsKf.size(); a.obs_kf = obsKf.data(); a.obs_mp = obsMp.data();
+    a.obs_uv = obsUv.data(); a.obs_inv_sigma2 = obsInvSigma2.data(); a.n_bobs = (int32_t)bobsKf.size(); a.bobs_kf = bobsKf.data();
+    a.bobs_mpb = bobsMpb.data(); a.bobs_xc = bobsXc.data(); a.bobs_inv_sigma2 = bobsInvSigma2.data(); a.n_odom = (int32_t)oi.size();
+    a.odom_kf_i = oi.data(); a.odom_kf_j = oj.data(); a.odom_Tij = oT.data(); a.odom_info = oInfo.data(); a.stop_flag = pbStopFlag;
+    a.obs_outlier = obsOutlier.data(); a.bobs_outlier = bobsOutlier.data();
+    check(fb_local_ba(&a));
+  }
+
+  // :2574-2669: vToErase / vToEraseBird in edge order, SetPose of the local key frames, SetWorldPos of the local points
+  void WriteBack(const CovisibilityMap &map, WindowTables &tables) {
+    toErase.clear(); toEraseBird.clear();
+    for (size_t i = 0; i < obsKf.size() && i < obsOutlier.size(); i++)
+      if (obsOutlier[i]) toErase.push_back({kfSlot[obsKf[i]], mpIndex[obsMp[i]], map.obsIdx[obsSrc[i]], obsSrc[i]});
+    for (size_t i = 0; i < bobsKf.size() && i < bobsOutlier.size(); i++)
+      if (bobsOutlier[i]) toEraseBird.push_back({kfSlot[bobsKf[i]], mpbIndex[bobsMpb[i]], tables.bobsIdx[bobsSrc[i]], bobsSrc[i]});
+    for (int k = 0; k < nLocal; k++) std::copy(kfTcw.begin() + (size_t)k * 12, kfTcw.begin() + (size_t)k * 12 + 12, tables.kfTcw.begin() + (size_t)kfSlot[k] * 12);
+    for (size_t j = 0; j < mpIndex.size(); j++) std::copy(mpXw.begin() + j * 3, mpXw.begin() + j * 3 + 3, tables.mpXw.begin() + (size_t)mpIndex[j] * 3);
+    for (size_t j = 0; j < mpbIndex.size(); j++) std::copy(mpbXw.begin() + j * 3, mpbXw.begin() + j * 3 + 3, tables.mpbXw.begin() + (size_t)mpbIndex[j] * 3);
+  }
+};
+
 // ---- Sim3Solver (include/Sim3Solver.h) ---------------------------------------------------------------------------------
 // One candidate per object, as in the reference.  The first iterate() runs fb_sim3_solver once: every iteration up to
 // mRansacMaxIts lands in a table, and iterate(n, ...) replays rows (mnIterations, mnIterations + n] of it, so

@@ -937,6 +937,91 @@ int fb_covis_keyframe_culling(fb_covis *g, const fb_covis_map *map, int32_t cur_
                               int32_t *n, int32_t *slots, int32_t *n_redundant, int32_t *n_mps, uint8_t *culled,
                               uint8_t *mp_bad_after); /* host pointers, the map's arrays included */
 
+/* ---- the local-BA window (head and tail of Optimizer::LocalBundleAdjustment[WithOdom], Optimizer.cc:838-889,
+ * :2139-2227, the edge loops :2312-2417, the write-back :2574-2669) ----------------------------------------------------
+ * The caller's per-key-frame and per-point tables next to fb_covis_map.  Read-only for fb_covis_local_window_dev;
+ * fb_covis_window_scatter_dev writes kf_Tcw, mp_xw and mpb_xw.  The bird side mirrors fb_covis_map for MapPointBird and is
+ * skipped when bobs_kf is NULL; its tombstone and out-of-range rules are those of the front edge list.                  */
+typedef struct fb_covis_kf_tables {
+  float *kf_Tcw;                  /* [max_keyframes][12]                                                               */
+  const uint8_t *kf_bad;          /* [max_keyframes] isBad()                                                           */
+  const uint8_t *kf_init;         /* [max_keyframes] isInit (Optimizer.cc:2260)                                        */
+  const fb_keypoint *kf_keys_un;  /* [max_keyframes][kp_stride] mvKeysUn (x, y, octave are read)                       */
+  int32_t n_levels;               /* 1 .. FB_MAX_LEVELS                                                                */
+  const float *inv_level_sigma2;  /* [n_levels] mvInvLevelSigma2; an octave outside [0, n_levels) is clamped + counted */
+  float *mp_xw;                   /* [map.n_mp][3] GetWorldPos()                                                       */
+  int32_t bird_stride;            /* 1 .. FB_COVIS_MAX_STRIDE                                                          */
+  const int32_t *kf_nb;           /* [max_keyframes] mvKeysBird.size()                                                 */
+  const int32_t *kf_mpb;          /* [max_keyframes][bird_stride] mvpMapPointsBird[i] as an index, -1 = NULL           */
+  const uint8_t *kf_bird_octave;  /* [max_keyframes][bird_stride] mvKeysBird[i].octave (:2404)                         */
+  const float *kf_bird_xc;        /* [max_keyframes][bird_stride][3] mvKeysBirdCamXYZ                                  */
+  int32_t n_mpb;
+  const uint8_t *mpb_bad;         /* [n_mpb]                                                                           */
+  float *mpb_xw;                  /* [n_mpb][3]                                                                        */
+  int32_t n_bobs;
+  const int32_t *bobs_mpb, *bobs_kf, *bobs_idx;  /* [n_bobs]; bobs_kf < 0: erased entry                                */
+} fb_covis_kf_tables;
+
+typedef struct fb_covis_window_header {
+  int32_t n_local, n_fixed, n_mp, n_obs, n_mpb, n_bobs;
+  int32_t overflow;               /* != 0: a list did not fit its capacity; what fitted is written, nothing past it    */
+} fb_covis_window_header;
+
+/* The window as caller-provided arrays with their capacities: everything fb_local_ba_args needs except the odometry
+ * edges.  Key frames: the local ones in lLocalKeyFrames order (cur, then GetVectorCovisibleKeyFrames() without the bad
+ * ones), then the fixed ones in lFixedCameras order.  Points in lLocalMapPoints order.  Edges grouped by point in that
+ * order, within a point in ascending kf_order, edges of bad key frames left out (:2332, :2392).  The bird arrays may be
+ * NULL (cap_mpb = cap_bobs = 0) when the call is made without the bird side.                                            */
+typedef struct fb_covis_window {
+  int32_t cap_kf, cap_mp, cap_obs, cap_mpb, cap_bobs;
+  int32_t *kf_slot;               /* [cap_kf]                                                                          */
+  uint8_t *kf_fixed;              /* [cap_kf] isInit of a local key frame, 1 for a fixed one                           */
+  float *kf_Tcw;                  /* [cap_kf][12] gathered                                                             */
+  int32_t *mp_index;              /* [cap_mp] map point indices                                                        */
+  float *mp_xw;                   /* [cap_mp][3] gathered                                                              */
+  int32_t *obs_kf, *obs_mp;       /* [cap_obs] indices into kf_slot / mp_index                                         */
+  int32_t *obs_src;               /* [cap_obs] the edge's index in the map's edge list                                 */
+  float *obs_uv;                  /* [cap_obs][2] mvKeysUn[idx].pt                                                     */
+  float *obs_inv_sigma2;          /* [cap_obs]                                                                         */
+  int32_t *mpb_index;             /* [cap_mpb]                                                                         */
+  float *mpb_xw;                  /* [cap_mpb][3]                                                                      */
+  int32_t *bobs_kf, *bobs_mpb, *bobs_src; /* [cap_bobs]                                                                */
+  float *bobs_xc;                 /* [cap_bobs][3] mvKeysBirdCamXYZ[idx]                                               */
+  float *bobs_inv_sigma2;         /* [cap_bobs]                                                                        */
+  fb_covis_window_header *header; /* [1]                                                                               */
+} fb_covis_window;
+
+/* Scratch for the window calls, ahead of time (they grow it on demand like the other map calls): the map's sizes as
+ * for fb_covis_reserve, plus the bird side's (0, 0 without it).                                                         */
+int fb_covis_reserve_window(fb_covis *g, int32_t n_mp, int32_t n_obs, int32_t n_mpb, int32_t n_bobs);
+
+/* Collects the window of cur_slot from the graph's current rows and the map (device pointers throughout); enqueues only.
+ * Local points: the local key frames in list order, features ascending, the first occurrence of each non-NULL, non-bad
+ * point (:2156-2170).  Fixed key frames: the local points in order, each point's observers in ascending kf_order, the
+ * first occurrence of a key frame that is not in the neighbour list; a bad neighbour is in neither list (it is marked at
+ * :2149 before the isBad test), a bad observer is marked and not listed (:2181-2186); with_bird != 0 continues the fixed
+ * list with the bird walk (:2213-2226).  Precondition: cur_slot is not the key frame with mnId == 0 (for it the
+ * reference's initial mnBA*ForKF == 0 marks make the window degenerate, and LocalMapping::Run never optimises it).
+ * Out-of-range entries are skipped and counted as in the other map calls.                                              */
+int fb_covis_local_window_dev(fb_covis *g, const fb_covis_map *map, const fb_covis_kf_tables *tables, int32_t cur_slot,
+                              int32_t with_bird, const fb_covis_window *out, void *stream);
+/* The one synchronisation: the header of the handle's last fb_covis_local_window_dev, and kf_slot / kf_fixed (host
+ * arrays of that call's cap_kf entries, either may be NULL; entries past n_local + n_fixed are -1 / 0), which
+ * fb_local_ba_dev and the host's odometry chain need.  FB_ERR_CAPACITY when the window overflowed a capacity.           */
+int fb_covis_local_window_header(fb_covis *g, fb_covis_window_header *header, int32_t *kf_slot, uint8_t *kf_fixed, void *stream);
+/* host pointers throughout (out->header included); FB_ERR_CAPACITY as above                                             */
+int fb_covis_local_window(fb_covis *g, const fb_covis_map *map, const fb_covis_kf_tables *tables, int32_t cur_slot,
+                          int32_t with_bird, const fb_covis_window *out);
+
+/* After the optimisation (:2574-2669), on the window's device arrays: kf_Tcw of the LOCAL key frames and mp_xw / mpb_xw
+ * go back into the tables by slot / index, and the edges flagged in d_obs_outlier / d_bobs_outlier (fb_local_ba_args;
+ * NULL = none) are compacted in edge order into d_erase / d_berase as rows (key frame slot, point index, feature index,
+ * edge index in the map's list), [cap_obs][4] / [cap_bobs][4], their counts in d_n_erase[0] / d_n_erase[1].
+ * EraseMapPointMatch, EraseObservation and UpdateNormalAndDepth stay with the host on those lists.                      */
+int fb_covis_window_scatter_dev(fb_covis *g, const fb_covis_map *map, const fb_covis_kf_tables *tables, const fb_covis_window *win,
+                                const uint8_t *d_obs_outlier, const uint8_t *d_bobs_outlier, int32_t *d_n_erase,
+                                int32_t *d_erase, int32_t *d_berase, void *stream);
+
 /* ======================================================================== */
 /* Frame geometry either side of the matchers (src/Frame.cc)                 */
 /* ======================================================================== */
@@ -1317,7 +1402,8 @@ int fb_local_ba(const fb_local_ba_args *args); /* host pointers */
 /* The same with the graph resident in HBM (the LocalMapping-side chain hands its results over on the device: triangulation
  * matches -> new points -> fuse -> local BA, LocalMapping.cc:62-99): kf_Tcw, mp_xw, mpb_xw, every obs_* / bobs_* array and the
  * two outlier arrays are DEVICE pointers; kf_fixed, the odometry edges (odom_*: at most 3 n_kf of them) and stop_flag stay
- * HOST pointers (the host chooses the window, Optimizer.cc:2139-2227, 2419-2495).  The edge records, the CSR by landmark / by
+ * HOST pointers (the window comes from the host or from fb_covis_local_window_dev, Optimizer.cc:2139-2227; the host builds
+ * the odometry chain, :2419-2495).  The edge records, the CSR by landmark / by
  * key frame and the duplicate check are built by kernels on `stream`, ordered behind the producers of the arrays; results are
  * written back on `stream`.  The call returns when the optimisation has finished (the schedule's length is data dependent:
  * the host watches the device-resident Levenberg-Marquardt loop), like the reference's blocking call.
