@@ -1,4 +1,4 @@
-// ba.hip -- Optimizer::LocalBundleAdjustment / LocalBundleAdjustmentWithOdom on gfx950.
+// ba.hip -- Optimizer::LocalBundleAdjustment / LocalBundleAdjustmentWithOdom / BundleAdjustmentWithOdom on gfx950.
 //
 // Replaces (reference file:line):
 //   Optimizer::LocalBundleAdjustment            src/Optimizer.cc:838-1165
@@ -20,8 +20,19 @@
 //                   v_mfma_f64_16x16x4_f64; upper-triangular 16x16 tiles only, like g2o
 //   k_ba_solve      S = Hpp + lambda I - sum S_part, dense LDL^T in LDS, triangular solves in one wave
 //   k_ba_update     landmark back-substitution, exp-map pose update, trial state, scale term
-// The accept/reject logic of Levenberg-Marquardt runs on the host between trials (a few scalars
-// are read back per trial); the abort flag (pbStopFlag) is polled there, between iterations.
+// Two schedules drive these kernels:
+//   device-resident (the default up to 23 free key frames, and always for fb_local_ba_dev): the k_ba_*_c twins of the
+//       kernels above read the Levenberg-Marquardt state from a control block in HBM and k_ba_control takes the
+//       accept / reject decision at the end of each slot; the host enqueues slots in batches, forwards the abort flag
+//       (pbStopFlag) on a side stream and reads the control block back once per batch;
+//   host-driven (more than 23 free key frames with the HBM-resident reduced system of ba_big.inc, FB_BA_TRACE,
+//       FB_BA_HOST_LM): the accept / reject logic runs on the host between trials (a few scalars are read back per
+//       trial) and the abort flag is polled there.
+// This file holds the kernels; the host side of the translation unit is included at its end:
+//   ba_exchange.inc  RCCL / callback transport of the landmark-sharded BA, fb_rccl_*
+//   ba_big.inc       kernels and host pieces of the HBM-resident reduced system
+//   ba_graph.inc     layout of the staged graph, host builder, device builder (k_bld_*), odometry CSR, argument agreement
+//   ba_driver.inc    plan, device binding, both schedules, result hand-over, local_ba_impl, the extern "C" entry points
 #include "fb_common.h"
 #include "fb_primitives.h"
 
@@ -1473,89 +1484,6 @@ __global__ void k_ba_export_c(int n_kf, int npt, St2 st, const BACtl *c, const u
 
 #define BA_UP(buf, vec) FB_TRY(buf.upload((vec).data(), (vec).size() * sizeof((vec)[0])))
 
-#include "ba_big.inc"
-
-// ---- exchange transport of the landmark-sharded BA ------------------------------------------------------------------
-// RCCL: the all-reduces are enqueued on the BA's stream and work on device buffers (nothing is staged through the host);
-// the entry points are resolved at run time from the RCCL the process already has (torch's librccl.so.1 when the host is
-// Python, /opt/rocm/lib otherwise), so the library carries no link-time dependency and single-GPU users never load it.
-// HOST: the fb_allreduce_fn callback of fb_local_ba_sharded (gloo in the CPU tests; host buffer).
-#include <dlfcn.h>
-namespace {
-struct RcclApi {
-  void *lib = nullptr;
-  int (*GetUniqueId)(void *) = nullptr;                              // ncclGetUniqueId(ncclUniqueId *)
-  int (*CommInitRank)(void **, int, fb_rccl_unique_id, int) = nullptr; // ncclCommInitRank(comm *, nranks, id BY VALUE, rank)
-  int (*CommDestroy)(void *) = nullptr;
-  int (*AllReduce)(const void *, void *, size_t, int, int, void *, hipStream_t) = nullptr;
-  const char *(*GetErrorString)(int) = nullptr;
-  int (*CommCount)(void *, int *) = nullptr;
-  int (*CommUserRank)(void *, int *) = nullptr;
-};
-RcclApi *rccl_api() {
-  // loaded once (a function-local static is initialised thread-safely)
-  static RcclApi api = [] {
-    RcclApi a;
-    for (const char *name : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"}) {
-      a.lib = dlopen(name, RTLD_NOW | RTLD_LOCAL);
-      if (a.lib) break;
-    }
-    if (a.lib) {
-      a.GetUniqueId = reinterpret_cast<decltype(a.GetUniqueId)>(dlsym(a.lib, "ncclGetUniqueId"));
-      a.CommInitRank = reinterpret_cast<decltype(a.CommInitRank)>(dlsym(a.lib, "ncclCommInitRank"));
-      a.CommDestroy = reinterpret_cast<decltype(a.CommDestroy)>(dlsym(a.lib, "ncclCommDestroy"));
-      a.AllReduce = reinterpret_cast<decltype(a.AllReduce)>(dlsym(a.lib, "ncclAllReduce"));
-      a.GetErrorString = reinterpret_cast<decltype(a.GetErrorString)>(dlsym(a.lib, "ncclGetErrorString"));
-      a.CommCount = reinterpret_cast<decltype(a.CommCount)>(dlsym(a.lib, "ncclCommCount"));
-      a.CommUserRank = reinterpret_cast<decltype(a.CommUserRank)>(dlsym(a.lib, "ncclCommUserRank"));
-      if (!a.GetUniqueId || !a.CommInitRank || !a.CommDestroy || !a.AllReduce) a.lib = nullptr;
-    }
-    return a;
-  }();
-  return api.lib ? &api : nullptr;
-}
-constexpr int kNcclDouble = 8, kNcclSum = 0;  // ncclFloat64, ncclSum (rccl.h)
-
-struct Xchg {
-  int world = 1;
-  void *comm = nullptr;            // ncclComm_t, or
-  fb_allreduce_fn cb = nullptr;    // host callback
-  void *ctx = nullptr;
-  bool active() const { return world > 1 || comm != nullptr; }  // a 1-rank communicator still goes through RCCL (tests)
-  // in-place sum over the ranks of n doubles in DEVICE memory, ordered behind the work already on stream s
-  // (src may differ from dbuf: out-of-place, the source stays as it is)
-  int sum_dev(double *dbuf, size_t n, hipStream_t s, std::vector<double> &scratch, const double *src = nullptr) const {
-    if (!src) src = dbuf;
-    if (!active() || n == 0) return FB_OK;
-    if (comm) {
-      const int rc = rccl_api()->AllReduce(src, dbuf, n, kNcclDouble, kNcclSum, comm, s);
-      if (rc != 0) { fb::set_error("fb_local_ba_sharded: ncclAllReduce failed: %s", rccl_api()->GetErrorString ? rccl_api()->GetErrorString(rc) : "?"); return FB_ERR_HIP; }
-      return FB_OK;
-    }
-    scratch.resize(n);
-    FB_HIP(hipStreamSynchronize(s));
-    FB_HIP(hipMemcpy(scratch.data(), src, n * 8, hipMemcpyDeviceToHost));
-    if (cb(ctx, scratch.data(), (int32_t)n, 0) != 0) { fb::set_error("fb_local_ba_sharded: all-reduce callback failed"); return FB_ERR_ARG; }
-    FB_HIP(hipMemcpy(dbuf, scratch.data(), n * 8, hipMemcpyHostToDevice));
-    return FB_OK;
-  }
-  // in-place reduction of n doubles in HOST memory (op 0 = sum, 1 = max); the host-driven schedule uses it
-  int reduce_host(double *hbuf, int n, int op) const {
-    if (!active() || n <= 0) return FB_OK;
-    if (cb) {
-      if (cb(ctx, hbuf, n, op) != 0) { fb::set_error("fb_local_ba_sharded: all-reduce callback failed"); return FB_ERR_ARG; }
-      return FB_OK;
-    }
-    fb::DevBuf d;
-    FB_TRY(d.upload(hbuf, (size_t)n * 8));
-    const int rc = rccl_api()->AllReduce(d.p, d.p, (size_t)n, kNcclDouble, op == 0 ? kNcclSum : 2 /* ncclMax */, comm, nullptr);
-    if (rc != 0) { fb::set_error("fb_local_ba_sharded: ncclAllReduce failed (%d)", rc); return FB_ERR_HIP; }
-    FB_HIP(hipStreamSynchronize(nullptr));
-    return d.download(hbuf, (size_t)n * 8);
-  }
-};
-}  // namespace
-
 #ifdef FB_BA_STAMPS
 extern "C" int fb_ba_debug_stamps(uint64_t *dst16) {  // probe build only: copies and clears the phase accumulators of the solve
   unsigned long long h[16], z[16] = {0};
@@ -1566,905 +1494,7 @@ extern "C" int fb_ba_debug_stamps(uint64_t *dst16) {  // probe build only: copie
 }
 #endif
 
-extern "C" int fb_rccl_get_unique_id(fb_rccl_unique_id *id) {
-  FB_ARG(id);
-  RcclApi *r = rccl_api();
-  if (!r) { fb::set_error("fb_rccl_get_unique_id: no RCCL in this process (librccl.so.1 not found)"); return FB_ERR_NODEVICE; }
-  const int rc = r->GetUniqueId(id);
-  if (rc != 0) { fb::set_error("ncclGetUniqueId failed (%d)", rc); return FB_ERR_HIP; }
-  return FB_OK;
-}
-extern "C" int fb_rccl_comm_info(void *comm, int *count, int *rank) {
-  FB_ARG(comm && count && rank);
-  RcclApi *r = rccl_api();
-  if (!r || !r->CommCount || !r->CommUserRank) { fb::set_error("fb_rccl_comm_info: ncclCommCount / ncclCommUserRank not available"); return FB_ERR_NODEVICE; }
-  int rc = r->CommCount(comm, count);
-  if (rc == 0) rc = r->CommUserRank(comm, rank);
-  if (rc != 0) { fb::set_error("fb_rccl_comm_info: RCCL error %d", rc); return FB_ERR_HIP; }
-  return FB_OK;
-}
-extern "C" int fb_rccl_comm_init(const fb_rccl_unique_id *id, int rank, int world, void **comm) {
-  FB_TRY(fb::check_device());
-  FB_ARG(id && comm && world >= 1 && rank >= 0 && rank < world);
-  RcclApi *r = rccl_api();
-  if (!r) { fb::set_error("fb_rccl_comm_init: no RCCL in this process (librccl.so.1 not found)"); return FB_ERR_NODEVICE; }
-  const int rc = r->CommInitRank(comm, world, *id, rank);
-  if (rc != 0) { fb::set_error("ncclCommInitRank failed: %s", r->GetErrorString ? r->GetErrorString(rc) : "?"); return FB_ERR_HIP; }
-  return FB_OK;
-}
-extern "C" int fb_rccl_comm_destroy(void *comm) {
-  RcclApi *r = rccl_api();
-  if (comm && r) r->CommDestroy(comm);
-  return FB_OK;
-}
-
-// optimisation schedule: LocalBundleAdjustment[WithOdom] = optimize(5) robust, chi2 gate, optimize(10) plain
-// (Optimizer.cc:2504-2560); BundleAdjustmentWithOdom = ONE optimize(nIterations), robust iff bRobust, no gate (:2048-2050)
-struct BASchedule {
-  int its1, robust1;
-  bool gate;
-  int its2;
-  double delta;  // Huber delta: sqrt(5.991) local (:2290), sqrt(5.99) global (:1836)
-};
-struct DevIn { hipStream_t stream = nullptr; };  // fb_local_ba_dev: the big arrays of fb_local_ba_args are DEVICE pointers
-static int local_ba_impl(const fb_local_ba_args *A, int rank, const Xchg &X, const BASchedule &sc, const DevIn *dv = nullptr);
-
-// ---- device-side graph builder (fb_local_ba_dev): what local_ba_impl's host passes do, as kernels ----------------------
-namespace {
-struct BuildIn {
-  const int32_t *obs_kf, *obs_mp; const float *obs_uv, *obs_inv;
-  const int32_t *bobs_kf, *bobs_mpb; const float *bobs_xc, *bobs_inv;
-  const float *kf_Tcw, *mp_xw, *mpb_xw;
-  int nF, nB, n_kf, n_mp, n_mpb, odom;
-  double wF, wB;
-};
-// per edge: the flat edge record (Optimizer.cc:2346-2367, 2399-2414) + the counts of the two CSR structures
-__global__ void k_bld_edges(BuildIn I, const int *poseIdx, int *e_pt, int *e_kf, int *e_pj, uint8_t *e_type, uint8_t *e_level,
-                            float *e_meas, double *e_info, int *lm_cnt, int *ps_cnt, int *bad) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= I.nF + I.nB) return;
-  int pt, kf;
-  if (e < I.nF) {
-    pt = I.obs_mp[e]; kf = I.obs_kf[e];
-    if (!(pt >= 0 && pt < I.n_mp && kf >= 0 && kf < I.n_kf)) { atomicOr(bad, 1); pt = 0; kf = 0; }
-    e_type[e] = T_PROJ;
-    e_meas[3 * e] = I.obs_uv[2 * e]; e_meas[3 * e + 1] = I.obs_uv[2 * e + 1]; e_meas[3 * e + 2] = 0.0f;
-    e_info[e] = I.odom ? (1.0 * (double)I.obs_inv[e]) * I.wF : (double)I.obs_inv[e];
-  } else {
-    const int i = e - I.nF;
-    int pb = I.bobs_mpb[i];
-    kf = I.bobs_kf[i];
-    if (!(pb >= 0 && pb < I.n_mpb && kf >= 0 && kf < I.n_kf)) { atomicOr(bad, 1); pb = 0; kf = 0; }
-    pt = I.n_mp + pb;
-    e_type[e] = T_XYZ;
-    for (int k = 0; k < 3; k++) e_meas[3 * e + k] = I.bobs_xc[3 * i + k];
-    e_info[e] = (1.0 * (double)I.bobs_inv[i]) * I.wB;
-  }
-  e_pt[e] = pt; e_kf[e] = kf; e_level[e] = 0;
-  const int pj = poseIdx[kf];
-  e_pj[e] = pj;
-  atomicAdd(&lm_cnt[pt + 1], 1);
-  if (pj >= 0) atomicAdd(&ps_cnt[pj + 1], 1);
-}
-__global__ void k_bld_state(BuildIn I, SE3 *poses, double *pts, float *kfT) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < I.n_kf) {
-    poses[i] = fb::se3_from_float12(I.kf_Tcw + 12 * i);
-    for (int k = 0; k < 12; k++) kfT[12 * i + k] = I.kf_Tcw[12 * i + k];
-  }
-  if (i < 3 * I.n_mp) pts[i] = I.mp_xw[i];
-  if (i < 3 * I.n_mpb) pts[3 * I.n_mp + i] = I.mpb_xw[i];
-}
-// in-place: cnt[0] = 0, cnt[i + 1] = count of bucket i  ->  exclusive starts; one workgroup, n up to millions
-__global__ __launch_bounds__(1024) void k_bld_scan(int *cnt, int n, int *fill) {
-  __shared__ int s_w[16], s_run;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  if (tid == 0) s_run = 0;
-  __syncthreads();
-  for (int base = 0; base <= n; base += 1024) {
-    const int i = base + tid;
-    const int v = i <= n ? cnt[i] : 0;
-    const int inc = fb::wave_incl_scan(v);
-    if (lane == 63) s_w[wv] = inc;
-    __syncthreads();
-    int off = s_run;
-    for (int w = 0; w < wv; w++) off += s_w[w];
-    const int incl = off + inc;
-    if (i <= n) { cnt[i] = incl; if (fill && i < n) fill[i] = incl; }  // start of bucket i = inclusive sum up to cnt[i] (cnt[0] = 0)
-    __syncthreads();
-    if (tid == 1023) s_run = incl;
-    __syncthreads();
-  }
-}
-__global__ void k_bld_scatter(int nE, const int *e_pt, const int *e_pj, int *fillL, int *fillP, int *lm_edges, int *ps_edges) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= nE) return;
-  lm_edges[atomicAdd(&fillL[e_pt[e]], 1)] = e;
-  if (e_pj[e] >= 0) ps_edges[atomicAdd(&fillP[e_pj[e]], 1)] = e;
-}
-// a landmark's edges in ascending edge index (the order the host builder produces: sums must not depend on the atomics'
-// order) + a key frame observes a point at most once (map<KeyFrame*, size_t>)
-__global__ void k_bld_sort_lm(int npt, const int *lm_start, int *lm_edges, const int *e_kf, int *bad) {
-  const int l = blockIdx.x * blockDim.x + threadIdx.x;
-  if (l >= npt) return;
-  const int a0 = lm_start[l], a1 = lm_start[l + 1];
-  for (int i = a0 + 1; i < a1; i++) {
-    const int v = lm_edges[i];
-    int j = i - 1;
-    while (j >= a0 && lm_edges[j] > v) { lm_edges[j + 1] = lm_edges[j]; j--; }
-    lm_edges[j + 1] = v;
-  }
-  for (int i = a0; i < a1; i++)
-    for (int j = i + 1; j < a1; j++)
-      if (e_kf[lm_edges[i]] == e_kf[lm_edges[j]]) atomicOr(bad, 2);
-}
-// a key frame's edges in ascending edge index: bitonic sort of its segment in LDS (one workgroup per free key frame)
-__global__ __launch_bounds__(1024) void k_bld_sort_ps(const int *ps_start, int *ps_edges, int cap, int *bad) {
-  extern __shared__ int s_v[];
-  const int k = blockIdx.x, tid = threadIdx.x;
-  const int a0 = ps_start[k], n = ps_start[k + 1] - a0;
-  int m = 1;
-  while (m < n) m <<= 1;
-  if (m > cap) { if (tid == 0) atomicOr(bad, 4); return; }  // one key frame with more observations than the LDS sort holds
-  for (int i = tid; i < m; i += 1024) s_v[i] = i < n ? ps_edges[a0 + i] : 0x7fffffff;
-  __syncthreads();
-  fb::bitonic_sort(s_v, m, tid, 1024);
-  for (int i = tid; i < n; i += 1024) ps_edges[a0 + i] = s_v[i];
-}
-__global__ void k_bld_check(const int *bad, BACtl *c) {
-  if (*bad) { c->badArgs = *bad; c->phase = 2; }
-}
-}  // namespace
-static const BASchedule kLocalSchedule = {5, 1, true, 10, (double)(float)sqrt(5.991)};
-
-extern "C" int fb_local_ba(const fb_local_ba_args *A) { return local_ba_impl(A, 0, Xchg(), kLocalSchedule); }
-extern "C" int fb_local_ba_dev(const fb_local_ba_args *A, void *stream) {
-  DevIn dv;
-  dv.stream = fb::as_stream(stream);
-  return local_ba_impl(A, 0, Xchg(), kLocalSchedule, &dv);
-}
-
-extern "C" int fb_global_ba(const fb_local_ba_args *A, int n_iterations, int robust) {
-  FB_ARG(n_iterations >= 0);
-  const BASchedule sc = {n_iterations, robust ? 1 : 0, false, 0, (double)(float)sqrt(5.99)};
-  return local_ba_impl(A, 0, Xchg(), sc);
-}
-
-extern "C" int fb_local_ba_sharded(const fb_local_ba_args *A, int rank, int world, fb_allreduce_fn allreduce, void *ctx) {
-  FB_ARG(world >= 1 && rank >= 0 && rank < world && (world == 1 || allreduce));
-  Xchg X;
-  X.world = world; X.cb = allreduce; X.ctx = ctx;
-  return local_ba_impl(A, rank, X, kLocalSchedule);
-}
-
-extern "C" int fb_local_ba_sharded_rccl(const fb_local_ba_args *A, int rank, int world, void *comm) {
-  FB_ARG(world >= 1 && rank >= 0 && rank < world && comm);
-  if (!rccl_api()) { fb::set_error("fb_local_ba_sharded_rccl: no RCCL in this process"); return FB_ERR_NODEVICE; }
-  Xchg X;
-  X.world = world; X.comm = comm;
-  return local_ba_impl(A, rank, X, kLocalSchedule);
-}
-
-// Landmark-partitioned BA: rank r owns the landmarks l with l % world == r and all their edges, the
-// odometry edges live on rank 0, the keyframe state is replicated.  Per LM trial two small all-reduces: the
-// Schur-reduced system (after k_ba_schur) and [Hpp, bp, chi2, scale] (after the linearisation at the trial state).
-// per host thread and device: the side stream for the abort request, the pinned mirror of the control block and the event
-// the host waits on (concurrent callers must not share them; a stream belongs to its device).  fb_shutdown releases the
-// calling thread's set.
-struct PerDev { hipStream_t sAux = nullptr; BACtl *hCtl = nullptr; hipEvent_t evDone = nullptr; };
-static thread_local PerDev g_perDev[64];
-
-extern "C" int fb_shutdown(void) {
-  int cur = 0;
-  const bool have = hipGetDevice(&cur) == hipSuccess;
-  for (int d = 0; d < 64; d++) {
-    PerDev &pd = g_perDev[d];
-    if (!pd.sAux && !pd.hCtl && !pd.evDone) continue;
-    if (hipSetDevice(d) != hipSuccess) continue;
-    if (pd.evDone) (void)hipEventDestroy(pd.evDone);
-    if (pd.hCtl) (void)hipHostFree(pd.hCtl);
-    if (pd.sAux) (void)hipStreamDestroy(pd.sAux);
-    pd = PerDev();
-  }
-  if (have) (void)hipSetDevice(cur);
-  fb::pool_release();
-  return FB_OK;
-}
-
-static int local_ba_impl(const fb_local_ba_args *A, int rank, const Xchg &X, const BASchedule &sc, const DevIn *dv) {
-  FB_TRY(fb::check_device());
-  const int world = X.world;
-  const bool timing = getenv("FB_BA_TIMING") != nullptr;  // host-side phase times on stderr (probe)
-  const auto tStart = std::chrono::steady_clock::now();
-  auto lap = [&](const char *what) {
-    if (timing) fprintf(stderr, "[fb_local_ba] %-28s %8.1f us\n", what, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tStart).count());
-  };
-  const bool sharded = X.active();
-  const bool devIn = dv != nullptr;   // observations / poses / points / result arrays live in HBM (fb_local_ba_dev)
-  hipStream_t s0 = devIn ? dv->stream : nullptr;
-  FB_ARG(!(devIn && sharded));
-  auto reduce = [&](double *buf, int n, int op) -> int { return sharded ? X.reduce_host(buf, n, op) : FB_OK; };
-  // (sharded: a rank must not return alone on ITS argument error -- the others would wait for it in the first exchange;
-  // the agreement block below reports it on every rank together)
-  if (!sharded) FB_ARG(A && A->n_kf > 0 && A->n_mp >= 0 && A->n_mpb >= 0 && A->n_obs >= 0 && A->kf_Tcw && A->kf_fixed);
-  // Optimizer.cc:902-906 / 2498-2500.  Sharded: a rank must not leave on its OWN view of the flag (the others would wait for
-  // it in the first exchange): every stop decision below goes through a reduction
-  if (!sharded && A->stop_flag && *A->stop_flag) return FB_OK;
-  const bool argsOk = A && A->n_kf > 0 && A->n_mp >= 0 && A->n_mpb >= 0 && A->n_obs >= 0 && A->kf_Tcw && A->kf_fixed;
-  if (sharded) {
-    // Agreement on the arguments before the first exchange: a rank that rejected its input alone would leave the others
-    // waiting in a collective.  (The same checks run again below, where they can no longer fail.)
-    int bad = argsOk ? 0 : 1;
-    if (!bad) {
-      const bool od = A->with_odom != 0;
-      int free = 0;
-      for (int k = 0; k < A->n_kf; k++) free += A->kf_fixed[k] ? 0 : 1;
-      if (6 * free > 4096) bad = 1;
-      std::vector<long long> pairs;
-      pairs.reserve((size_t)A->n_obs + (od ? A->n_bobs : 0));
-      for (int i = 0; i < A->n_obs && !bad; i++) {
-        if (!(A->obs_mp[i] >= 0 && A->obs_mp[i] < A->n_mp && A->obs_kf[i] >= 0 && A->obs_kf[i] < A->n_kf)) bad = 1;
-        else pairs.push_back(((long long)A->obs_mp[i] << 32) | (unsigned)A->obs_kf[i]);
-      }
-      for (int i = 0; od && i < A->n_bobs && !bad; i++) {
-        if (!(A->bobs_mpb[i] >= 0 && A->bobs_mpb[i] < A->n_mpb && A->bobs_kf[i] >= 0 && A->bobs_kf[i] < A->n_kf)) bad = 1;
-        else pairs.push_back(((long long)(A->n_mp + A->bobs_mpb[i]) << 32) | (unsigned)A->bobs_kf[i]);
-      }
-      for (int i = 0; od && rank == 0 && i < A->n_odom && !bad; i++)
-        if (!(A->odom_kf_i[i] >= 0 && A->odom_kf_i[i] < A->n_kf && A->odom_kf_j[i] >= 0 && A->odom_kf_j[i] < A->n_kf)) bad = 1;
-      if (!bad) {
-        std::sort(pairs.begin(), pairs.end());
-        if (std::adjacent_find(pairs.begin(), pairs.end()) != pairs.end()) bad = 1;
-      }
-    }
-    double v = bad;
-    FB_TRY(X.reduce_host(&v, 1, 1));
-    if (v > 0.0) {
-      fb::set_error(bad ? "fb_local_ba_sharded: bad arguments on this rank" : "fb_local_ba_sharded: another rank rejected its arguments");
-      return FB_ERR_ARG;
-    }
-  }
-  auto stopped = [&]() -> bool {
-    double v = (A->stop_flag && *A->stop_flag) ? 1.0 : 0.0;
-    if (sharded && X.reduce_host(&v, 1, 1) != FB_OK) return true;
-    return v > 0.0;
-  };
-  const bool odom = A->with_odom != 0;
-  const int n_kf = A->n_kf, n_mp = A->n_mp, n_mpb = odom ? A->n_mpb : 0;
-  const int npt = A->n_mp + A->n_mpb;  // bird points keep their slots even when unused
-  const int nF = A->n_obs, nB = odom ? A->n_bobs : 0, nE = nF + nB, nO = (odom && rank == 0) ? A->n_odom : 0;
-  (void)n_mpb;
-  // ---- host preprocessing: indices, CSR by landmark / pose.  Everything the kernels read is laid out in ONE host staging
-  //      buffer and goes to the device with one copy (two dozen small synchronous copies were a quarter of a millisecond)
-  std::vector<int> poseIdx(n_kf, -1);
-  int np = 0;
-  for (int k = 0; k < n_kf; k++) if (!A->kf_fixed[k]) poseIdx[k] = np++;
-  const int P6 = 6 * np;
-  if (P6 > 4096) { fb::set_error("fb_local_ba: more than 682 free keyframes"); return FB_ERR_CAPACITY; }
-  static thread_local std::vector<uint8_t> stage;
-  size_t stageBytes = 0;
-  auto reserve = [&](size_t bytes) { const size_t off = stageBytes; stageBytes += (bytes + 255) & ~(size_t)255; return off; };
-  const int nE1 = std::max(nE, 1), nO1 = std::max(nO, 1);
-  // small, host-built arrays first: the device-input variant uploads only this header
-  const size_t o_poseIdx = reserve((size_t)n_kf * 4), o_fixed = reserve(n_kf), o_oi = reserve((size_t)nO1 * 4), o_oj = reserve((size_t)nO1 * 4),
-               o_oz = reserve((size_t)nO1 * sizeof(SE3)), o_oinfo = reserve((size_t)nO1 * 8), o_ods = reserve((size_t)(np + 1) * 4),
-               o_ode = reserve((size_t)(2 * nO1) * 4), o_ctl = reserve(sizeof(BACtl)), o_abort = reserve(16);
-  const size_t headerBytes = stageBytes;   // (the control block and the abort word ride in the header: no separate synchronous copies)
-  const size_t o_lms = reserve((size_t)(npt + 1) * 4), o_pss = reserve((size_t)(np + 1) * 4);   // (zeroed together by the device builder)
-  const size_t o_ept = reserve((size_t)nE1 * 4), o_ekf = reserve((size_t)nE1 * 4),
-               o_epj = reserve((size_t)nE1 * 4), o_etype = reserve(nE1), o_elevel = reserve(nE1), o_emeas = reserve((size_t)nE1 * 12),
-               o_einfo = reserve((size_t)nE1 * 8), o_lme = reserve((size_t)nE1 * 4), o_pse = reserve((size_t)nE1 * 4),
-               o_poses = reserve((size_t)n_kf * sizeof(SE3)), o_pts = reserve((size_t)std::max(npt, 1) * 24),
-               o_kfT = reserve((size_t)n_kf * 48);
-  if (stage.size() < stageBytes) stage.resize(stageBytes);
-  uint8_t *hs = stage.data();
-  int *h_poseIdx = reinterpret_cast<int *>(hs + o_poseIdx), *e_pt = reinterpret_cast<int *>(hs + o_ept), *e_kf = reinterpret_cast<int *>(hs + o_ekf),
-      *e_pj = reinterpret_cast<int *>(hs + o_epj), *lm_start = reinterpret_cast<int *>(hs + o_lms), *lm_edges = reinterpret_cast<int *>(hs + o_lme),
-      *ps_start = reinterpret_cast<int *>(hs + o_pss), *ps_edges = reinterpret_cast<int *>(hs + o_pse), *o_i = reinterpret_cast<int *>(hs + o_oi),
-      *o_j = reinterpret_cast<int *>(hs + o_oj), *od_start = reinterpret_cast<int *>(hs + o_ods), *od_edges = reinterpret_cast<int *>(hs + o_ode);
-  uint8_t *e_type = hs + o_etype, *e_level = hs + o_elevel;
-  float *e_meas = reinterpret_cast<float *>(hs + o_emeas);
-  double *e_info = reinterpret_cast<double *>(hs + o_einfo), *o_info = reinterpret_cast<double *>(hs + o_oinfo);
-  SE3 *oZinv = reinterpret_cast<SE3 *>(hs + o_oz), *poses = reinterpret_cast<SE3 *>(hs + o_poses);
-  double *pts = reinterpret_cast<double *>(hs + o_pts);
-  memcpy(h_poseIdx, poseIdx.data(), (size_t)n_kf * 4);
-  memcpy(hs + o_fixed, A->kf_fixed, n_kf);
-  {  // initial Levenberg-Marquardt control block + abort word of the device-resident schedule
-    BACtl init;
-    memset(&init, 0, sizeof(init));
-    // (sharded: nE / nO are this rank's view; every rank holds all edges, so `anything` agrees across the ranks)
-    const bool anything = nE + (odom ? A->n_odom : 0) > 0 && (np > 0 || npt > 0);
-    init.phase = anything ? 0 : 2;
-    init.needInit = 1;
-    memcpy(hs + o_ctl, &init, sizeof(init));
-    const int abort0 = (A->stop_flag && *A->stop_flag) ? 1 : 0;  // sharded: raised before the call on this rank only
-    memset(hs + o_abort, 0, 16);
-    memcpy(hs + o_abort, &abort0, sizeof(int));
-  }
-  if (!devIn) {
-  memcpy(hs + o_kfT, A->kf_Tcw, (size_t)n_kf * 48);
-  // one pass over the observations fills the per-edge arrays and counts the two CSR structures, a second one scatters
-  for (int l = 0; l <= npt; l++) lm_start[l] = 0;
-  for (int k = 0; k <= np; k++) ps_start[k] = 0;
-  const double wFd = (double)A->wF, wBd = (double)A->wB;
-  // Observations usually arrive grouped by point (the reference walks its local map points): then the CSR by landmark is
-  // the edge order itself and the duplicate check (a key frame sees a point at most once) rides in this pass.
-  static thread_local std::vector<int> seen;
-  seen.assign(n_kf, -1);
-  bool grouped = true, dup = false;
-  int prevPt = -1;
-  for (int i = 0; i < nF; i++) {
-    const int pt = A->obs_mp[i], kf = A->obs_kf[i];
-    FB_ARG(pt >= 0 && pt < n_mp && kf >= 0 && kf < n_kf);
-    grouped = grouped && pt >= prevPt;
-    prevPt = pt;
-    dup = dup || seen[kf] == pt;
-    seen[kf] = pt;
-    e_pt[i] = pt; e_kf[i] = kf; e_type[i] = T_PROJ;
-    e_meas[3 * i] = A->obs_uv[2 * i]; e_meas[3 * i + 1] = A->obs_uv[2 * i + 1]; e_meas[3 * i + 2] = 0.0f;
-    e_info[i] = odom ? (1.0 * (double)A->obs_inv_sigma2[i]) * wFd : (double)A->obs_inv_sigma2[i];
-    e_level[i] = (sharded && pt % world != rank) ? 2 : 0;  // 2 = not this rank's landmark
-    const int pj = poseIdx[kf];
-    e_pj[i] = pj;
-    lm_start[pt + 1]++;
-    if (pj >= 0) ps_start[pj + 1]++;
-  }
-  for (int i = 0; i < nB; i++) {
-    FB_ARG(A->bobs_mpb[i] >= 0 && A->bobs_mpb[i] < A->n_mpb && A->bobs_kf[i] >= 0 && A->bobs_kf[i] < n_kf);
-    const int e = nF + i, pt = n_mp + A->bobs_mpb[i], kf = A->bobs_kf[i];
-    grouped = grouped && pt >= prevPt;
-    prevPt = pt;
-    dup = dup || seen[kf] == pt;
-    seen[kf] = pt;
-    e_pt[e] = pt; e_kf[e] = kf; e_type[e] = T_XYZ;
-    for (int k = 0; k < 3; k++) e_meas[3 * e + k] = A->bobs_xc[3 * i + k];
-    e_info[e] = (1.0 * (double)A->bobs_inv_sigma2[i]) * wBd;
-    e_level[e] = (sharded && pt % world != rank) ? 2 : 0;
-    const int pj = poseIdx[kf];
-    e_pj[e] = pj;
-    lm_start[pt + 1]++;
-    if (pj >= 0) ps_start[pj + 1]++;
-  }
-  for (int l = 0; l < npt; l++) lm_start[l + 1] += lm_start[l];
-  for (int k = 0; k < np; k++) ps_start[k + 1] += ps_start[k];
-  {
-    static thread_local std::vector<int> fillL, fillP;
-    fillP.assign(ps_start, ps_start + np);
-    if (grouped) {
-      for (int e = 0; e < nE; e++) {
-        lm_edges[e] = e;
-        if (e_pj[e] >= 0) ps_edges[fillP[e_pj[e]]++] = e;
-      }
-    } else {
-      fillL.assign(lm_start, lm_start + npt);
-      for (int e = 0; e < nE; e++) {
-        lm_edges[fillL[e_pt[e]]++] = e;
-        if (e_pj[e] >= 0) ps_edges[fillP[e_pj[e]]++] = e;
-      }
-      // a keyframe observes a point at most once (map<KeyFrame*,size_t>): stamp per key frame = last landmark seen
-      dup = false;
-      seen.assign(n_kf, -1);
-      for (int l = 0; l < npt && !dup; l++)
-        for (int c = lm_start[l]; c < lm_start[l + 1]; c++) {
-          int &sk = seen[e_kf[lm_edges[c]]];
-          dup = dup || sk == l;
-          sk = l;
-        }
-    }
-    if (dup) { fb::set_error("fb_local_ba: duplicate (keyframe, point) observation"); return FB_ERR_ARG; }
-  }
-  for (int k = 0; k < n_kf; k++) poses[k] = fb::se3_from_float12(A->kf_Tcw + 12 * k);
-  for (int i = 0; i < 3 * n_mp; i++) pts[i] = A->mp_xw[i];
-  for (int i = 0; i < 3 * A->n_mpb; i++) pts[3 * n_mp + i] = A->mpb_xw[i];
-  }  // !devIn
-  for (int i = 0; i < nO; i++) {
-    FB_ARG(A->odom_kf_i[i] >= 0 && A->odom_kf_i[i] < n_kf && A->odom_kf_j[i] >= 0 && A->odom_kf_j[i] < n_kf);
-    o_i[i] = A->odom_kf_i[i]; o_j[i] = A->odom_kf_j[i]; o_info[i] = A->odom_info[i];
-    oZinv[i] = fb::se3_inverse(fb::se3_from_float12(A->odom_Tij + 12 * i));
-  }
-  {
-    std::vector<std::vector<int>> inc(np);
-    for (int e = 0; e < nO; e++) {
-      const int pi = poseIdx[o_i[e]], pj = poseIdx[o_j[e]];
-      if (pi >= 0) inc[pi].push_back(e);
-      if (pj >= 0 && pj != pi) inc[pj].push_back(e);
-    }
-    od_start[0] = 0;
-    int q = 0;
-    for (int k = 0; k < np; k++) { for (int e : inc[k]) od_edges[q++] = e; od_start[k + 1] = q; }
-  }
-  // ---- device buffers: the staged graph (one copy) + one scratch allocation carved below
-  const int NT = (P6 + 1 + 15) / 16;
-  const int rows = NT * 16;
-  const int nLinBlocks = (npt + LIN_THREADS - 1) / LIN_THREADS;
-  const int nUpdBlocks = (4 * npt + n_kf + LIN_THREADS - 1) / LIN_THREADS;  // four lanes per landmark + one per key frame
-  int nWg = std::min(getenv("FB_BA_NWG") ? atoi(getenv("FB_BA_NWG")) : 256, std::max(1, (npt + CHUNK - 1) / CHUNK));
-  const int lmPerWg = ((npt + nWg - 1) / nWg + CHUNK - 1) / CHUNK * CHUNK;
-  nWg = std::max(1, (npt + lmPerWg - 1) / std::max(lmPerWg, 1));
-  lap("host preprocessing done");
-  fb::DevBuf d_stage, d_scratch, d_bld;
-  if (!devIn) {
-    FB_TRY(d_stage.upload(hs, stageBytes));
-  } else {
-    // only the header travels; the edge records, both CSR structures and the double-precision state are built by kernels
-    // from the caller's device arrays (same contents as the host passes above, incl. the ascending edge order inside a
-    // landmark / a key frame that the sums depend on)
-    FB_TRY(d_stage.alloc(stageBytes));
-    uint8_t *dsb = d_stage.as<uint8_t>();
-    FB_HIP(hipMemcpyAsync(dsb, hs, headerBytes, hipMemcpyHostToDevice, s0));
-    FB_ARG(A->kf_Tcw && (n_mp == 0 || A->mp_xw) && (A->n_mpb == 0 || A->mpb_xw));
-    FB_ARG(nF == 0 || (A->obs_kf && A->obs_mp && A->obs_uv && A->obs_inv_sigma2 && A->obs_outlier));
-    FB_ARG(nB == 0 || (A->bobs_kf && A->bobs_mpb && A->bobs_xc && A->bobs_inv_sigma2 && A->bobs_outlier));
-    FB_TRY(d_bld.alloc(((size_t)npt + np + 2) * 4 + 16));
-    int *fillL = d_bld.as<int>(), *fillP = fillL + npt + 1, *badDev = fillP + np + 1;
-    FB_HIP(hipMemsetAsync(dsb + o_lms, 0, (o_ept - o_lms), s0));   // lm_start | ps_start (counts accumulate into them)
-    FB_HIP(hipMemsetAsync(d_bld.p, 0, d_bld.bytes, s0));
-    BuildIn I;
-    I.obs_kf = A->obs_kf; I.obs_mp = A->obs_mp; I.obs_uv = A->obs_uv; I.obs_inv = A->obs_inv_sigma2;
-    I.bobs_kf = A->bobs_kf; I.bobs_mpb = A->bobs_mpb; I.bobs_xc = A->bobs_xc; I.bobs_inv = A->bobs_inv_sigma2;
-    I.kf_Tcw = A->kf_Tcw; I.mp_xw = A->mp_xw; I.mpb_xw = A->mpb_xw;
-    I.nF = nF; I.nB = nB; I.n_kf = n_kf; I.n_mp = n_mp; I.n_mpb = A->n_mpb; I.odom = odom ? 1 : 0; I.wF = (double)A->wF; I.wB = (double)A->wB;
-    int *dlms = reinterpret_cast<int *>(dsb + o_lms), *dpss = reinterpret_cast<int *>(dsb + o_pss);
-    int *dept = reinterpret_cast<int *>(dsb + o_ept), *dekf = reinterpret_cast<int *>(dsb + o_ekf), *depj = reinterpret_cast<int *>(dsb + o_epj);
-    int *dlme = reinterpret_cast<int *>(dsb + o_lme), *dpse = reinterpret_cast<int *>(dsb + o_pse);
-    int segCap = 1;
-    while (segCap < std::max(nE, 1) && segCap < 32768) segCap <<= 1;  // observations of ONE key frame: at most 32768 (128 KB of LDS)
-    { fb::ProfScope pr(fb::P_BA_MISC, s0);
-      if (nE > 0) k_bld_edges<<<(nE + 255) / 256, 256, 0, s0>>>(I, reinterpret_cast<const int *>(dsb + o_poseIdx), dept, dekf, depj, dsb + o_etype, dsb + o_elevel,
-                                                              reinterpret_cast<float *>(dsb + o_emeas), reinterpret_cast<double *>(dsb + o_einfo), dlms, dpss, badDev);
-      k_bld_state<<<(std::max(n_kf, 3 * std::max(n_mp, A->n_mpb)) + 255) / 256, 256, 0, s0>>>(I, reinterpret_cast<SE3 *>(dsb + o_poses), reinterpret_cast<double *>(dsb + o_pts),
-                                                                                              reinterpret_cast<float *>(dsb + o_kfT));
-      k_bld_scan<<<1, 1024, 0, s0>>>(dlms, npt, fillL);
-      k_bld_scan<<<1, 1024, 0, s0>>>(dpss, np, fillP);
-      if (nE > 0) {
-        k_bld_scatter<<<(nE + 255) / 256, 256, 0, s0>>>(nE, dept, depj, fillL, fillP, dlme, dpse);
-        k_bld_sort_lm<<<(npt + 255) / 256, 256, 0, s0>>>(npt, dlms, dlme, dekf, badDev);
-        if (np > 0) {
-          FB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_bld_sort_ps), hipFuncAttributeMaxDynamicSharedMemorySize, segCap * 4));
-          k_bld_sort_ps<<<np, 1024, (size_t)segCap * 4, s0>>>(dpss, dpse, segCap, badDev);
-        }
-      }
-      FB_HIP(hipGetLastError()); }
-  }
-  lap("graph uploaded");
-  uint8_t *ds = d_stage.as<uint8_t>();
-  size_t scratchBytes = 0;
-  auto carve = [&](size_t bytes) { const size_t off = scratchBytes; scratchBytes += (bytes + 255) & ~(size_t)255; return off; };
-  const size_t c_echi2 = carve((size_t)nE1 * 8);
-  size_t c_pose1 = carve((size_t)n_kf * sizeof(SE3)), c_pt1 = carve((size_t)std::max(npt, 1) * 24);
-  size_t c_Hll[2], c_bl[2], c_W[2], c_Hpp[2], c_bp[2], c_chi[2], c_max[2];
-  for (int q = 0; q < 2; q++) {
-    c_Hll[q] = carve((size_t)std::max(npt, 1) * 72); c_bl[q] = carve((size_t)std::max(npt, 1) * 24); c_W[q] = carve((size_t)nE1 * 144);
-    c_Hpp[q] = carve((size_t)std::max(P6 * P6, 1) * 8); c_bp[q] = carve((size_t)std::max(P6, 1) * 8); c_chi[q] = carve((size_t)(2 * nLinBlocks + 2) * 8); c_max[q] = carve((size_t)(2 * nLinBlocks + 2) * 8);
-  }
-  FB_TRY(d_scratch.alloc(scratchBytes));
-  uint8_t *dc = d_scratch.as<uint8_t>();
-  FB_HIP(hipMemsetAsync(dc + c_echi2, 0, (size_t)nE1 * 8, s0));
-  // state 0 = the staged copy, state 1 starts as the same poses / points
-  FB_HIP(hipMemcpyAsync(dc + c_pose1, ds + o_poses, (size_t)n_kf * sizeof(SE3), hipMemcpyDeviceToDevice, s0));
-  FB_HIP(hipMemcpyAsync(dc + c_pt1, ds + o_pts, (size_t)std::max(npt, 1) * 24, hipMemcpyDeviceToDevice, s0));
-  const uint8_t *d_fixed = ds + o_fixed;   // kf_fixed
-  const uint8_t *d_kfT0 = ds + o_kfT;      // the caller's float poses (fixed key frames are returned untouched)
-  BADev D;
-  D.n_kf = n_kf; D.np = np; D.npt = npt; D.nE = nE; D.nO = nO; D.quat = odom ? 1 : 0;
-  D.fx = A->fx; D.fy = A->fy; D.cx = A->cx; D.cy = A->cy; D.delta = sc.delta;
-  D.e_pj = reinterpret_cast<int *>(ds + o_epj);
-  D.poseIdx = reinterpret_cast<int *>(ds + o_poseIdx); D.e_pt = reinterpret_cast<int *>(ds + o_ept); D.e_kf = reinterpret_cast<int *>(ds + o_ekf);
-  D.e_type = ds + o_etype; D.e_meas = reinterpret_cast<float *>(ds + o_emeas); D.e_info = reinterpret_cast<double *>(ds + o_einfo);
-  D.e_level = ds + o_elevel; D.e_chi2 = reinterpret_cast<double *>(dc + c_echi2);
-  D.lm_start = reinterpret_cast<int *>(ds + o_lms); D.lm_edges = reinterpret_cast<int *>(ds + o_lme);
-  D.ps_start = reinterpret_cast<int *>(ds + o_pss); D.ps_edges = reinterpret_cast<int *>(ds + o_pse);
-  D.o_i = reinterpret_cast<int *>(ds + o_oi); D.o_j = reinterpret_cast<int *>(ds + o_oj); D.o_Zinv = reinterpret_cast<SE3 *>(ds + o_oz);
-  D.o_info = reinterpret_cast<double *>(ds + o_oinfo);
-  D.od_start = reinterpret_cast<int *>(ds + o_ods); D.od_edges = reinterpret_cast<int *>(ds + o_ode);
-  State st[2];
-  LinBuf lb[2];
-  st[0].pose = reinterpret_cast<SE3 *>(ds + o_poses); st[0].pt = reinterpret_cast<double *>(ds + o_pts);
-  st[1].pose = reinterpret_cast<SE3 *>(dc + c_pose1); st[1].pt = reinterpret_cast<double *>(dc + c_pt1);
-  for (int q = 0; q < 2; q++) {
-    lb[q].Hll = reinterpret_cast<double *>(dc + c_Hll[q]); lb[q].bl = reinterpret_cast<double *>(dc + c_bl[q]); lb[q].W = reinterpret_cast<double *>(dc + c_W[q]);
-    lb[q].Hpp = reinterpret_cast<double *>(dc + c_Hpp[q]); lb[q].bp = reinterpret_cast<double *>(dc + c_bp[q]); lb[q].chiPart = reinterpret_cast<double *>(dc + c_chi[q]); lb[q].maxPart = reinterpret_cast<double *>(dc + c_max[q]);
-  }
-  const size_t schurLds = (size_t)2 * rows * KPAD * 8;
-  const size_t solveLds = ((size_t)(P6 + 1) * (P6 + 1) + (size_t)(P6 + 1) * 6 + 96 + P6 + 2) * 8;  // the larger of k_ba_solve / solve_lookahead
-  // beyond ~23 free key frames the reduced system no longer fits LDS: HBM-resident path of ba_big.inc
-  const bool big = schurLds > 160 * 1024 || solveLds > 160 * 1024 || P6 + 1 > 256;
-  fb::DevBuf d_Dinv, d_Spart, d_xp, d_ok, d_scale, d_scal, d_bigS, d_bigM, d_bigU, d_bigR;
-  FB_TRY(d_Dinv.alloc((size_t)npt * 9 * 8)); FB_TRY(d_Spart.alloc(big ? 8 : (size_t)nWg * rows * rows * 8));
-  fb::DevBuf d_blkStart, d_blkPr, d_blkPc, d_entEr, d_entEc;
-  BigLists lists{};
-  if (big) {
-    FB_TRY(d_bigS.alloc((size_t)P6 * P6 * 8 + (size_t)P6 * 8));  // S | r
-    FB_TRY(d_bigM.alloc((size_t)P6 * P6 * 8 + (size_t)P6 * 8));  // M | rhs
-    FB_TRY(d_bigU.alloc((size_t)P6 * BIG_NB * 8));
-    // (row key frame <= column key frame) -> the edge pairs of the landmarks both observe; counting sort by block
-    std::vector<int> cnt((size_t)np * np + 1, 0);
-    auto for_pairs = [&](auto &&f) {
-      for (int l = 0; l < npt; l++)
-        for (int a = lm_start[l]; a < lm_start[l + 1]; a++) {
-          const int pa = poseIdx[e_kf[lm_edges[a]]];
-          if (pa < 0) continue;
-          for (int b2 = a; b2 < lm_start[l + 1]; b2++) {
-            const int pb = poseIdx[e_kf[lm_edges[b2]]];
-            if (pb < 0) continue;
-            if (pa <= pb) f(pa, pb, lm_edges[a], lm_edges[b2]);
-            else f(pb, pa, lm_edges[b2], lm_edges[a]);
-          }
-        }
-    };
-    for_pairs([&](int pr, int pc, int, int) { cnt[(size_t)pr * np + pc + 1]++; });
-    std::vector<int> blkStart(1, 0), blkPr, blkPc, slot((size_t)np * np, -1);
-    for (size_t key = 0; key < (size_t)np * np; key++)
-      if (cnt[key + 1] > 0) {
-        slot[key] = (int)blkPr.size();
-        blkPr.push_back((int)(key / np));
-        blkPc.push_back((int)(key % np));
-        blkStart.push_back(blkStart.back() + cnt[key + 1]);
-      }
-    std::vector<int> fillp(blkStart.begin(), blkStart.end() - 1), entEr(blkStart.back()), entEc(blkStart.back());
-    for_pairs([&](int pr, int pc, int er, int ec) {
-      const int q = fillp[slot[(size_t)pr * np + pc]]++;
-      entEr[q] = er;
-      entEc[q] = ec;
-    });
-    BA_UP(d_blkStart, blkStart); BA_UP(d_blkPr, blkPr); BA_UP(d_blkPc, blkPc); BA_UP(d_entEr, entEr); BA_UP(d_entEc, entEc);
-    lists.nBlocks = (int)blkPr.size();
-    lists.blk_start = d_blkStart.as<int>(); lists.blk_pr = d_blkPr.as<int>(); lists.blk_pc = d_blkPc.as<int>();
-    lists.ent_er = d_entEr.as<int>(); lists.ent_ec = d_entEc.as<int>();
-  }
-  FB_TRY(d_xp.alloc((size_t)std::max(P6, 1) * 8)); FB_TRY(d_ok.alloc(4)); FB_TRY(d_scale.alloc((size_t)nUpdBlocks * 8));
-  FB_TRY(d_scal.alloc(4 * 8));
-  FB_HIP(hipMemsetAsync(d_scal.p, 0, 4 * 8, s0));
-  // accumulator tiles per wave: NT<=8 -> 9, NT<=12 -> 20, NT<=16 -> 34
-  auto schurKernel = NT <= 8 ? k_ba_schur<9> : (NT <= 12 ? k_ba_schur<20> : k_ba_schur<34>);
-  if (!big) {
-    FB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(schurKernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)schurLds));
-    FB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_ba_solve), hipFuncAttributeMaxDynamicSharedMemorySize, (int)solveLds));
-  } else {
-    FB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_big_solve), hipFuncAttributeMaxDynamicSharedMemorySize, P6 * 8));
-  }
-  size_t odomLds = (size_t)std::max(nO, 1) * sizeof(OdomLin);
-  fb::DevBuf d_ol;
-  OdomLin *olGlobal = nullptr;
-  if (odomLds > 150 * 1024) {  // long odometry chains: per-edge linearisations in HBM
-    FB_TRY(d_ol.alloc(odomLds));
-    olGlobal = d_ol.as<OdomLin>();
-    odomLds = 0;
-  } else {
-    FB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_ba_odom<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)odomLds));
-  }
-
-  // ---- device-resident Levenberg-Marquardt (LDS-resident reduced system): no read-back inside the schedule.  Sharded:
-  //      two all-reduces per slot on this stream (the Schur-reduced system; the exchange block of the linearisation), every
-  //      rank enqueues the same slots and takes the same decisions from the reduced values.
-  if (devIn && big) { fb::set_error("fb_local_ba_dev: more than 23 free key frames (use fb_local_ba)"); return FB_ERR_CAPACITY; }
-  if (!big && (devIn || (!getenv("FB_BA_TRACE") && !getenv("FB_BA_HOST_LM")))) {
-    // per host thread and device (concurrent callers must not share the pinned mirror; a stream belongs to its device):
-    // side stream for the abort request (does not synchronise with the null stream), pinned mirror of the control block,
-    // the event the host polls
-    int devId = 0;
-    FB_HIP(hipGetDevice(&devId));
-    if (devId < 0 || devId >= 64) { fb::set_error("fb_local_ba: device id %d", devId); return FB_ERR_NODEVICE; }
-    PerDev &pd = g_perDev[devId];
-    if (!pd.sAux) FB_HIP(hipStreamCreateWithFlags(&pd.sAux, hipStreamNonBlocking));
-    if (!pd.hCtl) FB_HIP(hipHostMalloc(reinterpret_cast<void **>(&pd.hCtl), sizeof(BACtl), hipHostMallocDefault));
-    if (!pd.evDone) FB_HIP(hipEventCreateWithFlags(&pd.evDone, hipEventDisableTiming));
-    hipStream_t sAux = pd.sAux;
-    BACtl *hCtl = pd.hCtl;
-    hipEvent_t evDone = pd.evDone;
-    fb::DevBuf d_flags, d_kfT, d_ptOut, d_xb, d_ex;
-    const bool anything = nE + (odom ? A->n_odom : 0) > 0 && (np > 0 || npt > 0);
-    int *const d_abortp = reinterpret_cast<int *>(ds + o_abort);
-    BACtl *ctl = reinterpret_cast<BACtl *>(ds + o_ctl);
-    if (devIn) {  // a rejected graph (index out of range, duplicate observation) ends the schedule before it starts
-      k_bld_check<<<1, 1, 0, s0>>>(d_bld.as<int>() + npt + 1 + np + 1, ctl);
-      FB_HIP(hipGetLastError());
-    }
-    const BASched sched = {sc.its1, sc.robust1, sc.gate ? 1 : 0, sc.its2};
-    St2 st2; st2.s[0] = st[0]; st2.s[1] = st[1];
-    Lb2 lb2; lb2.b[0] = lb[0]; lb2.b[1] = lb[1];
-    auto schurC = NT <= 8 ? k_ba_schur_c<9> : (NT <= 12 ? k_ba_schur_c<20> : k_ba_schur_c<34>);
-    FB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(schurC), hipFuncAttributeMaxDynamicSharedMemorySize, (int)schurLds));
-    FB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_ba_solve_c), hipFuncAttributeMaxDynamicSharedMemorySize, (int)solveLds));
-    const int nS = rows * rows;
-    FB_HIP(hipMemsetAsync(d_Spart.p, 0, (size_t)nS * 8, s0));  // the lower tiles of the summed system are never written: keep them finite
-    const int nLin256 = (4 * npt + 255) / 256;  // four lanes per landmark; chi2 slot of the odometry role = nLin256
-    XBLay xb;
-    xb.oH = np * POSE_PARTS * 27; xb.oB = xb.oH + P6 * P6; xb.oS = xb.oB + P6; xb.oM = xb.oS + 4; xb.stride = xb.oM + world;
-    // sharded: the kernels of a linearisation fill the RAW blocks; exchange 2 sums BOTH raw blocks into the REDUCED ones out of
-    // place (which of the two the slot wrote is device-side knowledge; the raw block of the accepted linearisation is not
-    // touched until it is overwritten, so re-reducing it is idempotent); k_ba_control and k_ba_solve read the reduced blocks
-    FB_TRY(d_xb.alloc((size_t)(sharded ? 4 : 2) * xb.stride * 8));
-    FB_HIP(hipMemsetAsync(d_xb.p, 0, (size_t)(sharded ? 4 : 2) * xb.stride * 8, s0));
-    xb.base = d_xb.as<double>();
-    XBLay xr = xb;  // reduced
-    if (sharded) xr.base = xb.base + (size_t)2 * xb.stride;
-    const size_t linLds = olGlobal ? 0 : odomLds + (size_t)std::max(nO, 1) * 108 * 8;
-    bool linGlobal = olGlobal != nullptr;
-    fb::DevBuf d_olDev;
-    if (!linGlobal && linLds > 150 * 1024) {  // the products' scratch does not fit next to the records: HBM records, serial products
-      FB_TRY(d_olDev.alloc((size_t)std::max(nO, 1) * sizeof(OdomLin)));
-      olGlobal = d_olDev.as<OdomLin>();
-      linGlobal = true;
-    }
-    if (!linGlobal) FB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_ba_lin_c<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)linLds));
-    const int linGrid = nLin256 + POSE_PARTS * np + 1;
-    std::vector<double> hostScratch;
-    int rcSlot = FB_OK;
-    auto slot = [&]() {
-      if (rcSlot != FB_OK) return;
-      { fb::ProfScope pr(fb::P_BA_SCHUR, s0);
-        schurC<<<nWg, SCHUR_THREADS, schurLds, s0>>>(D, lb2, ctl, d_Dinv.as<double>(), d_Spart.as<double>(), P6, NT, lmPerWg); }
-      { fb::ProfScope pr(fb::P_BA_SOLVE, s0);
-        k_ba_sumparts_c<<<(nS + SUMPARTS_ELEMS - 1) / SUMPARTS_ELEMS, 256, 0, s0>>>(ctl, d_Spart.as<double>(), nWg, nS, rows);
-        if (sharded) rcSlot = X.sum_dev(d_Spart.as<double>(), (size_t)nS, s0, hostScratch);  // exchange 1: the Schur-reduced system
-        k_ba_solve_c<<<1, SOLVE_C_THREADS, solveLds, s0>>>(lb2, ctl, d_Spart.as<double>(), P6, NT, d_xp.as<double>(), d_scal.as<double>() + 3, xr); }
-      { fb::ProfScope pr(fb::P_BA_UPDATE, s0);
-        k_ba_update_c<<<nUpdBlocks, LIN_THREADS, 0, s0>>>(D, lb2, st2, ctl, d_Dinv.as<double>(), d_xp.as<double>(), d_scale.as<double>(), rank == 0 ? 1 : 0); }
-      { fb::ProfScope pr(fb::P_BA_LINEARIZE, s0);
-        if (linGlobal) k_ba_lin_c<true><<<linGrid, 256, 0, s0>>>(D, st2, lb2, ctl, sched, P6, nLin256, nLin256, olGlobal, xb);
-        else k_ba_lin_c<false><<<linGrid, 256, linLds, s0>>>(D, st2, lb2, ctl, sched, P6, nLin256, nLin256, nullptr, xb); }
-      { fb::ProfScope pr(fb::P_BA_MISC, s0);
-        if (sharded) {
-          k_ba_prex<<<1, 256, 0, s0>>>(D, lb2, ctl, nLin256, nLin256, d_scale.as<double>(), nUpdBlocks, xb, d_abortp, rank, world);
-          // exchange 2: both raw blocks -> the reduced blocks, one all-reduce
-          if (rcSlot == FB_OK) rcSlot = X.sum_dev(xr.at(0), (size_t)2 * xb.stride, s0, hostScratch, xb.at(0));
-          k_ba_control<true><<<1, 256, 0, s0>>>(D, lb2, ctl, sched, nLin256, nLin256, d_scale.as<double>(), nUpdBlocks, d_scal.as<double>() + 3, P6, xr, d_abortp, world);
-        } else {
-          k_ba_control<false><<<1, 256, 0, s0>>>(D, lb2, ctl, sched, nLin256, nLin256, d_scale.as<double>(), nUpdBlocks, d_scal.as<double>() + 3, P6, xb, d_abortp, world);
-        } }
-    };
-    FB_TRY(d_flags.alloc(std::max(nE, 1)));
-    FB_TRY(d_kfT.alloc((size_t)n_kf * 48));
-    FB_HIP(hipMemcpyAsync(d_kfT.p, d_kfT0, (size_t)n_kf * 48, hipMemcpyDeviceToDevice, s0));
-    FB_TRY(d_ptOut.alloc((size_t)std::max(npt, 1) * 12));
-    if (sharded) FB_TRY(d_ex.alloc(((size_t)npt * 3 + nE + 1) * 8));
-    bool abortSent = false;
-    static const int one = 1;
-    // a typical schedule takes one trial per iteration: its1 + its2 trials + the two opening linearisations
-    int batch = anything ? sc.its1 + (sc.gate ? sc.its2 + 1 : 0) + 1 + 2 : 0;
-    int rcLoop = FB_OK;
-    lap("buffers ready");
-    for (int round = 0; round < 64; round++) {
-      for (int i = 0; i < batch; i++) slot();
-      if (rcSlot != FB_OK) { rcLoop = rcSlot; break; }
-      lap("slots enqueued");
-      // the results of the state that is current now (final when the schedule has finished, which is the common case)
-      if (nE > 0) k_ba_gate_final_c<<<(nE + 255) / 256, 256, 0, s0>>>(D, st2, ctl, d_flags.as<uint8_t>());
-      k_ba_export_c<<<(n_kf + npt * 3 + 255) / 256, 256, 0, s0>>>(n_kf, npt, st2, ctl, d_fixed, d_kfT.as<float>(), d_ptOut.as<float>());
-      if (sharded) {  // every rank returns the complete result
-        const int nx = npt * 3 + nE;
-        k_ba_final_pack<<<(nx + 255) / 256, 256, 0, s0>>>(npt, nE, rank, world, d_ptOut.as<float>(), d_flags.as<uint8_t>(), d_ex.as<double>());
-        rcLoop = X.sum_dev(d_ex.as<double>(), (size_t)nx, s0, hostScratch);
-        if (rcLoop != FB_OK) break;
-        k_ba_final_unpack<<<(nx + 255) / 256, 256, 0, s0>>>(npt, nE, d_ex.as<double>(), d_ptOut.as<float>(), d_flags.as<uint8_t>());
-      }
-      if (hipGetLastError() != hipSuccess) { fb::set_error("fb_local_ba: kernel launch failed"); rcLoop = FB_ERR_HIP; break; }
-      if (hipMemcpyAsync(hCtl, ctl, sizeof(BACtl), hipMemcpyDeviceToHost, s0) != hipSuccess || hipEventRecord(evDone, s0) != hipSuccess) {
-        fb::set_error("fb_local_ba: control block read-back failed"); rcLoop = FB_ERR_HIP; break;
-      }
-      if (!A->stop_flag) {  // nothing to forward: block in the driver instead of holding a host core
-        const hipError_t q = hipEventSynchronize(evDone);
-        if (q != hipSuccess) { fb::set_error("fb_local_ba: %s", hipGetErrorString(q)); rcLoop = FB_ERR_HIP; }
-      } else {
-        for (;;) {  // wait; meanwhile forward pbStopFlag (the control kernel sees it at the end of the slot that is running)
-          const hipError_t q = hipEventQuery(evDone);
-          if (q == hipSuccess) break;
-          if (q != hipErrorNotReady) { fb::set_error("fb_local_ba: %s", hipGetErrorString(q)); rcLoop = FB_ERR_HIP; break; }
-          if (!abortSent && *A->stop_flag) {
-            (void)hipMemcpyAsync(d_abortp, &one, sizeof(int), hipMemcpyHostToDevice, sAux);
-            abortSent = true;
-          }
-          // a BA lasts milliseconds and the flag only has to reach the device before the running slot (~0.1 ms) ends:
-          // poll every 20 us instead of spinning on the LocalMapping thread's core
-          std::this_thread::sleep_for(std::chrono::microseconds(20));
-        }
-      }
-      if (rcLoop != FB_OK || hCtl->phase == 2) break;
-      batch = 6;
-    }
-    lap("schedule finished");
-    if (rcLoop != FB_OK) return rcLoop;
-    if (hCtl->phase != 2) { fb::set_error("fb_local_ba: the LM schedule did not finish"); return FB_ERR_HIP; }
-    if (devIn) {
-      if (hCtl->badArgs & 4) { fb::set_error("fb_local_ba_dev: a key frame with more than 32768 observations (use fb_local_ba)"); return FB_ERR_CAPACITY; }
-      if (hCtl->badArgs) {
-        fb::set_error(hCtl->badArgs & 1 ? "fb_local_ba_dev: observation index out of range" : "fb_local_ba_dev: duplicate (keyframe, point) observation");
-        return FB_ERR_ARG;
-      }
-      if (sc.gate) {
-        if (nF > 0) FB_HIP(hipMemcpyAsync(A->obs_outlier, d_flags.p, (size_t)nF, hipMemcpyDeviceToDevice, s0));
-        if (nB > 0) FB_HIP(hipMemcpyAsync(A->bobs_outlier, d_flags.as<uint8_t>() + nF, (size_t)nB, hipMemcpyDeviceToDevice, s0));
-      }
-      FB_HIP(hipMemcpyAsync(A->kf_Tcw, d_kfT.p, (size_t)n_kf * 48, hipMemcpyDeviceToDevice, s0));
-      if (n_mp > 0) FB_HIP(hipMemcpyAsync(A->mp_xw, d_ptOut.p, (size_t)n_mp * 12, hipMemcpyDeviceToDevice, s0));
-      if (A->n_mpb > 0) FB_HIP(hipMemcpyAsync(A->mpb_xw, d_ptOut.as<float>() + (size_t)3 * n_mp, (size_t)A->n_mpb * 12, hipMemcpyDeviceToDevice, s0));
-      FB_HIP(hipStreamSynchronize(s0));  // the scratch goes back to the pool when this function returns
-      lap("results copied (device)");
-      return FB_OK;
-    }
-    std::vector<uint8_t> flags(std::max(nE, 1));
-    FB_TRY(d_flags.download(flags.data(), std::max(nE, 1)));
-    std::vector<float> po((size_t)std::max(npt, 1) * 3);
-    FB_TRY(d_ptOut.download(po.data(), (size_t)npt * 12));
-    if (sc.gate) {  // the global BA classifies nothing
-      for (int i = 0; i < nF; i++) A->obs_outlier[i] = flags[i];
-      for (int i = 0; i < nB; i++) A->bobs_outlier[i] = flags[nF + i];
-    }
-    FB_TRY(d_kfT.download(A->kf_Tcw, (size_t)n_kf * 48));
-    for (int i = 0; i < 3 * n_mp; i++) A->mp_xw[i] = po[i];
-    for (int i = 0; i < 3 * A->n_mpb; i++) A->mpb_xw[i] = po[3 * n_mp + i];
-    lap("results copied out");
-    return FB_OK;
-  }
-
-  double lastScale = 0;  // sum x (lambda x + b) of the most recent k_ba_update (all ranks)
-  bool lastOk = true;    // LDL^T status of the most recent k_ba_solve
-  // one linearisation at state `si` into buffer `bi`; returns chi2 (and max diagonal when wanted)
-  auto linearize = [&](int si, int bi, int robust, bool wantDiag, double *chi, double *maxDiag) -> int {
-    if (P6 > 0) FB_HIP(hipMemsetAsync(lb[bi].Hpp, 0, (size_t)P6 * P6 * 8, s0));
-    { fb::ProfScope pr(fb::P_BA_LINEARIZE, s0);
-      if (nLinBlocks > 0) k_ba_linearize<<<nLinBlocks, LIN_THREADS, 0, s0>>>(D, st[si], lb[bi], robust);
-      if (np > 0) k_ba_pose<<<np, POSE_THREADS, 0, s0>>>(D, st[si], lb[bi], robust, P6);
-      if (olGlobal) k_ba_odom<true><<<1, 256, 0, s0>>>(D, st[si], lb[bi], P6, nLinBlocks, olGlobal);
-      else k_ba_odom<false><<<1, 256, odomLds, s0>>>(D, st[si], lb[bi], P6, nLinBlocks, nullptr); }
-    { fb::ProfScope pr(fb::P_BA_MISC, s0);
-      k_ba_scalars<<<1, 256, 0, s0>>>(lb[bi].chiPart, nLinBlocks + 1, lb[bi].Hpp, P6, lb[bi].Hll, npt, d_scal.as<double>(), wantDiag ? 1 : 0); }
-    double h[4];
-    FB_HIP(hipMemcpy(h, d_scal.p, 32, hipMemcpyDeviceToHost));  // chi2, max diagonal, scale term + solver status of the last trial
-    lastOk = h[3] != 0.0;
-    if (sharded) {
-      std::vector<double> ex((size_t)P6 * P6 + P6 + 2);
-      if (P6 > 0) {
-        FB_HIP(hipMemcpy(ex.data(), lb[bi].Hpp, (size_t)P6 * P6 * 8, hipMemcpyDeviceToHost));
-        FB_HIP(hipMemcpy(ex.data() + (size_t)P6 * P6, lb[bi].bp, (size_t)P6 * 8, hipMemcpyDeviceToHost));
-      }
-      ex[(size_t)P6 * P6 + P6] = h[0];
-      ex[(size_t)P6 * P6 + P6 + 1] = h[2];
-      FB_TRY(reduce(ex.data(), (int)ex.size(), 0));
-      if (P6 > 0) {
-        FB_HIP(hipMemcpy(lb[bi].Hpp, ex.data(), (size_t)P6 * P6 * 8, hipMemcpyHostToDevice));
-        FB_HIP(hipMemcpy(lb[bi].bp, ex.data() + (size_t)P6 * P6, (size_t)P6 * 8, hipMemcpyHostToDevice));
-      }
-      h[0] = ex[(size_t)P6 * P6 + P6];
-      h[2] = ex[(size_t)P6 * P6 + P6 + 1];
-      if (wantDiag) {  // the pose diagonals add up over the ranks: take the maximum on the REDUCED Hpp
-        double hp = 0;
-        for (int i = 0; i < P6; i++) hp = std::max(hp, std::fabs(ex[(size_t)i * P6 + i]));
-        k_ba_scalars<<<1, 256, 0, s0>>>(lb[bi].chiPart, 0, nullptr, 0, lb[bi].Hll, npt, d_scal.as<double>(), 1);
-        double hl[2];
-        FB_HIP(hipMemcpy(hl, d_scal.p, 16, hipMemcpyDeviceToHost));
-        h[1] = std::max(hp, hl[1]);
-        FB_TRY(reduce(&h[1], 1, 1));
-      }
-    }
-    *chi = h[0];
-    if (wantDiag) *maxDiag = h[1];
-    lastScale = h[2];
-    return FB_OK;
-  };
-  // SparseOptimizer::optimize + OptimizationAlgorithmLevenberg::solve, host-driven
-  int cur = 0;  // index of the accepted state / its linearisation
-  const bool trace = getenv("FB_BA_TRACE") != nullptr;
-  auto optimize = [&](int iterations, int robust) -> int {
-    double currentChi = 0, maxDiag = 0;
-    FB_TRY(linearize(cur, cur, robust, true, &currentChi, &maxDiag));
-    if (trace) fprintf(stderr, "[hip] optimize(%d) chi0=%.17g maxDiag=%.17g\n", iterations, currentChi, maxDiag);
-    double lambda = 0, ni = 2;
-    int nBad = 0;
-    for (int it = 0; it < iterations; it++) {
-      if (stopped()) break;  // terminate()
-      const double iniChi = currentChi;
-      if (it == 0) { lambda = 1e-5 * maxDiag; ni = 2; nBad = 0; }
-      double rho = 0;
-      int qmax = 0;
-      do {
-        const int tr = 1 - cur;
-        if (big) {
-          double *S = d_bigS.as<double>(), *rS = S + (size_t)P6 * P6, *M = d_bigM.as<double>(), *rhs = M + (size_t)P6 * P6;
-          { fb::ProfScope pr(fb::P_BA_SCHUR, s0);
-            FB_HIP(hipMemsetAsync(S, 0, (size_t)P6 * P6 * 8 + (size_t)P6 * 8, s0));  // blocks without a shared landmark stay 0
-            if (npt > 0) k_ba_dinv<<<(npt + 255) / 256, 256, 0, s0>>>(D, lb[cur], lambda, d_Dinv.as<double>());
-            if (lists.nBlocks > 0) k_ba_schur_gather<<<(lists.nBlocks + 3) / 4, 256, 0, s0>>>(D, lb[cur], d_Dinv.as<double>(), lists, S, P6);
-            if (np > 0) k_ba_rhs_gather<<<(np + 3) / 4, 256, 0, s0>>>(D, lb[cur], d_Dinv.as<double>(), rS); }
-          { fb::ProfScope pr(fb::P_BA_SOLVE, s0);
-            if (sharded) {  // exchange step 1: the Schur-reduced system and right-hand side
-              std::vector<double> ex((size_t)P6 * P6 + P6);
-              FB_HIP(hipMemcpy(ex.data(), S, ex.size() * 8, hipMemcpyDeviceToHost));
-              FB_TRY(reduce(ex.data(), (int)ex.size(), 0));
-              FB_HIP(hipMemcpy(S, ex.data(), ex.size() * 8, hipMemcpyHostToDevice));
-            }
-            const long long nel = (long long)P6 * P6;
-            k_big_assemble<<<(unsigned)((nel + 255) / 256), 256, 0, s0>>>(lb[cur], lambda, S, rS, M, rhs, P6, d_scal.as<double>() + 3);
-            for (int k0 = 0; k0 < P6; k0 += BIG_NB) {
-              const int kw = std::min(BIG_NB, P6 - k0);
-              k_big_panel<<<1, 256, 0, s0>>>(M, P6, k0, kw, d_bigU.as<double>(), d_scal.as<double>() + 3);
-              const int nbt = (P6 - k0 - kw + BIG_NB - 1) / BIG_NB;
-              if (nbt > 0) k_big_update<<<nbt * (nbt + 1) / 2, 256, 0, s0>>>(M, P6, k0, kw, d_bigU.as<double>());
-            }
-            k_big_solve<<<1, 256, (size_t)P6 * 8, s0>>>(M, rhs, P6, d_xp.as<double>()); }
-        } else {
-        { fb::ProfScope pr(fb::P_BA_SCHUR, s0);
-          schurKernel<<<nWg, SCHUR_THREADS, schurLds, s0>>>(D, lb[cur], lambda, d_Dinv.as<double>(), d_Spart.as<double>(), P6, NT, lmPerWg); }
-        { fb::ProfScope pr(fb::P_BA_SOLVE, s0);
-          // the workgroup partials are summed by a full-width kernel (one workgroup reading nWg x rows^2 doubles is slow)
-          const int nS = rows * rows;
-          k_ba_sumparts<<<(nS + SUMPARTS_ELEMS - 1) / SUMPARTS_ELEMS, 256, 0, s0>>>(d_Spart.as<double>(), nWg, nS);
-          const int nParts = 1;
-          if (sharded) {  // exchange step 1: the Schur-reduced system
-            std::vector<double> ex(nS);
-            FB_HIP(hipMemcpy(ex.data(), d_Spart.p, (size_t)nS * 8, hipMemcpyDeviceToHost));
-            FB_TRY(reduce(ex.data(), nS, 0));
-            FB_HIP(hipMemcpy(d_Spart.p, ex.data(), (size_t)nS * 8, hipMemcpyHostToDevice));
-          }
-          k_ba_solve<<<1, SOLVE_THREADS, solveLds, s0>>>(lb[cur], lambda, d_Spart.as<double>(), nParts, P6, NT, d_xp.as<double>(), d_scal.as<double>() + 3); }
-        }
-        { fb::ProfScope pr(fb::P_BA_UPDATE, s0);
-          k_ba_update<<<nUpdBlocks, LIN_THREADS, 0, s0>>>(D, lb[cur], st[cur], st[tr], d_Dinv.as<double>(), d_xp.as<double>(), lambda, d_scale.as<double>(), rank == 0 ? 1 : 0);
-          k_ba_scalars<<<1, 256, 0, s0>>>(d_scale.as<double>(), nUpdBlocks, nullptr, 0, nullptr, 0, d_scal.as<double>() + 2, 0); }
-        double tempChi = 0, dummy = 0;
-        FB_TRY(linearize(tr, tr, robust, false, &tempChi, &dummy));
-        double hs[1] = {lastScale};  // exchange step 2 happened inside linearize()
-        const int ok2 = lastOk ? 1 : 0;
-        if (!ok2) tempChi = 1.7976931348623157e308;
-        rho = currentChi - tempChi;
-        const double scale = hs[0] + 1e-3;
-        rho /= scale;
-        if (trace) fprintf(stderr, "[hip]  it=%d q=%d lambda=%.17g tempChi=%.17g scale=%.17g rho=%.17g ok=%d\n", it, qmax, lambda, tempChi, scale, rho, ok2);
-        if (rho > 0 && std::isfinite(tempChi)) {
-          double alpha = 1. - pow((2 * rho - 1), 3);
-          alpha = std::min(alpha, 2. / 3.);
-          lambda *= std::max(1. / 3., alpha);
-          ni = 2;
-          currentChi = tempChi;
-          cur = tr;  // discardTop: the trial state and its linearisation become current
-        } else {
-          lambda *= ni;
-          ni *= 2;  // pop: keep `cur`
-        }
-        qmax++;
-      } while (rho < 0 && qmax < 10 && !stopped());
-      if (qmax == 10 || rho == 0) break;
-      if ((iniChi - currentChi) * 1e3 < iniChi) nBad++;
-      else nBad = 0;
-      if (nBad >= 3) break;
-    }
-    return FB_OK;
-  };
-  if (nE + nO > 0 && (np > 0 || npt > 0)) FB_TRY(optimize(sc.its1, sc.robust1));
-  const bool more = sc.gate && !stopped();
-  if (more && nE > 0) {
-    k_ba_gate<<<(nE + 255) / 256, 256, 0, s0>>>(D, st[cur], 1, nullptr);
-    if (nE + nO > 0) FB_TRY(optimize(sc.its2, 0));
-  }
-  fb::DevBuf d_flags, d_kfT, d_ptOut;
-  FB_TRY(d_flags.alloc(std::max(nE, 1)));
-  if (nE > 0) k_ba_gate<<<(nE + 255) / 256, 256, 0, s0>>>(D, st[cur], 0, d_flags.as<uint8_t>());
-  FB_TRY(d_kfT.upload(A->kf_Tcw, (size_t)n_kf * 48));
-  FB_TRY(d_ptOut.alloc((size_t)std::max(npt, 1) * 12));
-  k_ba_export<<<(n_kf + npt * 3 + 255) / 256, 256, 0, s0>>>(n_kf, npt, st[cur].pose, st[cur].pt, d_fixed,
-                                                            d_kfT.as<float>(), d_ptOut.as<float>());
-  FB_HIP(hipGetLastError());
-  FB_HIP(hipDeviceSynchronize());
-  std::vector<uint8_t> flags(std::max(nE, 1));
-  FB_TRY(d_flags.download(flags.data(), std::max(nE, 1)));
-  std::vector<float> po((size_t)std::max(npt, 1) * 3);
-  FB_TRY(d_ptOut.download(po.data(), (size_t)npt * 12));
-  if (sharded) {  // every rank returns the complete result: owned landmarks / edges are summed with zeros
-    std::vector<double> ex((size_t)npt * 3 + nE);
-    for (int l = 0; l < npt; l++)
-      for (int c = 0; c < 3; c++) ex[(size_t)3 * l + c] = (l % world == rank) ? (double)po[(size_t)3 * l + c] : 0.0;
-    for (int e = 0; e < nE; e++) ex[(size_t)npt * 3 + e] = flags[e];
-    FB_TRY(reduce(ex.data(), (int)ex.size(), 0));
-    for (size_t i = 0; i < (size_t)npt * 3; i++) po[i] = (float)ex[i];
-    for (int e = 0; e < nE; e++) flags[e] = ex[(size_t)npt * 3 + e] != 0.0;
-  }
-  if (sc.gate) {  // the global BA classifies nothing
-    for (int i = 0; i < nF; i++) A->obs_outlier[i] = flags[i];
-    for (int i = 0; i < nB; i++) A->bobs_outlier[i] = flags[nF + i];
-  }
-  FB_TRY(d_kfT.download(A->kf_Tcw, (size_t)n_kf * 48));
-  for (int i = 0; i < 3 * n_mp; i++) A->mp_xw[i] = po[i];
-  for (int i = 0; i < 3 * A->n_mpb; i++) A->mpb_xw[i] = po[3 * n_mp + i];
-  return FB_OK;
-}
+#include "ba_exchange.inc"
+#include "ba_big.inc"
+#include "ba_graph.inc"
+#include "ba_driver.inc"

@@ -1,4 +1,5 @@
 // ba_big.inc -- the reduced pose system beyond the LDS-resident limit (more than 23 free key frames; included by ba.hip).
+// The kernels first, the host side (pair lists, one trial's Schur complement + solve) at the end of the file.
 //
 // Same mathematics as k_ba_schur / k_ba_solve (BlockSolver::solve with the Schur complement, block_solver.hpp:354-486,
 // dense LDL^T without pivoting), but the reduced system S (P6 x P6) lives in HBM and everything is a deterministic gather:
@@ -253,3 +254,83 @@ __global__ __launch_bounds__(256) void k_big_solve(const double *M, const double
   __syncthreads();
   for (int i = tid; i < P6; i += 256) xp[i] = y[i];
 }
+
+// ---- host side of the HBM-resident path -----------------------------------------------------------------------------------
+namespace {
+struct BigSys {
+  fb::DevBuf S, M, U;  // S | r,  M | rhs,  the panel's L D
+  fb::DevBuf blkStart, blkPr, blkPc, entEr, entEc;
+  BigLists lists{};
+};
+
+// (row key frame <= column key frame) -> the edge pairs of the landmarks both observe; counting sort by block.  Reads the
+// HOST copy of the staged graph.
+int big_prepare(BigSys &B, int np, int npt, int P6, const int *poseIdx, const int *e_kf, const int *lm_start, const int *lm_edges) {
+  FB_TRY(B.S.alloc((size_t)P6 * P6 * 8 + (size_t)P6 * 8));
+  FB_TRY(B.M.alloc((size_t)P6 * P6 * 8 + (size_t)P6 * 8));
+  FB_TRY(B.U.alloc((size_t)P6 * BIG_NB * 8));
+  std::vector<int> cnt((size_t)np * np + 1, 0);
+  auto for_pairs = [&](auto &&f) {
+    for (int l = 0; l < npt; l++)
+      for (int a = lm_start[l]; a < lm_start[l + 1]; a++) {
+        const int pa = poseIdx[e_kf[lm_edges[a]]];
+        if (pa < 0) continue;
+        for (int b2 = a; b2 < lm_start[l + 1]; b2++) {
+          const int pb = poseIdx[e_kf[lm_edges[b2]]];
+          if (pb < 0) continue;
+          if (pa <= pb) f(pa, pb, lm_edges[a], lm_edges[b2]);
+          else f(pb, pa, lm_edges[b2], lm_edges[a]);
+        }
+      }
+  };
+  for_pairs([&](int pr, int pc, int, int) { cnt[(size_t)pr * np + pc + 1]++; });
+  std::vector<int> blkStart(1, 0), blkPr, blkPc, slot((size_t)np * np, -1);
+  for (size_t key = 0; key < (size_t)np * np; key++)
+    if (cnt[key + 1] > 0) {
+      slot[key] = (int)blkPr.size();
+      blkPr.push_back((int)(key / np));
+      blkPc.push_back((int)(key % np));
+      blkStart.push_back(blkStart.back() + cnt[key + 1]);
+    }
+  std::vector<int> fillp(blkStart.begin(), blkStart.end() - 1), entEr(blkStart.back()), entEc(blkStart.back());
+  for_pairs([&](int pr, int pc, int er, int ec) {
+    const int q = fillp[slot[(size_t)pr * np + pc]]++;
+    entEr[q] = er;
+    entEc[q] = ec;
+  });
+  BA_UP(B.blkStart, blkStart); BA_UP(B.blkPr, blkPr); BA_UP(B.blkPc, blkPc); BA_UP(B.entEr, entEr); BA_UP(B.entEc, entEc);
+  B.lists.nBlocks = (int)blkPr.size();
+  B.lists.blk_start = B.blkStart.as<int>(); B.lists.blk_pr = B.blkPr.as<int>(); B.lists.blk_pc = B.blkPc.as<int>();
+  B.lists.ent_er = B.entEr.as<int>(); B.lists.ent_ec = B.entEc.as<int>();
+  return FB_OK;
+}
+
+// Schur complement + solve of one trial at `lambda` from the linearisation `lin`: the pose increment lands in xp, the
+// LDL^T status in *okFlag.  Sharded: the reduced system is summed over the ranks through the host (exchange step 1).
+int big_schur_solve(const BigSys &B, const BADev &D, const LinBuf &lin, double lambda, int P6, double *Dinv, double *xp, double *okFlag,
+                    const Xchg &X, hipStream_t s0) {
+  double *S = B.S.as<double>(), *rS = S + (size_t)P6 * P6, *M = B.M.as<double>(), *rhs = M + (size_t)P6 * P6;
+  { fb::ProfScope pr(fb::P_BA_SCHUR, s0);
+    FB_HIP(hipMemsetAsync(S, 0, (size_t)P6 * P6 * 8 + (size_t)P6 * 8, s0));  // blocks without a shared landmark stay 0
+    if (D.npt > 0) k_ba_dinv<<<(D.npt + 255) / 256, 256, 0, s0>>>(D, lin, lambda, Dinv);
+    if (B.lists.nBlocks > 0) k_ba_schur_gather<<<(B.lists.nBlocks + 3) / 4, 256, 0, s0>>>(D, lin, Dinv, B.lists, S, P6);
+    if (D.np > 0) k_ba_rhs_gather<<<(D.np + 3) / 4, 256, 0, s0>>>(D, lin, Dinv, rS); }
+  fb::ProfScope pr(fb::P_BA_SOLVE, s0);
+  if (X.active()) {
+    std::vector<double> ex((size_t)P6 * P6 + P6);
+    FB_HIP(hipMemcpy(ex.data(), S, ex.size() * 8, hipMemcpyDeviceToHost));
+    FB_TRY(X.reduce_host(ex.data(), (int)ex.size(), 0));
+    FB_HIP(hipMemcpy(S, ex.data(), ex.size() * 8, hipMemcpyHostToDevice));
+  }
+  const long long nel = (long long)P6 * P6;
+  k_big_assemble<<<(unsigned)((nel + 255) / 256), 256, 0, s0>>>(lin, lambda, S, rS, M, rhs, P6, okFlag);
+  for (int k0 = 0; k0 < P6; k0 += BIG_NB) {
+    const int kw = std::min(BIG_NB, P6 - k0);
+    k_big_panel<<<1, 256, 0, s0>>>(M, P6, k0, kw, B.U.as<double>(), okFlag);
+    const int nbt = (P6 - k0 - kw + BIG_NB - 1) / BIG_NB;
+    if (nbt > 0) k_big_update<<<nbt * (nbt + 1) / 2, 256, 0, s0>>>(M, P6, k0, kw, B.U.as<double>());
+  }
+  k_big_solve<<<1, 256, (size_t)P6 * 8, s0>>>(M, rhs, P6, xp);
+  return FB_OK;
+}
+}  // namespace

@@ -223,6 +223,70 @@ def test_local_ba_dev_rejects_bad_graphs():
     assert rc == 0
 
 
+def _dev_inputs(p, **kw):
+    """The in/out device arrays of a fb_local_ba_dev call as host copies, before the call."""
+    a, dev, keep = ba_problem.local_ba_args_dev(p, **kw)
+    return a, dev, keep, {k: v.cpu().numpy().copy() for k, v in dev.items()}
+
+
+def test_local_ba_dev_refuses_a_big_system_before_touching_anything():
+    """More than 23 free key frames from device inputs: refused by the plan, before anything is staged or enqueued -- the
+    caller's device arrays keep their bytes, and the thread's staging block (filled by an earlier, larger host-pointer
+    call) is not read.  The library works afterwards."""
+    import ctypes as C
+    import torch
+    import fishbirdeyevisualslam_amd as fb
+    from fishbirdeyevisualslam_amd import cabi
+    warm = synth.make_ba_problem(4212, n_kf=6, n_mp=900, n_mpb=120)   # leaves the staging block non-empty
+    a0, _, keep0 = ba_problem.local_ba_args(warm, with_odom=1)
+    H.call("fb_local_ba", a0)
+    p = synth.make_ba_problem(4210, n_kf=30, n_fixed=2, n_mp=300, n_mpb=60)
+    assert int((p["kf_fixed"] == 0).sum()) == 28
+    a, dev, keep, before = _dev_inputs(p, with_odom=1)
+    s = torch.cuda.Stream()
+    with torch.cuda.stream(s):
+        rc = fb.lib().fb_local_ba_dev(C.byref(a), C.c_void_p(s.cuda_stream))
+    assert rc == cabi.FB_ERR_CAPACITY
+    assert b"23 free key frames" in fb.lib().fb_last_error()
+    torch.cuda.synchronize()
+    for k in ("kf_Tcw", "mp_xw", "mpb_xw", "obs_outlier", "bobs_outlier"):
+        got = dev[k].cpu().numpy()
+        assert got.tobytes() == before[k].tobytes(), k
+    q = synth.make_ba_problem(4211, n_kf=6, n_mp=300, n_mpb=60)
+    rc, out_d = _run_dev(q, with_odom=1)
+    assert rc == 0
+    a2, out_h, keep2 = ba_problem.local_ba_args(q, with_odom=1)
+    H.call("fb_local_ba", a2)
+    for k in ("kf_Tcw", "mp_xw", "mpb_xw", "obs_outlier"):
+        assert out_d[k].tobytes() == out_h[k].tobytes(), k
+    nb = len(q["bobs_kf"])
+    np.testing.assert_array_equal(out_d["bobs_outlier"][:nb], out_h["bobs_outlier"][:nb])
+
+
+def test_local_ba_plan_boundary_23_24_free_key_frames():
+    """The plan's threshold between the LDS-resident and the HBM-resident reduced system: 23 free key frames run the
+    device-resident schedule from either entry point (byte-equal), 24 are refused from device inputs and take the
+    HBM-resident path from host pointers; both sides of the boundary meet the oracle bar."""
+    from fishbirdeyevisualslam_amd import cabi
+    p = synth.make_ba_problem(4220, n_kf=25, n_fixed=2, n_mp=300, n_mpb=60)
+    assert int((p["kf_fixed"] == 0).sum()) == 23
+    out_o, out_h, _, _ = _run(p, with_odom=1)
+    rc, out_d = _run_dev(p, with_odom=1)
+    assert rc == 0
+    for k in ("kf_Tcw", "mp_xw", "mpb_xw", "obs_outlier"):
+        assert out_d[k].tobytes() == out_h[k].tobytes(), k
+    nb = len(p["bobs_kf"])
+    np.testing.assert_array_equal(out_d["bobs_outlier"][:nb], out_h["bobs_outlier"][:nb])
+    _compare(p, out_o, out_h, 1)
+    _compare(p, out_o, out_d, 1)
+    p = synth.make_ba_problem(4221, n_kf=26, n_fixed=2, n_mp=300, n_mpb=60)
+    assert int((p["kf_fixed"] == 0).sum()) == 24
+    rc, _ = _run_dev(p, with_odom=1)
+    assert rc == cabi.FB_ERR_CAPACITY
+    out_o, out_h, _, _ = _run(p, with_odom=1)
+    _compare(p, out_o, out_h, 1)
+
+
 def test_triangulation_matches_feed_the_ba_on_the_device():
     """LocalMapping's hand-over without a host copy (LocalMapping.cc:231-476 -> :87-96): SearchForTriangulation (M7) runs on
     the device, its match array is turned into new points and observations by device code (torch ops standing in for the host's
