@@ -1,0 +1,352 @@
+"""Bundle-adjustment graphs that synth.make_ba_problem never produces, in plain numpy, plus the two checks every BA test
+shares: the one-sided chi2 / depth gate recomputed in float64 from a returned state, and the per-element parity norm.
+
+Every constructor starts from a small synth.make_ba_problem graph, edits its arrays and returns (problem, expectations).
+The expectations are known by construction:
+    with_odom        the entry mode the case is meant for
+    front_flags      {front edge index: the outlier flag it must come back with}
+    special          the edges / landmarks / key frames the case is about (for the case's own assertions)
+The constructions are proven on the CPU by tests/test_ba_structure.py (oracle only) before any kernel is compared on them.
+"""
+import numpy as np
+
+from fishbirdeyevisualslam_amd import synth
+
+CHI2_GATE = 5.991          # Optimizer.cc: chi2 > 5.991 is an outlier (2 degrees of freedom, 95 %)
+GATE_BAND = 0.01           # recomputed chi2 within 1 % of the gate is left out of the one-sided check (outputs are float32)
+REL_TOL = 1e-4             # BASELINE.json north_star
+
+OBS_KEYS = ("obs_kf", "obs_mp", "obs_uv", "obs_inv_sigma2")
+SMALL = dict(n_kf=24, n_fixed=4)   # 20 free key frames: device / host LM, NT = 8
+BIG = dict(n_kf=26, n_fixed=2)     # 24 free key frames: plan() selects the HBM-resident path
+
+
+# ---- helpers over a problem dict ----------------------------------------------------------------------------------------------
+def _base(seed, n_kf, n_fixed, n_mp, n_mpb):
+    p = synth.make_ba_problem(seed, n_kf=n_kf, n_fixed=n_fixed, n_mp=n_mp, n_mpb=n_mpb)
+    return {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in p.items()}
+
+
+def _keep_edges(p, keep):
+    """Keep the front observations selected by the boolean mask (order preserved); returns old -> new edge index."""
+    keep = np.asarray(keep, bool)
+    new = np.cumsum(keep) - 1
+    for k in OBS_KEYS:
+        p[k] = np.ascontiguousarray(p[k][keep])
+    return np.where(keep, new, -1)
+
+
+def _true_cam(p, kf, mp):
+    T = p["kf_true"].astype(np.float64).reshape(-1, 3, 4)[kf]
+    X = p["mp_true"].astype(np.float64)[mp]
+    return np.einsum("...ij,...j->...i", T[..., :3], X) + T[..., 3]
+
+
+def _project(p, pc):
+    return np.stack([p["fx"] * pc[..., 0] / pc[..., 2] + p["cx"], p["fy"] * pc[..., 1] / pc[..., 2] + p["cy"]], -1)
+
+
+def _tangential(p, uv):
+    """Unit vectors perpendicular to the ray from the principal point: the cameras drive forward, so the epipolar lines are
+    close to radial and no change of a point's depth absorbs a tangential displacement."""
+    r = np.asarray(uv, np.float64) - np.array([p["cx"], p["cy"]])
+    n = np.maximum(np.linalg.norm(r, axis=-1, keepdims=True), 1e-9)
+    t = np.stack([-r[..., 1], r[..., 0]], -1) / n
+    t[n[..., 0] < 1e-6] = (1.0, 0.0)
+    return t
+
+
+def edges_of(p, l):
+    return np.nonzero(p["obs_mp"] == l)[0]
+
+
+def observers(p):
+    return np.bincount(p["obs_mp"], minlength=len(p["mp_xw"]))
+
+
+# ---- the cases ------------------------------------------------------------------------------------------------------------------
+def _replace_landmark_edges(p, l, kfs, uvs, inv_sigma2):
+    """The front observations of landmark l become (kfs, uvs), in place of its old block of edges."""
+    old = edges_of(p, l)
+    at = int(old[0])
+    keep = np.ones(len(p["obs_kf"]), bool)
+    keep[old] = False
+    at -= int((~keep[:at]).sum())
+    _keep_edges(p, keep)
+    n = len(kfs)
+    p["obs_kf"] = np.insert(p["obs_kf"], at, np.asarray(kfs, np.int32))
+    p["obs_mp"] = np.insert(p["obs_mp"], at, np.full(n, l, np.int32))
+    p["obs_uv"] = np.insert(p["obs_uv"], at, np.asarray(uvs, np.float32).reshape(n, 2), axis=0)
+    p["obs_inv_sigma2"] = np.insert(p["obs_inv_sigma2"], at, np.full(n, inv_sigma2, np.float32))
+
+
+def behind_camera(seed=5104, big=False, n_special=4):
+    """A few landmarks 3-10 m BEHIND one of their observing cameras.  That camera's measurement is the pin-hole formula at
+    the negative depth (finite, and consistent with the generating geometry), so the edge's chi2 stays small and only the
+    depth clause of the gate (isDepthPositive) can flag it.  The other observers see the point in front, ordinary noise.
+
+    The point is placed 3.2 m ahead and 0.5-0.8 m to the side of one of the first two key frames: every key frame that still
+    has it in its image observes it (about five, half a metre apart and mostly fixed, so it is triangulated to a centimetre),
+    and the LAST key frame, which has driven 8-9 m past it, is the camera behind.  That measurement is taken at the coarsest
+    pyramid level (sigma^2 = 1.2^14): a centimetre of structure error is about a pixel there, a chi2 well below 3, so the
+    edge still fits at the returned state although it left the system at the gate."""
+    p = _base(seed, n_mp=300, n_mpb=60, **(BIG if big else SMALL))
+    g = np.random.default_rng(seed)
+    n_kf = len(p["kf_fixed"])
+    T = p["kf_true"].astype(np.float64).reshape(-1, 3, 4)
+    w, h = 2.0 * p["cx"], 2.0 * p["cy"]
+    pairs = []
+    for i, l in enumerate(np.nonzero(observers(p) >= 2)[0][10:10 + n_special]):
+        a = i % 2
+        Xc = np.array([(0.5 + 0.3 * g.random()) * (1 if i % 4 < 2 else -1), 0.2 * g.random(), 3.2])
+        Xw = T[a, :, :3].T @ (Xc - T[a, :, 3])
+        p["mp_true"][l] = Xw
+        p["mp_xw"][l] = (Xw + g.normal(0, 0.05, 3)).astype(np.float32)
+        Xw = p["mp_true"][l].astype(np.float64)
+        pc = np.einsum("kij,j->ki", T[:, :, :3], Xw) + T[:, :, 3]
+        uv = _project(p, pc)
+        front = [k for k in range(n_kf) if pc[k, 2] > 1.0 and 0 <= uv[k, 0] < w and 0 <= uv[k, 1] < h]
+        k_s = n_kf - 1
+        assert len(front) >= 4 and -10.0 <= pc[k_s, 2] <= -3.0, (len(front), pc[k_s, 2])
+        uvs = np.concatenate([uv[front] + g.normal(0, 1.0, (len(front), 2)), uv[k_s][None]])   # level-0 noise; exact behind
+        _replace_landmark_edges(p, l, front + [k_s], uvs, 1.0)
+        p["obs_inv_sigma2"][edges_of(p, l)[-1]] = synth.scale_tables()[3][7]
+        pairs.append((int(l), k_s))
+    special = [int(np.nonzero((p["obs_mp"] == l) & (p["obs_kf"] == k))[0][0]) for l, k in pairs]
+    return p, dict(with_odom=1, front_flags={e: 1 for e in special}, special=np.array(special))
+
+
+def landmark_fully_gated(seed=5204, big=False, n_special=5, px=80.0):
+    """Landmarks with exactly two observations, displaced by `px` (>= 50) pixels tangentially in opposite senses: no point fits
+    both, both edges leave at the gate after round 1 and the landmark has no active edge in round 2 (Hll = lambda I, bl = 0;
+    in g2o the vertex leaves the system)."""
+    assert px >= 50.0
+    p = _base(seed, n_mp=300, n_mpb=60, **(BIG if big else SMALL))
+    nobs = observers(p)
+    chosen = np.nonzero(nobs >= 2)[0][3:3 + n_special]
+    keep = np.ones(len(p["obs_kf"]), bool)
+    for l in chosen:
+        keep[edges_of(p, l)[2:]] = False
+    _keep_edges(p, keep)
+    flags, lm = {}, []
+    for l in chosen:
+        e0, e1 = edges_of(p, l)
+        for e, sgn in ((e0, 1.0), (e1, -1.0)):
+            p["obs_uv"][e] = (p["obs_uv"][e] + sgn * px * _tangential(p, p["obs_uv"][e])).astype(np.float32)
+            flags[int(e)] = 1
+        lm.append(int(l))
+    return p, dict(with_odom=1, front_flags=flags, special=np.array(lm))
+
+
+def keyframe_fully_gated(seed=5303, big=False):
+    """with_odom = 0.  Every observation of one free key frame is displaced by 150-300 px (>= 50) in a random direction: all its
+    edges leave at the gate, its Hpp block is lambda I in round 2.  (Without odometry the six degrees of freedom of that pose
+    are held by nothing else, and a Huber cost lets a pose interpolate three of its observations exactly; displacements of
+    this size keep such a fit out of reach of the five iterations of round 1.  tests/test_ba_structure.py proves that on
+    the oracle for the seed used.)  A second free key frame has no observation at all (in g2o it never enters the system).  A landmark that the removal
+    leaves with one observer loses that one too and becomes an isolated vertex, so no new single-observation landmark rides
+    along."""
+    p = _base(seed, n_mp=300, n_mpb=60, **(BIG if big else SMALL))
+    free = np.nonzero(p["kf_fixed"] == 0)[0]
+    kf_gated, kf_empty = int(free[len(free) // 3]), int(free[2 * len(free) // 3])
+    keep = p["obs_kf"] != kf_empty
+    # the displaced observations sit on landmarks with at least three other observers: on a two-observer landmark the Huber
+    # cost cannot tell which of the two is the wrong one
+    cnt = np.bincount(p["obs_mp"][keep], minlength=len(p["mp_xw"]))
+    keep &= ~((p["obs_kf"] == kf_gated) & (cnt[p["obs_mp"]] < 4))
+    left = np.bincount(p["obs_mp"][keep], minlength=len(p["mp_xw"]))
+    keep &= left[p["obs_mp"]] >= 2
+    _keep_edges(p, keep)
+    g = np.random.default_rng(seed)
+    ee = np.nonzero(p["obs_kf"] == kf_gated)[0]
+    assert len(ee) >= 20
+    th, mag = g.uniform(0.0, 2.0 * np.pi, len(ee)), g.uniform(150.0, 300.0, len(ee))
+    p["obs_uv"][ee] = (p["obs_uv"][ee] + mag[:, None] * np.stack([np.cos(th), np.sin(th)], 1)).astype(np.float32)
+    return p, dict(with_odom=0, front_flags={int(e): 1 for e in ee}, special=np.array([kf_gated, kf_empty]))
+
+
+def single_observation_landmark(seed=5405, big=False, n_special=6):
+    """Landmarks cut down to ONE edge: Hll has rank 2, lambda keeps it invertible."""
+    p = _base(seed, n_mp=300, n_mpb=60, **(BIG if big else SMALL))
+    chosen = np.arange(7, 7 + 11 * n_special, 11)
+    keep = np.ones(len(p["obs_kf"]), bool)
+    for l in chosen:
+        keep[edges_of(p, l)[1:]] = False
+    _keep_edges(p, keep)
+    assert (observers(p)[chosen] == 1).all()
+    return p, dict(with_odom=1, front_flags={}, special=chosen)
+
+
+def landmark_seen_only_by_fixed(seed=5501, big=False, n_special=5):
+    """Every observer of a handful of landmarks is a FIXED key frame: pj < 0 on each of their edges, so they have Hll and bl
+    but no W block and no row in the Schur complement (structure-only for those points)."""
+    p = _base(seed, n_mp=300, n_mpb=60, **(BIG if big else SMALL))
+    g = np.random.default_rng(seed)
+    fixed = np.nonzero(p["kf_fixed"] == 1)[0]
+    assert len(fixed) >= 2
+    fa, fb = int(fixed[0]), int(fixed[-1])
+    za, zb = (_true_cam(p, np.full(len(p["mp_xw"]), k), np.arange(len(p["mp_xw"])))[:, 2] for k in (fa, fb))
+    chosen = np.nonzero((za > 2.0) & (zb > 2.0) & (observers(p) >= 2))[0][:n_special]
+    assert len(chosen) == n_special
+    keep = np.ones(len(p["obs_kf"]), bool)
+    for l in chosen:
+        keep[edges_of(p, l)[2:]] = False
+    _keep_edges(p, keep)
+    ee = []
+    for l in chosen:
+        for e, k in zip(edges_of(p, l), (fa, fb)):
+            p["obs_kf"][e] = k
+            sig = 1.0 / np.sqrt(float(p["obs_inv_sigma2"][e]))
+            p["obs_uv"][e] = (_project(p, _true_cam(p, k, l)) + g.normal(0, 1.0, 2) * sig).astype(np.float32)
+            ee.append(int(e))
+    assert (p["kf_fixed"][p["obs_kf"][ee]] == 1).all()
+    return p, dict(with_odom=1, front_flags={}, special=chosen, special_edges=np.array(ee))
+
+
+STRUCTURAL = dict(behind_camera=behind_camera, landmark_fully_gated=landmark_fully_gated, keyframe_fully_gated=keyframe_fully_gated,
+                  single_observation_landmark=single_observation_landmark, landmark_seen_only_by_fixed=landmark_seen_only_by_fixed)
+
+FREE_COUNTS = tuple(range(1, 25))
+# seeds: 5600 + f, except where that graph puts a chi2 within 1e-3 of the gate on the oracle (tests/test_ba_structure.py)
+_FREE_SEED = {10: 5730, 21: 5741}
+
+
+def free_count(f, seed=None):
+    """f free key frames and 2 fixed: P6 = 6 f, NT = (6 f + 1 + 15) / 16 tiles, MAXT = 9 / 20 / 34 for NT <= 8 / 12 / 16;
+    f = 24 is the first count plan() hands to the HBM-resident path."""
+    p = _base(_FREE_SEED.get(f, 5600 + f) if seed is None else seed, n_kf=f + 2, n_fixed=2, n_mp=120, n_mpb=30)
+    assert int((p["kf_fixed"] == 0).sum()) == f
+    return p, dict(with_odom=1, front_flags={}, special=np.zeros(0, int))
+
+
+# plan() in ba_driver.inc: nWg = min(256, ceil(npt / 16)); lmPerWg = ceil(ceil(npt / nWg) / 16) * 16; nWg = ceil(npt / lmPerWg).
+# Up to 4096 points lmPerWg is 16 = CHUNK, so the last workgroup (= its only chunk) is partial whenever npt % 16 != 0:
+# 1, 15, 17, 33 and 100 (seven workgroups, the last with four landmarks); 16 is the exact fit.  FB_BA_NWG caps nWg: with 2 and
+# npt = 100, lmPerWg = 64 and the second workgroup holds [64, 100): two full chunks and a tail of four, the only way to a
+# workgroup with several chunks (the clear-after-MFMA traversal) at test size.
+POINT_COUNTS = (1, 15, 16, 17, 33, 100)
+NWG_CAP_FOR_CHUNKS = 2
+
+
+def point_count(n, seed=None):
+    """npt = n_mp + n_mpb (dims_of: the bird points follow the front points in one landmark array) set to n."""
+    n_mpb = n // 5
+    p = _base(5700 + n if seed is None else seed, n_kf=6, n_fixed=2, n_mp=n - n_mpb, n_mpb=n_mpb)
+    assert len(p["mp_xw"]) + len(p["mpb_xw"]) == n
+    return p, dict(with_odom=1, front_flags={}, special=np.zeros(0, int))
+
+
+# ---- checks on a returned state -----------------------------------------------------------------------------------------------
+def recompute(p, out, with_odom, wF=1.0, wB=1.0):
+    """Depth and chi2 of every front edge (and chi2 of every bird edge) in float64 from the returned float32 state."""
+    T = np.asarray(out["kf_Tcw"], np.float64).reshape(-1, 3, 4)
+    X = np.asarray(out["mp_xw"], np.float64).reshape(-1, 3)
+    pc = np.einsum("nij,nj->ni", T[p["obs_kf"], :, :3], X[p["obs_mp"]]) + T[p["obs_kf"], :, 3]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = _project(p, pc) - np.asarray(p["obs_uv"], np.float64).reshape(-1, 2)
+    info = p["obs_inv_sigma2"].astype(np.float64) * (wF if with_odom else 1.0)
+    res = dict(depth=pc[:, 2], chi2=info * (r ** 2).sum(1))
+    if with_odom and len(p["bobs_kf"]):
+        Xb = np.asarray(out["mpb_xw"], np.float64).reshape(-1, 3)
+        pb = np.einsum("nij,nj->ni", T[p["bobs_kf"], :, :3], Xb[p["bobs_mpb"]]) + T[p["bobs_kf"], :, 3]
+        rb = pb - np.asarray(p["bobs_xc"], np.float64).reshape(-1, 3)
+        res["bird_chi2"] = p["bobs_inv_sigma2"].astype(np.float64) * wB * (rb ** 2).sum(1)
+    return res
+
+
+def gate_check(p, out, with_odom):
+    """One-sided: every edge returned with flag 0 has depth > 0 and chi2 <= 5.991 at the returned state.  Edges whose
+    recomputed chi2 lies within 1 % of the gate are left out.  (Flag-1 edges are not checked: an edge gated after round 1
+    keeps the chi2 of that moment, as in the reference.)  Returns (violating edge indices, share of edges left out)."""
+    r = recompute(p, out, with_odom)
+    chi2 = r["chi2"]
+    flags = np.asarray(out["obs_outlier"])[: len(chi2)]
+    depth = r["depth"]
+    if "bird_chi2" in r:
+        nb = len(r["bird_chi2"])
+        chi2 = np.concatenate([chi2, r["bird_chi2"]])
+        flags = np.concatenate([flags, np.asarray(out["bobs_outlier"])[:nb]])
+        depth = np.concatenate([depth, np.ones(nb)])
+    band = np.abs(chi2 - CHI2_GATE) <= GATE_BAND * CHI2_GATE
+    bad = (flags == 0) & ~band & (~(depth > 0.0) | ~(chi2 <= CHI2_GATE))
+    return np.nonzero(bad)[0], float(band.sum()) / max(len(chi2), 1)
+
+
+def pose_rel(got, ref):
+    """Per key frame: max |difference| over its 3x4, scaled by max(1, max |T_k|) of ITS OWN reference pose."""
+    g, r = np.asarray(got, np.float64).reshape(-1, 12), np.asarray(ref, np.float64).reshape(-1, 12)
+    if len(r) == 0:
+        return np.zeros(0)
+    return np.abs(g - r).max(1) / np.maximum(1.0, np.abs(r).max(1))
+
+
+def point_rel(got, ref):
+    """Per landmark: max |difference| over its coordinates, scaled by max(1, ||x||) of ITS OWN reference position."""
+    g, r = np.asarray(got, np.float64).reshape(-1, 3), np.asarray(ref, np.float64).reshape(-1, 3)
+    if len(r) == 0:
+        return np.zeros(0)
+    return np.abs(g - r).max(1) / np.maximum(1.0, np.linalg.norm(r, axis=1))
+
+
+def worst_rel(per_element):
+    """Worst value of a per-element array; a non-finite entry is the worst there is (max() would drop a NaN)."""
+    per_element = np.asarray(per_element, np.float64)
+    if per_element.size == 0:
+        return 0.0
+    return float("inf") if not np.isfinite(per_element).all() else float(per_element.max())
+
+
+def worst_pose_rel(got, ref):
+    return worst_rel(pose_rel(got, ref))
+
+
+def worst_point_rel(got, ref):
+    return worst_rel(point_rel(got, ref))
+
+
+# ---- the cases by id, and the oracle's answer to each (computed once, shared by the CPU and the GPU tests, never modified) ----
+STRUCTURAL_IDS = tuple(("structural", name, False) for name in STRUCTURAL)
+STRUCTURAL_BIG_IDS = tuple(("structural", name, True) for name in STRUCTURAL)
+FREE_COUNT_IDS = tuple(("free_count", f) for f in FREE_COUNTS)
+POINT_COUNT_IDS = tuple(("point_count", n) for n in POINT_COUNTS)
+ALL_IDS = STRUCTURAL_IDS + STRUCTURAL_BIG_IDS + FREE_COUNT_IDS + POINT_COUNT_IDS
+
+
+def case_name(cid):
+    if cid[0] == "structural":
+        return cid[1] + ("-24free" if cid[2] else "")
+    return "%s(%d)" % cid
+
+
+def make(cid):
+    if cid[0] == "structural":
+        return STRUCTURAL[cid[1]](big=cid[2])
+    return dict(free_count=free_count, point_count=point_count)[cid[0]](cid[1])
+
+
+_ORACLE = {}
+
+
+def oracle(cid):
+    """(problem, expectations, oracle outputs, smallest |chi2 - 5.991| / 5.991 over the oracle's gate decisions)."""
+    if cid not in _ORACLE:
+        import ctypes as C
+
+        import oracle_lib as O
+        from fishbirdeyevisualslam_amd import ba_problem
+        p, ex = make(cid)
+        O.lib().orc_ba_margin_reset()
+        a, out, keep = ba_problem.local_ba_args(p, with_odom=ex["with_odom"])
+        O.call("orc_local_ba", a)
+        margin, decisions = C.c_double(0), C.c_long(0)
+        O.lib().orc_ba_margin_get(C.byref(margin), C.byref(decisions))
+        for v in out.values():
+            v.setflags(write=False)
+        _ORACLE[cid] = (p, ex, out, margin.value)
+    return _ORACLE[cid]
+
+
+def check_flags_by_construction(ex, out):
+    got = np.asarray(out["obs_outlier"])
+    wrong = [e for e, f in ex["front_flags"].items() if got[e] != f]
+    assert not wrong, "front edges %s did not get the flag their construction demands" % wrong[:10]

@@ -45,9 +45,11 @@ def test_pose_mask_sweep_240_problems(capsys):
 
 
 def test_local_ba_gate_sweep_60_problems(capsys):
-    """60 LocalBundleAdjustmentWithOdom problems (6-20 key frames): outlier flags identical, poses / landmarks within 1e-4;
+    """60 LocalBundleAdjustmentWithOdom problems (6-20 key frames): outlier flags identical, poses / landmarks within 1e-4 per
+    element (each pose by max(1, max|T_k|) of its own 3x4, each landmark by max(1, ||x||): ba_cases.pose_rel / point_rel);
     PRINTS the smallest |chi2 - 5.991| / 5.991 over every decision of the chi2 gate between the two optimisations and of the
     final outlier collection (Optimizer.cc:2534-2565, 2579-2610), front and bird edges: the margin behind 'identical flags'."""
+    import ba_cases as BC
     from fishbirdeyevisualslam_amd import ba_problem
     O.lib().orc_ba_margin_reset()
     worst_pose = worst_pt = 0.0
@@ -59,9 +61,8 @@ def test_local_ba_gate_sweep_60_problems(capsys):
         O.call("orc_local_ba", a)
         a2, oh, k2 = ba_problem.local_ba_args(p, with_odom=1)
         H.call("fb_local_ba", a2)
-        rel = lambda x, y: float(np.abs(x - y).max() / max(1.0, np.abs(y).max()))
-        worst_pose = max(worst_pose, rel(oh["kf_Tcw"], oo["kf_Tcw"]))
-        worst_pt = max(worst_pt, rel(oh["mp_xw"], oo["mp_xw"]), rel(oh["mpb_xw"], oo["mpb_xw"]))
+        worst_pose = max(worst_pose, BC.worst_pose_rel(oh["kf_Tcw"], oo["kf_Tcw"]))
+        worst_pt = max(worst_pt, BC.worst_point_rel(oh["mp_xw"], oo["mp_xw"]), BC.worst_point_rel(oh["mpb_xw"], oo["mpb_xw"]))
         assert worst_pose <= 1e-4 and worst_pt <= 1e-4, (i, worst_pose, worst_pt)
         np.testing.assert_array_equal(oh["obs_outlier"], oo["obs_outlier"], err_msg="problem %d front flags" % i)
         nb = len(p["bobs_kf"])
@@ -69,8 +70,8 @@ def test_local_ba_gate_sweep_60_problems(capsys):
     margin, decisions = C.c_double(0), C.c_long(0)
     O.lib().orc_ba_margin_get(C.byref(margin), C.byref(decisions))
     with capsys.disabled():
-        print("\n[local BA sweep] %d problems (6-20 key frames), %d chi2-gate decisions: outlier flags identical; worst relative difference "
-              "poses %.3g, landmarks %.3g; smallest |chi2 - 5.991| / 5.991 = %.3g" % (n, decisions.value, worst_pose, worst_pt, margin.value))
+        print("\n[local BA sweep] %d problems (6-20 key frames), %d chi2-gate decisions: outlier flags identical; worst per-element relative "
+              "difference poses %.3g, landmarks %.3g; smallest |chi2 - 5.991| / 5.991 = %.3g" % (n, decisions.value, worst_pose, worst_pt, margin.value))
     assert decisions.value > 100000
 
 
