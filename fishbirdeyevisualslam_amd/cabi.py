@@ -270,6 +270,16 @@ class CovisWindow(C.Structure):
                 ("bobs_xc", _vp), ("bobs_inv_sigma2", _vp), ("header", _vp)]
 
 
+FB_LOCAL_MAP_MAX_EXPAND = 80
+
+
+class LocalMapArgs(C.Structure):
+    _fields_ = [("batch", _i32), ("kp_stride", _i32), ("d_n", _vp), ("d_map_point", _vp), ("d_kf_bad", _vp),
+                ("cap_kf", _i32), ("d_local_kf", _vp), ("d_n_local_kf", _vp), ("cap_mp", _i32), ("d_local_mp", _vp),
+                ("d_n_local_mp", _vp), ("d_ref_kf", _vp), ("d_n_voters", _vp), ("d_overflow", _vp), ("d_gate_row", _vp),
+                ("gate_min", _i32), ("reuse_index", _i32)]
+
+
 class BirdFilterArgs(C.Structure):
     _fields_ = [("batch", _i32), ("match_stride", _i32), ("kp1_stride", _i32), ("kp2_stride", _i32),
                 ("n_matches", _vp), ("query_idx", _vp), ("train_idx", _vp), ("cam_xyz1", _vp), ("cam_xyz2", _vp),
@@ -384,6 +394,9 @@ EXPORTS = [
     "fb_covis_kfdb_rows", "fb_covis_keyframe_culling_dev", "fb_covis_keyframe_culling",
     "fb_covis_reserve_window", "fb_covis_local_window_dev", "fb_covis_local_window_header", "fb_covis_local_window",
     "fb_covis_window_scatter_dev",
+    "fb_covis_tree_set_dev", "fb_covis_tree_get_dev", "fb_covis_tree_get", "fb_covis_change_parent_dev", "fb_covis_erase_child_dev",
+    "fb_covis_children_dev", "fb_covis_children", "fb_covis_parent_dev", "fb_covis_first_connection_dev",
+    "fb_covis_tree_erase_keyframe_dev", "fb_covis_local_map_dev", "fb_covis_local_map", "fb_covis_reserve_local_map",
     "fb_in_frustum_dev", "fb_in_frustum", "fb_undistort_keypoints_dev", "fb_undistort_keypoints", "fb_image_bounds",
     "fb_pose_opt_batch_dev", "fb_pose_opt", "fb_pose_gather_front_dev", "fb_pose_gather_bird_dev",
     "fb_frame_create", "fb_frame_destroy", "fb_frame_extract_dev", "fb_frame_extract", "fb_frame_set_pose_dev",
@@ -391,6 +404,7 @@ EXPORTS = [
     "fb_frame_bird_mappoint_match_dev", "fb_frame_search_by_projection_dev", "fb_frame_pose_optimization_dev",
     "fb_frame_discard_outliers_dev", "fb_frame_match_bird_points_dev", "fb_frame_search_local_points_dev",
     "fb_frame_finish_dev", "fb_frame_drop_outliers_dev", "fb_frame_track_dev", "fb_frame_track_motion_model_dev", "fb_frame_track_local_map_dev",
+    "fb_frame_update_local_map_dev", "fb_frame_track_graph_dev",
     "fb_frame_copy_dev", "fb_frame_compute_bow_dev", "fb_frame_bow_view_dev", "fb_frame_search_by_bow_dev", "fb_frame_track_reference_dev", "fb_frame_track_using_bird_dev", "fb_frame_view_dev", "fb_frame_download", "fb_frame_counts",
     "fb_local_ba", "fb_local_ba_dev", "fb_local_ba_sharded", "fb_local_ba_sharded_rccl", "fb_rccl_get_unique_id", "fb_rccl_comm_init", "fb_rccl_comm_destroy", "fb_rccl_comm_info", "fb_global_ba",
 ]

@@ -226,3 +226,79 @@ class CovisibilityGraph:
                                                 _p(n), _p(er), _p(ber), _stream()), "fb_covis_window_scatter_dev")
         self._keep = (m, t, w, obs_outlier, bobs_outlier)
         return n, er, ber
+
+    # ---- the spanning tree -------------------------------------------------------------------------------------------------------
+    def tree_set(self, parent=None, linked=None, first=None):
+        p = None if parent is None else self._dev(parent)
+        l = None if linked is None else self._dev(linked, torch.uint8)
+        f = None if first is None else self._dev(first, torch.uint8)
+        check(lib().fb_covis_tree_set_dev(self.h, _p(p), _p(l), _p(f), _stream()), "fb_covis_tree_set_dev")
+        self._keep = (p, l, f)
+
+    def tree_get(self):
+        """(parent int32[K], linked uint8[K], first uint8[K]) device tensors"""
+        p, l, f = self._i32(self.K, -7), torch.zeros(self.K, dtype=torch.uint8, device=self.device), torch.zeros(self.K, dtype=torch.uint8, device=self.device)
+        check(lib().fb_covis_tree_get_dev(self.h, _p(p), _p(l), _p(f), _stream()), "fb_covis_tree_get_dev")
+        return p, l, f
+
+    def change_parent(self, slot, parent):
+        check(lib().fb_covis_change_parent_dev(self.h, int(slot), int(parent), _stream()), "fb_covis_change_parent_dev")
+
+    def erase_child(self, parent, slot):
+        check(lib().fb_covis_erase_child_dev(self.h, int(parent), int(slot), _stream()), "fb_covis_erase_child_dev")
+
+    def children(self, slot):
+        n, s = self._i32(1), self._i32(self.K, -1)
+        check(lib().fb_covis_children_dev(self.h, int(slot), _p(n), _p(s), _stream()), "fb_covis_children_dev")
+        return n, s
+
+    def parent(self, slot):
+        p = self._i32(1, -7)
+        check(lib().fb_covis_parent_dev(self.h, int(slot), _p(p), _stream()), "fb_covis_parent_dev")
+        return p
+
+    def first_connection(self, slots, n_counter, front, id0_slot=-1, now_state4=False, kf_frame_id=None, kf_in_map=None):
+        """KeyFrame.cc:665-690 on the outputs of update_connections(m, slots)"""
+        slots = self._dev(slots).reshape(-1)
+        fid = None if kf_frame_id is None else self._dev(kf_frame_id)
+        inm = None if kf_in_map is None else self._dev(kf_in_map, torch.uint8)
+        check(lib().fb_covis_first_connection_dev(self.h, slots.numel(), _p(slots), _p(n_counter), _p(front), int(id0_slot),
+                                                  1 if now_state4 else 0, _p(fid), _p(inm), _stream()), "fb_covis_first_connection_dev")
+        self._keep = (slots, n_counter, front, fid, inm)
+
+    def tree_erase_keyframe(self, slot, kf_bad):
+        b = self._dev(kf_bad, torch.uint8)
+        check(lib().fb_covis_tree_erase_keyframe_dev(self.h, int(slot), _p(b), _stream()), "fb_covis_tree_erase_keyframe_dev")
+        self._keep = b
+
+    # ---- Tracking::UpdateLocalMap --------------------------------------------------------------------------------------------------
+    def reserve_local_map(self, n_mp, n_obs, n_q=0, batch=1, with_window=False):
+        check(lib().fb_covis_reserve_local_map(self.h, int(n_mp), int(n_obs), int(n_q), int(batch), 1 if with_window else 0),
+              "fb_covis_reserve_local_map")
+
+    def local_map_arrays(self, n, map_point, kf_bad, cap_kf, cap_mp, local_kf=None, ref_kf=None, gate_row=None, gate_min=0, guard=0):
+        """Device arrays of a fb_local_map_args for frames n [B], map_point [B][S]; local_kf: per sequence the list that comes in.
+        Each output array is followed by `guard` elements the library never sees.  -> (dict of tensors, cabi.LocalMapArgs)"""
+        mp = self._dev(map_point)
+        B, S = mp.shape
+        t = dict(d_n=self._dev(n).reshape(-1), d_map_point=mp.clone(), d_kf_bad=self._dev(kf_bad, torch.uint8))
+        t["d_local_kf"] = torch.full((B * cap_kf + guard + 1,), -5, dtype=torch.int32, device=self.device)
+        t["d_n_local_kf"] = self._i32(B)
+        for b, l in enumerate(local_kf or ()):
+            t["d_local_kf"][b * cap_kf:b * cap_kf + min(len(l), cap_kf)] = self._dev(list(l)[:cap_kf]) if len(l) and cap_kf else self._i32(0)[:0]
+            t["d_n_local_kf"][b] = len(l)
+        t["d_local_mp"] = torch.full((B * cap_mp + guard + 1,), -5, dtype=torch.int32, device=self.device)
+        t["d_n_local_mp"] = self._i32(B, -5)
+        t["d_ref_kf"] = self._i32(B, -1) if ref_kf is None else self._dev(ref_kf).reshape(-1).clone()
+        t["d_n_voters"], t["d_overflow"] = self._i32(B, -5), self._i32(B, -5)
+        if gate_row is not None:
+            t["d_gate_row"] = self._dev(gate_row).reshape(-1)
+        a = cabi.LocalMapArgs()
+        cabi.fill(a, batch=B, kp_stride=S, cap_kf=int(cap_kf), cap_mp=int(cap_mp), gate_min=int(gate_min), reuse_index=0, **t)
+        return t, a
+
+    def local_map(self, m, a, reuse_index=False):
+        """Tracking::UpdateLocalMap for the arrays of local_map_arrays; enqueues only"""
+        a.reuse_index = 1 if reuse_index else 0
+        check(lib().fb_covis_local_map_dev(self.h, C.byref(m.c), C.byref(a), _stream()), "fb_covis_local_map_dev")
+        self._keep = (m, a)

@@ -1,7 +1,8 @@
 """Synthetic maps for the covisibility graph (fb_covis_*): key frames, map points and the observation edge list as the arrays
 of fb_covis_map, with the reference's quirks planted.
 
-    python -m fishbirdeyevisualslam_amd.covis_problem --probe     # times UpdateConnections / KeyFrameCulling at a LocalMapping-like size
+    python -m fishbirdeyevisualslam_amd.covis_problem --probe     # times UpdateConnections / KeyFrameCulling / the window / the local
+                                                                  # map and the tree calls at a LocalMapping-like size
 """
 import numpy as np
 
@@ -333,9 +334,94 @@ def _probe():
     print("window of key frame %d: %s" % (cur, hd))
     print("device local_window (collect, enqueued):  %.3f ms" % timed(lambda: G.local_window(m, t, cur, False)))
     print("device window_scatter:                    %.3f ms" % timed(lambda: G.window_scatter(m, t, w)))
+    _probe_local_map(p, m, G, t, cur)
     print("errors counted: %d" % G.error_count())
     G.close()
     _probe_host(p, cur)
+
+
+def local_map_frame(p, cur, n=2000):
+    """mvpMapPoints of a frame that tracked key frame cur's points (its first n features)"""
+    return np.ascontiguousarray(p["kf_mp"][cur][:n], np.int32)
+
+
+def _median_ms(fn, reps=50, warm=10):
+    """the whole call between two events: median of `reps` after `warm` warm-ups"""
+    import torch
+    for _ in range(warm):
+        fn()
+    ts = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ts.append(a.elapsed_time(b))
+    return float(np.median(ts))
+
+
+def _probe_local_map(p, m, G, t, cur):
+    """the two legs of section 7f: fb_covis_local_map_dev with reuse_index 0 / 1 (also right after a window call), and the tree calls"""
+    import torch
+    K = p["K"]
+    every = list(range(K))
+    nc, fr = G.update_connections(m, every)
+    G.first_connection(every, nc, fr, id0_slot=0)
+    frame = local_map_frame(p, cur)
+    G.reserve_local_map(m.n_mp, m.n_obs, n_q=30, batch=1, with_window=True)
+    d, a = G.local_map_arrays([len(frame)], frame[None, :], np.zeros(K, np.uint8), K + 84, m.n_mp)
+    G.local_map(m, a)
+    torch.cuda.synchronize()
+    print("local map of a %d-feature frame: %d voters, %d key frames, %d points" % (
+        len(frame), int(d["d_n_voters"].cpu()[0]), int(d["d_n_local_kf"].cpu()[0]), int(d["d_n_local_mp"].cpu()[0])))
+    print("device local_map, reuse_index = 0:        %.3f ms" % _median_ms(lambda: G.local_map(m, a, reuse_index=False)))
+    print("device local_map, reuse_index = 1:        %.3f ms" % _median_ms(lambda: G.local_map(m, a, reuse_index=True)))
+    G.local_window(m, t, cur, False)
+    print("device local_map, reuse_index = 1 (window's index): %.3f ms" % _median_ms(lambda: G.local_map(m, a, reuse_index=True)))
+    parent, linked, first = (x.clone() for x in G.tree_get())
+    bad = torch.zeros(K, dtype=torch.uint8, device=G.device)
+    n, s = G.children(cur)
+    torch.cuda.synchronize()
+    print("tree: key frame %d has %d children" % (cur, int(n.cpu()[0])))
+    batch = list(range(cur - 15, cur + 15))
+    nc, fr = G.update_connections(m, batch)
+
+    def first_again():
+        G.tree_set(first=torch.ones(K, dtype=torch.uint8, device=G.device))
+        G.first_connection(batch, nc, fr, id0_slot=0)
+
+    def erase_again():
+        G.tree_set(parent, linked, first)
+        G.tree_erase_keyframe(cur, bad)
+    print("device children:                          %.3f ms" % _median_ms(lambda: G.children(cur)))
+    print("device tree_set + first_connection(30):   %.3f ms" % _median_ms(first_again))
+    print("device tree_set + tree_erase_keyframe:    %.3f ms" % _median_ms(erase_again))
+    print("device tree_set alone:                    %.3f ms" % _median_ms(lambda: G.tree_set(parent, linked, first)))
+    G.tree_set(parent, linked, first)
+
+
+def _probe_host_local_map(p, cur, tests, d):
+    """Tracking::UpdateLocalMap and the tree part of SetBadFlag as std::map / std::set walks (tests/cpp/local_map_map_ref.cpp)"""
+    import os
+    import subprocess
+    src = os.path.join(tests, "cpp", "local_map_map_ref.cpp")
+    if not os.path.exists(src):
+        print("host local map figure: not measured")
+        return
+    exe, blob = os.path.join(d, "local_map_map_ref"), os.path.join(d, "local_map.bin")
+    subprocess.check_call(["g++", "-std=c++17", "-O2", src, "-o", exe])
+    frame = local_map_frame(p, cur)
+    with open(blob, "wb") as f:
+        f.write(np.array([p["K"], p["S"], len(p["mp_bad"]), len(p["obs_kf"])], np.int32).tobytes())
+        for k, dt in (("kf_n", np.int32), ("kf_mp", np.int32), ("kf_octave", np.uint8), ("mp_bad", np.uint8), ("obs_mp", np.int32),
+                      ("obs_kf", np.int32), ("obs_idx", np.int32), ("kf_order", np.uint64)):
+            f.write(np.ascontiguousarray(p[k], dt).tobytes())
+        f.write(np.array([len(frame)], np.int32).tobytes())
+        f.write(frame.tobytes())
+    local, bad, n_kf, n_mp, n_ch = subprocess.check_output([exe, blob, str(cur)]).decode().split()
+    print("C++ std::map, one core: UpdateLocalMap of a %d-feature frame %s ms (mean of 50; %s key frames, %s points), "
+          "SetBadFlag tree part %s ms (%s children)" % (len(frame), local, n_kf, n_mp, bad, n_ch))
 
 
 def _probe_host(p, cur):
@@ -381,6 +467,7 @@ def _probe_host(p, cur):
     R.keyframe_culling(g, m, cur)
     cull = (time.perf_counter() - t) * 1e3
     _probe_host_window(p, cur, g.get_vector_covisible_keyframes(cur), tests, d)
+    _probe_host_local_map(p, cur, tests, d)
     print("Python model:           update_connections(1) %.1f ms, (30) %.1f ms, keyframe_culling %.1f ms (culling copies the observations)" % (one, thirty, cull))
 
 
@@ -421,6 +508,13 @@ if __name__ == "__main__":
     import sys
     if "--probe" in sys.argv:
         _probe()
+    elif "--probe-host-local-map" in sys.argv:   # the host leg of section 7f alone: needs no device
+        import os
+        import tempfile
+        q = make_local_mapping_problem()
+        print("map: %d key frames x %d features, %d points, %d edges" % (q["K"], q["S"], len(q["mp_bad"]), len(q["obs_kf"])))
+        with tempfile.TemporaryDirectory() as tmp:
+            _probe_host_local_map(q, q["K"] // 2, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"), tmp)
     else:
         q = make_covis_problem()
         print("covis problem: %d points, %d edges (%d erased)" % (len(q["mp_bad"]), len(q["obs_kf"]), int((q["obs_kf"] < 0).sum())))

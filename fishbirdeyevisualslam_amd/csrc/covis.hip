@@ -7,6 +7,7 @@
 //   KeyFrame::SetBadFlag (graph part) / EraseConnection            :797-798, :807-808, :885-899
 //   LocalMapping::KeyFrameCulling                                  src/LocalMapping.cc:656-729
 //   MapPoint::EraseObservation (its effect on later key frames)    src/MapPoint.cc:111-137
+//   the spanning tree and Tracking::UpdateLocalMap                  covis_tree.inc
 //
 // State: one dense row of uint16 per key frame, W[a][b] = weight (bits 0..14, 0 = no entry) | member of the ordered vector
 // (bit 15).  mvpOrderedConnectedKeyFrames is always "descending by (weight, kf_order)" over the members, so it is derived
@@ -36,6 +37,9 @@ struct Gr {             // device arrays of one handle
   int32_t *rank;        // [K] position of the slot in ascending (kf_order, slot)
   int32_t *inv;         // [K] the slot at that position
   int32_t *err;         // [1] entries skipped as out of range
+  int32_t *parent;      // [K] mpParent, -1 = NULL                                  (the spanning tree: covis_tree.inc)
+  uint8_t *linked;      // [K] the slot is in mspChildrens of parent[slot]
+  uint8_t *first;       // [K] mbFirstConnection
 };
 
 template <typename T> __device__ __forceinline__ T ld(const T *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -138,6 +142,11 @@ __global__ __launch_bounds__(256) void k_cv_rank(Gr G, const uint64_t *order) {
 __global__ __launch_bounds__(256) void k_cv_identity(Gr G) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < G.K) { G.rank[i] = i; G.inv[i] = i; }
+}
+
+__global__ __launch_bounds__(256) void k_cv_tree_reset(Gr G) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < G.K) { G.parent[i] = -1; G.linked[i] = 0; G.first[i] = 1; }
 }
 
 // ---- UpdateConnections -------------------------------------------------------------------------------------------------
@@ -400,15 +409,20 @@ struct fb_covis {
   size_t scrBytes = 0;
   bool winValid = false;   // the scratch holds the lists of a fb_covis_local_window_dev (fb_covis_local_window_header reads them)
   int winCapKf = 0;
+  // where the last index() left the point -> edge index, and of which map: fb_local_map_args.reuse_index reads it again
+  struct IndexAt { bool valid = false; size_t head = 0, end = 0; fb_covis_map map{}; } at;
   int ensure() {
     FB_TRY(fb::check_device());
     if (block) return FB_OK;
-    const size_t k = K, oW = 0, oRank = up256(k * k * 2), oInv = oRank + up256(k * 4), oErr = oInv + up256(k * 4), total = oErr + 256;
+    const size_t k = K, oW = 0, oRank = up256(k * k * 2), oInv = oRank + up256(k * 4), oErr = oInv + up256(k * 4), oPar = oErr + 256,
+                 oLink = oPar + up256(k * 4), oFirst = oLink + up256(k), total = oFirst + up256(k);
     FB_HIP(hipMalloc(&block, total));
     uint8_t *b = static_cast<uint8_t *>(block);
     G.K = K; G.W = (uint16_t *)(b + oW); G.rank = (int32_t *)(b + oRank); G.inv = (int32_t *)(b + oInv); G.err = (int32_t *)(b + oErr);
+    G.parent = (int32_t *)(b + oPar); G.linked = b + oLink; G.first = b + oFirst;
     FB_HIP(hipMemset(block, 0, total));
     k_cv_identity<<<(K + 255) / 256, 256>>>(G);
+    k_cv_tree_reset<<<(K + 255) / 256, 256>>>(G);
     FB_HIP(hipGetLastError());
     FB_HIP(hipDeviceSynchronize());   // creation is rare; orders the default stream's work before every other stream
     return FB_OK;
@@ -419,7 +433,7 @@ struct fb_covis {
   }
   int need(size_t bytes) {
     if (bytes <= scrBytes) return FB_OK;
-    if (scr) { FB_HIP(hipDeviceSynchronize()); FB_HIP(hipFree(scr)); scr = nullptr; scrBytes = 0; winValid = false; }
+    if (scr) { FB_HIP(hipDeviceSynchronize()); FB_HIP(hipFree(scr)); scr = nullptr; scrBytes = 0; winValid = false; at.valid = false; }
     FB_HIP(hipMalloc(&scr, bytes));
     scrBytes = bytes;
     return FB_OK;
@@ -427,14 +441,23 @@ struct fb_covis {
   // ranks of M.kf_order, then the edge list grouped by point; nothing is kept from an earlier call.  The index lies `head`
   // bytes into the scratch (the window calls keep their own arrays, and a second index, in front of it).
   int index(const fb_covis_map &M, size_t n_q, bool culling, Index *ix, hipStream_t s, size_t head = 0, bool ranks = true) {
-    const size_t n_mp = M.n_mp, n_obs = M.n_obs, nb = (n_mp + 1 + CV_SCAN_TILE - 1) / CV_SCAN_TILE;
+    const size_t n_mp = M.n_mp, n_obs = M.n_obs;
     FB_TRY(need(head + scratch_bytes(n_mp, n_obs, n_q, K)));
+    at.valid = true; at.head = head; at.end = head + scratch_bytes(n_mp, n_obs, n_q, K); at.map = M;
     uint8_t *b = static_cast<uint8_t *>(scr) + head;
+    index_layout(b, n_mp, n_obs, n_q, ix);
+    return index_build(M, culling, ix, s, ranks);
+  }
+  void index_layout(uint8_t *b, size_t n_mp, size_t n_obs, size_t n_q, Index *ix) const {
+    const size_t nb = (n_mp + 1 + CV_SCAN_TILE - 1) / CV_SCAN_TILE;
     size_t off = 0;
     auto take = [&](size_t bytes) { uint8_t *p = b + off; off += up256(bytes); return p; };
     ix->start = (int32_t *)take((n_mp + 1) * 4); ix->fill = (int32_t *)take(n_mp * 4); ix->nobs = (int32_t *)take(n_mp * 4);
     ix->csr = (int32_t *)take(n_obs * 4); ix->dead = (int32_t *)take(n_obs * 4); ix->bsum = (int32_t *)take(nb * 4);
     ix->counter = (uint16_t *)take(n_q * K * 2);
+  }
+  int index_build(const fb_covis_map &M, bool culling, Index *ix, hipStream_t s, bool ranks) {
+    const size_t n_mp = M.n_mp, n_obs = M.n_obs, nb = (n_mp + 1 + CV_SCAN_TILE - 1) / CV_SCAN_TILE;
     if (ranks) k_cv_rank<<<(K + 255) / 256, 256, 0, s>>>(G, M.kf_order);
     // start and fill are adjacent: one memset
     FB_HIP(hipMemsetAsync(ix->start, 0, (size_t)((uint8_t *)ix->nobs - (uint8_t *)ix->start), s));
@@ -527,6 +550,8 @@ int fb_covis_clear(fb_covis *g, void *stream) {
   hipStream_t s = fb::as_stream(stream);
   FB_HIP(hipMemsetAsync(g->G.W, 0, (size_t)g->K * g->K * 2, s));
   FB_HIP(hipMemsetAsync(g->G.err, 0, 4, s));
+  k_cv_tree_reset<<<(g->K + 255) / 256, 256, 0, s>>>(g->G);
+  FB_HIP(hipGetLastError());
   return FB_OK;
 }
 
@@ -586,6 +611,7 @@ int fb_covis_update_connections(fb_covis *g, const fb_covis_map *H, int32_t n_q,
   st.out(n_counter, (size_t)n_q * 4, false); st.out(front, (size_t)n_q * 4, false);
   FB_TRY(st.commit(nullptr));
   FB_TRY(fb_covis_update_connections_dev(g, &M, n_q, slots, n_counter, front, nullptr));
+  g->at.valid = false;   // the index is of staged arrays that go back to the pool: nothing to reuse
   return st.fetch(nullptr);
 }
 
@@ -724,9 +750,11 @@ int fb_covis_keyframe_culling(fb_covis *g, const fb_covis_map *H, int32_t cur_sl
   FB_TRY(st.commit(nullptr));
   FB_TRY(fb_covis_keyframe_culling_dev(g, &M, cur_slot, id0_slot, not_erase, n, slots, n_redundant, n_mps, culled, mp_bad_after,
                                        nullptr));
+  g->at.valid = false;
   return st.fetch(nullptr);
 }
 
 }  // extern "C"
 
 #include "covis_window.inc"
+#include "covis_tree.inc"

@@ -137,7 +137,7 @@ __global__ __launch_bounds__(WIN_NT) void k_win_place(fb_covis_map M, WinS W, in
       W.side[sd].plist[pos] = mp;
       if (pos < O.cap_pt) {
         O.pt_index[pos] = mp;
-        for (int c = 0; c < 3; c++) O.pt_xw[(size_t)pos * 3 + c] = xw[(size_t)mp * 3 + c];
+        if (O.pt_xw) for (int c = 0; c < 3; c++) O.pt_xw[(size_t)pos * 3 + c] = xw[(size_t)mp * 3 + c];   // (the local map lists indices only)
       }
     }
     carry += total;
@@ -398,7 +398,9 @@ int fb_covis_local_window_dev(fb_covis *g, const fb_covis_map *M, const fb_covis
   const fb_covis_map maps[2] = {*M, bird ? win_bird_map(*M, *T) : *M};
   Index ix[2];
   FB_TRY(g->index(maps[0], 0, false, &ix[0], s, head, true));
+  const fb_covis::IndexAt front_at = g->at;
   if (bird) FB_TRY(g->index(maps[1], 0, false, &ix[1], s, head + idx0, false));
+  g->at = front_at;   // the front side's index is the one a later reuse_index reads
   k_win_local<<<1, CV_NT, 0, s>>>(g->G, cur_slot, T->kf_bad, W);
   const int n_sides = bird ? 2 : 1;
   for (int sd = 0; sd < n_sides; sd++) {
@@ -485,6 +487,7 @@ int fb_covis_local_window(fb_covis *g, const fb_covis_map *HM, const fb_covis_kf
   FB_TRY(st.commit(nullptr));
   T.kf_Tcw = const_cast<float *>(kf_Tcw); T.mp_xw = const_cast<float *>(mp_xw); T.mpb_xw = const_cast<float *>(mpb_xw);
   FB_TRY(fb_covis_local_window_dev(g, &M, &T, cur_slot, with_bird, &O, nullptr));
+  g->at.valid = false;   // the index is of staged arrays
   FB_TRY(st.fetch(nullptr));
   if (HO->header->overflow) { fb::set_error("fb_covis_local_window: a list is longer than its capacity"); return FB_ERR_CAPACITY; }
   return FB_OK;

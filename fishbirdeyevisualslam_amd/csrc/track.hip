@@ -1055,6 +1055,33 @@ int fb_frame_track_dev(fb_frame *cur, fb_frame *last, const fb_track_args *T, vo
   return local_map_impl(cur, last, T, fb::as_stream(stream), true);   // if (bOK) bOK = TrackLocalMap(), per sequence
 }
 
+// Tracking::UpdateLocalMap (Tracking.cc:1394) on the frame's own mvpMapPoints
+static fb_local_map_args frame_local_map_args(const fb_frame *cur, const fb_local_map_args *a) {
+  fb_local_map_args A = *a;
+  A.batch = cur->B; A.kp_stride = cur->cap; A.d_n = cur->n.as<int32_t>(); A.d_map_point = cur->mp.as<int32_t>();
+  A.cap_mp = cur->P.local_mp_cap;
+  return A;
+}
+
+int fb_frame_update_local_map_dev(fb_frame *cur, fb_covis *g, const fb_covis_map *map, const fb_local_map_args *a, void *stream) {
+  FB_TRY(fb::check_device());
+  FB_ARG(cur && g && map && a);
+  const fb_local_map_args A = frame_local_map_args(cur, a);
+  return fb_covis_local_map_dev(g, map, &A, stream);
+}
+
+int fb_frame_track_graph_dev(fb_frame *cur, fb_frame *last, const fb_track_args *T, fb_covis *g, const fb_covis_map *map,
+                             const fb_local_map_args *a, void *stream) {
+  FB_TRY(fb::check_device());
+  FB_ARG(cur && last && cur != last && cur->B == last->B && cur->cap == last->cap && track_args_ok(cur, T) && T->d_delta);
+  FB_ARG(g && map && a && a->d_local_mp && T->d_local_mp == a->d_local_mp && T->d_n_local_mp == a->d_n_local_mp);
+  fb_local_map_args A = frame_local_map_args(cur, a);
+  A.d_gate_row = cur->cnt(FB_CNT_MATCHES_MAP); A.gate_min = 10;       // if (bOK) bOK = TrackLocalMap(), per sequence
+  FB_TRY(motion_model_impl(cur, last, T, fb::as_stream(stream)));
+  FB_TRY(fb_covis_local_map_dev(g, map, &A, stream));
+  return local_map_impl(cur, last, T, fb::as_stream(stream), true);
+}
+
 int fb_frame_compute_bow_dev(fb_frame *f, const fb_vocabulary *voc, void *stream) {
   FB_TRY(fb::check_device());
   FB_ARG(f && voc);

@@ -891,7 +891,7 @@ int fb_covis_error_count(fb_covis *g, int32_t *count, void *stream);
  * its ordered list are the entries >= FB_COVIS_TH, or pKFmax alone (the smallest kf_order among the maxima, :627-643);
  * every member b gets AddConnection(a, w).  An empty counter changes nothing (:604-612).  d_n_counter[q] =
  * KFcounter.size(), d_front[q] = mvpOrderedConnectedKeyFrames.front() afterwards (-1: the vector is empty).  The spanning
- * tree (mpParent, mbFirstConnection) stays with the host; UpdateBirdConnections is not restated.                       */
+ * tree (mpParent, mbFirstConnection) follows with fb_covis_first_connection_dev; UpdateBirdConnections is not restated. */
 int fb_covis_update_connections_dev(fb_covis *g, const fb_covis_map *map, int32_t n_q, const int32_t *d_slots,
                                     int32_t *d_n_counter, int32_t *d_front, void *stream);
 int fb_covis_update_connections(fb_covis *g, const fb_covis_map *map, int32_t n_q, const int32_t *slots, int32_t *n_counter,
@@ -1021,6 +1021,100 @@ int fb_covis_local_window(fb_covis *g, const fb_covis_map *map, const fb_covis_k
 int fb_covis_window_scatter_dev(fb_covis *g, const fb_covis_map *map, const fb_covis_kf_tables *tables, const fb_covis_window *win,
                                 const uint8_t *d_obs_outlier, const uint8_t *d_bobs_outlier, int32_t *d_n_erase,
                                 int32_t *d_erase, int32_t *d_berase, void *stream);
+
+/* ---- the spanning tree (mpParent, mspChildrens, mbFirstConnection; KeyFrame.cc:665-690, :704-741, :810-868) ------------
+ * State per slot: parent (int32, -1 = mpParent == NULL), linked (uint8: the slot is in mspChildrens of parent[slot]) and
+ * first (uint8 = mbFirstConnection; 1 after create / clear).  GetChilds() of a non-bad key frame a is
+ * {c : parent[c] == a && linked[c]} in ascending kf_order (a std::set<KeyFrame*>).  linked is there because SetBadFlag
+ * leaves mpParent of the removed key frame set but erases it from its parent's set (:868).  ChangeParent adds to the new
+ * set without erasing from the old one (:724-729); the old parent is then the key frame that is going bad, and the
+ * children set of a key frame that has gone bad is not kept: nothing reachable reads it.  fb_covis_clear resets the tree.
+ * Every call enqueues on `stream`; the host variants wait for the default stream.                                       */
+/* the three arrays, whole ([max_keyframes] each; a NULL array is left out).  A parent outside [-1, max_keyframes) is
+ * stored as -1 and counted.                                                                                             */
+int fb_covis_tree_set_dev(fb_covis *g, const int32_t *d_parent, const uint8_t *d_linked, const uint8_t *d_first, void *stream);
+int fb_covis_tree_get_dev(fb_covis *g, int32_t *d_parent, uint8_t *d_linked, uint8_t *d_first, void *stream);
+int fb_covis_tree_get(fb_covis *g, int32_t *parent, uint8_t *linked, uint8_t *first); /* host pointers; synchronises     */
+/* slot->ChangeParent(parent) (:724-729).  Also how the host mirrors the parents UpdateBirdConnections sets (:470-556).  */
+int fb_covis_change_parent_dev(fb_covis *g, int32_t slot, int32_t parent, void *stream);
+/* parent->EraseChild(slot) (:718-722): linked is cleared only if parent[slot] == parent                                 */
+int fb_covis_erase_child_dev(fb_covis *g, int32_t parent, int32_t slot, void *stream);
+/* GetChilds() in set order (d_slots holds max_keyframes entries; entries past *d_n are left as they are) / GetParent()  */
+int fb_covis_children_dev(fb_covis *g, int32_t slot, int32_t *d_n, int32_t *d_slots, void *stream);
+int fb_covis_children(fb_covis *g, int32_t slot, int32_t *n, int32_t *slots);
+int fb_covis_parent_dev(fb_covis *g, int32_t slot, int32_t *d_parent, void *stream);
+/* The mbFirstConnection block of UpdateConnections (:665-690), on the outputs of fb_covis_update_connections_dev for the
+ * same batch, in list order.  Query q acts only when first[slot] != 0, slot != id0_slot (mnId == 0; -1 = none) and
+ * d_n_counter[q] != 0 (an empty counter returned at :604-612, mbFirstConnection stays set; d_front is then the front of
+ * the unchanged vector and says nothing).  Then parent = d_front[q], or, when now_state4 != 0 and
+ * frame_id[front] > frame_id[slot], this fork's override (:673-684): the key frame of the map (d_kf_in_map[slot] != 0)
+ * with the largest mnFrameId strictly between 0 and this key frame's (frame id 0 never wins: the comparison is > 0; the
+ * smaller kf_order among equal ids); if nothing qualifies the front stays.  linked = 1, first = 0.  d_kf_frame_id
+ * [max_keyframes] int32 and d_kf_in_map [max_keyframes] uint8 may be NULL when now_state4 == 0.                         */
+int fb_covis_first_connection_dev(fb_covis *g, int32_t n_q, const int32_t *d_slots, const int32_t *d_n_counter,
+                                  const int32_t *d_front, int32_t id0_slot, int32_t now_state4, const int32_t *d_kf_frame_id,
+                                  const uint8_t *d_kf_in_map, void *stream);
+/* The tree part of KeyFrame::SetBadFlag (:810-868).  Independent of fb_covis_erase_keyframe_dev (the key frame itself is
+ * never a parent candidate): the two may be called in either order.  Candidates = {parent[slot]}.  Repeatedly, over the
+ * linked children in ascending kf_order (bad ones, d_kf_bad[c] != 0, skipped) and each child's ordered list in list
+ * order, the pair (child, member that is a candidate) with the largest GetWeight under strict > (the first pair in that
+ * order wins a tie) is re-parented, the child joins the candidates and leaves the set; when no pair is left, the
+ * remaining children, bad ones included, get ChangeParent(parent[slot]) (:862-866).  Then linked[slot] = 0; parent[slot]
+ * is kept.  Precondition parent[slot] >= 0 (the reference dereferences it): otherwise nothing is done and the error
+ * counter goes up.  mnId == 0 / mbNotErase stay the caller's decision, as for fb_covis_erase_keyframe_dev.             */
+int fb_covis_tree_erase_keyframe_dev(fb_covis *g, int32_t slot, const uint8_t *d_kf_bad, void *stream);
+
+/* ---- Tracking::UpdateLocalMap = UpdateLocalKeyFrames + UpdateLocalPoints (Tracking.cc:2085-2229) -----------------------
+ * Every sequence of the batch tracks against the one map and graph of the handle.                                      */
+#define FB_LOCAL_MAP_MAX_EXPAND 80 /* "if(mvpLocalKeyFrames.size()>80) break" (:2175)                                  */
+typedef struct fb_local_map_args {
+  int32_t batch, kp_stride;
+  const int32_t *d_n;           /* [batch] mCurrentFrame.N                                                             */
+  int32_t *d_map_point;         /* [batch][kp_stride] in/out: mvpMapPoints as indices into the map's points, -1 = NULL;
+                                   an entry of a bad point becomes -1 (:2138)                                          */
+  const uint8_t *d_kf_bad;      /* [max_keyframes] KeyFrame::isBad()                                                   */
+  int32_t cap_kf;               /* a list never exceeds max(max_keyframes, 83) entries; more capacity is never used    */
+  int32_t *d_local_kf;          /* [batch][cap_kf] in/out: mvpLocalKeyFrames                                           */
+  int32_t *d_n_local_kf;        /* [batch] in/out                                                                      */
+  int32_t cap_mp;
+  int32_t *d_local_mp;          /* [batch][cap_mp] mvpLocalMapPoints                                                   */
+  int32_t *d_n_local_mp;        /* [batch]                                                                             */
+  int32_t *d_ref_kf;            /* [batch] in/out: mpReferenceKF, written only when there is a pKFmax (:2224-2228)     */
+  int32_t *d_n_voters;          /* [batch] keyframeCounter.size(), bad key frames included                             */
+  int32_t *d_overflow;          /* [batch] != 0: a list was longer than its capacity; what fitted is its prefix        */
+  const int32_t *d_gate_row;    /* [batch] or NULL: a sequence with d_gate_row[b] < gate_min is left entirely alone    */
+  int32_t gate_min;
+  int32_t reuse_index;          /* 0: the point -> edge index is rebuilt from the edge list, like every other map call;
+                                   1: the caller states that the last map-taking call on this handle used the same
+                                   fb_covis_map arrays, unchanged, and its index (and kf_order ranks) are used again.
+                                   A different map in that call is FB_ERR_ARG (pointers and sizes are compared; the
+                                   contents are the caller's statement).  A host-pointer variant leaves no index: after
+                                   one, or after the scratch had to grow, the index is rebuilt as with 0               */
+} fb_local_map_args;
+/* Votes (:2125-2141): every feature i < n with a point; a bad point (map.mp_bad) sets d_map_point[i] = -1 and does not
+ * vote; otherwise every live edge of the point votes for its key frame (a point held at two features votes twice; edges
+ * of bad key frames vote and are filtered later).  Empty counter (:2143-2144): d_local_kf, d_n_local_kf and d_ref_kf stay
+ * as they came in, and UpdateLocalPoints runs on that list (read up to min(d_n_local_kf, cap_kf) entries).  Voters
+ * (:2153-2168) in ascending kf_order, bad ones skipped; pKFmax is the first voter with a strictly larger count.
+ * Expansion (:2172-2222) over the voters only, in order: size > 80 ends it; each step takes (a) the first of
+ * GetBestCovisibilityKeyFrames(10) (bad ones occupy places) that is non-bad and unmarked, (b) the first child in set
+ * order that is non-bad and unmarked, (c) the parent if it exists and is unmarked (no isBad test), which ends the whole
+ * loop (the break at :2218 leaves the outer for).  Local points (:2095-2118): the local key frames in list order, the
+ * features ascending, the first occurrence of every non-NULL, non-bad point; the key frame's own isBad is not tested.
+ * A kf list the call builds is cut at cap_kf (the points come from what fitted), a point list at cap_mp; either sets
+ * d_overflow.  A list that came in and is kept by an empty counter is NOT judged: if d_n_local_kf > cap_kf it is read up to
+ * cap_kf, d_n_local_kf stays, and d_overflow reports the point list only.
+ * Out-of-range entries (d_map_point >= n_mp, a carried-over key frame outside the slots) are skipped and counted.
+ * Precondition: the frame is not the one with mnId == 0 (the initial marks equal it; Track never gets there).
+ * Scratch: see fb_covis_reserve_local_map.                                                                             */
+int fb_covis_local_map_dev(fb_covis *g, const fb_covis_map *map, const fb_local_map_args *a, void *stream);
+int fb_covis_local_map(fb_covis *g, const fb_covis_map *map, const fb_local_map_args *a); /* host pointers throughout     */
+/* Scratch for fb_covis_local_map_dev ahead of time.  The call keeps its own arrays BEHIND the index of the last
+ * map-taking call ([that call's head][index][local map]), so a reused index is not overwritten, neither by this call nor
+ * by the window's header arrays; n_q is the largest n_q of the fb_covis_update_connections_dev calls whose index is to be
+ * reused, with_window != 0 sizes the head for a fb_covis_local_window_dev on the same map (front side).  If the scratch
+ * has to grow, the index is lost and reuse_index = 1 rebuilds it once.                                                  */
+int fb_covis_reserve_local_map(fb_covis *g, int32_t n_mp, int32_t n_obs, int32_t n_q, int32_t batch, int32_t with_window);
 
 /* ======================================================================== */
 /* Frame geometry either side of the matchers (src/Frame.cc)                 */
@@ -1303,6 +1397,17 @@ int fb_frame_track_dev(fb_frame *cur, fb_frame *last, const fb_track_args *args,
  *   fb_frame_track_local_map_dev     Tracking::TrackLocalMap (:1387-1441, ref = tmpRefFrame) + the end of Track (:690-725)  */
 int fb_frame_track_motion_model_dev(fb_frame *cur, fb_frame *last, const fb_track_args *args, void *stream);
 int fb_frame_track_local_map_dev(fb_frame *cur, fb_frame *ref, const fb_track_args *args, void *stream);
+/* Tracking::UpdateLocalMap (Tracking.cc:1394, :2085-2229) for the frames of the handle: fb_covis_local_map_dev with batch,
+ * kp_stride, d_n and d_map_point taken from the frame and cap_mp = local_mp_cap (those fields of `a` are ignored).  Its
+ * d_local_mp / d_n_local_mp are exactly what fb_track_args.d_local_mp / d_n_local_mp read.  The frame's map point indices
+ * index the one map of `map`.                                                                                           */
+int fb_frame_update_local_map_dev(fb_frame *cur, fb_covis *g, const fb_covis_map *map, const fb_local_map_args *a, void *stream);
+/* fb_frame_track_dev with the list derived from the frame between its two halves, no synchronisation:
+ * TrackWithMotionModel -> UpdateLocalMap -> the rest of TrackLocalMap, the last two gated per sequence on
+ * FB_CNT_MATCHES_MAP >= 10 (a's own gate fields are ignored).  args->d_local_mp / d_n_local_mp must be a->d_local_mp /
+ * a->d_n_local_mp (FB_ERR_ARG otherwise).                                                                              */
+int fb_frame_track_graph_dev(fb_frame *cur, fb_frame *last, const fb_track_args *args, fb_covis *g, const fb_covis_map *map,
+                             const fb_local_map_args *a, void *stream);
 
 /* Tracking::TrackUsingBird (Tracking.cc:2014-2061: the frame of a LOST tracker that could not re-initialise, bHaveBird):
  * SetPose(detlaT * src pose) with src = mpReferenceKF's handle (IsbirdWithRefKF == 1) or tmpRefFrame, GetLocalMapForBird,
