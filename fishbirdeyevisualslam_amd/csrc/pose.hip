@@ -16,8 +16,14 @@
 // triangle of the 6x6 J^T W J and the 6-vector J^T W e (28 doubles), reduced with wavefront
 // shuffles and one LDS hop.  The pass at a trial pose doubles as the linearisation of the next
 // iteration when the step is accepted, so an LM iteration costs one pass per trial.  The 6x6
-// LDL^T, the exponential-map update and the lambda schedule run on lane 0.  Everything is fp64
-// like g2o; inputs/outputs are float like the reference's cv::Mat fields.
+// LDL^T and the exponential-map update run on one lane.  Everything is fp64 like g2o;
+// inputs/outputs are float like the reference's cv::Mat fields.
+//
+// The schedule is written once (lm_optimize10 = optimize(10), pose_rounds = the four rounds with
+// the classification between them) and has two users that differ in where the edges live and in
+// the solve policy: k_pose_opt (pose_generic: edges in LDS or HBM, any number of them) and
+// k_pose_opt_regs<NT, NE, EF, EB> (edges in registers; NE = NT - 64 gives the solver a wave of its
+// own), which leaves through pose_generic for a frame with more edges than its slots.
 #include <type_traits>
 #include "fb_common.h"
 #include "fb_primitives.h"
@@ -200,250 +206,63 @@ __device__ __forceinline__ void unpack_system(const double *red, double *H, doub
 // evaluations, which are held to a tolerance; the DECISION is an integer result, so its arithmetic is written out here
 // with contraction off and with g2o's own quotients (project2d: v / v(2)), operation for operation what the oracle
 // evaluates: given the same pose the masks are equal by construction, not by luck of the rounding.
-__device__ __forceinline__ double edge_chi2(const EdgeView &E, int e, bool bird, const fb::SE3 &T, double fx,
-                                            double fy, double cx, double cy) {
+__device__ __forceinline__ void decision_map(const fb::SE3 &T, float x0, float x1, float x2, double (&p)[3]) {
 #pragma clang fp contract(off)
-  const float *X = bird ? E.bxw + e * 3 : E.fxw + e * 3;
-  const double v0 = X[0], v1 = X[1], v2 = X[2];
+  const double v0 = x0, v1 = x1, v2 = x2;
   const double qx = T.r.x, qy = T.r.y, qz = T.r.z, qw = T.r.w;
   // Eigen's quaternion * vector (fb::quat_rotate), then + t (se3quat.h:217-220)
   double u0 = qy * v2 - qz * v1, u1 = qz * v0 - qx * v2, u2 = qx * v1 - qy * v0;
   u0 += u0; u1 += u1; u2 += u2;
-  const double p0 = (v0 + qw * u0 + (qy * u2 - qz * u1)) + T.t[0];
-  const double p1 = (v1 + qw * u1 + (qz * u0 - qx * u2)) + T.t[1];
-  const double p2 = (v2 + qw * u2 + (qx * u1 - qy * u0)) + T.t[2];
-  if (!bird) {
-    const double e0 = (double)E.fobs[e * 2] - ((p0 / p2) * fx + cx);
-    const double e1 = (double)E.fobs[e * 2 + 1] - ((p1 / p2) * fy + cy);
-    const double info = (double)E.finf[e] * E.wf;
-    double s = 0;
-    s += e0 * (info * e0);
-    s += e1 * (info * e1);
-    return s;
-  }
-  const double info = (double)E.binf[e] * E.wb;
-  const double d0 = (double)E.bxc[e * 3] - p0, d1 = (double)E.bxc[e * 3 + 1] - p1, d2 = (double)E.bxc[e * 3 + 2] - p2;
+  p[0] = (v0 + qw * u0 + (qy * u2 - qz * u1)) + T.t[0];
+  p[1] = (v1 + qw * u1 + (qz * u0 - qx * u2)) + T.t[1];
+  p[2] = (v2 + qw * u2 + (qx * u1 - qy * u0)) + T.t[2];
+}
+__device__ __forceinline__ double chi2_front_vals(float x0, float x1, float x2, float o0, float o1, double info, const fb::SE3 &T,
+                                                  double fx, double fy, double cx, double cy) {
+#pragma clang fp contract(off)
+  double p[3];
+  decision_map(T, x0, x1, x2, p);
+  const double e0 = (double)o0 - ((p[0] / p[2]) * fx + cx);
+  const double e1 = (double)o1 - ((p[1] / p[2]) * fy + cy);
+  double s = 0;
+  s += e0 * (info * e0);
+  s += e1 * (info * e1);
+  return s;
+}
+__device__ __forceinline__ double chi2_bird_vals(float x0, float x1, float x2, float c0, float c1, float c2, double info, const fb::SE3 &T) {
+#pragma clang fp contract(off)
+  double p[3];
+  decision_map(T, x0, x1, x2, p);
+  const double d0 = (double)c0 - p[0], d1 = (double)c1 - p[1], d2 = (double)c2 - p[2];
   double s = 0;
   s += d0 * (info * d0);
   s += d1 * (info * d1);
   s += d2 * (info * d2);
   return s;
 }
-
-// The generic schedule for any number of edges per frame: edges staged in LDS as float (staged = 1) or read from HBM / L2
-// in every evaluation (staged = 0), per-edge level bytes in LDS, butterfly sums.  It is the whole kernel for frames beyond
-// the register-resident kernel below, and that kernel's in-kernel way out for a frame with more edges than its slots.
-template <int NT>
-__device__ void pose_generic(const fb_pose_opt_args &A, int staged, uint8_t *smem, PoseLds &S, int *s_cnt) {
-  constexpr int POSE_THREADS = NT, NW = NT / 64;
-  const int bidx = blockIdx.x, tid = threadIdx.x;
-#ifdef FB_POSE_STAMPS
-  const unsigned long long pose_t_start = __builtin_amdgcn_s_memtime();
-#endif
-  const int mode = A.mode;
-  const size_t fo = (size_t)bidx * A.front_stride, bo = (size_t)bidx * A.bird_stride;
-  const int nfs = (mode != FB_POSE_BIRD) ? A.n_front[bidx] : 0;
-  const int nbs = (mode != FB_POSE_FRONT) ? A.n_bird[bidx] : 0;
-  float *Tcw = A.Tcw + (size_t)bidx * 12;
-  // ---- stage the edges
-  EdgeView E;
-  E.nfs = nfs; E.nbs = nbs;
-  uint8_t *flevel, *blevel;
-  {
-    float *lf = reinterpret_cast<float *>(smem);
-    size_t off = 0;
-    if (staged) {
-      float *fxw = lf; off += (size_t)A.front_stride * 3;
-      float *fobs = lf + off; off += (size_t)A.front_stride * 2;
-      float *finf = lf + off; off += (size_t)A.front_stride;
-      float *bxw = lf + off; off += (size_t)A.bird_stride * 3;
-      float *bxc = lf + off; off += (size_t)A.bird_stride * 3;
-      float *binf = lf + off; off += (size_t)A.bird_stride;
-      for (int i = tid; i < nfs * 3; i += POSE_THREADS) fxw[i] = A.front_xw[fo * 3 + i];
-      for (int i = tid; i < nfs * 2; i += POSE_THREADS) fobs[i] = A.front_obs[fo * 2 + i];
-      for (int i = tid; i < nbs * 3; i += POSE_THREADS) { bxw[i] = A.bird_xw[bo * 3 + i]; bxc[i] = A.bird_xc[bo * 3 + i]; }
-      E.fxw = fxw; E.fobs = fobs; E.finf = finf; E.bxw = bxw; E.bxc = bxc; E.binf = binf;
-      for (int i = tid; i < nfs; i += POSE_THREADS) finf[i] = A.front_inv_sigma2[fo + i];
-      for (int i = tid; i < nbs; i += POSE_THREADS) binf[i] = A.bird_inv_sigma2[bo + i];
-    } else {
-      E.fxw = A.front_xw + fo * 3; E.fobs = A.front_obs + fo * 2; E.finf = A.front_inv_sigma2 + fo;
-      E.bxw = A.bird_xw + bo * 3; E.bxc = A.bird_xc + bo * 3; E.binf = A.bird_inv_sigma2 + bo;
-    }
-    flevel = reinterpret_cast<uint8_t *>(lf + off);
-    blevel = flevel + ((A.front_stride + 15) & ~15);
-    E.flevel = flevel; E.blevel = blevel;
+// the same from an EdgeView (staged or global floats)
+__device__ __forceinline__ double edge_chi2(const EdgeView &E, int e, bool bird, const fb::SE3 &T, double fx,
+                                            double fy, double cx, double cy) {
+#pragma clang fp contract(off)
+  if (!bird) {
+    const float *X = E.fxw + e * 3, *O = E.fobs + e * 2;
+    return chi2_front_vals(X[0], X[1], X[2], O[0], O[1], (double)E.finf[e] * E.wf, T, fx, fy, cx, cy);
   }
-  if (tid < 2) s_cnt[tid] = 0;
-  __syncthreads();
-  // edge construction (Optimizer.cc:525-602): count edges, clear mvbOutlier of mapped slots
-  for (int i = tid; i < nfs; i += POSE_THREADS) {
-    const bool v = !A.front_valid || A.front_valid[fo + i];
-    flevel[i] = v ? 0 : 2;
-    if (v) { A.front_outlier[fo + i] = 0; atomicAdd(&s_cnt[0], 1); }
-  }
-  for (int i = tid; i < nbs; i += POSE_THREADS) {
-    const bool v = !A.bird_valid || A.bird_valid[bo + i];
-    blevel[i] = v ? 0 : 2;
-    if (v) atomicAdd(&s_cnt[1], 1);
-  }
-  __syncthreads();
-  const int nf = s_cnt[0], nb = s_cnt[1];
-  if (mode == FB_POSE_BIRD ? nb < 3 : nf < 3) {  // Optimizer.cc:379,607,776
-    if (tid == 0) A.ninliers[bidx] = 0;
-    return;
-  }
-  E.wf = (mode == FB_POSE_FRONT) ? 1.0 : (double)A.wF;
-  E.wb = (double)A.wB;
-  const double fx = A.fx, fy = A.fy, cx = A.cx, cy = A.cy;
-  const double delta = (double)(float)sqrt(5.991);  // const float deltaMono = sqrt(5.991)
+  const float *X = E.bxw + e * 3, *C = E.bxc + e * 3;
+  return chi2_bird_vals(X[0], X[1], X[2], C[0], C[1], C[2], (double)E.binf[e] * E.wb, T);
+}
+// the thresholds of the decision (Optimizer.cc:410,645,672,806)
+__device__ __forceinline__ bool front_is_bad(float chi2, int mode, float wF) {
   const float chi2Mono = (mode == FB_POSE_FRONT) ? 5.991f : 1.5f;
+  if (mode == FB_POSE_FRONT) return chi2 > chi2Mono;
+  return chi2 > chi2Mono * ((double)wF + 1e-9);
+}
+__device__ __forceinline__ bool bird_is_bad(float chi2, float wB) {
   const float chi2Bird = 5.991f;
-  if (tid == 0) {
-    S.T = fb::se3_from_float12(Tcw);
-    S.Teval = S.T;
-  }
-  __syncthreads();
-  const fb::SE3 T0 = S.T;
-
-  int nBad = 0, nBadBird = 0;
-  for (int it = 0; it < 4; it++) {
-    const bool robust = it < 3;  // setRobustKernel(0) after the third round (Optimizer.cc:657,685)
-    if (tid == 0) S.T = T0;      // vSE3->setEstimate(toSE3Quat(pFrame->mTcw))
-    __syncthreads();
-    // active edges = level 0 (initializeOptimization(0))
-    int nact = 0;
-    for (int i = tid; i < nfs; i += POSE_THREADS) nact += flevel[i] == 0;
-    for (int i = tid; i < nbs; i += POSE_THREADS) nact += blevel[i] == 0;
-    nact = __syncthreads_count(nact > 0);
-    if (nact > 0) {
-      // ---- optimize(10): OptimizationAlgorithmLevenberg
-      eval_pass<NT>(E, S.T, robust, delta, fx, fy, cx, cy, &S);
-      if (tid == 0) { unpack_system(S.red, S.H, S.b); S.Teval = S.T; }
-      double currentChi = S.red[0];
-      __syncthreads();
-      double lambda = 0, ni = 2;
-      int nBadLM = 0;
-      for (int iter = 0; iter < 10; iter++) {
-        const double iniChi = currentChi;
-        if (iter == 0) {
-          double m = 0;
-          for (int j = 0; j < 6; j++) m = fmax(fabs(S.H[j * 6 + j]), m);
-          lambda = 1e-5 * m;
-          ni = 2;
-          nBadLM = 0;
-        }
-        double rho = 0;
-        int qmax = 0;
-        do {
-          {
-            POSE_T0()
-            if (tid == 0) {
-              S.ok2 = fb::ldlt6(S.H, lambda, S.b, S.x) ? 1 : 0;
-              POSE_TICK(4)
-              S.Ttrial = fb::se3_mul(fb::se3_exp(S.x), S.T);  // oplus
-              S.Teval = S.Ttrial;
-              POSE_TICK(5)
-            }
-            __syncthreads();
-            POSE_TICK(6)
-          }
-          eval_pass<NT>(E, S.Ttrial, robust, delta, fx, fy, cx, cy, &S);
-          double tempChi = S.red[0];
-          if (!S.ok2) tempChi = 1.7976931348623157e308;
-          rho = currentChi - tempChi;
-          double scale = 0;
-          for (int j = 0; j < 6; j++) scale += S.x[j] * (lambda * S.x[j] + S.b[j]);
-          scale += 1e-3;
-          rho /= scale;
-          const bool accept = rho > 0 && isfinite(tempChi);
-          __syncthreads();  // everyone has read red/x/b
-          if (accept) {
-            double alpha = 1. - pow((2 * rho - 1), 3);
-            alpha = fmin(alpha, 2. / 3.);
-            const double scaleFactor = fmax(1. / 3., alpha);
-            lambda *= scaleFactor;
-            ni = 2;
-            currentChi = tempChi;
-            if (tid == 0) { S.T = S.Ttrial; unpack_system(S.red, S.H, S.b); }
-          } else {
-            lambda *= ni;
-            ni *= 2;
-          }
-          __syncthreads();
-          qmax++;
-        } while (rho < 0 && qmax < 10);
-        if (qmax == 10 || rho == 0) break;  // Terminate
-        if ((iniChi - currentChi) * 1e3 < iniChi) nBadLM++;
-        else nBadLM = 0;
-        if (nBadLM >= 3) break;
-      }
-    }
-    // ---- classify (Optimizer.cc:396-431, 627-686, 791-822)
-    POSE_T0()
-    const fb::SE3 T = S.T, Teval = S.Teval;
-    int bad = 0, badb = 0;
-    for (int i = tid; i < nfs; i += POSE_THREADS) {
-      if (flevel[i] == 2) continue;
-      const bool wasOut = A.front_outlier[fo + i] != 0;
-      const float chi2 = (float)edge_chi2(E, i, false, wasOut ? T : Teval, fx, fy, cx, cy);
-      bool isBad;
-      if (mode == FB_POSE_FRONT) isBad = chi2 > chi2Mono;
-      else isBad = chi2 > chi2Mono * ((double)A.wF + 1e-9);
-      A.front_outlier[fo + i] = isBad ? 1 : 0;
-      flevel[i] = isBad ? 1 : 0;
-      bad += isBad;
-    }
-    for (int i = tid; i < nbs; i += POSE_THREADS) {
-      if (blevel[i] == 2) continue;
-      const bool wasOut = A.bird_outlier[bo + i] != 0;
-      const float chi2 = (float)edge_chi2(E, i, true, wasOut ? T : Teval, fx, fy, cx, cy);
-      const float chi2Bad = (float)(chi2Bird * ((double)A.wB + 1e-9));
-      const bool isBad = chi2 > chi2Bad;
-      A.bird_outlier[bo + i] = isBad ? 1 : 0;
-      blevel[i] = isBad ? 1 : 0;
-      badb += isBad;
-    }
-    {
-      const double sb = wave_sum((double)bad), sbb = wave_sum((double)badb);
-      if ((tid & 63) == 0) { S.part[tid >> 6][0] = sb; S.part[tid >> 6][1] = sbb; }
-      __syncthreads();
-      double tb = 0, tbb = 0;
-      for (int w2 = 0; w2 < NW; w2++) { tb += S.part[w2][0]; tbb += S.part[w2][1]; }
-      nBad = (int)tb; nBadBird = (int)tbb;
-      __syncthreads();
-    }
-    POSE_TICK(7)
-    if (nf + nb < 10) break;  // optimizer.edges().size()<10
-  }
-  if (tid == 0) {
-    fb::se3_to_float12(S.T, Tcw);
-    A.ninliers[bidx] = (mode == FB_POSE_BIRD) ? nb - nBadBird : nf - nBad;
-  }
-#ifdef FB_POSE_STAMPS
-  if (blockIdx.x == 0 && tid == 0) g_pose_stamps[14] += __builtin_amdgcn_s_memtime() - pose_t_start;
-#endif
+  return chi2 > (float)(chi2Bird * ((double)wB + 1e-9));
 }
 
-__global__ __launch_bounds__(256) void k_pose_opt(fb_pose_opt_args A, int staged) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  __shared__ PoseLds S;
-  __shared__ int s_cnt[2];
-  pose_generic<256>(A, staged, smem, S, s_cnt);
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// k_pose_opt_reg -- the same schedule, built for the latency of ONE frame (single-sequence tracking is bounded by this
-// kernel).  Phase stamps of the LDS-staged kernel above (profiles/r02_pose_stamps_before.txt): an LM evaluation took
-// ~29 k cycles = 12.6 k edge arithmetic of one wave per SIMD, 7 k for the 28 cross-lane sums (ds_bpermute butterflies
-// are latency chains), 4 k for the 6x6 solve + exponential map on one lane.  Here
-//  * the edges of a thread live in REGISTERS (edge e -> thread e % NT, slot e / NT, up to 8 front + 4 bird slots), so an
-//    evaluation reads nothing but the pose from LDS and NT = 512 threads (two waves per SIMD) cover each other's fp64
-//    latencies;
-//  * the 28 sums go through an LDS transpose: every thread stores its 28 accumulators (conflict-free rows of NT + CPA
-//    doubles), 28 x CPA threads add 32 values each with 4 independent chains, the CPA partial sums of an accumulator
-//    sit in adjacent lanes and are combined with DPP row shifts (VALU moves, no LDS crossbar);
-//  * the update T <- exp(x) T is formed directly on the quaternion (no rotation matrix, one reciprocal square root per
-//    normalisation).
+// ---- the solver's and the edge pass's routines of the register-resident kernel (k_pose_opt_regs below)
 using fb::dpp_f64;
 
 using fb::rcp_f64_newton;
@@ -591,50 +410,300 @@ __device__ __forceinline__ void bird_edge_acc(const fb::SE3 &T, float x0, float 
   accumulate_bird_edge(p, err, info, robust, delta, acc);
 }
 
-// decision chi2 from register-resident edge data (same unfused arithmetic as edge_chi2 above)
-__device__ __forceinline__ double chi2_front_vals(float x0, float x1, float x2, float o0, float o1, double info, const fb::SE3 &T,
-                                                  double fx, double fy, double cx, double cy) {
-#pragma clang fp contract(off)
-  const double v0 = x0, v1 = x1, v2 = x2;
-  const double qx = T.r.x, qy = T.r.y, qz = T.r.z, qw = T.r.w;
-  double u0 = qy * v2 - qz * v1, u1 = qz * v0 - qx * v2, u2 = qx * v1 - qy * v0;
-  u0 += u0; u1 += u1; u2 += u2;
-  const double p0 = (v0 + qw * u0 + (qy * u2 - qz * u1)) + T.t[0];
-  const double p1 = (v1 + qw * u1 + (qz * u0 - qx * u2)) + T.t[1];
-  const double p2 = (v2 + qw * u2 + (qx * u1 - qy * u0)) + T.t[2];
-  const double e0 = (double)o0 - ((p0 / p2) * fx + cx);
-  const double e1 = (double)o1 - ((p1 / p2) * fy + cy);
-  double s = 0;
-  s += e0 * (info * e0);
-  s += e1 * (info * e1);
-  return s;
-}
-__device__ __forceinline__ double chi2_bird_vals(float x0, float x1, float x2, float c0, float c1, float c2, double info, const fb::SE3 &T) {
-#pragma clang fp contract(off)
-  const double v0 = x0, v1 = x1, v2 = x2;
-  const double qx = T.r.x, qy = T.r.y, qz = T.r.z, qw = T.r.w;
-  double u0 = qy * v2 - qz * v1, u1 = qz * v0 - qx * v2, u2 = qx * v1 - qy * v0;
-  u0 += u0; u1 += u1; u2 += u2;
-  const double p0 = (v0 + qw * u0 + (qy * u2 - qz * u1)) + T.t[0];
-  const double p1 = (v1 + qw * u1 + (qz * u0 - qx * u2)) + T.t[1];
-  const double p2 = (v2 + qw * u2 + (qx * u1 - qy * u0)) + T.t[2];
-  const double d0 = (double)c0 - p0, d1 = (double)c1 - p1, d2 = (double)c2 - p2;
-  double s = 0;
-  s += d0 * (info * d0);
-  s += d1 * (info * d1);
-  s += d2 * (info * d2);
-  return s;
+// The solve step of an LM trial: x from (H + lambda I) x = b, then oplus.  Precise for the generic schedule, the
+// reciprocal-based routines above for the register-resident kernel.
+struct SolvePrecise {
+  static __device__ __forceinline__ bool solve(const double *H, double lambda, const double *b, double *x) { return fb::ldlt6(H, lambda, b, x); }
+  static __device__ __forceinline__ fb::SE3 oplus(const double *x, const fb::SE3 &T) { return fb::se3_mul(fb::se3_exp(x), T); }
+};
+struct SolveFast {
+  static __device__ __forceinline__ bool solve(const double *H, double lambda, const double *b, double *x) { return ldlt6_fast(H, lambda, b, x); }
+  static __device__ __forceinline__ fb::SE3 oplus(const double *x, const fb::SE3 &T) { return se3_mul_fast(se3_exp_direct(x), T); }
+};
+
+// optimize(10) of OptimizationAlgorithmLevenberg from the pose in S.T.  eval(T, robust) leaves the 28 sums of the active
+// edges at pose T in S.red and ends in a barrier; `solver` is true in the one thread that solves and moves S.T.  Every
+// thread of the workgroup calls this and keeps the same lambda / rho / chi2 from the shared sums, so all of them reach
+// every barrier.
+template <class Solve, class Eval>
+__device__ __forceinline__ void lm_optimize10(PoseLds &S, bool solver, bool robust, Eval &eval) {
+  eval(S.T, robust);
+  if (solver) { unpack_system(S.red, S.H, S.b); S.Teval = S.T; }
+  double currentChi = S.red[0];
+  __syncthreads();
+  double lambda = 0, ni = 2;
+  int nBadLM = 0;
+  for (int iter = 0; iter < 10; iter++) {
+    const double iniChi = currentChi;
+    if (iter == 0) {
+      double m = 0;
+      for (int j = 0; j < 6; j++) m = fmax(fabs(S.H[j * 6 + j]), m);
+      lambda = 1e-5 * m;
+      ni = 2;
+      nBadLM = 0;
+    }
+    double rho = 0;
+    int qmax = 0;
+    do {
+      {
+        POSE_T0()
+        if (solver) {
+          S.ok2 = Solve::solve(S.H, lambda, S.b, S.x) ? 1 : 0;
+          POSE_TICK(4)
+          S.Ttrial = Solve::oplus(S.x, S.T);
+          S.Teval = S.Ttrial;
+          POSE_TICK(5)
+        }
+        __syncthreads();
+        POSE_TICK(6)
+      }
+      eval(S.Ttrial, robust);
+      double tempChi = S.red[0];
+      if (!S.ok2) tempChi = 1.7976931348623157e308;
+      rho = currentChi - tempChi;
+      double scale = 0;
+      for (int j = 0; j < 6; j++) scale += S.x[j] * (lambda * S.x[j] + S.b[j]);
+      scale += 1e-3;
+      rho /= scale;
+      const bool accept = rho > 0 && isfinite(tempChi);
+      __syncthreads();  // everyone has read red/x/b
+      if (accept) {
+        double alpha = 1. - pow((2 * rho - 1), 3);
+        alpha = fmin(alpha, 2. / 3.);
+        const double scaleFactor = fmax(1. / 3., alpha);
+        lambda *= scaleFactor;
+        ni = 2;
+        currentChi = tempChi;
+        if (solver) { S.T = S.Ttrial; unpack_system(S.red, S.H, S.b); }
+      } else {
+        lambda *= ni;
+        ni *= 2;
+      }
+      __syncthreads();
+      qmax++;
+    } while (rho < 0 && qmax < 10);
+    if (qmax == 10 || rho == 0) break;  // Terminate
+    if ((iniChi - currentChi) * 1e3 < iniChi) nBadLM++;
+    else nBadLM = 0;
+    if (nBadLM >= 3) break;
+  }
 }
 
-// EF / EB = front / bird edge slots per thread.  <512, 5, 3> (up to 2560 + 1536 edges: the 2000-feature extractor, capacity
-// 2064) keeps acc[28] + the edges + the per-edge temporaries inside the 256 registers two waves per SIMD leave a thread;
-// <512, 8, 4> (up to 4096 + 2048 edges, the 4000-feature initialisation extractor) spills a little.
-template <int NT, int EF, int EB>
-__global__ __launch_bounds__(NT) void k_pose_opt_reg(fb_pose_opt_args A) {
-  constexpr int CPA = NT / 32;   // threads that share one accumulator in the column sums (each adds 32 values)
-  constexpr int RS = NT + CPA;   // row stride in doubles: 2 * RS mod 64 = 2 * CPA, so the CPA-wide windows of the accumulators
-                                 // handled by one ds_read_b64 lane group fall into disjoint banks; the row writes are contiguous
-  constexpr int NWR = NT / 64;
+// workgroup totals of the bad edges a round found: the first NW waves hold edges (`counts` is false in the others)
+template <int NW>
+__device__ __forceinline__ void sum_bad(PoseLds &S, bool counts, int bad, int badb, int &nBad, int &nBadBird) {
+  if (counts) {
+    // per-wave counts through the ballots of each slot would cost 12 ballots; two wave sums + one LDS hop instead
+    const double sb = wave_sum((double)bad), sbb = wave_sum((double)badb);
+    if ((threadIdx.x & 63) == 0) { S.part[0][threadIdx.x >> 6] = sb; S.part[1][threadIdx.x >> 6] = sbb; }
+  }
+  __syncthreads();
+  double tb = 0, tbb = 0;
+  for (int w = 0; w < NW; w++) { tb += S.part[0][w]; tbb += S.part[1][w]; }
+  nBad = (int)tb; nBadBird = (int)tbb;
+  __syncthreads();
+}
+
+// The four rounds of Optimizer.cc:385-465 / 614-690 / 782-825 around optimize(10), from the pose in S.T0 to the result in
+// Tcw / ninliers.  The edge storage stays with the caller: active() = this thread has a level-0 edge, eval as in
+// lm_optimize10, classify(nBad, nBadBird) sets every edge's level and outlier flag from its chi2 and leaves the
+// workgroup's counts (it ends in sum_bad).
+template <class Solve, class Active, class Eval, class Classify>
+__device__ __forceinline__ void pose_rounds(const fb_pose_opt_args &A, PoseLds &S, bool solver, int nf, int nb, Active &active,
+                                            Eval &eval, Classify &classify) {
+  int nBad = 0, nBadBird = 0;
+  for (int it = 0; it < 4; it++) {
+    const bool robust = it < 3;   // setRobustKernel(0) after the third round (Optimizer.cc:657,685)
+    if (solver) S.T = S.T0;       // vSE3->setEstimate(toSE3Quat(pFrame->mTcw))
+    // active edges = level 0 (initializeOptimization(0)); the barrier also publishes S.T
+    if (__syncthreads_count(active()) > 0) lm_optimize10<Solve>(S, solver, robust, eval);
+    classify(nBad, nBadBird);     // Optimizer.cc:396-431, 627-686, 791-822
+    if (nf + nb < 10) break;      // optimizer.edges().size()<10
+  }
+  if (solver) {
+    fb::se3_to_float12(S.T, A.Tcw + (size_t)blockIdx.x * 12);
+    A.ninliers[blockIdx.x] = (A.mode == FB_POSE_BIRD) ? nb - nBadBird : nf - nBad;
+  }
+}
+
+// The generic schedule for any number of edges per frame: edges staged in LDS as float (staged = 1) or read from HBM / L2
+// in every evaluation (staged = 0), per-edge level bytes in LDS, butterfly sums.  It is the whole kernel for frames beyond
+// the register-resident kernel below, and that kernel's in-kernel way out for a frame with more edges than its slots.
+template <int NT>
+__device__ void pose_generic(const fb_pose_opt_args &A, int staged, uint8_t *smem, PoseLds &S, int *s_cnt) {
+  constexpr int POSE_THREADS = NT;
+  const int bidx = blockIdx.x, tid = threadIdx.x;
+#ifdef FB_POSE_STAMPS
+  const unsigned long long pose_t_start = __builtin_amdgcn_s_memtime();
+#endif
+  const int mode = A.mode;
+  const size_t fo = (size_t)bidx * A.front_stride, bo = (size_t)bidx * A.bird_stride;
+  const int nfs = (mode != FB_POSE_BIRD) ? A.n_front[bidx] : 0;
+  const int nbs = (mode != FB_POSE_FRONT) ? A.n_bird[bidx] : 0;
+  // ---- stage the edges
+  EdgeView E;
+  E.nfs = nfs; E.nbs = nbs;
+  uint8_t *flevel, *blevel;
+  {
+    float *lf = reinterpret_cast<float *>(smem);
+    size_t off = 0;
+    if (staged) {
+      float *fxw = lf; off += (size_t)A.front_stride * 3;
+      float *fobs = lf + off; off += (size_t)A.front_stride * 2;
+      float *finf = lf + off; off += (size_t)A.front_stride;
+      float *bxw = lf + off; off += (size_t)A.bird_stride * 3;
+      float *bxc = lf + off; off += (size_t)A.bird_stride * 3;
+      float *binf = lf + off; off += (size_t)A.bird_stride;
+      for (int i = tid; i < nfs * 3; i += POSE_THREADS) fxw[i] = A.front_xw[fo * 3 + i];
+      for (int i = tid; i < nfs * 2; i += POSE_THREADS) fobs[i] = A.front_obs[fo * 2 + i];
+      for (int i = tid; i < nbs * 3; i += POSE_THREADS) { bxw[i] = A.bird_xw[bo * 3 + i]; bxc[i] = A.bird_xc[bo * 3 + i]; }
+      E.fxw = fxw; E.fobs = fobs; E.finf = finf; E.bxw = bxw; E.bxc = bxc; E.binf = binf;
+      for (int i = tid; i < nfs; i += POSE_THREADS) finf[i] = A.front_inv_sigma2[fo + i];
+      for (int i = tid; i < nbs; i += POSE_THREADS) binf[i] = A.bird_inv_sigma2[bo + i];
+    } else {
+      E.fxw = A.front_xw + fo * 3; E.fobs = A.front_obs + fo * 2; E.finf = A.front_inv_sigma2 + fo;
+      E.bxw = A.bird_xw + bo * 3; E.bxc = A.bird_xc + bo * 3; E.binf = A.bird_inv_sigma2 + bo;
+    }
+    flevel = reinterpret_cast<uint8_t *>(lf + off);
+    blevel = flevel + ((A.front_stride + 15) & ~15);
+    E.flevel = flevel; E.blevel = blevel;
+  }
+  if (tid < 2) s_cnt[tid] = 0;
+  __syncthreads();
+  // edge construction (Optimizer.cc:525-602): count edges, clear mvbOutlier of mapped slots
+  for (int i = tid; i < nfs; i += POSE_THREADS) {
+    const bool v = !A.front_valid || A.front_valid[fo + i];
+    flevel[i] = v ? 0 : 2;
+    if (v) { A.front_outlier[fo + i] = 0; atomicAdd(&s_cnt[0], 1); }
+  }
+  for (int i = tid; i < nbs; i += POSE_THREADS) {
+    const bool v = !A.bird_valid || A.bird_valid[bo + i];
+    blevel[i] = v ? 0 : 2;
+    if (v) atomicAdd(&s_cnt[1], 1);
+  }
+  __syncthreads();
+  const int nf = s_cnt[0], nb = s_cnt[1];
+  if (mode == FB_POSE_BIRD ? nb < 3 : nf < 3) {  // Optimizer.cc:379,607,776
+    if (tid == 0) A.ninliers[bidx] = 0;
+    return;
+  }
+  E.wf = (mode == FB_POSE_FRONT) ? 1.0 : (double)A.wF;
+  E.wb = (double)A.wB;
+  const double fx = A.fx, fy = A.fy, cx = A.cx, cy = A.cy;
+  const double delta = (double)(float)sqrt(5.991);  // const float deltaMono = sqrt(5.991)
+  if (tid == 0) {
+    S.T = fb::se3_from_float12(A.Tcw + (size_t)bidx * 12);
+    S.Teval = S.T;
+    S.T0 = S.T;
+  }
+
+  auto active = [&] {
+    bool mine = false;
+    for (int i = tid; i < nfs; i += POSE_THREADS) mine |= flevel[i] == 0;
+    for (int i = tid; i < nbs; i += POSE_THREADS) mine |= blevel[i] == 0;
+    return mine;
+  };
+  auto eval = [&](const fb::SE3 &T, bool robust) { eval_pass<NT>(E, T, robust, delta, fx, fy, cx, cy, &S); };
+  auto classify = [&](int &nBad, int &nBadBird) {
+    POSE_T0()
+    const fb::SE3 T = S.T, Teval = S.Teval;
+    int bad = 0, badb = 0;
+    for (int i = tid; i < nfs; i += POSE_THREADS) {
+      if (flevel[i] == 2) continue;
+      const bool wasOut = A.front_outlier[fo + i] != 0;
+      const bool isBad = front_is_bad((float)edge_chi2(E, i, false, wasOut ? T : Teval, fx, fy, cx, cy), mode, A.wF);
+      A.front_outlier[fo + i] = isBad ? 1 : 0;
+      flevel[i] = isBad ? 1 : 0;
+      bad += isBad;
+    }
+    for (int i = tid; i < nbs; i += POSE_THREADS) {
+      if (blevel[i] == 2) continue;
+      const bool wasOut = A.bird_outlier[bo + i] != 0;
+      const bool isBad = bird_is_bad((float)edge_chi2(E, i, true, wasOut ? T : Teval, fx, fy, cx, cy), A.wB);
+      A.bird_outlier[bo + i] = isBad ? 1 : 0;
+      blevel[i] = isBad ? 1 : 0;
+      badb += isBad;
+    }
+    sum_bad<NT / 64>(S, true, bad, badb, nBad, nBadBird);
+    POSE_TICK(7)
+  };
+  pose_rounds<SolvePrecise>(A, S, tid == 0, nf, nb, active, eval, classify);
+#ifdef FB_POSE_STAMPS
+  if (blockIdx.x == 0 && tid == 0) g_pose_stamps[14] += __builtin_amdgcn_s_memtime() - pose_t_start;
+#endif
+}
+
+__global__ __launch_bounds__(256) void k_pose_opt(fb_pose_opt_args A, int staged) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  __shared__ PoseLds S;
+  __shared__ int s_cnt[2];
+  pose_generic<256>(A, staged, smem, S, s_cnt);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// k_pose_opt_regs -- the same schedule, built for the latency of ONE frame (single-sequence tracking is bounded by this
+// kernel).  Phase stamps of the LDS-staged kernel above (profiles/r02_pose_stamps_before.txt): an LM evaluation took
+// ~29 k cycles = 12.6 k edge arithmetic of one wave per SIMD, 7 k for the 28 cross-lane sums (ds_bpermute butterflies
+// are latency chains), 4 k for the 6x6 solve + exponential map on one lane.  Here
+//  * the edges of a thread live in REGISTERS (edge with rank r -> thread r % NE, slot r / NE), so an evaluation reads
+//    nothing but the pose from LDS and two waves per SIMD cover each other's fp64 latencies;
+//  * the 28 sums go through an LDS transpose: every edge thread stores its 28 accumulators (conflict-free rows of
+//    NE + CPA doubles), 28 x CPA threads add NE / CPA values each with 4 independent chains, the CPA partial sums of an
+//    accumulator sit in adjacent lanes and are combined with DPP row shifts (VALU moves, no LDS crossbar);
+//  * the update T <- exp(x) T is formed directly on the quaternion (SolveFast).
+// NT threads, of which the first NE carry edges:
+//  * NE == NT: every thread has the edge role and thread 0 also solves.  The 6x6 solve and the exponential map then run
+//    on a lane that also carries edges, their registers come on top of the edge registers, and with two waves per SIMD
+//    (<512, 512, 5, 3>) they spill; <256, 256, 10, 6> has one wave per SIMD and the whole register file.
+//  * NE == NT - 64: the last wave does nothing but the solve (thread NE).
+// The roles are instantiations of one generic lambda, so each is register-allocated on its own (no edge register is live
+// in the solver's code and vice versa) and they meet at the same barriers.  Same arithmetic and same order of every sum
+// in all of them.
+// EF / EB = front / bird edge slots per thread.  5 + 3 slots (2240 + 1344 edges on 448 threads: the 2000-feature
+// extractor, capacity 2064) keep acc[28] + the edges + the per-edge temporaries inside the 256 registers two waves per
+// SIMD leave a thread.
+// ---------------------------------------------------------------------------------------------------------------------
+template <int NT, int NE>
+struct PoseRegsShape {
+  static constexpr int CPA = NACC * 16 <= NE ? 16 : 8;  // threads that share one accumulator in the column sums
+  static constexpr int TRIPS = NE / CPA;                // values each of them adds
+  static constexpr int RS = NE + CPA;  // row stride in doubles: 2 * RS mod 64 = 2 * CPA, so the CPA-wide windows of the accumulators
+                                       // handled by one ds_read_b64 lane group fall into disjoint banks; the row writes are contiguous
+  static constexpr size_t LDS_BYTES = (size_t)NACC * RS * sizeof(double);  // the dynamic LDS of a launch
+  static_assert(NT % 64 == 0 && (NE == NT || NE == NT - 64), "edge waves, then at most one solver wave");
+  static_assert(NACC * CPA <= NE, "one thread per accumulator window");
+  static_assert(TRIPS * CPA == NE && TRIPS % 4 == 0, "four chains over all the edge threads' rows");
+  static_assert(CPA == 8 || CPA == 16, "a window is half a DPP row or a whole one: row_shr 8 / 4 / 2 / 1 never leave it");
+  static_assert((2 * RS) % 64 == 2 * CPA, "bank layout of the windows");
+};
+
+// Slot compaction of the edge construction (Optimizer.cc:525-602): the slots with an edge are ranked among the valid
+// slots, in slot order, so that a thread's registers hold real edges only.  Wave w scans the contiguous range of slots
+// [w * per, (w + 1) * per): count_valid_slots is its number of edges, rank_valid_slots writes the slot index of the edge
+// with rank r to idx[r] (base = the edges of the waves before).
+template <int NW>
+__device__ __forceinline__ int slots_per_wave(int n) { return (((n + NW - 1) / NW) + 63) & ~63; }
+__device__ __forceinline__ int count_valid_slots(const uint8_t *valid, int n, int per, int wv, int lane) {
+  int c = 0;
+  for (int i = wv * per + lane; i < min((wv + 1) * per, n); i += 64) c += (!valid || valid[i]) ? 1 : 0;
+  return (int)wave_sum((double)c);
+}
+__device__ __forceinline__ void rank_valid_slots(const uint8_t *valid, int n, int per, int wv, int lane, int base, unsigned short *idx) {
+  for (int i0 = wv * per; i0 < min((wv + 1) * per, n); i0 += 64) {
+    const int i = i0 + lane;
+    const bool v = i < min((wv + 1) * per, n) && (!valid || valid[i]);
+    const unsigned long long m = __ballot(v);
+    if (v) idx[base + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = (unsigned short)i;
+    base += __popcll(m);
+  }
+}
+
+template <int NT, int NE, int EF, int EB>
+__global__ __launch_bounds__(NT) void k_pose_opt_regs(fb_pose_opt_args A) {
+  using Shape = PoseRegsShape<NT, NE>;
+  constexpr int CPA = Shape::CPA, TRIPS = Shape::TRIPS, RS = Shape::RS;
+  constexpr int NWE = NE / 64, NWR = NT / 64;
+  constexpr int SOLVER = NE % NT;  // the thread that solves: 0, or the first one of the solver wave
   extern __shared__ __attribute__((aligned(16))) double s_part[];  // [NACC][RS]
   __shared__ PoseLds S;
   __shared__ int s_cnt[2];
@@ -647,352 +716,13 @@ __global__ __launch_bounds__(NT) void k_pose_opt_reg(fb_pose_opt_args A) {
   const size_t fo = (size_t)bidx * A.front_stride, bo = (size_t)bidx * A.bird_stride;
   const int nfs = (mode != FB_POSE_BIRD) ? A.n_front[bidx] : 0;
   const int nbs = (mode != FB_POSE_FRONT) ? A.n_bird[bidx] : 0;
-  float *Tcw = A.Tcw + (size_t)bidx * 12;
-  // ---- edge construction (Optimizer.cc:525-602).  The slots with an edge are compacted (rank among the valid slots, in
-  //      slot order) so that a thread's registers hold real edges only: wave w scans the contiguous range of slots
-  //      [w * per, (w + 1) * per), pass 1 counts, pass 2 writes the slot index of the edge with rank r to s_idx[r].
-  unsigned short *s_idxF = reinterpret_cast<unsigned short *>(s_part);   // [EF * NT]
-  unsigned short *s_idxB = s_idxF + EF * NT;                             // [EB * NT]
-  const int perF = (((nfs + NWR - 1) / NWR) + 63) & ~63, perB = (((nbs + NWR - 1) / NWR) + 63) & ~63;
-  {
-    int cf = 0, cb = 0;
-    for (int i = wv * perF + lane; i < min((wv + 1) * perF, nfs); i += 64) cf += (!A.front_valid || A.front_valid[fo + i]) ? 1 : 0;
-    for (int i = wv * perB + lane; i < min((wv + 1) * perB, nbs); i += 64) cb += (!A.bird_valid || A.bird_valid[bo + i]) ? 1 : 0;
-    cf = (int)wave_sum((double)cf); cb = (int)wave_sum((double)cb);
-    if (lane == 0) { s_wcnt[0][wv] = cf; s_wcnt[1][wv] = cb; }
-  }
-  __syncthreads();
-  int nf = 0, nb = 0, baseF = 0, baseB = 0;
-#pragma unroll
-  for (int w = 0; w < NWR; w++) {
-    if (w < wv) { baseF += s_wcnt[0][w]; baseB += s_wcnt[1][w]; }
-    nf += s_wcnt[0][w]; nb += s_wcnt[1][w];
-  }
-  if (nf > EF * NT || nb > EB * NT || A.front_stride > 65535 || A.bird_stride > 65535) {
-    // more edges than register slots: the generic schedule, edges read from HBM / L2 (the level bytes take the LDS)
-    __syncthreads();
-    pose_generic<NT>(A, 0, reinterpret_cast<uint8_t *>(s_part), S, s_cnt);
-    return;
-  }
-  if (mode == FB_POSE_BIRD ? nb < 3 : nf < 3) {  // Optimizer.cc:379,607,776
-    // (the edge slots' mvbOutlier entries are still cleared, as the edge construction loop does before the count is known)
-    for (int i = tid; i < nfs; i += NT)
-      if (!A.front_valid || A.front_valid[fo + i]) A.front_outlier[fo + i] = 0;
-    if (tid == 0) A.ninliers[bidx] = 0;
-    return;
-  }
-  for (int i0 = wv * perF; i0 < min((wv + 1) * perF, nfs); i0 += 64) {
-    const int i = i0 + lane;
-    const bool v = i < min((wv + 1) * perF, nfs) && (!A.front_valid || A.front_valid[fo + i]);
-    const unsigned long long m = __ballot(v);
-    if (v) s_idxF[baseF + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = (unsigned short)i;
-    baseF += __popcll(m);
-  }
-  for (int i0 = wv * perB; i0 < min((wv + 1) * perB, nbs); i0 += 64) {
-    const int i = i0 + lane;
-    const bool v = i < min((wv + 1) * perB, nbs) && (!A.bird_valid || A.bird_valid[bo + i]);
-    const unsigned long long m = __ballot(v);
-    if (v) s_idxB[baseB + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = (unsigned short)i;
-    baseB += __popcll(m);
-  }
-  __syncthreads();
-  // this thread's edges -> registers: edge with rank r = s * NT + tid.  level 0 = active, 1 = outlier level, 2 = no edge
-  // (two bits per slot); fidx / bidx_ = the frame slot the edge came from (where its outlier flag lives)
-  float fx0[EF], fx1[EF], fx2[EF], fo0[EF], fo1[EF], fin[EF];
-  float bx0[EB], bx1[EB], bx2[EB], bc0[EB], bc1[EB], bc2[EB], bin[EB];
-  int fidx[EF], bidx_[EB];
-  unsigned flev = 0, blev = 0, fout = 0, bout = 0;
-#pragma unroll
-  for (int s = 0; s < EF; s++) {
-    const int r = s * NT + tid;
-    const bool v = r < nf;
-    fx0[s] = fx1[s] = fx2[s] = fo0[s] = fo1[s] = fin[s] = 0.f;
-    fidx[s] = 0;
-    if (v) {
-      const int e = s_idxF[r];
-      fidx[s] = e;
-      const float *X = A.front_xw + (fo + e) * 3, *O = A.front_obs + (fo + e) * 2;
-      fx0[s] = X[0]; fx1[s] = X[1]; fx2[s] = X[2]; fo0[s] = O[0]; fo1[s] = O[1];
-      fin[s] = A.front_inv_sigma2[fo + e];
-      A.front_outlier[fo + e] = 0;
-    }
-    flev |= (v ? 0u : 2u) << (2 * s);
-  }
-#pragma unroll
-  for (int s = 0; s < EB; s++) {
-    const int r = s * NT + tid;
-    const bool v = r < nb;
-    bx0[s] = bx1[s] = bx2[s] = bc0[s] = bc1[s] = bc2[s] = bin[s] = 0.f;
-    bidx_[s] = 0;
-    if (v) {
-      const int e = s_idxB[r];
-      bidx_[s] = e;
-      const float *X = A.bird_xw + (bo + e) * 3, *Cc = A.bird_xc + (bo + e) * 3;
-      bx0[s] = X[0]; bx1[s] = X[1]; bx2[s] = X[2]; bc0[s] = Cc[0]; bc1[s] = Cc[1]; bc2[s] = Cc[2];
-      bin[s] = A.bird_inv_sigma2[bo + e];
-      if (A.bird_outlier[bo + e]) bout |= 1u << s;  // the incoming mvBirdOutlier decides which chi2 the first round recomputes
-    }
-    blev |= (v ? 0u : 2u) << (2 * s);
-  }
-  __syncthreads();  // s_idx lives in the buffer the evaluations overwrite
-  const double wf = (mode == FB_POSE_FRONT) ? 1.0 : (double)A.wF, wb = (double)A.wB;
-  const double fx = A.fx, fy = A.fy, cx = A.cx, cy = A.cy;
-  const double delta = (double)(float)sqrt(5.991);
-  const float chi2Mono = (mode == FB_POSE_FRONT) ? 5.991f : 1.5f;
-  const float chi2Bird = 5.991f;
-  if (tid == 0) {
-    S.T = fb::se3_from_float12(Tcw);
-    S.Teval = S.T;
-  }
-  __syncthreads();
-  const fb::SE3 T0 = S.T;
-
-  // one evaluation at pose T: robust chi2 + H + b over this thread's active edges, then the 28 column sums -> S.red
-  auto eval = [&](const fb::SE3 &T, bool robust) {
-    double acc[NACC];
-#pragma unroll
-    for (int i = 0; i < NACC; i++) acc[i] = 0;
-    POSE_T0()
-    POSE_COUNT(15)
-#pragma unroll
-    for (int s = 0; s < EF; s++)
-      if (((flev >> (2 * s)) & 3u) == 0u) {
-        // (opaque copies: otherwise the float -> double conversions and the weight product of every edge are hoisted out of
-        // the LM loop and held in registers -- three times the registers of the floats themselves, i.e. spills)
-        float a0 = fx0[s], a1 = fx1[s], a2 = fx2[s], a3 = fo0[s], a4 = fo1[s], a5 = fin[s];
-        asm volatile("" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5));
-        front_edge_acc(T, a0, a1, a2, a3, a4, (double)a5 * wf, robust, delta, fx, fy, cx, cy, acc);
-      }
-    POSE_TICK(0)
-#pragma unroll
-    for (int s = 0; s < EB; s++)
-      if (((blev >> (2 * s)) & 3u) == 0u) {
-        float a0 = bx0[s], a1 = bx1[s], a2 = bx2[s], a3 = bc0[s], a4 = bc1[s], a5 = bc2[s], a6 = bin[s];
-        asm volatile("" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6));
-        bird_edge_acc(T, a0, a1, a2, a3, a4, a5, (double)a6 * wb, robust, delta, acc);
-      }
-    POSE_TICK(1)
-#pragma unroll
-    for (int i = 0; i < NACC; i++) s_part[i * RS + tid] = acc[i];
-    __syncthreads();
-    POSE_TICK(2)
-    if (tid < NACC * CPA) {
-      const int a = tid / CPA, c = tid - a * CPA;
-      const double *row = s_part + a * RS + c;
-      double s0 = 0, s1 = 0, s2 = 0, s3 = 0;
-#pragma unroll
-      for (int k = 0; k < 32; k += 4) {
-        s0 += row[(k + 0) * CPA]; s1 += row[(k + 1) * CPA]; s2 += row[(k + 2) * CPA]; s3 += row[(k + 3) * CPA];
-      }
-      double v = (s0 + s1) + (s2 + s3);
-      // the CPA partial sums of accumulator a sit in CPA adjacent lanes of one 16-lane DPP row: shift-add towards the last lane
-      if (CPA == 16) v += dpp_f64<0x118>(v);  // row_shr:8
-      v += dpp_f64<0x114>(v);                 // row_shr:4
-      v += dpp_f64<0x112>(v);                 // row_shr:2
-      v += dpp_f64<0x111>(v);                 // row_shr:1
-      if (c == CPA - 1) S.red[a] = v;
-    }
-    __syncthreads();
-    POSE_TICK(3)
-  };
-
-  int nBad = 0, nBadBird = 0;
-  for (int it = 0; it < 4; it++) {
-    const bool robust = it < 3;
-    if (tid == 0) S.T = T0;
-    bool mine = false;
-#pragma unroll
-    for (int s = 0; s < EF; s++) mine |= ((flev >> (2 * s)) & 3u) == 0u;
-#pragma unroll
-    for (int s = 0; s < EB; s++) mine |= ((blev >> (2 * s)) & 3u) == 0u;
-    const int nact = __syncthreads_count(mine);  // also publishes S.T
-    if (nact > 0) {
-      eval(S.T, robust);
-      if (tid == 0) { unpack_system(S.red, S.H, S.b); S.Teval = S.T; }
-      double currentChi = S.red[0];
-      __syncthreads();
-      double lambda = 0, ni = 2;
-      int nBadLM = 0;
-      for (int iter = 0; iter < 10; iter++) {
-        const double iniChi = currentChi;
-        if (iter == 0) {
-          double m = 0;
-          for (int j = 0; j < 6; j++) m = fmax(fabs(S.H[j * 6 + j]), m);
-          lambda = 1e-5 * m;
-          ni = 2;
-          nBadLM = 0;
-        }
-        double rho = 0;
-        int qmax = 0;
-        do {
-          {
-            POSE_T0()
-            if (tid == 0) {
-              S.ok2 = ldlt6_fast(S.H, lambda, S.b, S.x) ? 1 : 0;
-              POSE_TICK(4)
-              S.Ttrial = se3_mul_fast(se3_exp_direct(S.x), S.T);  // oplus
-              S.Teval = S.Ttrial;
-              POSE_TICK(5)
-            }
-            __syncthreads();
-            POSE_TICK(6)
-          }
-          eval(S.Ttrial, robust);
-          double tempChi = S.red[0];
-          if (!S.ok2) tempChi = 1.7976931348623157e308;
-          rho = currentChi - tempChi;
-          double scale = 0;
-          for (int j = 0; j < 6; j++) scale += S.x[j] * (lambda * S.x[j] + S.b[j]);
-          scale += 1e-3;
-          rho /= scale;
-          const bool accept = rho > 0 && isfinite(tempChi);
-          __syncthreads();  // everyone has read red/x/b
-          if (accept) {
-            double alpha = 1. - pow((2 * rho - 1), 3);
-            alpha = fmin(alpha, 2. / 3.);
-            const double scaleFactor = fmax(1. / 3., alpha);
-            lambda *= scaleFactor;
-            ni = 2;
-            currentChi = tempChi;
-            if (tid == 0) { S.T = S.Ttrial; unpack_system(S.red, S.H, S.b); }
-          } else {
-            lambda *= ni;
-            ni *= 2;
-          }
-          __syncthreads();
-          qmax++;
-        } while (rho < 0 && qmax < 10);
-        if (qmax == 10 || rho == 0) break;
-        if ((iniChi - currentChi) * 1e3 < iniChi) nBadLM++;
-        else nBadLM = 0;
-        if (nBadLM >= 3) break;
-      }
-    }
-    // ---- classify (Optimizer.cc:396-431, 627-686, 791-822)
-    POSE_T0()
-    const fb::SE3 T = S.T, Teval = S.Teval;
-    int bad = 0, badb = 0;
-#pragma unroll
-    for (int s = 0; s < EF; s++) {
-      if (((flev >> (2 * s)) & 3u) == 2u) continue;
-      const bool wasOut = (fout >> s) & 1u;
-      float a0 = fx0[s], a1 = fx1[s], a2 = fx2[s], a3 = fo0[s], a4 = fo1[s], a5 = fin[s];
-      asm volatile("" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5));
-      const float chi2 = (float)chi2_front_vals(a0, a1, a2, a3, a4, (double)a5 * wf, wasOut ? T : Teval, fx, fy, cx, cy);
-      bool isBad;
-      if (mode == FB_POSE_FRONT) isBad = chi2 > chi2Mono;
-      else isBad = chi2 > chi2Mono * ((double)A.wF + 1e-9);
-      A.front_outlier[fo + fidx[s]] = isBad ? 1 : 0;
-      flev = (flev & ~(3u << (2 * s))) | ((isBad ? 1u : 0u) << (2 * s));
-      fout = (fout & ~(1u << s)) | ((isBad ? 1u : 0u) << s);
-      bad += isBad;
-    }
-#pragma unroll
-    for (int s = 0; s < EB; s++) {
-      if (((blev >> (2 * s)) & 3u) == 2u) continue;
-      const bool wasOut = (bout >> s) & 1u;
-      float a0 = bx0[s], a1 = bx1[s], a2 = bx2[s], a3 = bc0[s], a4 = bc1[s], a5 = bc2[s], a6 = bin[s];
-      asm volatile("" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6));
-      const float chi2 = (float)chi2_bird_vals(a0, a1, a2, a3, a4, a5, (double)a6 * wb, wasOut ? T : Teval);
-      const float chi2Bad = (float)(chi2Bird * ((double)A.wB + 1e-9));
-      const bool isBad = chi2 > chi2Bad;
-      A.bird_outlier[bo + bidx_[s]] = isBad ? 1 : 0;
-      blev = (blev & ~(3u << (2 * s))) | ((isBad ? 1u : 0u) << (2 * s));
-      bout = (bout & ~(1u << s)) | ((isBad ? 1u : 0u) << s);
-      badb += isBad;
-    }
-    {
-      // per-wave counts through the ballots of each slot would cost 12 ballots; two wave sums + one LDS hop instead
-      const double sb = wave_sum((double)bad), sbb = wave_sum((double)badb);
-      if ((tid & 63) == 0) { S.part[0][tid >> 6] = sb; S.part[1][tid >> 6] = sbb; }
-      __syncthreads();
-      double tb = 0, tbb = 0;
-      for (int w2 = 0; w2 < NWR; w2++) { tb += S.part[0][w2]; tbb += S.part[1][w2]; }
-      nBad = (int)tb; nBadBird = (int)tbb;
-      __syncthreads();
-    }
-    POSE_TICK(7)
-    if (nf + nb < 10) break;  // optimizer.edges().size()<10
-  }
-  if (tid == 0) {
-    fb::se3_to_float12(S.T, Tcw);
-    A.ninliers[bidx] = (mode == FB_POSE_BIRD) ? nb - nBadBird : nf - nBad;
-  }
-#ifdef FB_POSE_STAMPS
-  if (blockIdx.x == 0 && tid == 0) g_pose_stamps[14] += __builtin_amdgcn_s_memtime() - pose_t_start;
-#endif
-}
-
-// --- device-side edge construction (Optimizer.cc:525-602) --------------------------------
-struct GatherK { float inv_sigma2[FB_MAX_LEVELS]; int nlevels; };
-
-__global__ void k_gather_front(int kp_stride, int mp_stride, const int32_t *__restrict__ n, const fb_keypoint *__restrict__ kps,
-                               const int32_t *__restrict__ match, const float *__restrict__ mp_xw, GatherK G,
-                               float *__restrict__ xw, float *__restrict__ obs, float *__restrict__ inf,
-                               uint8_t *__restrict__ valid) {
-  const int b = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= kp_stride) return;
-  const size_t o = (size_t)b * kp_stride + i;
-  const int m = (i < n[b]) ? match[o] : -1;
-  if (m < 0) { valid[o] = 0; return; }
-  const fb_keypoint kp = kps[o];
-  const float *X = mp_xw + ((size_t)b * mp_stride + m) * 3;
-  xw[o * 3] = X[0]; xw[o * 3 + 1] = X[1]; xw[o * 3 + 2] = X[2];
-  obs[o * 2] = kp.x; obs[o * 2 + 1] = kp.y;
-  inf[o] = G.inv_sigma2[kp.octave];
-  valid[o] = 1;
-}
-
-__global__ void k_gather_bird(int kp_stride, int mp_stride, const int32_t *__restrict__ n, const fb_keypoint *__restrict__ kps,
-                              const float *__restrict__ cam, const int32_t *__restrict__ match, const float *__restrict__ mpb_xw,
-                              GatherK G, float *__restrict__ xw, float *__restrict__ xc, float *__restrict__ inf,
-                              uint8_t *__restrict__ valid) {
-  const int b = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= kp_stride) return;
-  const size_t o = (size_t)b * kp_stride + i;
-  const int m = (i < n[b]) ? match[o] : -1;
-  if (m < 0) { valid[o] = 0; return; }
-  const float *X = mpb_xw + ((size_t)b * mp_stride + m) * 3;
-  xw[o * 3] = X[0]; xw[o * 3 + 1] = X[1]; xw[o * 3 + 2] = X[2];
-  xc[o * 3] = cam[o * 3]; xc[o * 3 + 1] = cam[o * 3 + 1]; xc[o * 3 + 2] = cam[o * 3 + 2];
-  inf[o] = G.inv_sigma2[kps[o].octave];
-  valid[o] = 1;
-}
-
-// ------------------------------------------------------------------------------------------
-// k_pose_opt_split -- k_pose_opt_reg with the serial part of an LM step on a wave of its own.  In k_pose_opt_reg the 6x6
-// solve and the exponential map run on lane 0 of a wave that also carries edges: the registers of the solve come on top of
-// the edge registers and ~117 of them spill (704 B of scratch per lane, reloaded in every evaluation).  Here waves
-// 0 .. NWE-1 carry the edges and the last wave does nothing but the solve: the two roles are two instantiations of one
-// generic lambda, so each is register-allocated on its own (no edge register is live in the solver's code and vice versa)
-// and they meet at the same barriers.  Same arithmetic, same order of every sum as k_pose_opt_reg.
-// ------------------------------------------------------------------------------------------
-template <int NT, int EF, int EB>
-__global__ __launch_bounds__(NT) void k_pose_opt_split(fb_pose_opt_args A) {
-  constexpr int NE = NT - 64;    // edge threads
-  constexpr int NWE = NE / 64, NWR = NT / 64;
-  constexpr int CPA = NE / NACC; // threads that share one accumulator in the column sums: NACC * CPA = NE, each adds NE / CPA values
-  static_assert(CPA == 16 && NACC * CPA == NE, "the column sums are laid out for 448 edge threads");
-  constexpr int RS = NE + CPA;   // row stride in doubles (2 * RS mod 64 = 2 * CPA: the CPA-wide windows fall into disjoint banks)
-  extern __shared__ __attribute__((aligned(16))) double s_part[];  // [NACC][RS]
-  __shared__ PoseLds S;
-  __shared__ int s_cnt[2];
-  __shared__ int s_wcnt[2][NWR];
-  const int bidx = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int mode = A.mode;
-  const size_t fo = (size_t)bidx * A.front_stride, bo = (size_t)bidx * A.bird_stride;
-  const int nfs = (mode != FB_POSE_BIRD) ? A.n_front[bidx] : 0;
-  const int nbs = (mode != FB_POSE_FRONT) ? A.n_bird[bidx] : 0;
-  float *Tcw = A.Tcw + (size_t)bidx * 12;
-  // ---- edge construction (Optimizer.cc:525-602): the slots with an edge are compacted in slot order (all NWR waves scan)
+  // ---- edge construction: all NWR waves scan
+  const uint8_t *fvalid = A.front_valid ? A.front_valid + fo : nullptr, *bvalid = A.bird_valid ? A.bird_valid + bo : nullptr;
   unsigned short *s_idxF = reinterpret_cast<unsigned short *>(s_part);   // [EF * NE]
   unsigned short *s_idxB = s_idxF + EF * NE;                             // [EB * NE]
-  const int perF = (((nfs + NWR - 1) / NWR) + 63) & ~63, perB = (((nbs + NWR - 1) / NWR) + 63) & ~63;
+  const int perF = slots_per_wave<NWR>(nfs), perB = slots_per_wave<NWR>(nbs);
   {
-    int cf = 0, cb = 0;
-    for (int i = wv * perF + lane; i < min((wv + 1) * perF, nfs); i += 64) cf += (!A.front_valid || A.front_valid[fo + i]) ? 1 : 0;
-    for (int i = wv * perB + lane; i < min((wv + 1) * perB, nbs); i += 64) cb += (!A.bird_valid || A.bird_valid[bo + i]) ? 1 : 0;
-    cf = (int)wave_sum((double)cf); cb = (int)wave_sum((double)cb);
+    const int cf = count_valid_slots(fvalid, nfs, perF, wv, lane), cb = count_valid_slots(bvalid, nbs, perB, wv, lane);
     if (lane == 0) { s_wcnt[0][wv] = cf; s_wcnt[1][wv] = cb; }
   }
   __syncthreads();
@@ -1009,35 +739,24 @@ __global__ __launch_bounds__(NT) void k_pose_opt_split(fb_pose_opt_args A) {
     return;
   }
   if (mode == FB_POSE_BIRD ? nb < 3 : nf < 3) {  // Optimizer.cc:379,607,776
+    // (the edge slots' mvbOutlier entries are still cleared, as the edge construction loop does before the count is known)
     for (int i = tid; i < nfs; i += NT)
-      if (!A.front_valid || A.front_valid[fo + i]) A.front_outlier[fo + i] = 0;
+      if (!fvalid || fvalid[i]) A.front_outlier[fo + i] = 0;
     if (tid == 0) A.ninliers[bidx] = 0;
     return;
   }
-  for (int i0 = wv * perF; i0 < min((wv + 1) * perF, nfs); i0 += 64) {
-    const int i = i0 + lane;
-    const bool v = i < min((wv + 1) * perF, nfs) && (!A.front_valid || A.front_valid[fo + i]);
-    const unsigned long long m = __ballot(v);
-    if (v) s_idxF[baseF + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = (unsigned short)i;
-    baseF += __popcll(m);
-  }
-  for (int i0 = wv * perB; i0 < min((wv + 1) * perB, nbs); i0 += 64) {
-    const int i = i0 + lane;
-    const bool v = i < min((wv + 1) * perB, nbs) && (!A.bird_valid || A.bird_valid[bo + i]);
-    const unsigned long long m = __ballot(v);
-    if (v) s_idxB[baseB + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = (unsigned short)i;
-    baseB += __popcll(m);
-  }
-  if (tid == NE) {
-    S.T = fb::se3_from_float12(Tcw);
+  rank_valid_slots(fvalid, nfs, perF, wv, lane, baseF, s_idxF);
+  rank_valid_slots(bvalid, nbs, perB, wv, lane, baseB, s_idxB);
+  if (tid == SOLVER) {
+    S.T = fb::se3_from_float12(A.Tcw + (size_t)bidx * 12);
     S.Teval = S.T;
     S.T0 = S.T;
   }
   __syncthreads();
 
-  auto role = [&](auto edgeRole) {
-    constexpr bool EDGE = decltype(edgeRole)::value;
-    // this thread's edges -> registers (edge waves only): edge with rank r = s * NE + tid.  level 0 = active, 1 = outlier level,
+  auto role = [&](auto edgeRole, auto solveRole) {
+    constexpr bool EDGE = decltype(edgeRole)::value, SOLVE = decltype(solveRole)::value;
+    // this thread's edges -> registers (edge role only): edge with rank r = s * NE + tid.  level 0 = active, 1 = outlier level,
     // 2 = no edge (two bits per slot); fidx / bidx_ = the frame slot the edge came from (where its outlier flag lives)
     float fx0[EF], fx1[EF], fx2[EF], fo0[EF], fo1[EF], fin[EF];
     float bx0[EB], bx1[EB], bx2[EB], bc0[EB], bc1[EB], bc2[EB], bin[EB];
@@ -1081,59 +800,8 @@ __global__ __launch_bounds__(NT) void k_pose_opt_split(fb_pose_opt_args A) {
     const double wf = (mode == FB_POSE_FRONT) ? 1.0 : (double)A.wF, wb = (double)A.wB;
     const double fx = A.fx, fy = A.fy, cx = A.cx, cy = A.cy;
     const double delta = (double)(float)sqrt(5.991);
-    const float chi2Mono = (mode == FB_POSE_FRONT) ? 5.991f : 1.5f;
-    const float chi2Bird = 5.991f;
 
-    // one evaluation at pose *Tp: robust chi2 + H + b over this thread's active edges, then the 28 column sums -> S.red
-    // (the solver wave only keeps the two barriers)
-    auto eval = [&](const fb::SE3 *Tp, bool robust) {
-      if constexpr (EDGE) {
-        const fb::SE3 T = *Tp;
-        double acc[NACC];
-#pragma unroll
-        for (int i = 0; i < NACC; i++) acc[i] = 0;
-#pragma unroll
-        for (int s = 0; s < EF; s++)
-          if (((flev >> (2 * s)) & 3u) == 0u) {
-            // (opaque copies: otherwise the float -> double conversions and the weight product of every edge are hoisted out
-            // of the LM loop and held in registers -- three times the registers of the floats themselves)
-            float a0 = fx0[s], a1 = fx1[s], a2 = fx2[s], a3 = fo0[s], a4 = fo1[s], a5 = fin[s];
-            asm volatile("" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5));
-            front_edge_acc(T, a0, a1, a2, a3, a4, (double)a5 * wf, robust, delta, fx, fy, cx, cy, acc);
-          }
-#pragma unroll
-        for (int s = 0; s < EB; s++)
-          if (((blev >> (2 * s)) & 3u) == 0u) {
-            float a0 = bx0[s], a1 = bx1[s], a2 = bx2[s], a3 = bc0[s], a4 = bc1[s], a5 = bc2[s], a6 = bin[s];
-            asm volatile("" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6));
-            bird_edge_acc(T, a0, a1, a2, a3, a4, a5, (double)a6 * wb, robust, delta, acc);
-          }
-#pragma unroll
-        for (int i = 0; i < NACC; i++) s_part[i * RS + tid] = acc[i];
-      }
-      __syncthreads();
-      if constexpr (EDGE) {
-        const int a = tid / CPA, c = tid - a * CPA;  // NACC * CPA = NE: every edge thread sums one window
-        const double *row = s_part + a * RS + c;
-        double s0 = 0, s1 = 0, s2 = 0, s3 = 0;
-#pragma unroll
-        for (int k = 0; k < NE / CPA; k += 4) {
-          s0 += row[(k + 0) * CPA]; s1 += row[(k + 1) * CPA]; s2 += row[(k + 2) * CPA]; s3 += row[(k + 3) * CPA];
-        }
-        double v = (s0 + s1) + (s2 + s3);
-        v += dpp_f64<0x118>(v);  // row_shr:8: the CPA partial sums of accumulator a sit in the 16 lanes of one DPP row
-        v += dpp_f64<0x114>(v);  // row_shr:4
-        v += dpp_f64<0x112>(v);  // row_shr:2
-        v += dpp_f64<0x111>(v);  // row_shr:1
-        if (c == CPA - 1) S.red[a] = v;
-      }
-      __syncthreads();
-    };
-
-    int nBad = 0, nBadBird = 0;
-    for (int it = 0; it < 4; it++) {
-      const bool robust = it < 3;
-      if (!EDGE && tid == NE) S.T = S.T0;
+    auto active = [&] {
       bool mine = false;
       if constexpr (EDGE) {
 #pragma unroll
@@ -1141,64 +809,65 @@ __global__ __launch_bounds__(NT) void k_pose_opt_split(fb_pose_opt_args A) {
 #pragma unroll
         for (int s = 0; s < EB; s++) mine |= ((blev >> (2 * s)) & 3u) == 0u;
       }
-      const int nact = __syncthreads_count(mine);  // also publishes S.T
-      if (nact > 0) {
-        eval(&S.T, robust);
-        if (!EDGE && tid == NE) { unpack_system(S.red, S.H, S.b); S.Teval = S.T; }
-        double currentChi = S.red[0];
-        __syncthreads();
-        double lambda = 0, ni = 2;
-        int nBadLM = 0;
-        for (int iter = 0; iter < 10; iter++) {
-          const double iniChi = currentChi;
-          if (iter == 0) {
-            double m = 0;
-            for (int j = 0; j < 6; j++) m = fmax(fabs(S.H[j * 6 + j]), m);
-            lambda = 1e-5 * m;
-            ni = 2;
-            nBadLM = 0;
+      return mine;
+    };
+    // one evaluation at pose Tp: robust chi2 + H + b over this thread's active edges, then the 28 column sums -> S.red
+    // (a solver-only wave just keeps the two barriers)
+    auto eval = [&](const fb::SE3 &Tp, bool robust) {
+      POSE_T0()
+      POSE_COUNT(15)
+      if constexpr (EDGE) {
+        // (the pose is read from LDS where it is used: a copy taken here costs <256, 256, 10, 6> 12 more registers per lane,
+        // the extractor kernels of the other streams then no longer fit beside it, 1.3 % of the overlapped step;
+        // profiles/pose_unify_ab.txt)
+        const fb::SE3 &T = Tp;
+        double acc[NACC];
+#pragma unroll
+        for (int i = 0; i < NACC; i++) acc[i] = 0;
+#pragma unroll
+        for (int s = 0; s < EF; s++)
+          if (((flev >> (2 * s)) & 3u) == 0u) {
+            // (opaque copies: otherwise the float -> double conversions and the weight product of every edge are hoisted out of
+            // the LM loop and held in registers -- three times the registers of the floats themselves, i.e. spills)
+            float a0 = fx0[s], a1 = fx1[s], a2 = fx2[s], a3 = fo0[s], a4 = fo1[s], a5 = fin[s];
+            asm volatile("" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5));
+            front_edge_acc(T, a0, a1, a2, a3, a4, (double)a5 * wf, robust, delta, fx, fy, cx, cy, acc);
           }
-          double rho = 0;
-          int qmax = 0;
-          do {
-            if (!EDGE && tid == NE) {
-              S.ok2 = ldlt6_fast(S.H, lambda, S.b, S.x) ? 1 : 0;
-              S.Ttrial = se3_mul_fast(se3_exp_direct(S.x), S.T);  // oplus
-              S.Teval = S.Ttrial;
-            }
-            __syncthreads();
-            eval(&S.Ttrial, robust);
-            double tempChi = S.red[0];
-            if (!S.ok2) tempChi = 1.7976931348623157e308;
-            rho = currentChi - tempChi;
-            double scale = 0;
-            for (int j = 0; j < 6; j++) scale += S.x[j] * (lambda * S.x[j] + S.b[j]);
-            scale += 1e-3;
-            rho /= scale;
-            const bool accept = rho > 0 && isfinite(tempChi);
-            __syncthreads();  // everyone has read red/x/b
-            if (accept) {
-              double alpha = 1. - pow((2 * rho - 1), 3);
-              alpha = fmin(alpha, 2. / 3.);
-              const double scaleFactor = fmax(1. / 3., alpha);
-              lambda *= scaleFactor;
-              ni = 2;
-              currentChi = tempChi;
-              if (!EDGE && tid == NE) { S.T = S.Ttrial; unpack_system(S.red, S.H, S.b); }
-            } else {
-              lambda *= ni;
-              ni *= 2;
-            }
-            __syncthreads();
-            qmax++;
-          } while (rho < 0 && qmax < 10);
-          if (qmax == 10 || rho == 0) break;
-          if ((iniChi - currentChi) * 1e3 < iniChi) nBadLM++;
-          else nBadLM = 0;
-          if (nBadLM >= 3) break;
-        }
+        POSE_TICK(0)
+#pragma unroll
+        for (int s = 0; s < EB; s++)
+          if (((blev >> (2 * s)) & 3u) == 0u) {
+            float a0 = bx0[s], a1 = bx1[s], a2 = bx2[s], a3 = bc0[s], a4 = bc1[s], a5 = bc2[s], a6 = bin[s];
+            asm volatile("" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6));
+            bird_edge_acc(T, a0, a1, a2, a3, a4, a5, (double)a6 * wb, robust, delta, acc);
+          }
+        POSE_TICK(1)
+#pragma unroll
+        for (int i = 0; i < NACC; i++) s_part[i * RS + tid] = acc[i];
       }
-      // ---- classify (Optimizer.cc:396-431, 627-686, 791-822)
+      __syncthreads();
+      POSE_TICK(2)
+      if (EDGE && (NACC * CPA == NE || tid < NACC * CPA)) {
+        const int a = tid / CPA, c = tid - a * CPA;
+        const double *row = s_part + a * RS + c;
+        double s0 = 0, s1 = 0, s2 = 0, s3 = 0;
+#pragma unroll
+        for (int k = 0; k < TRIPS; k += 4) {
+          s0 += row[(k + 0) * CPA]; s1 += row[(k + 1) * CPA]; s2 += row[(k + 2) * CPA]; s3 += row[(k + 3) * CPA];
+        }
+        double v = (s0 + s1) + (s2 + s3);
+        // the CPA partial sums of accumulator a sit in CPA adjacent lanes of one 16-lane DPP row: shift-add towards the last lane
+        if (CPA == 16) v += dpp_f64<0x118>(v);  // row_shr:8
+        v += dpp_f64<0x114>(v);                 // row_shr:4
+        v += dpp_f64<0x112>(v);                 // row_shr:2
+        v += dpp_f64<0x111>(v);                 // row_shr:1
+        if (c == CPA - 1) S.red[a] = v;
+      }
+      __syncthreads();
+      POSE_TICK(3)
+    };
+    auto classify = [&](int &nBad, int &nBadBird) {
+      POSE_T0()
       int bad = 0, badb = 0;
       if constexpr (EDGE) {
         const fb::SE3 T = S.T, Teval = S.Teval;
@@ -1209,9 +878,7 @@ __global__ __launch_bounds__(NT) void k_pose_opt_split(fb_pose_opt_args A) {
           float a0 = fx0[s], a1 = fx1[s], a2 = fx2[s], a3 = fo0[s], a4 = fo1[s], a5 = fin[s];
           asm volatile("" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5));
           const float chi2 = (float)chi2_front_vals(a0, a1, a2, a3, a4, (double)a5 * wf, wasOut ? T : Teval, fx, fy, cx, cy);
-          bool isBad;
-          if (mode == FB_POSE_FRONT) isBad = chi2 > chi2Mono;
-          else isBad = chi2 > chi2Mono * ((double)A.wF + 1e-9);
+          const bool isBad = front_is_bad(chi2, mode, A.wF);
           A.front_outlier[fo + fidx[s]] = isBad ? 1 : 0;
           flev = (flev & ~(3u << (2 * s))) | ((isBad ? 1u : 0u) << (2 * s));
           fout = (fout & ~(1u << s)) | ((isBad ? 1u : 0u) << s);
@@ -1224,32 +891,78 @@ __global__ __launch_bounds__(NT) void k_pose_opt_split(fb_pose_opt_args A) {
           float a0 = bx0[s], a1 = bx1[s], a2 = bx2[s], a3 = bc0[s], a4 = bc1[s], a5 = bc2[s], a6 = bin[s];
           asm volatile("" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6));
           const float chi2 = (float)chi2_bird_vals(a0, a1, a2, a3, a4, a5, (double)a6 * wb, wasOut ? T : Teval);
-          const float chi2Bad = (float)(chi2Bird * ((double)A.wB + 1e-9));
-          const bool isBad = chi2 > chi2Bad;
+          const bool isBad = bird_is_bad(chi2, A.wB);
           A.bird_outlier[bo + bidx_[s]] = isBad ? 1 : 0;
           blev = (blev & ~(3u << (2 * s))) | ((isBad ? 1u : 0u) << (2 * s));
           bout = (bout & ~(1u << s)) | ((isBad ? 1u : 0u) << s);
           badb += isBad;
         }
-        const double sb = wave_sum((double)bad), sbb = wave_sum((double)badb);
-        if ((tid & 63) == 0) { S.part[0][tid >> 6] = sb; S.part[1][tid >> 6] = sbb; }
       }
-      __syncthreads();
-      {
-        double tb = 0, tbb = 0;
-        for (int w2 = 0; w2 < NWE; w2++) { tb += S.part[0][w2]; tbb += S.part[1][w2]; }
-        nBad = (int)tb; nBadBird = (int)tbb;
-      }
-      __syncthreads();
-      if (nf + nb < 10) break;  // optimizer.edges().size()<10
-    }
-    if (!EDGE && tid == NE) {
-      fb::se3_to_float12(S.T, Tcw);
-      A.ninliers[bidx] = (mode == FB_POSE_BIRD) ? nb - nBadBird : nf - nBad;
-    }
+      sum_bad<NWE>(S, EDGE, bad, badb, nBad, nBadBird);
+      POSE_TICK(7)
+    };
+    pose_rounds<SolveFast>(A, S, SOLVE && tid == SOLVER, nf, nb, active, eval, classify);
   };
-  if (wv < NWE) role(std::true_type{});
-  else role(std::false_type{});
+  if constexpr (NE == NT) role(std::true_type{}, std::true_type{});
+  else if (wv < NWE) role(std::true_type{}, std::false_type{});
+  else role(std::false_type{}, std::true_type{});
+#ifdef FB_POSE_STAMPS
+  if (blockIdx.x == 0 && tid == 0) g_pose_stamps[14] += __builtin_amdgcn_s_memtime() - pose_t_start;
+#endif
+}
+
+// --- device-side edge construction (Optimizer.cc:525-602) --------------------------------
+struct GatherK { float inv_sigma2[FB_MAX_LEVELS]; int nlevels; };
+
+__global__ void k_gather_front(int kp_stride, int mp_stride, const int32_t *__restrict__ n, const fb_keypoint *__restrict__ kps,
+                               const int32_t *__restrict__ match, const float *__restrict__ mp_xw, GatherK G,
+                               float *__restrict__ xw, float *__restrict__ obs, float *__restrict__ inf,
+                               uint8_t *__restrict__ valid) {
+  const int b = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= kp_stride) return;
+  const size_t o = (size_t)b * kp_stride + i;
+  const int m = (i < n[b]) ? match[o] : -1;
+  if (m < 0) { valid[o] = 0; return; }
+  const fb_keypoint kp = kps[o];
+  const float *X = mp_xw + ((size_t)b * mp_stride + m) * 3;
+  xw[o * 3] = X[0]; xw[o * 3 + 1] = X[1]; xw[o * 3 + 2] = X[2];
+  obs[o * 2] = kp.x; obs[o * 2 + 1] = kp.y;
+  inf[o] = G.inv_sigma2[kp.octave];
+  valid[o] = 1;
+}
+
+__global__ void k_gather_bird(int kp_stride, int mp_stride, const int32_t *__restrict__ n, const fb_keypoint *__restrict__ kps,
+                              const float *__restrict__ cam, const int32_t *__restrict__ match, const float *__restrict__ mpb_xw,
+                              GatherK G, float *__restrict__ xw, float *__restrict__ xc, float *__restrict__ inf,
+                              uint8_t *__restrict__ valid) {
+  const int b = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= kp_stride) return;
+  const size_t o = (size_t)b * kp_stride + i;
+  const int m = (i < n[b]) ? match[o] : -1;
+  if (m < 0) { valid[o] = 0; return; }
+  const float *X = mpb_xw + ((size_t)b * mp_stride + m) * 3;
+  xw[o * 3] = X[0]; xw[o * 3 + 1] = X[1]; xw[o * 3 + 2] = X[2];
+  xc[o * 3] = cam[o * 3]; xc[o * 3 + 1] = cam[o * 3 + 1]; xc[o * 3 + 2] = cam[o * 3 + 2];
+  inf[o] = G.inv_sigma2[kps[o].octave];
+  valid[o] = 1;
+}
+
+GatherK make_gather_k(const float *inv_level_sigma2, int nlevels) {
+  GatherK G;
+  memset(&G, 0, sizeof(G));
+  G.nlevels = nlevels;
+  for (int i = 0; i < nlevels; i++) G.inv_sigma2[i] = inv_level_sigma2[i];
+  return G;
+}
+
+// one launch of the register-resident kernel, with the dynamic LDS its own shape asks for
+template <int NT, int NE, int EF, int EB>
+int launch_pose_regs(const fb_pose_opt_args &A, hipStream_t s) {
+  constexpr int lds = (int)PoseRegsShape<NT, NE>::LDS_BYTES;
+  FB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_pose_opt_regs<NT, NE, EF, EB>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  k_pose_opt_regs<NT, NE, EF, EB><<<A.batch, NT, lds, s>>>(A);
+  FB_HIP(hipGetLastError());
+  return FB_OK;
 }
 
 }  // namespace
@@ -1268,33 +981,24 @@ int fb_pose_opt_batch_dev(const fb_pose_opt_args *A, void *stream) {
     FB_ARG(A->n_bird && A->bird_outlier && (A->bird_stride == 0 || (A->bird_xw && A->bird_xc && A->bird_inv_sigma2)));
   if (A->batch == 0) return FB_OK;
   // register-resident kernel whenever its in-kernel way out (level bytes of every slot in LDS) fits: by default
-  // k_pose_opt_split (448 edge threads + a solver wave; 120 B of scratch per lane); FB_POSE_NT=512 / 256 / 0 selects
-  // k_pose_opt_reg with 512 threads / with one wave per SIMD / the LDS-staged kernel (measurements only)
+  // k_pose_opt_regs<512, 448> (448 edge threads + a solver wave); FB_POSE_NT=512 / 256 / 0
+  // selects the one-role kernel with 512 threads / with one wave per SIMD / the LDS-staged kernel (measurements only)
   // Without FB_POSE_NT, batches of 64 frames or more take the 256-thread kernel instead: alone it is 9 % slower
   // (0.38 vs 0.35 ms), but its workgroup leaves 148 registers per SIMD lane to the extractor kernels of the other streams
   // (the split kernel holds a CU's whole register file while it runs): +1.5 % pairs/s in the overlapped step.
   static const int envNT = [] { const char *e = getenv("FB_POSE_NT"); const int v = e ? atoi(e) : -1; return v < 0 || v == 256 || v == 512 || v == 448 ? v : 0; }();
   const int regNT = envNT >= 0 ? envNT : (A->batch >= 64 ? 256 : 448);
+  const size_t flags = ((size_t)((A->front_stride + 15) & ~15)) + ((A->bird_stride + 15) & ~15);  // level bytes of pose_generic
   if (regNT) {
-    const size_t lds = regNT == 448 ? (size_t)NACC * (448 + 16) * sizeof(double) : (size_t)NACC * (regNT + regNT / 32) * sizeof(double);
-    const size_t flagBytes = ((size_t)((A->front_stride + 15) & ~15)) + ((A->bird_stride + 15) & ~15);
-    if (flagBytes <= lds && A->front_stride <= 65535 && A->bird_stride <= 65535) {
+    const size_t lds = regNT == 448 ? PoseRegsShape<512, 448>::LDS_BYTES : regNT == 512 ? PoseRegsShape<512, 512>::LDS_BYTES
+                                                                                         : PoseRegsShape<256, 256>::LDS_BYTES;
+    if (flags <= lds && A->front_stride <= 65535 && A->bird_stride <= 65535) {
       fb::ProfScope prof_(fb::P_POSE, fb::as_stream(stream));
-      if (regNT == 448) {  // 448 edge threads + the solver wave
-        FB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_pose_opt_split<512, 5, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        k_pose_opt_split<512, 5, 3><<<A->batch, 512, lds, fb::as_stream(stream)>>>(*A);
-      } else if (regNT == 512) {
-        FB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_pose_opt_reg<512, 5, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        k_pose_opt_reg<512, 5, 3><<<A->batch, 512, lds, fb::as_stream(stream)>>>(*A);
-      } else {
-        FB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_pose_opt_reg<256, 10, 6>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        k_pose_opt_reg<256, 10, 6><<<A->batch, 256, lds, fb::as_stream(stream)>>>(*A);
-      }
-      FB_HIP(hipGetLastError());
-      return FB_OK;
+      if (regNT == 448) return launch_pose_regs<512, 448, 5, 3>(*A, fb::as_stream(stream));
+      if (regNT == 512) return launch_pose_regs<512, 512, 5, 3>(*A, fb::as_stream(stream));
+      return launch_pose_regs<256, 256, 10, 6>(*A, fb::as_stream(stream));
     }
   }
-  const size_t flags = ((size_t)((A->front_stride + 15) & ~15)) + ((A->bird_stride + 15) & ~15);
   const size_t stagedBytes = ((size_t)A->front_stride * 6 + (size_t)A->bird_stride * 7) * 4;
   int staged = 1;
   size_t lds = stagedBytes + flags;
@@ -1353,10 +1057,7 @@ int fb_pose_gather_front_dev(int batch, int kp_stride, int mp_stride, const int3
   FB_TRY(fb::check_device());
   FB_ARG(batch >= 0 && kp_stride > 0 && inv_level_sigma2 && nlevels >= 1 && nlevels <= FB_MAX_LEVELS);
   if (batch == 0) return FB_OK;
-  GatherK G;
-  memset(&G, 0, sizeof(G));
-  G.nlevels = nlevels;
-  for (int i = 0; i < nlevels; i++) G.inv_sigma2[i] = inv_level_sigma2[i];
+  const GatherK G = make_gather_k(inv_level_sigma2, nlevels);
   fb::ProfScope prof_(fb::P_GATHER, fb::as_stream(stream));
   k_gather_front<<<dim3((kp_stride + 255) / 256, batch), 256, 0, fb::as_stream(stream)>>>(
       kp_stride, mp_stride, d_n, d_kps, d_match, d_mp_xw, G, d_front_xw, d_front_obs, d_front_inv_sigma2, d_front_valid);
@@ -1371,10 +1072,7 @@ int fb_pose_gather_bird_dev(int batch, int kp_stride, int mp_stride, const int32
   FB_TRY(fb::check_device());
   FB_ARG(batch >= 0 && kp_stride > 0 && inv_level_sigma2 && nlevels >= 1 && nlevels <= FB_MAX_LEVELS);
   if (batch == 0) return FB_OK;
-  GatherK G;
-  memset(&G, 0, sizeof(G));
-  G.nlevels = nlevels;
-  for (int i = 0; i < nlevels; i++) G.inv_sigma2[i] = inv_level_sigma2[i];
+  const GatherK G = make_gather_k(inv_level_sigma2, nlevels);
   fb::ProfScope prof_(fb::P_GATHER, fb::as_stream(stream));
   k_gather_bird<<<dim3((kp_stride + 255) / 256, batch), 256, 0, fb::as_stream(stream)>>>(
       kp_stride, mp_stride, d_n, d_kps, d_cam_xyz, d_match, d_mpb_xw, G, d_bird_xw, d_bird_xc, d_bird_inv_sigma2, d_bird_valid);

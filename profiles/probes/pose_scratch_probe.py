@@ -1,4 +1,4 @@
-"""Does k_pose_opt_reg (768 B of scratch per lane) slow down on a queue whose first kernels needed little scratch?"""
+"""Does k_pose_opt_reg (768 B of scratch per lane then; today k_pose_opt_regs<512, 512>) slow down on a queue whose first kernels needed little scratch?"""
 import os, sys, ctypes as C
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 sys.path.insert(0, '.')

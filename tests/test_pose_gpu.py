@@ -91,19 +91,20 @@ def test_pose_opt_noise_free_recovers_pose():
 
 @pytest.mark.parametrize("variant", ["512", "256", "0"])
 def test_pose_opt_other_kernel_variants(variant):
-    """The default is k_pose_opt_split; FB_POSE_NT selects k_pose_opt_reg with 512 / 256 threads or the LDS-staged kernel
-    (read once per process, hence a child process; the children run one after the other).  Same parity bar for each."""
+    """The default is k_pose_opt_regs<512, 448> (448 edge threads + a solver wave); FB_POSE_NT selects its one-role
+    instantiations with 512 / 256 threads or the LDS-staged kernel (read once per process, hence a child process; the
+    children run one after the other).  Same parity bar for each."""
     import os, subprocess, sys
     env = dict(os.environ, FB_POSE_NT=variant)
     here = os.path.dirname(os.path.abspath(__file__))
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(here, "test_pose_gpu.py"), "-q", "-x", "-m", "gpu",
-                        "-k", "config3 or weights_and_masks", "-p", "no:cacheprovider"],
+                        "-k", "config3 or weights_and_masks or register_slot_boundary", "-p", "no:cacheprovider"],
                        env=env, cwd=os.path.dirname(here), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
 
 
 def test_pose_opt_batch_of_64_takes_the_throughput_kernel():
-    """Batches of 64 frames or more run k_pose_opt_reg<256> (it shares its CUs with other streams' kernels); same bar."""
+    """Batches of 64 frames or more run k_pose_opt_regs<256, 256> (it shares its CUs with other streams' kernels); same bar."""
     probs = [synth.make_pose_problem(3300 + i, n_front=260 + 7 * (i % 9), n_bird=120 + 5 * (i % 7)) for i in range(64)]
     out_o, out_h = _run(probs, mode=cabi.FB_POSE_FRONT_BIRD)
     _compare(out_o, out_h, cabi.FB_POSE_FRONT_BIRD)
@@ -111,11 +112,39 @@ def test_pose_opt_batch_of_64_takes_the_throughput_kernel():
 
 @pytest.mark.parametrize("batch", [2, 64])
 def test_pose_opt_more_edges_than_register_slots(batch):
-    """Frames with more edges than the register kernels hold (2240 + 1344 in k_pose_opt_split, 2560 + 1536 in
-    k_pose_opt_reg<256>) leave through the in-kernel generic schedule (edges re-read from HBM); e.g. the 4000-feature
+    """Frames with more edges than the register kernels hold (2240 + 1344 in k_pose_opt_regs<512, 448>, 2560 + 1536 in
+    k_pose_opt_regs<256, 256>) leave through the in-kernel generic schedule (edges re-read from HBM); e.g. the 4000-feature
     initialisation extractor.  A batch of 64 mixes them with ordinary frames."""
     big = [synth.make_pose_problem(3400, n_front=3100, n_bird=300), synth.make_pose_problem(3401, n_front=900, n_bird=1700)]
     small = [synth.make_pose_problem(3410 + i, n_front=200 + 11 * (i % 5), n_bird=90 + 3 * (i % 4)) for i in range(batch - 2)]
     probs = small[: len(small) // 2] + [big[0]] + small[len(small) // 2:] + [big[1]]
     out_o, out_h = _run(probs, mode=cabi.FB_POSE_FRONT_BIRD)
     _compare(out_o, out_h, cabi.FB_POSE_FRONT_BIRD)
+
+
+def _spread_valid(n, n_invalid):
+    """n slots of which n_invalid, spread evenly over the whole range, hold no edge."""
+    v = np.ones(n, np.uint8)
+    v[np.round(np.linspace(0, n - 1, n_invalid)).astype(np.int64)] = 0
+    assert int(v.sum()) == n - n_invalid
+    return v
+
+
+def test_pose_opt_register_slot_boundary():
+    """On the capacity of the register slots (EF * NE front, EB * NE bird valid edges): a frame that fills the last slot, one
+    more front / one more bird edge (the in-kernel way out to the generic schedule), and frames whose valid edges are
+    exactly / one beyond the capacity among slot indices that run 360 past it (compaction, outlier flags written back
+    through the slot index)."""
+    import os
+    F, B = (2560, 1536) if os.environ.get("FB_POSE_NT") in ("256", "512") else (2240, 1344)
+    shapes = [(F, B), (F + 1, 300), (900, B + 1), (F + 360, 500), (F + 360, 500)]
+    probs = [synth.make_pose_problem(3500 + i, n_front=nf, n_bird=nb) for i, (nf, nb) in enumerate(shapes)]
+    fv = [np.ones(nf, np.uint8) for nf, _ in shapes[:3]] + [_spread_valid(F + 360, 360), _spread_valid(F + 360, 359)]
+    out_o, out_h = _run(probs, mode=cabi.FB_POSE_FRONT_BIRD, front_valid=fv)
+    _compare(out_o, out_h, cabi.FB_POSE_FRONT_BIRD)
+    for b in range(5):
+        n = len(fv[b])
+        # the front masks compared are not trivial (the generator's bird noise never reaches the bird threshold), and slots
+        # without an edge keep the prefill value
+        assert 0 < np.count_nonzero(out_o["front_outlier"][b, :n][fv[b] == 1]) < n
+        assert np.all(out_h["front_outlier"][b, :n][fv[b] == 0] == 9)
