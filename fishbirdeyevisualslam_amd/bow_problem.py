@@ -51,6 +51,24 @@ def make_bow_problem(seed, n_kf=1500, n_f=1500, share_prefix=True):
     return dict(kf_kps=kf, kf_desc=kd, kf_has_mp=(g.random(n_kf) < 0.6).astype(np.uint8), f_kps=f, f_desc=fd)
 
 
+def make_contended_bow_problem(seed, n_q, n_t):
+    """make_bow_problem with the roles swapped: the n_q query (key-frame side) features are noisy copies of the n_t candidate
+    features, so some 0.7 * n_q / n_t queries want each candidate and all but the first of them find it taken."""
+    p = make_bow_problem(seed, n_t, n_q)
+    g = synth.rng(seed + 3)
+    return dict(kf_kps=p["f_kps"], kf_desc=p["f_desc"], kf_has_mp=(g.random(n_q) < 0.6).astype(np.uint8),
+                f_kps=p["kf_kps"], f_desc=p["kf_desc"])
+
+
+def queries_kept_in_registers():
+    """k_match_bow_t keeps the per-query data of up to QPT * BOW_THREADS queries in registers and re-derives it every round
+    for more: two paths through the claim rounds, and a test of them needs a query count on either side."""
+    import os
+    import re
+    src = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "match_bow.hip")).read()
+    return int(re.search(r"constexpr int QPT = (\d+);", src).group(1)) * int(re.search(r"constexpr int BOW_THREADS = (\d+);", src).group(1))
+
+
 def bow_args(problems, nnratio=0.7, check_ori=1):
     B = len(problems)
     ks = max(len(p["kf_kps"]) for p in problems)

@@ -1,8 +1,11 @@
 /*
  * fb_rot_hist.h -- the matchers' rotation-consistency filter (ORBmatcher.cc: rotHist, ComputeThreeMaxima): every accepted
  * match votes for the bin of its angle difference, and matches outside the three most voted bins are dropped.
- * The loops that vote and drop stay in the kernels (they differ in what they index and in the reference's quirks);
- * this header owns the histogram, the bin arithmetic and the choice of the three bins.
+ * This header owns the histogram, the bin arithmetic and the choice of the three bins.  The loops that vote and drop:
+ * k_proj_frame, k_proj_kf and k_match_bow_t vote once per committed match and drop by query, the same loop in all three,
+ * which is fb::commit_matches (fb_claims.h).  k_birdview (votes for matches that failed the ratio test), k_init_match
+ * (votes for every acceptance, keeps only the last one per target) and k_match_triangulation (bins indexed by the KF1
+ * feature, no claim rounds) carry quirks of the reference and keep their own.
  */
 #ifndef FB_ROT_HIST_H_
 #define FB_ROT_HIST_H_

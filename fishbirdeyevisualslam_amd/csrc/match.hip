@@ -16,15 +16,15 @@
 // candidates with v_bcnt_u32_b32.  HBM traffic per problem is therefore the algorithmic
 // minimum (each input byte read once, each output written once).
 //
-// Serial semantics: M2/M3 skip a candidate that an EARLIER query already took (with a map
-// point that has observations).  That dependency is resolved by a fixed-point iteration:
-// every round all queries re-pick their best candidate given the previous round's claims
-// ("owner[c] = smallest claiming query index"); query q only honours claims of q' < q.
-// By induction on q the iteration converges to exactly the serial result (query 0 is final
-// after round 0, query q after at most round q); in practice 2-3 rounds.
+// Serial semantics: M2/M3/M4 skip a candidate that an EARLIER query already took (M2/M3: with a map
+// point that has observations).  That dependency is resolved by the fixed-point iteration of
+// fb_claims.h (fb::Claims: the rounds, the owner / assign arrays and their barriers; fb::commit_matches:
+// assign array -> match array, count and rotation filter).  A kernel here only writes its own query loop
+// between begin_round() and end_round().
 #include "fb_common.h"
 
 #include <type_traits>
+#include "fb_claims.h"
 #include "fb_frame_geom.h"
 #include "fb_primitives.h"
 #include "fb_rot_hist.h"
@@ -43,6 +43,7 @@ struct TargetLds {  // target frame staged in LDS
   const uint16_t *cs;    // [ncell+1]
   const uint32_t *items; // [n] key point index | octave << 16 in cell order: the level test of a walk needs no second load
   uint32_t descLds;      // LDS byte address of the descriptor table, or DESC_NOT_IN_LDS (then `desc` points into HBM / L2)
+  uint8_t *rest;         // first LDS byte after the staged frame (16-B aligned): the kernel's own arrays
 };
 constexpr uint32_t DESC_NOT_IN_LDS = 0xFFFFFFFFu;
 
@@ -193,8 +194,17 @@ __device__ __forceinline__ TargetLds stage_target(uint8_t *smem, const Carve &cv
     litems[i] = (uint32_t)idx | ((uint32_t)(kps[idx].octave & 0xff) << 16);
   }
   TargetLds T{withDesc ? reinterpret_cast<const uint4 *>(ldesc) : src, lxy, cv.hasOct ? loct : nullptr, lcs, litems,
-              withDesc ? (uint32_t)(uintptr_t)ldesc : DESC_NOT_IN_LDS};
+              withDesc ? (uint32_t)(uintptr_t)ldesc : DESC_NOT_IN_LDS, smem + cv.end};
   return T;
+}
+
+// the staged target of the argument structs that call it cur_* (frame b of the batch)
+template <typename Args>
+__device__ __forceinline__ TargetLds stage_cur(uint8_t *smem, const Args &A, int b, bool descInLds, bool withOct = true) {
+  const int ncell = A.grid.cols * A.grid.rows;
+  const size_t co = (size_t)b * A.cur_stride;
+  return stage_target(smem, Carve(A.cur_stride, ncell, descInLds, withOct), A.n_cur[b], ncell, A.cur_kps + co, A.cur_desc + co * 32,
+                      A.cur_cell_start + (size_t)b * (ncell + 1), A.cur_cell_items + co, descInLds);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -225,28 +235,23 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_proj_frame(fb_proj_frame_args
   // (its callbacks never ask for a target key point's octave by index: no by-index octave array in LDS, Carve::withOct = false)
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   typedef unsigned short u16;
-  constexpr int NONE16 = 0xFFFF;
   const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
-  const int ncell = A.grid.cols * A.grid.rows;
   const size_t co = (size_t)b * A.cur_stride, lo = (size_t)b * A.last_stride;
   const int ncur = A.n_cur[b], nlast = A.n_last[b];
   M3_T0()
-  const Carve cv(A.cur_stride, ncell, descInLds != 0, false);
-  const TargetLds T = stage_target(smem, cv, ncur, ncell, A.cur_kps + co, A.cur_desc + co * 32,
-                                   A.cur_cell_start + (size_t)b * (ncell + 1), A.cur_cell_items + co, descInLds != 0);
-  int *ownerA = reinterpret_cast<int *>(smem + cv.end);  // [cur_stride]
-  int *ownerB = ownerA + A.cur_stride;                   // [cur_stride]
-  uint32_t *cache = reinterpret_cast<uint32_t *>(ownerB + A.cur_stride);  // [last_stride][cacheK]  dist << 16 | idx
-  u16 *assignA = reinterpret_cast<u16 *>(cache + (size_t)A.last_stride * cacheK);  // [last_stride]
-  u16 *assignB = assignA + A.last_stride;                // [last_stride]
-  u16 *perm = assignB + A.last_stride;                   // [last_stride] queries sorted by octave (processing order)
+  const TargetLds T = stage_cur(smem, A, b, descInLds != 0, false);
+  int *owners = reinterpret_cast<int *>(T.rest);         // [2][cur_stride]
+  uint32_t *cache = reinterpret_cast<uint32_t *>(owners + 2 * A.cur_stride);  // [last_stride][cacheK]  dist << 16 | idx
+  u16 *assigns = reinterpret_cast<u16 *>(cache + (size_t)A.last_stride * cacheK);  // [2][last_stride]
+  u16 *perm = assigns + 2 * A.last_stride;               // [last_stride] queries sorted by octave (processing order)
   uint8_t *meta = reinterpret_cast<uint8_t *>(perm + A.last_stride);  // [last_stride] cached count | complete << 7
-  __shared__ int s_changed, s_n, s_oct[FB_MAX_LEVELS + 1];
+  __shared__ fb::ClaimFlags s_cf;
+  __shared__ int s_oct[FB_MAX_LEVELS + 1];
   __shared__ fb::RotHist s_rot;
   __shared__ float s_T[12];
   if (tid < 12) s_T[tid] = A.cur_Tcw[(size_t)b * 12 + tid];
   if (tid <= FB_MAX_LEVELS) s_oct[tid] = 0;
-  const uint8_t *blocked0 = A.cur_blocked ? A.cur_blocked + co : nullptr;
+  fb::Claims<u16> C(s_cf, owners, A.cur_stride, assigns, A.last_stride, A.cur_blocked ? A.cur_blocked + co : nullptr, ncur, nlast);
   float thEff = A.th;   // the second attempt (retry_below > 0 and fewer matches than that) searches with retry_th
   __syncthreads();
   M3_TICK(0)
@@ -267,11 +272,10 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_proj_frame(fb_proj_frame_args
   __syncthreads();
   M3_TICK(1)
 
-  // full grid walk of query q against the claims in `owner`; fill = also (re)build the query's cache
-  // fill = also (re)build the query's cache.  The callback only APPENDS the eligible candidates (distance
+  // full grid walk of query q against last round's claims; fill = also (re)build the query's cache.  The callback only APPENDS the eligible candidates (distance
   // <= TH_HIGH, walk order) to eight registers; the stable top-K selection runs after the walk, once, in straight-line code.
   // More than eight eligible candidates: the cache is left empty and incomplete, i.e. later rounds walk again.
-  auto full_search = [&](int q, const int *owner, const bool fill) -> int {
+  auto full_search = [&](int q, const bool fill) -> int {
     int best = NONE;
     uint32_t e0 = 0xFFFFFFFFu, e1 = e0, e2 = e0, e3 = e0, e4 = e0, e5 = e0, e6 = e0, e7 = e0;  // newest in e0
     int nElig = 0;
@@ -288,13 +292,11 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_proj_frame(fb_proj_frame_args
           const int oct = A.last_octave[lo + q];
           const float radius = thEff * A.scale_factors[oct];
           uint32_t d[8];
-          const uint4 *dq = reinterpret_cast<const uint4 *>(A.last_desc + (lo + q) * 32);
-          const uint4 d0 = dq[0], d1 = dq[1];
-          d[0] = d0.x; d[1] = d0.y; d[2] = d0.z; d[3] = d0.w; d[4] = d1.x; d[5] = d1.y; d[6] = d1.z; d[7] = d1.w;
+          fb::load_desc(A.last_desc + (lo + q) * 32, d);
           int bestDist = 256;
           for_area<false>(A.grid, T, u, v, radius, oct - 1, oct + 1, [&](int i2) {
-            const int own = owner[i2];
-            if (own == -1) return;      // occupied on entry: never a candidate
+            const int own = C.owner(i2);
+            if (own == C.BLOCKED) return;  // occupied on entry: never a candidate
             const int dist = target_hamming(T, d, i2);
             if (fill && dist <= TH_HIGH) {
               nElig++;
@@ -340,13 +342,9 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_proj_frame(fb_proj_frame_args
   // Tracking.cc:1339-1349 in one launch: nmatches = SearchByProjection(th); if (nmatches < 20) { fill(mvpMapPoints, NULL);
   // nmatches = SearchByProjection(2 * th); } -- the second search starts from scratch on the staged frame
   for (int attempt = 0; attempt < 2; attempt++) {
-  for (int i = tid; i < ncur; i += nt) ownerA[i] = (blocked0 && blocked0[i]) ? -1 : NONE;
-  for (int q = tid; q < nlast; q += nt) assignA[q] = NONE16;
-  __syncthreads();
-  for (int round = 0; round <= nlast + 1; round++) {
-    for (int i = tid; i < ncur; i += nt) ownerB[i] = (blocked0 && blocked0[i]) ? -1 : NONE;
-    if (tid == 0) s_changed = 0;
-    __syncthreads();
+  C.start();
+  for (int round = 0; C.more(round); round++) {
+    C.begin_round();
     for (int pq = tid; pq < nlast; pq += nt) {
       const int q = perm[pq];
       int best = NONE;
@@ -356,68 +354,31 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_proj_frame(fb_proj_frame_args
         const int m = meta[q], n = m & 0x7f;
         for (int k = 0; k < n; k++) {
           const int i2 = (int)(cache[(size_t)q * cacheK + k] & 0xFFFFu);
-          if (!(ownerA[i2] < q)) { best = i2; break; }
+          if (!C.taken(i2, q)) { best = i2; break; }
         }
         walk = best == NONE && !(m & 0x80);
       }
-      if (walk) best = full_search(q, ownerA, fillNow);   // ONE call site: one copy of the walk and its callbacks in the kernel
-      const int best16 = best == NONE ? NONE16 : best;
-      assignB[q] = (u16)best16;
-      if (best16 != assignA[q]) s_changed = 1;
-      if (best != NONE && A.last_obs_pos[lo + q]) atomicMin(&ownerB[best], q);
+      if (walk) best = full_search(q, fillNow);   // ONE call site: one copy of the walk and its callbacks in the kernel
+      C.submit(q, best, best != NONE && A.last_obs_pos[lo + q]);
     }
-    __syncthreads();
-    const int changed = s_changed;
-    int *t = ownerA; ownerA = ownerB; ownerB = t;
-    u16 *t16 = assignA; assignA = assignB; assignB = t16;
-    __syncthreads();
+    const bool done = C.end_round();
     if (round == 0) { M3_TICK(2) } else { M3_TICK(3) }
     M3_COUNT(5)
-    if (!changed) break;
+    if (done) break;
   }
 
   // commit: last writer wins; rotation histogram culling (ORBmatcher.cc:1446-1468)
-  int *matchL = ownerB;  // reuse
-  u16 *binQ = assignB;   // reuse: histogram bin of each accepted query
-  for (int i = tid; i < ncur; i += nt) matchL[i] = -1;
-  s_rot.clear();
-  if (tid == 0) s_n = 0;
-  __syncthreads();
-  const bool ori = A.matcher.check_orientation != 0;
-  for (int q = tid; q < nlast; q += nt) {
-    const int c = assignA[q];
-    if (c == NONE16) continue;
-    atomicMax(&matchL[c], q);
-    atomicAdd(&s_n, 1);
-    if (ori) {
-      const int bin = rot_bin(A.last_angle[lo + q] - A.cur_kps[co + c].angle);
-      s_rot.add(bin);
-      binQ[q] = (u16)bin;
-    }
-  }
-  __syncthreads();
-  if (ori) {
-    s_rot.pick();
-    for (int q = tid; q < nlast; q += nt) {
-      const int c = assignA[q];
-      if (c == NONE16) continue;
-      const int bin = binQ[q];
-      if (!s_rot.keeps(bin)) {
-        matchL[c] = -1;
-        atomicSub(&s_n, 1);
-      }
-    }
-    __syncthreads();
-  }
-  __syncthreads();
-  if (attempt == 0 && A.retry_below > 0 && s_n < A.retry_below) {  // (workgroup-uniform)
+  const int *matchL = fb::commit_matches<true>(C, fb::QueryIndex(), &s_rot, A.matcher.check_orientation != 0,
+                                               [&](int q, int c) { return A.last_angle[lo + q] - A.cur_kps[co + c].angle; });
+  if (attempt == 0 && A.retry_below > 0 && s_cf.n < A.retry_below) {  // (workgroup-uniform)
     thEff = A.retry_th;
-    // matchL / binQ alias ownerB / assignB: which of the two buffers holds what is irrelevant for a search from scratch
+    // matchL and the bins alias C.ownerB / C.assignB: which of the two buffers holds what is irrelevant for a search from
+    // scratch (C.start() refills both A buffers, begin_round() the B owners)
     __syncthreads();
     continue;
   }
   for (int i = tid; i < ncur; i += nt) A.match_cur_to_last[co + i] = matchL[i];
-  if (tid == 0) { A.nmatches[b] = s_n; if (A.retried) A.retried[b] = attempt; }
+  if (tid == 0) { A.nmatches[b] = s_cf.n; if (A.retried) A.retried[b] = attempt; }
   break;
   }
   M3_TICK(4)
@@ -431,28 +392,18 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_proj_frame(fb_proj_frame_args
 // ---------------------------------------------------------------------------------------
 __global__ __launch_bounds__(MATCH_THREADS) void k_proj_kf(fb_proj_kf_args A, int descInLds) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  typedef unsigned short u16;
-  constexpr int NONE16 = 0xFFFF;
   const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
-  const int ncell = A.grid.cols * A.grid.rows;
   const size_t co = (size_t)b * A.cur_stride, ko = (size_t)b * A.kf_stride;
   const int ncur = A.n_cur[b], nkf = A.n_kf[b];
-  const Carve cv(A.cur_stride, ncell, descInLds != 0);
-  const TargetLds T = stage_target(smem, cv, ncur, ncell, A.cur_kps + co, A.cur_desc + co * 32,
-                                   A.cur_cell_start + (size_t)b * (ncell + 1), A.cur_cell_items + co, descInLds != 0);
-  int *ownerA = reinterpret_cast<int *>(smem + cv.end);  // [cur_stride]
-  int *ownerB = ownerA + A.cur_stride;                   // [cur_stride]
-  u16 *assignA = reinterpret_cast<u16 *>(ownerB + A.cur_stride);  // [kf_stride] chosen slot or NONE16
-  u16 *assignB = assignA + A.kf_stride;                  // [kf_stride]
-  __shared__ int s_changed, s_n;
+  const TargetLds T = stage_cur(smem, A, b, descInLds != 0);
+  __shared__ fb::ClaimFlags s_cf;
   __shared__ fb::RotHist s_rot;
   __shared__ float s_T[12], s_Ow[3];
   if (tid < 12) s_T[tid] = A.cur_Tcw[(size_t)b * 12 + tid];
   if (tid == 64) fb::camera_centre(A.cur_Tcw + (size_t)b * 12, s_Ow);
-  const uint8_t *blocked0 = A.cur_blocked ? A.cur_blocked + co : nullptr;
-  for (int i = tid; i < ncur; i += nt) ownerA[i] = (blocked0 && blocked0[i]) ? -1 : NONE;
-  for (int q = tid; q < nkf; q += nt) assignA[q] = NONE16;
-  __syncthreads();
+  // owners [2][cur_stride] ints, then the chosen slot of each point [2][kf_stride] in 16 bits
+  fb::Claims<uint16_t> C(s_cf, T.rest, A.cur_stride, A.kf_stride, A.cur_blocked ? A.cur_blocked + co : nullptr, ncur, nkf);
+  C.start();
 
   // the geometric gates are cheap and are re-evaluated every round instead of being stored per point
   auto gate = [&](int q, float &u, float &v) -> int {
@@ -470,10 +421,8 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_proj_kf(fb_proj_kf_args A, in
     return fb::predict_scale(maxD, dist3D, A.log_scale_factor, A.n_levels);
   };
 
-  for (int round = 0; round <= nkf + 1; round++) {
-    for (int i = tid; i < ncur; i += nt) ownerB[i] = (blocked0 && blocked0[i]) ? -1 : NONE;
-    if (tid == 0) s_changed = 0;
-    __syncthreads();
+  for (int round = 0; C.more(round); round++) {
+    C.begin_round();
     for (int q = tid; q < nkf; q += nt) {
       int best = NONE;
       float u, v;
@@ -481,148 +430,90 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_proj_kf(fb_proj_kf_args A, in
       if (lvl >= 0) {
         const float radius = A.th * A.scale_factors[lvl];
         uint32_t d[8];
-        const uint4 *dq = reinterpret_cast<const uint4 *>(A.kf_desc + (ko + q) * 32);
-        const uint4 d0 = dq[0], d1 = dq[1];
-        d[0] = d0.x; d[1] = d0.y; d[2] = d0.z; d[3] = d0.w; d[4] = d1.x; d[5] = d1.y; d[6] = d1.z; d[7] = d1.w;
+        fb::load_desc(A.kf_desc + (ko + q) * 32, d);
         int bestDist = 256;
         for_area<false>(A.grid, T, u, v, radius, lvl - 1, lvl + 1, [&](int i2) {
-          if (ownerA[i2] < q) return;
+          if (C.taken(i2, q)) return;
           const int dist = target_hamming(T, d, i2);
           if (dist < bestDist) { bestDist = dist; best = i2; }
         });
         if (bestDist > A.orb_dist) best = NONE;
       }
-      const int best16 = best == NONE ? NONE16 : best;
-      assignB[q] = (u16)best16;
-      if (best16 != assignA[q]) s_changed = 1;
-      if (best != NONE) atomicMin(&ownerB[best], q);
+      C.submit(q, best);
     }
-    __syncthreads();
-    const int changed = s_changed;
-    int *t = ownerA; ownerA = ownerB; ownerB = t;
-    u16 *t16 = assignA; assignA = assignB; assignB = t16;
-    __syncthreads();
-    if (!changed) break;
+    if (C.end_round()) break;
   }
-
-  int *matchL = ownerB;
-  u16 *binQ = assignB;
-  for (int i = tid; i < ncur; i += nt) matchL[i] = -1;
-  s_rot.clear();
-  if (tid == 0) s_n = 0;
-  __syncthreads();
-  const bool ori = A.matcher.check_orientation != 0;
-  for (int q = tid; q < nkf; q += nt) {
-    const int c = assignA[q];
-    if (c == NONE16) continue;
-    matchL[c] = q;  // a claimed slot blocks every later point: one claimer per slot
-    atomicAdd(&s_n, 1);
-    if (ori) {
-      const int bin = rot_bin(A.kf_angle[ko + q] - A.cur_kps[co + c].angle);
-      s_rot.add(bin);
-      binQ[q] = (u16)bin;
-    }
-  }
-  __syncthreads();
-  if (ori) {
-    s_rot.pick();
-    for (int q = tid; q < nkf; q += nt) {
-      const int c = assignA[q];
-      if (c == NONE16) continue;
-      const int bin = binQ[q];
-      if (!s_rot.keeps(bin)) {
-        matchL[c] = -1;
-        atomicSub(&s_n, 1);
-      }
-    }
-    __syncthreads();
-  }
+  // a claimed slot blocks every later point: one claimer per slot
+  const int *matchL = fb::commit_matches<false>(C, fb::QueryIndex(), &s_rot, A.matcher.check_orientation != 0,
+                                                [&](int q, int c) { return A.kf_angle[ko + q] - A.cur_kps[co + c].angle; });
   for (int i = tid; i < ncur; i += nt) A.match_cur_to_kf[co + i] = matchL[i];
-  if (tid == 0) A.nmatches[b] = s_n;
+  if (tid == 0) A.nmatches[b] = s_cf.n;
 }
 
 // ---------------------------------------------------------------------------------------
 // M2  SearchByProjection(Frame&, const vector<MapPoint*>&, th)
 // ---------------------------------------------------------------------------------------
+__device__ __forceinline__ float m2_radius(const fb_proj_points_args &A, size_t e, bool bFactor, int lvl) {
+  float r = A.mp_view_cos[e] > 0.998 ? 2.5f : 4.0f;  // RadiusByViewingCos
+  if (bFactor) r *= A.th;
+  return r * A.scale_factors[lvl];
+}
+
+// The M2 decision (ORBmatcher.cc:85-127): best and second-best admissible candidate in walk order, then TH_HIGH and, when
+// both sit on the same level, the ratio test.
+struct M2Pick {
+  int bestDist = 256, bestLevel = -1, bestDist2 = 256, bestLevel2 = -1, bestIdx = -1;
+  __device__ __forceinline__ void take(int idx, int dist, int lev) {
+    if (dist < bestDist) { bestDist2 = bestDist; bestDist = dist; bestLevel2 = bestLevel; bestLevel = lev; bestIdx = idx; }
+    else if (dist < bestDist2) { bestLevel2 = lev; bestDist2 = dist; }
+  }
+  __device__ __forceinline__ int result(float nnratio) const {
+    return (bestDist <= TH_HIGH && !(bestLevel == bestLevel2 && bestDist > nnratio * bestDist2)) ? bestIdx : NONE;
+  }
+};
+
 #ifdef FB_MATCH_STAMPS
 __device__ int g_m2_rounds[4];  // probe build only: rounds / queries in view / launches of k_proj_points (block 0)
 #endif
 __global__ __launch_bounds__(MATCH_THREADS) void k_proj_points(fb_proj_points_args A, int descInLds) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
-  const int ncell = A.grid.cols * A.grid.rows;
   const size_t co = (size_t)b * A.cur_stride, mo = (size_t)b * A.mp_stride;
   const int ncur = A.n_cur[b], nmp = A.n_mp[b];
-  const Carve cv(A.cur_stride, ncell, descInLds != 0);
-  const TargetLds T = stage_target(smem, cv, ncur, ncell, A.cur_kps + co, A.cur_desc + co * 32,
-                                   A.cur_cell_start + (size_t)b * (ncell + 1), A.cur_cell_items + co, descInLds != 0);
-  int *ownerA = reinterpret_cast<int *>(smem + cv.end);
-  int *ownerB = ownerA + A.cur_stride;
-  int *assignA = ownerB + A.cur_stride;
-  int *assignB = assignA + A.mp_stride;
-  __shared__ int s_changed, s_n;
-  const uint8_t *blocked0 = A.cur_blocked ? A.cur_blocked + co : nullptr;
-  for (int i = tid; i < ncur; i += nt) ownerA[i] = (blocked0 && blocked0[i]) ? -1 : NONE;
-  for (int q = tid; q < nmp; q += nt) assignA[q] = NONE;
+  const TargetLds T = stage_cur(smem, A, b, descInLds != 0);
+  __shared__ fb::ClaimFlags s_cf;
+  fb::Claims<int> C(s_cf, T.rest, A.cur_stride, A.mp_stride, A.cur_blocked ? A.cur_blocked + co : nullptr, ncur, nmp);
+  C.start();
   const bool bFactor = A.th != 1.0f;
-  __syncthreads();
-  for (int round = 0; round <= nmp + 1; round++) {
-    for (int i = tid; i < ncur; i += nt) ownerB[i] = (blocked0 && blocked0[i]) ? -1 : NONE;
-    if (tid == 0) s_changed = 0;
-    __syncthreads();
+  for (int round = 0; C.more(round); round++) {
+    C.begin_round();
     for (int q = tid; q < nmp; q += nt) {
       int best = NONE;
       if (A.mp_track[mo + q]) {
         const int lvl = A.mp_level[mo + q];
-        float r = A.mp_view_cos[mo + q] > 0.998 ? 2.5f : 4.0f;  // RadiusByViewingCos
-        if (bFactor) r *= A.th;
         uint32_t d[8];
-        const uint4 *dq = reinterpret_cast<const uint4 *>(A.mp_desc + (mo + q) * 32);
-        const uint4 d0 = dq[0], d1 = dq[1];
-        d[0] = d0.x; d[1] = d0.y; d[2] = d0.z; d[3] = d0.w; d[4] = d1.x; d[5] = d1.y; d[6] = d1.z; d[7] = d1.w;
-        int bestDist = 256, bestLevel = -1, bestDist2 = 256, bestLevel2 = -1, bestIdx = -1;
-        for_area<false>(A.grid, T, A.mp_proj[(mo + q) * 2], A.mp_proj[(mo + q) * 2 + 1], r * A.scale_factors[lvl],
+        fb::load_desc(A.mp_desc + (mo + q) * 32, d);
+        M2Pick pick;
+        for_area<false>(A.grid, T, A.mp_proj[(mo + q) * 2], A.mp_proj[(mo + q) * 2 + 1], m2_radius(A, mo + q, bFactor, lvl),
                         lvl - 1, lvl, [&](int idx) {
-          if (ownerA[idx] < q) return;
-          const int dist = target_hamming(T, d, idx);
-          if (dist < bestDist) {
-            bestDist2 = bestDist; bestDist = dist; bestLevel2 = bestLevel; bestLevel = T.oct[idx]; bestIdx = idx;
-          } else if (dist < bestDist2) {
-            bestLevel2 = T.oct[idx]; bestDist2 = dist;
-          }
+          if (!C.taken(idx, q)) pick.take(idx, target_hamming(T, d, idx), (int)T.oct[idx]);
         });
-        if (bestDist <= TH_HIGH && !(bestLevel == bestLevel2 && bestDist > A.matcher.nnratio * bestDist2)) best = bestIdx;
+        best = pick.result(A.matcher.nnratio);
       }
-      assignB[q] = best;
-      if (best != assignA[q]) s_changed = 1;
-      if (best != NONE && A.mp_obs_pos[mo + q]) atomicMin(&ownerB[best], q);
+      C.submit(q, best, best != NONE && A.mp_obs_pos[mo + q]);
     }
-    __syncthreads();
-    const int changed = s_changed;
-    int *t = ownerA; ownerA = ownerB; ownerB = t;
-    t = assignA; assignA = assignB; assignB = t;
-    __syncthreads();
+    const bool done = C.end_round();
 #ifdef FB_MATCH_STAMPS
     if (b == 0 && tid == 0) atomicAdd(&g_m2_rounds[0], 1);
 #endif
-    if (!changed) break;
+    if (done) break;
   }
 #ifdef FB_MATCH_STAMPS
   if (b == 0 && tid == 0) { atomicAdd(&g_m2_rounds[2], 1); int c = 0; for (int q = 0; q < nmp; q++) c += A.mp_track[mo + q]; atomicAdd(&g_m2_rounds[1], c); }
 #endif
-  int *matchL = ownerB;
-  for (int i = tid; i < ncur; i += nt) matchL[i] = -1;
-  if (tid == 0) s_n = 0;
-  __syncthreads();
-  for (int q = tid; q < nmp; q += nt) {
-    const int c = assignA[q];
-    if (c == NONE) continue;
-    atomicMax(&matchL[c], q);
-    atomicAdd(&s_n, 1);
-  }
-  __syncthreads();
+  const int *matchL = fb::commit_matches<true>(C, fb::QueryIndex());  // last writer wins
   for (int i = tid; i < ncur; i += nt) A.match_cur_to_mp[co + i] = matchL[i];
-  if (tid == 0) A.nmatches[b] = s_n;
+  if (tid == 0) A.nmatches[b] = s_cf.n;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -636,28 +527,13 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_proj_points(fb_proj_points_ar
 // ---------------------------------------------------------------------------------------
 constexpr int M2_K = 8, M2_OVER = 255, M2_CAND_THREADS = 256;
 
-struct GridLds { const float2 *xy; const uint8_t *oct; const uint16_t *cs; const uint16_t *items; };
-__device__ __forceinline__ TargetLds stage_grid_only(uint8_t *smem, const Carve &cv, int n, int ncell, const fb_keypoint *kps,
-                                                     const uint8_t *desc, const int32_t *cs, const int32_t *items) {
-  return stage_target(smem, cv, n, ncell, kps, desc, cs, items, false);
-}
-
-__device__ __forceinline__ float m2_radius(const fb_proj_points_args &A, size_t e, bool bFactor, int lvl) {
-  float r = A.mp_view_cos[e] > 0.998 ? 2.5f : 4.0f;  // RadiusByViewingCos
-  if (bFactor) r *= A.th;
-  return r * A.scale_factors[lvl];
-}
-
 __global__ __launch_bounds__(M2_CAND_THREADS) void k_m2_candidates(fb_proj_points_args A, uint32_t *cand, uint8_t *ncand) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int b = blockIdx.y, tid = threadIdx.x;
-  const int ncell = A.grid.cols * A.grid.rows;
-  const size_t co = (size_t)b * A.cur_stride, mo = (size_t)b * A.mp_stride;
-  const int ncur = A.n_cur[b], nmp = A.n_mp[b];
+  const size_t mo = (size_t)b * A.mp_stride;
+  const int nmp = A.n_mp[b];
   if ((int)(blockIdx.x * M2_CAND_THREADS) >= nmp) return;
-  const Carve cv(A.cur_stride, ncell, false);
-  const TargetLds T = stage_grid_only(smem, cv, ncur, ncell, A.cur_kps + co, A.cur_desc + co * 32,
-                                      A.cur_cell_start + (size_t)b * (ncell + 1), A.cur_cell_items + co);
+  const TargetLds T = stage_cur(smem, A, b, false);  // the grid only: descriptors from HBM / L2
   __syncthreads();
   const int q = blockIdx.x * M2_CAND_THREADS + tid;
   if (q >= nmp) return;
@@ -665,9 +541,7 @@ __global__ __launch_bounds__(M2_CAND_THREADS) void k_m2_candidates(fb_proj_point
   if (A.mp_track[mo + q]) {
     const int lvl = A.mp_level[mo + q];
     uint32_t d[8];
-    const uint4 *dq = reinterpret_cast<const uint4 *>(A.mp_desc + (mo + q) * 32);
-    const uint4 d0 = dq[0], d1 = dq[1];
-    d[0] = d0.x; d[1] = d0.y; d[2] = d0.z; d[3] = d0.w; d[4] = d1.x; d[5] = d1.y; d[6] = d1.z; d[7] = d1.w;
+    fb::load_desc(A.mp_desc + (mo + q) * 32, d);
     uint32_t *out = cand + (mo + q) * M2_K;
     for_area<false>(A.grid, T, A.mp_proj[(mo + q) * 2], A.mp_proj[(mo + q) * 2 + 1], m2_radius(A, mo + q, A.th != 1.0f, lvl), lvl - 1, lvl,
                     [&](int idx) {
@@ -685,35 +559,20 @@ __global__ __launch_bounds__(M2_CAND_THREADS) void k_m2_candidates(fb_proj_point
 __global__ __launch_bounds__(MATCH_THREADS) void k_m2_resolve(fb_proj_points_args A, const uint32_t *cand, const uint8_t *ncand) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
-  const int ncell = A.grid.cols * A.grid.rows;
   const size_t co = (size_t)b * A.cur_stride, mo = (size_t)b * A.mp_stride;
   const int ncur = A.n_cur[b], nmp = A.n_mp[b];
-  const Carve cv(A.cur_stride, ncell, false);
-  const TargetLds T = stage_grid_only(smem, cv, ncur, ncell, A.cur_kps + co, A.cur_desc + co * 32,
-                                      A.cur_cell_start + (size_t)b * (ncell + 1), A.cur_cell_items + co);
-  int *ownerA = reinterpret_cast<int *>(smem + cv.end);
-  int *ownerB = ownerA + A.cur_stride;
-  int *assignA = ownerB + A.cur_stride;
-  int *assignB = assignA + A.mp_stride;
-  __shared__ int s_changed, s_n;
-  const uint8_t *blocked0 = A.cur_blocked ? A.cur_blocked + co : nullptr;
-  for (int i = tid; i < ncur; i += nt) ownerA[i] = (blocked0 && blocked0[i]) ? -1 : NONE;
-  for (int q = tid; q < nmp; q += nt) assignA[q] = NONE;
+  const TargetLds T = stage_cur(smem, A, b, false);
+  __shared__ fb::ClaimFlags s_cf;
+  fb::Claims<int> C(s_cf, T.rest, A.cur_stride, A.mp_stride, A.cur_blocked ? A.cur_blocked + co : nullptr, ncur, nmp);
+  C.start();
   const bool bFactor = A.th != 1.0f;
-  __syncthreads();
-  for (int round = 0; round <= nmp + 1; round++) {
-    for (int i = tid; i < ncur; i += nt) ownerB[i] = (blocked0 && blocked0[i]) ? -1 : NONE;
-    if (tid == 0) s_changed = 0;
-    __syncthreads();
+  for (int round = 0; C.more(round); round++) {
+    C.begin_round();
     for (int q = tid; q < nmp; q += nt) {
       int best = NONE;
       const int nc = ncand[mo + q];
       if (nc > 0) {
-        int bestDist = 256, bestLevel = -1, bestDist2 = 256, bestLevel2 = -1, bestIdx = -1;
-        auto take = [&](int idx, int dist, int lev) {
-          if (dist < bestDist) { bestDist2 = bestDist; bestDist = dist; bestLevel2 = bestLevel; bestLevel = lev; bestIdx = idx; }
-          else if (dist < bestDist2) { bestLevel2 = lev; bestDist2 = dist; }
-        };
+        M2Pick pick;
         if (nc != M2_OVER) {
           const uint4 *cq = reinterpret_cast<const uint4 *>(cand + (mo + q) * M2_K);
           const uint4 c0 = cq[0];
@@ -723,47 +582,27 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_m2_resolve(fb_proj_points_arg
           for (int k = 0; k < M2_K; k++) {
             if (k >= nc) break;
             const int idx = (int)(c[k] & 0xFFFFu);
-            if (ownerA[idx] < q) continue;
-            take(idx, (int)(c[k] >> 20), (int)((c[k] >> 16) & 0xF));
+            if (C.taken(idx, q)) continue;
+            pick.take(idx, (int)(c[k] >> 20), (int)((c[k] >> 16) & 0xF));
           }
         } else {  // more candidates than the cache holds: the full walk, descriptors from HBM / L2
           const int lvl = A.mp_level[mo + q];
           uint32_t d[8];
-          const uint4 *dq = reinterpret_cast<const uint4 *>(A.mp_desc + (mo + q) * 32);
-          const uint4 d0 = dq[0], d1 = dq[1];
-          d[0] = d0.x; d[1] = d0.y; d[2] = d0.z; d[3] = d0.w; d[4] = d1.x; d[5] = d1.y; d[6] = d1.z; d[7] = d1.w;
+          fb::load_desc(A.mp_desc + (mo + q) * 32, d);
           for_area<false>(A.grid, T, A.mp_proj[(mo + q) * 2], A.mp_proj[(mo + q) * 2 + 1], m2_radius(A, mo + q, bFactor, lvl), lvl - 1, lvl,
                           [&](int idx) {
-            if (ownerA[idx] < q) return;
-            take(idx, target_hamming(T, d, idx), (int)T.oct[idx]);
+            if (!C.taken(idx, q)) pick.take(idx, target_hamming(T, d, idx), (int)T.oct[idx]);
           });
         }
-        if (bestDist <= TH_HIGH && !(bestLevel == bestLevel2 && bestDist > A.matcher.nnratio * bestDist2)) best = bestIdx;
+        best = pick.result(A.matcher.nnratio);
       }
-      assignB[q] = best;
-      if (best != assignA[q]) s_changed = 1;
-      if (best != NONE && A.mp_obs_pos[mo + q]) atomicMin(&ownerB[best], q);
+      C.submit(q, best, best != NONE && A.mp_obs_pos[mo + q]);
     }
-    __syncthreads();
-    const int changed = s_changed;
-    int *t = ownerA; ownerA = ownerB; ownerB = t;
-    t = assignA; assignA = assignB; assignB = t;
-    __syncthreads();
-    if (!changed) break;
+    if (C.end_round()) break;
   }
-  int *matchL = ownerB;
-  for (int i = tid; i < ncur; i += nt) matchL[i] = -1;
-  if (tid == 0) s_n = 0;
-  __syncthreads();
-  for (int q = tid; q < nmp; q += nt) {
-    const int c = assignA[q];
-    if (c == NONE) continue;
-    atomicMax(&matchL[c], q);
-    atomicAdd(&s_n, 1);
-  }
-  __syncthreads();
+  const int *matchL = fb::commit_matches<true>(C, fb::QueryIndex());  // last writer wins
   for (int i = tid; i < ncur; i += nt) A.match_cur_to_mp[co + i] = matchL[i];
-  if (tid == 0) A.nmatches[b] = s_n;
+  if (tid == 0) A.nmatches[b] = s_cf.n;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -772,13 +611,10 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_m2_resolve(fb_proj_points_arg
 __global__ __launch_bounds__(MATCH_THREADS) void k_bird_mappoints(fb_bird_mp_args A, int descInLds) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
-  const int ncell = A.grid.cols * A.grid.rows;
   const size_t co = (size_t)b * A.cur_stride, ro = (size_t)b * A.ref_stride;
   const int ncur = A.n_cur[b], nref = A.n_ref[b];
-  const Carve cv(A.cur_stride, ncell, descInLds != 0);
-  const TargetLds T = stage_target(smem, cv, ncur, ncell, A.cur_kps + co, A.cur_desc + co * 32,
-                                   A.cur_cell_start + (size_t)b * (ncell + 1), A.cur_cell_items + co, descInLds != 0);
-  int *writer = reinterpret_cast<int *>(smem + cv.end);  // [cur_stride]
+  const TargetLds T = stage_cur(smem, A, b, descInLds != 0);
+  int *writer = reinterpret_cast<int *>(T.rest);  // [cur_stride]
   __shared__ float s_Tcw[12], s_Tbw[12];
   __shared__ int s_n;
   if (tid < 12) s_Tcw[tid] = A.cur_Tcw[(size_t)b * 12 + tid];
@@ -803,9 +639,7 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_bird_mappoints(fb_bird_mp_arg
     const float pty = (float)(A.bird_rows / 2 - (lp[0] - A.rear_axle_to_center) * A.meter2pixel);
     if (ptx < 0 || ptx >= A.bird_cols || pty < 0 || pty >= A.bird_rows) continue;
     uint32_t d[8];
-    const uint4 *dq = reinterpret_cast<const uint4 *>(A.ref_desc + (ro + i1) * 32);
-    const uint4 d0 = dq[0], d1 = dq[1];
-    d[0] = d0.x; d[1] = d0.y; d[2] = d0.z; d[3] = d0.w; d[4] = d1.x; d[5] = d1.y; d[6] = d1.z; d[7] = d1.w;
+    fb::load_desc(A.ref_desc + (ro + i1) * 32, d);
     int bestDist = INT_MAX, bestDist2 = INT_MAX, bestIdx = -1;
     for_area<true>(A.grid, T, ptx, pty, (float)A.window_size, -1, -1, [&](int i2) {
       if (i2 >= ncur) return;
@@ -838,13 +672,10 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_bird_mappoints(fb_bird_mp_arg
 __global__ __launch_bounds__(MATCH_THREADS) void k_birdview(fb_birdview_args A, int descInLds) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
-  const int ncell = A.grid.cols * A.grid.rows;
   const size_t co = (size_t)b * A.cur_stride, ro = (size_t)b * A.ref_stride;
   const int ncur = A.n_cur[b], nref = A.n_ref[b];
-  const Carve cv(A.cur_stride, ncell, descInLds != 0);
-  const TargetLds T = stage_target(smem, cv, ncur, ncell, A.cur_kps + co, A.cur_desc + co * 32,
-                                   A.cur_cell_start + (size_t)b * (ncell + 1), A.cur_cell_items + co, descInLds != 0);
-  int *m12 = reinterpret_cast<int *>(smem + cv.end);  // [ref_stride]
+  const TargetLds T = stage_cur(smem, A, b, descInLds != 0);
+  int *m12 = reinterpret_cast<int *>(T.rest);  // [ref_stride]
   int *bins = m12 + A.ref_stride;                      // [ref_stride] histogram bin of i1 or -1
   __shared__ int s_n, s_nd;
   __shared__ fb::RotHist s_rot;
@@ -1009,7 +840,7 @@ size_t match_lds_bytes(int cur_stride, int ncell, int extra_ints, bool withDesc 
 // HBM/L2 (frames with more key points than ~2900, e.g. nFeatures = 4000) and only positions, octaves and the grid are staged
 struct LdsPlan { size_t bytes; int descInLds; };
 constexpr size_t LDS_BUDGET = 160 * 1024 - 512;  // leave room for the kernels' static __shared__ variables
-int check_lds(size_t bytes, const char *what);
+using fb::check_lds;
 int plan_lds(int cur_stride, int ncell, int extra_ints, const char *what, LdsPlan *p) {
   p->descInLds = 1;
   p->bytes = Carve(cur_stride, ncell, true).end + (size_t)extra_ints * 4;
@@ -1018,14 +849,6 @@ int plan_lds(int cur_stride, int ncell, int extra_ints, const char *what, LdsPla
     p->bytes = Carve(cur_stride, ncell, false).end + (size_t)extra_ints * 4;
   }
   return check_lds(p->bytes, what);
-}
-
-int check_lds(size_t bytes, const char *what) {
-  if (bytes > 160 * 1024) {
-    fb::set_error("%s: frame too large for the LDS-staged matcher (%zu B > 160 KiB)", what, bytes);
-    return FB_ERR_CAPACITY;
-  }
-  return FB_OK;
 }
 
 template <typename K>

@@ -9,9 +9,9 @@
 // node, so the merge-join of the reference (lower_bound skips, :181-265) is a binary search per query.
 //
 // M5 is greedy in keyframe-feature order (a frame feature that already received a MapPoint is skipped,
-// :210): resolved with the same fixed-point iteration as M2/M3 (see match.hip), claims here always block.
+// :210): resolved with the same fixed-point iteration as M2/M3 (fb_claims.h), claims here always block.
 #include "fb_common.h"
-#include "fb_rot_hist.h"
+#include "fb_claims.h"
 
 namespace {
 
@@ -72,13 +72,11 @@ __global__ __launch_bounds__(BOW_THREADS) void k_match_bow_t(fb_bow_args A, cons
   // descriptor table of the candidate side: LDS when it fits, else read from HBM/L2 (frames with > ~3400 key points)
   const size_t descBytes = descInLds ? (size_t)A.f_stride * 32 : 0;
   const uint4 *fdesc = descInLds ? reinterpret_cast<const uint4 *>(smem) : reinterpret_cast<const uint4 *>(A.f_desc + fo * 32);
-  int *ownerA = reinterpret_cast<int *>(smem + descBytes);  // [f_stride]
-  int *ownerB = ownerA + A.f_stride;
-  int *assignA = ownerB + A.f_stride;                                // [kf item_stride]
-  int *assignB = assignA + A.kf_fv.item_stride;
-  int *fitems = assignB + A.kf_fv.item_stride;                       // [f item_stride] F.mFeatVec's items: walked by every query in every round
-  __shared__ int s_changed, s_n;
+  int *owners = reinterpret_cast<int *>(smem + descBytes);          // owner [2][f_stride], assign [2][kf item_stride]
+  int *fitems = owners + 2 * A.f_stride + 2 * A.kf_fv.item_stride;   // [f item_stride] F.mFeatVec's items: walked by every query in every round
+  __shared__ fb::ClaimFlags s_cf;
   __shared__ fb::RotHist s_rot;
+  fb::Claims<int> C(s_cf, owners, A.f_stride, A.kf_fv.item_stride, nullptr, nF, nQ);
   {
     const int nFi = F.n > 0 ? min(F.start[F.n], A.f_fv.item_stride) : 0;
     for (int i = tid; i < nFi; i += nt) fitems[i] = F.items[i];
@@ -88,9 +86,7 @@ __global__ __launch_bounds__(BOW_THREADS) void k_match_bow_t(fb_bow_args A, cons
     uint4 *dst = reinterpret_cast<uint4 *>(smem);
     for (int i = tid; i < nF * 2; i += nt) dst[i] = src[i];
   }
-  for (int i = tid; i < nF; i += nt) ownerA[i] = NONE;
-  for (int q = tid; q < nQ; q += nt) assignA[q] = NONE;
-  __syncthreads();
+  C.start();
   // What a query needs in every round of the fixed point -- its key-frame feature, whether that carries a MapPoint, the
   // frame-side node (two binary searches over the CSR in HBM) and its descriptor -- does not change between rounds: a lane
   // resolves it once for its (at most QPT) queries and keeps it in registers; a round then only touches LDS.  (Re-deriving it
@@ -99,25 +95,25 @@ __global__ __launch_bounds__(BOW_THREADS) void k_match_bow_t(fb_bow_args A, cons
   const bool cached = nQ <= QPT * nt;
   int qc0[QPT], qc1[QPT];       // candidate range in F.items, empty = the query cannot match
   uint32_t qd[QPT][8];
+  auto resolve = [&](int q, int &c0, int &c1, uint32_t *d) {
+    const int realIdxKF = K.items[q];
+    if (!A.kf_has_mp[ko + realIdxKF]) return;
+    const int fi = find_node(F, K.ids[node_of_item(K, q)]);
+    if (fi >= 0) { c0 = F.start[fi]; c1 = F.start[fi + 1]; load_desc(A.kf_desc + (ko + realIdxKF) * 32, d); }
+  };
 #pragma unroll
   for (int s_ = 0; s_ < QPT; s_++) {
     qc0[s_] = 0; qc1[s_] = 0;
 #pragma unroll
     for (int w = 0; w < 8; w++) qd[s_][w] = 0;
     const int q = tid + s_ * nt;
-    if (cached && q < nQ) {
-      const int realIdxKF = K.items[q];
-      if (A.kf_has_mp[ko + realIdxKF]) {
-        const int fi = find_node(F, K.ids[node_of_item(K, q)]);
-        if (fi >= 0) { qc0[s_] = F.start[fi]; qc1[s_] = F.start[fi + 1]; load_desc(A.kf_desc + (ko + realIdxKF) * 32, qd[s_]); }
-      }
-    }
+    if (cached && q < nQ) resolve(q, qc0[s_], qc1[s_], qd[s_]);
   }
   auto evaluate = [&](int q, int c0, int c1, const uint32_t *d) {
     int bestDist1 = 256, bestIdxF = -1, bestDist2 = 256;
     for (int c = c0; c < c1; c++) {
       const int realIdxF = fitems[c];
-      if (ownerA[realIdxF] < q) continue;  // vpMapPointMatches[realIdxF] already set by an earlier feature
+      if (C.taken(realIdxF, q)) continue;  // vpMapPointMatches[realIdxF] already set by an earlier feature
       if (KFKF && !f_has_mp[fo + realIdxF]) continue;
       const int dist = fb::hamming256(d, fdesc + realIdxF * 2);
       if (dist < bestDist1) { bestDist2 = bestDist1; bestDist1 = dist; bestIdxF = realIdxF; }
@@ -126,73 +122,28 @@ __global__ __launch_bounds__(BOW_THREADS) void k_match_bow_t(fb_bow_args A, cons
     const bool low = KFKF ? bestDist1 < TH_LOW : bestDist1 <= TH_LOW;
     return (low && (float)bestDist1 < A.matcher.nnratio * (float)bestDist2) ? bestIdxF : NONE;
   };
-  for (int round = 0; round <= nQ + 1; round++) {
-    for (int i = tid; i < nF; i += nt) ownerB[i] = NONE;
-    if (tid == 0) s_changed = 0;
-    __syncthreads();
+  for (int round = 0; C.more(round); round++) {
+    C.begin_round();
     if (cached) {
 #pragma unroll
       for (int s_ = 0; s_ < QPT; s_++) {
         const int q = tid + s_ * nt;
         if (q >= nQ) continue;
-        const int best = qc1[s_] > qc0[s_] ? evaluate(q, qc0[s_], qc1[s_], qd[s_]) : NONE;
-        assignB[q] = best;
-        if (best != assignA[q]) s_changed = 1;
-        if (best != NONE) atomicMin(&ownerB[best], q);
+        C.submit(q, qc1[s_] > qc0[s_] ? evaluate(q, qc0[s_], qc1[s_], qd[s_]) : NONE);
       }
     } else {
       for (int q = tid; q < nQ; q += nt) {
-        int best = NONE;
-        const int realIdxKF = K.items[q];
-        if (A.kf_has_mp[ko + realIdxKF]) {
-          const int fi = find_node(F, K.ids[node_of_item(K, q)]);
-          if (fi >= 0) {
-            uint32_t d[8];
-            load_desc(A.kf_desc + (ko + realIdxKF) * 32, d);
-            best = evaluate(q, F.start[fi], F.start[fi + 1], d);
-          }
-        }
-        assignB[q] = best;
-        if (best != assignA[q]) s_changed = 1;
-        if (best != NONE) atomicMin(&ownerB[best], q);
+        int c0 = 0, c1 = 0;
+        uint32_t d[8];
+        resolve(q, c0, c1, d);
+        C.submit(q, c1 > c0 ? evaluate(q, c0, c1, d) : NONE);
       }
     }
-    __syncthreads();
-    const int changed = s_changed;
-    int *t = ownerA; ownerA = ownerB; ownerB = t;
-    t = assignA; assignA = assignB; assignB = t;
-    __syncthreads();
-    if (!changed) break;
+    if (C.end_round()) break;
   }
-  int *matchL = ownerB;
-  for (int i = tid; i < nF; i += nt) matchL[i] = -1;
-  s_rot.clear();
-  if (tid == 0) s_n = 0;
-  __syncthreads();
-  const bool ori = A.matcher.check_orientation != 0;
-  for (int q = tid; q < nQ; q += nt) {
-    const int c = assignA[q];
-    if (c == NONE) continue;
-    const int realIdxKF = K.items[q];
-    matchL[c] = realIdxKF;  // unique claimer: a claimed slot blocks every later query
-    atomicAdd(&s_n, 1);
-    if (ori) {
-      const int bin = rot_bin(A.kf_kps[ko + realIdxKF].angle - A.f_kps[fo + c].angle);
-      s_rot.add(bin);
-      assignB[q] = bin;
-    }
-  }
-  __syncthreads();
-  if (ori) {
-    s_rot.pick();
-    for (int q = tid; q < nQ; q += nt) {
-      const int c = assignA[q];
-      if (c == NONE) continue;
-      const int bin = assignB[q];
-      if (!s_rot.keeps(bin)) { matchL[c] = -1; atomicSub(&s_n, 1); }
-    }
-    __syncthreads();
-  }
+  // unique claimer: a claimed slot blocks every later query.  The match of a frame feature is the key-frame FEATURE of its query.
+  const int *matchL = fb::commit_matches<false>(C, [&](int q) { return K.items[q]; }, &s_rot, A.matcher.check_orientation != 0,
+                                                [&](int idxKF, int c) { return A.kf_kps[ko + idxKF].angle - A.f_kps[fo + c].angle; });
   if (KFKF) {
     const int nK = A.n_kf[b];
     for (int i = tid; i < nK; i += nt) match12[ko + i] = -1;
@@ -202,7 +153,7 @@ __global__ __launch_bounds__(BOW_THREADS) void k_match_bow_t(fb_bow_args A, cons
   } else {
     for (int i = tid; i < nF; i += nt) A.match_f_to_kf[fo + i] = matchL[i];
   }
-  if (tid == 0) A.nmatches[b] = s_n;
+  if (tid == 0) A.nmatches[b] = s_cf.n;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -302,10 +253,7 @@ __global__ __launch_bounds__(BOW_THREADS) void k_match_triangulation(fb_triangul
   if (tid == 0) A.nmatches[b] = s_n;
 }
 
-int lds_ok(size_t bytes, const char *what) {
-  if (bytes > 160 * 1024) { fb::set_error("%s: frame too large for the LDS-staged matcher (%zu B)", what, bytes); return FB_ERR_CAPACITY; }
-  return FB_OK;
-}
+using fb::check_lds;
 
 }  // namespace
 
@@ -315,7 +263,7 @@ int match_triangulation_shared(const fb_triangulation_args &A, const int32_t *sk
   size_t lds = (size_t)A.kf2_stride * 48 + (size_t)A.kf1_stride * 8 + 16;
   const int descInLds = lds <= 160 * 1024 - 512;
   if (!descInLds) lds -= (size_t)A.kf2_stride * 32;
-  FB_TRY(lds_ok(lds, "fb_create_new_map_points"));
+  FB_TRY(check_lds(lds, "fb_create_new_map_points"));
   FB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_match_triangulation), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   fb::ProfScope prof_(fb::P_NP_M7, stream);
   k_match_triangulation<<<A.batch, BOW_THREADS, lds, stream>>>(A, descInLds, 1, skip);
@@ -333,7 +281,7 @@ int fb_match_bow_dev(const fb_bow_args *A, void *stream) {
   size_t lds = (size_t)A->f_stride * 32 + (size_t)A->f_stride * 8 + (size_t)A->kf_fv.item_stride * 8 + (size_t)A->f_fv.item_stride * 4 + 16;
   const int descInLds = lds <= 160 * 1024 - 512;
   if (!descInLds) lds -= (size_t)A->f_stride * 32;
-  FB_TRY(lds_ok(lds, "fb_match_bow"));
+  FB_TRY(check_lds(lds, "fb_match_bow"));
   FB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_match_bow_t<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   fb::ProfScope prof_(fb::P_BOW, fb::as_stream(stream));
   k_match_bow_t<false><<<A->batch, BOW_THREADS, lds, fb::as_stream(stream)>>>(*A, nullptr, nullptr, descInLds);
@@ -354,7 +302,7 @@ int fb_match_bow_kf_dev(const fb_bow_kf_args *K, void *stream) {
   size_t lds = (size_t)A.f_stride * 32 + (size_t)A.f_stride * 8 + (size_t)A.kf_fv.item_stride * 8 + (size_t)A.f_fv.item_stride * 4 + 16;
   const int descInLds = lds <= 160 * 1024 - 512;
   if (!descInLds) lds -= (size_t)A.f_stride * 32;
-  FB_TRY(lds_ok(lds, "fb_match_bow_kf"));
+  FB_TRY(check_lds(lds, "fb_match_bow_kf"));
   FB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_match_bow_t<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   fb::ProfScope prof_(fb::P_BOW_KF, fb::as_stream(stream));
   k_match_bow_t<true><<<A.batch, BOW_THREADS, lds, fb::as_stream(stream)>>>(A, K->has_mp2, K->matches12, descInLds);
@@ -369,7 +317,7 @@ int fb_match_triangulation_dev(const fb_triangulation_args *A, void *stream) {
   size_t lds = (size_t)A->kf2_stride * 48 + (size_t)A->kf1_stride * 8 + 16;
   const int descInLds = lds <= 160 * 1024 - 512;
   if (!descInLds) lds -= (size_t)A->kf2_stride * 32;
-  FB_TRY(lds_ok(lds, "fb_match_triangulation"));
+  FB_TRY(check_lds(lds, "fb_match_triangulation"));
   FB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_match_triangulation), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   fb::ProfScope prof_(fb::P_TRIANG, fb::as_stream(stream));
   k_match_triangulation<<<A->batch, BOW_THREADS, lds, fb::as_stream(stream)>>>(*A, descInLds, 0, nullptr);

@@ -20,12 +20,12 @@ struct KfTargetLds {
   int n;
 };
 
-__device__ __forceinline__ KfTargetLds stage_kf(uint8_t *smem, const Carve &cv, const fb_kf_target &K, int b, bool withDesc) {
+__device__ __forceinline__ KfTargetLds stage_kf(uint8_t *smem, const fb_kf_target &K, int b, bool withDesc) {
   const int ncell = K.grid.cols * K.grid.rows;
   const size_t o = (size_t)b * K.kf_stride;
   KfTargetLds r;
   r.n = K.n_kf[b];
-  r.T = stage_target(smem, cv, r.n, ncell, K.kf_kps + o, K.kf_desc + o * 32, K.kf_cell_start + (size_t)b * (ncell + 1),
+  r.T = stage_target(smem, Carve(K.kf_stride, ncell, withDesc), r.n, ncell, K.kf_kps + o, K.kf_desc + o * 32, K.kf_cell_start + (size_t)b * (ncell + 1),
                      K.kf_cell_items + o, withDesc);
   return r;
 }
@@ -100,9 +100,7 @@ template <int MODE>
 __global__ __launch_bounds__(MATCH_THREADS) void k_fuse_search(fb_fuse_args A, int descInLds) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
-  const int ncell = A.kf.grid.cols * A.kf.grid.rows;
-  const Carve cv(A.kf.kf_stride, ncell, descInLds != 0);
-  const KfTargetLds KT = stage_kf(smem, cv, A.kf, b, descInLds != 0);
+  const KfTargetLds KT = stage_kf(smem, A.kf, b, descInLds != 0);
   __shared__ float s_T[12], s_Ow[3];
   if (tid == 0) {
     if (MODE == MODE_FUSE) {
@@ -127,36 +125,24 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_fuse_search(fb_fuse_args A, i
 }
 
 // SearchByProjection(pKF, Scw, ...): greedy in point order (a slot written to vpMatched blocks later points, :372),
-// resolved with the fixed-point iteration of match.hip
+// resolved with the fixed-point iteration of fb_claims.h
 __global__ __launch_bounds__(MATCH_THREADS) void k_proj_sim3(fb_proj_sim3_args A, int descInLds) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
-  const int ncell = A.kf.grid.cols * A.kf.grid.rows;
-  const Carve cv(A.kf.kf_stride, ncell, descInLds != 0);
-  const KfTargetLds KT = stage_kf(smem, cv, A.kf, b, descInLds != 0);
+  const KfTargetLds KT = stage_kf(smem, A.kf, b, descInLds != 0);
   const int nkf = KT.n, ms = A.mp.mp_stride, ks = A.kf.kf_stride;
-  int *ownerA = reinterpret_cast<int *>(smem + cv.end);  // [ks]
-  int *ownerB = ownerA + ks;
-  // per-point state is one u16 pair (vpPoints of a loop closure can be several thousand); the cheap geometric gates
-  // are re-evaluated every round instead of being stored
-  typedef unsigned short u16;
-  constexpr int NONE16 = 0xFFFF;
-  u16 *assignA = reinterpret_cast<u16 *>(ownerB + ks);   // [ms]
-  u16 *assignB = assignA + ms;
   __shared__ float s_T[12], s_Ow[3];
-  __shared__ int s_changed, s_n;
+  __shared__ fb::ClaimFlags s_cf;
   if (tid == 0) decompose_sim3(A.Scw + (size_t)b * 12, s_T, s_Ow);
   const size_t mo = (size_t)b * ms, ko = (size_t)b * ks;
   const int nmp = A.mp.n_mp[b];
-  const uint8_t *blocked0 = A.kf_matched ? A.kf_matched + ko : nullptr;
-  for (int i = tid; i < nkf; i += nt) ownerA[i] = (blocked0 && blocked0[i]) ? -1 : NONE;
-  for (int q = tid; q < nmp; q += nt) assignA[q] = NONE16;
-  __syncthreads();
+  // owners [2][ks]; per-point state is one u16 pair (vpPoints of a loop closure can be several thousand); the cheap
+  // geometric gates are re-evaluated every round instead of being stored
+  fb::Claims<uint16_t> C(s_cf, KT.T.rest, ks, ms, A.kf_matched ? A.kf_matched + ko : nullptr, nkf, nmp);
+  C.start();
   const float th = (float)A.th;
-  for (int round = 0; round <= nmp + 1; round++) {
-    for (int i = tid; i < nkf; i += nt) ownerB[i] = (blocked0 && blocked0[i]) ? -1 : NONE;
-    if (tid == 0) s_changed = 0;
-    __syncthreads();
+  for (int round = 0; C.more(round); round++) {
+    C.begin_round();
     for (int q = tid; q < nmp; q += nt) {
       int best = NONE;
       if (A.mp.mp_valid[mo + q]) {
@@ -164,33 +150,15 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_proj_sim3(fb_proj_sim3_args A
         const int lvl = gate_point<MODE_PROJ_SIM3>(A.kf, s_T, s_Ow, A.mp, mo + q, u, v);
         if (lvl >= 0)
           best = search_point<MODE_PROJ_SIM3>(A.kf, KT.T, A.mp.mp_desc + (mo + q) * 32, u, v, lvl, th,
-                                              [&](int idx) { return ownerA[idx] < q; });
+                                              [&](int idx) { return C.taken(idx, q); });
       }
-      const int best16 = best == NONE ? NONE16 : best;
-      assignB[q] = (u16)best16;
-      if (best16 != assignA[q]) s_changed = 1;
-      if (best != NONE) atomicMin(&ownerB[best], q);
+      C.submit(q, best);
     }
-    __syncthreads();
-    const int changed = s_changed;
-    int *t = ownerA; ownerA = ownerB; ownerB = t;
-    u16 *t16 = assignA; assignA = assignB; assignB = t16;
-    __syncthreads();
-    if (!changed) break;
+    if (C.end_round()) break;
   }
-  int *matchL = ownerB;
-  for (int i = tid; i < nkf; i += nt) matchL[i] = -1;
-  if (tid == 0) s_n = 0;
-  __syncthreads();
-  for (int q = tid; q < nmp; q += nt) {
-    const int c = assignA[q];
-    if (c == NONE16) continue;
-    matchL[c] = q;
-    atomicAdd(&s_n, 1);
-  }
-  __syncthreads();
+  const int *matchL = fb::commit_matches<false>(C, fb::QueryIndex());  // one claimer per slot
   for (int i = tid; i < nkf; i += nt) A.match_kf_to_mp[ko + i] = matchL[i];
-  if (tid == 0) A.nmatches[b] = s_n;
+  if (tid == 0) A.nmatches[b] = s_cf.n;
 }
 
 // one direction of SearchBySim3 for the points of the query key frame (:1151-1223 / :1226-1298)
@@ -258,15 +226,13 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_sim3(fb_sim3_args A, int carv
   const int N1 = A.mp1.n_mp[b], N2 = A.mp2.n_mp[b];
   const size_t o1 = (size_t)b * A.mp1.mp_stride, o2 = (size_t)b * A.mp2.mp_stride;
   {  // KF1 points into KF2
-    const Carve c2(A.kf2.kf_stride, A.kf2.grid.cols * A.kf2.grid.rows, descInLds != 0);
-    const KfTargetLds KT = stage_kf(smem, c2, A.kf2, b, descInLds != 0);
+    const KfTargetLds KT = stage_kf(smem, A.kf2, b, descInLds != 0);
     __syncthreads();
     sim3_direction(A.kf2, KT.T, A.mp1, o1, N1, s_T1, s_sR21, s_t21, A.th, vnMatch1);
   }
   __syncthreads();
   {  // KF2 points into KF1
-    const Carve c1(A.kf1.kf_stride, A.kf1.grid.cols * A.kf1.grid.rows, descInLds != 0);
-    const KfTargetLds KT = stage_kf(smem, c1, A.kf1, b, descInLds != 0);
+    const KfTargetLds KT = stage_kf(smem, A.kf1, b, descInLds != 0);
     __syncthreads();
     sim3_direction(A.kf1, KT.T, A.mp2, o2, N2, s_T2, s_sR12, s_t12, A.th, vnMatch2);
   }

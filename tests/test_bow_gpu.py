@@ -10,6 +10,24 @@ from fishbirdeyevisualslam_amd import bow_problem as BP, synth
 pytestmark = pytest.mark.gpu
 
 
+@pytest.mark.parametrize("above", [False, True])
+def test_search_by_bow_contention(above):
+    """The serial 'frame feature already has a MapPoint' rule with 150 candidates, below and above the query count up to which
+    the kernel keeps its queries in registers.  The rule fires: the candidates limit the number of matches."""
+    limit = BP.queries_kept_in_registers()
+    n_q = limit + 104 if above else 2000
+    assert (n_q > limit) == above
+    probs = [BP.make_contended_bow_problem(6500 + i, n_q, 150) for i in range(2)]
+    for ori in (1, 0):
+        a, oo, k = BP.bow_args(probs, check_ori=ori)
+        O.call("orc_match_bow", a)
+        a2, oh, k2 = BP.bow_args(probs, check_ori=ori)
+        H.call("fb_match_bow", a2)
+        np.testing.assert_array_equal(oh["match_f_to_kf"], oo["match_f_to_kf"])
+        np.testing.assert_array_equal(oh["nmatches"], oo["nmatches"])
+        assert 2 * oo["nmatches"].min() >= 150
+
+
 @pytest.mark.parametrize("seed,nkf,nf,share", [(6000, 1500, 1500, True), (6001, 2064, 700, True), (6002, 400, 2000, False), (6003, 30, 30, True)])
 def test_search_by_bow(seed, nkf, nf, share):
     probs = [BP.make_bow_problem(seed + 10 * i, nkf, nf, share) for i in range(3)]

@@ -144,6 +144,29 @@ def test_gpu_fuse_and_projection_sim3(seed, nkf, nmp):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("blocked", [True, False])
+def test_gpu_projection_sim3_contention(blocked):
+    """2000 points compete for 150 key points in a wide window: the serial 'slot already written to vpMatched' rule, with
+    and without slots that are matched on entry.  The rule fires: the free slots limit the number of matches."""
+    H = _hip()
+    probs = [KP.make_kf_points_problem(8500 + i, 150, 2000, True) for i in range(2)]
+    if not blocked:
+        for p in probs:
+            p["kf_matched"] = np.zeros_like(p["kf_matched"])
+    cs, ci = _grid([p["kf_kps"] for p in probs], 150)
+    a, oo, k = KP.proj_sim3_args(probs, cs, ci, th=40)
+    O.call("orc_match_projection_sim3", a)
+    a2, oh, k2 = KP.proj_sim3_args(probs, cs, ci, th=40)
+    H.call("fb_match_projection_sim3", a2)
+    np.testing.assert_array_equal(oh["match_kf_to_mp"], oo["match_kf_to_mp"])
+    np.testing.assert_array_equal(oh["nmatches"], oo["nmatches"])
+    for b, p in enumerate(probs):
+        free = int((p["kf_matched"] == 0).sum())
+        assert (free < 150) == blocked
+        assert 2 * oo["nmatches"][b] >= free
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("seed,n1,n2,ns", [(8100, 1500, 1500, 900), (8101, 2064, 800, 500), (8102, 40, 60, 20)])
 def test_gpu_search_by_sim3(seed, n1, n2, ns):
     H = _hip()

@@ -136,10 +136,27 @@ def test_birdview_match(seed, ncur, nref):
         assert out["nmatches"].min() > 10
 
 
+def test_search_by_projection_points_contention():
+    """Many map points compete for few key points: the serial 'already has a map point with observations' rule of M2 (the
+    two-phase kernels here, the one-kernel version through test_one_kernel_version_of_search_local_points, whose -k
+    selection matches this test's name as well).  The rule fires: without observations no point claims its key point, and
+    the oracle then answers differently."""
+    probs = [synth.make_proj_points_problem(2250 + i, 120, 2000) for i in range(2)]
+    geom = P.grid_geom(synth.front_grid_geom(1280, 720))
+    cs, ci = P.build_grid_host([p["cur_kps"] for p in probs], geom, O.grid_build, 120)
+    out = _both(lambda: P.proj_points_args(probs, cs, ci, th=5.0), "orc_match_projection_points",
+                "fb_match_projection_points", ["match_cur_to_mp", "nmatches"])
+    unclaimed = [dict(p, mp_obs_pos=np.zeros_like(p["mp_obs_pos"])) for p in probs]
+    a, free, keep = P.proj_points_args(unclaimed, cs, ci, th=5.0)
+    O.call("orc_match_projection_points", a)
+    for b in range(2):
+        assert (free["match_cur_to_mp"][b] != out["match_cur_to_mp"][b]).any()
+
+
 def test_one_kernel_version_of_search_local_points():
     """The host-pointer entry point of M2 runs the two-phase matcher (candidate lists by many workgroups, then the serial rule
     on the lists); FB_M2_ONE_KERNEL (read once per process, hence a child process) selects the one-workgroup-per-frame
-    kernel a _dev caller without a workspace gets.  Same parity bar."""
+    kernel a _dev caller without a workspace gets.  Same parity bar, the contention case included."""
     import os, subprocess, sys
     env = dict(os.environ, FB_M2_ONE_KERNEL="1")
     here = os.path.dirname(os.path.abspath(__file__))

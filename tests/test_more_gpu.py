@@ -9,7 +9,7 @@ import pytest
 
 import hip_lib as H
 import oracle_lib as O
-from fishbirdeyevisualslam_amd import more_problems as M, problems as P, synth
+from fishbirdeyevisualslam_amd import bow_problem as BP, more_problems as M, problems as P, synth
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -56,6 +56,29 @@ def test_search_by_bow_keyframes(seed, n1, n2, share):
         np.testing.assert_array_equal(oh["nmatches"], oo["nmatches"])
     if share and n1 >= 400:
         assert oo["nmatches"].min() > 50
+
+
+@pytest.mark.parametrize("above", [False, True])
+def test_search_by_bow_keyframes_contention(above):
+    """M6 under contention (see test_bow_gpu.test_search_by_bow_contention): the free candidates are the KF2 features that
+    carry a MapPoint, and they limit the number of matches."""
+    limit = BP.queries_kept_in_registers()
+    n_q = limit + 104 if above else 2000
+    assert (n_q > limit) == above
+    probs = []
+    for i in range(2):
+        p = BP.make_contended_bow_problem(6500 + i, n_q, 150)
+        probs.append(dict(kps1=p["kf_kps"], desc1=p["kf_desc"], has_mp1=p["kf_has_mp"], kps2=p["f_kps"], desc2=p["f_desc"],
+                          has_mp2=(synth.rng(6600 + i).random(150) < 0.7).astype(np.uint8)))
+    for ori in (1, 0):
+        a, oo, k = M.bow_kf_args(probs, check_ori=ori)
+        O.call("orc_match_bow_kf", a)
+        a2, oh, k2 = M.bow_kf_args(probs, check_ori=ori)
+        H.call("fb_match_bow_kf", a2)
+        np.testing.assert_array_equal(oh["matches12"], oo["matches12"])
+        np.testing.assert_array_equal(oh["nmatches"], oo["nmatches"])
+        for b, p in enumerate(probs):
+            assert 2 * oo["nmatches"][b] >= p["has_mp2"].sum()
 
 
 @pytest.mark.parametrize("seed,n", [(7200, 5000), (7201, 257), (7202, 1), (7203, 0)])
