@@ -305,6 +305,21 @@ class PoseOptArgs(C.Structure):
                 ("Tcw", _vp), ("front_outlier", _vp), ("ninliers", _vp)]
 
 
+class PoseGatherLevels(C.Structure):
+    _fields_ = [("inv_sigma2", _f32 * FB_MAX_LEVELS), ("nlevels", _i32)]
+
+
+class FrameTailFrontArgs(C.Structure):
+    _fields_ = [("m3", ProjFrameArgs), ("edge", PoseGatherLevels), ("front_xw", _vp), ("front_obs", _vp),
+                ("front_inv_sigma2", _vp), ("front_valid", _vp), ("n_front", _vp), ("Tcw", _vp)]
+
+
+class FrameTailBirdArgs(C.Structure):
+    _fields_ = [("m9", BirdMpArgs), ("pixel2meter", C.c_double), ("Tcb", _f32 * 12), ("edge", PoseGatherLevels),
+                ("bird_xw", _vp), ("bird_xc", _vp), ("bird_inv_sigma2", _vp), ("bird_valid", _vp), ("bird_outlier", _vp),
+                ("n_bird", _vp)]
+
+
 class LocalBAArgs(C.Structure):
     _fields_ = [("with_odom", _i32), ("fx", _f32), ("fy", _f32), ("cx", _f32), ("cy", _f32),
                 ("wF", _f32), ("wB", _f32), ("wP", _f32),
@@ -399,6 +414,7 @@ EXPORTS = [
     "fb_covis_tree_erase_keyframe_dev", "fb_covis_local_map_dev", "fb_covis_local_map", "fb_covis_reserve_local_map",
     "fb_in_frustum_dev", "fb_in_frustum", "fb_undistort_keypoints_dev", "fb_undistort_keypoints", "fb_image_bounds",
     "fb_pose_opt_batch_dev", "fb_pose_opt", "fb_pose_gather_front_dev", "fb_pose_gather_bird_dev",
+    "fb_frame_tail_front_dev", "fb_frame_tail_bird_dev",
     "fb_frame_create", "fb_frame_destroy", "fb_frame_extract_dev", "fb_frame_extract", "fb_frame_set_pose_dev",
     "fb_frame_predict_pose_dev", "fb_frame_clear_map_points_dev", "fb_frame_set_map_points_dev",
     "fb_frame_bird_mappoint_match_dev", "fb_frame_search_by_projection_dev", "fb_frame_pose_optimization_dev",

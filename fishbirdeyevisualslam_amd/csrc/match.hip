@@ -25,6 +25,7 @@
 
 #include <type_traits>
 #include "fb_claims.h"
+#include "fb_edge_gather.h"
 #include "fb_frame_geom.h"
 #include "fb_primitives.h"
 #include "fb_rot_hist.h"
@@ -231,15 +232,18 @@ __device__ unsigned long long g_m3_stamps[8];  // probe build only (block 0): st
 #define M3_COUNT(slot_)
 #endif
 
-__global__ __launch_bounds__(MATCH_THREADS) void k_proj_frame(fb_proj_frame_args A, int cacheK, int descInLds) {
+// The body for frame b on a staged target T, whose cell lists came from the caller's arrays (k_proj_frame) or straight from
+// the LDS of the grid build (k_frame_tail_front).  Nothing of T.rest is written before the first barrier here, so a caller
+// may have staged from scratch arrays that lie there.  tail(matchL) runs once, by every thread, behind the stores of the
+// final match array (matchL[i], i < ncur, in LDS).
+template <typename Tail>
+__device__ __forceinline__ void proj_frame_body(const fb_proj_frame_args &A, const TargetLds &T, int b, int cacheK, Tail &&tail) {
   // (its callbacks never ask for a target key point's octave by index: no by-index octave array in LDS, Carve::withOct = false)
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   typedef unsigned short u16;
-  const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+  const int tid = threadIdx.x, nt = blockDim.x;
   const size_t co = (size_t)b * A.cur_stride, lo = (size_t)b * A.last_stride;
   const int ncur = A.n_cur[b], nlast = A.n_last[b];
   M3_T0()
-  const TargetLds T = stage_cur(smem, A, b, descInLds != 0, false);
   int *owners = reinterpret_cast<int *>(T.rest);         // [2][cur_stride]
   uint32_t *cache = reinterpret_cast<uint32_t *>(owners + 2 * A.cur_stride);  // [last_stride][cacheK]  dist << 16 | idx
   u16 *assigns = reinterpret_cast<u16 *>(cache + (size_t)A.last_stride * cacheK);  // [2][last_stride]
@@ -379,10 +383,18 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_proj_frame(fb_proj_frame_args
   }
   for (int i = tid; i < ncur; i += nt) A.match_cur_to_last[co + i] = matchL[i];
   if (tid == 0) { A.nmatches[b] = s_cf.n; if (A.retried) A.retried[b] = attempt; }
+  tail(matchL);
   break;
   }
   M3_TICK(4)
   M3_COUNT(6)
+}
+
+__global__ __launch_bounds__(MATCH_THREADS) void k_proj_frame(fb_proj_frame_args A, int cacheK, int descInLds) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  const int b = blockIdx.x;
+  const TargetLds T = stage_cur(smem, A, b, descInLds != 0, false);
+  proj_frame_body(A, T, b, cacheK, [](const int *) {});
 }
 
 // ---------------------------------------------------------------------------------------
@@ -608,12 +620,15 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_m2_resolve(fb_proj_points_arg
 // ---------------------------------------------------------------------------------------
 // M9  BirdMapPointMatch
 // ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(MATCH_THREADS) void k_bird_mappoints(fb_bird_mp_args A, int descInLds) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
-  const size_t co = (size_t)b * A.cur_stride, ro = (size_t)b * A.ref_stride;
+// The body for frame b on a staged target T (T.rest is not written before the first barrier here).  cam = the frame's
+// mvKeysBirdCamXYZ, [ncur][3], in global memory or LDS.  commit(writer) runs once, by every thread, behind the last barrier:
+// writer[i], i < ncur, is the reference point that took key point i, or -1.
+template <typename Commit>
+__device__ __forceinline__ void bird_mappoints_body(const fb_bird_mp_args &A, const TargetLds &T, int b, const float *cam,
+                                                    Commit &&commit) {
+  const int tid = threadIdx.x, nt = blockDim.x;
+  const size_t ro = (size_t)b * A.ref_stride;
   const int ncur = A.n_cur[b], nref = A.n_ref[b];
-  const TargetLds T = stage_cur(smem, A, b, descInLds != 0);
   int *writer = reinterpret_cast<int *>(T.rest);  // [cur_stride]
   __shared__ float s_Tcw[12], s_Tbw[12];
   __shared__ int s_n;
@@ -652,7 +667,7 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_bird_mappoints(fb_bird_mp_arg
     if (!(bestIdx > 0)) continue;  // sic: vnMatches12[i1] > 0, ORBmatcher.cc:1871
     float pc[3];
     xform(s_Tcw, X, pc);
-    const float *qv = A.cur_cam_xyz + (co + bestIdx) * 3;
+    const float *qv = cam + (size_t)bestIdx * 3;
     const float e0 = pc[0] - qv[0], e1 = pc[1] - qv[1], e2 = pc[2] - qv[2];
     const double disC = sqrt((double)e0 * e0 + (double)e1 * e1 + (double)e2 * e2);
     if (disC < A.filter_size) {
@@ -661,9 +676,20 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_bird_mappoints(fb_bird_mp_arg
     }
   }
   __syncthreads();
-  for (int i = tid; i < ncur; i += nt)
-    if (writer[i] >= 0) A.match_cur_to_ref[co + i] = writer[i];
+  commit(writer);
   if (tid == 0) A.ninliers[b] = s_n;
+}
+
+__global__ __launch_bounds__(MATCH_THREADS) void k_bird_mappoints(fb_bird_mp_args A, int descInLds) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+  const size_t co = (size_t)b * A.cur_stride;
+  const int ncur = A.n_cur[b];
+  const TargetLds T = stage_cur(smem, A, b, descInLds != 0);
+  bird_mappoints_body(A, T, b, A.cur_cam_xyz + co * 3, [&](const int *writer) {  // the caller pre-filled the match array
+    for (int i = tid; i < ncur; i += nt)
+      if (writer[i] >= 0) A.match_cur_to_ref[co + i] = writer[i];
+  });
 }
 
 // ---------------------------------------------------------------------------------------
@@ -744,23 +770,15 @@ __global__ void k_descriptor_distance(const uint4 *__restrict__ a, const uint4 *
 // (cells hold <1 keypoint on average; the sort restores ascending keypoint index, which is
 // the push_back order of Frame.cc:389-396).
 // ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_grid_build(const fb_keypoint *__restrict__ kps, const int32_t *__restrict__ n,
-                                                    int kp_stride, fb_grid_geom g, int32_t *__restrict__ cell_start,
-                                                    int32_t *__restrict__ cell_items, int itemsInLds) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+// The body for one frame, by the NT threads of a workgroup: cnt [ncell+1] and fillp [ncell] live in LDS; ci [kp_stride] is
+// where the items are scattered and sorted (LDS, or the frame's global array).  On return (behind a barrier) cnt holds the
+// cell starts and ci the items; nothing has been stored for the caller yet.
+template <int NT>
+__device__ __forceinline__ void grid_build_body(const fb_keypoint *__restrict__ k, int nk, const fb_grid_geom &g, int *cnt,
+                                                int *fillp, int *ci) {
+  const int tid = threadIdx.x, nt = NT;
   const int ncell = g.cols * g.rows;
-  int *cnt = reinterpret_cast<int *>(smem);  // [ncell+1]
-  int *fillp = cnt + ncell + 1;              // [ncell]
-  // the items are scattered, sorted per cell and written out from LDS (itemsInLds): the per-cell insertion sort on the
-  // global array was a chain of dependent global accesses per cell, 12 cells per lane -- most of this kernel at batch 1
-  int *li = fillp + ncell;                   // [kp_stride] when itemsInLds
-  __shared__ int s_part[256 / 64];
-  const fb_keypoint *k = kps + (size_t)b * kp_stride;
-  int32_t *cs = cell_start + (size_t)b * (ncell + 1);
-  int32_t *cig = cell_items + (size_t)b * kp_stride;
-  int *ci = itemsInLds ? li : cig;
-  const int nk = min(max(n[b], 0), kp_stride);
+  __shared__ int s_part[NT / 64];
   for (int i = tid; i <= ncell; i += nt) cnt[i] = 0;
   __syncthreads();
   auto cell_of = [&](const fb_keypoint &kp) -> int {
@@ -774,15 +792,15 @@ __global__ __launch_bounds__(256) void k_grid_build(const fb_keypoint *__restric
     if (c >= 0) atomicAdd(&cnt[c], 1);
   }
   __syncthreads();
-  // exclusive scan over ncell counters: per-thread chunk sums, then scan of 256 partials
+  // exclusive scan over ncell counters: per-thread chunk sums, then scan of the NT partials
   const int chunk = (ncell + nt - 1) / nt;
   const int c0 = min(tid * chunk, ncell), c1 = min(c0 + chunk, ncell);
   int s = 0;
   for (int c = c0; c < c1; c++) s += cnt[c];
-  // exclusive scan of the 256 chunk sums: shuffles inside a wave, four wave totals through LDS (one lane walking the 256
-  // partials in LDS was half of this kernel at batch 1)
+  // exclusive scan of the NT chunk sums: shuffles inside a wave, the wave totals through LDS (one lane walking the
+  // partials in LDS was half of k_grid_build at batch 1)
   int tot;
-  int run = fb::block_excl_scan<256>(s, s_part, &tot);
+  int run = fb::block_excl_scan<NT>(s, s_part, &tot);
   if (tid == 0) cnt[ncell] = tot;
   __syncthreads();
   for (int c = c0; c < c1; c++) { const int v = cnt[c]; cnt[c] = run; fillp[c] = run; run += v; }
@@ -802,12 +820,39 @@ __global__ __launch_bounds__(256) void k_grid_build(const fb_keypoint *__restric
       ci[j + 1] = v;
     }
   }
+  __syncthreads();
+}
+
+// LDS ints of grid_build_body with the items in LDS / without
+__host__ __device__ inline size_t grid_lds_ints(int ncell, int kp_stride, bool itemsInLds) {
+  return (size_t)(2 * ncell + 1) + (itemsInLds ? (size_t)kp_stride : 0);
+}
+
+// the frame's CSR from LDS (or, for the items, from where they already are) to the caller's arrays
+__device__ __forceinline__ void grid_store(const int *cnt, const int *li, int ncell, int32_t *cs, int32_t *cig) {
+  const int tid = threadIdx.x, nt = blockDim.x;
   for (int i = tid; i <= ncell; i += nt) cs[i] = cnt[i];
-  if (itemsInLds) {
-    __syncthreads();
+  if (li != cig) {
     const int nitems = cnt[ncell];
     for (int i = tid; i < nitems; i += nt) cig[i] = li[i];
   }
+}
+
+__global__ __launch_bounds__(256) void k_grid_build(const fb_keypoint *__restrict__ kps, const int32_t *__restrict__ n,
+                                                    int kp_stride, fb_grid_geom g, int32_t *__restrict__ cell_start,
+                                                    int32_t *__restrict__ cell_items, int itemsInLds) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  const int b = blockIdx.x;
+  const int ncell = g.cols * g.rows;
+  int *cnt = reinterpret_cast<int *>(smem);  // [ncell+1]
+  int *fillp = cnt + ncell + 1;              // [ncell]
+  // the items are scattered, sorted per cell and written out from LDS (itemsInLds): the per-cell insertion sort on the
+  // global array was a chain of dependent global accesses per cell, 12 cells per lane -- most of this kernel at batch 1
+  int *li = fillp + ncell;                   // [kp_stride] when itemsInLds
+  int32_t *cig = cell_items + (size_t)b * kp_stride;
+  int *ci = itemsInLds ? li : cig;
+  grid_build_body<256>(kps + (size_t)b * kp_stride, min(max(n[b], 0), kp_stride), g, cnt, fillp, ci);
+  grid_store(cnt, ci, ncell, cell_start + (size_t)b * (ncell + 1), cig);
 }
 
 // Frame.cc:365-373: BirdPixel2BaseXY (Converter.cc:284-292) then BaseXY2CamXYZ (:312-318)
@@ -816,20 +861,102 @@ struct BirdCamK {
   double pixel2meter, rear;
   float Tcb[12];
 };
+__device__ __forceinline__ void bird_key_to_cam(const fb_keypoint &kp, const BirdCamK &K, float o[3]) {
+  float p[3];
+  p[0] = (float)((K.rows / 2 - kp.y) * K.pixel2meter + K.rear);
+  p[1] = (float)((K.cols / 2 - kp.x) * K.pixel2meter);
+  p[2] = 0.f;
+  xform(K.Tcb, p, o);
+}
 __global__ void k_bird_keys_to_cam(const fb_keypoint *__restrict__ kps, const int32_t *__restrict__ n, int kp_stride,
                                    BirdCamK K, float *__restrict__ cam) {
   const int b = blockIdx.y;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n[b]) return;
-  const fb_keypoint kp = kps[(size_t)b * kp_stride + i];
-  float p[3];
-  p[0] = (float)((K.rows / 2 - kp.y) * K.pixel2meter + K.rear);
-  p[1] = (float)((K.cols / 2 - kp.x) * K.pixel2meter);
-  p[2] = 0.f;
   float o[3];
-  xform(K.Tcb, p, o);
+  bird_key_to_cam(kps[(size_t)b * kp_stride + i], K, o);
   float *dst = cam + ((size_t)b * kp_stride + i) * 3;
   dst[0] = o[0]; dst[1] = o[1]; dst[2] = o[2];
+}
+
+// ---------------------------------------------------------------------------------------
+// The per-frame tail of the tracking step in one launch per camera, one workgroup per frame pair:
+//   front: AssignFeaturesToGrid -> M3 -> front edges of PoseOptimizationWithBird, n_front, SetPose(prediction)
+//   bird : AssignFeaturesToGrid -> mvKeysBirdCamXYZ -> M9 on a fresh mvpMapPointsBird -> bird edges, n_bird, fresh mvBirdOutlier
+// The cell lists are built in LDS and staged from there (they are still stored: callers read them); the grid's scratch arrays
+// lie where the matcher's own arrays (T.rest) begin and are dead before those are first written.
+// ---------------------------------------------------------------------------------------
+struct GridScratch { int *cnt, *fillp, *items; };
+// builds frame b's grid at `at`, stores it to cell_start / cell_items (written here, whatever the struct's const says)
+template <typename Args>
+__device__ __forceinline__ GridScratch tail_grid(uint8_t *at, const Args &A, int b, bool itemsInLds) {
+  const int ncell = A.grid.cols * A.grid.rows;
+  const size_t co = (size_t)b * A.cur_stride;
+  GridScratch G;
+  G.cnt = reinterpret_cast<int *>(at);
+  G.fillp = G.cnt + ncell + 1;
+  int32_t *cig = const_cast<int32_t *>(A.cur_cell_items) + co;
+  G.items = itemsInLds ? G.fillp + ncell : cig;
+  grid_build_body<MATCH_THREADS>(A.cur_kps + co, min(max(A.n_cur[b], 0), A.cur_stride), A.grid, G.cnt, G.fillp, G.items);
+  grid_store(G.cnt, G.items, ncell, const_cast<int32_t *>(A.cur_cell_start) + (size_t)b * (ncell + 1), cig);
+  return G;
+}
+
+__global__ __launch_bounds__(MATCH_THREADS) void k_frame_tail_front(fb_frame_tail_front_args F, int cacheK, int descInLds,
+                                                                    int itemsInLds) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  const fb_proj_frame_args &A = F.m3;
+  const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+  const int ncell = A.grid.cols * A.grid.rows;
+  const size_t co = (size_t)b * A.cur_stride;
+  const int ncur = A.n_cur[b];
+  const Carve cv(A.cur_stride, ncell, descInLds != 0, false);
+  const GridScratch G = tail_grid(smem + cv.end, A, b, itemsInLds != 0);
+  if (!itemsInLds) __syncthreads();  // the items come back from the global array
+  const TargetLds T = stage_target(smem, cv, ncur, ncell, A.cur_kps + co, A.cur_desc + co * 32, G.cnt, G.items, descInLds != 0);
+  if (tid == 0) F.n_front[b] = ncur;
+  if (tid < 12) F.Tcw[(size_t)b * 12 + tid] = A.cur_Tcw[(size_t)b * 12 + tid];  // SetPose(prediction), Tracking.cc:1314-1320
+  proj_frame_body(A, T, b, cacheK, [&](const int *matchL) {
+    const float *mp = A.last_xw + (size_t)b * A.last_stride * 3;
+    for (int i = tid; i < A.cur_stride; i += nt)
+      fb::gather_front_edge(co + i, i < ncur ? matchL[i] : -1, A.cur_kps, mp, F.edge, F.front_xw, F.front_obs, F.front_inv_sigma2,
+                            F.front_valid);
+  });
+}
+
+__global__ __launch_bounds__(MATCH_THREADS) void k_frame_tail_bird(fb_frame_tail_bird_args F, BirdCamK K, int descInLds,
+                                                                   int itemsInLds, int camInLds) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  const fb_bird_mp_args &A = F.m9;
+  const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+  const int ncell = A.grid.cols * A.grid.rows;
+  const size_t co = (size_t)b * A.cur_stride;
+  const int ncur = A.n_cur[b];
+  const Carve cv(A.cur_stride, ncell, descInLds != 0);
+  const GridScratch G = tail_grid(smem + cv.end, A, b, itemsInLds != 0);
+  if (!itemsInLds) __syncthreads();
+  const TargetLds T = stage_target(smem, cv, ncur, ncell, A.cur_kps + co, A.cur_desc + co * 32, G.cnt, G.items, descInLds != 0);
+  __syncthreads();  // the grid's scratch is dead: the LDS copy of the camera positions lies over it
+  // mvKeysBirdCamXYZ: stored for the caller; M9 and the edges read the LDS copy (behind the body's writer array) when it fits
+  float *gcam = const_cast<float *>(A.cur_cam_xyz) + co * 3;
+  float *lcam = reinterpret_cast<float *>(T.rest) + A.cur_stride;
+  for (int i = tid; i < ncur; i += nt) {
+    float o[3];
+    bird_key_to_cam(A.cur_kps[co + i], K, o);
+    gcam[i * 3] = o[0]; gcam[i * 3 + 1] = o[1]; gcam[i * 3 + 2] = o[2];
+    if (camInLds) { lcam[i * 3] = o[0]; lcam[i * 3 + 1] = o[1]; lcam[i * 3 + 2] = o[2]; }
+  }
+  if (tid == 0) F.n_bird[b] = ncur;
+  const float *cam = camInLds ? lcam : gcam;
+  bird_mappoints_body(A, T, b, cam, [&](const int *writer) {
+    const float *mp = A.ref_xw + (size_t)b * A.ref_stride * 3;
+    for (int i = tid; i < A.cur_stride; i += nt) {
+      const int m = i < ncur ? writer[i] : -1;   // a fresh mvpMapPointsBird: every slot of the stride is written
+      A.match_cur_to_ref[co + i] = m;
+      F.bird_outlier[co + i] = 1;                // mvBirdOutlier = vector<bool>(Nbird, true) of a fresh Frame (Frame.cc:356)
+      fb::gather_bird_edge(co + i, m, A.cur_kps, cam + (size_t)i * 3, mp, F.edge, F.bird_xw, F.bird_xc, F.bird_inv_sigma2, F.bird_valid);
+    }
+  });
 }
 
 size_t match_lds_bytes(int cur_stride, int ncell, int extra_ints, bool withDesc = true, bool withOct = true) {
@@ -1019,6 +1146,69 @@ int fb_match_bird_mappoints_dev(const fb_bird_mp_args *A, void *stream) {
   FB_TRY(set_max_lds(k_bird_mappoints, lds));
   fb::ProfScope prof_(fb::P_BIRD_MP, fb::as_stream(stream));
   k_bird_mappoints<<<A->batch, MATCH_THREADS, lds, fb::as_stream(stream)>>>(*A, lp.descInLds);
+  FB_HIP(hipGetLastError());
+  return FB_OK;
+}
+
+int fb_frame_tail_front_dev(const fb_frame_tail_front_args *F, void *stream) {
+  FB_TRY(fb::check_device());
+  FB_ARG(F);
+  const fb_proj_frame_args *A = &F->m3;
+  FB_ARG(A->batch >= 0 && A->cur_stride > 0 && A->last_stride >= 0 && A->cur_stride < 65536);
+  FB_ARG(A->grid.cols > 0 && A->grid.rows > 0 && F->edge.nlevels >= 1 && F->edge.nlevels <= FB_MAX_LEVELS);
+  FB_ARG(A->cur_cell_start && A->cur_cell_items && F->n_front && F->Tcw && F->front_xw && F->front_obs && F->front_inv_sigma2 && F->front_valid);
+  if (A->batch == 0) return FB_OK;
+  const int ncell = A->grid.cols * A->grid.rows;
+  // the matcher's plan is that of fb_match_projection_frame_dev; the grid's scratch shares the matcher's own arrays, with the
+  // items in LDS when that fits (the bench's 64x48 cells at 2064 key points: descriptors, cache and items all in LDS)
+  const int base_ints = 2 * A->cur_stride + 2 * A->last_stride + 4;
+  static const bool noCache = getenv("FB_M3_NO_CACHE") != nullptr;
+  int cacheK = noCache ? 0 : CACHE_K, descInLds = 1;
+  size_t lds = match_lds_bytes(A->cur_stride, ncell, base_ints + cacheK * A->last_stride, true, false);
+  if (lds > LDS_BUDGET) { cacheK = 0; lds = match_lds_bytes(A->cur_stride, ncell, base_ints, true, false); }
+  if (lds > LDS_BUDGET) { cacheK = CACHE_K; descInLds = 0; lds = match_lds_bytes(A->cur_stride, ncell, base_ints + cacheK * A->last_stride, false, false); }
+  if (lds > LDS_BUDGET) { cacheK = 0; lds = match_lds_bytes(A->cur_stride, ncell, base_ints, false, false); }
+  const size_t staged = Carve(A->cur_stride, ncell, descInLds != 0, false).end;
+  int itemsInLds = 1;
+  size_t gridLds = staged + grid_lds_ints(ncell, A->cur_stride, true) * 4;
+  if (gridLds > LDS_BUDGET) { itemsInLds = 0; gridLds = staged + grid_lds_ints(ncell, A->cur_stride, false) * 4; }
+  if (gridLds > lds) lds = gridLds;
+  FB_TRY(check_lds(lds, "fb_frame_tail_front"));
+  FB_TRY(set_max_lds(k_frame_tail_front, lds));
+  fb::ProfScope prof_(fb::P_TAIL_FRONT, fb::as_stream(stream));
+  k_frame_tail_front<<<A->batch, MATCH_THREADS, lds, fb::as_stream(stream)>>>(*F, cacheK, descInLds, itemsInLds);
+  FB_HIP(hipGetLastError());
+  return FB_OK;
+}
+
+int fb_frame_tail_bird_dev(const fb_frame_tail_bird_args *F, void *stream) {
+  FB_TRY(fb::check_device());
+  FB_ARG(F);
+  const fb_bird_mp_args *A = &F->m9;
+  FB_ARG(A->batch >= 0 && A->cur_stride > 0 && A->ref_stride >= 0 && A->cur_stride < 65536);
+  FB_ARG(A->grid.cols > 0 && A->grid.rows > 0 && F->edge.nlevels >= 1 && F->edge.nlevels <= FB_MAX_LEVELS);
+  FB_ARG(A->cur_cell_start && A->cur_cell_items && A->cur_cam_xyz && A->match_cur_to_ref && F->n_bird && F->bird_outlier && F->bird_xw &&
+         F->bird_xc && F->bird_inv_sigma2 && F->bird_valid);
+  if (A->batch == 0) return FB_OK;
+  const int ncell = A->grid.cols * A->grid.rows;
+  // writer array + the camera positions in LDS when they fit beside the staged frame, else the matcher's own plan
+  int camInLds = 1;
+  LdsPlan lp;
+  lp.descInLds = 1;
+  lp.bytes = Carve(A->cur_stride, ncell, true).end + (size_t)A->cur_stride * 16;
+  if (lp.bytes > LDS_BUDGET) { camInLds = 0; FB_TRY(plan_lds(A->cur_stride, ncell, A->cur_stride, "fb_frame_tail_bird", &lp)); }
+  const size_t staged = Carve(A->cur_stride, ncell, lp.descInLds != 0).end;
+  int itemsInLds = 1;
+  size_t gridLds = staged + grid_lds_ints(ncell, A->cur_stride, true) * 4;
+  if (gridLds > LDS_BUDGET) { itemsInLds = 0; gridLds = staged + grid_lds_ints(ncell, A->cur_stride, false) * 4; }
+  size_t lds = lp.bytes > gridLds ? lp.bytes : gridLds;
+  FB_TRY(check_lds(lds, "fb_frame_tail_bird"));
+  FB_TRY(set_max_lds(k_frame_tail_bird, lds));
+  BirdCamK K;
+  K.cols = A->bird_cols; K.rows = A->bird_rows; K.pixel2meter = F->pixel2meter; K.rear = A->rear_axle_to_center;
+  memcpy(K.Tcb, F->Tcb, sizeof(K.Tcb));
+  fb::ProfScope prof_(fb::P_TAIL_BIRD, fb::as_stream(stream));
+  k_frame_tail_bird<<<A->batch, MATCH_THREADS, lds, fb::as_stream(stream)>>>(*F, K, lp.descInLds, itemsInLds, camInLds);
   FB_HIP(hipGetLastError());
   return FB_OK;
 }

@@ -26,6 +26,7 @@
 // own), which leaves through pose_generic for a frame with more edges than its slots.
 #include <type_traits>
 #include "fb_common.h"
+#include "fb_edge_gather.h"
 #include "fb_primitives.h"
 #include "fb_se3.h"
 
@@ -912,7 +913,7 @@ __global__ __launch_bounds__(NT) void k_pose_opt_regs(fb_pose_opt_args A) {
 }
 
 // --- device-side edge construction (Optimizer.cc:525-602) --------------------------------
-struct GatherK { float inv_sigma2[FB_MAX_LEVELS]; int nlevels; };
+using fb::GatherK;  // fb_edge_gather.h: one edge per key point slot, shared with the fused tail kernels of match.hip
 
 __global__ void k_gather_front(int kp_stride, int mp_stride, const int32_t *__restrict__ n, const fb_keypoint *__restrict__ kps,
                                const int32_t *__restrict__ match, const float *__restrict__ mp_xw, GatherK G,
@@ -921,14 +922,7 @@ __global__ void k_gather_front(int kp_stride, int mp_stride, const int32_t *__re
   const int b = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= kp_stride) return;
   const size_t o = (size_t)b * kp_stride + i;
-  const int m = (i < n[b]) ? match[o] : -1;
-  if (m < 0) { valid[o] = 0; return; }
-  const fb_keypoint kp = kps[o];
-  const float *X = mp_xw + ((size_t)b * mp_stride + m) * 3;
-  xw[o * 3] = X[0]; xw[o * 3 + 1] = X[1]; xw[o * 3 + 2] = X[2];
-  obs[o * 2] = kp.x; obs[o * 2 + 1] = kp.y;
-  inf[o] = G.inv_sigma2[kp.octave];
-  valid[o] = 1;
+  fb::gather_front_edge(o, (i < n[b]) ? match[o] : -1, kps, mp_xw + (size_t)b * mp_stride * 3, G, xw, obs, inf, valid);
 }
 
 __global__ void k_gather_bird(int kp_stride, int mp_stride, const int32_t *__restrict__ n, const fb_keypoint *__restrict__ kps,
@@ -938,22 +932,10 @@ __global__ void k_gather_bird(int kp_stride, int mp_stride, const int32_t *__res
   const int b = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= kp_stride) return;
   const size_t o = (size_t)b * kp_stride + i;
-  const int m = (i < n[b]) ? match[o] : -1;
-  if (m < 0) { valid[o] = 0; return; }
-  const float *X = mpb_xw + ((size_t)b * mp_stride + m) * 3;
-  xw[o * 3] = X[0]; xw[o * 3 + 1] = X[1]; xw[o * 3 + 2] = X[2];
-  xc[o * 3] = cam[o * 3]; xc[o * 3 + 1] = cam[o * 3 + 1]; xc[o * 3 + 2] = cam[o * 3 + 2];
-  inf[o] = G.inv_sigma2[kps[o].octave];
-  valid[o] = 1;
+  fb::gather_bird_edge(o, (i < n[b]) ? match[o] : -1, kps, cam + o * 3, mpb_xw + (size_t)b * mp_stride * 3, G, xw, xc, inf, valid);
 }
 
-GatherK make_gather_k(const float *inv_level_sigma2, int nlevels) {
-  GatherK G;
-  memset(&G, 0, sizeof(G));
-  G.nlevels = nlevels;
-  for (int i = 0; i < nlevels; i++) G.inv_sigma2[i] = inv_level_sigma2[i];
-  return G;
-}
+using fb::make_gather_k;
 
 // one launch of the register-resident kernel, with the dynamic LDS its own shape asks for
 template <int NT, int NE, int EF, int EB>

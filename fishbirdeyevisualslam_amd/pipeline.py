@@ -4,6 +4,11 @@ pairs (one tracked sequence each), every stage through the C-ABI (*_dev entry po
 
 This is the order Tracking::GrabImageMonocularWithOdom -> TrackWithMotionModel runs them
 (Tracking.cc:292-339, 1312-1385).  torch is used only for device memory and the stream.
+
+Everything behind the extraction of a camera -- grid, matcher, edge gather, the counts and the predicted pose -- is ONE
+launch (fb_frame_tail_front_dev / fb_frame_tail_bird_dev).  step() runs both on the pose stream, ahead of the pose
+kernel, so that the extraction streams carry nothing but extraction; for that every buffer between extraction and pose
+optimisation exists twice (set k & 1 belongs to step k).
 """
 import ctypes as C
 
@@ -41,36 +46,33 @@ class FramePipeline:
         B, cap, d = batch, self.cap, self.dev
         z = lambda *s, dt=torch.uint8: torch.zeros(*s, dtype=dt, device=d)
         self.f_img, self.b_img = z(B, self.fh, self.fw), z(B, self.bh, self.bw)
-        self.f_kps, self.b_kps = z(B, cap * 24), z(B, cap * 24)
-        self.f_desc, self.b_desc = z(B, cap, 32), z(B, cap, 32)
-        self.f_n, self.b_n = z(B, dt=torch.int32), z(B, dt=torch.int32)
         self.geom_f = fill(cabi.GridGeom(), **synth.front_grid_geom(self.fw, self.fh))
         self.geom_b = fill(cabi.GridGeom(), **synth.bird_grid_geom(self.bw, self.bh))
-        self.f_cs = z(B, self.geom_f.cols * self.geom_f.rows + 1, dt=torch.int32)
-        self.b_cs = z(B, self.geom_b.cols * self.geom_b.rows + 1, dt=torch.int32)
-        self.f_ci, self.b_ci = z(B, cap, dt=torch.int32), z(B, cap, dt=torch.int32)
-        self.b_cam = z(B, cap, 3, dt=torch.float32)
         # last frame / reference bird map points (filled by set_map)
         self.nl, self.nr = n_last, n_ref
         self.last = dict(valid=z(B, n_last), obs=z(B, n_last), xw=z(B, n_last, 3, dt=torch.float32), desc=z(B, n_last, 32),
                          octave=z(B, n_last, dt=torch.int32), angle=z(B, n_last, dt=torch.float32), n=z(B, dt=torch.int32))
         self.ref = dict(valid=z(B, n_ref), xw=z(B, n_ref, 3, dt=torch.float32), desc=z(B, n_ref, 32), n=z(B, dt=torch.int32))
         self.Tcw0 = z(B, 12, dt=torch.float32)
-        # match buffers
-        self.m_front, self.nm_front = z(B, cap, dt=torch.int32), z(B, dt=torch.int32)
-        self.m_bird, self.nm_bird = z(B, cap, dt=torch.int32), z(B, dt=torch.int32)
-        # pose stage: edge arrays, pose, outlier flags and counts exist TWICE (set k & 1 belongs to step k), so that the edge
-        # gather of step k + 1 does not have to wait for the pose kernel of step k to let go of its inputs: consecutive pose
-        # kernels run back to back (at B = 1 the wait was 60 us of a 398 us step)
+        # Everything a step writes exists TWICE (set k & 1 belongs to step k): what extraction writes and the tail reads
+        # (key points, descriptors, counts), the tail's own outputs (cell lists, bird camera positions, matches) and the
+        # pose stage (edge arrays, pose, outlier flags, counts).  The extraction of step k + 1 therefore never waits for
+        # the tail or the pose kernel of step k; a set is reused two steps later, behind its evP.
+        ncf, ncb = self.geom_f.cols * self.geom_f.rows + 1, self.geom_b.cols * self.geom_b.rows + 1
         self._sets = []
         for _ in range(2):
             self._sets.append(dict(
+                f_kps=z(B, cap * 24), b_kps=z(B, cap * 24), f_desc=z(B, cap, 32), b_desc=z(B, cap, 32),
+                f_n=z(B, dt=torch.int32), b_n=z(B, dt=torch.int32), f_cs=z(B, ncf, dt=torch.int32), b_cs=z(B, ncb, dt=torch.int32),
+                f_ci=z(B, cap, dt=torch.int32), b_ci=z(B, cap, dt=torch.int32), b_cam=z(B, cap, 3, dt=torch.float32),
+                m_front=z(B, cap, dt=torch.int32), nm_front=z(B, dt=torch.int32), m_bird=z(B, cap, dt=torch.int32), nm_bird=z(B, dt=torch.int32),
                 Tcw=z(B, 12, dt=torch.float32), e_fxw=z(B, cap, 3, dt=torch.float32), e_fobs=z(B, cap, 2, dt=torch.float32),
                 e_finf=z(B, cap, dt=torch.float32), e_fvalid=z(B, cap), e_fout=z(B, cap), e_bxw=z(B, cap, 3, dt=torch.float32),
                 e_bxc=z(B, cap, 3, dt=torch.float32), e_binf=z(B, cap, dt=torch.float32), e_bvalid=z(B, cap), e_bout=z(B, cap),
                 ninl=z(B, dt=torch.int32), e_nf=z(B, dt=torch.int32), e_nb=z(B, dt=torch.int32), evP=torch.cuda.Event(), pending=False))
+        self._last = self._sets[0]  # the set of the last step (of build_world's extraction before the first one)
         self._k = 0  # step counter; results_host() reads the set of the last step
-        # three streams: front chain, bird chain, pose optimisation (latency-bound, overlaps the next extraction)
+        # three streams: front extraction, bird extraction, tails + pose optimisation (latency-bound, overlap the next extraction)
         # (the three streams are shared by every pipeline of a device: the HIP runtime folds streams onto a few hardware queues,
         # and streams that land on one queue serialise -- a second pipeline with streams of its own measured 0.72 instead of
         # 0.47 ms per step at B = 8)
@@ -89,31 +91,48 @@ class FramePipeline:
                 self.L.fb_orb_destroy(h)
         self.orb_f = self.orb_b = C.c_void_p()
 
-    # ---- argument structs (pointers are fixed for the lifetime of the pipeline) ----
+    # the buffers of the last step's set under their plain names (pipe.f_kps, pipe.m_front, ...)
+    def __getattr__(self, name):
+        sets = self.__dict__.get("_last")
+        if sets is not None and name in sets:
+            return sets[name]
+        raise AttributeError(name)
+
+    # ---- argument structs (pointers are fixed for the lifetime of the pipeline), one of each per set ----
     def _build_args(self):
-        B, cap = self.B, self.cap
-        a = cabi.ProjFrameArgs()
-        fill(a, batch=B, cur_stride=cap, last_stride=self.nl, n_cur=self.f_n, cur_kps=self.f_kps, cur_desc=self.f_desc,
-             cur_cell_start=self.f_cs, cur_cell_items=self.f_ci, cur_blocked=None, cur_Tcw=self.Tcw0,
-             n_last=self.last["n"], last_valid=self.last["valid"], last_obs_pos=self.last["obs"], last_xw=self.last["xw"],
-             last_desc=self.last["desc"], last_octave=self.last["octave"], last_angle=self.last["angle"], th=15.0,
-             match_cur_to_last=self.m_front, nmatches=self.nm_front,
-             scale_factors=[self.tables.scale_factor[i] for i in range(cabi.FB_MAX_LEVELS)])
-        fill(a.cam, fx=self.fx, fy=self.fy, cx=self.cx, cy=self.cy, min_x=0.0, min_y=0.0, max_x=float(self.fw), max_y=float(self.fh))
-        a.grid = self.geom_f
-        fill(a.matcher, nnratio=0.9, check_orientation=1)  # ORBmatcher matcher(0.9,true), Tracking.cc:1339
-        self.a_m3 = a
-        m = cabi.BirdMpArgs()
-        fill(m, batch=B, cur_stride=cap, ref_stride=self.nr, n_cur=self.b_n, cur_kps=self.b_kps, cur_desc=self.b_desc,
-             cur_cam_xyz=self.b_cam, cur_cell_start=self.b_cs, cur_cell_items=self.b_ci, cur_Tcw=self.Tcw0,
-             n_ref=self.ref["n"], ref_valid=self.ref["valid"], ref_xw=self.ref["xw"], ref_desc=self.ref["desc"],
-             Tbc=[float(x) for x in self.Tbc[:3, :4].reshape(12)], bird_cols=self.bw, bird_rows=self.bh,
-             meter2pixel=synth.METER2PIXEL, rear_axle_to_center=synth.REAR_AXLE_TO_CENTER, window_size=10,
-             filter_size=0.05, match_cur_to_ref=self.m_bird, ninliers=self.nm_bird)
-        m.grid = self.geom_b
-        fill(m.matcher, nnratio=0.9, check_orientation=1)  # Tracking.cc:2008
-        self.a_m9 = m
+        B, cap, nl = self.B, self.cap, self.params.nlevels
         for S in self._sets:
+            tf = cabi.FrameTailFrontArgs()
+            a = tf.m3
+            fill(a, batch=B, cur_stride=cap, last_stride=self.nl, n_cur=S["f_n"], cur_kps=S["f_kps"], cur_desc=S["f_desc"],
+                 cur_cell_start=S["f_cs"], cur_cell_items=S["f_ci"], cur_blocked=None, cur_Tcw=self.Tcw0,
+                 n_last=self.last["n"], last_valid=self.last["valid"], last_obs_pos=self.last["obs"], last_xw=self.last["xw"],
+                 last_desc=self.last["desc"], last_octave=self.last["octave"], last_angle=self.last["angle"], th=15.0,
+                 match_cur_to_last=S["m_front"], nmatches=S["nm_front"],
+                 scale_factors=[self.tables.scale_factor[i] for i in range(cabi.FB_MAX_LEVELS)])
+            fill(a.cam, fx=self.fx, fy=self.fy, cx=self.cx, cy=self.cy, min_x=0.0, min_y=0.0, max_x=float(self.fw), max_y=float(self.fh))
+            a.grid = self.geom_f
+            fill(a.matcher, nnratio=0.9, check_orientation=1)  # ORBmatcher matcher(0.9,true), Tracking.cc:1339
+            fill(tf.edge, inv_sigma2=[self.tables.inv_level_sigma2[i] for i in range(nl)], nlevels=nl)
+            fill(tf, front_xw=S["e_fxw"], front_obs=S["e_fobs"], front_inv_sigma2=S["e_finf"], front_valid=S["e_fvalid"],
+                 n_front=S["e_nf"], Tcw=S["Tcw"])   # Tcw = Tcw0: SetPose(prediction), Tracking.cc:1314-1320
+            S["a_tail_front"] = tf
+            tb = cabi.FrameTailBirdArgs()
+            m = tb.m9
+            fill(m, batch=B, cur_stride=cap, ref_stride=self.nr, n_cur=S["b_n"], cur_kps=S["b_kps"], cur_desc=S["b_desc"],
+                 cur_cam_xyz=S["b_cam"], cur_cell_start=S["b_cs"], cur_cell_items=S["b_ci"], cur_Tcw=self.Tcw0,
+                 n_ref=self.ref["n"], ref_valid=self.ref["valid"], ref_xw=self.ref["xw"], ref_desc=self.ref["desc"],
+                 Tbc=[float(x) for x in self.Tbc[:3, :4].reshape(12)], bird_cols=self.bw, bird_rows=self.bh,
+                 meter2pixel=synth.METER2PIXEL, rear_axle_to_center=synth.REAR_AXLE_TO_CENTER, window_size=10,
+                 filter_size=0.05, match_cur_to_ref=S["m_bird"], ninliers=S["nm_bird"])
+            m.grid = self.geom_b
+            fill(m.matcher, nnratio=0.9, check_orientation=1)  # Tracking.cc:2008
+            fill(tb.edge, inv_sigma2=[self.tables.inv_level_sigma2[i] for i in range(nl)], nlevels=nl)
+            # m_bird starts at -1 (mvpMapPointsBird of a new frame) and e_bout at 1 (mvBirdOutlier of a fresh Frame,
+            # Frame.cc:356): the tail kernel writes both over the whole stride
+            fill(tb, pixel2meter=synth.PIXEL2METER, Tcb=list(self._Tcb12), bird_xw=S["e_bxw"], bird_xc=S["e_bxc"],
+                 bird_inv_sigma2=S["e_binf"], bird_valid=S["e_bvalid"], bird_outlier=S["e_bout"], n_bird=S["e_nb"])
+            S["a_tail_bird"] = tb
             p = cabi.PoseOptArgs()
             fill(p, batch=B, mode=cabi.FB_POSE_FRONT_BIRD, front_stride=cap, bird_stride=cap, fx=self.fx, fy=self.fy,
                  cx=self.cx, cy=self.cy, wF=1.0, wB=1.0, n_front=S["e_nf"], front_xw=S["e_fxw"], front_obs=S["e_fobs"],
@@ -122,79 +141,61 @@ class FramePipeline:
                  Tcw=S["Tcw"], front_outlier=S["e_fout"], ninliers=S["ninl"])
             S["a_pose"] = p
 
-    # ---- stages ----
-    def extract(self, s, which="both"):
-        L, B = self.L, self.B
+    # ---- stages (S = the set they work on; by default the last step's) ----
+    def extract(self, s, which="both", S=None):
+        L, B, S = self.L, self.B, S or self._last
         if which in ("both", "front"):
             check(L.fb_orb_extract_batch_dev(self.orb_f, _vp(self.f_img), B, self.fw, self.fh, self.fw, C.c_size_t(self.fw * self.fh),
-                                             _vp(self.f_kps), _vp(self.f_desc), _vp(self.f_n), s), "extract front")
+                                             _vp(S["f_kps"]), _vp(S["f_desc"]), _vp(S["f_n"]), s), "extract front")
         if which in ("both", "bird"):
             check(L.fb_orb_extract_batch_dev(self.orb_b, _vp(self.b_img), B, self.bw, self.bh, self.bw, C.c_size_t(self.bw * self.bh),
-                                             _vp(self.b_kps), _vp(self.b_desc), _vp(self.b_n), s), "extract bird")
+                                             _vp(S["b_kps"]), _vp(S["b_desc"]), _vp(S["b_n"]), s), "extract bird")
 
-    def grids(self, s, which="both"):
-        L, B, cap = self.L, self.B, self.cap
+    def grids(self, s, which="both", S=None):
+        """The cell lists and the bird camera positions alone (build_world; a step gets them from its tail launches)."""
+        L, B, cap, S = self.L, self.B, self.cap, S or self._last
         if which in ("both", "front"):
-            check(L.fb_grid_build_batch_dev(_vp(self.f_kps), _vp(self.f_n), B, cap, C.byref(self.geom_f), _vp(self.f_cs), _vp(self.f_ci), s), "grid front")
+            check(L.fb_grid_build_batch_dev(_vp(S["f_kps"]), _vp(S["f_n"]), B, cap, C.byref(self.geom_f), _vp(S["f_cs"]), _vp(S["f_ci"]), s), "grid front")
         if which in ("both", "bird"):
-            check(L.fb_grid_build_batch_dev(_vp(self.b_kps), _vp(self.b_n), B, cap, C.byref(self.geom_b), _vp(self.b_cs), _vp(self.b_ci), s), "grid bird")
-            check(L.fb_bird_keys_to_cam_dev(_vp(self.b_kps), _vp(self.b_n), B, cap, self.bw, self.bh, C.c_double(synth.PIXEL2METER),
-                                            C.c_double(synth.REAR_AXLE_TO_CENTER), self._Tcb12, _vp(self.b_cam), s), "bird cam")
+            check(L.fb_grid_build_batch_dev(_vp(S["b_kps"]), _vp(S["b_n"]), B, cap, C.byref(self.geom_b), _vp(S["b_cs"]), _vp(S["b_ci"]), s), "grid bird")
+            check(L.fb_bird_keys_to_cam_dev(_vp(S["b_kps"]), _vp(S["b_n"]), B, cap, self.bw, self.bh, C.c_double(synth.PIXEL2METER),
+                                            C.c_double(synth.REAR_AXLE_TO_CENTER), self._Tcb12, _vp(S["b_cam"]), s), "bird cam")
 
-    def match_front(self, s):
-        check(self.L.fb_match_projection_frame_dev(C.byref(self.a_m3), s), "M3")
+    def tail_front(self, s, S):
+        """grid -> M3 -> front edges, e_nf, Tcw = Tcw0, in one launch"""
+        check(self.L.fb_frame_tail_front_dev(C.byref(S["a_tail_front"]), s), "tail front")
 
-    def match_bird(self, s):
-        self.m_bird.fill_(-1)  # mvpMapPointsBird starts empty for a new frame
-        check(self.L.fb_match_bird_mappoints_dev(C.byref(self.a_m9), s), "M9")
-
-    def gather_front(self, s, S):
-        L, B, cap, nl = self.L, self.B, self.cap, self.params.nlevels
-        S["e_nf"].copy_(self.f_n)
-        S["Tcw"].copy_(self.Tcw0)   # SetPose(prediction), Tracking.cc:1314-1320
-        check(L.fb_pose_gather_front_dev(B, cap, self.nl, _vp(self.f_n), _vp(self.f_kps), _vp(self.m_front), _vp(self.last["xw"]),
-                                         self._inv_sigma2, nl, _vp(S["e_fxw"]), _vp(S["e_fobs"]), _vp(S["e_finf"]), _vp(S["e_fvalid"]), s), "gather front")
-
-    def gather_bird(self, s, S):
-        L, B, cap, nl = self.L, self.B, self.cap, self.params.nlevels
-        S["e_nb"].copy_(self.b_n)
-        S["e_bout"].fill_(1)        # mvBirdOutlier = vector<bool>(Nbird, true) of a fresh Frame (Frame.cc:356)
-        check(L.fb_pose_gather_bird_dev(B, cap, self.nr, _vp(self.b_n), _vp(self.b_kps), _vp(self.b_cam), _vp(self.m_bird), _vp(self.ref["xw"]),
-                                        self._inv_sigma2, nl, _vp(S["e_bxw"]), _vp(S["e_bxc"]), _vp(S["e_binf"]), _vp(S["e_bvalid"]), s), "gather bird")
+    def tail_bird(self, s, S):
+        """grid -> bird camera positions -> M9 on a fresh match array -> bird edges, e_nb, fresh outlier flags, in one launch"""
+        check(self.L.fb_frame_tail_bird_dev(C.byref(S["a_tail_bird"]), s), "tail bird")
 
     def pose(self, s, S):
         check(self.L.fb_pose_opt_batch_dev(C.byref(S["a_pose"]), s), "pose opt")
 
     def step(self):
-        """One pass of the hot path over the batch.  The front chain and the bird chain run on their own streams;
-        the pose optimisation (one workgroup per frame, latency bound) runs on a third one so that it overlaps the
-        next step's extraction.  Callers synchronise with torch.cuda.synchronize() / results_host()."""
+        """One pass of the hot path over the batch.  The front and the bird extraction run on their own streams; the two
+        tail launches and the pose optimisation (one workgroup per frame, latency bound) run on a third one, where they
+        overlap the next step's extraction.  Callers synchronise with torch.cuda.synchronize() / results_host()."""
         cur = torch.cuda.current_stream(self.dev)
         S = self._sets[self._k & 1]
         self.sF.wait_stream(cur)
         self.sB.wait_stream(cur)
+        if S["pending"]:  # the tails and the pose kernel of two steps ago read this set (long done in steady state)
+            self.sF.wait_event(S["evP"])
+            self.sB.wait_event(S["evP"])
         with torch.cuda.stream(self.sF):
-            s = C.c_void_p(self.sF.cuda_stream)
-            self.extract(s, "front")
-            self.grids(s, "front")
-            self.match_front(s)
-            if S["pending"]:
-                self.sF.wait_event(S["evP"])  # the pose kernel of two steps ago read this set's edge arrays
-            self.gather_front(s, S)
-            self.evF.record(self.sF)
+            self.extract(C.c_void_p(self.sF.cuda_stream), "front", S)
+            self.evF.record(self.sF)  # extraction has finished reading the images
         with torch.cuda.stream(self.sB):
-            s = C.c_void_p(self.sB.cuda_stream)
-            self.extract(s, "bird")
-            self.grids(s, "bird")
-            self.match_bird(s)
-            if S["pending"]:
-                self.sB.wait_event(S["evP"])
-            self.gather_bird(s, S)
+            self.extract(C.c_void_p(self.sB.cuda_stream), "bird", S)
             self.evB.record(self.sB)
         with torch.cuda.stream(self.sP):
+            s = C.c_void_p(self.sP.cuda_stream)
             self.sP.wait_event(self.evF)
+            self.tail_front(s, S)
             self.sP.wait_event(self.evB)
-            self.pose(C.c_void_p(self.sP.cuda_stream), S)
+            self.tail_bird(s, S)
+            self.pose(s, S)
             S["evP"].record(self.sP)
             S["pending"] = True
         self._last = S
@@ -205,15 +206,12 @@ class FramePipeline:
         cur = torch.cuda.current_stream(self.dev)
         s = C.c_void_p(cur.cuda_stream)
         S = self._sets[self._k & 1]
-        if S["pending"]:  # a pose kernel of an overlapped step() may still read this set's edge arrays on the pose stream
+        if S["pending"]:  # a tail or pose kernel of an overlapped step() may still read this set on the pose stream
             cur.wait_event(S["evP"])
             S["pending"] = False
-        self.extract(s)
-        self.grids(s)
-        self.match_front(s)
-        self.match_bird(s)
-        self.gather_front(s, S)
-        self.gather_bird(s, S)
+        self.extract(s, "both", S)
+        self.tail_front(s, S)
+        self.tail_bird(s, S)
         self.pose(s, S)
         self._last = S
         self._k += 1
@@ -224,7 +222,8 @@ class FramePipeline:
         self.b_img.copy_(torch.from_numpy(np.ascontiguousarray(bird)).to(self.dev))
 
     def keypoints_host(self, which="front"):
-        kps, desc, n = (self.f_kps, self.f_desc, self.f_n) if which == "front" else (self.b_kps, self.b_desc, self.b_n)
+        S = self._last
+        kps, desc, n = (S["f_kps"], S["f_desc"], S["f_n"]) if which == "front" else (S["b_kps"], S["b_desc"], S["b_n"])
         n = n.cpu().numpy()
         k = kps.cpu().numpy().view(cabi.KP_DTYPE).reshape(self.B, self.cap)
         return [k[b, : n[b]].copy() for b in range(self.B)], [desc[b, : n[b]].cpu().numpy() for b in range(self.B)]
@@ -239,7 +238,7 @@ class FramePipeline:
         torch.cuda.synchronize()
         fk, fd = self.keypoints_host("front")
         bk, bd = self.keypoints_host("bird")
-        bcam = self.b_cam.cpu().numpy()
+        bcam = self._last["b_cam"].cpu().numpy()
         B, nl, nr = self.B, self.nl, self.nr
         world = []
         for b in range(B):
@@ -296,7 +295,7 @@ class FramePipeline:
     def results_host(self):
         torch.cuda.synchronize()
         S = self._last
-        return dict(n_front=self.f_n.cpu().numpy(), n_bird=self.b_n.cpu().numpy(), nm_front=self.nm_front.cpu().numpy(),
-                    nm_bird=self.nm_bird.cpu().numpy(), ninliers=S["ninl"].cpu().numpy(), Tcw=S["Tcw"].cpu().numpy(),
+        return dict(n_front=S["f_n"].cpu().numpy(), n_bird=S["b_n"].cpu().numpy(), nm_front=S["nm_front"].cpu().numpy(),
+                    nm_bird=S["nm_bird"].cpu().numpy(), ninliers=S["ninl"].cpu().numpy(), Tcw=S["Tcw"].cpu().numpy(),
                     front_outlier=S["e_fout"].cpu().numpy(), bird_outlier=S["e_bout"].cpu().numpy(),
-                    m_front=self.m_front.cpu().numpy(), m_bird=self.m_bird.cpu().numpy())
+                    m_front=S["m_front"].cpu().numpy(), m_bird=S["m_bird"].cpu().numpy())

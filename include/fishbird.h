@@ -1210,6 +1210,12 @@ typedef struct fb_pose_opt_args {
 } fb_pose_opt_args;
 int fb_pose_opt_batch_dev(const fb_pose_opt_args *args, void *stream);
 
+/* inv_level_sigma2 of the first nlevels pyramid levels, by value (the edge builders' kernel argument) */
+typedef struct fb_pose_gather_levels {
+  float inv_sigma2[FB_MAX_LEVELS];
+  int32_t nlevels;
+} fb_pose_gather_levels;
+
 /* Device-side form of the edge construction loops of PoseOptimizationWithBird
  * (Optimizer.cc:525-571 front, :575-602 bird): slot i of the frame becomes edge i.
  *   front: valid = match[i] >= 0, Xw = mp_xw[match[i]], obs = kps[i].pt,
@@ -1226,6 +1232,44 @@ int fb_pose_gather_bird_dev(int batch, int kp_stride, int mp_stride, const int32
                             float *d_bird_xw, float *d_bird_xc, float *d_bird_inv_sigma2,
                             uint8_t *d_bird_valid, void *stream);
 int fb_pose_opt(const fb_pose_opt_args *args); /* host pointers */
+
+/* The per-frame tail of the tracking step (Tracking.cc:292-339, 1312-1385), one launch per camera and one workgroup per
+ * frame pair.  Each call computes exactly what the separate entry points it names compute, into the same arrays, byte for
+ * byte; the cell lists, and for the bird camera mvKeysBirdCamXYZ, are still stored for the caller but go from stage to stage
+ * in LDS.  m3.cur_cell_start / cur_cell_items (and m9.cur_cam_xyz) are declared const in the matcher structs and are
+ * OUTPUTS here.
+ *
+ * fb_frame_tail_front_dev = fb_grid_build_batch_dev(m3.cur_kps, m3.n_cur, m3.grid -> m3.cur_cell_*)
+ *                           -> fb_match_projection_frame_dev(&m3)
+ *                           -> fb_pose_gather_front_dev(m3.match_cur_to_last, m3.last_xw -> front_*)
+ *                           and n_front[b] = m3.n_cur[b], Tcw[b] = m3.cur_Tcw[b]  (SetPose(prediction), Tracking.cc:1314-1320) */
+typedef struct fb_frame_tail_front_args {
+  fb_proj_frame_args m3;
+  fb_pose_gather_levels edge;    /* inv_level_sigma2 of the extractor, as fb_pose_gather_front_dev takes it */
+  float *front_xw, *front_obs, *front_inv_sigma2; /* [batch][m3.cur_stride][3 | 2 | 1] edge i = key point slot i */
+  uint8_t *front_valid;          /* [batch][m3.cur_stride], written over the whole stride                    */
+  int32_t *n_front;              /* [batch]                                                                   */
+  float *Tcw;                    /* [batch][12]                                                               */
+} fb_frame_tail_front_args;
+int fb_frame_tail_front_dev(const fb_frame_tail_front_args *args, void *stream);
+
+/* fb_frame_tail_bird_dev  = fb_grid_build_batch_dev(m9.cur_kps, m9.n_cur, m9.grid -> m9.cur_cell_*)
+ *                           -> fb_bird_keys_to_cam_dev(pixel2meter, m9.rear_axle_to_center, Tcb -> m9.cur_cam_xyz)
+ *                           -> fb_match_bird_mappoints_dev(&m9) on m9.match_cur_to_ref = -1 over the whole stride
+ *                              (mvpMapPointsBird of a new frame: the call sets it, no pre-fill)
+ *                           -> fb_pose_gather_bird_dev(m9.match_cur_to_ref, m9.ref_xw -> bird_*)
+ *                           and n_bird[b] = m9.n_cur[b], bird_outlier = 1 over the whole stride (Frame.cc:356) */
+typedef struct fb_frame_tail_bird_args {
+  fb_bird_mp_args m9;
+  double pixel2meter;            /* Converter.cc:284-292                                                      */
+  float Tcb[12];                 /* rows 0..2 of Frame::Tcb                                                   */
+  fb_pose_gather_levels edge;
+  float *bird_xw, *bird_xc, *bird_inv_sigma2;     /* [batch][m9.cur_stride][3 | 3 | 1]                        */
+  uint8_t *bird_valid;           /* [batch][m9.cur_stride]                                                    */
+  uint8_t *bird_outlier;         /* [batch][m9.cur_stride]                                                    */
+  int32_t *n_bird;               /* [batch]                                                                   */
+} fb_frame_tail_bird_args;
+int fb_frame_tail_bird_dev(const fb_frame_tail_bird_args *args, void *stream);
 
 /* ======================================================================== */
 /* Device-resident Frame and the per-frame tracking chain                    */
