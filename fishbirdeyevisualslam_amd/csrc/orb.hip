@@ -29,10 +29,27 @@ constexpr int HALF_PATCH = 15;      // :73
 constexpr int PATCH_SIZE = 31;      // :72
 constexpr int BORDER = EDGE_THRESHOLD - 3;  // minBorderX/Y, :773
 
-// stored as float (the values are small integers): the rotation below works in float, this saves the conversions
-__constant__ float c_pattern[1024] = {
+// The 256 tests are stored one dword each: x0 | y0 << 8 | x1 << 16 | y1 << 24, every coordinate biased by PAT_BIAS into a
+// byte.  k_describe unpacks them with v_cvt_f32_ubyte0..3 and subtracts the bias, which is exact in float: the rotation
+// sees the same values as with a float table, and a lane fetches 16 B of pattern instead of 64 B.
+constexpr int PATTERN_XY[1024] = {
 #include "orb_pattern.inc"
 };
+constexpr int pattern_extreme(bool wantMax) {
+  int m = PATTERN_XY[0];
+  for (int i = 1; i < 1024; i++) m = wantMax ? (PATTERN_XY[i] > m ? PATTERN_XY[i] : m) : (PATTERN_XY[i] < m ? PATTERN_XY[i] : m);
+  return m;
+}
+constexpr int PAT_BIAS = -pattern_extreme(false);
+static_assert(PAT_BIAS >= 0 && pattern_extreme(true) + PAT_BIAS <= 255, "a pattern coordinate does not fit a biased byte");
+struct PackedPattern { uint32_t test[256]; };
+constexpr PackedPattern pack_pattern() {
+  PackedPattern p{};
+  for (int t = 0; t < 256; t++)
+    for (int k = 0; k < 4; k++) p.test[t] |= (uint32_t)(PATTERN_XY[t * 4 + k] + PAT_BIAS) << (8 * k);
+  return p;
+}
+__constant__ PackedPattern c_pattern = pack_pattern();
 
 struct LevelInfo {
   int w, h, pitch;
@@ -60,6 +77,10 @@ struct OrbK {
   int cellBase[FB_MAX_LEVELS + 1];  // first FAST cell of each level (contiguous copy for one scalar load)
   int grpBase[FB_MAX_LEVELS + 1];   // first k_fast wave of each level (a wave = FAST_CPW consecutive cells)
   int totalGroups;
+  // k_describe: a workgroup serves DESC_WPB * DESC_KPW consecutive slots of ONE level's run of lvlOut
+  int descBase[FB_MAX_LEVELS + 1];  // first k_describe workgroup of each level
+  int runBase[FB_MAX_LEVELS];       // L[l].outBase / L[l].outCap again, contiguous: the record address needs nothing else
+  int runCap[FB_MAX_LEVELS];
   long long pyrStride;   // bytes per image of levels >= 1
   long long blurStride;  // bytes per image of the blurred pyramid (all levels)
   int blurStrips[FB_MAX_LEVELS + 1];  // first k_blur strip of each level
@@ -1184,29 +1205,41 @@ __global__ __launch_bounds__(256) void k_blur(OrbK K, const uint8_t *__restrict_
 }
 
 // ------------------------------------------------------------------------------------------
-// One wave per keypoint: orientation (IC_Angle on the raw level), 256 steered BRIEF tests on the blurred level,
-// and the final cv::KeyPoint record.  Key points sit >= 19 px inside the level (EDGE_THRESHOLD), so the radius-15
-// orientation patch and the radius-18 test footprint never leave the image.
+// Orientation (IC_Angle on the raw level), 256 steered BRIEF tests on the blurred level, and the final cv::KeyPoint
+// record.  Key points sit >= 19 px inside the level (EDGE_THRESHOLD), so the radius-15 orientation patch and the
+// radius-18 test footprint never leave the image.
 // ------------------------------------------------------------------------------------------
-// One wave per key point.  The radius-15 raw patch (orientation) and the radius-18 blurred patch (BRIEF tests) are
-// staged into LDS with coalesced dword loads: the 512 rotated sample positions are then LDS gathers instead of
-// scattered byte loads that would each cost a cache-line lookup in the vector L1 (measured: the L1 tag rate, not
-// ALU or HBM, bounded the direct-gather version).
+// The radius-15 raw patch (orientation) and the radius-18 blurred patch (BRIEF tests) are staged into LDS with
+// coalesced dword loads: the 512 rotated sample positions are then LDS gathers instead of scattered byte loads that
+// would each cost a cache-line lookup in the vector L1 (measured: the L1 tag rate, not ALU or HBM, bounded the
+// direct-gather version).
 constexpr int DP_RAW_DW = 9, DP_RAW_ROWS = 31;    // 31 rows x 36 B  (x-15 .. x+15 after dword alignment)
 constexpr int DP_BL_DW = 10, DP_BL_ROWS = 37;     // 37 rows x 40 B  (x-18 .. x+18 after dword alignment)
 
 constexpr int DESC_WPB = 4;  // waves per workgroup (they never talk to each other)
-constexpr int DESC_KPW = 2;  // consecutive key points per wave, all their patch loads in flight together
+constexpr int DESC_KPW = 2;  // consecutive slots per wave, all their patch loads in flight together
 
-// A wave owns DESC_KPW consecutive key points.  What does not depend on the key point (level counts, sampling
-// pattern, orientation tables) is fetched once per wave, the DESC_KPW records with one load, and the patch loads of ALL
-// of the wave's key points are requested before the first patch is used.  The kernel is bound by the latency of its
-// ~70 scattered cache lines per key point (ablation: 37 % record + table fetch, 53 % patch staging + moments, 10 % the
-// 256 tests), not by arithmetic.  Measured at B=256 (per step, both images): one key point per wave 0.97 ms; 8 per wave
-// with the NEXT patch prefetched during the tests 1.47 ms (the tests are far too short to cover a patch); 2 per wave
-// with both patches requested together 0.93 ms and the best overlap with the other streams; 4 per wave the same.
-// More resident waves do not help either (amdgpu_waves_per_eu 6: 76 VGPRs, same time; 7: spills, 1.12 ms).
-__global__ __launch_bounds__(64 * DESC_WPB) void k_describe(OrbK K, const uint8_t *__restrict__ img0, long long imgStride,
+// A wave owns DESC_KPW consecutive slots of ONE level's run of lvlOut (never of two levels: the last wave of a level
+// with an odd count has one key point).  The workgroups of a level are K.descBase[l] .. K.descBase[l + 1]), sized for the
+// run's capacity, so the level and the address of the wave's records follow from blockIdx alone: the records, the level
+// counts and the level's geometry are requested together, and one wait later the wave knows whether its slots are
+// occupied (slot < cnts[l]), where its key points go (sum of the counts below l, + slot: level-major, quadtree order
+// within a level) and what to fetch.  (Before, a wave owned a global key-point index: counts -> record -> level geometry
+// -> patches were four dependent round trips.)  The sampling pattern is 16 B and the orientation table 16 B per lane
+// (64 B and 32 B as float4 / separate weight and mask dwords before).
+// The kernel is bound by the latency of its ~70 scattered cache lines per key point, not by arithmetic.  Measured at
+// B=256 (single stream, front / bird image): 698 / 416 us per launch with global key-point indices and float tables,
+// 651 / 392 us with this mapping (minima 527 / 393 -> 468 / 365 us); the overlapped step 3.466 -> 3.387 ms.  The
+// prologue-only ablation (K.dbg == 11) does NOT fall with it, 25 -> 42 us at B=64: it now contains the level geometry
+// and waits for the scalar tables of all FB_MAX_LEVELS levels, which the full kernel hides behind the record fetch.
+// DESC_KPW 3 and 4 with the freed registers (88 / 95 VGPRs against 75, scratch 0) give the same step within the
+// run-to-run spread (3.375 / 3.384 against 3.387 ms): 2 stays.  Older measurements, with global indices (per step, both
+// images): one key point per wave 0.97 ms; 8 per wave with the NEXT patch prefetched during the tests 1.47 ms (the
+// tests are far too short to cover a patch); 2 per wave with both patches requested together 0.93 ms.  More resident
+// waves did not help the overlapped step (amdgpu_waves_per_eu 6: same time; 7: spills, 1.12 ms), so the occupancy is
+// pinned at the 5 waves per SIMD it had at 85 VGPRs.
+__global__ __launch_bounds__(64 * DESC_WPB) __attribute__((amdgpu_waves_per_eu(5, 5)))
+void k_describe(OrbK K, const uint8_t *__restrict__ img0, long long imgStride,
                                                  int pitch0, const uint8_t *__restrict__ pyr,
                                                  const uint8_t *__restrict__ blur, const uint4 *__restrict__ angTab,
                                                  const uint32_t *__restrict__ lvlOut, const int *__restrict__ lvlCount,
@@ -1217,34 +1250,50 @@ __global__ __launch_bounds__(64 * DESC_WPB) void k_describe(OrbK K, const uint8_
   const int b = blockIdx.y, lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   uint32_t *rawp = rawp_all[wv], *blp = blp_all[wv];
+  // per-lane tables: tests 4*lane .. 4*lane+3 and the IC_Angle weights of this lane's half row
+  const uint4 pq = reinterpret_cast<const uint4 *>(c_pattern.test)[lane];
+  const uint4 angT = angTab[lane < 62 ? lane : 0];
   // XCD-aware mapping (as in k_fast): consecutive workgroups go to different XCDs; give each XCD a contiguous run of
-  // key points (neighbours in the quadtree order overlap in the image) so that their patches share lines in one L2
-  const int first = (((int)(blockIdx.x & 7) * ((gridDim.x + 7) >> 3) + (int)(blockIdx.x >> 3)) * DESC_WPB + wv) * DESC_KPW;
+  // slots (neighbours in the quadtree order overlap in the image) so that their patches share lines in one L2.  The
+  // grid is a multiple of 8 workgroups; those past the last level's run find their slot past every count and leave.
+  const int wg = (int)(blockIdx.x & 7) * (int)(gridDim.x >> 3) + (int)(blockIdx.x >> 3);
+  int l = 0, runBase = K.runBase[0], runCap = K.runCap[0];
+#pragma unroll
+  for (int i = 1; i < FB_MAX_LEVELS; i++)
+    if (i < K.nlevels && wg >= K.descBase[i]) { l = i; runBase = K.runBase[i]; runCap = K.runCap[i]; }
+  const int slot = ((wg - K.descBase[l]) * DESC_WPB + wv) * DESC_KPW;
+  // three independent fetches: the records (an empty slot reads the run's last entry and drops it) ...
+  const uint32_t *run = lvlOut + (long long)b * K.outStride + runBase;
+  uint32_t rec[DESC_KPW];
+#pragma unroll
+  for (int j = 0; j < DESC_KPW; j++) rec[j] = run[min(slot + j, runCap - 1)];
+  // ... the level counts ...
   const int *cnts = lvlCount + b * K.nlevels;
-  int lstart[FB_MAX_LEVELS + 1];
-  lstart[0] = 0;
+  int below = 0, total = 0, mine = 0;
 #pragma unroll
-  for (int l = 0; l < FB_MAX_LEVELS; l++) lstart[l + 1] = lstart[l] + (l < K.nlevels ? cnts[l] : 0);
-  const int nk = min(lstart[FB_MAX_LEVELS], K.capOut);
-  if (blockIdx.x == 0 && threadIdx.x == 0) nOut[b] = nk;
-  if (first >= nk) return;
-  const int nmine = min(DESC_KPW, nk - first);
-  // lanes 0..nmine-1 fetch the records of the wave's key points (level = the run of the per-level counts they fall in)
-  int kl = 0;
-  uint32_t recv;
-  {
-    const int ki = first + min(lane, nmine - 1);
-    int adj = K.L[0].outBase;
-#pragma unroll
-    for (int l = 1; l < FB_MAX_LEVELS; l++)
-      if (l < K.nlevels && ki >= lstart[l]) { kl = l; adj = K.L[l].outBase - lstart[l]; }
-    recv = lvlOut[(long long)b * K.outStride + adj + ki];
+  for (int i = 0; i < FB_MAX_LEVELS; i++) {
+    const int ci = cnts[i];  // (the buffer has FB_MAX_LEVELS entries of slack: an unconditional load, all of them together)
+    const int c = i < K.nlevels ? ci : 0;
+    total += c; below += i < l ? c : 0; mine = i == l ? c : mine;
   }
-  float4 pp[4];
-#pragma unroll
-  for (int t = 0; t < 4; t++) pp[t] = reinterpret_cast<const float4 *>(c_pattern)[lane * 4 + t];
-  const uint4 angW = angTab[(lane < 62 ? lane : 0) * 2], angK = angTab[(lane < 62 ? lane : 0) * 2 + 1];
-  if (K.dbg == 11) { if ((int)(pp[0].x + pp[1].y + pp[2].z + pp[3].w) + (int)angW.x + (int)angK.y + (int)recv == 1234567) nOut[0] = 1; return; }
+  // ... and the level's geometry
+  const LevelInfo &Lv = K.L[l];
+  const int lvPitch = Lv.pitch, lvPatch = Lv.patchSize;
+  const long long lvOff = Lv.off, lvBoff = Lv.boff;
+  const float lvScale = Lv.scale;
+  const int nk = min(total, K.capOut);
+  if (wg == 0 && threadIdx.x == 0) nOut[b] = nk;  // wg == 0 is blockIdx.x == 0: once per image
+  const int first = below + slot;  // output index of the wave's first key point; past capOut it is dropped
+  const int nmine = min(DESC_KPW, min(mine - slot, nk - first));
+  if (K.dbg == 11) { if ((int)(pq.x + pq.w) + (int)angT.x + (int)rec[0] + (int)rec[DESC_KPW - 1] + nmine + lvPitch + lvPatch + (int)lvOff + (int)lvBoff + (int)lvScale == 1234567) nOut[0] = 1; return; }
+  if (nmine <= 0) return;
+  const uint4 angW = make_uint4(angT.x & 0x0f0f0f0fu, angT.y & 0x0f0f0f0fu, angT.z & 0x0f0f0f0fu, angT.w & 0x0f0f0f0fu);
+  const uint4 angK = make_uint4((angT.x >> 4) & 0x01010101u, (angT.y >> 4) & 0x01010101u, (angT.z >> 4) & 0x01010101u, (angT.w >> 4) & 0x01010101u);
+  // the wave's level: source of the raw patch (level 0 is the caller's image) and of the blurred patch
+  const uint8_t *lvImg = l == 0 ? img0 + (long long)b * imgStride : pyr + (long long)b * K.pyrStride + lvOff;
+  const int rawPitch = l == 0 ? pitch0 : lvPitch;
+  const uint8_t *lvBlur = blur + (long long)b * K.blurStride + lvBoff;
+  const bool rawAligned = ((reinterpret_cast<uintptr_t>(lvImg) | (uintptr_t)rawPitch) & 3) == 0;
   // fixed lane -> (row within a group, dword) mapping: 6 rows x 10 dwords (7 x 9 for the raw patch) per pass, so the
   // global offsets and the LDS indices are constants per lane (32-bit offsets from wave-uniform bases, 24-bit
   // multiplies: 64/32-bit integer multiplies are quarter rate)
@@ -1252,23 +1301,16 @@ __global__ __launch_bounds__(64 * DESC_WPB) void k_describe(OrbK K, const uint8_
   const int rb0 = (lane * 205) >> 11, dwb = lane - rb0 * DP_BL_DW;   // lane / 10
   const int rr0 = (lane * 57) >> 9, dwr = lane - rr0 * DP_RAW_DW;    // lane / 9
   struct KP {  // wave-uniform description of one key point
-    int cx, cy, resp, myl, pitch, bpitch, bxa, box, rxa, rox, patchSize;
-    float scale;
+    int cx, cy, resp, pitch, bpitch, bxa, box, rxa, rox;
     const uint8_t *img, *bbase;
     bool rawAligned;
   };
   auto decode = [&](int j) {
     KP k;
-    const uint32_t rec = (uint32_t)__builtin_amdgcn_readlane((int)recv, j);
-    k.myl = __builtin_amdgcn_readlane(kl, j);
-    k.cx = rec & 0xFFF; k.cy = (rec >> 12) & 0xFFF; k.resp = rec >> 24;
-    const LevelInfo &Lv = K.L[k.myl];
-    if (k.myl == 0) { k.img = img0 + (long long)b * imgStride; k.pitch = pitch0; }
-    else { k.img = pyr + (long long)b * K.pyrStride + Lv.off; k.pitch = Lv.pitch; }
-    k.bbase = blur + (long long)b * K.blurStride + Lv.boff;
-    k.bpitch = Lv.pitch; k.scale = Lv.scale; k.patchSize = Lv.patchSize;
+    const uint32_t r = rec[j];
+    k.cx = r & 0xFFF; k.cy = (r >> 12) & 0xFFF; k.resp = r >> 24;
+    k.img = lvImg; k.pitch = rawPitch; k.bbase = lvBlur; k.bpitch = lvPitch; k.rawAligned = rawAligned;
     k.bxa = (k.cx - 18) & ~3; k.box = (k.cx - 18) - k.bxa;
-    k.rawAligned = ((reinterpret_cast<uintptr_t>(k.img) | (uintptr_t)k.pitch) & 3) == 0;
     k.rxa = (k.cx - 15) & ~3;
     k.rox = k.rawAligned ? (k.cx - 15) - k.rxa : 0;
     return k;
@@ -1321,7 +1363,7 @@ __global__ __launch_bounds__(64 * DESC_WPB) void k_describe(OrbK K, const uint8_
   KP kpv[DESC_KPW];
 #pragma unroll
   for (int j = 0; j < DESC_KPW; j++) {
-    kpv[j] = decode(min(j, nmine - 1));
+    kpv[j] = decode(j);
     if (j < nmine) issue(kpv[j], vb[j], vr[j]);
   }
 #pragma unroll
@@ -1331,7 +1373,7 @@ __global__ __launch_bounds__(64 * DESC_WPB) void k_describe(OrbK K, const uint8_
     stage(cur, vb[j], vr[j]);
     // IC_Angle (ORBextractor.cc:77-104): lanes 2*(v+15) and 2*(v+15)+1 sum the left (u < 0) and right (u >= 0) part
     // of row v of the circular patch.  Each half row is 16 bytes read as dwords; |u| weights and the circular mask
-    // (|u| <= umax[|v|]) come from a per-lane table (angTab[lane] = 4 weight dwords + 4 mask dwords) and the sums
+    // (|u| <= umax[|v|]) come from a per-lane table (angTab[lane] = 4 dwords, unpacked above into angW / angK) and the sums
     // are v_dot4_u32_u8.
     int m10 = 0, m01 = 0;
     if (lane < 62) {
@@ -1350,7 +1392,7 @@ __global__ __launch_bounds__(64 * DESC_WPB) void k_describe(OrbK K, const uint8_
     }
     m10 = fb::wave_sum(m10);
     m01 = fb::wave_sum(m01);
-    if (K.dbg == 12) { if (m10 + m01 == 12345678 && (int)(pp[0].x + pp[1].y + pp[2].z + pp[3].w) == 77777) nOut[0] = 1; continue; }
+    if (K.dbg == 12) { if (m10 + m01 == 12345678 && (int)(pq.x + pq.w) == 77777) nOut[0] = 1; continue; }
     const float angle = fb_fast_atan2((float)m01, (float)m10);
     // computeOrbDescriptor (ORBextractor.cc:107-147): lane computes tests 4*lane .. 4*lane+3
     const float factorPI = 0x1.1df46ap-6f;
@@ -1361,7 +1403,9 @@ __global__ __launch_bounds__(64 * DESC_WPB) void k_describe(OrbK K, const uint8_
     int nib = 0;
 #pragma unroll
     for (int t = 0; t < 4; t++) {
-      const float x0 = pp[t].x, y0 = pp[t].y, x1 = pp[t].z, y1 = pp[t].w;
+      const uint32_t p = t == 0 ? pq.x : t == 1 ? pq.y : t == 2 ? pq.z : pq.w;
+      const float x0 = (float)(p & 0xFFu) - (float)PAT_BIAS, y0 = (float)((p >> 8) & 0xFFu) - (float)PAT_BIAS;
+      const float x1 = (float)((p >> 16) & 0xFFu) - (float)PAT_BIAS, y1 = (float)(p >> 24) - (float)PAT_BIAS;
       const int t0 = centre[__mul24(fb_cvround(x0 * bb + y0 * a), DP_BL_DW * 4) + fb_cvround(x0 * a - y0 * bb)];
       const int t1 = centre[__mul24(fb_cvround(x1 * bb + y1 * a), DP_BL_DW * 4) + fb_cvround(x1 * a - y1 * bb)];
       nib |= (t0 < t1) << t;
@@ -1377,11 +1421,11 @@ __global__ __launch_bounds__(64 * DESC_WPB) void k_describe(OrbK K, const uint8_
       fb_keypoint kp;
       kp.x = (float)cur.cx;
       kp.y = (float)cur.cy;
-      if (cur.myl != 0) { kp.x *= cur.scale; kp.y *= cur.scale; }  // ORBextractor.cc:1095-1101
-      kp.size = (float)cur.patchSize;
+      if (l != 0) { kp.x *= lvScale; kp.y *= lvScale; }  // ORBextractor.cc:1095-1101
+      kp.size = (float)lvPatch;
       kp.angle = angle;
       kp.response = (float)cur.resp;
-      kp.octave = cur.myl;
+      kp.octave = l;
       kps[o] = kp;
     }
     // the LDS reads of this key point are ordered before the writes of the next one (same wave, in-order LDS)
@@ -1590,6 +1634,17 @@ int prepare(fb_orb *o, int w, int h, int batch) {
     }
     K.totalGroups = gsum;
   }
+  {  // k_describe: whole workgroups per level, so that no wave straddles two levels
+    int wsum = 0;
+    for (int l = 0; l <= FB_MAX_LEVELS; l++) {
+      K.descBase[l] = wsum;
+      if (l < p.nlevels) {
+        K.runBase[l] = K.L[l].outBase;
+        K.runCap[l] = K.L[l].outCap;
+        wsum += (K.L[l].outCap + DESC_WPB * DESC_KPW - 1) / (DESC_WPB * DESC_KPW);
+      }
+    }
+  }
   for (int l = 0; l <= FB_MAX_LEVELS; l++) K.cellBase[l] = l < p.nlevels ? K.L[l].cellBase : cells;
   K.dbg = getenv("FB_FAST_DBG") ? atoi(getenv("FB_FAST_DBG")) : 0;
   {
@@ -1637,17 +1692,17 @@ int prepare(fb_orb *o, int w, int h, int batch) {
     o->rt[l].ibeta = reinterpret_cast<const short *>(base + tabOff[l * 4 + 3]);
   }
   const size_t B = batch;
-  {  // IC_Angle tables of k_describe: lane 2r+half owns half of patch row v = r-15; per byte j of its 16-byte span the
-     // weight |u| and the inclusion mask |u| <= umax[|v|] (left half: u = j-15, u = 0 belongs to the right half)
-    std::vector<uint32_t> tab(64 * 8, 0);
+  {  // IC_Angle table of k_describe: lane 2r+half owns half of patch row v = r-15; per byte j of its 16-byte span the
+     // weight |u| (low nibble) and the inclusion mask |u| <= umax[|v|] (bit 4; left half: u = j-15, u = 0 belongs to
+     // the right half).  An excluded byte is 0.
+    std::vector<uint32_t> tab(64 * 4, 0);
     for (int lane = 0; lane < 62; lane++) {
       const int v = (lane >> 1) - 15, half = lane & 1, dmax = K.umax[v < 0 ? -v : v];
       for (int j = 0; j < 16; j++) {
         const int au = half ? j : 15 - j;
         const bool inc = au <= dmax && (half || au != 0);
         if (!inc) continue;
-        tab[lane * 8 + (j >> 2)] |= (uint32_t)au << (8 * (j & 3));
-        tab[lane * 8 + 4 + (j >> 2)] |= 1u << (8 * (j & 3));
+        tab[lane * 4 + (j >> 2)] |= ((uint32_t)au | 0x10u) << (8 * (j & 3));
       }
     }
     FB_TRY(o->angTab.upload(tab.data(), tab.size() * 4));
@@ -1658,7 +1713,7 @@ int prepare(fb_orb *o, int w, int h, int batch) {
   FB_TRY(o->cellCand.alloc(B * K.candStride * 4 + 16));
   FB_TRY(o->cellCount.alloc(B * (size_t)K.totalCells * 4 + 16));
   FB_TRY(o->nodeOf.alloc(B * K.candStride * 2 + 16));
-  FB_TRY(o->counts.alloc(B * p.nlevels * 4 * 2));  // candCount | lvlCount
+  FB_TRY(o->counts.alloc(B * p.nlevels * 4 * 2 + FB_MAX_LEVELS * 4));  // candCount | lvlCount | slack: k_describe reads FB_MAX_LEVELS counts per image
   FB_TRY(o->timers.alloc(FB_ORB_TIMER_WORDS * 8));
   FB_HIP(hipMemset(o->timers.p, 0, FB_ORB_TIMER_WORDS * 8));
   K.timers = o->timers.as<unsigned long long>();
@@ -1794,7 +1849,7 @@ int fb_orb_extract_batch_dev(fb_orb *o, const uint8_t *d_images, int batch, int 
   if (fork) FB_HIP(hipStreamWaitEvent(s, o->evJoin, 0));  // the blurred levels are complete
   {
   fb::ProfScope prof_(fb::P_DESCRIBE, s);
-  k_describe<<<dim3(((K.capOut + DESC_WPB * DESC_KPW - 1) / (DESC_WPB * DESC_KPW) + 7) / 8 * 8, batch), 64 * DESC_WPB, 0, s>>>(K, d_images, (long long)image_stride, stride, o->pyr.as<uint8_t>(),
+  k_describe<<<dim3((K.descBase[nl] + 7) / 8 * 8, batch), 64 * DESC_WPB, 0, s>>>(K, d_images, (long long)image_stride, stride, o->pyr.as<uint8_t>(),
                                                    o->blur.as<uint8_t>(), o->angTab.as<uint4>(), o->lvlOut.as<uint32_t>(), lvlCount, d_keypoints,
                                                    d_descriptors, d_n);
   }
