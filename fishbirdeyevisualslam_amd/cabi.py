@@ -280,6 +280,18 @@ class LocalMapArgs(C.Structure):
                 ("gate_min", _i32), ("reuse_index", _i32)]
 
 
+class CorrectLoopArgs(C.Structure):
+    _fields_ = [("q", C.c_double * 4), ("t", C.c_double * 3), ("s", C.c_double), ("cur_slot", _i32), ("reuse_index", _i32),
+                ("scale_factors", _vp), ("mp_ref_kf", _vp), ("mp_normal", _vp), ("mp_min_dist", _vp), ("mp_max_dist", _vp),
+                ("d_mp_corrected_ref", _vp), ("d_n_set", _vp), ("d_set_slots", _vp)]
+
+
+class PropagateGbaArgs(C.Structure):
+    _fields_ = [("n_origins", _i32), ("origins", _vp), ("kf_gba", _vp), ("kf_Tcw_gba", _vp), ("kf_Tcw_bef", _vp),
+                ("mp_gba", _vp), ("mp_pos_gba", _vp), ("mp_ref_kf", _vp), ("mpb_gba", _vp), ("mpb_pos_gba", _vp),
+                ("mpb_ref_kf", _vp), ("d_reached", _vp)]
+
+
 class BirdFilterArgs(C.Structure):
     _fields_ = [("batch", _i32), ("match_stride", _i32), ("kp1_stride", _i32), ("kp2_stride", _i32),
                 ("n_matches", _vp), ("query_idx", _vp), ("train_idx", _vp), ("cam_xyz1", _vp), ("cam_xyz2", _vp),
@@ -412,6 +424,8 @@ EXPORTS = [
     "fb_covis_tree_set_dev", "fb_covis_tree_get_dev", "fb_covis_tree_get", "fb_covis_change_parent_dev", "fb_covis_erase_child_dev",
     "fb_covis_children_dev", "fb_covis_children", "fb_covis_parent_dev", "fb_covis_first_connection_dev",
     "fb_covis_tree_erase_keyframe_dev", "fb_covis_local_map_dev", "fb_covis_local_map", "fb_covis_reserve_local_map",
+    "fb_covis_correct_loop_dev", "fb_covis_correct_loop", "fb_covis_reserve_correct_loop", "fb_covis_propagate_gba_dev",
+    "fb_covis_propagate_gba",
     "fb_in_frustum_dev", "fb_in_frustum", "fb_undistort_keypoints_dev", "fb_undistort_keypoints", "fb_image_bounds",
     "fb_pose_opt_batch_dev", "fb_pose_opt", "fb_pose_gather_front_dev", "fb_pose_gather_bird_dev",
     "fb_frame_tail_front_dev", "fb_frame_tail_bird_dev",

@@ -302,3 +302,55 @@ class CovisibilityGraph:
         a.reuse_index = 1 if reuse_index else 0
         check(lib().fb_covis_local_map_dev(self.h, C.byref(m.c), C.byref(a), _stream()), "fb_covis_local_map_dev")
         self._keep = (m, a)
+
+    # ---- map correction: CorrectLoop and the tail of RunGlobalBundleAdjustment -------------------------------------------------
+    def reserve_correct_loop(self, n_mp, n_obs, n_q=0, n_mpb=0, bird_stride=0):
+        check(lib().fb_covis_reserve_correct_loop(self.h, int(n_mp), int(n_obs), int(n_q), int(n_mpb), int(bird_stride)),
+              "fb_covis_reserve_correct_loop")
+
+    def _filled(self, x, dtype, n, fill=0):
+        """x (n elements) as a flat device tensor of at least one element"""
+        out = torch.full((max(n, 1),), fill, dtype=dtype, device=self.device)
+        if x is not None and n:
+            out[:n] = self._dev(x, dtype).reshape(-1)
+        return out
+
+    def correct_loop_arrays(self, m, scale_factors, mp_ref_kf, mp_normal, mp_min_dist, mp_max_dist):
+        """Device arrays of a fb_correct_loop_args for the map m: the in/out MapPoint members and the outputs.
+        -> (dict of tensors, cabi.CorrectLoopArgs)"""
+        n = m.n_mp
+        t = dict(scale_factors=self._dev(scale_factors, torch.float32).reshape(-1), mp_ref_kf=self._filled(mp_ref_kf, torch.int32, n, -1),
+                 mp_normal=self._filled(mp_normal, torch.float32, 3 * n), mp_min_dist=self._filled(mp_min_dist, torch.float32, n),
+                 mp_max_dist=self._filled(mp_max_dist, torch.float32, n), d_mp_corrected_ref=self._i32(n, -1), d_n_set=self._i32(1),
+                 d_set_slots=self._i32(self.K, -1))
+        a = cabi.CorrectLoopArgs()
+        cabi.fill(a, reuse_index=0, **t)
+        return t, a
+
+    def correct_loop(self, m, t, a, cur_slot, q, tr, s, reuse_index=False):
+        """LoopClosing::CorrectLoop (:438-541) with mg2oScw = (q xyzw, tr, s) on the tables t and the arrays of
+        correct_loop_arrays; the graph row of cur_slot must be current.  Enqueues only."""
+        cabi.fill(a, q=[float(x) for x in q], t=[float(x) for x in tr], s=float(s), cur_slot=int(cur_slot), reuse_index=1 if reuse_index else 0)
+        check(lib().fb_covis_correct_loop_dev(self.h, C.byref(m.c), C.byref(t.c), C.byref(a), _stream()), "fb_covis_correct_loop_dev")
+        self._keep = (m, t, a)
+
+    def propagate_gba_arrays(self, m, t, origins, kf_gba, kf_Tcw_gba, kf_Tcw_bef, mp_gba, mp_pos_gba, mp_ref_kf, mpb_gba=None,
+                             mpb_pos_gba=None, mpb_ref_kf=None):
+        """Device arrays of a fb_propagate_gba_args -> (dict of tensors, cabi.PropagateGbaArgs)"""
+        K, n, nb = self.K, m.n_mp, t.n_mpb
+        origins = self._dev(origins).reshape(-1)
+        d = dict(origins=origins if origins.numel() else self._i32(1), kf_gba=self._filled(kf_gba, torch.uint8, K),
+                 kf_Tcw_gba=self._filled(kf_Tcw_gba, torch.float32, 12 * K), kf_Tcw_bef=self._filled(kf_Tcw_bef, torch.float32, 12 * K),
+                 mp_gba=self._filled(mp_gba, torch.uint8, n), mp_pos_gba=self._filled(mp_pos_gba, torch.float32, 3 * n),
+                 mp_ref_kf=self._filled(mp_ref_kf, torch.int32, n, -1), d_reached=self._filled(None, torch.uint8, K))
+        if t.bird:
+            d.update(mpb_gba=self._filled(mpb_gba, torch.uint8, nb), mpb_pos_gba=self._filled(mpb_pos_gba, torch.float32, 3 * nb),
+                     mpb_ref_kf=self._filled(mpb_ref_kf, torch.int32, nb, -1))
+        a = cabi.PropagateGbaArgs()
+        cabi.fill(a, n_origins=int(origins.numel()), **d)
+        return d, a
+
+    def propagate_gba(self, m, t, a):
+        """The map update that ends RunGlobalBundleAdjustment (:714-825) over the handle's spanning tree.  Enqueues only."""
+        check(lib().fb_covis_propagate_gba_dev(self.h, C.byref(m.c), C.byref(t.c), C.byref(a), _stream()), "fb_covis_propagate_gba_dev")
+        self._keep = (m, t, a)

@@ -2,7 +2,8 @@
 of fb_covis_map, with the reference's quirks planted.
 
     python -m fishbirdeyevisualslam_amd.covis_problem --probe     # times UpdateConnections / KeyFrameCulling / the window / the local
-                                                                  # map and the tree calls at a LocalMapping-like size
+                                                                  # map, the tree calls and the two map correction calls at a
+                                                                  # LocalMapping-like size
 """
 import numpy as np
 
@@ -303,6 +304,115 @@ def make_local_mapping_problem(seed=4, K=500, S=2000, n_mp=100000, per_point=6, 
     return arr
 
 
+def rotation(axis_angle):
+    """Rodrigues in double -> 3x3"""
+    w = np.asarray(axis_angle, np.float64)
+    th = float(np.linalg.norm(w))
+    if th < 1e-12:
+        return np.eye(3)
+    k = w / th
+    Kx = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    return np.eye(3) + np.sin(th) * Kx + (1 - np.cos(th)) * (Kx @ Kx)
+
+
+def pose12(R, t):
+    return np.hstack([np.asarray(R, np.float64), np.asarray(t, np.float64).reshape(3, 1)]).astype(np.float32).reshape(12)
+
+
+def empty_map_correct_problem(K=4, S=4, BS=2, n_mp=0, n_mpb=0):
+    """The arrays fb_covis_correct_loop and fb_covis_propagate_gba read, for a map with nothing in it: identity poses, every
+    feature NULL, no edge, no graph connection (`connections`: (a, b, w) for a->AddConnection(b, w)), no tree, Scw = identity."""
+    eye = pose12(np.eye(3), np.zeros(3))
+    return dict(K=K, S=S, BS=BS, kf_n=np.full(K, S, np.int32), kf_mp=np.full((K, S), -1, np.int32), kf_octave=np.zeros((K, S), np.uint8),
+                mp_bad=np.zeros(n_mp, np.uint8), obs_mp=np.zeros(0, np.int32), obs_kf=np.zeros(0, np.int32), obs_idx=np.zeros(0, np.int32),
+                kf_order=(1000 + 16 * np.arange(K)).astype(np.uint64), connections=[], parent=np.full(K, -1, np.int32),
+                linked=np.zeros(K, np.uint8), kf_Tcw=np.tile(eye, (K, 1)), mp_xw=np.zeros((n_mp, 3), np.float32),
+                kf_nb=np.full(K, BS, np.int32), kf_mpb=np.full((K, BS), -1, np.int32), mpb_bad=np.zeros(n_mpb, np.uint8),
+                mpb_xw=np.zeros((n_mpb, 3), np.float32), scale_factors=(1.2 ** np.arange(N_LEVELS)).astype(np.float32),
+                mp_ref_kf=np.zeros(n_mp, np.int32), mp_normal=np.tile(np.array([0, 0, 1], np.float32), (n_mp, 1)),
+                mp_min_dist=np.full(n_mp, 0.5, np.float32), mp_max_dist=np.full(n_mp, 50.0, np.float32), cur=0,
+                q=np.array([0.0, 0.0, 0.0, 1.0]), t=np.zeros(3), s=1.0, origins=np.zeros(0, np.int32), kf_gba=np.zeros(K, np.uint8),
+                kf_Tcw_gba=np.tile(eye, (K, 1)), kf_Tcw_bef=np.tile(eye, (K, 1)), mp_gba=np.zeros(n_mp, np.uint8),
+                mp_pos_gba=np.zeros((n_mp, 3), np.float32), mpb_gba=np.zeros(n_mpb, np.uint8), mpb_pos_gba=np.zeros((n_mpb, 3), np.float32),
+                mpb_ref_kf=np.full(n_mpb, -1, np.int32))
+
+
+def add_edge(c, mp, kf, idx):
+    """one entry of the edge list (MapPoint::mObservations); the key frame's own kf_mp entry is set apart from it"""
+    for k, v in (("obs_mp", mp), ("obs_kf", kf), ("obs_idx", idx)):
+        c[k] = np.append(c[k], np.int32(v))
+
+
+def make_map_correct_problem(seed=1, K=8, S=8, BS=4, n_mp=16, n_mpb=8, bad_entries=False):
+    """A small random map for CorrectLoop and the GBA tree update: rigid poses, points held by one to three key frames (some
+    held without an edge, some edges without the hold, tombstones), a covisibility list for `cur` that ties in weight so
+    kf_order decides, a forest with an unlinked child, flags on part of it, and a Sim3 with s != 1.  bad_entries plants
+    out-of-range indices (kf_mp, kf_mpb, mp_ref_kf, an octave, an edge, an origin)."""
+    g = np.random.default_rng(seed)
+    c = empty_map_correct_problem(K, S, BS, n_mp, n_mpb)
+    c["kf_order"] = (g.permutation(K) * 48 + 4096).astype(np.uint64)
+    c["kf_n"] = g.integers(S // 2, S + 1, K).astype(np.int32)
+    c["kf_nb"] = g.integers(BS // 2, BS + 1, K).astype(np.int32)
+    for k in range(K):
+        c["kf_Tcw"][k] = pose12(rotation(g.normal(0, 0.6, 3)), g.normal(0, 2, 3))
+        c["kf_Tcw_gba"][k] = pose12(rotation(g.normal(0, 0.6, 3)), g.normal(0, 2, 3))
+        c["kf_Tcw_bef"][k] = pose12(rotation(g.normal(0, 0.6, 3)), g.normal(0, 2, 3))
+    c["kf_octave"] = g.integers(0, N_LEVELS, (K, S)).astype(np.uint8)
+    c["mp_xw"] = g.normal(0, 4, (n_mp, 3)).astype(np.float32)
+    c["mpb_xw"] = g.normal(0, 4, (n_mpb, 3)).astype(np.float32)
+    c["mp_pos_gba"] = g.normal(0, 4, (n_mp, 3)).astype(np.float32)
+    c["mpb_pos_gba"] = g.normal(0, 4, (n_mpb, 3)).astype(np.float32)
+    c["mp_bad"] = (g.random(n_mp) < 0.15).astype(np.uint8)
+    c["mpb_bad"] = (g.random(n_mpb) < 0.15).astype(np.uint8)
+    c["mp_gba"] = (g.random(n_mp) < 0.4).astype(np.uint8)
+    c["mpb_gba"] = (g.random(n_mpb) < 0.4).astype(np.uint8)
+    c["mp_ref_kf"] = g.integers(0, K, n_mp).astype(np.int32)
+    c["mpb_ref_kf"] = g.integers(-1, K, n_mpb).astype(np.int32)
+    c["mp_normal"] = g.normal(0, 1, (n_mp, 3)).astype(np.float32)
+    used = np.zeros(K, np.int32)
+    for mp in range(n_mp):
+        for kf in g.choice(K, int(g.integers(0, 4)), replace=False):
+            kf = int(kf)
+            if used[kf] >= c["kf_n"][kf]:
+                continue
+            idx = int(used[kf])
+            used[kf] += 1
+            r = g.random()
+            if r < 0.85:
+                c["kf_mp"][kf, idx] = mp
+            if r > 0.1:
+                add_edge(c, mp, kf, idx)
+            if g.random() < 0.1:
+                add_edge(c, mp, -1 - int(g.integers(0, 3)), idx)
+    for mpb in range(n_mpb):
+        for kf in g.choice(K, int(g.integers(0, 4)), replace=False):
+            free = np.flatnonzero(c["kf_mpb"][kf, :c["kf_nb"][kf]] < 0)
+            for idx in free[:int(g.integers(1, 3))]:                     # now and then the same bird point at two features
+                c["kf_mpb"][kf, idx] = mpb
+    c["cur"] = int(g.integers(0, K))
+    for b in g.choice([k for k in range(K) if k != c["cur"]], int(g.integers(1, K - 1)), replace=False):
+        c["connections"].append((c["cur"], int(b), int(g.integers(1, 3))))
+    order = [int(x) for x in g.permutation(K)]
+    n_roots = int(g.integers(1, 3))
+    for i, k in enumerate(order[n_roots:], n_roots):
+        c["parent"][k] = order[int(g.integers(0, i))]
+        c["linked"][k] = 0 if g.random() < 0.15 else 1
+    c["origins"] = np.array(order[:n_roots], np.int32)
+    c["kf_gba"] = (g.random(K) < 0.5).astype(np.uint8)
+    c["q"] = g.normal(0, 1, 4)
+    c["q"] /= np.linalg.norm(c["q"])
+    c["t"], c["s"] = g.normal(0, 1, 3), float(g.uniform(0.7, 1.6))
+    if bad_entries:
+        c["kf_mp"][c["cur"], 0] = n_mp + 3
+        c["kf_mpb"][c["cur"], 0] = n_mpb
+        c["mp_ref_kf"][:2] = (-1, K)
+        c["mpb_ref_kf"][0] = K + 1
+        c["kf_octave"][int(order[0]), :] = N_LEVELS
+        add_edge(c, n_mp, 0, 0)
+        c["origins"] = np.append(c["origins"], np.array([order[-1], K, c["origins"][0]], np.int32)).astype(np.int32)
+    return c
+
+
 def _probe():
     import time
     import torch
@@ -335,6 +445,7 @@ def _probe():
     print("device local_window (collect, enqueued):  %.3f ms" % timed(lambda: G.local_window(m, t, cur, False)))
     print("device window_scatter:                    %.3f ms" % timed(lambda: G.window_scatter(m, t, w)))
     _probe_local_map(p, m, G, t, cur)
+    _probe_map_correct(p, m, G, cur)
     print("errors counted: %d" % G.error_count())
     G.close()
     _probe_host(p, cur)
@@ -399,6 +510,50 @@ def _probe_local_map(p, m, G, t, cur):
     print("device tree_set + tree_erase_keyframe:    %.3f ms" % _median_ms(erase_again))
     print("device tree_set alone:                    %.3f ms" % _median_ms(lambda: G.tree_set(parent, linked, first)))
     G.tree_set(parent, linked, first)
+
+
+def _probe_map_correct(p, m, G, cur):
+    """fb_covis_correct_loop_dev (reuse_index 0 / 1) and fb_covis_propagate_gba_dev on the probe's map; for the second the
+    tree is a binary heap over the slots (slot 0 the origin, depth 9) and is put back afterwards.  Scw is cur's own pose and kf_Tcw_gba = kf_Tcw, so the repeated
+    calls keep the map where it is; half of the key frames and a third of the points carry the GBA flag."""
+    import torch
+    from .covis import DeviceTables
+    K, n_mp = p["K"], len(p["mp_bad"])
+    g = np.random.default_rng(11)
+    tab = window_tables(p, 7)
+    tab["kf_Tcw"] = np.stack([pose12(rotation(g.normal(0, 0.5, 3)), g.normal(0, 3, 3)) for _ in range(K)])
+    t = DeviceTables(dict(p, **tab))
+    ref = np.zeros(n_mp, np.int32)
+    live = p["obs_kf"] >= 0
+    ref[p["obs_mp"][live]] = p["obs_kf"][live]
+    scale = (1.2 ** np.arange(N_LEVELS)).astype(np.float32)
+    G.reserve_correct_loop(m.n_mp, m.n_obs, 30)
+    d, a = G.correct_loop_arrays(m, scale, ref, g.normal(0, 1, (n_mp, 3)), np.ones(n_mp), np.full(n_mp, 9.0))
+    T = tab["kf_Tcw"][cur].reshape(3, 4).astype(np.float64)
+    w = np.sqrt(max(0.0, 1 + T[0, 0] + T[1, 1] + T[2, 2])) / 2
+    q = [(T[2, 1] - T[1, 2]) / (4 * w), (T[0, 2] - T[2, 0]) / (4 * w), (T[1, 0] - T[0, 1]) / (4 * w), w]
+    G.update_connections(m, [cur])
+    G.correct_loop(m, t, a, cur, q, T[:, 3], 1.0)
+    torch.cuda.synchronize()
+    print("correct_loop of key frame %d: %d key frames in the set, %d of %d points moved" % (
+        cur, int(d["d_n_set"].cpu()[0]), int((d["d_mp_corrected_ref"][:n_mp] >= 0).sum().cpu()), n_mp))
+    print("device correct_loop, reuse_index = 0:     %.3f ms" % _median_ms(lambda: G.correct_loop(m, t, a, cur, q, T[:, 3], 1.0)))
+    print("device correct_loop, reuse_index = 1:     %.3f ms" % _median_ms(lambda: G.correct_loop(m, t, a, cur, q, T[:, 3], 1.0, reuse_index=True)))
+    flags = torch.from_numpy((g.random(K) < 0.5).astype(np.uint8)).to(G.device)
+    poses = t.t["kf_Tcw"].clone()
+    gd, ga = G.propagate_gba_arrays(m, t, [0], flags, poses, poses, (g.random(n_mp) < 0.33).astype(np.uint8), t.t["mp_xw"].reshape(-1).clone(), ref)   # mPosGBA: the positions as they are
+
+    saved = [x.clone() for x in G.tree_get()]
+    G.tree_set((np.arange(K) - 1) // 2, np.ones(K, np.uint8))
+
+    def gba_again():
+        gd["kf_gba"][:K].copy_(flags)
+        G.propagate_gba(m, t, ga)
+    gba_again()
+    torch.cuda.synchronize()
+    print("propagate_gba from slot 0: %d of %d key frames reached" % (int(gd["d_reached"][:K].sum().cpu()), K))
+    print("device flag copy + propagate_gba:         %.3f ms" % _median_ms(gba_again))
+    G.tree_set(*saved)
 
 
 def _probe_host_local_map(p, cur, tests, d):

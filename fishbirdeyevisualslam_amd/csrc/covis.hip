@@ -8,6 +8,7 @@
 //   LocalMapping::KeyFrameCulling                                  src/LocalMapping.cc:656-729
 //   MapPoint::EraseObservation (its effect on later key frames)    src/MapPoint.cc:111-137
 //   the spanning tree and Tracking::UpdateLocalMap                  covis_tree.inc
+//   LoopClosing::CorrectLoop and the map update after the global BA  covis_correct.inc
 //
 // State: one dense row of uint16 per key frame, W[a][b] = weight (bits 0..14, 0 = no entry) | member of the ordered vector
 // (bit 15).  mvpOrderedConnectedKeyFrames is always "descending by (weight, kf_order)" over the members, so it is derived
@@ -758,3 +759,4 @@ int fb_covis_keyframe_culling(fb_covis *g, const fb_covis_map *H, int32_t cur_sl
 
 #include "covis_window.inc"
 #include "covis_tree.inc"
+#include "covis_correct.inc"

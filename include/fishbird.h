@@ -1116,6 +1116,93 @@ int fb_covis_local_map(fb_covis *g, const fb_covis_map *map, const fb_local_map_
  * has to grow, the index is lost and reuse_index = 1 rebuilds it once.                                                  */
 int fb_covis_reserve_local_map(fb_covis *g, int32_t n_mp, int32_t n_obs, int32_t n_q, int32_t batch, int32_t with_window);
 
+/* ---- map correction: LoopClosing::CorrectLoop (LoopClosing.cc:438-541) and the map update that ends
+ * LoopClosing::RunGlobalBundleAdjustment (:714-825), on fb_covis_map / fb_covis_kf_tables ---------------------------------
+ * Neither call has a floating-point decision: every branch is NULL, bad, holder order or a flag.                        */
+typedef struct fb_correct_loop_args {
+  double q[4], t[3], s;         /* mg2oScw as g2o::Sim3's own members: r (x, y, z, w), t, s                            */
+  int32_t cur_slot;             /* mpCurrentKF                                                                         */
+  int32_t reuse_index;          /* as fb_local_map_args.reuse_index                                                    */
+  const float *scale_factors;   /* [tables.n_levels] mvScaleFactors                                                    */
+  const int32_t *mp_ref_kf;     /* [map.n_mp] mpRefKF as a slot                                                        */
+  float *mp_normal;             /* [map.n_mp][3] in/out: mNormalVector                                                 */
+  float *mp_min_dist;           /* [map.n_mp] in/out: mfMinDistance                                                    */
+  float *mp_max_dist;           /* [map.n_mp] in/out: mfMaxDistance                                                    */
+  int32_t *d_mp_corrected_ref;  /* [map.n_mp] mnCorrectedReference as a slot, -1: the point was not touched            */
+  int32_t *d_n_set;             /* [1] mvpCurrentConnectedKFs.size()                                                   */
+  int32_t *d_set_slots;         /* [max_keyframes] the set in ascending kf_order; entries past *d_n_set are left alone  */
+} fb_correct_loop_args;
+/* Precondition: the graph row of cur_slot is current (the reference calls UpdateConnections on it at :435; the caller
+ * does that with fb_covis_update_connections_dev).  Reads of tables: kf_Tcw, n_levels, mp_xw and, unless kf_mpb is NULL
+ * (no bird side), bird_stride, kf_nb, kf_mpb, n_mpb, mpb_bad, mpb_xw; nothing else of it is looked at.  The octave of
+ * feature i is map.kf_octave.
+ * Set (:438-439) = GetVectorCovisibleKeyFrames(cur) followed by cur, bad key frames included (no isBad test).
+ * NonCorrectedSim3[i] = Sim3(Riw, tiw, 1); CorrectedSim3[i] = Sim3(Ric, tic, 1) * Scw with Tic = Tiw * Twc(cur), a CV_32F
+ * product; CorrectedSim3[cur] = Scw; all from the poses as they come in.  Twc and Ow of a pose are what
+ * KeyFrame::SetPose makes of it (KeyFrame.cc:104-118); cv::Mat products accumulate in double and round once; the Sim3
+ * algebra is g2o's (sim3.h:64, :144, :233, :266) in double.
+ * Map points: the point loop iterates a std::map<KeyFrame*, Sim3>, so it runs in ascending kf_order, not in list order.
+ * A non-NULL, non-bad point is moved once, by the holder with the smallest kf_order among the set members whose kf_mp row
+ * contains it (mnCorrectedByKF), through CorrectedSwi.map(Siw.map(P)) of that holder; d_mp_corrected_ref = that slot.
+ * UpdateNormalAndDepth (MapPoint.cc:330-371) runs on each moved point inside that serial loop, so it sees a half-corrected
+ * map: each observer (live edge; bad key frames are not tested) contributes its camera centre, an observer that is in the
+ * set with kf_order strictly smaller than the holder's its CORRECTED centre, every other observer its old one -- the
+ * holder itself included, whose SetPose comes after its point loop.  dist is to the reference key frame's centre under
+ * the same rule; level is the octave at observations[pRefKF], and when the reference key frame is not among the observers
+ * operator[] inserts 0 there, so the level is feature 0's octave.  A point with no live edge keeps its normal and
+ * distances; it is still moved.  mfMaxDistance = dist * scale[level], mfMinDistance = max / scale[n_levels - 1],
+ * normal / n.
+ * Bird points (:506-525): line :523 is a comparison, not an assignment, so a bird point is never marked.  Every set
+ * member that holds it in kf_mpb moves it again (once per feature it is held at), in ascending kf_order, each applying
+ * its own CorrectedSwi o Siw to the result of the one before.
+ * Poses: kf_Tcw[i] = [R(CorrectedSiw) | t / s] for every set member, written after all reads of old poses.
+ * d_set_slots is the list to hand to fb_covis_update_connections_dev for the UpdateConnections at :540: those calls
+ * depend on no pose, so one batched call after this one equals the interleaved calls.
+ * Out-of-range entries (kf_mp, kf_mpb, and for a moved point with a live edge mp_ref_kf and the octave, which then keeps
+ * its normal and distances) are skipped and counted (fb_covis_error_count), never used as an index.
+ * Not restated: the loop fusion (:545-560), SearchAndFuse, OptimizeEssentialGraph.  Enqueues only.                      */
+int fb_covis_correct_loop_dev(fb_covis *g, const fb_covis_map *map, const fb_covis_kf_tables *tables,
+                              const fb_correct_loop_args *a, void *stream);
+int fb_covis_correct_loop(fb_covis *g, const fb_covis_map *map, const fb_covis_kf_tables *tables,
+                          const fb_correct_loop_args *a); /* host pointers throughout */
+/* Scratch for fb_covis_correct_loop_dev ahead of time: behind the index, like fb_covis_reserve_local_map; n_mpb and
+ * bird_stride are 0 without the bird side (which takes max_keyframes * bird_stride ints).                              */
+int fb_covis_reserve_correct_loop(fb_covis *g, int32_t n_mp, int32_t n_obs, int32_t n_q, int32_t n_mpb, int32_t bird_stride);
+
+typedef struct fb_propagate_gba_args {
+  int32_t n_origins;
+  const int32_t *origins;       /* [n_origins] mvpKeyFrameOrigins as slots                                             */
+  uint8_t *kf_gba;              /* [max_keyframes] in/out: mnBAGlobalForKF == nLoopKF                                  */
+  float *kf_Tcw_gba;            /* [max_keyframes][12] in/out: mTcwGBA                                                 */
+  float *kf_Tcw_bef;            /* [max_keyframes][12] in/out: mTcwBefGBA                                              */
+  const uint8_t *mp_gba;        /* [map.n_mp] mnBAGlobalForKF == nLoopKF of the point                                  */
+  const float *mp_pos_gba;      /* [map.n_mp][3] mPosGBA                                                               */
+  const int32_t *mp_ref_kf;     /* [map.n_mp] mpRefKF as a slot                                                        */
+  const uint8_t *mpb_gba;       /* [tables.n_mpb] } the same for MapPointBird; mpb_ref_kf == -1: pRefKF == NULL        */
+  const float *mpb_pos_gba;     /* [tables.n_mpb][3] }                                                                 */
+  const int32_t *mpb_ref_kf;    /* [tables.n_mpb] }                                                                    */
+  uint8_t *d_reached;           /* [max_keyframes] 1: the walk visited the key frame                                   */
+} fb_propagate_gba_args;
+/* Reads of tables: kf_Tcw, mp_xw and, unless mpb_xw is NULL (no bird side), n_mpb, mpb_bad, mpb_xw; of map: n_mp, mp_bad.
+ * Key frames (:715-740): a breadth-first walk from the origins over GetChilds(), which is parent[c] == a && linked[c] of
+ * the handle's tree.  For an unflagged child TcwGBA = (Tcw_child * Twc_parent) * TcwGBA_parent, two CV_32F 4x4 products,
+ * each rounded, and its flag is set.  Both factors of the first product are OLD poses: Twc is read at :721 before the
+ * parent's SetPose at :737; the only dependence on the walk is through the parent's TcwGBA.  Every visited key frame
+ * gets kf_Tcw_bef = kf_Tcw and then kf_Tcw = kf_Tcw_gba.  Key frames that are not reached keep all three arrays.
+ * Precondition, checked and counted rather than trusted: the origins are distinct slots with parent == -1; an entry that
+ * is out of range, has a parent, or repeats an earlier one is counted and left out.  The walk then ends on any input; one
+ * deeper than max_keyframes levels would stop and be counted.
+ * Points (:747-825), after the key frames: a bad point is left alone; a flagged point becomes its pos_gba; otherwise the
+ * point is skipped unless its reference key frame's flag is set after the walk, and then becomes
+ * Rwc * (Rcw_bef * P + tcw_bef) + twc, with Rcw_bef / tcw_bef from kf_Tcw_bef as it stands (for a flagged but unreached
+ * key frame that is whatever the caller passed, which is why the array is in/out) and Twc that of the new pose.  A map
+ * point whose reference is -1 or out of range is skipped and counted (the reference dereferences it); a bird point
+ * whose reference is -1 is skipped (:799-803), out of range skipped and counted.  Enqueues only; no scratch.            */
+int fb_covis_propagate_gba_dev(fb_covis *g, const fb_covis_map *map, const fb_covis_kf_tables *tables,
+                               const fb_propagate_gba_args *a, void *stream);
+int fb_covis_propagate_gba(fb_covis *g, const fb_covis_map *map, const fb_covis_kf_tables *tables,
+                           const fb_propagate_gba_args *a); /* host pointers throughout */
+
 /* ======================================================================== */
 /* Frame geometry either side of the matchers (src/Frame.cc)                 */
 /* ======================================================================== */
