@@ -9,30 +9,28 @@
 //   BlockSolver::solve (Schur complement)       core/block_solver.hpp:354-486
 //   OptimizationAlgorithmLevenberg::solve       core/optimization_algorithm_levenberg.cpp:61-164
 //
-// Kernels per LM evaluation (all fp64 like g2o):
-//   k_ba_linearize  one lane per landmark: residuals, Huber weights, Hll (3x3), bl, and the 6x3
-//                   pose-landmark blocks W_e of its edges; per-block partial chi2
-//   k_ba_pose       one workgroup per free keyframe: Hpp diagonal block + bp (wave-shuffle reduce)
-//   k_ba_odom       pose-pose EdgeSE3Quat blocks (few edges) added into the dense Hpp
-// and per LM trial (given lambda):
-//   k_ba_schur      THE MFMA KERNEL: S_part = sum_l (W_l D_l^-1) W_l^T and the reduced rhs, as dense
+// One Levenberg-Marquardt schedule, resident on the device, drives every entry point.  Its state (lambda, chi2, iteration and
+// trial counters, which of the two states is the accepted one) lives in a control block in HBM (BACtl); the host enqueues
+// identical "slots" of kernels, every kernel reads the control block, and k_ba_control takes the accept / reject decision at
+// the end of each slot.  The host forwards the abort flag (pbStopFlag) on a side stream and reads the control block back once
+// per batch of slots -- after every slot when FB_BA_HOST_LM or FB_BA_TRACE is set (host-paced: same kernels, same order).
+// Kernels of a slot (all fp64 like g2o):
+//   k_ba_schur_c    THE MFMA KERNEL: S_part = sum_l (W_l D_l^-1) W_l^T and the reduced rhs, as dense
 //                   LDS panels (6n x 3c per chunk of c landmarks) multiplied with
 //                   v_mfma_f64_16x16x4_f64; upper-triangular 16x16 tiles only, like g2o
-//   k_ba_solve      S = Hpp + lambda I - sum S_part, dense LDL^T in LDS, triangular solves in one wave
-//   k_ba_update     landmark back-substitution, exp-map pose update, trial state, scale term
-// Two schedules drive these kernels:
-//   device-resident (the default up to 23 free key frames, and always for fb_local_ba_dev): the k_ba_*_c twins of the
-//       kernels above read the Levenberg-Marquardt state from a control block in HBM and k_ba_control takes the
-//       accept / reject decision at the end of each slot; the host enqueues slots in batches, forwards the abort flag
-//       (pbStopFlag) on a side stream and reads the control block back once per batch;
-//   host-driven (more than 23 free key frames with the HBM-resident reduced system of ba_big.inc, FB_BA_TRACE,
-//       FB_BA_HOST_LM): the accept / reject logic runs on the host between trials (a few scalars are read back per
-//       trial) and the abort flag is polled there.
+//   k_ba_sumparts_c the workgroup partials of the Schur complement summed in a fixed order
+//   k_ba_solve_c    S = Hpp + lambda I - sum S_part, dense LDL^T in LDS with look-ahead, backward substitution in one wave
+//                   (more than 23 free key frames: the reduced system lives in HBM, the kernels of ba_big.inc take these three places)
+//   k_ba_update_c   landmark back-substitution, exp-map pose update, trial state, scale term; the chi2 gate between the rounds
+//   k_ba_lin_c      the linearisation at the trial state in one launch of three roles: four lanes per landmark (residuals,
+//                   Huber weights, Hll, bl, the 6x3 blocks W_e, partial chi2), a quarter of a free key frame's edges per
+//                   workgroup (parts of its Hpp diagonal block and bp), one workgroup for the pose-pose EdgeSE3Quat blocks
+//   k_ba_control    sums the parts, takes the decision (sharded: k_ba_prex and an all-reduce precede it)
 // This file holds the kernels; the host side of the translation unit is included at its end:
 //   ba_exchange.inc  RCCL / callback transport of the landmark-sharded BA, fb_rccl_*
 //   ba_big.inc       kernels and host pieces of the HBM-resident reduced system
 //   ba_graph.inc     layout of the staged graph, host builder, device builder (k_bld_*), odometry CSR, argument agreement
-//   ba_driver.inc    plan, device binding, both schedules, result hand-over, local_ba_impl, the extern "C" entry points
+//   ba_driver.inc    plan, device binding, the slot loop, result hand-over, local_ba_impl, the extern "C" entry points
 #include "fb_common.h"
 #include "fb_primitives.h"
 
@@ -51,7 +49,6 @@ constexpr int T_PROJ = 0, T_XYZ = 1;
 constexpr int LIN_THREADS = 128;
 constexpr int POSE_THREADS = 256;
 constexpr int SCHUR_THREADS = 256;
-constexpr int SOLVE_THREADS = 256;
 constexpr int CHUNK = 16;  // landmarks per MFMA panel (K = 48)
 constexpr int KP = 3 * CHUNK;
 constexpr int KPAD = KP + 2;  // LDS row stride in doubles (breaks the 2-way bank conflict of stride 48)
@@ -79,10 +76,10 @@ struct LinBuf {  // linearisation at one state
   double *Hll;   // [npt][9]
   double *bl;    // [npt][3]
   double *W;     // [nE][18]
-  double *Hpp;   // [P6][P6] dense
+  double *Hpp;   // [P6][P6]: the key frames' 6x6 diagonal blocks only (the pose-pose blocks are HppO of the exchange block)
   double *bp;    // [P6]
-  double *chiPart;  // [nLinBlocks + 1] (last = odom chi2)
-  double *maxPart;  // [nLinBlocks] max |diag Hll| of the block's landmarks (lambda_0 = 1e-5 max diag; device-resident schedule)
+  double *chiPart;  // [nLin + 1] per workgroup of the landmark role (last = odom chi2)
+  double *maxPart;  // [nLin] max |diag Hll| of the workgroup's landmarks (lambda_0 = 1e-5 max diag)
 };
 
 struct State {
@@ -91,7 +88,7 @@ struct State {
 };
 
 // fb::rcp_f64_newton serves the pivots of the reduced pose system: the BA is held to 1e-4 on poses and landmarks, and an
-// IEEE division is ~35 dependent instructions on the critical path of every block step of k_ba_solve
+// IEEE division is ~35 dependent instructions on the critical path of every block step of k_ba_solve_c
 using fb::rcp_f64_newton;
 using fb::wave_sum;
 using fb::dpp_f64;
@@ -221,7 +218,7 @@ __device__ __forceinline__ void lin_edge(const BADev &D, const LinBuf &B, const 
   }
 }
 
-// The same with FOUR lanes per landmark (device-resident schedule): lane `sub` of a quad takes the landmark's edges sub,
+// The landmark role of the linearisation, FOUR lanes per landmark: lane `sub` of a quad takes the landmark's edges sub,
 // sub + 4, ...; Hll, bl and chi2 are summed over the quad with two DPP quad permutes ((a0 + a1) + (a2 + a3)).  A landmark has
 // 2..10 observers, so one lane per landmark walked them serially with three dependent gathers each: the landmark role was
 // the long pole of the linearisation launch.
@@ -275,69 +272,16 @@ __device__ __forceinline__ void linearize_quad_body(const BADev &D, const State 
     double s = 0, m = 0;
     for (int i = 0; i < TH / 64; i++) { s += s_part[i]; m = fmax(m, s_part[TH / 64 + i]); }
     B.chiPart[blockIdx.x] = s;
-    if (B.maxPart) B.maxPart[blockIdx.x] = m;
+    B.maxPart[blockIdx.x] = m;
   }
 }
 
 // ------------------------------------------------------------------------------------------
-// k_ba_linearize: one lane per landmark
+// The key-frame role of the linearisation: this workgroup sums every nparts-th edge of free key frame k starting at `part`;
+// its 27 sums (21 upper entries of the Hpp diagonal block, 6 of bp) go to partOut (k_ba_control adds the parts in order)
 // ------------------------------------------------------------------------------------------
-template <int TH>
-__device__ __forceinline__ void linearize_body(const BADev &D, const State &S, const LinBuf &B, int robust, double *s_part) {
-  const int l = blockIdx.x * TH + threadIdx.x;
-  double chi = 0, hmax = 0;
-  if (l < D.npt) {
-    const double X[3] = {S.pt[3 * l], S.pt[3 * l + 1], S.pt[3 * l + 2]};
-    double H[9], b3[3] = {0, 0, 0};
-#pragma unroll
-    for (int i = 0; i < 9; i++) H[i] = 0;
-    // The edges of a landmark are walked in chunks of 4 with the three dependent gathers (edge id -> its scalars and key
-    // frame -> the key frame's pose) each issued for the whole chunk: three memory latencies per chunk, not per edge.
-    const int cBeg = D.lm_start[l], cEnd = D.lm_start[l + 1];
-    for (int c0 = cBeg; c0 < cEnd; c0 += 4) {
-      int ee[4], kfv[4], lvl[4], typ[4];
-      double infov[4], measv[4][3];
-      SE3 Tv[4];
-#pragma unroll
-      for (int u = 0; u < 4; u++) ee[u] = D.lm_edges[min(c0 + u, cEnd - 1)];
-#pragma unroll
-      for (int u = 0; u < 4; u++) {
-        kfv[u] = D.e_kf[ee[u]]; lvl[u] = D.e_level[ee[u]]; typ[u] = D.e_type[ee[u]]; infov[u] = D.e_info[ee[u]];
-        measv[u][0] = D.e_meas[3 * ee[u]]; measv[u][1] = D.e_meas[3 * ee[u] + 1]; measv[u][2] = D.e_meas[3 * ee[u] + 2];
-      }
-#pragma unroll
-      for (int u = 0; u < 4; u++) Tv[u] = S.pose[kfv[u]];
-#pragma unroll
-      for (int u = 0; u < 4; u++) {
-      if (c0 + u >= cEnd) break;
-      lin_edge(D, B, X, ee[u], kfv[u], lvl[u], typ[u], infov[u], measv[u], Tv[u], robust, H, b3, chi);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < 9; i++) B.Hll[(size_t)9 * l + i] = H[i];
-#pragma unroll
-    for (int i = 0; i < 3; i++) B.bl[(size_t)3 * l + i] = b3[i];
-    hmax = fmax(fmax(fabs(H[0]), fabs(H[4])), fabs(H[8]));
-  }
-  const double ws = wave_sum(chi);
-  hmax = fb::wave_max(hmax);
-  if ((threadIdx.x & 63) == 0) { s_part[threadIdx.x >> 6] = ws; s_part[TH / 64 + (threadIdx.x >> 6)] = hmax; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double s = 0, m = 0;
-    for (int i = 0; i < TH / 64; i++) { s += s_part[i]; m = fmax(m, s_part[TH / 64 + i]); }
-    B.chiPart[blockIdx.x] = s;
-    if (B.maxPart) B.maxPart[blockIdx.x] = m;
-  }
-}
-
-// ------------------------------------------------------------------------------------------
-// k_ba_pose: one workgroup per free keyframe -> Hpp(k,k) and bp(k)
-// ------------------------------------------------------------------------------------------
-// part / nparts: this workgroup sums every nparts-th edge of key frame k starting at `part`; partOut != nullptr: the 27 sums
-// (21 upper Hpp entries, 6 bp) go to partOut instead of Hpp / bp (k_ba_control adds the parts in order)
-__device__ __forceinline__ void pose_body(const BADev &D, const State &S, const LinBuf &B, int robust, int P6, double (*s_part)[27], int k,
-                                          int part = 0, int nparts = 1, double *partOut = nullptr) {
+__device__ __forceinline__ void pose_body(const BADev &D, const State &S, int robust, double (*s_part)[27], int k, int part, int nparts,
+                                          double *partOut) {
   const int tid = threadIdx.x;
   double acc[27];
 #pragma unroll
@@ -392,29 +336,20 @@ __device__ __forceinline__ void pose_body(const BADev &D, const State &S, const 
     s_part[0][tid] = s;
   }
   __syncthreads();
-  if (partOut) {
-    if (tid < 27) partOut[tid] = s_part[0][tid];
-    return;
-  }
-  if (tid < 36) {
-    const int i = tid / 6, j = tid % 6;
-    const int a = i < j ? i : j, b2 = i < j ? j : i;
-    const int idx = a * 6 - a * (a - 1) / 2 + (b2 - a);  // upper-triangular packing
-    B.Hpp[(size_t)(6 * k + i) * P6 + 6 * k + j] = s_part[0][idx];
-  }
-  if (tid < 6) B.bp[6 * k + tid] = s_part[0][21 + tid];
+  if (tid < 27) partOut[tid] = s_part[0][tid];
 }
 
 // ------------------------------------------------------------------------------------------
-// k_ba_odom: EdgeSE3Quat (OdomG2oTypeQuat.cc:180-204). Phase a: one lane per edge computes the
-// residual and Jacobians into LDS; phase b: one lane per (free pose, row) adds the blocks into Hpp
+// The odometry role of the linearisation: EdgeSE3Quat (OdomG2oTypeQuat.cc:180-204). Phase a: one lane per edge computes the
+// residual and Jacobians into LDS; phase b: one lane per (free pose, row) adds the pose-pose blocks into HppO / bpO
 // in edge order (deterministic).
 // ------------------------------------------------------------------------------------------
 struct OdomLin { double A[36], Bm[36], err[6]; };
+constexpr int ODOM_DENSE_CLEAR_P6 = 138;  // 23 free key frames, the largest LDS-resident system (plan() in ba_driver.inc)
 
 template <bool GLOBAL>  // GLOBAL: the per-edge linearisations live in HBM scratch (they do not fit LDS)
 __device__ __forceinline__ void odom_body(const BADev &D, const State &S, const LinBuf &B, int P6, int chiSlot, OdomLin *ol, double *s_chi,
-                                          double *Hout, double *bout, bool zeroFirst, double *tmp = nullptr) {
+                                          double *HppO, double *bpO, double *tmp) {
   const int tid = threadIdx.x;
   double chi = 0;
   // tmp != nullptr (LDS, 108 doubles per edge: adj(T2) | adj(T1^-1) | J adj(T2)): the two 6x6x6 products of an edge are
@@ -490,9 +425,24 @@ __device__ __forceinline__ void odom_body(const BADev &D, const State &S, const 
   // phase b: lane (k, i) = row i of free pose k.  The row's diagonal block and right-hand side entry are accumulated in
   // registers over the incident edges and written once; an off-diagonal block is loaded, updated and stored as a group of six
   // (one memory round trip per block: the 72 dependent read-modify-writes per row this replaces were most of the role's time)
-  if (zeroFirst) {  // Hout / bout are this role's own scratch: clear it with coalesced stores
-    for (int i = tid; i < P6 * P6; i += 256) Hout[i] = 0;
+  // HppO / bpO are this role's own scratch; the diagonal blocks and bpO are stored whole below, the off-diagonal blocks are
+  // cleared here.  LDS-resident system: all of HppO, with coalesced stores.  Beyond it P6 x P6 stores from this one workgroup
+  // would take longer than the rest of the linearisation: HppO starts cleared and only the blocks of the odometry edges are ever
+  // written, so a row clears just the blocks its edges are about to add into (four dependent gathers: slower at small P6)
+  if (P6 <= ODOM_DENSE_CLEAR_P6) {
+    for (int i = tid; i < P6 * P6; i += 256) HppO[i] = 0;
     __syncthreads();
+  } else {
+    for (int row = tid; row < P6; row += 256) {
+      const int k = row / 6;
+      for (int cc = D.od_start[k]; cc < D.od_start[k + 1]; cc++) {
+        const int e = D.od_edges[cc];
+        const int pe[2] = {D.poseIdx[D.o_i[e]], D.poseIdx[D.o_j[e]]};
+        for (int side = 0; side < 2; side++)
+          if (pe[side] >= 0 && pe[side] != k)
+            for (int j = 0; j < 6; j++) HppO[(size_t)row * P6 + 6 * pe[side] + j] = 0;
+      }
+    }
   }
   for (int row = tid; row < P6; row += 256) {
     const int k = row / 6, i = row % 6;
@@ -520,7 +470,7 @@ __device__ __forceinline__ void odom_body(const BADev &D, const State &S, const 
         if (pc == k) {
           for (int j = 0; j < 6; j++) dg[j] += v[j];
         } else {
-          double *dst = Hout + (size_t)row * P6 + 6 * pc, t6[6];
+          double *dst = HppO + (size_t)row * P6 + 6 * pc, t6[6];
           for (int j = 0; j < 6; j++) t6[j] = dst[j];
           for (int j = 0; j < 6; j++) dst[j] = t6[j] + v[j];
         }
@@ -531,19 +481,13 @@ __device__ __forceinline__ void odom_body(const BADev &D, const State &S, const 
         bacc += b2;
       }
     }
-    double *dd = Hout + (size_t)row * P6 + 6 * k;
-    if (zeroFirst) {
-      for (int j = 0; j < 6; j++) dd[j] = dg[j];
-      bout[row] = bacc;
-    } else {
-      for (int j = 0; j < 6; j++) dd[j] += dg[j];
-      bout[row] += bacc;
-    }
+    for (int j = 0; j < 6; j++) HppO[(size_t)row * P6 + 6 * k + j] = dg[j];
+    bpO[row] = bacc;
   }
 }
 
 // ------------------------------------------------------------------------------------------
-// k_ba_schur: MFMA fp64 accumulation of the Schur complement.
+// k_ba_schur_c: MFMA fp64 accumulation of the Schur complement.
 //   C[NT*16][NT*16] (upper tiles) += Yp[rows][K] * Wp[rows][K]^T over chunks of CHUNK landmarks,
 //   Yp = W_e * Dinv_l scattered at rows 6*pose.., columns 3*li..; Wp likewise with W_e;
 //   Wp row P6 carries bl so that column P6 of C is the reduced right-hand side (coefficients).
@@ -669,168 +613,15 @@ __device__ __forceinline__ void schur_body(const BADev &D, const LinBuf &B, doub
 }
 
 // ------------------------------------------------------------------------------------------
-// k_ba_solve: reduce partials, S = Hpp + lambda I - sum, LDL^T (no pivoting) and solves.
-// ------------------------------------------------------------------------------------------
-// HppO != nullptr: the dense Hpp is not materialised: B.Hpp holds the key frames' diagonal blocks only and HppO the
-// odometry (pose-pose) blocks (device-resident schedule)
-__device__ __forceinline__ void solve_body(const LinBuf &B, double lambda, const double *Spart, int nWg, int P6,
-                                           int NT, double *xp, double *okFlag, uint8_t *smem, int &s_ok, const double *HppO = nullptr) {
-  double *A = reinterpret_cast<double *>(smem);  // [P6][P6+1] lower triangle used
-  const int ld = P6 + 1;
-  double *rhs = A + (size_t)P6 * ld;             // [P6]
-  const int tid = threadIdx.x, rows = NT * 16;
-  if (tid == 0) s_ok = 1;
-  for (int idx = tid; idx < P6 * P6; idx += SOLVE_THREADS) {
-    const int i = idx / P6, j = idx % P6;
-    if (j > i) continue;  // lower triangle: A[i][j] = S[j][i] (upper, as g2o's solver reads it)
-    double s = 0;
-    for (int w = 0; w < nWg; w++) s += Spart[(size_t)w * rows * rows + (size_t)j * rows + i];
-    double h;
-    if (HppO) h = (i / 6 == j / 6 ? B.Hpp[(size_t)j * P6 + i] : 0.0) + HppO[(size_t)j * P6 + i];
-    else h = B.Hpp[(size_t)j * P6 + i];
-    if (i == j) h += lambda;
-    A[(size_t)i * ld + j] = h - s;
-  }
-  for (int i = tid; i < P6; i += SOLVE_THREADS) {
-    double s = 0;
-    for (int w = 0; w < nWg; w++) s += Spart[(size_t)w * rows * rows + (size_t)i * rows + P6];
-    rhs[i] = B.bp[i] - s;
-  }
-  __syncthreads();
-  // Blocked right-looking LDL^T with 6x6 blocks (one keyframe per block): per block step every thread factors the
-  // diagonal block redundantly in registers (no broadcast barrier), one thread per row solves the panel, and the
-  // trailing sub-matrix gets a rank-6 update -- two barriers per keyframe instead of one per column.
-  // On exit A holds the unit-lower L below the diagonal and D on it.
-  double *Up = rhs + P6;  // [P6][6] panel u = l * d of the current block step
-  const int nb6 = P6 / 6;
-  for (int J = 0; J < nb6; J++) {
-    const int c0 = 6 * J, c1 = c0 + 6;
-    double Lb[6][6], d[6], dinv[6];
-#pragma unroll
-    for (int r = 0; r < 6; r++)
-#pragma unroll
-      for (int c = 0; c <= r; c++) Lb[r][c] = A[(size_t)(c0 + r) * ld + c0 + c];
-    bool neg = false;
-#pragma unroll
-    for (int c = 0; c < 6; c++) {
-      double dc = Lb[c][c];
-#pragma unroll
-      for (int m = 0; m < c; m++) dc -= Lb[c][m] * Lb[c][m] * d[m];
-      if (dc == 0) neg = true;  // SimplicialLDLT: the factorisation fails on a pivot that is exactly 0, negative pivots proceed
-      d[c] = dc;
-      const double inv = dc != 0 ? rcp_f64_newton(dc) : 0.0;
-      dinv[c] = inv;
-#pragma unroll
-      for (int r = c + 1; r < 6; r++) {
-        double v = Lb[r][c];
-#pragma unroll
-        for (int m = 0; m < c; m++) v -= Lb[r][m] * Lb[c][m] * d[m];
-        Lb[r][c] = v * inv;
-      }
-    }
-    if (neg && tid == 0) s_ok = 0;
-    __syncthreads();  // everyone has read the diagonal block before it is overwritten
-    if (tid == 0) {
-#pragma unroll
-      for (int r = 0; r < 6; r++) {
-        A[(size_t)(c0 + r) * ld + c0 + r] = d[r];
-#pragma unroll
-        for (int c = 0; c < r; c++) A[(size_t)(c0 + r) * ld + c0 + c] = Lb[r][c];
-      }
-    }
-    for (int i = c1 + tid; i < P6; i += SOLVE_THREADS) {  // panel: row i of L below the block
-      double u[6];
-#pragma unroll
-      for (int c = 0; c < 6; c++) {
-        double v = A[(size_t)i * ld + c0 + c];
-#pragma unroll
-        for (int m = 0; m < c; m++) v -= u[m] * Lb[c][m];
-        u[c] = v;
-      }
-#pragma unroll
-      for (int c = 0; c < 6; c++) {
-        Up[(size_t)i * 6 + c] = u[c];
-        A[(size_t)i * ld + c0 + c] = u[c] * dinv[c];  // dinv = 0 for a zero pivot, as the division rule above
-      }
-    }
-    __syncthreads();
-    const int tr = tid >> 4, tc = tid & 15;
-    for (int i = c1 + tr; i < P6; i += 16) {
-      double u[6];
-#pragma unroll
-      for (int c = 0; c < 6; c++) u[c] = Up[(size_t)i * 6 + c];
-      for (int k = c1 + tc; k <= i; k += 16) {
-        double acc2 = 0;
-#pragma unroll
-        for (int c = 0; c < 6; c++) acc2 += u[c] * A[(size_t)k * ld + c0 + c];
-        A[(size_t)i * ld + k] -= acc2;
-      }
-    }
-    __syncthreads();
-  }
-  // Triangular solves, blocked like the factorisation: per 6-row block every thread solves the 6x6 triangle
-  // redundantly from LDS (no broadcast barrier), then the rows outside the block take their rank-6 update in parallel
-  // -- one barrier per key frame and direction instead of 2 x P6 dependent shuffle steps in a single wave.
-  for (int J = 0; J < nb6; J++) {  // forward: L y = b
-    const int c0 = 6 * J, c1 = c0 + 6;
-    double yJ[6];
-#pragma unroll
-    for (int r = 0; r < 6; r++) {
-      double v = rhs[c0 + r];
-#pragma unroll
-      for (int m = 0; m < r; m++) v -= A[(size_t)(c0 + r) * ld + c0 + m] * yJ[m];
-      yJ[r] = v;
-    }
-    __syncthreads();  // everyone has read rhs[c0..c1) before it is overwritten / the rows below are updated
-    if (tid < 6) rhs[c0 + tid] = yJ[tid];
-    for (int i = c1 + tid; i < P6; i += SOLVE_THREADS) {
-      double v = rhs[i];
-#pragma unroll
-      for (int c = 0; c < 6; c++) v -= A[(size_t)i * ld + c0 + c] * yJ[c];
-      rhs[i] = v;
-    }
-    __syncthreads();
-  }
-  for (int i = tid; i < P6; i += SOLVE_THREADS) {  // D^-1
-    const double dd = A[(size_t)i * ld + i];
-    rhs[i] = dd != 0 ? rhs[i] * rcp_f64_newton(dd) : 0.0;
-  }
-  __syncthreads();
-  for (int J = nb6 - 1; J >= 0; J--) {  // backward: L^T x = y
-    const int c0 = 6 * J;
-    double xJ[6];
-#pragma unroll
-    for (int r = 5; r >= 0; r--) {
-      double v = rhs[c0 + r];
-#pragma unroll
-      for (int m = 5; m > r; m--) v -= A[(size_t)(c0 + m) * ld + c0 + r] * xJ[m];
-      xJ[r] = v;
-    }
-    __syncthreads();
-    if (tid < 6) rhs[c0 + tid] = xJ[tid];
-    for (int i = tid; i < c0; i += SOLVE_THREADS) {
-      double v = rhs[i];
-#pragma unroll
-      for (int c = 0; c < 6; c++) v -= A[(size_t)(c0 + c) * ld + i] * xJ[c];
-      rhs[i] = v;
-    }
-    __syncthreads();
-  }
-  for (int i = tid; i < P6; i += SOLVE_THREADS) xp[i] = rhs[i];
-  __syncthreads();
-  if (tid == 0) *okFlag = s_ok ? 1.0 : 0.0;
-}
-
-// ------------------------------------------------------------------------------------------
-// solve_lookahead: the same LDL^T (6x6 blocks, no pivoting, fails on a zero pivot) arranged for latency -- this one
-// workgroup sits on the critical path of every LM trial.
+// solve_lookahead (k_ba_solve_c): S = Hpp + lambda I - Spart, dense LDL^T in LDS (6x6 blocks, no pivoting, fails on a zero
+// pivot) and the solves, arranged for latency -- this one workgroup sits on the critical path of every LM trial.
 //  * the right-hand side rides along as row P6 of the matrix: its panel steps ARE the forward substitution, so after the
 //    factorisation row P6 holds z = D^-1 L^-1 b and only the backward substitution remains;
 //  * look-ahead: in the trailing update of step J wave 0 updates only the NEXT diagonal block, factors it (a chain of ~100
 //    dependent fp64 operations) and publishes L, d, 1/d through LDS, while the other three waves update the rest of the
 //    trailing matrix; every thread used to factor the block redundantly BETWEEN the barriers;
 //  * two barriers per key frame instead of three.
-// HppO as in solve_body.
+// The dense Hpp is not materialised: B.Hpp holds the key frames' diagonal blocks only and HppO the odometry (pose-pose) blocks.
 #ifdef FB_BA_STAMPS
 __device__ unsigned long long g_ba_stamps[16];
 #define BA_T0() unsigned long long bt_ = 0; if (threadIdx.x == 0) { __builtin_amdgcn_sched_barrier(0); bt_ = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); }
@@ -1024,7 +815,7 @@ __device__ __forceinline__ void solve_lookahead(const LinBuf &B, double lambda, 
 }
 
 // ------------------------------------------------------------------------------------------
-// k_ba_update: back-substitution, trial state, scale term sum x (lambda x + b)
+// k_ba_update_c: back-substitution, trial state, scale term sum x (lambda x + b)
 // ------------------------------------------------------------------------------------------
 // Four lanes per landmark (as in the linearisation): lane q takes the landmark's edges q, q + 4, ..., the partial sums meet
 // in a two-step butterfly (the same value on all four lanes), lane q < 3 then finishes coordinate q.  One lane per landmark
@@ -1080,18 +871,18 @@ __device__ __forceinline__ void update_body(const BADev &D, const LinBuf &B, con
 }
 
 // Spart[0] = sum over the workgroup partials (sharded BA: the local sum that goes through the all-reduce)
-// rows > 0: the buffers are [rows][rows] matrices of which only the upper 16x16 tiles (and with them column P6, the reduced
+// The buffers are [rows][rows] matrices of which only the upper 16x16 tiles (and with them column P6, the reduced
 // right-hand side) are ever written and read: the lower tiles are skipped
 // 256-thread workgroups: 64 consecutive elements x 4 quarters of the partials (a wave = one quarter, so its loads are
 // contiguous); the quarters meet in LDS in a fixed order.  One thread per element over all nWg partials kept only 64
 // workgroups busy on 19 MB.
 constexpr int SUMPARTS_ELEMS = 64;
-__device__ __forceinline__ void sumparts_body(double *Spart, int nWg, int n, int rows = 0) {
+__device__ __forceinline__ void sumparts_body(double *Spart, int nWg, int n, int rows) {
   __shared__ double s_q[3][SUMPARTS_ELEMS];
   const int lane = threadIdx.x & 63, q = threadIdx.x >> 6;
   const int i = blockIdx.x * SUMPARTS_ELEMS + lane;
   bool live = i < n;
-  if (live && rows > 0) {
+  if (live) {
     const int r = i / rows, c = i - r * rows;
     live = (r >> 4) <= (c >> 4);
   }
@@ -1111,32 +902,6 @@ __device__ __forceinline__ void sumparts_body(double *Spart, int nWg, int n, int
   __syncthreads();
   if (q == 0 && live) Spart[i] = ((s + s_q[0][lane]) + s_q[1][lane]) + s_q[2][lane];
 }
-__global__ void k_ba_sumparts(double *Spart, int nWg, int n) { sumparts_body(Spart, nWg, n); }
-
-// sum of partials in index order + max |diag| (computeLambdaInit)
-__global__ void k_ba_scalars(const double *part, int n, const double *Hpp, int P6, const double *Hll, int npt, double *out,
-                             int wantDiag) {
-  __shared__ double s_m[256];
-  const int tid = threadIdx.x;
-  if (tid == 0) {
-    double s = 0;
-    for (int i = 0; i < n; i++) s += part[i];
-    out[0] = s;
-  }
-  if (wantDiag) {
-    double m = 0;
-    for (int i = tid; i < P6; i += 256) m = fmax(m, fabs(Hpp[(size_t)i * P6 + i]));
-    for (int i = tid; i < npt * 3; i += 256) m = fmax(m, fabs(Hll[(size_t)9 * (i / 3) + 4 * (i % 3)]));
-    s_m[tid] = m;
-    __syncthreads();
-    if (tid == 0) {
-      double mm = 0;
-      for (int i = 0; i < 256; i++) mm = fmax(mm, s_m[i]);
-      out[1] = mm;
-    }
-  }
-}
-
 // gating between the two optimisation rounds and the final outlier flags
 // (Optimizer.cc:1059-1073,1102-1115 / 2534-2565,2573-2607)
 __device__ __forceinline__ void gate_edge(const BADev &D, const State &S, int setLevel, uint8_t *outFlag, int e) {
@@ -1166,42 +931,6 @@ __device__ __forceinline__ void gate_edge(const BADev &D, const State &S, int se
   else outFlag[e] = bad ? 1 : 0;
 }
 
-// ---- __global__ entry points of the bodies above: explicit arguments (host-driven Levenberg-Marquardt: sharded BA, the
-//      HBM-resident reduced system of ba_big.inc, FB_BA_TRACE) ---------------------------------------------------------
-__global__ __launch_bounds__(LIN_THREADS) void k_ba_linearize(BADev D, State S, LinBuf B, int robust) {
-  __shared__ double s_part[2 * LIN_THREADS / 64];
-  linearize_body<LIN_THREADS>(D, S, B, robust, s_part);
-}
-__global__ __launch_bounds__(POSE_THREADS) void k_ba_pose(BADev D, State S, LinBuf B, int robust, int P6) {
-  __shared__ double s_part[POSE_THREADS / 64][27];
-  pose_body(D, S, B, robust, P6, s_part, blockIdx.x);
-}
-template <bool GLOBAL>
-__global__ __launch_bounds__(256) void k_ba_odom(BADev D, State S, LinBuf B, int P6, int chiSlot, OdomLin *olGlobal) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  __shared__ double s_chi[256];
-  odom_body<GLOBAL>(D, S, B, P6, chiSlot, GLOBAL ? olGlobal : reinterpret_cast<OdomLin *>(smem), s_chi, B.Hpp, B.bp, false);
-}
-template <int MAXT>
-__global__ __launch_bounds__(SCHUR_THREADS) void k_ba_schur(BADev D, LinBuf B, double lambda, double *Dinv, double *Spart, int P6, int NT, int lmPerWg) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  schur_body<MAXT>(D, B, lambda, Dinv, Spart, P6, NT, lmPerWg, smem);
-}
-__global__ __launch_bounds__(SOLVE_THREADS) void k_ba_solve(LinBuf B, double lambda, const double *Spart, int nWg, int P6, int NT, double *xp, double *okFlag) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  __shared__ int s_ok;
-  solve_body(B, lambda, Spart, nWg, P6, NT, xp, okFlag, smem, s_ok);
-}
-__global__ __launch_bounds__(LIN_THREADS) void k_ba_update(BADev D, LinBuf B, State cur, State trial, const double *Dinv, const double *xp, double lambda,
-                                                           double *scalePart, int countPoses) {
-  __shared__ double s_part[LIN_THREADS / 64];
-  update_body(D, B, cur, trial, Dinv, xp, lambda, scalePart, countPoses, s_part);
-}
-__global__ void k_ba_gate(BADev D, State S, int setLevel, uint8_t *outFlag) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e < D.nE) gate_edge(D, S, setLevel, outFlag, e);
-}
-
 // ---- device-resident Levenberg-Marquardt ------------------------------------------------------------------------------
 // The accept / reject logic of OptimizationAlgorithmLevenberg::solve (optimization_algorithm_levenberg.cpp:61-164), the
 // iteration loop of SparseOptimizer::optimize and the two-stage schedule of LocalBundleAdjustment[WithOdom]
@@ -1220,6 +949,7 @@ struct BACtl {
   int abort;     // terminate(): set by the host when it sees *pbStopFlag
   int trials, slots;
   int badArgs;   // device-side graph builder (fb_local_ba_dev): 1 = index out of range, 2 = duplicate (key frame, point)
+  double trChi, trScale, trRho;  // FB_BA_TRACE: tempChi, scale and rho of the last trial (after an opening linearisation: chi2_0, max diagonal, 0)
 };
 struct BASched { int its1, robust1, gate, its2; };
 struct St2 { State s[2]; };
@@ -1368,6 +1098,7 @@ __device__ __forceinline__ void control_body(const BADev &D, const Lb2 &lb, BACt
     k.needInit = 0;
     k.currentChi = chi; k.iniChi = chi;
     k.lambda = 1e-5 * maxDiag; k.ni = 2; k.nBad = 0; k.it = 0; k.qmax = 0;
+    k.trChi = chi; k.trScale = maxDiag; k.trRho = 0;
     if (its <= 0 || k.abort) endOpt = true;
   } else {
     k.trials++;
@@ -1375,6 +1106,7 @@ __device__ __forceinline__ void control_body(const BADev &D, const Lb2 &lb, BACt
     if (*okFlag == 0.0) tempChi = 1.7976931348623157e308;  // solver failure (levenberg.cpp:126-127)
     double rho = k.currentChi - tempChi;
     rho /= scale + 1e-3;
+    k.trChi = tempChi; k.trScale = scale + 1e-3; k.trRho = rho;
     if (rho > 0 && isfinite(tempChi)) {
       double alpha = 1. - pow((2 * rho - 1), 3);
       alpha = fmin(alpha, 2. / 3.);
@@ -1421,7 +1153,7 @@ __global__ __launch_bounds__(256) void k_ba_control(BADev D, Lb2 lb, BACtl *c, B
 // other): blocks [0, nLin) = landmarks (Hll, bl, W, chi2); the next POSE_PARTS * np blocks = a quarter of the edges of one
 // free key frame each (27 partial sums of its Hpp diagonal block and bp); the last block = the odometry edges (their
 // pose-pose blocks HppO, bpO).  The dense Hpp is never materialised: k_ba_control adds the key-frame parts into the diagonal
-// blocks and bp, k_ba_solve reads diagonal blocks + HppO.  Scratch per linearisation buffer t: [HppO | bpO], poseP.
+// blocks and bp, k_ba_solve_c / k_big_assemble read diagonal blocks + HppO.  Scratch per linearisation buffer t: [HppO | bpO], poseP.
 // (Measured and dropped: the workgroup that finishes last -- a ticket in BACtl behind a device-scope fence -- taking the slot's
 // decision itself instead of a k_ba_control launch.  A device-scope release / acquire on this part writes back and invalidates
 // the XCD's L2 (buffer_wbl2 sc1 / buffer_inv sc1), once per workgroup: the linearisation went from 21 to 49 us.)
@@ -1438,11 +1170,11 @@ __global__ __launch_bounds__(256) void k_ba_lin_c(BADev D, St2 st, Lb2 lb, const
     linearize_quad_body<256>(D, st.s[t], lb.b[t], robust, s_buf);
   } else if (bx < nLin + POSE_PARTS * D.np) {
     const int q = bx - nLin, k = q / POSE_PARTS, part = q - k * POSE_PARTS;
-    pose_body(D, st.s[t], lb.b[t], robust, P6, reinterpret_cast<double(*)[27]>(s_buf), k, part, POSE_PARTS, xb.at(t) + (size_t)q * 27);
+    pose_body(D, st.s[t], robust, reinterpret_cast<double(*)[27]>(s_buf), k, part, POSE_PARTS, xb.at(t) + (size_t)q * 27);
   } else {
     OdomLin *ol = GLOBAL ? olGlobal : reinterpret_cast<OdomLin *>(smem);
     double *tmp = GLOBAL ? nullptr : reinterpret_cast<double *>(ol + max(D.nO, 1));  // the launch reserves 108 doubles per edge behind the records
-    odom_body<GLOBAL>(D, st.s[t], lb.b[t], P6, chiSlot, ol, s_buf, xb.at(t) + xb.oH, xb.at(t) + xb.oB, true, tmp);
+    odom_body<GLOBAL>(D, st.s[t], lb.b[t], P6, chiSlot, ol, s_buf, xb.at(t) + xb.oH, xb.at(t) + xb.oB, tmp);
   }
 }
 
@@ -1450,13 +1182,6 @@ __global__ __launch_bounds__(256) void k_ba_lin_c(BADev D, St2 st, Lb2 lb, const
 __global__ void k_ba_gate_final_c(BADev D, St2 st, const BACtl *c, uint8_t *outFlag) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e < D.nE) gate_edge(D, st.s[c->cur], 0, outFlag, e);
-}
-
-__global__ void k_ba_export(int n_kf, int npt, const SE3 *pose, const double *pt, const uint8_t *fixed, float *kfT, float *ptOut) {
-  const int g = blockIdx.x * blockDim.x + threadIdx.x;
-  if (g < n_kf) {
-    if (!fixed[g]) fb::se3_to_float12(pose[g], kfT + 12 * g);
-  } else if (g < n_kf + npt * 3) ptOut[g - n_kf] = (float)pt[g - n_kf];
 }
 
 // sharded result: every rank contributes its own landmarks (points as exported floats) and edge flags, the others zeros

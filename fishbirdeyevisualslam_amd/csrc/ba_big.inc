@@ -1,13 +1,15 @@
 // ba_big.inc -- the reduced pose system beyond the LDS-resident limit (more than 23 free key frames; included by ba.hip).
-// The kernels first, the host side (pair lists, one trial's Schur complement + solve) at the end of the file.
+// The kernels first, the host side (pair lists, the Schur complement + solve part of a slot) at the end of the file.
 //
-// Same mathematics as k_ba_schur / k_ba_solve (BlockSolver::solve with the Schur complement, block_solver.hpp:354-486,
-// dense LDL^T without pivoting), but the reduced system S (P6 x P6) lives in HBM and everything is a deterministic gather:
+// Same mathematics as k_ba_schur_c / k_ba_solve_c (BlockSolver::solve with the Schur complement, block_solver.hpp:354-486,
+// dense LDL^T without pivoting) and the same place in a slot of the device-resident schedule: every kernel reads the
+// Levenberg-Marquardt state from BACtl and does nothing in a slot that only linearises or after the schedule has finished.
+// The reduced system S (P6 x P6) lives in HBM and everything is a deterministic gather:
 //   k_ba_dinv            lane per landmark: (Hll + lambda I)^-1
 //   k_ba_schur_gather    one wave per non-zero 6x6 block (pr <= pc) of S: sum over the landmarks seen by both key frames of
 //                        (W_a D^-1) W_b^T; the (block -> edge pair) lists are built once per BA on the host
 //   k_ba_rhs_gather      one wave per free key frame: r_a = sum over its edges of (W_a D^-1) b_l
-//   k_big_assemble       M = Hpp + lambda I - S (lower triangle), rhs = bp - r
+//   k_big_assemble       M = diagonal blocks of Hpp + HppO + lambda I - S (lower triangle), rhs = bp - r
 //   k_big_panel          one workgroup: right-looking LDL^T of a 48x48 diagonal block in LDS, then the panel below it
 //   k_big_update         trailing update M22 -= L21 D L21^T, one 48x48 tile per workgroup, lower triangle only
 //   k_big_solve          one workgroup: blocked forward / diagonal / backward substitution, vector in LDS; the triangular
@@ -15,9 +17,13 @@
 
 constexpr int BIG_NB = 48;  // panel width (8 key frames)
 
-__global__ __launch_bounds__(256) void k_ba_dinv(BADev D, LinBuf B, double lambda, double *Dinv) {
+__device__ __forceinline__ bool big_idle(const BACtl *c) { return c->phase == 2 || c->needInit; }  // no trial in this slot
+
+__global__ __launch_bounds__(256) void k_ba_dinv(BADev D, Lb2 lb, const BACtl *c, double *Dinv) {
   const int l = blockIdx.x * 256 + threadIdx.x;
-  if (l >= D.npt) return;
+  if (big_idle(c) || l >= D.npt) return;
+  const LinBuf &B = lb.b[c->cur];
+  const double lambda = c->lambda;
   double M[9];
 #pragma unroll
   for (int i = 0; i < 9; i++) M[i] = B.Hll[(size_t)9 * l + i];
@@ -38,9 +44,10 @@ struct BigLists {  // device CSR: block -> (row edge, column edge) pairs, row bl
   const int *ent_er, *ent_ec;
 };
 
-__global__ __launch_bounds__(256) void k_ba_schur_gather(BADev D, LinBuf B, const double *Dinv, BigLists Lst, double *S, int P6) {
+__global__ __launch_bounds__(256) void k_ba_schur_gather(BADev D, Lb2 lb, const BACtl *c, const double *Dinv, BigLists Lst, double *S, int P6) {
   const int blk = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (blk >= Lst.nBlocks) return;
+  if (big_idle(c) || blk >= Lst.nBlocks) return;
+  const LinBuf &B = lb.b[c->cur];
   double acc[36];
 #pragma unroll
   for (int i = 0; i < 36; i++) acc[i] = 0;
@@ -73,9 +80,10 @@ __global__ __launch_bounds__(256) void k_ba_schur_gather(BADev D, LinBuf B, cons
   }
 }
 
-__global__ __launch_bounds__(256) void k_ba_rhs_gather(BADev D, LinBuf B, const double *Dinv, double *r) {
+__global__ __launch_bounds__(256) void k_ba_rhs_gather(BADev D, Lb2 lb, const BACtl *c, const double *Dinv, double *r) {
   const int k = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (k >= D.np) return;
+  if (big_idle(c) || k >= D.np) return;
+  const LinBuf &B = lb.b[c->cur];
   double acc[6] = {0, 0, 0, 0, 0, 0};
   for (int c = D.ps_start[k] + lane; c < D.ps_start[k + 1]; c += 64) {
     const int e = D.ps_edges[c];
@@ -95,16 +103,21 @@ __global__ __launch_bounds__(256) void k_ba_rhs_gather(BADev D, LinBuf B, const 
     for (int i = 0; i < 6; i++) r[6 * k + i] = acc[i];
 }
 
-// M (lower triangle, row-major, ld = P6) = Hpp + lambda I - S ; rhs = bp - r.  S and Hpp hold the UPPER triangle.
-__global__ void k_big_assemble(LinBuf B, double lambda, const double *S, const double *r, double *M, double *rhs, int P6,
-                               double *okFlag) {
+// M (lower triangle, row-major, ld = P6) = Hpp + lambda I - S ; rhs = bp - r, formed as solve_lookahead forms them: the
+// dense Hpp is not materialised, B.Hpp holds the key frames' diagonal blocks and HppO (exchange block of the accepted
+// linearisation) the pose-pose blocks.  S, Hpp and HppO are read in their UPPER triangle.
+__global__ void k_big_assemble(Lb2 lb, const BACtl *c, XBLay xb, const double *S, const double *r, double *M, double *rhs, int P6, double *okFlag) {
+  if (big_idle(c)) return;
+  const LinBuf &B = lb.b[c->cur];
+  const double *HppO = xb.at(c->cur) + xb.oH;
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx < (long long)P6 * P6) {
     const int i = (int)(idx / P6), j = (int)(idx % P6);
     if (j <= i) {
-      double h = B.Hpp[(size_t)j * P6 + i];
-      if (i == j) h += lambda;
-      M[(size_t)i * P6 + j] = h - S[(size_t)j * P6 + i];
+      double h = HppO[(size_t)j * P6 + i] - S[(size_t)j * P6 + i];
+      if (i / 6 == j / 6) h += B.Hpp[(size_t)j * P6 + i];  // same key frame: the diagonal block
+      if (i == j) h += c->lambda;
+      M[(size_t)i * P6 + j] = h;
     }
   }
   if (idx < P6) rhs[idx] = B.bp[idx] - r[idx];
@@ -113,10 +126,11 @@ __global__ void k_big_assemble(LinBuf B, double lambda, const double *S, const d
 
 // LDL^T of the diagonal block [k0, k0+kw) and the panel below it.  On exit M holds unit-lower L (below the diagonal) and
 // D (on it) in these columns; U[row][c] = L[row][k0+c] * d_c for the trailing update.
-__global__ __launch_bounds__(256) void k_big_panel(double *M, int P6, int k0, int kw, double *U, double *okFlag) {
+__global__ __launch_bounds__(256) void k_big_panel(const BACtl *c, double *M, int P6, int k0, int kw, double *U, double *okFlag) {
   __shared__ double Ld[BIG_NB][BIG_NB + 1];
   __shared__ double dd[BIG_NB];
   __shared__ int s_neg;
+  if (big_idle(c)) return;
   const int tid = threadIdx.x;
   if (tid == 0) s_neg = 0;
   for (int i = tid; i < kw * kw; i += 256) {
@@ -127,7 +141,7 @@ __global__ __launch_bounds__(256) void k_big_panel(double *M, int P6, int k0, in
   for (int c = 0; c < kw; c++) {  // right-looking: column c is final when its turn comes
     const double dc = Ld[c][c];
     const double inv = dc != 0 ? 1.0 / dc : 0.0;
-    if (tid == 0) { dd[c] = dc; if (dc == 0) s_neg = 1; }  // SimplicialLDLT rule (see solve_body)
+    if (tid == 0) { dd[c] = dc; if (dc == 0) s_neg = 1; }  // SimplicialLDLT rule (see solve_lookahead)
     const int m = kw - c - 1;  // trailing size
     for (int rr = tid >> 4; rr < m; rr += 16) {
       const double lr = Ld[c + 1 + rr][c] * inv;
@@ -165,8 +179,9 @@ __global__ __launch_bounds__(256) void k_big_panel(double *M, int P6, int k0, in
 }
 
 // trailing update of the lower triangle: tile (bi, bj), bj <= bi, of the rows >= k0 + kw
-__global__ __launch_bounds__(256) void k_big_update(double *M, int P6, int k0, int kw, const double *U) {
+__global__ __launch_bounds__(256) void k_big_update(const BACtl *c, double *M, int P6, int k0, int kw, const double *U) {
   __shared__ double Lt[BIG_NB][BIG_NB + 1], Ut[BIG_NB][BIG_NB + 1];
+  if (big_idle(c)) return;
   const int t0 = k0 + kw;
   const int nb = (P6 - t0 + BIG_NB - 1) / BIG_NB;
   int bi = 0, rem = blockIdx.x;  // blockIdx.x enumerates (bi, bj <= bi)
@@ -193,8 +208,9 @@ __global__ __launch_bounds__(256) void k_big_update(double *M, int P6, int k0, i
 }
 
 // L y = b, z = D^-1 y, L^T x = z.  One workgroup, the vector in LDS (P6 <= 4096).
-__global__ __launch_bounds__(256) void k_big_solve(const double *M, const double *rhs, int P6, double *xp) {
+__global__ __launch_bounds__(256) void k_big_solve(const BACtl *c, const double *M, const double *rhs, int P6, double *xp) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  if (big_idle(c)) return;
   double *y = reinterpret_cast<double *>(smem);   // [P6]
   __shared__ double Lp[BIG_NB][BIG_NB + 1];       // diagonal block of the current panel
   const int tid = threadIdx.x, lane = tid & 63;
@@ -305,32 +321,28 @@ int big_prepare(BigSys &B, int np, int npt, int P6, const int *poseIdx, const in
   return FB_OK;
 }
 
-// Schur complement + solve of one trial at `lambda` from the linearisation `lin`: the pose increment lands in xp, the
-// LDL^T status in *okFlag.  Sharded: the reduced system is summed over the ranks through the host (exchange step 1).
-int big_schur_solve(const BigSys &B, const BADev &D, const LinBuf &lin, double lambda, int P6, double *Dinv, double *xp, double *okFlag,
-                    const Xchg &X, hipStream_t s0) {
+// The Schur complement + solve part of a slot (the HBM-resident twin of k_ba_schur_c / k_ba_sumparts_c / k_ba_solve_c): at
+// the accepted linearisation and lambda of BACtl, the pose increment lands in xp, the LDL^T status in *okFlag.  Sharded: the
+// reduced system S | r is summed over the ranks on the stream (exchange 1).
+int big_slot_solve(const BigSys &B, const BADev &D, const Lb2 &lb, const BACtl *ctl, const XBLay &xr, int P6, double *Dinv, double *xp, double *okFlag,
+                   const Xchg &X, std::vector<double> &hostScratch, hipStream_t s0) {
   double *S = B.S.as<double>(), *rS = S + (size_t)P6 * P6, *M = B.M.as<double>(), *rhs = M + (size_t)P6 * P6;
+  const size_t nS = (size_t)P6 * P6 + P6;
   { fb::ProfScope pr(fb::P_BA_SCHUR, s0);
-    FB_HIP(hipMemsetAsync(S, 0, (size_t)P6 * P6 * 8 + (size_t)P6 * 8, s0));  // blocks without a shared landmark stay 0
-    if (D.npt > 0) k_ba_dinv<<<(D.npt + 255) / 256, 256, 0, s0>>>(D, lin, lambda, Dinv);
-    if (B.lists.nBlocks > 0) k_ba_schur_gather<<<(B.lists.nBlocks + 3) / 4, 256, 0, s0>>>(D, lin, Dinv, B.lists, S, P6);
-    if (D.np > 0) k_ba_rhs_gather<<<(D.np + 3) / 4, 256, 0, s0>>>(D, lin, Dinv, rS); }
+    FB_HIP(hipMemsetAsync(S, 0, nS * 8, s0));  // blocks without a shared landmark stay 0
+    if (D.npt > 0) k_ba_dinv<<<(D.npt + 255) / 256, 256, 0, s0>>>(D, lb, ctl, Dinv);
+    if (B.lists.nBlocks > 0) k_ba_schur_gather<<<(B.lists.nBlocks + 3) / 4, 256, 0, s0>>>(D, lb, ctl, Dinv, B.lists, S, P6);
+    if (D.np > 0) k_ba_rhs_gather<<<(D.np + 3) / 4, 256, 0, s0>>>(D, lb, ctl, Dinv, rS); }
   fb::ProfScope pr(fb::P_BA_SOLVE, s0);
-  if (X.active()) {
-    std::vector<double> ex((size_t)P6 * P6 + P6);
-    FB_HIP(hipMemcpy(ex.data(), S, ex.size() * 8, hipMemcpyDeviceToHost));
-    FB_TRY(X.reduce_host(ex.data(), (int)ex.size(), 0));
-    FB_HIP(hipMemcpy(S, ex.data(), ex.size() * 8, hipMemcpyHostToDevice));
-  }
-  const long long nel = (long long)P6 * P6;
-  k_big_assemble<<<(unsigned)((nel + 255) / 256), 256, 0, s0>>>(lin, lambda, S, rS, M, rhs, P6, okFlag);
+  FB_TRY(X.sum_dev(S, nS, s0, hostScratch));
+  k_big_assemble<<<(unsigned)(((long long)P6 * P6 + 255) / 256), 256, 0, s0>>>(lb, ctl, xr, S, rS, M, rhs, P6, okFlag);
   for (int k0 = 0; k0 < P6; k0 += BIG_NB) {
     const int kw = std::min(BIG_NB, P6 - k0);
-    k_big_panel<<<1, 256, 0, s0>>>(M, P6, k0, kw, B.U.as<double>(), okFlag);
+    k_big_panel<<<1, 256, 0, s0>>>(ctl, M, P6, k0, kw, B.U.as<double>(), okFlag);
     const int nbt = (P6 - k0 - kw + BIG_NB - 1) / BIG_NB;
-    if (nbt > 0) k_big_update<<<nbt * (nbt + 1) / 2, 256, 0, s0>>>(M, P6, k0, kw, B.U.as<double>());
+    if (nbt > 0) k_big_update<<<nbt * (nbt + 1) / 2, 256, 0, s0>>>(ctl, M, P6, k0, kw, B.U.as<double>());
   }
-  k_big_solve<<<1, 256, (size_t)P6 * 8, s0>>>(M, rhs, P6, xp);
+  k_big_solve<<<1, 256, (size_t)P6 * 8, s0>>>(ctl, M, rhs, P6, xp);
   return FB_OK;
 }
 }  // namespace

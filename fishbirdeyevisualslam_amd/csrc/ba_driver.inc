@@ -1,6 +1,6 @@
 // ba_driver.inc -- the host driver of every bundle adjustment entry point (included by ba.hip).  local_ba_impl is the table of
-// contents: agreement -> plan -> stage/build -> bind -> one of the two Levenberg-Marquardt drivers -> results.  Everything a
-// call owns sits in one BACtx; the stages are free functions over it.
+// contents: agreement -> plan -> stage/build -> bind -> the device-resident Levenberg-Marquardt schedule -> results.
+// Everything a call owns sits in one BACtx; the stages are free functions over it.
 // optimisation schedule: LocalBundleAdjustment[WithOdom] = optimize(5) robust, chi2 gate, optimize(10) plain
 // (Optimizer.cc:2504-2560); BundleAdjustmentWithOdom = ONE optimize(nIterations), robust iff bRobust, no gate (:2048-2050)
 struct BASchedule {
@@ -24,13 +24,13 @@ struct BAPlan {
   bool sharded, devIn;
   int rank, world;
   int P6, NT, rows;
-  int nLinBlocks, nUpdBlocks;  // k_ba_linearize: a lane per landmark; k_ba_update: four lanes per landmark + one per key frame
-  int nWg, lmPerWg;            // k_ba_schur: workgroups and landmarks of each (a multiple of CHUNK)
+  int nLinBlocks, nUpdBlocks;  // LIN_THREADS landmarks each (sizes the chi2 / max partials); k_ba_update_c: four lanes per landmark + one per key frame
+  int nWg, lmPerWg;            // k_ba_schur_c: workgroups and landmarks of each (a multiple of CHUNK)
   size_t schurLds, solveLds;
   bool big;       // beyond ~23 free key frames the reduced system no longer fits LDS: HBM-resident path of ba_big.inc
   bool anything;  // (sharded: nE is this rank's view; every rank holds all edges, so this agrees across the ranks)
-  bool timing, trace, hostLm;  // FB_BA_TIMING (host-side phase times on stderr), FB_BA_TRACE, FB_BA_HOST_LM
-  bool device_lm() const { return !big && (devIn || (!trace && !hostLm)); }
+  bool timing, trace;  // FB_BA_TIMING (host-side phase times on stderr), FB_BA_TRACE (one line per slot; implies paced)
+  bool paced;          // FB_BA_HOST_LM: one slot per batch, the control block read back after each
 };
 
 int plan(const fb_local_ba_args *A, int rank, const Xchg &X, bool devIn, BAPlan &P) {
@@ -48,13 +48,13 @@ int plan(const fb_local_ba_args *A, int rank, const Xchg &X, bool devIn, BAPlan 
   P.lmPerWg = ((d.npt + P.nWg - 1) / P.nWg + CHUNK - 1) / CHUNK * CHUNK;
   P.nWg = std::max(1, (d.npt + P.lmPerWg - 1) / std::max(P.lmPerWg, 1));
   P.schurLds = (size_t)2 * P.rows * KPAD * 8;
-  P.solveLds = ((size_t)(P.P6 + 1) * (P.P6 + 1) + (size_t)(P.P6 + 1) * 6 + 96 + P.P6 + 2) * 8;  // the larger of k_ba_solve / solve_lookahead
+  P.solveLds = ((size_t)(P.P6 + 1) * (P.P6 + 1) + (size_t)(P.P6 + 1) * 6 + 96 + P.P6 + 2) * 8;  // solve_lookahead
   P.big = P.schurLds > 160 * 1024 || P.solveLds > 160 * 1024 || P.P6 + 1 > 256;
   if (devIn && P.big) { fb::set_error("fb_local_ba_dev: more than 23 free key frames (use fb_local_ba)"); return FB_ERR_CAPACITY; }
   P.anything = d.nE + (d.odom ? A->n_odom : 0) > 0 && (d.np > 0 || d.npt > 0);
   P.timing = getenv("FB_BA_TIMING") != nullptr;
   P.trace = getenv("FB_BA_TRACE") != nullptr;
-  P.hostLm = getenv("FB_BA_HOST_LM") != nullptr;
+  P.paced = P.trace || getenv("FB_BA_HOST_LM") != nullptr;
   return FB_OK;
 }
 
@@ -92,8 +92,6 @@ struct StreamDrain {
   }
 };
 
-using SchurFn = void (*)(BADev, LinBuf, double, double *, double *, int, int, int);
-
 struct BACtx {  // one call
   const fb_local_ba_args *A;
   const Xchg &X;
@@ -104,9 +102,9 @@ struct BACtx {  // one call
   GraphLayout G;
   uint8_t *hs = nullptr;  // host copy of the staged graph (device input: only its header is filled)
   // device blocks; they return to the pool when the context goes
-  fb::DevBuf d_stage, d_bld, d_scratch, d_Dinv, d_Spart, d_xp, d_ok, d_scale, d_scal, d_ol;
+  fb::DevBuf d_stage, d_bld, d_scratch, d_Dinv, d_Spart, d_xp, d_ok, d_scale, d_ol;
   BigSys bigSys;
-  fb::DevBuf d_xb, d_olDev, d_ex;        // device-resident schedule
+  fb::DevBuf d_xb, d_olDev, d_ex;        // exchange blocks, odometry records, sharded result
   fb::DevBuf d_flags, d_kfT, d_ptOut;    // results
   BADev D;
   State st[2];
@@ -115,7 +113,6 @@ struct BACtx {  // one call
   const float *d_kfT0 = nullptr;
   BACtl *ctl = nullptr;
   int *d_abort = nullptr;
-  SchurFn schurKernel = nullptr;
   OdomLin *olGlobal = nullptr;  // long odometry chains: per-edge linearisations in HBM
   size_t odomLds = 0;
   StreamDrain drain;  // LAST member: destroyed first, before any block above is given back
@@ -197,24 +194,12 @@ int alloc_solver(BACtx &c) {
     const GraphLayout &G = c.G;
     FB_TRY(big_prepare(c.bigSys, d.np, d.npt, P6, G.poseIdx.at(c.hs), G.e_kf.at(c.hs), G.lm_start.at(c.hs), G.lm_edges.at(c.hs)));
   }
-  FB_TRY(c.d_xp.alloc((size_t)std::max(P6, 1) * 8)); FB_TRY(c.d_ok.alloc(4)); FB_TRY(c.d_scale.alloc((size_t)P.nUpdBlocks * 8));
-  FB_TRY(c.d_scal.alloc(4 * 8));
-  FB_HIP(hipMemsetAsync(c.d_scal.p, 0, 4 * 8, c.s0));
-  // accumulator tiles per wave: NT<=8 -> 9, NT<=12 -> 20, NT<=16 -> 34
-  c.schurKernel = P.NT <= 8 ? k_ba_schur<9> : (P.NT <= 12 ? k_ba_schur<20> : k_ba_schur<34>);
-  if (!P.big) {
-    FB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(c.schurKernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.schurLds));
-    FB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_ba_solve), hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.solveLds));
-  } else {
-    FB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_big_solve), hipFuncAttributeMaxDynamicSharedMemorySize, P6 * 8));
-  }
+  FB_TRY(c.d_xp.alloc((size_t)std::max(P6, 1) * 8)); FB_TRY(c.d_ok.alloc(8)); FB_TRY(c.d_scale.alloc((size_t)P.nUpdBlocks * 8));
   c.odomLds = (size_t)std::max(d.nO, 1) * sizeof(OdomLin);
   if (c.odomLds > 150 * 1024) {  // long odometry chains: per-edge linearisations in HBM
     FB_TRY(c.d_ol.alloc(c.odomLds));
     c.olGlobal = c.d_ol.as<OdomLin>();
     c.odomLds = 0;
-  } else {
-    FB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_ba_odom<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.odomLds));
   }
   return FB_OK;
 }
@@ -256,9 +241,9 @@ int results_to_device(BACtx &c) {
   return FB_OK;
 }
 
-// ---- device-resident Levenberg-Marquardt (LDS-resident reduced system): no read-back inside the schedule.  Sharded: two
-//      all-reduces per slot on this stream (the Schur-reduced system; the exchange block of the linearisation), every rank
-//      enqueues the same slots and takes the same decisions from the reduced values.
+// ---- device-resident Levenberg-Marquardt: no read-back inside a batch of slots.  Sharded: two all-reduces per slot on this
+//      stream (the Schur-reduced system; the exchange block of the linearisation), every rank enqueues the same slots and
+//      takes the same decisions from the reduced values.
 struct DevLm {
   PerDev *pd = nullptr;
   BASched sched;
@@ -293,17 +278,23 @@ int dev_lm_prepare(BACtx &c, DevLm &L) {
   L.sched = {c.sc.its1, c.sc.robust1, c.sc.gate ? 1 : 0, c.sc.its2};
   L.st2.s[0] = c.st[0]; L.st2.s[1] = c.st[1];
   L.lb2.b[0] = c.lb[0]; L.lb2.b[1] = c.lb[1];
-  L.schurC = P.NT <= 8 ? k_ba_schur_c<9> : (P.NT <= 12 ? k_ba_schur_c<20> : k_ba_schur_c<34>);
-  FB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(L.schurC), hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.schurLds));
-  FB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_ba_solve_c), hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.solveLds));
   L.nS = P.rows * P.rows;
-  FB_HIP(hipMemsetAsync(c.d_Spart.p, 0, (size_t)L.nS * 8, s0));  // the lower tiles of the summed system are never written: keep them finite
+  if (P.big) {
+    FB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_big_solve), hipFuncAttributeMaxDynamicSharedMemorySize, P.P6 * 8));
+  } else {
+    // accumulator tiles per wave: NT<=8 -> 9, NT<=12 -> 20, NT<=16 -> 34
+    L.schurC = P.NT <= 8 ? k_ba_schur_c<9> : (P.NT <= 12 ? k_ba_schur_c<20> : k_ba_schur_c<34>);
+    FB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(L.schurC), hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.schurLds));
+    FB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_ba_solve_c), hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.solveLds));
+    FB_HIP(hipMemsetAsync(c.d_Spart.p, 0, (size_t)L.nS * 8, s0));  // the lower tiles of the summed system are never written: keep them finite
+  }
   L.nLin256 = (4 * d.npt + 255) / 256;
   XBLay &xb = L.xb;
   xb.oH = d.np * POSE_PARTS * 27; xb.oB = xb.oH + P.P6 * P.P6; xb.oS = xb.oB + P.P6; xb.oM = xb.oS + 4; xb.stride = xb.oM + P.world;
   // sharded: the kernels of a linearisation fill the RAW blocks; exchange 2 sums BOTH raw blocks into the REDUCED ones out of
   // place (which of the two the slot wrote is device-side knowledge; the raw block of the accepted linearisation is not
-  // touched until it is overwritten, so re-reducing it is idempotent); k_ba_control and k_ba_solve read the reduced blocks
+  // touched until it is overwritten, so re-reducing it is idempotent); k_ba_control and the solve read the reduced blocks.
+  // The blocks start cleared: the odometry role relies on it for HppO
   FB_TRY(c.d_xb.alloc((size_t)(P.sharded ? 4 : 2) * xb.stride * 8));
   FB_HIP(hipMemsetAsync(c.d_xb.p, 0, (size_t)(P.sharded ? 4 : 2) * xb.stride * 8, s0));
   xb.base = c.d_xb.as<double>();
@@ -334,15 +325,19 @@ void dev_lm_slot(BACtx &c, DevLm &L) {
   const BADev &D = c.D;
   hipStream_t s0 = c.s0;
   double *Dinv = c.d_Dinv.as<double>(), *Spart = c.d_Spart.as<double>(), *xp = c.d_xp.as<double>(), *scale = c.d_scale.as<double>(),
-         *okFlag = c.d_scal.as<double>() + 3;
+         *okFlag = c.d_ok.as<double>();
   BACtl *ctl = c.ctl;
   const int nLin256 = L.nLin256;
-  { fb::ProfScope pr(fb::P_BA_SCHUR, s0);
-    L.schurC<<<P.nWg, SCHUR_THREADS, P.schurLds, s0>>>(D, L.lb2, ctl, Dinv, Spart, P.P6, P.NT, P.lmPerWg); }
-  { fb::ProfScope pr(fb::P_BA_SOLVE, s0);
+  if (P.big) {
+    L.rcSlot = big_slot_solve(c.bigSys, D, L.lb2, ctl, L.xr, P.P6, Dinv, xp, okFlag, c.X, L.hostScratch, s0);
+  } else {
+    { fb::ProfScope pr(fb::P_BA_SCHUR, s0);
+      L.schurC<<<P.nWg, SCHUR_THREADS, P.schurLds, s0>>>(D, L.lb2, ctl, Dinv, Spart, P.P6, P.NT, P.lmPerWg); }
+    fb::ProfScope pr(fb::P_BA_SOLVE, s0);
     k_ba_sumparts_c<<<(L.nS + SUMPARTS_ELEMS - 1) / SUMPARTS_ELEMS, 256, 0, s0>>>(ctl, Spart, P.nWg, L.nS, P.rows);
     if (P.sharded) L.rcSlot = c.X.sum_dev(Spart, (size_t)L.nS, s0, L.hostScratch);  // exchange 1: the Schur-reduced system
-    k_ba_solve_c<<<1, SOLVE_C_THREADS, P.solveLds, s0>>>(L.lb2, ctl, Spart, P.P6, P.NT, xp, okFlag, L.xr); }
+    k_ba_solve_c<<<1, SOLVE_C_THREADS, P.solveLds, s0>>>(L.lb2, ctl, Spart, P.P6, P.NT, xp, okFlag, L.xr);
+  }
   { fb::ProfScope pr(fb::P_BA_UPDATE, s0);
     k_ba_update_c<<<P.nUpdBlocks, LIN_THREADS, 0, s0>>>(D, L.lb2, L.st2, ctl, Dinv, xp, scale, P.rank == 0 ? 1 : 0); }
   { fb::ProfScope pr(fb::P_BA_LINEARIZE, s0);
@@ -404,23 +399,38 @@ int dev_lm_wait(BACtx &c, DevLm &L, bool &abortSent) {
   }
 }
 
+// FB_BA_TRACE: the slot that took the control block from `was` to `now`, in the format of the oracle's trace (se3_oracle.h)
+void trace_slot(const BACtl &was, const BACtl &now, const BASchedule &sc) {
+  if (was.phase == 2 || now.badArgs) return;  // the slot did nothing
+  if (was.needInit) fprintf(stderr, "[hip] optimize(%d) chi0=%.17g maxDiag=%.17g\n", was.phase == 0 ? sc.its1 : sc.its2, now.trChi, now.trScale);
+  else fprintf(stderr, "[hip]  it=%d q=%d lambda=%.17g tempChi=%.17g scale=%.17g rho=%.17g ok=%d\n", was.it, was.qmax, was.lambda, now.trChi, now.trScale,
+               now.trRho, now.trChi != 1.7976931348623157e308 ? 1 : 0);
+}
+
 int run_device_lm(BACtx &c) {
   const BASchedule &sc = c.sc;
   DevLm L;
   FB_TRY(dev_lm_prepare(c, L));
   bool abortSent = false;
-  // a typical schedule takes one trial per iteration: its1 + its2 trials + the two opening linearisations
+  // a typical schedule takes one trial per iteration: its1 + its2 trials + the two opening linearisations; the longest one
+  // ten trials per iteration.  Paced (FB_BA_HOST_LM, FB_BA_TRACE): the host looks at the control block after every slot
   int batch = c.P.anything ? sc.its1 + (sc.gate ? sc.its2 + 1 : 0) + 1 + 2 : 0;
+  if (c.P.paced) batch = std::min(batch, 1);
+  const int maxSlots = 2 + 10 * (sc.its1 + (sc.gate ? sc.its2 : 0));
   c.lap("buffers ready");
   const BACtl *hCtl = L.pd->hCtl;
-  for (int round = 0; round < 64; round++) {
+  BACtl was = *c.G.ctl.at(c.hs);
+  for (int enqueued = 0;;) {
     for (int i = 0; i < batch; i++) dev_lm_slot(c, L);
+    enqueued += batch;
     FB_TRY(L.rcSlot);
     c.lap("slots enqueued");
     FB_TRY(dev_lm_export(c, L));
     FB_TRY(dev_lm_wait(c, L, abortSent));
-    if (hCtl->phase == 2) break;
-    batch = 6;
+    if (c.P.trace) trace_slot(was, *hCtl, sc);
+    was = *hCtl;
+    if (hCtl->phase == 2 || enqueued >= maxSlots) break;
+    batch = c.P.paced ? 1 : 6;
   }
   c.drain.done();  // the event was the last thing on the stream
   c.lap("schedule finished");
@@ -443,173 +453,6 @@ int run_device_lm(BACtx &c) {
   return FB_OK;
 }
 
-// ---- host-driven Levenberg-Marquardt: SparseOptimizer::optimize + OptimizationAlgorithmLevenberg::solve on the host, a few
-//      scalars read back per trial.  The path of the HBM-resident system, of FB_BA_TRACE and of FB_BA_HOST_LM.
-struct HostLm {
-  int cur = 0;           // index of the accepted state / its linearisation
-  double lastScale = 0;  // sum x (lambda x + b) of the most recent k_ba_update (all ranks)
-  bool lastOk = true;    // LDL^T status of the most recent solve
-};
-bool stopped(const BACtx &c) {  // sharded: no rank leaves on its own view of the flag
-  double v = (c.A->stop_flag && *c.A->stop_flag) ? 1.0 : 0.0;
-  if (c.P.sharded && c.X.reduce_host(&v, 1, 1) != FB_OK) return true;
-  return v > 0.0;
-}
-
-// one linearisation at state `si` into buffer `bi`; returns chi2 (and max diagonal when wanted)
-int host_linearize(BACtx &c, HostLm &h, int si, int bi, int robust, bool wantDiag, double *chi, double *maxDiag) {
-  const BAPlan &P = c.P;
-  const int P6 = P.P6, npt = P.d.npt, np = P.d.np, nLinBlocks = P.nLinBlocks;
-  const BADev &D = c.D;
-  const LinBuf &B = c.lb[bi];
-  hipStream_t s0 = c.s0;
-  if (P6 > 0) FB_HIP(hipMemsetAsync(B.Hpp, 0, (size_t)P6 * P6 * 8, s0));
-  { fb::ProfScope pr(fb::P_BA_LINEARIZE, s0);
-    if (nLinBlocks > 0) k_ba_linearize<<<nLinBlocks, LIN_THREADS, 0, s0>>>(D, c.st[si], B, robust);
-    if (np > 0) k_ba_pose<<<np, POSE_THREADS, 0, s0>>>(D, c.st[si], B, robust, P6);
-    if (c.olGlobal) k_ba_odom<true><<<1, 256, 0, s0>>>(D, c.st[si], B, P6, nLinBlocks, c.olGlobal);
-    else k_ba_odom<false><<<1, 256, c.odomLds, s0>>>(D, c.st[si], B, P6, nLinBlocks, nullptr); }
-  { fb::ProfScope pr(fb::P_BA_MISC, s0);
-    k_ba_scalars<<<1, 256, 0, s0>>>(B.chiPart, nLinBlocks + 1, B.Hpp, P6, B.Hll, npt, c.d_scal.as<double>(), wantDiag ? 1 : 0); }
-  double v[4];
-  FB_HIP(hipMemcpy(v, c.d_scal.p, 32, hipMemcpyDeviceToHost));  // chi2, max diagonal, scale term + solver status of the last trial
-  h.lastOk = v[3] != 0.0;
-  if (P.sharded) {  // exchange step 2: [Hpp, bp, chi2, scale]
-    std::vector<double> ex((size_t)P6 * P6 + P6 + 2);
-    if (P6 > 0) {
-      FB_HIP(hipMemcpy(ex.data(), B.Hpp, (size_t)P6 * P6 * 8, hipMemcpyDeviceToHost));
-      FB_HIP(hipMemcpy(ex.data() + (size_t)P6 * P6, B.bp, (size_t)P6 * 8, hipMemcpyDeviceToHost));
-    }
-    ex[(size_t)P6 * P6 + P6] = v[0];
-    ex[(size_t)P6 * P6 + P6 + 1] = v[2];
-    FB_TRY(c.X.reduce_host(ex.data(), (int)ex.size(), 0));
-    if (P6 > 0) {
-      FB_HIP(hipMemcpy(B.Hpp, ex.data(), (size_t)P6 * P6 * 8, hipMemcpyHostToDevice));
-      FB_HIP(hipMemcpy(B.bp, ex.data() + (size_t)P6 * P6, (size_t)P6 * 8, hipMemcpyHostToDevice));
-    }
-    v[0] = ex[(size_t)P6 * P6 + P6];
-    v[2] = ex[(size_t)P6 * P6 + P6 + 1];
-    if (wantDiag) {  // the pose diagonals add up over the ranks: take the maximum on the REDUCED Hpp
-      double hp = 0;
-      for (int i = 0; i < P6; i++) hp = std::max(hp, std::fabs(ex[(size_t)i * P6 + i]));
-      k_ba_scalars<<<1, 256, 0, s0>>>(B.chiPart, 0, nullptr, 0, B.Hll, npt, c.d_scal.as<double>(), 1);
-      double hl[2];
-      FB_HIP(hipMemcpy(hl, c.d_scal.p, 16, hipMemcpyDeviceToHost));
-      v[1] = std::max(hp, hl[1]);
-      FB_TRY(c.X.reduce_host(&v[1], 1, 1));
-    }
-  }
-  *chi = v[0];
-  if (wantDiag) *maxDiag = v[1];
-  h.lastScale = v[2];
-  return FB_OK;
-}
-
-// Schur complement + solve of one trial with the LDS-resident kernels (the HBM-resident twin is big_schur_solve)
-int lds_schur_solve(BACtx &c, const LinBuf &lin, double lambda) {
-  const BAPlan &P = c.P;
-  hipStream_t s0 = c.s0;
-  { fb::ProfScope pr(fb::P_BA_SCHUR, s0);
-    c.schurKernel<<<P.nWg, SCHUR_THREADS, P.schurLds, s0>>>(c.D, lin, lambda, c.d_Dinv.as<double>(), c.d_Spart.as<double>(), P.P6, P.NT, P.lmPerWg); }
-  fb::ProfScope pr(fb::P_BA_SOLVE, s0);
-  // the workgroup partials are summed by a full-width kernel (one workgroup reading nWg x rows^2 doubles is slow)
-  const int nS = P.rows * P.rows;
-  k_ba_sumparts<<<(nS + SUMPARTS_ELEMS - 1) / SUMPARTS_ELEMS, 256, 0, s0>>>(c.d_Spart.as<double>(), P.nWg, nS);
-  const int nParts = 1;
-  if (P.sharded) {  // exchange step 1: the Schur-reduced system
-    std::vector<double> ex(nS);
-    FB_HIP(hipMemcpy(ex.data(), c.d_Spart.p, (size_t)nS * 8, hipMemcpyDeviceToHost));
-    FB_TRY(c.X.reduce_host(ex.data(), nS, 0));
-    FB_HIP(hipMemcpy(c.d_Spart.p, ex.data(), (size_t)nS * 8, hipMemcpyHostToDevice));
-  }
-  k_ba_solve<<<1, SOLVE_THREADS, P.solveLds, s0>>>(lin, lambda, c.d_Spart.as<double>(), nParts, P.P6, P.NT, c.d_xp.as<double>(), c.d_scal.as<double>() + 3);
-  return FB_OK;
-}
-
-int host_optimize(BACtx &c, HostLm &h, int iterations, int robust) {
-  const BAPlan &P = c.P;
-  hipStream_t s0 = c.s0;
-  double currentChi = 0, maxDiag = 0;
-  FB_TRY(host_linearize(c, h, h.cur, h.cur, robust, true, &currentChi, &maxDiag));
-  if (P.trace) fprintf(stderr, "[hip] optimize(%d) chi0=%.17g maxDiag=%.17g\n", iterations, currentChi, maxDiag);
-  double lambda = 0, ni = 2;
-  int nBad = 0;
-  for (int it = 0; it < iterations; it++) {
-    if (stopped(c)) break;  // terminate()
-    const double iniChi = currentChi;
-    if (it == 0) { lambda = 1e-5 * maxDiag; ni = 2; nBad = 0; }
-    double rho = 0;
-    int qmax = 0;
-    do {
-      const int cur = h.cur, tr = 1 - cur;
-      if (P.big) FB_TRY(big_schur_solve(c.bigSys, c.D, c.lb[cur], lambda, P.P6, c.d_Dinv.as<double>(), c.d_xp.as<double>(), c.d_scal.as<double>() + 3, c.X, s0));
-      else FB_TRY(lds_schur_solve(c, c.lb[cur], lambda));
-      { fb::ProfScope pr(fb::P_BA_UPDATE, s0);
-        k_ba_update<<<P.nUpdBlocks, LIN_THREADS, 0, s0>>>(c.D, c.lb[cur], c.st[cur], c.st[tr], c.d_Dinv.as<double>(), c.d_xp.as<double>(), lambda, c.d_scale.as<double>(), P.rank == 0 ? 1 : 0);
-        k_ba_scalars<<<1, 256, 0, s0>>>(c.d_scale.as<double>(), P.nUpdBlocks, nullptr, 0, nullptr, 0, c.d_scal.as<double>() + 2, 0); }
-      double tempChi = 0, dummy = 0;
-      FB_TRY(host_linearize(c, h, tr, tr, robust, false, &tempChi, &dummy));  // (exchange step 2 happens inside)
-      const int ok2 = h.lastOk ? 1 : 0;
-      if (!ok2) tempChi = 1.7976931348623157e308;
-      rho = currentChi - tempChi;
-      const double scale = h.lastScale + 1e-3;
-      rho /= scale;
-      if (P.trace) fprintf(stderr, "[hip]  it=%d q=%d lambda=%.17g tempChi=%.17g scale=%.17g rho=%.17g ok=%d\n", it, qmax, lambda, tempChi, scale, rho, ok2);
-      if (rho > 0 && std::isfinite(tempChi)) {
-        double alpha = 1. - pow((2 * rho - 1), 3);
-        alpha = std::min(alpha, 2. / 3.);
-        lambda *= std::max(1. / 3., alpha);
-        ni = 2;
-        currentChi = tempChi;
-        h.cur = tr;  // discardTop: the trial state and its linearisation become current
-      } else {
-        lambda *= ni;
-        ni *= 2;  // pop: keep `cur`
-      }
-      qmax++;
-    } while (rho < 0 && qmax < 10 && !stopped(c));
-    if (qmax == 10 || rho == 0) break;
-    if ((iniChi - currentChi) * 1e3 < iniChi) nBad++;
-    else nBad = 0;
-    if (nBad >= 3) break;
-  }
-  return FB_OK;
-}
-
-int run_host_lm(BACtx &c) {
-  const BAPlan &P = c.P;
-  const BADims &d = P.d;
-  const BASchedule &sc = c.sc;
-  const int nE = d.nE, npt = d.npt;
-  hipStream_t s0 = c.s0;
-  HostLm h;
-  if (nE + d.nO > 0 && (d.np > 0 || npt > 0)) FB_TRY(host_optimize(c, h, sc.its1, sc.robust1));
-  const bool more = sc.gate && !stopped(c);
-  if (more && nE > 0) {
-    k_ba_gate<<<(nE + 255) / 256, 256, 0, s0>>>(c.D, c.st[h.cur], 1, nullptr);
-    if (nE + d.nO > 0) FB_TRY(host_optimize(c, h, sc.its2, 0));
-  }
-  FB_TRY(c.d_flags.alloc(std::max(nE, 1)));
-  if (nE > 0) k_ba_gate<<<(nE + 255) / 256, 256, 0, s0>>>(c.D, c.st[h.cur], 0, c.d_flags.as<uint8_t>());
-  FB_TRY(c.d_kfT.upload(c.A->kf_Tcw, (size_t)d.n_kf * 48));
-  FB_TRY(c.d_ptOut.alloc((size_t)std::max(npt, 1) * 12));
-  k_ba_export<<<(d.n_kf + npt * 3 + 255) / 256, 256, 0, s0>>>(d.n_kf, npt, c.st[h.cur].pose, c.st[h.cur].pt, c.d_fixed, c.d_kfT.as<float>(), c.d_ptOut.as<float>());
-  FB_HIP(hipGetLastError());
-  FB_HIP(hipDeviceSynchronize());
-  c.drain.done();
-  HostResult r;
-  FB_TRY(fetch_results(c, r));
-  if (P.sharded) {  // every rank returns the complete result: owned landmarks / edges are summed with zeros
-    std::vector<double> ex((size_t)npt * 3 + nE);
-    for (int l = 0; l < npt; l++)
-      for (int k = 0; k < 3; k++) ex[(size_t)3 * l + k] = (l % P.world == P.rank) ? (double)r.po[(size_t)3 * l + k] : 0.0;
-    for (int e = 0; e < nE; e++) ex[(size_t)npt * 3 + e] = r.flags[e];
-    FB_TRY(c.X.reduce_host(ex.data(), (int)ex.size(), 0));
-    for (size_t i = 0; i < (size_t)npt * 3; i++) r.po[i] = (float)ex[i];
-    for (int e = 0; e < nE; e++) r.flags[e] = ex[(size_t)npt * 3 + e] != 0.0;
-  }
-  return results_to_host(c, r);
-}
 }  // namespace
 
 static int local_ba_impl(const fb_local_ba_args *A, int rank, const Xchg &X, const BASchedule &sc, const DevIn *dv = nullptr) {
@@ -625,7 +468,7 @@ static int local_ba_impl(const fb_local_ba_args *A, int rank, const Xchg &X, con
   FB_TRY(stage_graph(c));
   FB_TRY(bind_device(c));
   FB_TRY(alloc_solver(c));
-  return c.P.device_lm() ? run_device_lm(c) : run_host_lm(c);
+  return run_device_lm(c);
 }
 
 static const BASchedule kLocalSchedule = {5, 1, true, 10, (double)(float)sqrt(5.991)};
@@ -645,7 +488,7 @@ extern "C" int fb_global_ba(const fb_local_ba_args *A, int n_iterations, int rob
 
 // Landmark-partitioned BA (SURVEY 8e): rank r owns the landmarks l with l % world == r and all their edges, the
 // odometry edges live on rank 0, the keyframe state is replicated.  Per LM trial two small all-reduces: the
-// Schur-reduced system (after k_ba_schur) and [Hpp, bp, chi2, scale] (after the linearisation at the trial state).
+// Schur-reduced system (after k_ba_schur_c / the gathers of ba_big.inc) and the exchange block (after the linearisation at the trial state).
 extern "C" int fb_local_ba_sharded(const fb_local_ba_args *A, int rank, int world, fb_allreduce_fn allreduce, void *ctx) {
   FB_ARG(world >= 1 && rank >= 0 && rank < world && (world == 1 || allreduce));
   Xchg X;

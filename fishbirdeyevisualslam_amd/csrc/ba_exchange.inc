@@ -63,7 +63,7 @@ struct Xchg {
     FB_HIP(hipMemcpy(dbuf, scratch.data(), n * 8, hipMemcpyHostToDevice));
     return FB_OK;
   }
-  // in-place reduction of n doubles in HOST memory (op 0 = sum, 1 = max); the host-driven schedule uses it
+  // in-place reduction of n doubles in HOST memory (op 0 = sum, 1 = max): the argument agreement before anything is enqueued
   int reduce_host(double *hbuf, int n, int op) const {
     if (!active() || n <= 0) return FB_OK;
     if (cb) {

@@ -1,5 +1,5 @@
 """Bundle adjustment beyond the LDS-resident limit (> 23 free key frames): the reduced pose system lives in HBM
-(csrc/ba_big.inc: atomic block scatter of the Schur complement, blocked LDL^T over several kernels).  Same parity bar as
+(csrc/ba_big.inc: deterministic block gather of the Schur complement, blocked LDL^T over several kernels).  Same parity bar as
 tests/test_ba_gpu.py: poses / landmarks within 1e-4 relative of the oracle per element (ba_cases.pose_rel / point_rel), outlier flags identical."""
 import ctypes as C
 

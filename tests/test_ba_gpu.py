@@ -137,12 +137,28 @@ def test_local_ba_structure_only_and_no_bird():
     np.testing.assert_array_equal(out_h["obs_outlier"], out_o["obs_outlier"])
 
 
-def test_local_ba_host_driven_schedule_still_matches(monkeypatch):
-    """FB_BA_HOST_LM=1 selects the host-driven Levenberg-Marquardt loop (the path of > 23 free key frames) on a small problem."""
+def test_local_ba_host_paced_schedule_still_matches(monkeypatch):
+    """FB_BA_HOST_LM=1 runs the device-resident Levenberg-Marquardt schedule host-paced (one slot per batch, the control block
+    read back after each) on a small problem."""
     monkeypatch.setenv("FB_BA_HOST_LM", "1")
     p = synth.make_ba_problem(4006, n_kf=6, n_mp=500, n_mpb=120)
     out_o, out_h, _, _ = _run(p, with_odom=1)
     _compare(p, out_o, out_h, 1)
+
+
+def test_local_ba_28_free_key_frames_host_paced_equals_default(monkeypatch):
+    """28 free key frames (P6 = 168: three full panels of 48 and a last one 24 wide) on the HBM-resident path against the
+    oracle, and the same call host-paced (FB_BA_HOST_LM=1): byte-equal, so the kernels of ba_big.inc do nothing in the slots
+    the default take enqueues beyond the end of the schedule."""
+    p = synth.make_ba_problem(4210, n_kf=30, n_fixed=2, n_mp=300, n_mpb=60)
+    assert int((p["kf_fixed"] == 0).sum()) == 28
+    out_o, out_h, _, _ = _run(p, with_odom=1)
+    _compare(p, out_o, out_h, 1)
+    monkeypatch.setenv("FB_BA_HOST_LM", "1")
+    a, out_p, keep = ba_problem.local_ba_args(p, with_odom=1)
+    H.call("fb_local_ba", a)
+    for k in ("kf_Tcw", "mp_xw", "mpb_xw", "obs_outlier", "bobs_outlier"):
+        assert out_p[k].tobytes() == out_h[k].tobytes(), k
 
 
 def test_local_ba_stop_flag_raised_while_running():

@@ -1,6 +1,7 @@
 """GPU parity on the graphs of tests/ba_cases.py: HIP local bundle adjustment vs the CPU oracle through every path a case can
-take -- fb_local_ba (device-resident LM), fb_local_ba with FB_BA_HOST_LM=1 (host-driven LM), fb_local_ba_dev (graph built by
-kernels; byte-equal to fb_local_ba) and, with 24 free key frames, the HBM-resident path of ba_big.inc.
+take -- fb_local_ba (device-resident LM), fb_local_ba with FB_BA_HOST_LM=1 (the same schedule host-paced, one slot per batch;
+byte-equal), fb_local_ba_dev (graph built by kernels; byte-equal to fb_local_ba) and, with 24 free key frames, the HBM-resident
+path of ba_big.inc (default and host-paced; byte-equal).
 
 Asserted per path: outlier flags identical to the oracle AND to the flags the construction demands; the one-sided chi2 / depth
 gate recomputed in numpy float64 on the HIP output; poses and landmarks within 1e-4 (BASELINE.json north_star) PER ELEMENT
@@ -55,16 +56,29 @@ def _check(p, ex, out_o, out_h, label, capsys):
     assert out_h["kf_Tcw"][fx].tobytes() == np.ascontiguousarray(p["kf_Tcw"][fx], np.float32).tobytes(), label + ": fixed key frames"
 
 
+def _paced(p, ex, monkeypatch):
+    monkeypatch.setenv("FB_BA_HOST_LM", "1")
+    out = _host(p, ex)
+    monkeypatch.delenv("FB_BA_HOST_LM")
+    return out
+
+
+def _assert_same_bytes(out_a, out_b, label):
+    for k in ("kf_Tcw", "mp_xw", "mpb_xw", "obs_outlier", "bobs_outlier"):
+        assert out_a[k].tobytes() == out_b[k].tobytes(), "%s: %s differs" % (label, k)
+
+
 def _lds_paths(cid, monkeypatch, capsys):
-    """Up to 23 free key frames: device LM from host pointers, host LM, device LM from device inputs (byte-equal)."""
+    """Up to 23 free key frames: device LM from host pointers, the same host-paced (byte-equal: the default take enqueues
+    slots past the end of the schedule and the paced one does not, so equality also proves the kernels' `phase == 2` and
+    `needInit` guards), device LM from device inputs (byte-equal)."""
     p, ex, out_o, _ = BC.oracle(cid)
     name = BC.case_name(cid)
     out_h = _host(p, ex)
     _check(p, ex, out_o, out_h, name + " / fb_local_ba", capsys)
-    monkeypatch.setenv("FB_BA_HOST_LM", "1")
-    out_l = _host(p, ex)
-    monkeypatch.delenv("FB_BA_HOST_LM")
+    out_l = _paced(p, ex, monkeypatch)
     _check(p, ex, out_o, out_l, name + " / FB_BA_HOST_LM=1", capsys)
+    _assert_same_bytes(out_l, out_h, name + ": FB_BA_HOST_LM=1 against the default take")
     rc, out_d = _dev(p, ex)
     assert rc == 0
     out_d = {k: out_d[k][: len(out_h[k])] for k in out_h}   # an empty host array travels as a one-element placeholder
@@ -76,11 +90,15 @@ def _lds_paths(cid, monkeypatch, capsys):
     return p, ex, out_o, out_h
 
 
-def _big_path(cid, capsys):
-    """24 free key frames: the HBM-resident path from host pointers, FB_ERR_CAPACITY from device inputs."""
+def _big_path(cid, monkeypatch, capsys):
+    """24 free key frames (P6 = 144: three full panels of 48): the HBM-resident path from host pointers, the same host-paced
+    (byte-equal: every kernel of ba_big.inc is a no-op in a slot that only linearises and after the schedule has finished),
+    FB_ERR_CAPACITY from device inputs."""
     p, ex, out_o, _ = BC.oracle(cid)
     assert int((p["kf_fixed"] == 0).sum()) == 24
-    _check(p, ex, out_o, _host(p, ex), BC.case_name(cid) + " / fb_local_ba (HBM-resident)", capsys)
+    out_h = _host(p, ex)
+    _check(p, ex, out_o, out_h, BC.case_name(cid) + " / fb_local_ba (HBM-resident)", capsys)
+    _assert_same_bytes(_paced(p, ex, monkeypatch), out_h, BC.case_name(cid) + " (HBM-resident): FB_BA_HOST_LM=1 against the default take")
     rc, _ = _dev(p, ex)
     assert rc == cabi.FB_ERR_CAPACITY
     return p, ex, out_o
@@ -128,21 +146,21 @@ def test_landmark_seen_only_by_fixed(monkeypatch, capsys):
 
 
 @pytest.mark.parametrize("name", list(BC.STRUCTURAL))
-def test_structural_case_on_the_hbm_resident_path(name, capsys):
+def test_structural_case_on_the_hbm_resident_path(name, monkeypatch, capsys):
     """The same five graphs with 24 free key frames: pins the e_level filters of k_ba_schur_gather / k_ba_rhs_gather, the pair
     lists of big_prepare for landmarks without a free observer, and k_ba_dinv on the degenerate Hll (ba_big.inc)."""
-    _big_path(("structural", name, True), capsys)
+    _big_path(("structural", name, True), monkeypatch, capsys)
 
 
 @pytest.mark.parametrize("f", BC.FREE_COUNTS[:-1])
 def test_free_count(f, monkeypatch, capsys):
     """Every count of free key frames the LDS-resident system takes, 1...23: pins the NT = (6 f + 1 + 15) / 16 tile count and
-    the MAXT = 9 / 20 / 34 dispatch of k_ba_schur[_c] / k_ba_solve[_c], among them 2 and 5 (a tile boundary), 19-21 (NT = 8) and 22."""
+    the MAXT = 9 / 20 / 34 dispatch of k_ba_schur_c / k_ba_solve_c, among them 2 and 5 (a tile boundary), 19-21 (NT = 8) and 22."""
     _lds_paths(("free_count", f), monkeypatch, capsys)
 
 
-def test_free_count_24_takes_the_hbm_resident_path(capsys):
-    _big_path(("free_count", 24), capsys)
+def test_free_count_24_takes_the_hbm_resident_path(monkeypatch, capsys):
+    _big_path(("free_count", 24), monkeypatch, capsys)
 
 
 @pytest.mark.parametrize("n", BC.POINT_COUNTS)

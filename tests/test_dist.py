@@ -107,8 +107,8 @@ def test_sharded_local_ba_rccl_single_rank_vs_oracle():
 
 @pytest.mark.gpu
 def test_sharded_rccl_single_rank_hbm_resident_system():
-    """30 key frames: the reduced system lives in HBM and the Levenberg-Marquardt loop is host-driven; the exchanges of that
-    path go through the same transport (RCCL: staged through a device buffer)."""
+    """30 key frames: the reduced system lives in HBM; the schedule is the device-resident one and exchange 1 of that path
+    (the reduced system S | r) is an ncclAllReduce on the BA stream like the others."""
     import numpy as np
     import fishbirdeyevisualslam_amd as fb
     import oracle_lib as O

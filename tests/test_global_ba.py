@@ -41,7 +41,8 @@ def test_oracle_global_ba_reduces_the_error():
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("seed,n_kf,n_mp,n_mpb,its,robust", [(4100, 6, 500, 120, 10, 1), (4101, 12, 3000, 600, 20, 0),
-                                                             (4102, 20, 8000, 2000, 10, 1)])
+                                                             (4102, 20, 8000, 2000, 10, 1),
+                                                             (4103, 25, 400, 100, 10, 1)])   # 24 free key frames: HBM-resident system
 def test_gpu_global_ba_matches_oracle(seed, n_kf, n_mp, n_mpb, its, robust):
     import fishbirdeyevisualslam_amd as fb
     p = _problem(seed, n_kf, n_mp, n_mpb)
