@@ -292,6 +292,26 @@ class PropagateGbaArgs(C.Structure):
                 ("mpb_ref_kf", _vp), ("d_reached", _vp)]
 
 
+FB_REFRESH_NORMAL_DEPTH, FB_REFRESH_DESCRIPTOR, FB_REFRESH_STAGE = 1, 2, 128
+
+
+class PointRefreshArgs(C.Structure):
+    _fields_ = [("d_list", _vp), ("d_n_list", _vp), ("n_list", _i32), ("what", _i32), ("reuse_index", _i32), ("n_levels", _i32),
+                ("kf_Tcw", _vp), ("kf_bad", _vp), ("kf_desc", _vp), ("scale_factors", _vp), ("mp_xw", _vp), ("mp_ref_kf", _vp),
+                ("mp_normal", _vp), ("mp_min_dist", _vp), ("mp_max_dist", _vp), ("mp_desc", _vp)]
+
+
+class NewKeyframeArgs(C.Structure):
+    _fields_ = [("slot", _i32), ("n_features", _i32), ("obs_cap", _i32), ("obs_mp", _vp), ("obs_kf", _vp), ("obs_idx", _vp),
+                ("d_n_added", _vp), ("recent_cap", _i32), ("d_recent", _vp), ("d_n_recent", _vp), ("refresh", PointRefreshArgs)]
+
+
+class MapPointCullingArgs(C.Structure):
+    _fields_ = [("cur_kf_id", _i32), ("n_th_obs", _i32), ("mp_first_kf_id", _vp), ("mp_found", _vp), ("mp_visible", _vp),
+                ("recent_cap", _i32), ("d_recent", _vp), ("d_n_recent", _vp), ("kf_mp", _vp), ("mp_bad", _vp), ("obs_kf", _vp),
+                ("d_n_culled", _vp), ("d_culled", _vp), ("d_n_erased", _vp), ("erased_cap", _i32), ("d_erased", _vp)]
+
+
 class BirdFilterArgs(C.Structure):
     _fields_ = [("batch", _i32), ("match_stride", _i32), ("kp1_stride", _i32), ("kp2_stride", _i32),
                 ("n_matches", _vp), ("query_idx", _vp), ("train_idx", _vp), ("cam_xyz1", _vp), ("cam_xyz2", _vp),
@@ -426,6 +446,9 @@ EXPORTS = [
     "fb_covis_tree_erase_keyframe_dev", "fb_covis_local_map_dev", "fb_covis_local_map", "fb_covis_reserve_local_map",
     "fb_covis_correct_loop_dev", "fb_covis_correct_loop", "fb_covis_reserve_correct_loop", "fb_covis_propagate_gba_dev",
     "fb_covis_propagate_gba",
+    "fb_covis_refresh_points_dev", "fb_covis_refresh_points", "fb_covis_reserve_refresh_points",
+    "fb_covis_process_new_keyframe_dev", "fb_covis_process_new_keyframe", "fb_covis_reserve_process_new_keyframe",
+    "fb_covis_map_point_culling_dev", "fb_covis_map_point_culling", "fb_covis_reserve_map_point_culling",
     "fb_in_frustum_dev", "fb_in_frustum", "fb_undistort_keypoints_dev", "fb_undistort_keypoints", "fb_image_bounds",
     "fb_pose_opt_batch_dev", "fb_pose_opt", "fb_pose_gather_front_dev", "fb_pose_gather_bird_dev",
     "fb_frame_tail_front_dev", "fb_frame_tail_bird_dev",

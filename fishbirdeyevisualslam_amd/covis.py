@@ -24,13 +24,17 @@ class DeviceMap:
     FIELDS = (("kf_n", np.int32), ("kf_mp", np.int32), ("kf_octave", np.uint8), ("mp_bad", np.uint8), ("obs_mp", np.int32),
               ("obs_kf", np.int32), ("obs_idx", np.int32), ("kf_order", np.uint64))
 
-    def __init__(self, arrays, device="cuda:0"):
+    def __init__(self, arrays, device="cuda:0", obs_spare=0):
+        """obs_spare: entries the three edge arrays hold beyond n_obs (tombstones), for process_new_keyframe to append to."""
         self.device = torch.device(device)
         self.K, self.S = np.asarray(arrays["kf_mp"]).shape
         self.n_mp, self.n_obs = len(arrays["mp_bad"]), len(arrays["obs_kf"])
+        self.obs_cap = self.n_obs + int(obs_spare)
         self.t = {}
         for name, dt in self.FIELDS:
             a = np.ascontiguousarray(arrays[name], dt)
+            if name.startswith("obs_") and obs_spare:
+                a = np.concatenate([a, np.full(int(obs_spare), -1, dt)])
             if a.size == 0:
                 a = np.zeros(1, dt)
             if dt == np.uint64:
@@ -38,6 +42,12 @@ class DeviceMap:
             self.t[name] = torch.from_numpy(a.copy()).to(self.device)
         self.c = cabi.CovisMap()
         cabi.fill(self.c, max_keyframes=self.K, kp_stride=self.S, n_mp=self.n_mp, n_obs=self.n_obs, **self.t)
+
+    def grow(self, n):
+        """The edge list is n entries longer (the block a process_new_keyframe wrote)."""
+        assert self.n_obs + int(n) <= self.obs_cap
+        self.n_obs += int(n)
+        self.c.n_obs = self.n_obs
 
     def bytes(self):
         return b"".join(self.t[name].cpu().numpy().tobytes() for name, _ in self.FIELDS)
@@ -354,3 +364,80 @@ class CovisibilityGraph:
         """The map update that ends RunGlobalBundleAdjustment (:714-825) over the handle's spanning tree.  Enqueues only."""
         check(lib().fb_covis_propagate_gba_dev(self.h, C.byref(m.c), C.byref(t.c), C.byref(a), _stream()), "fb_covis_propagate_gba_dev")
         self._keep = (m, t, a)
+
+    # ---- the per-point side of LocalMapping: refresh, ProcessNewKeyFrame, MapPointCulling ----------------------------------------
+    def reserve_refresh_points(self, n_mp, n_obs, n_q=0):
+        check(lib().fb_covis_reserve_refresh_points(self.h, int(n_mp), int(n_obs), int(n_q)), "fb_covis_reserve_refresh_points")
+
+    def refresh_arrays(self, m, kf_Tcw, kf_bad, kf_desc, scale_factors, mp_xw, mp_ref_kf, mp_normal, mp_min_dist, mp_max_dist, mp_desc,
+                       guard=0):
+        """Device arrays of a fb_point_refresh_args for the map m; the four in/out arrays are followed by `guard` rows the
+        library never sees -> (dict of tensors, cabi.PointRefreshArgs)"""
+        n, K, S = m.n_mp, self.K, m.S
+
+        def padded(x, dtype, width, fill):
+            out = torch.full(((max(n, 1) + guard) * width,), fill, dtype=dtype, device=self.device)
+            if n:
+                out[:n * width] = self._dev(x, dtype).reshape(-1)
+            return out
+        t = dict(kf_Tcw=self._filled(kf_Tcw, torch.float32, 12 * K), kf_bad=self._filled(kf_bad, torch.uint8, K),
+                 kf_desc=self._filled(kf_desc, torch.uint8, 32 * K * S), scale_factors=self._dev(scale_factors, torch.float32).reshape(-1),
+                 mp_xw=self._filled(mp_xw, torch.float32, 3 * n), mp_ref_kf=self._filled(mp_ref_kf, torch.int32, n, -1),
+                 mp_normal=padded(mp_normal, torch.float32, 3, 7.0), mp_min_dist=padded(mp_min_dist, torch.float32, 1, 7.0),
+                 mp_max_dist=padded(mp_max_dist, torch.float32, 1, 7.0), mp_desc=padded(mp_desc, torch.uint8, 32, 0xEE))
+        a = cabi.PointRefreshArgs()
+        cabi.fill(a, n_levels=int(t["scale_factors"].numel()), what=cabi.FB_REFRESH_NORMAL_DEPTH | cabi.FB_REFRESH_DESCRIPTOR, **t)
+        return t, a
+
+    def refresh_points(self, m, a, points=None, n_points=None, what=None, reuse_index=False):
+        """UpdateNormalAndDepth and / or ComputeDistinctiveDescriptors for the listed points (None: every point; n_points: a
+        device int32[1] that holds the list's length) on the arrays of refresh_arrays.  Enqueues only."""
+        lst = None if points is None else self._dev(points).reshape(-1)
+        keep = lst
+        if lst is not None and lst.numel() == 0:
+            lst = self._i32(1)
+        cabi.fill(a, d_list=lst, d_n_list=n_points, n_list=0 if keep is None else int(keep.numel()),
+                  reuse_index=1 if reuse_index else 0)
+        if what is not None:
+            a.what = int(what)
+        check(lib().fb_covis_refresh_points_dev(self.h, C.byref(m.c), C.byref(a), _stream()), "fb_covis_refresh_points_dev")
+        self._keep = (m, a, lst, n_points)
+
+    def recent_list(self, cap, points=()):
+        """mlpRecentAddedMapPoints as device arrays -> (d_recent int32[cap], d_n_recent int32[1])"""
+        r, n = self._i32(cap, -1), self._i32(1)
+        pts = list(points)
+        if pts:
+            r[:len(pts)] = self._dev(pts)
+            n[0] = len(pts)
+        return r, n
+
+    def process_new_keyframe(self, m, refresh, slot, n_features, recent, n_recent):
+        """The point loop of LocalMapping::ProcessNewKeyFrame for the key frame in `slot` of m (a DeviceMap with obs_spare) on
+        the arrays of refresh_arrays and recent_list -> d_n_added int32[1].  The edge list of m is n_features longer
+        afterwards (m.grow); UpdateConnections and the first connection are the caller's next calls.  Enqueues only."""
+        a = cabi.NewKeyframeArgs()
+        n_added = self._i32(1, -1)
+        cabi.fill(a, slot=int(slot), n_features=int(n_features), obs_cap=int(m.obs_cap), obs_mp=m.t["obs_mp"], obs_kf=m.t["obs_kf"],
+                  obs_idx=m.t["obs_idx"], d_n_added=n_added, recent_cap=int(recent.numel()), d_recent=recent, d_n_recent=n_recent)
+        a.refresh = refresh
+        check(lib().fb_covis_process_new_keyframe_dev(self.h, C.byref(m.c), C.byref(a), _stream()), "fb_covis_process_new_keyframe_dev")
+        m.grow(n_features)
+        self._keep = (m, a, refresh, recent, n_recent, n_added)
+        return n_added
+
+    def map_point_culling(self, m, cur_kf_id, mp_first_kf_id, mp_found, mp_visible, recent, n_recent, n_th_obs=2, erased_cap=None):
+        """LocalMapping::MapPointCulling over the recent list, editing kf_mp, mp_bad and obs_kf of m -> dict of device tensors:
+        n_culled[1], culled[cap], n_erased[1], erased[erased_cap][4] rows (kf slot, point, feature, edge).  Enqueues only."""
+        cap = int(recent.numel())
+        ecap = m.n_obs if erased_cap is None else int(erased_cap)
+        out = dict(n_culled=self._i32(1, -1), culled=self._i32(cap, -1), n_erased=self._i32(1, -1),
+                   erased=torch.full((max(ecap, 1), 4), -1, dtype=torch.int32, device=self.device))
+        t = (self._dev(mp_first_kf_id), self._dev(mp_found), self._dev(mp_visible))
+        a = cabi.MapPointCullingArgs()
+        cabi.fill(a, cur_kf_id=int(cur_kf_id), n_th_obs=int(n_th_obs), mp_first_kf_id=t[0], mp_found=t[1], mp_visible=t[2],
+                  recent_cap=cap, d_recent=recent, d_n_recent=n_recent, kf_mp=m.t["kf_mp"], mp_bad=m.t["mp_bad"], obs_kf=m.t["obs_kf"],
+                  d_n_culled=out["n_culled"], d_culled=out["culled"], d_n_erased=out["n_erased"], erased_cap=ecap, d_erased=out["erased"])
+        check(lib().fb_covis_map_point_culling_dev(self.h, C.byref(m.c), C.byref(a), _stream()), "fb_covis_map_point_culling_dev")
+        self._keep = (m, a, t, recent, n_recent, out)
+        return out

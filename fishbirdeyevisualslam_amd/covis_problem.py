@@ -2,8 +2,9 @@
 of fb_covis_map, with the reference's quirks planted.
 
     python -m fishbirdeyevisualslam_amd.covis_problem --probe     # times UpdateConnections / KeyFrameCulling / the window / the local
-                                                                  # map, the tree calls and the two map correction calls at a
-                                                                  # LocalMapping-like size
+                                                                  # map, the tree calls, the two map correction calls and the
+                                                                  # per-point calls at a LocalMapping-like size
+    python -m fishbirdeyevisualslam_amd.covis_problem --probe-points   # the local map and the per-point calls alone
 """
 import numpy as np
 
@@ -319,6 +320,75 @@ def pose12(R, t):
     return np.hstack([np.asarray(R, np.float64), np.asarray(t, np.float64).reshape(3, 1)]).astype(np.float32).reshape(12)
 
 
+def refresh_tables(g, arr, n_levels=8, pool=8, kf_bad_share=0.1):
+    """The arrays the point refresh, ProcessNewKeyFrame and MapPointCulling read next to a finished map `arr` (K, S from
+    kf_mp): poses, kf_bad, kf_desc drawn from a pool of `pool` descriptors (so medians tie), scale factors, positions,
+    reference key frames (an observer; for every ninth point with one, some other slot), the in/out MapPoint members with
+    arbitrary contents, and found / visible / first-id for the culling.  Drawn from the generator g; arr is updated."""
+    K, S = np.asarray(arr["kf_mp"]).shape
+    n_mp = len(arr["mp_bad"])
+    descs = g.integers(0, 256, (pool, 32), dtype=np.uint8)
+    observers = [[] for _ in range(n_mp)]
+    for mp, kf in zip(np.asarray(arr["obs_mp"]).tolist(), np.asarray(arr["obs_kf"]).tolist()):
+        if 0 <= kf < K and 0 <= mp < n_mp:
+            observers[mp].append(kf)
+    ref = np.zeros(n_mp, np.int32)
+    for mp in range(n_mp):
+        o = observers[mp]
+        ref[mp] = int(g.integers(0, K)) if (not o or mp % 9 == 8) else int(o[int(g.integers(0, len(o)))])
+    arr.update(
+        kf_Tcw=np.stack([pose12(rotation(g.normal(0, 0.4, 3)), g.normal(0, 2.0, 3)) for _ in range(K)]),
+        kf_bad=(g.random(K) < kf_bad_share).astype(np.uint8),
+        kf_desc=descs[g.integers(0, pool, (K, S))],
+        scale_factors=(np.float32(1.2) ** np.arange(n_levels, dtype=np.float32)).astype(np.float32),
+        mp_xw=(g.normal(0, 1.0, (n_mp, 3)) + np.array([0, 0, 12.0])).astype(np.float32),
+        mp_ref_kf=ref,
+        mp_normal=g.normal(0, 1, (n_mp, 3)).astype(np.float32), mp_min_dist=g.random(n_mp).astype(np.float32),
+        mp_max_dist=(g.random(n_mp) + 5).astype(np.float32), mp_desc=g.integers(0, 256, (n_mp, 32), dtype=np.uint8),
+        mp_found=g.integers(0, 9, n_mp).astype(np.int32), mp_visible=g.integers(0, 9, n_mp).astype(np.int32),
+        mp_first_kf_id=g.integers(-1, 8, n_mp).astype(np.int32))
+    return arr
+
+
+def make_refresh_problem(seed=1, K=None, S=4, n_mp=None, counts=(0, 1, 2, 3, 63, 64, 65, 130), n_levels=8, pool=8, tombstones=0.15,
+                         n_recent=0):
+    """A map for the point refresh: point p has counts[p] observers (then n_mp - len(counts) more with 0..5), each at a free
+    feature of a distinct slot; octaves below n_levels; a few bad points and bad key frames; tombstones scattered through
+    the shuffled edge list; kf_order pointer-like.  K defaults to what the counts need at stride S.  Also kf_desc, mp_ref_kf,
+    found / visible / first-id and a recent list of n_recent entries (with repeats)."""
+    g = np.random.default_rng(seed)
+    counts = list(counts)
+    n_fixed = len(counts)
+    if n_mp is not None:
+        counts += [int(x) for x in g.integers(0, 6, max(n_mp - len(counts), 0))]
+    n_mp = len(counts)
+    if K is None:
+        K = max(max(counts, default=0) + 6, (sum(counts) + S - 1) // S + 8)
+    free = [list(g.permutation(S)) for _ in range(K)]
+    kf_mp = np.full((K, S), -1, np.int32)
+    edges = []
+    for p in sorted(range(n_mp), key=lambda q: -counts[q]):
+        tie = g.random(K)
+        slots = sorted((s for s in range(K) if free[s]), key=lambda s: (-len(free[s]), tie[s]))[:counts[p]]
+        assert len(slots) == counts[p], "K * S is too small for the counts"
+        for s in slots:
+            i = int(free[s].pop())
+            kf_mp[s, i] = p
+            edges.append((p, s, i))
+    for _ in range(int(len(edges) * tombstones) + 3):                                                  # erased entries: any mp / idx, obs_kf < 0
+        edges.append((int(g.integers(0, max(n_mp, 1))), -1, int(g.integers(0, S))))
+    edges = [edges[i] for i in g.permutation(len(edges))]
+    mp_bad = np.zeros(n_mp, np.uint8)
+    if n_mp > n_fixed:                                                                                 # the points with the stated counts stay good
+        mp_bad[n_fixed + g.choice(n_mp - n_fixed, max((n_mp - n_fixed) // 6, 1), replace=False)] = 1
+    arr = dict(kf_n=np.full(K, S, np.int32), kf_mp=kf_mp, kf_octave=g.integers(0, n_levels, (K, S)).astype(np.uint8), mp_bad=mp_bad,
+               obs_mp=np.array([e[0] for e in edges], np.int32), obs_kf=np.array([e[1] for e in edges], np.int32),
+               obs_idx=np.array([e[2] for e in edges], np.int32), kf_order=pointer_like_order(g, K, list(range(K))), K=K, S=S)
+    refresh_tables(g, arr, n_levels, pool)
+    arr["recent"] = g.integers(0, max(n_mp, 1), n_recent).astype(np.int32)
+    return arr
+
+
 def empty_map_correct_problem(K=4, S=4, BS=2, n_mp=0, n_mpb=0):
     """The arrays fb_covis_correct_loop and fb_covis_propagate_gba read, for a map with nothing in it: identity poses, every
     feature NULL, no edge, no graph connection (`connections`: (a, b, w) for a->AddConnection(b, w)), no tree, Scw = identity."""
@@ -448,6 +518,7 @@ def _probe():
     _probe_map_correct(p, m, G, cur)
     print("errors counted: %d" % G.error_count())
     G.close()
+    _probe_points(p, cur)
     _probe_host(p, cur)
 
 
@@ -456,13 +527,17 @@ def local_map_frame(p, cur, n=2000):
     return np.ascontiguousarray(p["kf_mp"][cur][:n], np.int32)
 
 
-def _median_ms(fn, reps=50, warm=10):
-    """the whole call between two events: median of `reps` after `warm` warm-ups"""
+def _median_ms(fn, reps=50, warm=10, prep=None):
+    """the whole call between two events: median of `reps` after `warm` warm-ups; prep() runs before each call, outside the events"""
     import torch
     for _ in range(warm):
+        if prep:
+            prep()
         fn()
     ts = []
     for _ in range(reps):
+        if prep:
+            prep()
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
         fn()
@@ -510,6 +585,76 @@ def _probe_local_map(p, m, G, t, cur):
     print("device tree_set + tree_erase_keyframe:    %.3f ms" % _median_ms(erase_again))
     print("device tree_set alone:                    %.3f ms" % _median_ms(lambda: G.tree_set(parent, linked, first)))
     G.tree_set(parent, linked, first)
+
+
+def make_new_keyframe_problem(p, new, n_matched=300, n_known=10, seed=21):
+    """The probe's map with key frame `new` turned into one that has just arrived: it holds its first n_matched + n_known
+    points, the edges of the first n_matched of them are tombstones (ProcessNewKeyFrame adds them), the last n_known still
+    observe it (they go to the recent list).  Plus the arrays of refresh_tables.  -> a new dict"""
+    q = {k: (np.array(v) if isinstance(v, np.ndarray) else v) for k, v in p.items()}
+    N = n_matched + n_known
+    row = q["kf_mp"][new].copy()
+    assert np.all(row[:N] >= 0), "key frame %d holds fewer than %d points" % (new, N)
+    gone = (q["obs_kf"] == new) & ~((q["obs_idx"] >= n_matched) & (q["obs_idx"] < N))
+    q["obs_kf"][gone] = -1
+    row[N:] = -1
+    q["kf_mp"][new] = row
+    q["kf_n"][new] = N
+    return refresh_tables(np.random.default_rng(seed), q)
+
+
+def _probe_points(p, cur):
+    """section 7h: fb_covis_refresh_points_dev, fb_covis_process_new_keyframe_dev and fb_covis_map_point_culling_dev on the
+    probe's map, with key frame cur arriving with 300 matched points; whole calls between two events"""
+    import torch
+    from .covis import CovisibilityGraph, DeviceMap
+    q = make_new_keyframe_problem(p, cur)
+    N, n_mp = int(q["kf_n"][cur]), len(q["mp_bad"])
+    m = DeviceMap(q, obs_spare=N)
+    G = CovisibilityGraph(q["K"])
+    t, a = G.refresh_arrays(m, *(q[k] for k in ("kf_Tcw", "kf_bad", "kf_desc", "scale_factors", "mp_xw", "mp_ref_kf", "mp_normal",
+                                                "mp_min_dist", "mp_max_dist", "mp_desc")))
+    pts = np.ascontiguousarray(q["kf_mp"][cur][:N])
+    print("new key frame %d: %d features, %d matched points without an edge" % (cur, N, N - 10))
+    pts_h, pts = pts, torch.from_numpy(pts).to(G.device)                                              # no upload inside a timed call
+    G.refresh_points(m, a, pts)
+    print("device refresh_points(%d points, both parts), reuse_index = 0: %.3f ms" % (N, _median_ms(lambda: G.refresh_points(m, a, pts))))
+    print("device refresh_points(%d points, both parts), reuse_index = 1: %.3f ms" % (N, _median_ms(lambda: G.refresh_points(m, a, pts, reuse_index=True))))
+    print("device refresh_points(%d points, normal and depth), reuse_index = 1: %.3f ms" % (N, _median_ms(lambda: G.refresh_points(m, a, pts, what=1, reuse_index=True))))
+    print("device refresh_points(every point: %d), reuse_index = 1: %.3f ms" % (n_mp, _median_ms(lambda: G.refresh_points(m, a, None, what=3, reuse_index=True))))
+    base = m.n_obs
+    recent, n_recent = G.recent_list(4 * N + 64)
+    added = []
+
+    def pnk():
+        m.n_obs = base
+        m.c.n_obs = base
+        added.append(G.process_new_keyframe(m, a, cur, N, recent, n_recent))
+    ms = _median_ms(pnk, prep=lambda: n_recent.zero_())
+    torch.cuda.synchronize()
+    print("device process_new_keyframe: %.3f ms (%d edges added, %d recent entries)" % (ms, int(added[-1].cpu()[0]), int(n_recent.cpu()[0])))
+    # MapPointCulling over a recent list of the key frame's points; the three arrays it edits are put back before every call
+    g = np.random.default_rng(5)
+    first = np.full(n_mp, 7, np.int32)
+    first[pts_h] = g.integers(6, 10, N)
+    found, vis = np.full(n_mp, 4, np.int32), np.full(n_mp, 4, np.int32)
+    found[pts_h[::5]] = 0
+    first, found, vis = (torch.from_numpy(x).to(G.device) for x in (first, found, vis))
+    keep = {k: m.t[k].clone() for k in ("kf_mp", "mp_bad", "obs_kf")}
+    lst = pts
+    out = []
+
+    def restore():
+        for k, v in keep.items():
+            m.t[k].copy_(v)
+        recent[:N].copy_(lst)
+        n_recent.fill_(N)
+    ms = _median_ms(lambda: out.append(G.map_point_culling(m, 9, first, found, vis, recent, n_recent)), prep=restore)
+    torch.cuda.synchronize()
+    print("device map_point_culling(list of %d): %.3f ms (%d culled, %d edges erased, %d kept)" % (
+        N, ms, int(out[-1]["n_culled"].cpu()[0]), int(out[-1]["n_erased"].cpu()[0]), int(n_recent.cpu()[0])))
+    print("errors counted: %d" % G.error_count())
+    G.close()
 
 
 def _probe_map_correct(p, m, G, cur):
@@ -663,6 +808,15 @@ if __name__ == "__main__":
     import sys
     if "--probe" in sys.argv:
         _probe()
+    elif "--probe-points" in sys.argv:           # the legs of section 7h alone: the local map (the shared index path), then the three calls
+        import torch
+        from .covis import CovisibilityGraph, DeviceMap, DeviceTables
+        q = make_local_mapping_problem()
+        qm, qG = DeviceMap(q), CovisibilityGraph(q["K"])
+        print("map: %d key frames x %d features, %d points, %d edges" % (q["K"], q["S"], qm.n_mp, qm.n_obs))
+        _probe_local_map(q, qm, qG, DeviceTables(dict(q, **window_tables(q, 7))), q["K"] // 2)
+        qG.close()
+        _probe_points(q, q["K"] // 2)
     elif "--probe-host-local-map" in sys.argv:   # the host leg of section 7f alone: needs no device
         import os
         import tempfile

@@ -759,4 +759,5 @@ int fb_covis_keyframe_culling(fb_covis *g, const fb_covis_map *H, int32_t cur_sl
 
 #include "covis_window.inc"
 #include "covis_tree.inc"
+#include "covis_points.inc"
 #include "covis_correct.inc"

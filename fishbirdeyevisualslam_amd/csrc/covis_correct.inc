@@ -217,7 +217,8 @@ __device__ __forceinline__ void cl_move(const ClEntry &E, float *X) {   // :495-
 }
 
 // One thread per map point: the move by its holder, then UpdateNormalAndDepth (MapPoint.cc:330-371) over its live edges in
-// ascending kf_order (a selection over the point's few edges: the sum of CV_32F unit vectors depends on the order).
+// ascending kf_order (a selection over the point's few edges: the sum of CV_32F unit vectors depends on the order).  The
+// arithmetic is nd_unit / nd_finish of covis_points.inc, the one copy k_pt_refresh uses too.
 __global__ __launch_bounds__(CL_NT) void k_cl_move(fb_covis_map M, Gr G, const int32_t *start, const int32_t *csr, fb_correct_loop_args A,
                                                    float *mp_xw, int n_levels, ClS S) {
   const int mp = blockIdx.x * CL_NT + threadIdx.x;
@@ -251,21 +252,16 @@ __global__ __launch_bounds__(CL_NT) void k_cl_move(fb_covis_map M, Gr G, const i
     last = best;
     const int kf = M.obs_kf[be];
     if (kf == ref) ref_idx = M.obs_idx[be];
-    const float *Ow = centre(kf);
-    const float d0 = X[0] - Ow[0], d1 = X[1] - Ow[1], d2 = X[2] - Ow[2];
-    const float inv = (float)(1.0 / sqrt((double)d0 * (double)d0 + (double)d1 * (double)d1 + (double)d2 * (double)d2));   // Mat / cv::norm
-    nx = nx + d0 * inv; ny = ny + d1 * inv; nz = nz + d2 * inv;         // :355
+    float u[3];
+    nd_unit(X, centre(kf), u);
+    nx = nx + u[0]; ny = ny + u[1]; nz = nz + u[2];                     // :355
     n++;
   }
   const int level = M.kf_octave[(size_t)ref * M.kp_stride + ref_idx];   // :361
   if (level >= n_levels) { atomicAdd(G.err, 1); return; }
-  const float *Or = centre(ref);
-  const float dist = fb::norm3(X[0] - Or[0], X[1] - Or[1], X[2] - Or[2]);
-  const float maxd = dist * A.scale_factors[level];                     // :367-369
-  A.mp_max_dist[mp] = maxd;
-  A.mp_min_dist[mp] = maxd / A.scale_factors[n_levels - 1];
-  const float in = (float)(1.0 / (double)n);
-  A.mp_normal[(size_t)mp * 3] = nx * in; A.mp_normal[(size_t)mp * 3 + 1] = ny * in; A.mp_normal[(size_t)mp * 3 + 2] = nz * in;
+  const float sum[3] = {nx, ny, nz};
+  nd_finish(X, centre(ref), A.scale_factors[level], A.scale_factors[n_levels - 1], sum, n, A.mp_normal + (size_t)mp * 3, A.mp_min_dist + mp,
+            A.mp_max_dist + mp);
 }
 
 // the (set member, bird feature) pairs of every bird point: block p links the features of the member at position p

@@ -25,6 +25,7 @@
 
 #include <type_traits>
 #include "fb_claims.h"
+#include "fb_distinctive.h"
 #include "fb_edge_gather.h"
 #include "fb_frame_geom.h"
 #include "fb_primitives.h"

@@ -357,7 +357,8 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_init_match(fb_init_match_args
 }
 
 // ComputeDistinctiveDescriptors: one wave per map point; lane i owns observation i (i, i+64, ...).  The median of row i
-// is found by bisection on the distance value (0..256), recomputing the row's distances from LDS each step.
+// is found by bisection on the distance value (0..256), recomputing the row's distances from LDS each step
+// (fb::distinctive_pick, shared with k_pt_refresh).
 constexpr int DISTINCT_MAX_OBS = 1024;
 __global__ __launch_bounds__(64) void k_distinctive(const int32_t *__restrict__ obs_start, const uint8_t *__restrict__ obs_desc,
                                                     int n_mp, int32_t *__restrict__ best_obs) {
@@ -369,26 +370,7 @@ __global__ __launch_bounds__(64) void k_distinctive(const int32_t *__restrict__ 
   const uint4 *src = reinterpret_cast<const uint4 *>(obs_desc + (size_t)s0 * 32);
   for (int i = lane; i < N * 2; i += 64) D[i] = src[i];
   __syncthreads();
-  const int k = (int)(0.5 * (N - 1));
-  int bestMedian = INT_MAX, bestIdx = INT_MAX;
-  for (int i = lane; i < N; i += 64) {
-    uint32_t d[8];
-    const uint4 a = D[i * 2], c = D[i * 2 + 1];
-    d[0] = a.x; d[1] = a.y; d[2] = a.z; d[3] = a.w; d[4] = c.x; d[5] = c.y; d[6] = c.z; d[7] = c.w;
-    int lo = 0, hi = 256;  // smallest v with #{j : dist(i,j) <= v} >= k+1
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      int cnt = 0;
-      for (int j = 0; j < N; j++) cnt += (fb::hamming256(d, D + j * 2) <= mid) ? 1 : 0;
-      if (cnt >= k + 1) hi = mid; else lo = mid + 1;
-    }
-    if (lo < bestMedian) { bestMedian = lo; bestIdx = i; }  // ascending i per lane: first minimum kept
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const int om = __shfl_xor(bestMedian, o, 64), oi = __shfl_xor(bestIdx, o, 64);
-    if (om < bestMedian || (om == bestMedian && oi < bestIdx)) { bestMedian = om; bestIdx = oi; }
-  }
+  const int bestIdx = fb::distinctive_pick(lane, N, [&](int j) { return D + j * 2; });
   if (lane == 0) best_obs[p] = bestIdx;
 }
 

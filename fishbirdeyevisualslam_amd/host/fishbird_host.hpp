@@ -709,6 +709,87 @@ struct CovisibilityMap {
     m.obs_mp = obsMp.data(); m.obs_kf = obsKf.data(); m.obs_idx = obsIdx.data(); m.kf_order = kfOrder.data();
     return m;
   }
+
+  // ---- the per-point side of LocalMapping (MapPoint.cc:151-168, :242-307, :330-371; LocalMapping.cc:158-179, :207-228) ----
+  // PointTables is what these calls read and write next to the map: per key frame pose, isBad() and mDescriptors, per point
+  // position, mpRefKF as a slot, normal, the two distances, the descriptor, and mnFound / mnVisible / (int)mnFirstKFid.
+  struct PointTables {
+    std::vector<float> kfTcw, scaleFactors, mpXw, mpNormal, mpMinDist, mpMaxDist;   // [K][12], [levels], [points][3], [points][3], [points] x 2
+    std::vector<uint8_t> kfBad, kfDesc, mpDesc;                                     // [K], [K][kpStride][32], [points][32]
+    std::vector<int32_t> mpRefKF, mpFound, mpVisible, mpFirstKFid;                  // [points]
+    PointTables(const CovisibilityMap &m, int nLevels)
+        : kfTcw((size_t)m.maxKeyFrames * 12, 0.f), scaleFactors(nLevels, 1.f), kfBad(m.maxKeyFrames, 0),
+          kfDesc((size_t)m.maxKeyFrames * m.kpStride * 32, 0) {
+      for (int k = 0; k < m.maxKeyFrames; k++) kfTcw[(size_t)k * 12] = kfTcw[(size_t)k * 12 + 5] = kfTcw[(size_t)k * 12 + 10] = 1.f;
+      resize(m.mpBad.size());
+    }
+    void resize(size_t n) {   // after CovisibilityMap::NewMapPoint
+      mpXw.resize(n * 3, 0.f); mpNormal.resize(n * 3, 0.f); mpMinDist.resize(n, 0.f); mpMaxDist.resize(n, 0.f); mpDesc.resize(n * 32, 0);
+      mpRefKF.resize(n, 0); mpFound.resize(n, 1); mpVisible.resize(n, 1); mpFirstKFid.resize(n, 0);
+    }
+    fb_point_refresh_args view() {
+      fb_point_refresh_args a;
+      memset(&a, 0, sizeof(a));
+      a.n_levels = (int32_t)scaleFactors.size(); a.kf_Tcw = kfTcw.data(); a.kf_bad = kfBad.data(); a.kf_desc = kfDesc.data();
+      a.scale_factors = scaleFactors.data(); a.mp_xw = mpXw.data(); a.mp_ref_kf = mpRefKF.data(); a.mp_normal = mpNormal.data();
+      a.mp_min_dist = mpMinDist.data(); a.mp_max_dist = mpMaxDist.data(); a.mp_desc = mpDesc.data();
+      return a;
+    }
+  };
+  // pMP->UpdateNormalAndDepth() and / or pMP->ComputeDistinctiveDescriptors() for the listed points (NULL: every point)
+  void RefreshPoints(fb_covis *g, PointTables &t, const std::vector<int> *points = nullptr,
+                     int what = FB_REFRESH_NORMAL_DEPTH | FB_REFRESH_DESCRIPTOR) const {
+    const fb_covis_map m = view();
+    fb_point_refresh_args a = t.view();
+    a.what = what;
+    if (points) { a.d_list = points->data(); a.n_list = (int32_t)points->size(); }
+    if (points && points->empty()) return;
+    check(fb_covis_refresh_points(g, &m, &a));
+  }
+  // The point loop of LocalMapping::ProcessNewKeyFrame for the key frame in `slot` (kfN, kfMapPoints, kfOctave, kfDesc and
+  // its pose are filled).  The edge list grows by kfN[slot] entries, new edges first, then tombstones; `recent` is
+  // mlpRecentAddedMapPoints.  Returns the number of new edges.
+  int ProcessNewKeyFrame(fb_covis *g, PointTables &t, int slot, std::vector<int> &recent) {
+    const int N = kfN[slot];
+    const fb_covis_map m = view();
+    const size_t n0 = obsKf.size(), r0 = recent.size();
+    obsMp.resize(n0 + N, -1); obsKf.resize(n0 + N, -1); obsIdx.resize(n0 + N, -1);
+    recent.resize(r0 + N, -1);
+    fb_covis_map grown = m;                                                         // the same arrays after the resize
+    grown.obs_mp = obsMp.data(); grown.obs_kf = obsKf.data(); grown.obs_idx = obsIdx.data();
+    fb_new_keyframe_args a;
+    memset(&a, 0, sizeof(a));
+    int32_t nAdded = 0, nRecent = (int32_t)r0;
+    a.slot = slot; a.n_features = N; a.obs_cap = (int32_t)obsKf.size(); a.obs_mp = obsMp.data(); a.obs_kf = obsKf.data(); a.obs_idx = obsIdx.data();
+    a.d_n_added = &nAdded; a.recent_cap = (int32_t)recent.size(); a.d_recent = recent.data(); a.d_n_recent = &nRecent; a.refresh = t.view();
+    check(fb_covis_process_new_keyframe(g, &grown, &a));
+    recent.resize(nRecent);
+    return nAdded;
+  }
+  struct Culled {
+    std::vector<int> points;                          // got SetBadFlag(), in list order: mpMap->EraseMapPoint for each
+    struct Row { int kf, point, idx, edge; };         // the erased observations, per point in ascending kfOrder
+    std::vector<Row> erased;
+  };
+  // LocalMapping::MapPointCulling over `recent` (in/out); edits mpBad, obsKf and kfMapPoints like MapPoint::SetBadFlag
+  Culled MapPointCulling(fb_covis *g, const PointTables &t, int currentKFid, int nThObs, std::vector<int> &recent) {
+    Culled out;
+    if (recent.empty()) return out;
+    const fb_covis_map m = view();
+    fb_map_point_culling_args a;
+    memset(&a, 0, sizeof(a));
+    int32_t nRecent = (int32_t)recent.size(), nCulled = 0, nErased = 0;
+    std::vector<int32_t> culled(recent.size(), -1), rows(obsKf.size() * 4 + 4, -1);
+    a.cur_kf_id = currentKFid; a.n_th_obs = nThObs; a.mp_first_kf_id = t.mpFirstKFid.data(); a.mp_found = t.mpFound.data();
+    a.mp_visible = t.mpVisible.data(); a.recent_cap = nRecent; a.d_recent = recent.data(); a.d_n_recent = &nRecent;
+    a.kf_mp = kfMapPoints.data(); a.mp_bad = mpBad.data(); a.obs_kf = obsKf.data(); a.d_n_culled = &nCulled; a.d_culled = culled.data();
+    a.d_n_erased = &nErased; a.erased_cap = (int32_t)obsKf.size(); a.d_erased = rows.data();
+    check(fb_covis_map_point_culling(g, &m, &a));
+    recent.resize(nRecent);
+    out.points.assign(culled.begin(), culled.begin() + nCulled);
+    for (int r = 0; r < nErased; r++) out.erased.push_back({rows[(size_t)r * 4], rows[(size_t)r * 4 + 1], rows[(size_t)r * 4 + 2], rows[(size_t)r * 4 + 3]});
+    return out;
+  }
 };
 
 class CovisibilityGraph {

@@ -1203,6 +1203,104 @@ int fb_covis_propagate_gba_dev(fb_covis *g, const fb_covis_map *map, const fb_co
 int fb_covis_propagate_gba(fb_covis *g, const fb_covis_map *map, const fb_covis_kf_tables *tables,
                            const fb_propagate_gba_args *a); /* host pointers throughout */
 
+/* ---- the per-point side of LocalMapping: MapPoint::UpdateNormalAndDepth / ComputeDistinctiveDescriptors
+ * (MapPoint.cc:242-307, :330-371), LocalMapping::ProcessNewKeyFrame (LocalMapping.cc:158-179) and MapPointCulling
+ * (:207-228) on fb_covis_map.  These are the calls in which the library writes the caller's map arrays: each names the
+ * arrays it writes, and the writable pointers of the last two must be the map's own.                                   */
+#define FB_REFRESH_NORMAL_DEPTH 1
+#define FB_REFRESH_DESCRIPTOR 2
+#define FB_REFRESH_STAGE 128 /* observers whose descriptors one wave stages in LDS; a longer list reads kf_desc          */
+typedef struct fb_point_refresh_args {
+  const int32_t *d_list;        /* [n_list] map point indices, or NULL: every point of the map (n_list, d_n_list ignored) */
+  const int32_t *d_n_list;      /* [1] the list's length on the device (clamped to n_list), or NULL: n_list              */
+  int32_t n_list;               /* the list's length, or its capacity when d_n_list is given                           */
+  int32_t what;                 /* FB_REFRESH_NORMAL_DEPTH | FB_REFRESH_DESCRIPTOR                                       */
+  int32_t reuse_index;          /* as fb_local_map_args.reuse_index                                                    */
+  int32_t n_levels;             /* 1 .. FB_MAX_LEVELS                                                                  */
+  const float *kf_Tcw;          /* [max_keyframes][12]                                                                 */
+  const uint8_t *kf_bad;        /* [max_keyframes] KeyFrame::isBad()                                                   */
+  const uint8_t *kf_desc;       /* [max_keyframes][kp_stride][32] mDescriptors; 16-byte aligned                        */
+  const float *scale_factors;   /* [n_levels] mvScaleFactors                                                           */
+  const float *mp_xw;           /* [map.n_mp][3]                                                                       */
+  const int32_t *mp_ref_kf;     /* [map.n_mp] mpRefKF as a slot                                                        */
+  float *mp_normal;             /* [map.n_mp][3] in/out                                                                */
+  float *mp_min_dist;           /* [map.n_mp] in/out                                                                   */
+  float *mp_max_dist;           /* [map.n_mp] in/out                                                                   */
+  uint8_t *mp_desc;             /* [map.n_mp][32] in/out: mDescriptor; 16-byte aligned                                 */
+} fb_point_refresh_args;
+/* For every listed point, one wave.  A bad point and a point without a live edge keep everything.  The observers are the
+ * point's live edges in ascending kf_order (the reference iterates a std::map<KeyFrame*, size_t>).
+ * Normal and depth: every observer contributes, bad key frames included (no isBad test at :350-357); the CV_32F sum of
+ * unit vectors runs in observer order, each norm accumulated in double; Ow is what KeyFrame::SetPose makes of kf_Tcw; dist
+ * is to the reference key frame's centre; level is the octave at observations[pRefKF], feature 0's when the reference key
+ * frame is no observer (operator[] inserts 0); mfMaxDistance = dist * scale[level], mfMinDistance = max / scale[n_levels -
+ * 1], normal / n.  A reference slot or a level out of range is counted and the point keeps its normal and distances.
+ * Descriptor: the observers whose key frame is not bad (:265); none: the descriptor stays.  The observer with the least
+ * median distance (index (int)(0.5 * (N - 1)) of its sorted row), the first in observer order among equals, gives its 32
+ * bytes.  Any number of observers up to max_keyframes is handled; up to FB_REFRESH_STAGE descriptors are staged in LDS.
+ * A point listed twice gives what listing it once gives.  A list entry outside [0, n_mp) is skipped and counted.  The
+ * point -> edge index is built or reused like in fb_covis_correct_loop_dev and stays valid.  Enqueues only.            */
+int fb_covis_refresh_points_dev(fb_covis *g, const fb_covis_map *map, const fb_point_refresh_args *a, void *stream);
+int fb_covis_refresh_points(fb_covis *g, const fb_covis_map *map, const fb_point_refresh_args *a); /* host pointers; d_n_list
+                                                                                                      must be NULL           */
+int fb_covis_reserve_refresh_points(fb_covis *g, int32_t n_mp, int32_t n_obs, int32_t n_q);
+
+typedef struct fb_new_keyframe_args {
+  int32_t slot;                 /* mpCurrentKeyFrame; kf_n, kf_mp, kf_octave, kf_desc and its pose are filled already   */
+  int32_t n_features;           /* its N as the host knows it; 0 .. kp_stride                                          */
+  int32_t obs_cap;              /* capacity of the edge arrays; map.n_obs + n_features <= obs_cap                      */
+  int32_t *obs_mp, *obs_kf, *obs_idx;  /* the map's edge arrays, writable (the same pointers as in map)               */
+  int32_t *d_n_added;           /* [1] the number of new edges                                                         */
+  int32_t recent_cap;
+  int32_t *d_recent;            /* [recent_cap] in/out: mlpRecentAddedMapPoints as point indices                       */
+  int32_t *d_n_recent;          /* [1] in/out                                                                          */
+  fb_point_refresh_args refresh; /* the arrays of the refresh; d_list, d_n_list, n_list, what, reuse_index are ignored  */
+} fb_new_keyframe_args;
+/* For i = 0 .. n_features - 1 in order: a NULL entry and a bad point are skipped; a point with no live edge to slot gets
+ * the edge (mp, slot, i) and is refreshed, both parts, on the grown edge list; a point that has one (an edge added earlier
+ * in this loop included: a point held at two features, at its second) is appended to d_recent, in ascending i.  An entry
+ * that does not fit recent_cap is dropped and counted.
+ * The call owns the block [map.n_obs, map.n_obs + n_features) of the edge arrays: the new edges first, in ascending i, the
+ * rest tombstones (obs_kf = obs_mp = obs_idx = -1).  Without waiting, the caller goes on with n_obs + n_features, and may
+ * compact later.  If kf_n[slot] != n_features the block is all tombstones, *d_n_added = 0, nothing else is written and one
+ * error is counted.  UpdateConnections and the mbFirstConnection block stay fb_covis_update_connections_dev and
+ * fb_covis_first_connection_dev on the grown map.  The handle's index is invalid afterwards.  Enqueues only.            */
+int fb_covis_process_new_keyframe_dev(fb_covis *g, const fb_covis_map *map, const fb_new_keyframe_args *a, void *stream);
+int fb_covis_process_new_keyframe(fb_covis *g, const fb_covis_map *map, const fb_new_keyframe_args *a); /* host pointers */
+int fb_covis_reserve_process_new_keyframe(fb_covis *g, int32_t n_mp, int32_t n_obs, int32_t n_q, int32_t n_features);
+
+typedef struct fb_map_point_culling_args {
+  int32_t cur_kf_id;            /* (int)mpCurrentKeyFrame->mnId                                                        */
+  int32_t n_th_obs;             /* 2 monocular, 3 otherwise (:200-205)                                                 */
+  const int32_t *mp_first_kf_id; /* [map.n_mp] (int)mnFirstKFid; -1 for a point made from a Frame                      */
+  const int32_t *mp_found;      /* [map.n_mp] mnFound                                                                  */
+  const int32_t *mp_visible;    /* [map.n_mp] mnVisible                                                                */
+  int32_t recent_cap;
+  int32_t *d_recent;            /* [recent_cap] in/out; the kept entries stay in list order                            */
+  int32_t *d_n_recent;          /* [1] in/out (read clamped to recent_cap)                                             */
+  int32_t *kf_mp;               /* } the map's arrays, writable (the same pointers as in map)                          */
+  uint8_t *mp_bad;              /* }                                                                                   */
+  int32_t *obs_kf;              /* }                                                                                   */
+  int32_t *d_n_culled;          /* [1]                                                                                 */
+  int32_t *d_culled;            /* [recent_cap] the points that got SetBadFlag, in list order (for Map::EraseMapPoint) */
+  int32_t *d_n_erased;          /* [1] rows wanted; rows past erased_cap are not written                               */
+  int32_t erased_cap;
+  int32_t *d_erased;            /* [erased_cap][4] the erased edges as rows (key frame slot, point index, feature index,
+                                   edge index), the row shape of fb_covis_window_scatter_dev: grouped by point in the
+                                   order of d_culled, within a point in ascending kf_order                              */
+} fb_map_point_culling_args;
+/* The walk of :207-228 over the list, in the reference's branch order: a bad point is dropped; (float)found / visible <
+ * 0.25f (the int -> float conversions and one correctly rounded division as written: visible == 0 gives inf or NaN, and a
+ * comparison with NaN is false) -> SetBadFlag, dropped; cur - first >= 2 && Observations() <= n_th_obs -> SetBadFlag,
+ * dropped; cur - first >= 3 -> dropped; otherwise kept.  Observations() is the number of live edges.  SetBadFlag
+ * (MapPoint.cc:151-168): mp_bad = 1, every live edge of the point becomes a tombstone (obs_kf = -1) and kf_mp[kf][idx] = -1
+ * for each, unconditionally like EraseMapPointMatch(idx).  A point listed twice takes its branch at the first entry and is
+ * dropped as bad at the second, as in the serial walk.  A list entry outside [0, n_mp) is dropped and counted.  The graph
+ * is not touched.  The handle's index is invalid afterwards.  Enqueues only.                                           */
+int fb_covis_map_point_culling_dev(fb_covis *g, const fb_covis_map *map, const fb_map_point_culling_args *a, void *stream);
+int fb_covis_map_point_culling(fb_covis *g, const fb_covis_map *map, const fb_map_point_culling_args *a); /* host pointers */
+int fb_covis_reserve_map_point_culling(fb_covis *g, int32_t n_mp, int32_t n_obs, int32_t n_q, int32_t recent_cap);
+
 /* ======================================================================== */
 /* Frame geometry either side of the matchers (src/Frame.cc)                 */
 /* ======================================================================== */
