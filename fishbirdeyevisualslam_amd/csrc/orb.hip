@@ -18,6 +18,8 @@
 //
 // OpenCV semantics (not vendored in the reference -> "parity unpinned") are
 // those of oracle/orb_oracle.cpp; this file must agree with it bit for bit.
+#include <climits>
+
 #include "fb_common.h"
 #include "fb_fast_score.h"
 #include "fb_primitives.h"
@@ -1111,13 +1113,15 @@ __device__ __forceinline__ int reflect101(int i, int n) {
   return i;
 }
 
-__global__ __launch_bounds__(256) void k_blur(OrbK K, const uint8_t *__restrict__ img0, long long imgStride, int pitch0,
+// One launch blurs the levels [l0, l1): its grid covers the strips blurStrips[l0] .. blurStrips[l1] (the whole pyramid is
+// [0, nlevels)), so that a level can be blurred as soon as the resize that writes it has run (FB_ORB_BLUR_CUTS).
+__global__ __launch_bounds__(256) void k_blur(OrbK K, int l0, int l1, const uint8_t *__restrict__ img0, long long imgStride, int pitch0,
                                               const uint8_t *__restrict__ pyr, uint8_t *__restrict__ blur) {
   const int b = blockIdx.y;
-  const int strip = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+  const int strip = __builtin_amdgcn_readfirstlane(K.blurStrips[l0] + blockIdx.x * 4 + (threadIdx.x >> 6));
   const int lane = threadIdx.x & 63;
-  if (strip >= K.blurStrips[K.nlevels]) return;
-  int l = 0;
+  if (strip >= K.blurStrips[l1]) return;
+  int l = l0;
   while (strip >= K.blurStrips[l + 1]) l++;
   const LevelInfo &L = K.L[l];
   const int w = L.w, h = L.h;
@@ -1149,11 +1153,19 @@ __global__ __launch_bounds__(256) void k_blur(OrbK K, const uint8_t *__restrict_
     }
   }
   const bool anyEdge = __ballot(edge) != 0ull;
-  const uint32_t WA = 18u | (34u << 8) | (49u << 16) | (55u << 24), WB = 49u | (34u << 8) | (18u << 16);
+  // horizontal pass: the taps of pixel j are the window bytes 1+j .. 7+j.  The weights are shifted to the bytes, not the
+  // bytes to the weights: W<j><d> weighs dword d of the window for pixel j (2 + 3 + 3 + 2 dots per row and no v_alignbyte;
+  // 6 v_alignbyte + 8 dots before).  The constants live in scalar registers.
+  constexpr uint32_t W0A = (18u << 8) | (34u << 16) | (49u << 24), W0B = 55u | (49u << 8) | (34u << 16) | (18u << 24);
+  constexpr uint32_t W1A = (18u << 16) | (34u << 24), W1B = 49u | (55u << 8) | (49u << 16) | (34u << 24), W1C = 18u;
+  constexpr uint32_t W2A = 18u << 24, W2B = 34u | (49u << 8) | (55u << 16) | (49u << 24), W2C = 34u | (18u << 8);
+  constexpr uint32_t W3B = 18u | (34u << 8) | (49u << 16) | (55u << 24), W3C = 49u | (34u << 8) | (18u << 16);
   // vertical pass: the horizontal sums are 16-bit (<= 255 * 256), so two successive rows of a pixel share a register and
   // v_dot2_u32_u16 takes two taps at once: pairs[r % 6][k] = row r-1 | row r << 16 of pixel k
   uint32_t pairs[6][4];
   uint32_t prevh[4] = {0u, 0u, 0u, 0u};
+  uint32_t rnd = 1u << 15;         // the rounding term of the vertical pass, pinned to a scalar register: as a literal it is
+  asm volatile("" : "+s"(rnd));    // moved into a vector register again for every row
   // The source rows run BLUR_PF rows ahead of the arithmetic: a load -> wait -> use per row would serialise one memory
   // latency per row (22 per wave).  Row indices past the image are reflected, so every prefetch address is valid.
   constexpr int BLUR_PF = 4;
@@ -1180,23 +1192,28 @@ __global__ __launch_bounds__(256) void k_blur(OrbK K, const uint8_t *__restrict_
     }
     uint32_t hr[4];
     // taps of pixel j are window bytes 1+j .. 7+j
-    hr[0] = __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(w2, w1, 1), WB, __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(w1, w0, 1), WA, 0u, false), false);
-    hr[1] = __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(w2, w1, 2), WB, __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(w1, w0, 2), WA, 0u, false), false);
-    hr[2] = __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(w2, w1, 3), WB, __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(w1, w0, 3), WA, 0u, false), false);
-    hr[3] = __builtin_amdgcn_udot4(w2, WB, __builtin_amdgcn_udot4(w1, WA, 0u, false), false);
+    hr[0] = __builtin_amdgcn_udot4(w1, W0B, __builtin_amdgcn_udot4(w0, W0A, 0u, false), false);
+    hr[1] = __builtin_amdgcn_udot4(w2, W1C, __builtin_amdgcn_udot4(w1, W1B, __builtin_amdgcn_udot4(w0, W1A, 0u, false), false), false);
+    hr[2] = __builtin_amdgcn_udot4(w2, W2C, __builtin_amdgcn_udot4(w1, W2B, __builtin_amdgcn_udot4(w0, W2A, 0u, false), false), false);
+    hr[3] = __builtin_amdgcn_udot4(w2, W3C, __builtin_amdgcn_udot4(w1, W3B, 0u, false), false);
     if (r >= 6) {
       typedef unsigned short u16x2b __attribute__((ext_vector_type(2)));
       const u16x2b W01 = {18, 34}, W23 = {49, 55}, W45 = {49, 34};
-      uint32_t packed = 0;
+      uint32_t sum[4];
 #pragma unroll
       for (int k = 0; k < 4; k++) {
         // rows r-6 .. r with weights 18 34 49 55 49 34 18: three two-tap dots on the row pairs + the new row
-        uint32_t sum = (uint32_t)__mul24(18, (int)hr[k]) + (1u << 15);
-        sum = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2b, pairs[(r + 1) % 6][k]), W01, sum, false);  // rows r-6, r-5
-        sum = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2b, pairs[(r + 3) % 6][k]), W23, sum, false);  // rows r-4, r-3
-        sum = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2b, pairs[(r + 5) % 6][k]), W45, sum, false);  // rows r-2, r-1
-        packed |= (uint32_t)min((int)(sum >> 16), 255) << (8 * k);
+        sum[k] = (uint32_t)__mul24(18, (int)hr[k]) + rnd;
+        sum[k] = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2b, pairs[(r + 1) % 6][k]), W01, sum[k], false);  // rows r-6, r-5
+        sum[k] = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2b, pairs[(r + 3) % 6][k]), W23, sum[k], false);  // rows r-4, r-3
+        sum[k] = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2b, pairs[(r + 5) % 6][k]), W45, sum[k], false);  // rows r-2, r-1
       }
+      // min(sum >> 16, 255) of four pixels -> four bytes: the high halves of two sums share a register (sum <= 257 * 65535
+      // + 2^15, so a high half is <= 257), one packed 16-bit min clamps both, and a last v_perm gathers the low bytes
+      const u16x2b C255 = {255, 255};
+      const u16x2b h01 = __builtin_elementwise_min(__builtin_bit_cast(u16x2b, __builtin_amdgcn_perm(sum[1], sum[0], 0x07060302u)), C255);
+      const u16x2b h23 = __builtin_elementwise_min(__builtin_bit_cast(u16x2b, __builtin_amdgcn_perm(sum[3], sum[2], 0x07060302u)), C255);
+      const uint32_t packed = __builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, h23), __builtin_bit_cast(uint32_t, h01), 0x06040200u);
       *reinterpret_cast<uint32_t *>(out + (uint32_t)(__mul24(yo, L.pitch) + x0)) = packed;
     }
 #pragma unroll
@@ -1442,12 +1459,15 @@ void k_describe(OrbK K, const uint8_t *__restrict__ img0, long long imgStride,
 struct fb_orb {
   fb_orb_params p;
   fb_orb_tables t;
-  // k_blur runs on a stream of its own beside k_octree (see fb_orb_extract_batch_dev); created on first use
+  // FB_ORB_SIDE_MIN: k_blur on a stream of its own (see fb_orb_extract_batch_dev); created on first use
   hipStream_t sideStream = nullptr;
   hipEvent_t evFork = nullptr, evJoin = nullptr;
+  hipEvent_t evLevel[FB_MAX_LEVELS] = {};  // evLevel[l]: the resize that writes level l has been enqueued on the caller's stream
   ~fb_orb() {
     if (evFork) (void)hipEventDestroy(evFork);
     if (evJoin) (void)hipEventDestroy(evJoin);
+    for (hipEvent_t e : evLevel)
+      if (e) (void)hipEventDestroy(e);
     if (sideStream) (void)hipStreamDestroy(sideStream);
   }
   int kpStride = 0;  // fb_orb_set_output_stride (0 = the capacity)
@@ -1771,7 +1791,66 @@ int fb_orb_extract_batch_dev(fb_orb *o, const uint8_t *d_images, int batch, int 
   const int nl = K.nlevels;
   int *candCount = o->counts.as<int>();
   int *lvlCount = candCount + (size_t)o->batchCap * nl;
+  // The Gaussian blur needs only the raw levels, so it is launched right behind the last resize, before k_fast.  By default
+  // it stays on the caller's stream at every batch size: in the B = 256 step (front, bird and pose streams side by side)
+  // a fork to a side stream costs more than the overlap returns, wherever the fork is placed and however the levels are
+  // grouped (profiles/blur_schedule_ab.json).  The fork is still there for a caller whose extractor has the GPU to itself
+  // (one stream: the blur then runs beside k_fast and the quadtree): FB_ORB_SIDE_MIN = smallest batch that forks (default:
+  // never), and a set bit l of FB_ORB_BLUR_CUTS starts a new group of levels at level l, each group launched behind the
+  // resize of its last level (default 0: one launch over [0, nlevels)).  What the order of the forked launches rests on:
+  //  (a) the blur of this call writes o->blur, which k_describe of the previous call on this handle may still read: evFork is
+  //      recorded on `s` behind that k_describe, and every launch on the side stream waits for evFork or for a later event
+  //      of `s`;
+  //  (b) the level-0 blur reads the caller's images: `s` waits for evJoin (recorded behind the last blur launch) before
+  //      k_describe, so whatever the caller records on `s` after this call lies behind every read of the images;
+  //  (c) when every kernel is bracketed for the per-kernel table (fb_prof_enable without fb_prof_only) everything stays on the
+  //      caller's stream and the blur is ONE launch over [0, nlevels), so that the table shows each kernel on its own.
+  static const int sideMin = [] {
+    const char* e = getenv("FB_ORB_SIDE_MIN");
+    return e ? atoi(e) : INT_MAX;
+  }();
+  static const unsigned blurCutsEnv = [] {
+    const char* e = getenv("FB_ORB_BLUR_CUTS");
+    return e ? (unsigned)strtoul(e, nullptr, 0) : 0u;
+  }();
+  const bool profAll = fb::g_prof_on && fb::g_prof_only < 0;
+  const bool fork = batch >= sideMin && !profAll;
+  const unsigned blurCuts = profAll ? 0u : blurCutsEnv;
+  auto blurLevels = [&](int l0, int l1, hipStream_t st) {
+#ifndef FB_ORB_ABLATE_BLUR  // probe build only (profiles/probes/ablate_blur.sh): what the step costs without the blur launch (results are then wrong)
+    const int strips = K.blurStrips[l1] - K.blurStrips[l0];
+    if (strips <= 0) return;  // levels too small to hold a key point
+    fb::ProfScope prof_(fb::P_BLUR, st);
+    k_blur<<<dim3((strips + 3) / 4, batch), 256, 0, st>>>(K, l0, l1, d_images, (long long)image_stride, stride, o->pyr.as<uint8_t>(), o->blur.as<uint8_t>());
+#endif
+  };
+  hipStream_t sBlur = s;
+  int blurFrom = 0;  // first level that no launch covers yet
+  // level l (its resize, for l >= 1) has just been enqueued on `s`: launches the group that ends with it, if one does
+  auto blurBehind = [&](int l) -> int {
+    if (l + 1 < nl && !((blurCuts >> (l + 1)) & 1u)) return FB_OK;
+    if (fork && l > 0) {
+      FB_HIP(hipEventRecord(o->evLevel[l], s));
+      FB_HIP(hipStreamWaitEvent(sBlur, o->evLevel[l], 0));
+    }
+    blurLevels(blurFrom, l + 1, sBlur);
+    blurFrom = l + 1;
+    return FB_OK;
+  };
+  if (fork) {
+    if (!o->sideStream) {
+      if (!o->evFork) FB_HIP(hipEventCreateWithFlags(&o->evFork, hipEventDisableTiming));
+      if (!o->evJoin) FB_HIP(hipEventCreateWithFlags(&o->evJoin, hipEventDisableTiming));
+      for (int l = 1; l < FB_MAX_LEVELS; l++)
+        if (!o->evLevel[l]) FB_HIP(hipEventCreateWithFlags(&o->evLevel[l], hipEventDisableTiming));
+      FB_HIP(hipStreamCreateWithFlags(&o->sideStream, hipStreamNonBlocking));
+    }
+    sBlur = o->sideStream;
+    FB_HIP(hipEventRecord(o->evFork, s));
+    FB_HIP(hipStreamWaitEvent(sBlur, o->evFork, 0));
+  }
   FB_HIP(hipMemsetAsync(o->cellCount.p, 0, (size_t)batch * K.totalCells * 4, s));
+  FB_TRY(blurBehind(0));
   // pyramid
   for (int l = 1; l < nl; l++) {
     const LevelInfo &D = K.L[l], &S = K.L[l - 1];
@@ -1779,6 +1858,7 @@ int fb_orb_extract_batch_dev(fb_orb *o, const uint8_t *d_images, int batch, int 
     const long long sstr = (l == 1) ? (long long)image_stride : K.pyrStride;
     const int spitch = (l == 1) ? stride : S.pitch;
     dim3 blk(64, 4), grd((D.pitch / 4 + 63) / 64, (D.h + 3) / 4, batch);
+    {
     fb::ProfScope prof_(fb::P_RESIZE, s);
     const bool rows = o->rowsOK[l] && spitch >= 12 && ((reinterpret_cast<uintptr_t>(src) | (uintptr_t)spitch | (uintptr_t)sstr) & 3) == 0;
     if (rows && o->mergeOK[l]) {
@@ -1790,7 +1870,10 @@ int fb_orb_extract_batch_dev(fb_orb *o, const uint8_t *d_images, int batch, int 
     } else {
       k_resize<<<grd, blk, 0, s>>>(src, sstr, S.w, S.h, spitch, o->pyr.as<uint8_t>() + D.off, K.pyrStride, D.w, D.h, D.pitch, o->rt[l]);
     }
+    }
+    FB_TRY(blurBehind(l));
   }
+  if (fork) FB_HIP(hipEventRecord(o->evJoin, sBlur));
   if (K.totalCells > 0) {
     fb::ProfScope prof_(K.fastTP == 44 ? fb::P_FAST : K.fastTP == 56 ? fb::P_FAST56 : fb::P_FAST72, s);
     const dim3 grdF((K.totalGroups + 7) / 8 * 8, batch);
@@ -1805,35 +1888,6 @@ int fb_orb_extract_batch_dev(fb_orb *o, const uint8_t *d_images, int batch, int 
       FAST_LAUNCH(FAST_MAX_TILE)
 #undef FAST_LAUNCH
   }
-  // The Gaussian blur (vector-ALU bound) and the quadtree (one workgroup per image level, latency bound: 70 % of its wave
-  // cycles wait) are independent and complement each other: the blur goes to a side stream that forks here, after k_fast, and
-  // joins before k_describe (calls of FB_ORB_SIDE_MIN = 64 images or more: the fork/join costs ~0.05 ms of latency).
-  // (When every kernel is bracketed for the per-kernel table -- fb_prof_enable without fb_prof_only -- everything stays on the
-  // caller's stream, so that the table shows each kernel on its own.)
-  static const int sideMin = [] {
-    const char* e = getenv("FB_ORB_SIDE_MIN");
-    return e ? atoi(e) : 64;
-  }();
-  const bool fork = batch >= sideMin && !(fb::g_prof_on && fb::g_prof_only < 0);
-  hipStream_t sBlur = s;
-  if (fork) {
-    if (!o->sideStream) {
-      FB_HIP(hipStreamCreateWithFlags(&o->sideStream, hipStreamNonBlocking));
-      FB_HIP(hipEventCreateWithFlags(&o->evFork, hipEventDisableTiming));
-      FB_HIP(hipEventCreateWithFlags(&o->evJoin, hipEventDisableTiming));
-    }
-    sBlur = o->sideStream;
-    FB_HIP(hipEventRecord(o->evFork, s));
-    FB_HIP(hipStreamWaitEvent(sBlur, o->evFork, 0));
-  }
-#ifndef FB_ORB_ABLATE_BLUR  // probe build only (profiles/probes/ablate_blur.sh): what the step costs without the blur launch (results are then wrong)
-  {
-    fb::ProfScope prof_(fb::P_BLUR, sBlur);
-    k_blur<<<dim3((K.blurStrips[nl] + 3) / 4, batch), 256, 0, sBlur>>>(K, d_images, (long long)image_stride, stride, o->pyr.as<uint8_t>(),
-                                                                        o->blur.as<uint8_t>());
-  }
-#endif
-  if (fork) FB_HIP(hipEventRecord(o->evJoin, sBlur));
   static const int octWideMax = getenv("FB_OCT_WIDE_MAX") ? atoi(getenv("FB_OCT_WIDE_MAX")) : 512;
   const bool octWide = nl * batch <= octWideMax;  // few workgroups: 1024 threads each (two such workgroups fill a CU's wave slots)
   FB_HIP(hipFuncSetAttribute(octWide ? reinterpret_cast<const void *>(k_octree<1024>) : reinterpret_cast<const void *>(k_octree<256>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)o->octreeLds));
