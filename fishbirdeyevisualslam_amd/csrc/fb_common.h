@@ -12,6 +12,7 @@
 #include <climits>
 #include <cstring>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/fishbird.h"
@@ -91,7 +92,11 @@ struct DevBuf {
   size_t bytes = 0, granted = 0;
   DevBuf() {}
   DevBuf(const DevBuf &) = delete;
-  DevBuf &operator=(const DevBuf &) = delete;
+  DevBuf(DevBuf &&o) noexcept : p(o.p), bytes(o.bytes), granted(o.granted) { o.p = nullptr; }
+  DevBuf &operator=(DevBuf &&o) noexcept {  // the block held before goes back to the pool with `o`
+    std::swap(p, o.p); std::swap(bytes, o.bytes); std::swap(granted, o.granted);
+    return *this;
+  }
   ~DevBuf() { if (p) pool_give(p, granted); }
   int alloc(size_t n) {
     if (p) { pool_give(p, granted); p = nullptr; }

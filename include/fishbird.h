@@ -127,8 +127,12 @@ int fb_orb_extract(fb_orb *h, const uint8_t *image, int width, int height, int s
  * d_descriptors[batch][cap][32], d_n[batch], cap = fb_orb_capacity(); d_n[b] is
  * clamped to cap (asynchronous call: no error channel for the overflow above).
  * Stream semantics: everything is ordered after the work already in `stream` and is complete for work enqueued to
- * `stream` afterwards.  Calls of 64 images or more run one kernel on a stream the handle owns, forked from and joined
- * back into `stream` with events inside the call (legal under stream capture as well).  */
+ * `stream` afterwards.  By default every kernel runs on `stream`.  Only when the environment variable FB_ORB_SIDE_MIN is
+ * set do calls of at least that many images run the Gaussian blur on a stream the handle owns, forked from and joined
+ * back into `stream` with events inside the call (legal under stream capture as well).
+ * The first call at a new image size, or with a larger batch, sizes the handle's workspace (it allocates, so it is not
+ * for stream capture).  A call that returns an error, a refused image size included, leaves the handle usable at its
+ * previous size: the next call at that size runs as if the failed one had not been made.  */
 int fb_orb_extract_batch_dev(fb_orb *h, const uint8_t *d_images, int batch, int width, int height,
                              int stride, size_t image_stride, fb_keypoint *d_keypoints,
                              uint8_t *d_descriptors, int32_t *d_n, void *stream);

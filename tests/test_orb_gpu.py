@@ -131,9 +131,9 @@ def test_fast_phase_timers(monkeypatch):
         orb.close()
 
 
-def test_batch_of_72_images_takes_the_side_stream_and_matches_single_image_calls():
-    # calls of 64 images or more run k_blur on a side stream of the extractor beside k_octree (fork after k_fast, join
-    # before k_describe); the result must not depend on that, nor on a second call reusing the same buffers at once
+def test_batch_of_72_images_matches_single_image_calls_and_the_oracle():
+    # the batched entry point on a stream of the caller's, three calls back to back on the same buffers: every image of
+    # the batch gives what the single-image entry point gives for it, and for three of them what the oracle gives
     import torch
     B, w, h = 72, 320, 240
     p = O.orb_params(nfeatures=500)
@@ -146,7 +146,7 @@ def test_batch_of_72_images_takes_the_side_stream_and_matches_single_image_calls
         d_desc = torch.zeros(B * orb.cap * 32, dtype=torch.uint8, device=dev)
         d_n = torch.zeros(B, dtype=torch.int32, device=dev)
         st = torch.cuda.Stream()
-        for _ in range(3):  # back-to-back calls: the fork / join events are reused
+        for _ in range(3):  # back-to-back calls reuse the workspace
             fb.check(fb.lib().fb_orb_extract_batch_dev(orb.h, C.c_void_p(d_img.data_ptr()), B, w, h, w, C.c_size_t(w * h),
                                                        C.c_void_p(d_kps.data_ptr()), C.c_void_p(d_desc.data_ptr()),
                                                        C.c_void_p(d_n.data_ptr()), C.c_void_p(st.cuda_stream)), "extract batch")
@@ -167,8 +167,9 @@ def test_batch_of_72_images_takes_the_side_stream_and_matches_single_image_calls
         orb.close()
 
 
-def test_batch_extraction_with_the_side_stream_can_be_captured_in_a_graph():
-    # fishbird.h: the fork / join of the side stream is legal under stream capture; the replayed graph gives the same bytes
+def test_batch_extraction_can_be_captured_in_a_graph():
+    # fishbird.h: the batch call only enqueues on the caller's stream once its workspace is sized, so it is legal under stream
+    # capture; the replayed graph gives the same bytes
     import torch
     B, w, h = 64, 256, 192
     p = O.orb_params(nfeatures=300)
@@ -187,7 +188,7 @@ def test_batch_extraction_with_the_side_stream_can_be_captured_in_a_graph():
                                                        C.c_void_p(d_n.data_ptr()), C.c_void_p(stream.cuda_stream)), "extract batch")
 
         st = torch.cuda.Stream()
-        call(st)  # direct call (also creates the side stream and its events)
+        call(st)  # direct call (sizes the workspace, which allocates: not under capture)
         st.synchronize()
         ref = (d_n.clone(), d_kps.clone(), d_desc.clone())
         assert int(ref[0].min()) > 50
@@ -215,3 +216,28 @@ def test_single_level_with_many_features_is_extracted_or_refused_as_capacity(nf)
     except fb.FishbirdError as e:
         assert "(-3)" in str(e) and "nfeatures too large for the LDS quadtree" in str(e), str(e)
     _check_image(O.orb_params(nfeatures=300), synth.synth_image(78, 200, 160), stagewise=False)
+
+
+def test_refused_size_leaves_the_handle_usable_at_its_previous_size():
+    """A call that prepare() refuses must not touch the handle: 100x80 (all eight levels >= 1 px, the last 1x1; the oracle
+    accepts it), then 60x50 on the SAME handle (level 7 rounds to 0 px: refused with "is empty" after the argument checks),
+    then the first image again, which must give the first result and the oracle's."""
+    p = O.orb_params(nfeatures=500, scale_factor=2.0, nlevels=8)
+    img = synth.synth_image(5, 100, 80)
+    k_o, d_o = O.orb_extract(p, img)
+    orb = H.Orb(p)
+    try:
+        k0, d0 = orb.extract(img)
+        with pytest.raises(RuntimeError, match="is empty"):
+            orb.extract(synth.synth_image(6, 60, 50))
+        k1, d1 = orb.extract(img)
+    finally:
+        orb.close()
+    assert len(k_o) > 10
+    for k, d in ((k0, d0), (k1, d1)):
+        assert len(k) == len(k_o)
+        for f in ("octave", "x", "y", "response", "size", "angle"):
+            np.testing.assert_array_equal(k[f], k_o[f], err_msg=f)
+        np.testing.assert_array_equal(d, d_o)
+    np.testing.assert_array_equal(k1, k0)
+    np.testing.assert_array_equal(d1, d0)
