@@ -28,15 +28,18 @@ constexpr int WG = 1024;    // workgroup-per-sequence kernels
 
 struct FrameDev {  // device pointers of one frame, passed to kernels by value
   int cap;
+  int map_cap; uint8_t *seen_mark;  // [batch][map_cap] pMP->mnLastFrameSeen == this frame's mnId, written by k_discard
   int32_t *n; fb_keypoint *kps, *kps_un; uint8_t *desc; int32_t *mp; uint8_t *outlier;
   int32_t *nb; fb_keypoint *bkps; uint8_t *bdesc; float *bcam; int32_t *mpb; uint8_t *boutlier;
   float *Tcw;
 };
 
-// mvpMapPoints = NULL, mvbOutlier = false (Frame.cc:327-328); mvpMapPointsBird = NULL, mvBirdOutlier = TRUE (:355-356)
+// mvpMapPoints = NULL, mvbOutlier = false (Frame.cc:327-328); mvpMapPointsBird = NULL, mvBirdOutlier = TRUE (:355-356).
+// A new Frame has a new mnId (Frame.cc:265): no map point carries it in mnLastFrameSeen yet, so the marks are cleared.
 __global__ __launch_bounds__(TT) void k_frame_reset(FrameDev F, int32_t *counts, int B) {
   const int b = blockIdx.y, i = blockIdx.x * TT + threadIdx.x;
   if (blockIdx.x == 0 && threadIdx.x < FB_CNT_COUNT) counts[threadIdx.x * B + b] = 0;
+  for (int j = i; j < F.map_cap; j += gridDim.x * TT) F.seen_mark[(size_t)b * F.map_cap + j] = 0;
   if (i >= F.cap) return;
   const size_t o = (size_t)b * F.cap + i;
   F.mp[o] = -1; F.outlier[o] = 0; F.mpb[o] = -1; F.boutlier[o] = 1;
@@ -215,7 +218,11 @@ __global__ __launch_bounds__(TT) void k_edges(FrameDev F, MapDev map, BirdMapDev
 
 // "Discard outliers" of TrackWithMotionModel (Tracking.cc:1358-1376): one workgroup per sequence
 // and of TrackReferenceKeyFrame (:1222-1241); src_slot = the matcher count nmatches starts from; gate_min > 0: a sequence
-// whose src_slot count is below it returned before the loop (:1212-1213)
+// whose src_slot count is below it returned before the loop (:1212-1213).
+// pMP->mnLastFrameSeen = mCurrentFrame.mnId of a dropped point (:1370 / :1235) is a byte per map point on the frame handle
+// (the caller's map arrays stay read-only).  It lives as long as the frame id: a second discard in the same frame (the
+// fall-back from the motion model to the reference key frame) adds its marks, only Frame construction clears them.
+// pMP->mbTrackInView = false (:1369 / :1234) needs no state: k_local_points rebuilds the track members.
 __global__ __launch_bounds__(WG) void k_discard(FrameDev F, MapDev map, int32_t *counts, int B, int src_slot, int gate_min) {
   __shared__ int s_w[WG / 64];
   const int b = blockIdx.x, n = min(F.n[b], F.cap);
@@ -225,7 +232,10 @@ __global__ __launch_bounds__(WG) void k_discard(FrameDev F, MapDev map, int32_t 
     const size_t o = (size_t)b * F.cap + i;
     const int id = F.mp[o];
     if (id < 0) continue;
-    if (F.outlier[o]) { F.mp[o] = -1; F.outlier[o] = 0; dropped++; }
+    if (F.outlier[o]) {
+      if (id < F.map_cap) F.seen_mark[(size_t)b * F.map_cap + id] = 1;   // (always: map_ok() holds map.stride <= map_cap; kept as the store's own bound)
+      F.mp[o] = -1; F.outlier[o] = 0; dropped++;
+    }
     else if (map.obs_pos[(size_t)b * map.stride + id]) inmap++;
   }
   dropped = fb::block_sum<WG>(dropped, s_w);
@@ -334,8 +344,9 @@ struct LocalScratch { uint8_t *seen, *blocked, *inview, *obs; float *proj; int32
 struct FrustumK { fb_camera cam; float log_scale_factor; int n_levels; };
 
 // SearchLocalPoints (Tracking.cc:1947-1984), one workgroup per sequence:
+//   0. "seen" starts from the marks the discard loops of this frame left (k_discard): mnLastFrameSeen == mnId already
 //   1. points the frame holds: bad ones are dropped from the frame, the others are marked seen (mnLastFrameSeen = mnId)
-//   2. every other good point of mvpLocalMapPoints: isInFrustum(pMP, 0.5) -> the dense track members M2 reads
+//   2. every other good point of mvpLocalMapPoints (:1974-1977): isInFrustum(pMP, 0.5) -> the dense track members M2 reads
 __global__ __launch_bounds__(WG) void k_local_points(FrameDev F, MapDev map, const int32_t *local, const int32_t *n_local, int lcap,
                                                      FrustumK K, LocalScratch S, int32_t *counts, int B, const int32_t *gate_row, int gate_min) {
   __shared__ int s_w[WG / 64];
@@ -349,7 +360,8 @@ __global__ __launch_bounds__(WG) void k_local_points(FrameDev F, MapDev map, con
   const int nmap = min(max(map.n[b], 0), map.stride);
   if (tid < 12) s_T[tid] = F.Tcw[(size_t)b * 12 + tid];
   if (tid == 64) fb::camera_centre(F.Tcw + (size_t)b * 12, s_Ow);
-  for (int i = tid; i < nmap; i += WG) S.seen[mo + i] = 0;
+  // (nmap <= map.stride <= map_cap by map_ok(); the test only bounds the load on its own array)
+  for (int i = tid; i < nmap; i += WG) S.seen[mo + i] = i < F.map_cap ? F.seen_mark[(size_t)b * F.map_cap + i] : 0;
   __syncthreads();
   const int n = min(F.n[b], F.cap);
   for (int i = tid; i < n; i += WG) {
@@ -455,6 +467,7 @@ struct fb_frame {
   fb::DevBuf n, kps, kps_un, desc, cs, ci, mp, outlier;
   fb::DevBuf nb, bkps, bdesc, bcam, bcs, bci, mpb, boutlier, nb_pre, bkps_pre, bdesc_pre;
   fb::DevBuf Tcw, counts;
+  fb::DevBuf seen_mark;   // mnLastFrameSeen == mnId per map point, [batch][map_cap] (k_discard writes, k_local_points reads)
   // scratch
   fb::DevBuf m3_valid, m3_obs, m3_xw, m3_desc, m3_oct, m3_ang, m_front;
   fb::DevBuf m9_valid, m9_xw, m9_desc, m9_n, m_bird, ones;
@@ -483,6 +496,7 @@ struct fb_frame {
   FrameDev dev() const {
     FrameDev F;
     F.cap = cap;
+    F.map_cap = P.map_cap; F.seen_mark = seen_mark.as<uint8_t>();
     F.n = n.as<int32_t>(); F.kps = kps.as<fb_keypoint>(); F.kps_un = kps_un.as<fb_keypoint>(); F.desc = desc.as<uint8_t>();
     F.mp = mp.as<int32_t>(); F.outlier = outlier.as<uint8_t>();
     F.nb = nb.as<int32_t>(); F.bkps = bkps.as<fb_keypoint>(); F.bdesc = bdesc.as<uint8_t>(); F.bcam = bcam.as<float>();
@@ -583,7 +597,7 @@ int fb_frame_create(const fb_frame_params *p, fb_frame **out) {
   AL(mp, B * cap * 4); AL(outlier, B * cap);
   AL(nb, B * 4); AL(bkps, B * cap * KP); AL(bdesc, B * cap * 32); AL(bcam, B * cap * 12); AL(bcs, B * (32 * 32 + 1) * 4); AL(bci, B * cap * 4);
   AL(mpb, B * cap * 4); AL(boutlier, B * cap); AL(nb_pre, B * 4); AL(bkps_pre, B * cap * KP); AL(bdesc_pre, B * cap * 32);
-  AL(Tcw, B * 48); AL(counts, B * FB_CNT_COUNT * 4);
+  AL(Tcw, B * 48); AL(counts, B * FB_CNT_COUNT * 4); AL(seen_mark, B * (size_t)p->map_cap);
   AL(m3_valid, B * cap); AL(m3_obs, B * cap); AL(m3_xw, B * cap * 12); AL(m3_desc, B * cap * 32); AL(m3_oct, B * cap * 4); AL(m3_ang, B * cap * 4);
   AL(m_front, B * cap * 4);
   AL(m9_valid, B * lb); AL(m9_xw, B * lb * 12); AL(m9_desc, B * lb * 32); AL(m9_n, B * 4); AL(m_bird, B * cap * 4); AL(ones, B * lb);
@@ -597,6 +611,7 @@ int fb_frame_create(const fb_frame_params *p, fb_frame **out) {
   if (rc != FB_OK) { delete f; return rc; }
   hipError_t e = hipMemset(f->ones.p, 1, B * lb);
   if (e == hipSuccess) e = hipMemset(f->counts.p, 0, B * FB_CNT_COUNT * 4);
+  if (e == hipSuccess) e = hipMemset(f->seen_mark.p, 0, B * (size_t)p->map_cap);
   if (e == hipSuccess) e = hipMemset(f->n.p, 0, B * 4);
   if (e == hipSuccess) e = hipMemset(f->nb.p, 0, B * 4);
   if (e == hipSuccess) e = hipMemset(f->Tcw.p, 0, B * 48);
@@ -1122,7 +1137,7 @@ int fb_frame_track_using_bird_dev(fb_frame *cur, fb_frame *src, fb_frame *ref, c
 
 int fb_frame_copy_dev(fb_frame *dst, const fb_frame *src, void *stream) {
   FB_TRY(fb::check_device());
-  FB_ARG(dst && src && dst != src && dst->B == src->B && dst->cap == src->cap);
+  FB_ARG(dst && src && dst != src && dst->B == src->B && dst->cap == src->cap && dst->P.map_cap == src->P.map_cap);
   hipStream_t s = fb::as_stream(stream);
   const size_t B = src->B, cap = src->cap;
   if (src->bowDone && !dst->bow_nw.p) {
@@ -1133,7 +1148,7 @@ int fb_frame_copy_dev(fb_frame *dst, const fb_frame *src, void *stream) {
 #define CP(buf) FB_HIP(hipMemcpyAsync(dst->buf.p, src->buf.p, src->buf.bytes, hipMemcpyDeviceToDevice, s))
   CP(n); CP(kps); CP(kps_un); CP(desc); CP(cs); CP(ci); CP(mp); CP(outlier);
   CP(nb); CP(bkps); CP(bdesc); CP(bcam); CP(bcs); CP(bci); CP(mpb); CP(boutlier);
-  CP(Tcw); CP(counts);
+  CP(Tcw); CP(counts); CP(seen_mark);
   if (src->bowDone) { CP(bow_nw); CP(bow_ids); CP(bow_vals); CP(fv_nn); CP(fv_ids); CP(fv_start); CP(fv_items); }
 #undef CP
   dst->bowDone = src->bowDone;

@@ -1578,7 +1578,10 @@ int fb_frame_search_by_projection_dev(fb_frame *cur, const fb_frame *last, const
  * which = 0 writes FB_CNT_POSE1_INLIERS, 1 writes FB_CNT_POSE2_INLIERS.                                                 */
 int fb_frame_pose_optimization_dev(fb_frame *f, const fb_map_points *map, const fb_map_points_bird *mpb, int mode,
                                    float wB, float wF, int which, void *stream);
-/* "Discard outliers" of TrackWithMotionModel (Tracking.cc:1358-1376)                                                     */
+/* "Discard outliers" of TrackWithMotionModel (Tracking.cc:1358-1376).  A dropped point is marked as seen in this frame
+ * (pMP->mnLastFrameSeen = mCurrentFrame.mnId, :1370): the mark is a byte per map point ON THE FRAME HANDLE (`map` stays
+ * read-only), it is what fb_frame_search_local_points_dev skips, fb_frame_copy_dev copies it, a further discard in the
+ * same frame adds to it, and only fb_frame_extract[_dev] (a new Frame, a new mnId) clears it.                           */
 int fb_frame_discard_outliers_dev(fb_frame *f, const fb_map_points *map, void *stream);
 /* GetPerFrameMatchedBirdPoints (Tracking.cc:2724-2733): BirdviewMatch(cur, ref keys / descriptors, ..., 0, window)
  * (M8) followed by the whole of FilterBirdOutlierInFront(ref, cur, matches, filter_size) (:1825-1914), bookkeeping
@@ -1586,7 +1589,9 @@ int fb_frame_discard_outliers_dev(fb_frame *f, const fb_map_points *map, void *s
  * to `mpb` with position ptwC and cur's descriptor) that ref.mvpMapPointsBird[query] receives as well.                  */
 int fb_frame_match_bird_points_dev(fb_frame *cur, fb_frame *ref, fb_map_points_bird *mpb, int window_size,
                                    float filter_size, const fb_matcher_params *matcher, void *stream);
-/* SearchLocalPoints (Tracking.cc:1947-1997): points the frame already holds are marked seen, isInFrustum(pMP, 0.5) on the
+/* SearchLocalPoints (Tracking.cc:1947-1997): points the frame already holds are marked seen -- like the points the
+ * discard loops of this frame dropped (the marks fb_frame_discard_outliers_dev and the fused stages leave on the handle;
+ * :1974: neither projected, nor counted in FB_CNT_TO_MATCH, nor matched again) --, isInFrustum(pMP, 0.5) on the
  * others of mvpLocalMapPoints (d_local: indices into `map`, [batch][params.local_mp_cap]; NULL = the whole table), then
  * SearchByProjection(cur, mvpLocalMapPoints, th) (ORBmatcher.cc:46-130; M2) if anything is to be matched.               */
 int fb_frame_search_local_points_dev(fb_frame *f, const fb_map_points *map, const int32_t *d_local,
@@ -1650,7 +1655,9 @@ int fb_frame_track_using_bird_dev(fb_frame *cur, fb_frame *src, fb_frame *ref, c
 
 /* Frame(const Frame &) (Frame.cc:49-82: tmpRefFrame = new Frame(mCurrentFrame), Tracking.cc:746) and the member copies of
  * KeyFrame::KeyFrame(Frame &F, ...) (KeyFrame.cc:32-91): every member array of src into dst (same parameters), device to
- * device on the stream, including the BoW when src has it.                                                               */
+ * device on the stream, including the BoW when src has it and the frame's seen marks (fb_frame_discard_outliers_dev).
+ * FB_ERR_ARG unless both handles were created with the same batch, orb parameters (capacity) and map_cap: the arrays
+ * are copied whole.                                                                                                     */
 int fb_frame_copy_dev(fb_frame *dst, const fb_frame *src, void *stream);
 
 /* Frame::ComputeBoW (Frame.cc:628-635; KeyFrame::ComputeBoW, KeyFrame.cc:93-102) on the handle: transform(mDescriptors,

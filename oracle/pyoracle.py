@@ -218,6 +218,30 @@ class OracleChain:
         assert self.L.orc_frame_track(self.cur, self.last, C.byref(self.targs)) == 0
         self.k += 1
 
+    def track_stage_by_stage(self, front, bird, contour, mask, delta, delta_kf=None, mode="motion"):
+        """track_modes(mode = "motion" / "motion+reference") with each "Discard outliers" loop as a call of its own.  Returns
+        the frame's views in front of and behind each loop: "motion_pose", "motion_discard" [, "reference_pose",
+        "reference_discard"]; the frame after TrackLocalMap is view() as usual."""
+        self.extract(front, bird, contour, mask)
+        self.keep["delta"] = np.ascontiguousarray(delta, np.float32)
+        cabi.fill(self.targs, d_delta=self.keep["delta"])
+        out = {}
+        assert self.L.orc_frame_track_motion_model_ex(self.cur, self.last, C.byref(self.targs), 0) == 0
+        out["motion_pose"] = self.view("cur")
+        self.discard_outliers("PROJ_MATCHES", 20)
+        out["motion_discard"] = self.view("cur")
+        if "reference" in mode:
+            self.keep["delta_kf"] = np.ascontiguousarray(delta_kf, np.float32)
+            cabi.fill(self.targs, d_delta=self.keep["delta_kf"])
+            assert self.L.orc_frame_track_reference_ex(self.cur, self.kf, self.last, C.byref(self.voc), C.byref(self.targs), 0) == 0
+            cabi.fill(self.targs, d_delta=self.keep["delta"])
+            out["reference_pose"] = self.view("cur")
+            self.discard_outliers("BOW_MATCHES", 15)
+            out["reference_discard"] = self.view("cur")
+        assert self.L.orc_frame_track_local_map(self.cur, self.last, C.byref(self.targs)) == 0
+        self.k += 1
+        return out
+
     # ---- reference key frame ----
     def set_vocabulary(self, voc_arrays, L):
         self.keep["voc"] = {k: np.ascontiguousarray(v) for k, v in voc_arrays.items()}
@@ -254,6 +278,25 @@ class OracleChain:
             cabi.fill(self.targs, d_delta=self.keep["delta"])
         assert self.L.orc_frame_track_local_map(self.cur, self.last, C.byref(self.targs)) == 0
         self.k += 1
+
+    # ---- the steps one by one, on the current frame (no k += 1: the caller builds the frame's associations itself) ----
+    def set_map_points(self, mp, mpb=None):
+        a = np.ascontiguousarray(mp, np.int32)
+        b = np.ascontiguousarray(mpb, np.int32) if mpb is not None else None
+        assert self.L.orc_frame_set_map_points(self.cur, C.c_void_p(a.ctypes.data), C.c_void_p(b.ctypes.data) if b is not None else None) == 0
+
+    def set_pose(self, Tcw):
+        t = np.ascontiguousarray(Tcw, np.float32)
+        assert self.L.orc_frame_set_pose(self.cur, C.c_void_p(t.ctypes.data)) == 0
+
+    def pose_optimization(self, which=0):
+        assert self.L.orc_frame_pose_optimization(self.cur, C.byref(self.targs), which) == 0
+
+    def discard_outliers(self, src="PROJ_MATCHES", gate_min=0):
+        assert self.L.orc_frame_discard_outliers(self.cur, C.byref(self.targs), cabi.FB_CNT[src], gate_min) == 0
+
+    def search_local_points(self):
+        assert self.L.orc_frame_search_local_points(self.cur, C.byref(self.targs)) == 0
 
     def drop_outliers(self, which="last"):
         f = self.last if which == "last" else self.cur

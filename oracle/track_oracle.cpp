@@ -15,6 +15,8 @@
  *   Tracking::TrackReferenceKeyFrame   :1180-1244 with Frame::ComputeBoW (Frame.cc:628-635); the reference key frame is a
  *                                      frame object (a KeyFrame is built from one, KeyFrame.cc:32-91)
  * mvpMapPoints / mvpMapPointsBird are indices into the caller's map tables (-1 = NULL), like the product's fb_frame.
+ * The one MapPoint member the chain writes, mnLastFrameSeen == mCurrentFrame.mnId, is a per-point flag of the frame
+ * (orc_frame::seen_mark): the caller's tables stay read-only, and the flag lives as long as the frame id does.
  * The matchers / extractor / optimiser called in between are the other files of this oracle.
  */
 #include <chrono>
@@ -54,6 +56,7 @@ struct orc_frame {
   std::vector<int32_t> n, nb, mp, mpb, cs, ci, bcs, bci, counts;
   std::vector<fb_keypoint> kps, kps_un, bkps;
   std::vector<uint8_t> desc, bdesc, outlier, boutlier;
+  std::vector<uint8_t> seen_mark;  // [B][map_cap] pMP->mnLastFrameSeen == this frame's mnId, set by the "Discard outliers" loops
   std::vector<float> bcam, Tcw;
   // mBowVec / mFeatVec (Frame.h:128-129), empty until ComputeBoW
   int min_inliers = 30;   // threshold of the last end-of-Track clean-up
@@ -137,6 +140,7 @@ int orc_frame_create(const fb_frame_params *p, orc_frame **out) {
   f->kps.assign(B * cap, fb_keypoint{}); f->kps_un.assign(B * cap, fb_keypoint{}); f->bkps.assign(B * cap, fb_keypoint{});
   f->desc.assign(B * cap * 32, 0); f->bdesc.assign(B * cap * 32, 0); f->outlier.assign(B * cap, 0); f->boutlier.assign(B * cap, 1);
   f->bcam.assign(B * cap * 3, 0.f); f->Tcw.assign(B * 12, 0.f);
+  f->seen_mark.assign(B * (size_t)p->map_cap, 0);
   std::memset(f->stage_s, 0, sizeof(f->stage_s));
   *out = f;
   return FB_OK;
@@ -189,6 +193,7 @@ int orc_frame_extract(orc_frame *f, const uint8_t *front, int front_stride, cons
   orc_grid_build(f->kps_un.data(), f->n.data(), f->B, f->cap, &f->gF, f->cs.data(), f->ci.data());  // AssignFeaturesToGrid, :376
   orc_grid_build(f->bkps.data(), f->nb.data(), f->B, f->cap, &f->gB, f->bcs.data(), f->bci.data());
   std::fill(f->counts.begin(), f->counts.end(), 0);
+  std::fill(f->seen_mark.begin(), f->seen_mark.end(), 0);  // a new mnId: no point was seen in this frame yet
   f->bow_done = false;
   return FB_OK;
 }
@@ -329,7 +334,9 @@ void search_by_projection_last(orc_frame *cur, const orc_frame *last, const fb_m
 
 // the "Discard outliers" loop of TrackWithMotionModel (Tracking.cc:1358-1376) and TrackReferenceKeyFrame (:1221-1241);
 // nmatches starts from the matcher's return value (src_slot).  gate: sequences whose gate_slot counter is below gate_min
-// returned before the loop (TrackReferenceKeyFrame :1209-1210)
+// returned before the loop (TrackReferenceKeyFrame :1209-1210).  A dropped point is marked as seen in this frame
+// (pMP->mnLastFrameSeen = mCurrentFrame.mnId, :1370 / :1235): SearchLocalPoints skips it (:1974).  mbTrackInView = false
+// (:1369 / :1234) needs no state here: the track members are rebuilt by every search_local_points.
 void discard_outliers(orc_frame *cur, const fb_map_points *map, int src_slot, bool gate = false, int gate_slot = 0, int gate_min = 0) {
   const size_t B = cur->B, cap = cur->cap;
   for (size_t b = 0; b < B; b++) {
@@ -338,7 +345,10 @@ void discard_outliers(orc_frame *cur, const fb_map_points *map, int src_slot, bo
     for (int i = 0; i < cur->n[b]; i++) {
       const size_t o = b * cap + i;
       if (cur->mp[o] < 0) continue;
-      if (cur->outlier[o]) { cur->mp[o] = -1; cur->outlier[o] = 0; nmatches--; }
+      if (cur->outlier[o]) {
+        if (cur->mp[o] < cur->P.map_cap) cur->seen_mark[b * (size_t)cur->P.map_cap + cur->mp[o]] = 1;
+        cur->mp[o] = -1; cur->outlier[o] = 0; nmatches--;
+      }
       else if (map->obs_pos[b * map->stride + cur->mp[o]]) nmatchesMap++;
     }
     cnt(cur, FB_CNT_MATCHES)[b] = nmatches;
@@ -427,6 +437,8 @@ void search_local_points(orc_frame *cur, const fb_track_args *T, const fb_map_po
         proj(B * (size_t)lcap * 2, 0.f), vcos(B * (size_t)lcap, 0.f), Ow(B * 3, 0.f);
     std::vector<int32_t> level(B * (size_t)lcap, 0), nl(B, 0), match(B * cap, -1);
     for (size_t b = 0; b < B; b++) {
+      for (int id = 0; id < map->n[b] && id < cur->P.map_cap; id++)  // mnLastFrameSeen == mnId from the discard loops
+        seen[b * map->stride + id] = cur->seen_mark[b * (size_t)cur->P.map_cap + id];
       for (int i = 0; i < cur->n[b]; i++) {  // :1950-1966
         const size_t o = b * cap + i;
         const int id = cur->mp[o];
@@ -559,7 +571,9 @@ void track_local_map(orc_frame *cur, orc_frame *last, const fb_track_args *T, fb
 extern "C" {
 
 // Tracking::Track for a frame in state OK: TrackWithMotionModel + TrackLocalMap + the clean-up (host pointers in T)
-int orc_frame_track_motion_model(orc_frame *cur, orc_frame *last, const fb_track_args *T) {
+// discard = 0: stop in front of the "Discard outliers" loop, so that a test can look at the frame the loop is given and
+// then run it with orc_frame_discard_outliers(f, T, FB_CNT_PROJ_MATCHES, 20)
+int orc_frame_track_motion_model_ex(orc_frame *cur, orc_frame *last, const fb_track_args *T, int discard) {
   const fb_map_points *map = &T->map;
   fb_map_points_bird mpbv = T->mpb;
   std::memset(cur->stage_s, 0, sizeof(cur->stage_s));
@@ -582,8 +596,12 @@ int orc_frame_track_motion_model(orc_frame *cur, orc_frame *last, const fb_track
   }
   t1 = now();
   cur->stage_s[4] = t1 - t0;
-  discard_outliers(cur, map, FB_CNT_PROJ_MATCHES, true, FB_CNT_PROJ_MATCHES, 20);                // :1358-1376
+  if (discard) discard_outliers(cur, map, FB_CNT_PROJ_MATCHES, true, FB_CNT_PROJ_MATCHES, 20);   // :1358-1376
   return FB_OK;
+}
+
+int orc_frame_track_motion_model(orc_frame *cur, orc_frame *last, const fb_track_args *T) {
+  return orc_frame_track_motion_model_ex(cur, last, T, 1);
 }
 
 int orc_frame_track_local_map(orc_frame *cur, orc_frame *last, const fb_track_args *T) {
@@ -623,7 +641,9 @@ int orc_frame_compute_bow(orc_frame *f, const fb_vocabulary *voc) {
 
 // Tracking::TrackReferenceKeyFrame (Tracking.cc:1180-1244), bLooseCouple = true (System.cc:32), bHaveBird.
 // kf = mpReferenceKF (its BoW computed, KeyFrame.cc:93-102), last = tmpRefFrame, T->d_delta = detlaT of :1185.
-int orc_frame_track_reference(orc_frame *cur, orc_frame *kf, orc_frame *last, const fb_vocabulary *voc, const fb_track_args *T) {
+// discard = 0: as orc_frame_track_motion_model_ex; the loop is then orc_frame_discard_outliers(f, T, FB_CNT_BOW_MATCHES, 15)
+int orc_frame_track_reference_ex(orc_frame *cur, orc_frame *kf, orc_frame *last, const fb_vocabulary *voc, const fb_track_args *T,
+                                 int discard) {
   const size_t B = cur->B, cap = cur->cap;
   const fb_map_points *map = &T->map;
   fb_map_points_bird mpbv = T->mpb;
@@ -666,8 +686,12 @@ int orc_frame_track_reference(orc_frame *cur, orc_frame *kf, orc_frame *last, co
     pose_optimization(cur, map, &mpbv, FB_POSE_FRONT_BIRD, T->wB, T->wF, FB_CNT_POSE1_INLIERS);
     cur->n = n_keep; cur->nb = nb_keep;
   }
-  discard_outliers(cur, map, FB_CNT_BOW_MATCHES, true, FB_CNT_BOW_MATCHES, 15);   // :1222-1241
+  if (discard) discard_outliers(cur, map, FB_CNT_BOW_MATCHES, true, FB_CNT_BOW_MATCHES, 15);   // :1222-1241
   return FB_OK;
+}
+
+int orc_frame_track_reference(orc_frame *cur, orc_frame *kf, orc_frame *last, const fb_vocabulary *voc, const fb_track_args *T) {
+  return orc_frame_track_reference_ex(cur, kf, last, voc, T, 1);
 }
 
 // Tracking::TrackUsingBird (Tracking.cc:2014-2061); src = mpReferenceKF or tmpRefFrame, last = tmpRefFrame
@@ -679,6 +703,26 @@ int orc_frame_track_using_bird(orc_frame *cur, orc_frame *src, orc_frame *last, 
   per_frame_matched_bird_points(cur, last, &mpbv, 11);           // :2038-2053: else branch (numPt <= 10) matches first
   pose_optimization(cur, map, &mpbv, FB_POSE_BIRD, 1.0f, 1.0f, FB_CNT_POSE1_INLIERS, false);   // BirdOptimization(&mCurrentFrame, 1.0)
   per_frame_matched_bird_points(cur, last, &mpbv, 0);            // :2056
+  return FB_OK;
+}
+
+// ---- the steps one by one (the counterparts of fb_frame_pose_optimization_dev, fb_frame_discard_outliers_dev and
+// fb_frame_search_local_points_dev), for tests that build the frame's associations themselves ----
+int orc_frame_pose_optimization(orc_frame *f, const fb_track_args *T, int which) {
+  fb_map_points_bird mpbv = T->mpb;
+  pose_optimization(f, &T->map, &mpbv, FB_POSE_FRONT_BIRD, T->wB, T->wF, which ? FB_CNT_POSE2_INLIERS : FB_CNT_POSE1_INLIERS);
+  return FB_OK;
+}
+
+// src_slot: the counter nmatches starts from; gate_min > 0: a sequence whose src_slot counter is below it returned before the loop
+int orc_frame_discard_outliers(orc_frame *f, const fb_track_args *T, int src_slot, int gate_min) {
+  if (src_slot < 0 || src_slot >= FB_CNT_COUNT) return FB_ERR_ARG;
+  discard_outliers(f, &T->map, src_slot, gate_min > 0, src_slot, gate_min);
+  return FB_OK;
+}
+
+int orc_frame_search_local_points(orc_frame *f, const fb_track_args *T) {
+  search_local_points(f, T, &T->map);
   return FB_OK;
 }
 
