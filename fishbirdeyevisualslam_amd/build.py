@@ -12,11 +12,11 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libfishbird_hip.so")
-SOURCES = ["runtime.hip", "match.hip", "match_bow.hip", "frame.hip", "track.hip", "bow.hip", "orb.hip", "pose.hip", "ba.hip", "mapping.hip", "kfdb.hip", "sim3_solver.hip", "covis.hip"]
+SOURCES = ["runtime.hip", "match.hip", "match_bow.hip", "frame.hip", "track.hip", "bow.hip", "orb.hip", "pose.hip", "ba.hip", "mapping.hip", "kfdb.hip", "sim3_solver.hip", "opt_sim3.hip", "covis.hip"]
 # Files whose results are held to a floating-point tolerance (poses: 1e-4 relative), not to bit equality with the
 # oracle: fused multiply-adds are allowed there.  An LM evaluation of k_pose_opt is ~75 % fp64 edge arithmetic that one
 # wave per SIMD issues back to back; mul + add pairs instead of fma made it a quarter longer.
-FMA_OK = {"pose.hip"}
+FMA_OK = {"pose.hip", "opt_sim3.hip"}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-fgpu-rdc=0" if False else "-Wall", "-Wno-unused-function"]
 

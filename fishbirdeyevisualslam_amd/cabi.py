@@ -208,6 +208,15 @@ class Sim3SolverArgs(C.Structure):
                 ("inlier_mask", _vp), ("workspace", _vp), ("workspace_bytes", C.c_size_t)]
 
 
+class OptimizeSim3Args(C.Structure):
+    _fields_ = [("n_cand", _i32), ("kf1", KfTarget), ("kf2", KfTarget), ("mp1", MpList), ("mp2", MpList),
+                ("T1w", _vp), ("T2w", _vp), ("kf2_index", _vp), ("inv_level_sigma2", _f32 * FB_MAX_LEVELS),
+                ("matches12", _vp), ("s12", _vp), ("R12", _vp), ("t12", _vp), ("hyp_stride", _i32), ("th2", _f32),
+                ("fix_scale", _i32), ("n_inliers", _vp), ("n_correspondences", _vp), ("n_bad", _vp),
+                ("q", _vp), ("t", _vp), ("s", _vp), ("scw_q", _vp), ("scw_t", _vp), ("scw_s", _vp), ("Scw", _vp),
+                ("workspace", _vp), ("workspace_bytes", C.c_size_t)]
+
+
 class InitMatchArgs(C.Structure):
     _fields_ = [("batch", _i32), ("f1_stride", _i32), ("f2_stride", _i32), ("n1", _vp), ("kps1", _vp), ("desc1", _vp),
                 ("n2", _vp), ("kps2", _vp), ("desc2", _vp), ("f2_cell_start", _vp), ("f2_cell_items", _vp),
@@ -431,6 +440,7 @@ EXPORTS = [
     "fb_distinctive_descriptors_dev", "fb_distinctive_descriptors",
     "fb_create_new_map_points_workspace", "fb_create_new_map_points_dev", "fb_create_new_map_points",
     "fb_sim3_solver_workspace", "fb_sim3_solver_dev", "fb_sim3_solver",
+    "fb_optimize_sim3_workspace", "fb_optimize_sim3_dev", "fb_optimize_sim3",
     "fb_bird_filter_matches_dev", "fb_bird_filter_matches", "fb_bow_transform_dev", "fb_bow_transform",
     "fb_bow_score_dev", "fb_bow_score", "fb_kfdb_create", "fb_kfdb_destroy", "fb_kfdb_clear", "fb_kfdb_add_dev", "fb_kfdb_add",
     "fb_kfdb_add_frame_dev", "fb_kfdb_erase", "fb_kfdb_query_dev", "fb_kfdb_query", "fb_kfdb_min_score_dev", "fb_kfdb_min_score",

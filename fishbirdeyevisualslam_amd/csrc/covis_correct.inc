@@ -61,7 +61,7 @@ void cl_layout(uint8_t *b, size_t K, size_t n_mp, size_t n_mpb, size_t BS, ClS *
   S->bnext = (int32_t *)take(K * BS * 4);
 }
 
-struct Sim3d { fb::Quat r; double t[3], s; };
+using fb::Sim3d; using fb::sim3_map; using fb::sim3_mul; using fb::sim3_inverse;  // g2o::Sim3 in double, fb_se3.h
 
 // Sim3(Matrix3d(R of a CV_32F pose), Vector3d(t), 1.0): Quaterniond(R) is not normalised (sim3.h:64)
 __device__ __forceinline__ Sim3d sim3_from_pose(const float *T) {
@@ -72,29 +72,6 @@ __device__ __forceinline__ Sim3d sim3_from_pose(const float *T) {
   S.s = 1.0;
   return S;
 }
-__device__ __forceinline__ void sim3_map(const Sim3d &S, const double x[3], double o[3]) {   // s*(r*xyz) + t, sim3.h:144
-  double rx[3];
-  fb::quat_rotate(S.r, x, rx);
-  o[0] = S.s * rx[0] + S.t[0]; o[1] = S.s * rx[1] + S.t[1]; o[2] = S.s * rx[2] + S.t[2];
-}
-__device__ __forceinline__ Sim3d sim3_mul(const Sim3d &a, const Sim3d &b) {                    // sim3.h:266
-  Sim3d r;
-  r.r = fb::quat_mul(a.r, b.r);
-  double rt[3];
-  fb::quat_rotate(a.r, b.t, rt);
-  r.t[0] = a.s * rt[0] + a.t[0]; r.t[1] = a.s * rt[1] + a.t[1]; r.t[2] = a.s * rt[2] + a.t[2];
-  r.s = a.s * b.s;
-  return r;
-}
-__device__ __forceinline__ Sim3d sim3_inverse(const Sim3d &a) {                                // sim3.h:233
-  Sim3d r;
-  r.r.x = -a.r.x; r.r.y = -a.r.y; r.r.z = -a.r.z; r.r.w = a.r.w;
-  const double f = -1. / a.s, nt[3] = {f * a.t[0], f * a.t[1], f * a.t[2]};
-  fb::quat_rotate(r.r, nt, r.t);
-  r.s = 1. / a.s;
-  return r;
-}
-
 // rows 0..2 of Twc as KeyFrame::SetPose leaves it (KeyFrame.cc:108-115): Rwc = Rcw.t(), Ow = -Rwc*tcw
 __device__ __forceinline__ void pose_inverse(const float *T, float *Twc) {
   float Ow[3];

@@ -224,20 +224,21 @@ __host__ __device__ inline void huber(double e, double delta, double &rho0, doub
   }
 }
 
-// Symmetric 6x6 solve, LDL^T without pivoting; false on a negative pivot
+// Symmetric N x N solve, LDL^T without pivoting; false on a negative pivot
 // (LinearSolverDense, solvers/linear_solver_dense.h:65-113: Eigen LDLT::isPositive()).
-__host__ __device__ inline bool ldlt6(const double H[36], double lambda, const double b[6], double x[6]) {
-  double A[36], d[6], dinv[6], y[6];
+template <int N>
+__host__ __device__ inline bool ldlt(const double *H, double lambda, const double *b, double *x) {
+  double A[N * N], d[N], dinv[N], y[N];
 #pragma unroll
-  for (int i = 0; i < 36; i++) A[i] = H[i];
+  for (int i = 0; i < N * N; i++) A[i] = H[i];
 #pragma unroll
-  for (int j = 0; j < 6; j++) A[j * 6 + j] += lambda;
+  for (int j = 0; j < N; j++) A[j * N + j] += lambda;
   bool ok = true;
 #pragma unroll
-  for (int j = 0; j < 6; j++) {
-    double dj = A[j * 6 + j];
+  for (int j = 0; j < N; j++) {
+    double dj = A[j * N + j];
 #pragma unroll
-    for (int k = 0; k < j; k++) dj -= A[j * 6 + k] * A[j * 6 + k] * d[k];
+    for (int k = 0; k < j; k++) dj -= A[j * N + k] * A[j * N + k] * d[k];
     if (dj < 0) ok = false;
     d[j] = dj;
     // one reciprocal per pivot: this routine runs on ONE lane inside every LM trial of k_pose_opt, and an fp64 division is
@@ -245,31 +246,108 @@ __host__ __device__ inline bool ldlt6(const double H[36], double lambda, const d
     const double inv = dj != 0 ? 1.0 / dj : 0.0;
     dinv[j] = inv;
 #pragma unroll
-    for (int i = j + 1; i < 6; i++) {
-      double s = A[i * 6 + j];
+    for (int i = j + 1; i < N; i++) {
+      double s = A[i * N + j];
 #pragma unroll
-      for (int k = 0; k < j; k++) s -= A[i * 6 + k] * A[j * 6 + k] * d[k];
-      A[i * 6 + j] = s * inv;
+      for (int k = 0; k < j; k++) s -= A[i * N + k] * A[j * N + k] * d[k];
+      A[i * N + j] = s * inv;
     }
   }
   if (!ok) return false;
 #pragma unroll
-  for (int i = 0; i < 6; i++) {
+  for (int i = 0; i < N; i++) {
     double s = b[i];
 #pragma unroll
-    for (int k = 0; k < i; k++) s -= A[i * 6 + k] * y[k];
+    for (int k = 0; k < i; k++) s -= A[i * N + k] * y[k];
     y[i] = s;
   }
 #pragma unroll
-  for (int i = 0; i < 6; i++) y[i] = y[i] * dinv[i];
+  for (int i = 0; i < N; i++) y[i] = y[i] * dinv[i];
 #pragma unroll
-  for (int i = 5; i >= 0; i--) {
+  for (int i = N - 1; i >= 0; i--) {
     double s = y[i];
 #pragma unroll
-    for (int k = i + 1; k < 6; k++) s -= A[k * 6 + i] * x[k];
+    for (int k = i + 1; k < N; k++) s -= A[k * N + i] * x[k];
     x[i] = s;
   }
   return true;
+}
+__host__ __device__ inline bool ldlt6(const double H[36], double lambda, const double b[6], double x[6]) { return ldlt<6>(H, lambda, b, x); }
+
+// ---- g2o::Sim3 (Thirdparty/g2o/g2o/types/sim3.h): a quaternion that is NOT renormalised, a translation and a scale
+struct Sim3d { Quat r; double t[3], s; };
+
+__host__ __device__ inline void sim3_map(const Sim3d &S, const double x[3], double o[3]) {   // s*(r*xyz) + t, sim3.h:144
+  double rx[3];
+  quat_rotate(S.r, x, rx);
+  o[0] = S.s * rx[0] + S.t[0]; o[1] = S.s * rx[1] + S.t[1]; o[2] = S.s * rx[2] + S.t[2];
+}
+__host__ __device__ inline Sim3d sim3_mul(const Sim3d &a, const Sim3d &b) {                    // sim3.h:266
+  Sim3d r;
+  r.r = quat_mul(a.r, b.r);
+  double rt[3];
+  quat_rotate(a.r, b.t, rt);
+  r.t[0] = a.s * rt[0] + a.t[0]; r.t[1] = a.s * rt[1] + a.t[1]; r.t[2] = a.s * rt[2] + a.t[2];
+  r.s = a.s * b.s;
+  return r;
+}
+__host__ __device__ inline Sim3d sim3_inverse(const Sim3d &a) {                                // sim3.h:233
+  Sim3d r;
+  r.r.x = -a.r.x; r.r.y = -a.r.y; r.r.z = -a.r.z; r.r.w = a.r.w;
+  const double f = -1. / a.s, nt[3] = {f * a.t[0], f * a.t[1], f * a.t[2]};
+  quat_rotate(r.r, nt, r.t);
+  r.s = 1. / a.s;
+  return r;
+}
+
+// Sim3(const Vector7d &update), sim3.h:70-142: (omega, upsilon, sigma) with the reference's small-angle and small-sigma
+// branches (eps = 0.00001, R = I + Omega + Omega^2 below it, sic); r = Quaterniond(R), not normalised
+__host__ __device__ inline Sim3d sim3_exp(const double u[7]) {
+  const double omega[3] = {u[0], u[1], u[2]}, ups[3] = {u[3], u[4], u[5]}, sigma = u[6];
+  const double theta = sqrt(omega[0] * omega[0] + omega[1] * omega[1] + omega[2] * omega[2]);
+  double Om[9], Om2[9], R[9];
+  skew3(omega, Om);
+  mat3_mul(Om, Om, Om2);
+  const double I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+  Sim3d S;
+  S.s = exp(sigma);
+  const double eps = 0.00001;
+  double A, B, C;
+  if (fabs(sigma) < eps) {
+    C = 1;
+    if (theta < eps) {
+      A = 1. / 2.; B = 1. / 6.;
+      for (int i = 0; i < 9; i++) R[i] = I[i] + Om[i] + Om2[i];
+    } else {
+      const double theta2 = theta * theta;
+      A = (1 - cos(theta)) / theta2;
+      B = (theta - sin(theta)) / (theta2 * theta);
+      const double a = sin(theta) / theta, b = (1 - cos(theta)) / (theta * theta);
+      for (int i = 0; i < 9; i++) R[i] = I[i] + a * Om[i] + b * Om2[i];
+    }
+  } else {
+    C = (S.s - 1) / sigma;
+    if (theta < eps) {
+      const double sigma2 = sigma * sigma;
+      A = ((sigma - 1) * S.s + 1) / sigma2;
+      B = ((0.5 * sigma2 - sigma + 1) * S.s) / (sigma2 * sigma);
+      for (int i = 0; i < 9; i++) R[i] = I[i] + Om[i] + Om2[i];
+    } else {
+      const double ra = sin(theta) / theta, rb = (1 - cos(theta)) / (theta * theta);
+      for (int i = 0; i < 9; i++) R[i] = I[i] + ra * Om[i] + rb * Om2[i];
+      const double a = S.s * sin(theta), b = S.s * cos(theta);
+      const double theta2 = theta * theta, sigma2 = sigma * sigma, c = theta2 + sigma2;
+      A = (a * sigma + (1 - b) * theta) / (theta * c);
+      B = (C - ((b - 1) * sigma + a * theta) / c) * 1. / theta2;
+    }
+  }
+  S.r = quat_from_R(R);
+  for (int i = 0; i < 3; i++) {
+    const double w0 = A * Om[i * 3] + B * Om2[i * 3] + C * I[i * 3], w1 = A * Om[i * 3 + 1] + B * Om2[i * 3 + 1] + C * I[i * 3 + 1],
+                 w2 = A * Om[i * 3 + 2] + B * Om2[i * 3 + 2] + C * I[i * 3 + 2];
+    S.t[i] = w0 * ups[0] + w1 * ups[1] + w2 * ups[2];
+  }
+  return S;
 }
 
 }  // namespace fb

@@ -19,7 +19,7 @@
 // LDL^T and the exponential-map update run on one lane.  Everything is fp64 like g2o;
 // inputs/outputs are float like the reference's cv::Mat fields.
 //
-// The schedule is written once (lm_optimize10 = optimize(10), pose_rounds = the four rounds with
+// The schedule is written once (fb::lm_optimize of fb_lm.h = optimize(n), pose_rounds = the four rounds with
 // the classification between them) and has two users that differ in where the edges live and in
 // the solve policy: k_pose_opt (pose_generic: edges in LDS or HBM, any number of them) and
 // k_pose_opt_regs<NT, NE, EF, EB> (edges in registers; NE = NT - 64 gives the solver a wave of its
@@ -30,15 +30,10 @@
 #include "fb_primitives.h"
 #include "fb_se3.h"
 
-namespace {
-
-constexpr int POSE_THREADS = 256;  // the LDS-staged kernel
-constexpr int NACC = 28;  // chi2, 21 x H upper, 6 x b
-
 // -DFB_POSE_STAMPS (profiles/probes/pose_stamps.py builds that variant on the GPU box): thread 0 of workgroup 0 adds the
 // shader-clock time of each phase of an LM evaluation to g_pose_stamps[]; compiled out of the product build.
 #ifdef FB_POSE_STAMPS
-__device__ unsigned long long g_pose_stamps[16];
+namespace { __device__ unsigned long long g_pose_stamps[16]; }
 #define POSE_T0() unsigned long long pt_ = 0; if (blockIdx.x == 0 && threadIdx.x == 0) { __builtin_amdgcn_sched_barrier(0); pt_ = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); }
 #define POSE_TICK(slot_) if (blockIdx.x == 0 && threadIdx.x == 0) { __builtin_amdgcn_sched_barrier(0); const unsigned long long t_ = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); g_pose_stamps[slot_] += t_ - pt_; pt_ = t_; }
 #define POSE_COUNT(slot_) if (blockIdx.x == 0 && threadIdx.x == 0) g_pose_stamps[slot_] += 1;
@@ -47,8 +42,18 @@ __device__ unsigned long long g_pose_stamps[16];
 #define POSE_TICK(slot_)
 #define POSE_COUNT(slot_)
 #endif
+// the LM schedule of fb_lm.h carries these stamps: its hooks are set before it is included
+#define FB_LM_T0() POSE_T0()
+#define FB_LM_TICK(slot_) POSE_TICK(slot_)
+#include "fb_lm.h"
 
-struct PoseLds {  // fixed-size shared state
+namespace {
+
+constexpr int POSE_THREADS = 256;  // the LDS-staged kernel
+constexpr int NACC = 28;  // chi2, 21 x H upper, 6 x b
+
+struct PoseLds {  // fixed-size shared state (the St of fb_lm.h)
+  static constexpr int DIM = 6;
   fb::SE3 T, Ttrial, Teval, T0;
   double H[36], b[6], x[6];
   double red[NACC];
@@ -193,13 +198,6 @@ __device__ void eval_pass(const EdgeView &E, const fb::SE3 &T, bool robust, doub
   }
   __syncthreads();
   POSE_TICK(3)
-}
-
-__device__ __forceinline__ void unpack_system(const double *red, double *H, double *b) {
-  int k = 1;
-  for (int i = 0; i < 6; i++)
-    for (int j = i; j < 6; j++) { H[i * 6 + j] = red[k]; H[j * 6 + i] = red[k]; k++; }
-  for (int i = 0; i < 6; i++) b[i] = red[22 + i];
 }
 
 // chi2 of one edge at pose T for the inlier / outlier decision (computeError + chi2(), base_edge.h:58-61; compared as
@@ -422,74 +420,6 @@ struct SolveFast {
   static __device__ __forceinline__ fb::SE3 oplus(const double *x, const fb::SE3 &T) { return se3_mul_fast(se3_exp_direct(x), T); }
 };
 
-// optimize(10) of OptimizationAlgorithmLevenberg from the pose in S.T.  eval(T, robust) leaves the 28 sums of the active
-// edges at pose T in S.red and ends in a barrier; `solver` is true in the one thread that solves and moves S.T.  Every
-// thread of the workgroup calls this and keeps the same lambda / rho / chi2 from the shared sums, so all of them reach
-// every barrier.
-template <class Solve, class Eval>
-__device__ __forceinline__ void lm_optimize10(PoseLds &S, bool solver, bool robust, Eval &eval) {
-  eval(S.T, robust);
-  if (solver) { unpack_system(S.red, S.H, S.b); S.Teval = S.T; }
-  double currentChi = S.red[0];
-  __syncthreads();
-  double lambda = 0, ni = 2;
-  int nBadLM = 0;
-  for (int iter = 0; iter < 10; iter++) {
-    const double iniChi = currentChi;
-    if (iter == 0) {
-      double m = 0;
-      for (int j = 0; j < 6; j++) m = fmax(fabs(S.H[j * 6 + j]), m);
-      lambda = 1e-5 * m;
-      ni = 2;
-      nBadLM = 0;
-    }
-    double rho = 0;
-    int qmax = 0;
-    do {
-      {
-        POSE_T0()
-        if (solver) {
-          S.ok2 = Solve::solve(S.H, lambda, S.b, S.x) ? 1 : 0;
-          POSE_TICK(4)
-          S.Ttrial = Solve::oplus(S.x, S.T);
-          S.Teval = S.Ttrial;
-          POSE_TICK(5)
-        }
-        __syncthreads();
-        POSE_TICK(6)
-      }
-      eval(S.Ttrial, robust);
-      double tempChi = S.red[0];
-      if (!S.ok2) tempChi = 1.7976931348623157e308;
-      rho = currentChi - tempChi;
-      double scale = 0;
-      for (int j = 0; j < 6; j++) scale += S.x[j] * (lambda * S.x[j] + S.b[j]);
-      scale += 1e-3;
-      rho /= scale;
-      const bool accept = rho > 0 && isfinite(tempChi);
-      __syncthreads();  // everyone has read red/x/b
-      if (accept) {
-        double alpha = 1. - pow((2 * rho - 1), 3);
-        alpha = fmin(alpha, 2. / 3.);
-        const double scaleFactor = fmax(1. / 3., alpha);
-        lambda *= scaleFactor;
-        ni = 2;
-        currentChi = tempChi;
-        if (solver) { S.T = S.Ttrial; unpack_system(S.red, S.H, S.b); }
-      } else {
-        lambda *= ni;
-        ni *= 2;
-      }
-      __syncthreads();
-      qmax++;
-    } while (rho < 0 && qmax < 10);
-    if (qmax == 10 || rho == 0) break;  // Terminate
-    if ((iniChi - currentChi) * 1e3 < iniChi) nBadLM++;
-    else nBadLM = 0;
-    if (nBadLM >= 3) break;
-  }
-}
-
 // workgroup totals of the bad edges a round found: the first NW waves hold edges (`counts` is false in the others)
 template <int NW>
 __device__ __forceinline__ void sum_bad(PoseLds &S, bool counts, int bad, int badb, int &nBad, int &nBadBird) {
@@ -507,7 +437,7 @@ __device__ __forceinline__ void sum_bad(PoseLds &S, bool counts, int bad, int ba
 
 // The four rounds of Optimizer.cc:385-465 / 614-690 / 782-825 around optimize(10), from the pose in S.T0 to the result in
 // Tcw / ninliers.  The edge storage stays with the caller: active() = this thread has a level-0 edge, eval as in
-// lm_optimize10, classify(nBad, nBadBird) sets every edge's level and outlier flag from its chi2 and leaves the
+// fb::lm_optimize, classify(nBad, nBadBird) sets every edge's level and outlier flag from its chi2 and leaves the
 // workgroup's counts (it ends in sum_bad).
 template <class Solve, class Active, class Eval, class Classify>
 __device__ __forceinline__ void pose_rounds(const fb_pose_opt_args &A, PoseLds &S, bool solver, int nf, int nb, Active &active,
@@ -517,7 +447,7 @@ __device__ __forceinline__ void pose_rounds(const fb_pose_opt_args &A, PoseLds &
     const bool robust = it < 3;   // setRobustKernel(0) after the third round (Optimizer.cc:657,685)
     if (solver) S.T = S.T0;       // vSE3->setEstimate(toSE3Quat(pFrame->mTcw))
     // active edges = level 0 (initializeOptimization(0)); the barrier also publishes S.T
-    if (__syncthreads_count(active()) > 0) lm_optimize10<Solve>(S, solver, robust, eval);
+    if (__syncthreads_count(active()) > 0) fb::lm_optimize<true>(S, Solve{}, solver, robust, eval, 10);  // optimize(10), fb_lm.h
     classify(nBad, nBadBird);     // Optimizer.cc:396-431, 627-686, 791-822
     if (nf + nb < 10) break;      // optimizer.edges().size()<10
   }

@@ -427,8 +427,23 @@ class ORBmatcher {
 };
 
 // ---- Optimizer ---------------------------------------------------------------------------------------------------
+struct Sim3KeyFrame;               // (below, with Sim3Solver)
+struct Sim3 {                      // g2o::Sim3's own members
+  double q[4] = {0, 0, 0, 1};      // r (x, y, z, w), not normalised
+  double t[3] = {0, 0, 0};
+  double s = 1;
+};
+
 class Optimizer {
  public:
+  // Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale) (Optimizer.cc:1560-1775) as LoopClosing.cc:341-368
+  // calls it: R12 / t12 / s12 are pSolver->GetEstimated*() and gScm = Sim3(R, t, s) is built from them as at :357.
+  // vnMatches1[i1] = feature of pKF2 whose MapPoint is vpMatches1[i1], or -1 (fb_match_sim3's matches12); entries the
+  // reference nulls become -1.  g2oS12 receives the optimised Sim3 (the input one when 0 is returned); mg2oScw = gScm * gSmw
+  // (:364-366) and Scw (rows 0..2 of Converter::toCvMat(mg2oScw), 12 floats) are filled when given.  Returns nInliers.
+  static int OptimizeSim3(const Sim3KeyFrame &kf1, const Sim3KeyFrame &kf2, std::vector<int32_t> &vnMatches1, const float *R12,
+                          const float *t12, float s12, Sim3 &g2oS12, float th2, bool bFixScale, const float *mvInvLevelSigma2,
+                          int nLevels, Sim3 *mg2oScw = nullptr, float *Scw = nullptr);
   // points[i] / birdPoints[i] describe pFrame->mvpMapPoints[i] / mvpMapPointsBird[i]
   static int PoseOptimization(Frame *f, const std::vector<MapPointRef> &points) {
     return run(f, FB_POSE_FRONT, points, {}, 1.f, 1.f);
@@ -1136,6 +1151,38 @@ class Sim3Solver {
   std::vector<uint8_t> accept_;
   std::vector<uint32_t> mask_;
 };
+
+inline int Optimizer::OptimizeSim3(const Sim3KeyFrame &kf1, const Sim3KeyFrame &kf2, std::vector<int32_t> &vnMatches1, const float *R12,
+                                   const float *t12, float s12, Sim3 &g2oS12, float th2, bool bFixScale,
+                                   const float *mvInvLevelSigma2, int nLevels, Sim3 *mg2oScw, float *Scw) {
+  if ((int)vnMatches1.size() != kf1.N || kf1.N < 1 || kf2.N < 1)
+    throw std::runtime_error("OptimizeSim3: vpMatches1.size() must equal pKF1->N, and both key frames need features");
+  const int32_t n1 = kf1.N;
+  int32_t nIn = 0, nCorr = 0, nBad = 0;
+  Sim3 scw;
+  float scwRows[12];
+  fb_optimize_sim3_args a;
+  memset(&a, 0, sizeof(a));
+  a.n_cand = 1;
+  a.kf1.kf_stride = kf1.N; a.kf1.n_kf = &n1; a.kf1.kf_kps = kf1.mvKeysUn;
+  a.kf2.kf_stride = kf2.N; a.kf2.kf_kps = kf2.mvKeysUn;
+  a.kf1.cam.fx = kf1.fx; a.kf1.cam.fy = kf1.fy; a.kf1.cam.cx = kf1.cx; a.kf1.cam.cy = kf1.cy;
+  a.kf2.cam.fx = kf2.fx; a.kf2.cam.fy = kf2.fy; a.kf2.cam.cx = kf2.cx; a.kf2.cam.cy = kf2.cy;
+  a.mp1.mp_stride = kf1.N; a.mp1.mp_valid = kf1.mpValid; a.mp1.mp_xw = kf1.mpWorldPos;
+  a.mp2.mp_stride = kf2.N; a.mp2.mp_valid = kf2.mpValid; a.mp2.mp_xw = kf2.mpWorldPos;
+  a.T1w = kf1.Tcw; a.T2w = kf2.Tcw; a.kf2_index = kf2.indexInKeyFrame;
+  for (int l = 0; l < FB_MAX_LEVELS; l++) a.inv_level_sigma2[l] = l < nLevels ? mvInvLevelSigma2[l] : 0.0f;
+  a.matches12 = vnMatches1.data();
+  a.s12 = &s12; a.R12 = R12; a.t12 = t12; a.hyp_stride = 1;
+  a.th2 = th2; a.fix_scale = bFixScale ? 1 : 0;
+  a.n_inliers = &nIn; a.n_correspondences = &nCorr; a.n_bad = &nBad;
+  a.q = g2oS12.q; a.t = g2oS12.t; a.s = &g2oS12.s;
+  a.scw_q = scw.q; a.scw_t = scw.t; a.scw_s = &scw.s; a.Scw = scwRows;
+  check(fb_optimize_sim3(&a));
+  if (mg2oScw) *mg2oScw = scw;
+  if (Scw) memcpy(Scw, scwRows, sizeof(scwRows));
+  return nIn;
+}
 
 }  // namespace fishbird
 #endif

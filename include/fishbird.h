@@ -738,6 +738,66 @@ size_t fb_sim3_solver_workspace(int n_cand, int n1_stride);
 int fb_sim3_solver_dev(const fb_sim3_solver_args *args, void *stream);  /* no host synchronisation */
 int fb_sim3_solver(const fb_sim3_solver_args *args);                    /* host pointers */
 
+/* Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale) (src/Optimizer.cc:1560-1775; called at
+ * LoopClosing.cc:341-360) for every candidate pKF2 of one pKF1 in one call, followed by mg2oScw = gScm * gSmw
+ * (LoopClosing.cc:364-368).  kf1 / kf2 / mp1 / mp2 / T1w / T2w / kf2_index mean what they mean in fb_sim3_solver_args;
+ * additionally kf_kps holds mvKeysUn's pt (the edges' measurements).  MONOCULAR: cam is fx, fy, cx, cy.
+ * The seams of the reference, as implemented:
+ *  - correspondence i1 is SKIPPED, and not counted in nCorrespondences, when matches12[i1] < 0, when pMP1 =
+ *    GetMapPointMatches()[i1] is NULL or bad (mp1.mp_valid), when pMP2 is bad (mp2.mp_valid[matches12[i1]]), or when
+ *    i2 = pMP2->GetIndexInKeyFrame(pKF2) < 0 (:1615-1650).  MEMORY SAFETY, not in the reference: matches12[i1] or i2 >= the KF2
+ *    stride, or an octave (of mvKeysUn[i1] / pKF2->mvKeysUn[i2]) outside [0, FB_MAX_LEVELS), also skips; such a value is
+ *    never used as an index.
+ *  - P3Dc = R*Xw + t is a CV_32F product, ((r0*X + r1*Y) + r2*Z) + t without FMA (:1632,:1640), then widened to double;
+ *    deltaHuber = sqrt(th2) is a float; invSigmaSquare is a float widened into the information matrix.
+ *  - gScm = Sim3(toMatrix3d(R12), toVector3d(t12), s12): Quaterniond(R) in double from the floats, not normalised.
+ *  - round 1 is optimize(5); a pair is bad if e12.chi2() > th2 || e21.chi2() > th2 (double chi2 against the float widened);
+ *    bad pairs leave the graph and matches12[i1] = -1; nMoreIterations = nBad > 0 ? 10 : 5.
+ *  - nCorrespondences - nBad < 10 returns 0: matches12 keeps the round-1 nulls and g2oS12 is NOT written back (:1745), so
+ *    q / t / s hold the INPUT Sim3 and scw_* / Scw follow from it.  nCorrespondences == 0 returns 0 without a solve.
+ *  - round 2 is initializeOptimization(); optimize(nMoreIterations) with a fresh lambda; the final check nulls matches12
+ *    but removes nothing; n_inliers counts the rest.
+ *  - the edges have no linearizeOplus (types_seven_dof_expmap.h:147,169), so the Jacobian is g2o's NUMERIC one: central
+ *    differences with delta = 1e-9 through oplus on the Sim3 vertex (base_binary_edge.hpp:147-173).  oplusImpl zeroes
+ *    update[6] IN the solver's x when fix_scale (types_seven_dof_expmap.h:60-70): column 6 of J is then exactly 0 and only
+ *    the LM damping makes the 7x7 system regular.  LM is OptimizationAlgorithmLevenberg with LinearSolverDense.
+ * Pointers are DEVICE pointers for _dev.                                                                            */
+typedef struct fb_optimize_sim3_args {
+  int32_t n_cand;                 /* candidates pKF2 of this call, >= 1                                       */
+  fb_kf_target kf1;               /* pKF1, batch 1. Read: kf_stride, n_kf (= vpMatches1.size()), kf_kps, cam    */
+  fb_kf_target kf2;               /* the candidates, batch n_cand. Read: kf_stride, kf_kps, cam                 */
+  fb_mp_list mp1;                 /* per KF1 feature (mp_stride == kf1.kf_stride): mp_valid = pMP1 && !isBad(), mp_xw */
+  fb_mp_list mp2;                 /* per feature of each candidate ([n_cand][kf2 stride]): mp_valid = !isBad(), mp_xw */
+  const float *T1w;               /* [12] pKF1 GetRotation | GetTranslation, row-major 3x4                    */
+  const float *T2w;               /* [n_cand][12]                                                            */
+  const int32_t *kf2_index;       /* [n_cand][kf2 stride] pMP2->GetIndexInKeyFrame(pKF2), or NULL = the slot */
+  float inv_level_sigma2[FB_MAX_LEVELS]; /* mvInvLevelSigma2 (both key frames)                                */
+  int32_t *matches12;             /* IN/OUT [n_cand][kf1 stride]: KF2 feature whose point is vpMatches1[i1], or -1 (what
+                                     fb_match_sim3 / fb_match_bow_kf write); set to -1 where the reference nulls vpMatches1 */
+  const float *s12;               /* the input Sim3 of candidate c: s12[c * hyp_stride],                      */
+  const float *R12;               /*   R12 + 9 * c * hyp_stride,                                              */
+  const float *t12;               /*   t12 + 3 * c * hyp_stride                                               */
+  int32_t hyp_stride;             /* 1 (or 0) = dense [n_cand] arrays as in fb_sim3_args; FB_SIM3_MAX_HYP = &s[0][k],
+                                     &R[0][k][0], &t[0][k][0] of fb_sim3_solver's tables: row k of every candidate */
+  float th2;                      /* 10 at LoopClosing.cc:360                                                */
+  int32_t fix_scale;              /* mbFixScale                                                              */
+  /* outputs per candidate */
+  int32_t *n_inliers;             /* [n_cand] the return value                                               */
+  int32_t *n_correspondences;     /* [n_cand] nCorrespondences                                               */
+  int32_t *n_bad;                 /* [n_cand] nBad of the first round                                        */
+  double *q, *t, *s;              /* [n_cand][4] (x, y, z, w), [n_cand][3], [n_cand]: g2oS12 on return        */
+  double *scw_q, *scw_t, *scw_s;  /* mg2oScw = gScm * Sim3(R2w, t2w, 1): the q / t / s of fb_correct_loop_args */
+  float *Scw;                     /* [n_cand][12] Converter::toCvMat(mg2oScw) rows 0..2, [s*R | t]: the Scw of
+                                     fb_proj_sim3_args and the pose of fb_fuse_args (Sim3 variant)            */
+  /* device scratch of fb_optimize_sim3_workspace(n_cand, kf1 stride) bytes, 16-byte aligned, private to the call until it
+   * has finished on `stream` (_dev only; the host drop-in allocates its own)                                        */
+  void *workspace;
+  size_t workspace_bytes;
+} fb_optimize_sim3_args;
+size_t fb_optimize_sim3_workspace(int n_cand, int kf1_stride);
+int fb_optimize_sim3_dev(const fb_optimize_sim3_args *args, void *stream);  /* enqueues only: no host synchronisation */
+int fb_optimize_sim3(const fb_optimize_sim3_args *args);                    /* host pointers */
+
 /* ======================================================================== */
 /* DBoW2 vocabulary transform (Frame::ComputeBoW, src/Frame.cc:628-635)       */
 /* ======================================================================== */

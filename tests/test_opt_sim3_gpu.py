@@ -1,0 +1,289 @@
+"""fb_optimize_sim3_dev / fb_optimize_sim3 on the device against the literal model of Optimizer::OptimizeSim3
+(tests/opt_sim3_ref.py).
+
+Measured on one MI355X over PARITY (worst difference of the device against the model, 15 candidates, none razor): MEASURED
+below.  The bounds are 10 x the measured values (room for other seeds) and stay inside the project's 1e-4 parity definition.
+The numeric Jacobian multiplies the rounding of two projections by 1 / (2e-9), so the two sides differ by more than the 1e-8
+of the pose optimisation; Scw is one float ulp at magnitude 2..4.
+RAZOR_GAP is the relative chi2 change the bounded Sim3 difference can cause: a mapped point moves by at most
+dP = TOL[t] max(1, |t|) + |P| (2 TOL[q] + TOL[s]) <= 6.93e-7 * 6 + 25 * (3.8e-8 + 9.6e-8) = 7.6e-6 m, a projection by
+(f / z_min) (1 + |x / z|) dP <= 500 / 3 * 1.3 * 7.6e-6 = 1.6e-3 px, and chi2 at the threshold (|e| sqrt(info) = sqrt(10)) by
+2 * 1.6e-3 / 3.16 = 1e-3 relative.  The smallest gap of the parity set is 0.24."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import opt_sim3_ref as R
+from fishbirdeyevisualslam_amd import cabi, opt_sim3_problem as OP
+
+pytestmark = pytest.mark.gpu
+
+# worst differences measured on the GPU over PARITY (q up to sign absolute, t over max(1, |t|), s relative, Scw absolute)
+MEASURED = dict(q=1.9e-9, t=6.93e-8, s=9.6e-9, scw_q=1.81e-9, scw_t=2.17e-8, scw_s=9.6e-9, Scw=2.38e-7)
+TOL = {k: 10 * v for k, v in MEASURED.items()}
+PARITY, RAZOR_GAP, RAZOR_SHARE_CAP = OP.PARITY, OP.RAZOR_GAP, OP.RAZOR_SHARE_CAP
+
+
+def _to_dev(a, keep, out):
+    import torch
+    d = {}
+    for sub, field, key in OP.INPUT_FIELDS:
+        v = keep[key]
+        d[key] = torch.from_numpy(np.ascontiguousarray(v.view(np.uint8) if v.dtype == cabi.KP_DTYPE else v).copy()).to("cuda:0")
+        tgt = a if sub is None else getattr(a, sub)
+        if getattr(tgt, field):
+            cabi.fill(tgt, **{field: d[key]})
+    for k in OP.OUTPUT_FIELDS:
+        d[k] = torch.from_numpy(out[k].copy()).to("cuda:0")
+        cabi.fill(a, **{k: d[k]})
+    return d
+
+
+def _run_dev(p, tweak=None, **kw):
+    import torch
+    import fishbirdeyevisualslam_amd as fb
+    a, out, keep = OP.optimize_args(p, **kw)
+    d = _to_dev(a, keep, out)
+    lib = fb.lib()
+    lib.fb_optimize_sim3_workspace.restype = C.c_size_t
+    wsb = lib.fb_optimize_sim3_workspace(a.n_cand, a.kf1.kf_stride)
+    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device="cuda:0")
+    cabi.fill(a, workspace=ws, workspace_bytes=wsb)
+    if tweak:
+        tweak(a)
+    rc = lib.fb_optimize_sim3_dev(C.byref(a), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    torch.cuda.synchronize()
+    return rc, {k: d[k].cpu().numpy() for k in OP.OUTPUT_FIELDS}
+
+
+def _diffs(got, c, m):
+    """-> the difference of candidate c per quantity"""
+    out = {}
+    for k in ("q", "scw_q"):
+        a, b = got[k][c], m[k]
+        out[k] = float(min(np.abs(a - b).max(), np.abs(a + b).max()))
+    for k in ("t", "scw_t"):
+        out[k] = float(np.abs(got[k][c] - m[k]).max() / max(1.0, float(np.linalg.norm(m[k]))))
+    for k in ("s", "scw_s"):
+        out[k] = abs(float(got[k][c]) - m[k]) / abs(m[k])
+    out["Scw"] = float(np.abs(got["Scw"][c].astype(np.float64) - m["Scw"].astype(np.float64)).max())
+    return out
+
+
+def _check(p, got, worst, counts, **kw):
+    for c in range(p["C"]):
+        m = R.optimize_sim3(p, c, **kw)
+        assert int(got["n_correspondences"][c]) == m["n_correspondences"], c
+        razor = [i1 for i1, g in m["pair_gap"].items() if g < RAZOR_GAP]
+        counts[0] += 1
+        diff = np.nonzero(got["matches12"][c] != m["matches12"])[0]
+        if razor:
+            counts[1] += 1
+            assert set(diff.tolist()) <= set(razor), "candidate %d differs outside its razor pairs" % c
+            assert abs(int(got["n_bad"][c]) - m["n_bad"]) <= len(razor) and abs(int(got["n_inliers"][c]) - m["n_inliers"]) <= len(razor)
+            continue
+        assert len(diff) == 0, (c, diff)
+        assert int(got["n_bad"][c]) == m["n_bad"] and int(got["n_inliers"][c]) == m["n_inliers"], c
+        for k, v in _diffs(got, c, m).items():
+            worst[k] = max(worst[k], v)
+        worst["gap"] = min(worst["gap"], m["min_gap"])
+
+
+def test_parity_with_the_literal_model():
+    worst = dict(q=0.0, t=0.0, s=0.0, scw_q=0.0, scw_t=0.0, scw_s=0.0, Scw=0.0, gap=np.inf)
+    counts = [0, 0]
+    for seed, n_corr, kw in PARITY:
+        p = OP.make_problem(seed, n_corr, **kw)
+        rc, got = _run_dev(p)
+        assert rc == 0
+        _check(p, got, worst, counts)
+    print("opt_sim3 parity: worst " + " ".join("%s %.3g" % kv for kv in worst.items()) + "; razor candidates %d of %d" % (counts[1], counts[0]))
+    assert counts[1] <= RAZOR_SHARE_CAP * counts[0]
+    for k, tol in TOL.items():
+        assert worst[k] <= tol <= 1e-4, (k, worst[k])
+
+
+def test_gate_below_ten_keeps_the_input_sim3_and_the_round_one_nulls():
+    p = OP.make_problem(14, [11, 63, 11], n1=150, n2=170, n_outliers=[0, 0, 3])
+    rc, got = _run_dev(p)
+    assert rc == 0
+    cd = p["cands"][2]
+    g_in = R.Sim3.from_R(np.asarray(cd["R12"], np.float64).reshape(3, 3).tolist(), [float(v) for v in cd["t12"]], float(cd["s12"]))
+    assert int(got["n_inliers"][2]) == 0 and int(got["n_bad"][2]) >= 2
+    np.testing.assert_array_equal(got["q"][2], np.array(g_in.r))
+    np.testing.assert_array_equal(got["t"][2], np.array(g_in.t))
+    assert float(got["s"][2]) == g_in.s
+    assert (got["matches12"][2] != cd["matches12"]).sum() == int(got["n_bad"][2])
+
+
+def test_fixed_scale_leaves_s_at_its_input():
+    p = OP.make_problem(17, [150, 40], n1=333, n2=301, n_outliers=[10, 0], fix_scale=1)
+    rc, got = _run_dev(p)
+    assert rc == 0 and (got["n_inliers"] > 0).all()
+    assert got["s"].tolist() == [1.0, 1.0]
+
+
+def test_null_index_array_is_the_slot_and_rows_of_the_solver_tables_are_read_by_stride():
+    p = OP.make_problem(19, [80, 70], n1=200, n2=210, n_outliers=[4, 0], plants=("noindex2", "bigindex2"))
+    worst = dict(q=0.0, t=0.0, s=0.0, scw_q=0.0, scw_t=0.0, scw_s=0.0, Scw=0.0, gap=np.inf)
+    rc, got = _run_dev(p, with_index=False, hyp_stride=cabi.FB_SIM3_MAX_HYP)
+    assert rc == 0 and got["n_correspondences"].tolist() == [82, 72]   # the two index plants are kept now
+    _check(p, got, worst, [0, 0], with_index=False)
+    for k, tol in TOL.items():
+        assert worst[k] <= tol, (k, worst[k])
+
+
+def test_key_frame_too_large_for_lds_reads_the_workspace():
+    """3000 features are 156 000 B of columns, above what the kernel may take of a CU's LDS: the global-memory variant."""
+    p = OP.make_problem(20, [150], n1=3000, n2=600, n_outliers=[9])
+    worst = dict(q=0.0, t=0.0, s=0.0, scw_q=0.0, scw_t=0.0, scw_s=0.0, Scw=0.0, gap=np.inf)
+    rc, got = _run_dev(p)
+    assert rc == 0
+    _check(p, got, worst, [0, 0])
+    for k, tol in TOL.items():
+        assert worst[k] <= tol, (k, worst[k])
+    rc, got = _run_dev(p, tweak=lambda a: setattr(a, "workspace_bytes", 16))
+    assert rc == cabi.FB_ERR_ARG and (got["n_inliers"] == -7).all()
+
+
+def test_non_finite_candidate_keeps_its_input_sim3():
+    """A NaN map point makes the 7x7 system non-finite on the first step: no trial is accepted (as in g2o, where every
+    comparison with NaN is false) and the Sim3 stays at its input; the candidate beside it is untouched by it."""
+    p = OP.make_problem(21, [40, 40], n1=120, n2=130)
+    i1 = int(p["truth"][0]["i1"][3])
+    j2 = int(p["cands"][0]["matches12"][i1])
+    p["cands"][0]["xw2"][j2, 0] = np.nan
+    rc, got = _run_dev(p)
+    assert rc == 0
+    m = [R.optimize_sim3(p, c) for c in range(2)]
+    for k in ("n_correspondences", "n_bad", "n_inliers"):   # NaN > th2 is false: nothing is nulled, every pair counts
+        assert int(got[k][0]) == m[0][k], k
+    assert int(got["n_correspondences"][0]) == 40 and np.array_equal(got["matches12"][0], m[0]["matches12"])
+    np.testing.assert_array_equal(got["q"][0], m[0]["q"])   # the input, bit for bit
+    np.testing.assert_array_equal(got["t"][0], m[0]["t"])
+    assert float(got["s"][0]) == m[0]["s"]
+    assert int(got["n_inliers"][1]) == m[1]["n_inliers"] and np.array_equal(got["matches12"][1], m[1]["matches12"])
+
+
+def test_host_drop_in_is_byte_equal_to_dev():
+    import fishbirdeyevisualslam_amd as fb
+    p = OP.make_problem(11, [150, 30], n1=333, n2=301, n_outliers=[12, 0], plants=OP.PLANTS)
+    rc, got = _run_dev(p)
+    assert rc == 0
+    a, out, keep = OP.optimize_args(p)
+    assert fb.lib().fb_optimize_sim3(C.byref(a)) == 0, fb.lib().fb_last_error()
+    for k in OP.OUTPUT_FIELDS:
+        assert out[k].tobytes() == np.ascontiguousarray(got[k]).tobytes(), k
+
+
+def test_bad_arguments_are_rejected_before_any_launch():
+    p = OP.make_problem(22, [30], n1=100, n2=100)
+    for tweak in (lambda a: setattr(a, "n_cand", 0), lambda a: setattr(a, "s12", None), lambda a: setattr(a.mp1, "mp_stride", 99),
+                  lambda a: setattr(a, "Scw", None), lambda a: setattr(a, "hyp_stride", -1)):
+        rc, got = _run_dev(p, tweak=tweak)
+        assert rc == cabi.FB_ERR_ARG and (got["n_inliers"] == -7).all()
+
+
+def _on_device(struct, arrays, hold):
+    import torch
+    for k, v in arrays.items():
+        t = torch.from_numpy(np.ascontiguousarray(v.view(np.uint8) if v.dtype == cabi.KP_DTYPE else v).copy()).to("cuda:0")
+        hold.append(t)
+        cabi.fill(struct, **{k: t})
+        arrays[k] = t
+
+
+def test_verification_block_of_compute_sim3_is_one_stream_of_dev_calls():
+    """fb_sim3_solver_dev -> fb_match_sim3_dev -> fb_optimize_sim3_dev -> fb_match_projection_sim3_dev on one stream with one
+    synchronisation at the end: the first hypothesis row of the solver's tables is passed by pointer (hyp_stride =
+    FB_SIM3_MAX_HYP), SearchBySim3's matches12 is OptimizeSim3's in/out array where it lies, and the Scw it writes is
+    SearchByProjection's input without the host seeing it.  The final match_kf_to_mp / nmatches equal the same chain with the
+    literal model's Scw substituted (the model runs on the downloaded matches and hypothesis; the problem is not razor)."""
+    import torch
+    import fishbirdeyevisualslam_amd as fb
+    import oracle_lib as O
+    from fishbirdeyevisualslam_amd import kf_problems as KP, more_problems as M, problems as P, sim3_problem as SP, synth
+    lib = fb.lib()
+    MAXH = cabi.FB_SIM3_MAX_HYP
+    n1, n2 = 700, 650
+    q = KP.make_sim3_problem(8400, n1, n2, 450)
+    geom = P.grid_geom(synth.front_grid_geom(KP.W, KP.H))
+    g1 = P.build_grid_host([q["kps1"]], geom, O.grid_build, n1)
+    g2 = P.build_grid_host([q["kps2"]], geom, O.grid_build, n2)
+    sig2 = np.asarray(synth.scale_tables()[2], np.float32)
+    inv_sig2 = np.asarray(synth.scale_tables()[3], np.float32)
+    # SearchByBoW's matches (host call, before the chain) are the solver's input
+    bp = dict(kps1=q["kps1"], desc1=q["desc1"], has_mp1=q["mp_valid1"], kps2=q["kps2"], desc2=q["desc2"], has_mp2=q["mp_valid2"])
+    ab, ob, _kb = M.bow_kf_args([bp])
+    assert lib.fb_match_bow_kf(C.byref(ab)) == 0, lib.fb_last_error()
+    sp = dict(C=1, n1=n1, n2=n2, kps1=q["kps1"], valid1=q["mp_valid1"], index1=np.arange(n1, dtype=np.int32), xw1=q["mp_xw1"], T1=q["T1w"],
+              cands=[dict(kps2=q["kps2"], valid2=q["mp_valid2"], index2=np.arange(n2, dtype=np.int32), xw2=q["mp_xw2"], T2=q["T2w"],
+                          matches12=ob["matches12"][0].copy())],
+              level_sigma2=sig2, fix_scale=1, fx=KP.FX, fy=KP.FY, cx=KP.W / 2.0, cy=KP.H / 2.0, ransac_prob=0.99, min_inliers=20,
+              max_iterations=MAXH)
+    N = SP.count_kept(sp, 0)
+    assert N >= 20
+    sp["rand_idx"] = SP.random_int_table(np.random.default_rng(8401), N)[None]
+    hold = []
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    # 1. the solver
+    a1, o1, k1 = SP.solver_args(sp, with_index=False)
+    for sub, field, key in SP.INPUT_FIELDS:
+        tgt = a1 if sub is None else getattr(a1, sub)
+        if key in k1 and getattr(tgt, field):
+            _on_device(tgt, {field: k1[key]}, hold)
+    d1 = {k: v for k, v in o1.items()}
+    d1["corr"] = o1["corr"].view(np.uint8)
+    _on_device(a1, d1, hold)
+    lib.fb_sim3_solver_workspace.restype = C.c_size_t
+    ws1 = torch.empty(max(lib.fb_sim3_solver_workspace(1, n1), 16), dtype=torch.uint8, device="cuda:0")
+    cabi.fill(a1, workspace=ws1, workspace_bytes=ws1.numel())
+    assert lib.fb_sim3_solver_dev(C.byref(a1), st) == 0, lib.fb_last_error()
+    # 2. SearchBySim3 with row 0 of the tables
+    a2, o2, (kk1, kk2, mk1, mk2, k2) = KP.sim3_args([q], g1, g2)
+    for struct, arrays in ((a2.kf1, kk1), (a2.kf2, kk2), (a2.mp1, mk1), (a2.mp2, mk2), (a2, k2), (a2, o2)):
+        _on_device(struct, arrays, hold)
+    cabi.fill(a2, s12=d1["s"].data_ptr(), R12=d1["R"].data_ptr(), t12=d1["t"].data_ptr())
+    assert lib.fb_match_sim3_dev(C.byref(a2), st) == 0, lib.fb_last_error()
+    # 3. OptimizeSim3 on the matcher's key-frame blocks, its matches12 and the same row
+    a3 = cabi.OptimizeSim3Args()
+    o3 = dict(n_inliers=np.full(1, -7, np.int32), n_correspondences=np.full(1, -7, np.int32), n_bad=np.full(1, -7, np.int32),
+              q=np.full((1, 4), -7.0), t=np.full((1, 3), -7.0), s=np.full(1, -7.0), scw_q=np.full((1, 4), -7.0), scw_t=np.full((1, 3), -7.0),
+              scw_s=np.full(1, -7.0), Scw=np.full((1, 12), -7.0, np.float32))
+    _on_device(a3, o3, hold)
+    a3.kf1, a3.kf2, a3.mp1, a3.mp2 = a2.kf1, a2.kf2, a2.mp1, a2.mp2
+    cabi.fill(a3, n_cand=1, T1w=k2["T1w"], T2w=k2["T2w"], matches12=o2["matches12"], s12=d1["s"].data_ptr(), R12=d1["R"].data_ptr(),
+              t12=d1["t"].data_ptr(), hyp_stride=MAXH, th2=10.0, fix_scale=1, inv_level_sigma2=[float(x) for x in inv_sig2])
+    m_sim3 = o2["matches12"].clone()  # (device-side copy for the model; the host sees nothing until the end)
+    assert lib.fb_optimize_sim3_dev(C.byref(a3), st) == 0, lib.fb_last_error()
+    # 4. SearchByProjection(pKF1, Scw, KF2's points)
+    pp = dict(kf_kps=q["kps1"], kf_desc=q["desc1"], kf_matched=np.zeros(n1, np.uint8), pose=np.zeros(12, np.float32),
+              **{k[:-1]: v for k, v in q.items() if k.startswith("mp_") and k.endswith("2")})
+    T1 = np.asarray(q["T1w"], np.float64).reshape(3, 4)  # (the generator leaves the normals 0: every point seen from KF1's centre)
+    po = pp["mp_xw"].astype(np.float64) + T1[:, :3].T @ T1[:, 3]
+    pp["mp_normal"] = (po / np.linalg.norm(po, axis=1, keepdims=True)).astype(np.float32)
+    a4, o4, (pk, pm, k4) = KP.proj_sim3_args([pp], *g1)
+    for struct, arrays in ((a4.kf, pk), (a4.mp, pm), (a4, k4), (a4, o4)):
+        _on_device(struct, arrays, hold)
+    cabi.fill(a4, Scw=o3["Scw"])
+    assert lib.fb_match_projection_sim3_dev(C.byref(a4), st) == 0, lib.fb_last_error()
+    torch.cuda.synchronize()
+    # ---- the same with the literal model in the place of step 3
+    mp = dict(C=1, n1=n1, n2=n2, kps1=q["kps1"], valid1=q["mp_valid1"], xw1=q["mp_xw1"], T1=q["T1w"], fix_scale=1, fx=KP.FX, fy=KP.FY,
+              cx=KP.W / 2.0, cy=KP.H / 2.0, th2=10.0, inv_level_sigma2=inv_sig2,
+              cands=[dict(kps2=q["kps2"], valid2=q["mp_valid2"], index2=np.arange(n2, dtype=np.int32), xw2=q["mp_xw2"], T2=q["T2w"],
+                          matches12=m_sim3.cpu().numpy()[0], R12=d1["R"].cpu().numpy()[0, 0], t12=d1["t"].cpu().numpy()[0, 0],
+                          s12=d1["s"].cpu().numpy()[0, 0])])
+    m = R.optimize_sim3(mp, 0)
+    print("chain: SearchBySim3 found %d, nCorrespondences %d, nBad %d, nInliers %d, smallest gap %.3g" % (
+        int(o2["nfound"].cpu()[0]), m["n_correspondences"], m["n_bad"], m["n_inliers"], m["min_gap"]))
+    assert m["n_correspondences"] >= 10 and m["min_gap"] >= RAZOR_GAP
+    assert int(o3["n_correspondences"].cpu()[0]) == m["n_correspondences"] and int(o3["n_inliers"].cpu()[0]) == m["n_inliers"]
+    np.testing.assert_array_equal(o2["matches12"].cpu().numpy()[0], m["matches12"])
+    pp["pose"] = m["Scw"]
+    a5, o5, _k5 = KP.proj_sim3_args([pp], *g1)
+    assert lib.fb_match_projection_sim3(C.byref(a5)) == 0, lib.fb_last_error()
+    np.testing.assert_array_equal(o4["match_kf_to_mp"].cpu().numpy(), o5["match_kf_to_mp"])
+    np.testing.assert_array_equal(o4["nmatches"].cpu().numpy(), o5["nmatches"])
+    assert int(o5["nmatches"][0]) > 0
