@@ -83,7 +83,8 @@ struct ProfScope {  // (the record list is mutex-protected and a scope closes it
 // Device scratch that lives for one host-pointer call.
 // hipMalloc/hipFree cost tens of microseconds each and the host-pointer entry points need dozens of scratch
 // buffers per call, so freed blocks are kept in a per-device pool of power-of-two size classes (runtime.hip).
-void *pool_take(size_t bytes, size_t *granted);  // nullptr on failure (error set)
+// exact: a long-lived block (a handle's arena) is granted its size rounded up to 256 bytes instead of a power of two
+void *pool_take(size_t bytes, size_t *granted, bool exact = false);  // nullptr on failure (error set)
 void pool_give(void *p, size_t granted);
 void pool_release();  // frees every idle block (fb_shutdown)
 
@@ -98,10 +99,10 @@ struct DevBuf {
     return *this;
   }
   ~DevBuf() { if (p) pool_give(p, granted); }
-  int alloc(size_t n) {
+  int alloc(size_t n, bool exact = false) {
     if (p) { pool_give(p, granted); p = nullptr; }
     bytes = n ? n : 1;
-    p = pool_take(bytes, &granted);
+    p = pool_take(bytes, &granted, exact);
     if (!p) return FB_ERR_HIP;
     return FB_OK;
   }

@@ -36,9 +36,10 @@ size_t g_pooled_bytes = 0;
 constexpr size_t kPoolCap = (size_t)4 << 30;  // keep at most 4 GiB of idle scratch
 }  // namespace
 
-void *pool_take(size_t bytes, size_t *granted) {
+void *pool_take(size_t bytes, size_t *granted, bool exact) {
   size_t cls = 256;
-  while (cls < bytes) cls <<= 1;
+  if (exact) cls = (bytes + 255) & ~(size_t)255;
+  else while (cls < bytes) cls <<= 1;
   int dev = 0;
   (void)hipGetDevice(&dev);
   {

@@ -1530,6 +1530,8 @@ int fb_frame_tail_bird_dev(const fb_frame_tail_bird_args *args, void *stream);
  * below take frames where the reference's ORBmatcher / Optimizer methods take Frame& / Frame*, so that consecutive calls
  * (extract -> match -> optimise -> match -> optimise, and frame k -> frame k+1) hand their results over on the device.
  * mvpMapPoints[i] / mvpMapPointsBird[i] are kept as int32 indices into the caller's map tables (-1 = NULL).
+ * The handle owns three device blocks: the members (what fb_frame_copy_dev copies), the BoW arrays (from the first
+ * fb_frame_compute_bow_dev on) and the scratch its stages hand each other; fb_frame_view_dev points into the first.
  *
  * All *_dev entry points only enqueue on `stream`; the return values of the reference functions (match / inlier counts)
  * land in the frame's counter block, which fb_frame_counts reads back (one synchronisation per frame instead of one per
@@ -1716,6 +1718,7 @@ int fb_frame_track_using_bird_dev(fb_frame *cur, fb_frame *src, fb_frame *ref, c
 /* Frame(const Frame &) (Frame.cc:49-82: tmpRefFrame = new Frame(mCurrentFrame), Tracking.cc:746) and the member copies of
  * KeyFrame::KeyFrame(Frame &F, ...) (KeyFrame.cc:32-91): every member array of src into dst (same parameters), device to
  * device on the stream, including the BoW when src has it and the frame's seen marks (fb_frame_discard_outliers_dev).
+ * A handle owns its member arrays as one block and the BoW arrays as a second: the copy is one transfer of each.
  * FB_ERR_ARG unless both handles were created with the same batch, orb parameters (capacity) and map_cap: the arrays
  * are copied whole.                                                                                                     */
 int fb_frame_copy_dev(fb_frame *dst, const fb_frame *src, void *stream);

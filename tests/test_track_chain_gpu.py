@@ -430,3 +430,135 @@ def test_chain_lost_frames_keep_their_members():
     modes = {1: "motion", 2: "motion", 3: "motion"}
     seen, worst = _run_modes(2, 4, (640, 480), (384, 384), 250.0, 9960, modes, min_inliers=100000, defer_drop=True, verbose=True)
     assert seen.get("kept_outliers", 0) > 0, seen
+
+
+def _frame_view(tc, handle):
+    import ctypes as C
+    bufs, v = T.alloc_view(tc.B, tc.cap)
+    assert tc.L.fb_frame_download(handle, C.byref(v), tc._stream()) == 0, tc.L.fb_last_error()
+    return bufs
+
+
+def _frame_bow(tc, handle):
+    """The arrays of fb_frame_bow_view_dev on the host."""
+    import ctypes as C
+    import torch
+    B, cap = tc.B, tc.cap
+    view = cabi.BowTransformArgs()
+    assert tc.L.fb_frame_bow_view_dev(handle, C.byref(view)) == 0, tc.L.fb_last_error()
+    torch.cuda.synchronize()
+    hip = C.CDLL("libamdhip64.so")
+    shapes = dict(n_words=((B,), np.int32), bow_ids=((B, cap), np.uint32), bow_vals=((B, cap), np.float64), fv_n_nodes=((B,), np.int32),
+                  fv_node_ids=((B, cap), np.uint32), fv_node_start=((B, cap + 1), np.int32), fv_items=((B, cap), np.int32))
+    out = {}
+    for k, (shp, dt) in shapes.items():
+        out[k] = np.zeros(shp, dt)
+        assert hip.hipMemcpy(C.c_void_p(out[k].ctypes.data), C.c_void_p(getattr(view, k)), C.c_size_t(out[k].nbytes), 2) == 0
+    return out
+
+
+def _same_bytes(a, b, tag, whole=True):
+    """whole: the arrays byte for byte; else rows up to n / n_bird (two handles with different pasts differ beyond them)."""
+    for k in a:
+        if whole or a[k].ndim < 2 or k in ("Tcw", "counts"):
+            assert a[k].tobytes() == b[k].tobytes(), (tag, k)
+            continue
+        cnt = a["n_bird"] if k in ("kps_bird", "desc_bird", "bird_cam_xyz", "map_point_bird", "bird_outlier") else a["n"]
+        for bb in range(len(cnt)):
+            assert a[k][bb, :cnt[bb]].tobytes() == b[k][bb, :cnt[bb]].tobytes(), (tag, k, bb)
+
+
+def test_frame_copy_carries_every_member():
+    """fb_frame_copy_dev (KeyFrame(Frame&)) hands over every member of a tracked frame, the ones fb_frame_view does not show
+    (mGrid / mGridBirdview: cs, ci, bcs, bci; the mnLastFrameSeen marks) included.  2 sequences, 640x480 + 384x384, local
+    lists, the vocabulary of test_chain_reference_keyframe_path.
+      1. two tracked frames, ComputeBoW on the second, copy into a fresh handle: every view field is byte-equal over the
+         whole array (not only [:n]), the BoW arrays over their valid prefix;
+      2. the next frame is constructed twice and tracked once against the original and once against the copy (the bird map
+         table, which tracking appends to, starts from the same snapshot): every view field (rows up to n / n_bird: the two
+         handles held other frames before) and every counter is byte-equal, and so are the two reference frames (whole
+         arrays) and the two tables afterwards;
+      3. what only the copied frame itself reads: a third construction of that frame runs TrackWithMotionModel, is copied,
+         and TrackLocalMap runs on the original and on the copy.  M2 and M8 read the frame's own grids and SearchLocalPoints
+         its marks, so a copy that lost one of them gives other matches.  The discard loop of that frame must have dropped
+         a point in some sequence (a mark is set), or the step shows nothing about the marks; the rule the marks feed is
+         pinned against a literal model in test_track_local_gpu.py."""
+    import ctypes as C
+    import torch
+    from fishbirdeyevisualslam_amd.bow_problem import make_vocabulary
+    B, wh, bwh, seed = 2, (640, 480), (384, 384), 9700
+    seq = S.Sequence(B, 4, seed=seed, front_wh=wh, bird_wh=bwh, fx=250.0, fy=250.0, device="cuda:0")
+    tc = T.TrackChain(B, wh, bwh, K=seq.Kc, D=seq.D, use_lists=True)
+    L, s = tc.L, tc._stream()
+    mask_d = torch.from_numpy(seq.mask).cuda()
+    f, b, c = seq.render(0)
+    tc.extract(f, b, c, mask_d)
+    M, MB, mp0, mpb0, Tcw0 = seq.build_map(tc.view("cur"), tc.tables, map_cap=tc.map_cap, bird_cap=tc.bird_cap)
+    lm, lb = _lists(M, MB, seed + 5)
+    vv, vk, first_leaf = make_vocabulary(seed + 1, k=5, L=5)
+    tc.set_vocabulary(vk, 5)
+    tc.set_map(M, MB, lm, lb)
+    tc.init_first(mp0, mpb0, Tcw0)
+    for k in (1, 2):
+        tc.set_delta(seq.delta(k))
+        tc.track(*seq.render(k), mask_d)
+    orig = tc.last
+    assert L.fb_frame_compute_bow_dev(orig, C.byref(tc.voc), s) == 0, L.fb_last_error()
+    copy = C.c_void_p()
+    assert L.fb_frame_create(C.byref(tc.params), C.byref(copy)) == 0, L.fb_last_error()
+    tc.frames.append(copy)   # (destroyed with the others)
+    assert L.fb_frame_copy_dev(copy, orig, s) == 0, L.fb_last_error()
+    # 1.
+    vo = _frame_view(tc, orig)
+    assert (vo["counts"][cabi.FB_CNT["MATCHES_INLIERS"]] >= 30).all() and (vo["map_point_bird"] >= 0).any(), vo["counts"][:12].T
+    _same_bytes(vo, _frame_view(tc, copy), "copied frame")
+    bo, bc = _frame_bow(tc, orig), _frame_bow(tc, copy)
+    for bb in range(B):
+        nw, nn = int(bo["n_words"][bb]), int(bo["fv_n_nodes"][bb])
+        assert nw > 0 and nn > 0 and bc["n_words"][bb] == nw and bc["fv_n_nodes"][bb] == nn
+        ni = int(bo["fv_node_start"][bb, nn])
+        for k, m in (("bow_ids", nw), ("bow_vals", nw), ("fv_node_ids", nn), ("fv_node_start", nn + 1), ("fv_items", ni)):
+            assert bo[k][bb, :m].tobytes() == bc[k][bb, :m].tobytes(), (k, bb)
+    # 2.
+    table = lambda: {k: v.clone() for k, v in tc.mpb.items()}
+
+    def restore(t):
+        for k, v in t.items():
+            tc.mpb[k].copy_(v)
+    f, b, c = seq.render(3)
+    tc.set_delta(seq.delta(3))
+    X, Y = tc.frames[0], tc.frames[1]
+    assert orig.value == tc.frames[2].value
+    before = table()
+    tc.extract(f, b, c, mask_d, frame=X)
+    assert L.fb_frame_track_dev(X, orig, C.byref(tc.targs), s) == 0, L.fb_last_error()
+    vx, after = _frame_view(tc, X), table()
+    restore(before)
+    tc.extract(f, b, c, mask_d, frame=Y)
+    assert L.fb_frame_track_dev(Y, copy, C.byref(tc.targs), s) == 0, L.fb_last_error()
+    assert (vx["counts"][cabi.FB_CNT["MATCHES_INLIERS"]] >= 30).all(), vx["counts"][:12].T
+    _same_bytes(vx, _frame_view(tc, Y), "tracked against the copy", whole=False)
+    _same_bytes(_frame_view(tc, orig), _frame_view(tc, copy), "reference frames after tracking")
+    torch.cuda.synchronize()
+    for k in after:
+        assert torch.equal(after[k], tc.mpb[k]), ("bird table", k)
+    # 3.
+    Z, Z2 = X, tc.kf
+    tc.extract(f, b, c, mask_d, frame=Z)
+    assert L.fb_frame_track_motion_model_dev(Z, orig, C.byref(tc.targs), s) == 0, L.fb_last_error()
+    assert L.fb_frame_copy_dev(Z2, Z, s) == 0, L.fb_last_error()
+    vz = _frame_view(tc, Z)
+    dropped = vz["counts"][cabi.FB_CNT["PROJ_MATCHES"]] - vz["counts"][cabi.FB_CNT["MATCHES"]]
+    print("points the discard loop dropped (marks set) per sequence:", dropped.tolist())
+    assert (dropped > 0).any(), dropped
+    before = table()
+    assert L.fb_frame_track_local_map_dev(Z, orig, C.byref(tc.targs), s) == 0, L.fb_last_error()
+    vz, after = _frame_view(tc, Z), table()
+    restore(before)
+    assert L.fb_frame_track_local_map_dev(Z2, copy, C.byref(tc.targs), s) == 0, L.fb_last_error()
+    assert (vz["counts"][cabi.FB_CNT["LOCAL_MATCHES"]] > 0).all() and (vz["counts"][cabi.FB_CNT["BIRDVIEW_MATCHES"]] > 0).all(), vz["counts"][:12].T
+    _same_bytes(vz, _frame_view(tc, Z2), "TrackLocalMap on the copy")
+    torch.cuda.synchronize()
+    for k in after:
+        assert torch.equal(after[k], tc.mpb[k]), ("bird table after TrackLocalMap", k)
+    tc.close()
