@@ -16,6 +16,7 @@
 // compared bit for bit with tests/covis_ref.py.
 #include "fb_common.h"
 #include "fb_primitives.h"
+#include "covis_plan.h"
 
 #include <algorithm>
 
@@ -24,9 +25,6 @@ struct fb_covis;
 namespace {
 
 constexpr int CV_MAXK = FB_KFDB_MAX_KEYFRAMES;
-constexpr int CV_NT = 1024;
-constexpr int CV_SCAN_ITEMS = 4;                      // consecutive ints per thread of a scan tile
-constexpr int CV_SCAN_TILE = CV_NT * CV_SCAN_ITEMS;
 constexpr uint32_t CV_W = 0x7fffu, CV_MEMBER = 0x8000u;
 constexpr uint32_t KEY_NONE32 = 0xffffffffu;
 static_assert(CV_MAXK <= 4096, "a rank is kept in 12 bits");
@@ -393,11 +391,19 @@ __global__ __launch_bounds__(CV_NT) void k_cv_cull(Gr G, fb_covis_map M, const i
   }
 }
 
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 struct Index {          // scratch of one call that takes a map
   int32_t *start, *fill, *csr, *bsum, *nobs, *dead;
   uint16_t *counter;
+};
+
+struct IndexAsk {       // what a call wants of fb_covis::acquire
+  size_t n_q = 0;       // queries of an update_connections (the counter rows)
+  bool culling = false; // nobs / dead are set up as the culling overlay
+  bool ranks = true;    // the ranks of M.kf_order are computed (the window's bird side shares the front side's)
+  bool reuse = false;   // the caller's reuse_index
+  bool kept = true;     // the index is the one a later reuse_index reads
+  size_t head = 0;      // where a new index goes (behind a window head or the window's front index)
+  size_t tail = 0;      // bytes the call keeps behind the index
 };
 
 }  // namespace
@@ -406,21 +412,17 @@ struct fb_covis {
   int K = 0;
   void *block = nullptr;
   Gr G{};
-  void *scr = nullptr;
-  size_t scrBytes = 0;
-  bool winValid = false;   // the scratch holds the lists of a fb_covis_local_window_dev (fb_covis_local_window_header reads them)
-  int winCapKf = 0;
-  // where the last index() left the point -> edge index, and of which map: fb_local_map_args.reuse_index reads it again
-  struct IndexAt { bool valid = false; size_t head = 0, end = 0; fb_covis_map map{}; } at;
+  uint8_t *scr = nullptr;
+  ScratchState state{};   // what scr holds; written by the scratch_*() of covis_plan.h only
   int ensure() {
     FB_TRY(fb::check_device());
     if (block) return FB_OK;
-    const size_t k = K, oW = 0, oRank = up256(k * k * 2), oInv = oRank + up256(k * 4), oErr = oInv + up256(k * 4), oPar = oErr + 256,
-                 oLink = oPar + up256(k * 4), oFirst = oLink + up256(k), total = oFirst + up256(k);
+    GraphOff o;
+    const size_t total = plan_graph(K, &o);
     FB_HIP(hipMalloc(&block, total));
     uint8_t *b = static_cast<uint8_t *>(block);
-    G.K = K; G.W = (uint16_t *)(b + oW); G.rank = (int32_t *)(b + oRank); G.inv = (int32_t *)(b + oInv); G.err = (int32_t *)(b + oErr);
-    G.parent = (int32_t *)(b + oPar); G.linked = b + oLink; G.first = b + oFirst;
+    G.K = K; G.W = (uint16_t *)(b + o.W); G.rank = (int32_t *)(b + o.rank); G.inv = (int32_t *)(b + o.inv); G.err = (int32_t *)(b + o.err);
+    G.parent = (int32_t *)(b + o.parent); G.linked = b + o.linked; G.first = b + o.first;
     FB_HIP(hipMemset(block, 0, total));
     k_cv_identity<<<(K + 255) / 256, 256>>>(G);
     k_cv_tree_reset<<<(K + 255) / 256, 256>>>(G);
@@ -428,37 +430,41 @@ struct fb_covis {
     FB_HIP(hipDeviceSynchronize());   // creation is rare; orders the default stream's work before every other stream
     return FB_OK;
   }
-  static size_t scratch_bytes(size_t n_mp, size_t n_obs, size_t n_q, size_t k) {
-    const size_t nb = (n_mp + 1 + CV_SCAN_TILE - 1) / CV_SCAN_TILE;
-    return up256((n_mp + 1) * 4) + 2 * up256(n_mp * 4) + 2 * up256(n_obs * 4) + up256(nb * 4) + up256(n_q * k * 2) + 256;
-  }
   int need(size_t bytes) {
-    if (bytes <= scrBytes) return FB_OK;
-    if (scr) { FB_HIP(hipDeviceSynchronize()); FB_HIP(hipFree(scr)); scr = nullptr; scrBytes = 0; winValid = false; at.valid = false; }
-    FB_HIP(hipMalloc(&scr, bytes));
-    scrBytes = bytes;
+    if (bytes <= state.capacity) return FB_OK;
+    if (scr) { FB_HIP(hipDeviceSynchronize()); FB_HIP(hipFree(scr)); scr = nullptr; scratch_clear(state); }
+    FB_HIP(hipMalloc(reinterpret_cast<void **>(&scr), bytes));
+    scratch_grown(state, bytes);
     return FB_OK;
   }
-  // ranks of M.kf_order, then the edge list grouped by point; nothing is kept from an earlier call.  The index lies `head`
-  // bytes into the scratch (the window calls keep their own arrays, and a second index, in front of it).
-  int index(const fb_covis_map &M, size_t n_q, bool culling, Index *ix, hipStream_t s, size_t head = 0, bool ranks = true) {
-    const size_t n_mp = M.n_mp, n_obs = M.n_obs;
-    FB_TRY(need(head + scratch_bytes(n_mp, n_obs, n_q, K)));
-    at.valid = true; at.head = head; at.end = head + scratch_bytes(n_mp, n_obs, n_q, K); at.map = M;
-    uint8_t *b = static_cast<uint8_t *>(scr) + head;
-    index_layout(b, n_mp, n_obs, n_q, ix);
-    return index_build(M, culling, ix, s, ranks);
+  int reserve(const CallPlan &c) {
+    FB_TRY(ensure());
+    return need(c.total);
   }
-  void index_layout(uint8_t *b, size_t n_mp, size_t n_obs, size_t n_q, Index *ix) const {
-    const size_t nb = (n_mp + 1 + CV_SCAN_TILE - 1) / CV_SCAN_TILE;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { uint8_t *p = b + off; off += up256(bytes); return p; };
-    ix->start = (int32_t *)take((n_mp + 1) * 4); ix->fill = (int32_t *)take(n_mp * 4); ix->nobs = (int32_t *)take(n_mp * 4);
-    ix->csr = (int32_t *)take(n_obs * 4); ix->dead = (int32_t *)take(n_obs * 4); ix->bsum = (int32_t *)take(nb * 4);
-    ix->counter = (uint16_t *)take(n_q * K * 2);
+  // The index of M for one call, and where the call's tail begins.  Reused when the call asks for it and the state allows;
+  // otherwise the scratch is sized once for the whole call (nothing later reallocates), the ranks of M.kf_order and the edge
+  // list grouped by point are built at a.head, and the state learns of it once that is enqueued.
+  int acquire(const fb_covis_map &M, const IndexAsk &a, Index *ix, uint8_t **tail, hipStream_t s) {
+    IndexOff o;
+    const size_t bytes = plan_index(M.n_mp, M.n_obs, a.n_q, K, &o);
+    const IndexStep st = scratch_decide(state, a.reuse, M, a.head, bytes, a.tail);
+    FB_ARG(!st.refused);
+    if (!st.reuse) {
+      FB_TRY(need(st.total));
+      scratch_build_begins(state, st.index_at, a.kept);
+    }
+    uint8_t *b = scr + st.index_at;
+    ix->start = (int32_t *)(b + o.start); ix->fill = (int32_t *)(b + o.fill); ix->nobs = (int32_t *)(b + o.nobs);
+    ix->csr = (int32_t *)(b + o.csr); ix->dead = (int32_t *)(b + o.dead); ix->bsum = (int32_t *)(b + o.bsum);
+    ix->counter = (uint16_t *)(b + o.counter);
+    if (tail) *tail = scr + st.tail_at;
+    if (st.reuse) return FB_OK;
+    FB_TRY(index_build(M, a.culling, ix, s, a.ranks));
+    scratch_build_done(state, st.index_at, st.tail_at, M, a.kept);
+    return FB_OK;
   }
   int index_build(const fb_covis_map &M, bool culling, Index *ix, hipStream_t s, bool ranks) {
-    const size_t n_mp = M.n_mp, n_obs = M.n_obs, nb = (n_mp + 1 + CV_SCAN_TILE - 1) / CV_SCAN_TILE;
+    const size_t n_mp = M.n_mp, n_obs = M.n_obs, nb = scan_tiles(n_mp);
     if (ranks) k_cv_rank<<<(K + 255) / 256, 256, 0, s>>>(G, M.kf_order);
     // start and fill are adjacent: one memset
     FB_HIP(hipMemsetAsync(ix->start, 0, (size_t)((uint8_t *)ix->nobs - (uint8_t *)ix->start), s));
@@ -559,8 +565,7 @@ int fb_covis_clear(fb_covis *g, void *stream) {
 int fb_covis_reserve(fb_covis *g, int32_t n_mp, int32_t n_obs, int32_t n_q) {
   FB_ARG(g);
   FB_ARG(n_mp >= 0 && n_mp < INT_MAX && n_obs >= 0 && n_q >= 0 && n_q <= g->K);
-  FB_TRY(g->ensure());
-  return g->need(fb_covis::scratch_bytes(n_mp, n_obs, n_q, g->K));
+  return g->reserve(plan_map_call(g->K, n_mp, n_obs, n_q, 0));
 }
 
 int fb_covis_set_order_dev(fb_covis *g, const uint64_t *d_kf_order, void *stream) {
@@ -590,7 +595,9 @@ int fb_covis_update_connections_dev(fb_covis *g, const fb_covis_map *M, int32_t 
   if (n_q == 0) return FB_OK;
   hipStream_t s = fb::as_stream(stream);
   Index ix;
-  FB_TRY(g->index(*M, n_q, false, &ix, s));
+  IndexAsk ask;
+  ask.n_q = n_q;
+  FB_TRY(g->acquire(*M, ask, &ix, nullptr, s));
   k_cv_counter<<<n_q, CV_NT, 0, s>>>(*M, g->G, ix.start, ix.csr, d_slots, ix.counter);
   k_cv_apply<<<1, CV_NT, 0, s>>>(g->G, n_q, d_slots, ix.counter, d_n_counter, d_front);
   FB_HIP(hipGetLastError());
@@ -611,8 +618,8 @@ int fb_covis_update_connections(fb_covis *g, const fb_covis_map *H, int32_t n_q,
   st.in(slots, (size_t)n_q * 4);
   st.out(n_counter, (size_t)n_q * 4, false); st.out(front, (size_t)n_q * 4, false);
   FB_TRY(st.commit(nullptr));
+  IndexDropGuard drop(g->state);   // the index is of staged arrays that go back to the pool: nothing to reuse
   FB_TRY(fb_covis_update_connections_dev(g, &M, n_q, slots, n_counter, front, nullptr));
-  g->at.valid = false;   // the index is of staged arrays that go back to the pool: nothing to reuse
   return st.fetch(nullptr);
 }
 
@@ -723,7 +730,9 @@ int fb_covis_keyframe_culling_dev(fb_covis *g, const fb_covis_map *M, int32_t cu
   FB_TRY(g->ensure());
   hipStream_t s = fb::as_stream(stream);
   Index ix;
-  FB_TRY(g->index(*M, 0, true, &ix, s));
+  IndexAsk ask;
+  ask.culling = true;
+  FB_TRY(g->acquire(*M, ask, &ix, nullptr, s));
   if (M->n_mp) FB_HIP(hipMemcpyAsync(d_mp_bad_after, M->mp_bad, (size_t)M->n_mp, hipMemcpyDeviceToDevice, s));
   k_cv_cull<<<1, CV_NT, 0, s>>>(g->G, *M, ix.start, ix.csr, ix.nobs, ix.dead, cur_slot, id0_slot, d_not_erase, d_n, d_slots,
                                 d_n_redundant, d_n_mps, d_culled, d_mp_bad_after);
@@ -749,9 +758,9 @@ int fb_covis_keyframe_culling(fb_covis *g, const fb_covis_map *H, int32_t cur_sl
   st.out(slots, K * 4, true); st.out(n_redundant, K * 4, true); st.out(n_mps, K * 4, true); st.out(culled, K, true);
   st.out(mp_bad_after, (size_t)M.n_mp, false);
   FB_TRY(st.commit(nullptr));
+  IndexDropGuard drop(g->state);
   FB_TRY(fb_covis_keyframe_culling_dev(g, &M, cur_slot, id0_slot, not_erase, n, slots, n_redundant, n_mps, culled, mp_bad_after,
                                        nullptr));
-  g->at.valid = false;
   return st.fetch(nullptr);
 }
 

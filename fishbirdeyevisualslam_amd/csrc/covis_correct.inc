@@ -50,15 +50,10 @@ struct ClS {            // the scratch of one call, behind the index
   int32_t *bnext;       // [K][BS] } pair = position * BS + feature
 };
 
-size_t cl_bytes(size_t K, size_t n_mp, size_t n_mpb, size_t BS) {
-  return 256 + up256(K * 4) + up256(K * sizeof(ClEntry)) + up256(K * 12) + up256(n_mp * 4) + up256(n_mpb * 4) + up256(K * BS * 4);
-}
-void cl_layout(uint8_t *b, size_t K, size_t n_mp, size_t n_mpb, size_t BS, ClS *S) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) { uint8_t *p = b + off; off += up256(bytes); return p; };
-  S->hdr = (int32_t *)take(256); S->pos = (int32_t *)take(K * 4); S->tab = (ClEntry *)take(K * sizeof(ClEntry));
-  S->ow_old = (float *)take(K * 12); S->owner = (int32_t *)take(n_mp * 4); S->bhead = (int32_t *)take(n_mpb * 4);
-  S->bnext = (int32_t *)take(K * BS * 4);
+static_assert(sizeof(ClEntry) == CL_ENTRY_BYTES, "plan_correct_loop sizes the table by it");
+void cl_map(uint8_t *b, const ClOff &o, ClS *S) {
+  S->hdr = (int32_t *)(b + o.hdr); S->pos = (int32_t *)(b + o.pos); S->tab = (ClEntry *)(b + o.tab); S->ow_old = (float *)(b + o.ow_old);
+  S->owner = (int32_t *)(b + o.owner); S->bhead = (int32_t *)(b + o.bhead); S->bnext = (int32_t *)(b + o.bnext);
 }
 
 using fb::Sim3d; using fb::sim3_map; using fb::sim3_mul; using fb::sim3_inverse;  // g2o::Sim3 in double, fb_se3.h
@@ -405,8 +400,8 @@ int fb_covis_reserve_correct_loop(fb_covis *g, int32_t n_mp, int32_t n_obs, int3
   FB_ARG(g);
   FB_ARG(n_mp >= 0 && n_mp < INT_MAX && n_obs >= 0 && n_q >= 0 && n_q <= g->K && n_mpb >= 0 && n_mpb < INT_MAX);
   FB_ARG(bird_stride >= 0 && bird_stride <= FB_COVIS_MAX_STRIDE);
-  FB_TRY(g->ensure());
-  return g->need(fb_covis::scratch_bytes(n_mp, n_obs, n_q, g->K) + cl_bytes(g->K, n_mp, n_mpb, bird_stride));
+  ClOff co;
+  return g->reserve(plan_map_call(g->K, n_mp, n_obs, n_q, plan_correct_loop(g->K, n_mp, n_mpb, bird_stride, &co)));
 }
 
 int fb_covis_correct_loop_dev(fb_covis *g, const fb_covis_map *M, const fb_covis_kf_tables *T, const fb_correct_loop_args *a, void *stream) {
@@ -416,21 +411,15 @@ int fb_covis_correct_loop_dev(fb_covis *g, const fb_covis_map *M, const fb_covis
   FB_TRY(g->ensure());
   hipStream_t s = fb::as_stream(stream);
   const bool bird = cl_has_bird(T);
-  const size_t K = g->K, n_mp = M->n_mp, n_obs = M->n_obs, n_mpb = bird ? T->n_mpb : 0, BS = bird ? T->bird_stride : 0;
-  const size_t cl = cl_bytes(K, n_mp, n_mpb, BS);
-  bool reuse = a->reuse_index && g->at.valid;
-  if (reuse) { FB_ARG(same_map(g->at.map, *M)); }                       // the caller's statement, as far as it can be checked
-  if (reuse && g->at.end + cl > g->scrBytes) reuse = false;             // growing the scratch would lose the index: rebuilt once
+  const size_t K = g->K, n_mp = M->n_mp, n_mpb = bird ? T->n_mpb : 0, BS = bird ? T->bird_stride : 0;
+  ClOff co;
+  IndexAsk ask;
+  ask.reuse = a->reuse_index != 0; ask.tail = plan_correct_loop(K, n_mp, n_mpb, BS, &co);
   Index ix;
-  if (reuse) {
-    g->index_layout(static_cast<uint8_t *>(g->scr) + g->at.head, n_mp, n_obs, 0, &ix);
-  } else {
-    FB_TRY(g->need(fb_covis::scratch_bytes(n_mp, n_obs, 0, K) + cl));   // once: nothing below reallocates
-    FB_TRY(g->index(*M, 0, false, &ix, s));
-    g->winValid = false;                                                // the index lies where the window's header arrays were
-  }
+  uint8_t *tail;
+  FB_TRY(g->acquire(*M, ask, &ix, &tail, s));
   ClS S;
-  cl_layout(static_cast<uint8_t *>(g->scr) + g->at.end, K, n_mp, n_mpb, BS, &S);
+  cl_map(tail, co, &S);
   k_cl_set<<<1, CV_NT, 0, s>>>(g->G, T->kf_Tcw, *a, S);
   if (n_mp) {
     FB_HIP(hipMemsetAsync(S.owner, 0x7f, n_mp * 4, s));
@@ -473,8 +462,8 @@ int fb_covis_correct_loop(fb_covis *g, const fb_covis_map *HM, const fb_covis_kf
   }
   FB_TRY(st.commit(nullptr));
   A.reuse_index = 0;   // the staged arrays are new device arrays every call
+  IndexDropGuard drop(g->state);
   FB_TRY(fb_covis_correct_loop_dev(g, &M, &T, &A, nullptr));
-  g->at.valid = false;   // the index is of staged arrays
   return st.fetch(nullptr);
 }
 

@@ -17,7 +17,6 @@
 namespace {
 
 constexpr int PT_STAGE = FB_REFRESH_STAGE;
-constexpr int PT_NT = 256;
 constexpr uint32_t PT_IDX = 0x7fffu;                   // a sort key is rank << 15 | feature index (kp_stride <= 32767)
 static_assert(FB_COVIS_MAX_STRIDE <= 0x7fff, "a feature index is kept in 15 bits");
 enum { MPC_NONE = -1, MPC_DROP = 0, MPC_CULL = 1, MPC_KEEP = 2 };
@@ -230,14 +229,9 @@ struct MpcS {           // the scratch of one call, behind the index
   int32_t *val, *dec, *rowbase;   // [cap] the list as it came in, the branch of each entry, where its erased rows begin
   int32_t *bcnt;        // [blocks][3] kept, culled, erased rows of a block of PT_NT entries
 };
-size_t mpc_bytes(size_t n_mp, size_t cap) {
-  return up256(n_mp * 4) + 3 * up256(cap * 4) + up256(((cap + PT_NT - 1) / PT_NT) * 12 + 12);
-}
-void mpc_layout(uint8_t *b, size_t n_mp, size_t cap, MpcS *S) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) { uint8_t *p = b + off; off += up256(bytes); return p; };
-  S->first = (int32_t *)take(n_mp * 4); S->val = (int32_t *)take(cap * 4); S->dec = (int32_t *)take(cap * 4);
-  S->rowbase = (int32_t *)take(cap * 4); S->bcnt = (int32_t *)take(((cap + PT_NT - 1) / PT_NT) * 12 + 12);
+void mpc_map(uint8_t *b, const MpcOff &o, MpcS *S) {
+  S->first = (int32_t *)(b + o.first); S->val = (int32_t *)(b + o.val); S->dec = (int32_t *)(b + o.dec);
+  S->rowbase = (int32_t *)(b + o.rowbase); S->bcnt = (int32_t *)(b + o.bcnt);
 }
 
 // the branch of every entry from the map as it came in (:209-227); nothing of the map is written yet
@@ -353,22 +347,6 @@ int check_refresh(const fb_covis_map *M, const fb_point_refresh_args *a) {
   return check_refresh_arrays(M, a);
 }
 
-// the index of the map for a call that keeps `behind` bytes of its own after it: reused when the caller says so and it can be
-int pt_index(fb_covis *g, const fb_covis_map *M, int reuse_index, size_t behind, Index *ix, hipStream_t s) {
-  const size_t K = g->K, n_mp = M->n_mp, n_obs = M->n_obs;
-  bool reuse = reuse_index && g->at.valid;
-  if (reuse) { FB_ARG(same_map(g->at.map, *M)); }                       // the caller's statement, as far as it can be checked
-  if (reuse && g->at.end + behind > g->scrBytes) reuse = false;         // growing the scratch would lose the index: rebuilt once
-  if (reuse) {
-    g->index_layout(static_cast<uint8_t *>(g->scr) + g->at.head, n_mp, n_obs, 0, ix);
-  } else {
-    FB_TRY(g->need(fb_covis::scratch_bytes(n_mp, n_obs, 0, K) + behind));   // once: nothing below reallocates
-    FB_TRY(g->index(*M, 0, false, ix, s));
-    g->winValid = false;                                                // the index lies where the window's header arrays were
-  }
-  return FB_OK;
-}
-
 int launch_refresh(fb_covis *g, const fb_covis_map *M, const Index &ix, const PtRun &R, hipStream_t s) {
   const int blocks = R.list ? R.n_list : M->n_mp;
   if (blocks == 0) return FB_OK;
@@ -377,8 +355,6 @@ int launch_refresh(fb_covis *g, const fb_covis_map *M, const Index &ix, const Pt
   FB_HIP(hipGetLastError());
   return FB_OK;
 }
-
-size_t pnk_bytes(size_t n_features) { return 2 * up256(n_features * 4) + 256; }
 
 int check_new_keyframe(const fb_covis *g, const fb_covis_map *M, const fb_new_keyframe_args *a) {
   FB_ARG(a);
@@ -408,8 +384,7 @@ extern "C" {
 int fb_covis_reserve_refresh_points(fb_covis *g, int32_t n_mp, int32_t n_obs, int32_t n_q) {
   FB_ARG(g);
   FB_ARG(n_mp >= 0 && n_mp < INT_MAX && n_obs >= 0 && n_q >= 0 && n_q <= g->K);
-  FB_TRY(g->ensure());
-  return g->need(fb_covis::scratch_bytes(n_mp, n_obs, n_q, g->K));
+  return g->reserve(plan_map_call(g->K, n_mp, n_obs, n_q, 0));
 }
 
 int fb_covis_refresh_points_dev(fb_covis *g, const fb_covis_map *M, const fb_point_refresh_args *a, void *stream) {
@@ -420,7 +395,9 @@ int fb_covis_refresh_points_dev(fb_covis *g, const fb_covis_map *M, const fb_poi
   FB_TRY(g->ensure());
   hipStream_t s = fb::as_stream(stream);
   Index ix;
-  FB_TRY(pt_index(g, M, a->reuse_index, 0, &ix, s));
+  IndexAsk ask;
+  ask.reuse = a->reuse_index != 0;
+  FB_TRY(g->acquire(*M, ask, &ix, nullptr, s));
   PtRun R;
   memset(&R, 0, sizeof(R));
   R.A = *a; R.list = a->d_list; R.d_n = a->d_n_list; R.n_list = a->d_list ? a->n_list : 0; R.cap = g->K;
@@ -446,16 +423,16 @@ int fb_covis_refresh_points(fb_covis *g, const fb_covis_map *HM, const fb_point_
   st.out(A.mp_desc, n_mp * 32, true);
   FB_TRY(st.commit(nullptr));
   A.reuse_index = 0;   // the staged arrays are new device arrays every call
+  IndexDropGuard drop(g->state);
   FB_TRY(fb_covis_refresh_points_dev(g, &M, &A, nullptr));
-  g->at.valid = false;   // the index is of staged arrays
   return st.fetch(nullptr);
 }
 
 int fb_covis_reserve_process_new_keyframe(fb_covis *g, int32_t n_mp, int32_t n_obs, int32_t n_q, int32_t n_features) {
   FB_ARG(g);
   FB_ARG(n_mp >= 0 && n_mp < INT_MAX && n_obs >= 0 && n_q >= 0 && n_q <= g->K && n_features >= 0);
-  FB_TRY(g->ensure());
-  return g->need(fb_covis::scratch_bytes(n_mp, n_obs, n_q, g->K) + pnk_bytes(n_features));
+  PnkOff po;
+  return g->reserve(plan_map_call(g->K, n_mp, n_obs, n_q, plan_new_keyframe(n_features, &po)));
 }
 
 int fb_covis_process_new_keyframe_dev(fb_covis *g, const fb_covis_map *M, const fb_new_keyframe_args *a, void *stream) {
@@ -466,11 +443,14 @@ int fb_covis_process_new_keyframe_dev(fb_covis *g, const fb_covis_map *M, const 
   FB_TRY(g->ensure());
   hipStream_t s = fb::as_stream(stream);
   const size_t NF = a->n_features;
+  PnkOff po;
+  IndexAsk ask;
+  ask.tail = plan_new_keyframe(NF, &po);
   Index ix;
-  FB_TRY(pt_index(g, M, 0, pnk_bytes(NF), &ix, s));
-  uint8_t *b = static_cast<uint8_t *>(g->scr) + g->at.end;
-  int32_t *gain = (int32_t *)b, *gain_idx = (int32_t *)(b + up256(NF * 4)), *n_gain = (int32_t *)(b + 2 * up256(NF * 4));
-  g->at.valid = false;                                                  // the edge list grows: a later reuse_index rebuilds
+  uint8_t *b;
+  FB_TRY(g->acquire(*M, ask, &ix, &b, s));
+  int32_t *gain = (int32_t *)(b + po.gain), *gain_idx = (int32_t *)(b + po.gain_idx), *n_gain = (int32_t *)(b + po.n_gain);
+  scratch_drop_index(g->state);                                         // the edge list grows: a later reuse_index rebuilds
   if (M->n_mp) FB_HIP(hipMemsetAsync(ix.nobs, 0x7f, (size_t)M->n_mp * 4, s));   // (the culling overlay's array is free here)
   k_pnk<<<1, CV_NT, 0, s>>>(*M, g->G, ix.start, ix.csr, ix.nobs, *a, gain, gain_idx, n_gain);
   FB_HIP(hipGetLastError());
@@ -501,6 +481,7 @@ int fb_covis_process_new_keyframe(fb_covis *g, const fb_covis_map *HM, const fb_
   st.out(F.mp_desc, n_mp * 32, true);
   FB_TRY(st.commit(nullptr));
   M.obs_mp = A.obs_mp; M.obs_kf = A.obs_kf; M.obs_idx = A.obs_idx;
+  IndexDropGuard drop(g->state);
   FB_TRY(fb_covis_process_new_keyframe_dev(g, &M, &A, nullptr));
   return st.fetch(nullptr);
 }
@@ -508,8 +489,8 @@ int fb_covis_process_new_keyframe(fb_covis *g, const fb_covis_map *HM, const fb_
 int fb_covis_reserve_map_point_culling(fb_covis *g, int32_t n_mp, int32_t n_obs, int32_t n_q, int32_t recent_cap) {
   FB_ARG(g);
   FB_ARG(n_mp >= 0 && n_mp < INT_MAX && n_obs >= 0 && n_q >= 0 && n_q <= g->K && recent_cap >= 0);
-  FB_TRY(g->ensure());
-  return g->need(fb_covis::scratch_bytes(n_mp, n_obs, n_q, g->K) + mpc_bytes(n_mp, recent_cap));
+  MpcOff mo;
+  return g->reserve(plan_map_call(g->K, n_mp, n_obs, n_q, plan_point_culling(n_mp, recent_cap, &mo)));
 }
 
 int fb_covis_map_point_culling_dev(fb_covis *g, const fb_covis_map *M, const fb_map_point_culling_args *a, void *stream) {
@@ -526,11 +507,15 @@ int fb_covis_map_point_culling_dev(fb_covis *g, const fb_covis_map *M, const fb_
     FB_HIP(hipMemsetAsync(a->d_n_recent, 0, 4, s));
     return FB_OK;
   }
+  MpcOff mo;
+  IndexAsk ask;
+  ask.tail = plan_point_culling(n_mp, cap, &mo);
   Index ix;
-  FB_TRY(pt_index(g, M, 0, mpc_bytes(n_mp, cap), &ix, s));
+  uint8_t *tail;
+  FB_TRY(g->acquire(*M, ask, &ix, &tail, s));
   MpcS S;
-  mpc_layout(static_cast<uint8_t *>(g->scr) + g->at.end, n_mp, cap, &S);
-  g->at.valid = false;                                                  // edges become tombstones: a later reuse_index rebuilds
+  mpc_map(tail, mo, &S);
+  scratch_drop_index(g->state);                                         // edges become tombstones: a later reuse_index rebuilds
   const unsigned nb = (unsigned)((cap + PT_NT - 1) / PT_NT);
   if (n_mp) FB_HIP(hipMemsetAsync(S.first, 0x7f, n_mp * 4, s));
   k_mpc_decide<<<nb, PT_NT, 0, s>>>(*M, ix.start, *a, S, g->G.err);
@@ -560,6 +545,7 @@ int fb_covis_map_point_culling(fb_covis *g, const fb_covis_map *HM, const fb_map
   st.out(A.d_n_erased, 4, false); st.out(A.d_erased, (size_t)A.erased_cap * 16, true);
   FB_TRY(st.commit(nullptr));
   M.kf_mp = A.kf_mp; M.mp_bad = A.mp_bad; M.obs_kf = A.obs_kf;
+  IndexDropGuard drop(g->state);
   FB_TRY(fb_covis_map_point_culling_dev(g, &M, &A, nullptr));
   return st.fetch(nullptr);
 }

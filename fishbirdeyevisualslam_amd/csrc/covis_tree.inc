@@ -15,9 +15,7 @@
 
 namespace {
 
-constexpr int LM_EXPAND = FB_LOCAL_MAP_MAX_EXPAND;     // the expansion loop stops once the list is longer than this
-constexpr int LM_NEIGH = FB_KFDB_COVIS;                 // GetBestCovisibilityKeyFrames(10)
-constexpr int LM_HDR = 64;                              // ints of header per sequence: the window's WH_* and the ones below
+// LM_EXPAND, LM_NEIGH, LM_HDR: covis_plan.h.  A sequence's header holds the window's WH_* and the ones below.
 enum { LH_GATED = WH_COUNT, LH_CARRY, LH_VOTERS, LH_KF_OVER };
 constexpr uint32_t TREE_DONE = 0xffffffffu;
 static_assert(LM_NEIGH <= 64 && LH_KF_OVER < LM_HDR, "one wave tests the neighbours; the header holds the flags");
@@ -174,18 +172,10 @@ struct LmS {            // the scratch of one call, behind the index
   int list;
 };
 
-int lm_list(int K) { return std::max(K, LM_EXPAND + 4); }            // voters <= K; with an expansion <= 80 + 3
-size_t lm_bytes(size_t batch, size_t K, size_t n_mp) {
-  return batch * (up256(LM_HDR * 4) + up256(LM_EXPAND * 4) + up256((size_t)LM_EXPAND * LM_NEIGH * 4) + up256((size_t)lm_list((int)K) * 4)) +
-         up256((size_t)lm_list((int)K) * 4) + 2 * up256(n_mp * 4);
-}
-void lm_layout(uint8_t *b, size_t batch, size_t K, size_t n_mp, LmS *S) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) { uint8_t *p = b + off; off += bytes; return p; };
-  S->list = lm_list((int)K);
-  S->hdr = (int32_t *)take(batch * up256(LM_HDR * 4)); S->voters = (int32_t *)take(batch * up256(LM_EXPAND * 4));
-  S->rows = (int32_t *)take(batch * up256((size_t)LM_EXPAND * LM_NEIGH * 4)); S->wslot = (int32_t *)take(batch * up256((size_t)S->list * 4));
-  S->rowcnt = (int32_t *)take(up256((size_t)S->list * 4)); S->ptkey = (int32_t *)take(up256(n_mp * 4)); S->plist = (int32_t *)take(up256(n_mp * 4));
+void lm_map(uint8_t *b, const LmOff &o, LmS *S) {
+  S->list = o.list;
+  S->hdr = (int32_t *)(b + o.hdr); S->voters = (int32_t *)(b + o.voters); S->rows = (int32_t *)(b + o.rows); S->wslot = (int32_t *)(b + o.wslot);
+  S->rowcnt = (int32_t *)(b + o.rowcnt); S->ptkey = (int32_t *)(b + o.ptkey); S->plist = (int32_t *)(b + o.plist);
 }
 __host__ __device__ constexpr size_t lm_ints(size_t n) { return ((n * 4 + 255) & ~(size_t)255) / 4; }   // a per-sequence stride
 __host__ __device__ __forceinline__ int32_t *lm_hdr(const LmS &S, int b) { return S.hdr + b * lm_ints(LM_HDR); }
@@ -361,12 +351,6 @@ int check_local_map(const fb_local_map_args *a) {
   return FB_OK;
 }
 
-bool same_map(const fb_covis_map &a, const fb_covis_map &b) {
-  return a.max_keyframes == b.max_keyframes && a.kp_stride == b.kp_stride && a.n_mp == b.n_mp && a.n_obs == b.n_obs && a.kf_n == b.kf_n &&
-         a.kf_mp == b.kf_mp && a.kf_octave == b.kf_octave && a.mp_bad == b.mp_bad && a.obs_mp == b.obs_mp && a.obs_kf == b.obs_kf &&
-         a.obs_idx == b.obs_idx && a.kf_order == b.kf_order;
-}
-
 int tree_slot(fb_covis *g, int32_t slot) {
   FB_ARG(g);
   FB_ARG(slot >= 0 && slot < g->K);
@@ -474,9 +458,7 @@ int fb_covis_tree_erase_keyframe_dev(fb_covis *g, int32_t slot, const uint8_t *d
 int fb_covis_reserve_local_map(fb_covis *g, int32_t n_mp, int32_t n_obs, int32_t n_q, int32_t batch, int32_t with_window) {
   FB_ARG(g);
   FB_ARG(n_mp >= 0 && n_mp < INT_MAX && n_obs >= 0 && n_q >= 0 && n_q <= g->K && batch >= 1);
-  FB_TRY(g->ensure());
-  return g->need((with_window ? win_head_bytes(g->K, n_mp, 0) : 0) + fb_covis::scratch_bytes(n_mp, n_obs, n_q, g->K) +
-                 lm_bytes(batch, g->K, n_mp));
+  return g->reserve(plan_local_map_call(g->K, n_mp, n_obs, n_q, batch, with_window != 0));
 }
 
 int fb_covis_local_map_dev(fb_covis *g, const fb_covis_map *M, const fb_local_map_args *a, void *stream) {
@@ -485,20 +467,15 @@ int fb_covis_local_map_dev(fb_covis *g, const fb_covis_map *M, const fb_local_ma
   FB_TRY(check_local_map(a));
   FB_TRY(g->ensure());
   hipStream_t s = fb::as_stream(stream);
-  const size_t K = g->K, n_mp = M->n_mp, n_obs = M->n_obs, lm = lm_bytes(a->batch, K, n_mp);
-  bool reuse = a->reuse_index && g->at.valid;
-  if (reuse) { FB_ARG(same_map(g->at.map, *M)); }                   // the caller's statement, as far as it can be checked
-  if (reuse && g->at.end + lm > g->scrBytes) reuse = false;         // growing the scratch would lose the index: rebuilt once
+  const size_t n_mp = M->n_mp;
+  LmOff lo;
+  IndexAsk ask;
+  ask.reuse = a->reuse_index != 0; ask.tail = plan_local_map(a->batch, g->K, n_mp, &lo);
   Index ix;
-  if (reuse) {
-    g->index_layout(static_cast<uint8_t *>(g->scr) + g->at.head, n_mp, n_obs, 0, &ix);
-  } else {
-    FB_TRY(g->need(fb_covis::scratch_bytes(n_mp, n_obs, 0, K) + lm));   // once: nothing below reallocates
-    FB_TRY(g->index(*M, 0, false, &ix, s));
-    g->winValid = false;                                            // the index lies where the window's header arrays were
-  }
+  uint8_t *tail;
+  FB_TRY(g->acquire(*M, ask, &ix, &tail, s));
   LmS S;
-  lm_layout(static_cast<uint8_t *>(g->scr) + g->at.end, a->batch, K, n_mp, &S);
+  lm_map(tail, lo, &S);
   fb_local_map_args A = *a;
   k_lm_vote<<<A.batch, CV_NT, 0, s>>>(*M, g->G, ix.start, ix.csr, A, S);
   k_lm_rows<<<A.batch * LM_EXPAND, CV_NT, 0, s>>>(g->G, S);
@@ -541,8 +518,8 @@ int fb_covis_local_map(fb_covis *g, const fb_covis_map *HM, const fb_local_map_a
   st.out(A.d_ref_kf, B * 4, true); st.out(A.d_n_voters, B * 4, true); st.out(A.d_overflow, B * 4, true);
   FB_TRY(st.commit(nullptr));
   A.reuse_index = 0;   // the staged arrays are new device arrays every call
+  IndexDropGuard drop(g->state);
   FB_TRY(fb_covis_local_map_dev(g, &M, &A, nullptr));
-  g->at.valid = false;   // the index is of staged arrays
   return st.fetch(nullptr);
 }
 

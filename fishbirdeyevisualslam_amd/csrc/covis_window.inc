@@ -299,25 +299,13 @@ __global__ __launch_bounds__(CV_NT) void k_win_erase(fb_covis_map M, fb_covis_kf
   if (threadIdx.x == 0) n_erase[sd] = carry;
 }
 
-size_t win_side_bytes(size_t n_pt) {
-  const size_t nb = (n_pt + 1 + CV_SCAN_TILE - 1) / CV_SCAN_TILE;
-  return 2 * up256(n_pt * 4) + up256((n_pt + 1) * 4) + up256(nb * 4);
-}
-size_t win_head_bytes(size_t K, size_t n_mp, size_t n_mpb) {
-  return 256 + 4 * up256(K * 4) + up256(K) + up256(K * 8) + win_side_bytes(n_mp) + win_side_bytes(n_mpb);
-}
-
-void win_layout(uint8_t *b, size_t K, size_t n_mp, size_t n_mpb, WinS *W) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) { uint8_t *p = b + off; off += up256(bytes); return p; };
-  W->hdr = (int32_t *)take(256);
-  W->lpos = (int32_t *)take(K * 4); W->widx = (int32_t *)take(K * 4); W->wslot = (int32_t *)take(K * 4); W->rowcnt = (int32_t *)take(K * 4);
-  W->wfixed = take(K); W->fixkey = (uint64_t *)take(K * 8);
-  const size_t n[2] = {n_mp, n_mpb};
+void win_map(uint8_t *b, const WinOff &o, WinS *W) {
+  W->hdr = (int32_t *)(b + o.hdr);
+  W->lpos = (int32_t *)(b + o.lpos); W->widx = (int32_t *)(b + o.widx); W->wslot = (int32_t *)(b + o.wslot);
+  W->rowcnt = (int32_t *)(b + o.rowcnt); W->wfixed = b + o.wfixed; W->fixkey = (uint64_t *)(b + o.fixkey);
   for (int sd = 0; sd < 2; sd++) {
-    W->side[sd].ptkey = (int32_t *)take(n[sd] * 4); W->side[sd].plist = (int32_t *)take(n[sd] * 4);
-    W->side[sd].eoff = (int32_t *)take((n[sd] + 1) * 4);
-    W->side[sd].bsum = (int32_t *)take(((n[sd] + 1 + CV_SCAN_TILE - 1) / CV_SCAN_TILE) * 4);
+    W->side[sd].ptkey = (int32_t *)(b + o.side[sd].ptkey); W->side[sd].plist = (int32_t *)(b + o.side[sd].plist);
+    W->side[sd].eoff = (int32_t *)(b + o.side[sd].eoff); W->side[sd].bsum = (int32_t *)(b + o.side[sd].bsum);
   }
 }
 
@@ -371,9 +359,7 @@ extern "C" {
 int fb_covis_reserve_window(fb_covis *g, int32_t n_mp, int32_t n_obs, int32_t n_mpb, int32_t n_bobs) {
   FB_ARG(g);
   FB_ARG(n_mp >= 0 && n_mp < INT_MAX && n_obs >= 0 && n_mpb >= 0 && n_mpb < INT_MAX && n_bobs >= 0);
-  FB_TRY(g->ensure());
-  return g->need(win_head_bytes(g->K, n_mp, n_mpb) + fb_covis::scratch_bytes(n_mp, n_obs, 0, g->K) +
-                 fb_covis::scratch_bytes(n_mpb, n_bobs, 0, g->K));
+  return g->reserve(plan_window_call(g->K, n_mp, n_obs, n_mpb, n_bobs));
 }
 
 int fb_covis_local_window_dev(fb_covis *g, const fb_covis_map *M, const fb_covis_kf_tables *T, int32_t cur_slot, int32_t with_bird,
@@ -388,19 +374,21 @@ int fb_covis_local_window_dev(fb_covis *g, const fb_covis_map *M, const fb_covis
   FB_TRY(g->ensure());
   hipStream_t s = fb::as_stream(stream);
   const size_t K = g->K, n_pt[2] = {(size_t)M->n_mp, bird ? (size_t)T->n_mpb : 0}, n_e[2] = {(size_t)M->n_obs, bird ? (size_t)T->n_bobs : 0};
-  const size_t head = win_head_bytes(K, n_pt[0], n_pt[1]), idx0 = fb_covis::scratch_bytes(n_pt[0], n_e[0], 0, K);
-  FB_TRY(g->need(head + idx0 + fb_covis::scratch_bytes(n_pt[1], n_e[1], 0, K)));   // once: nothing below reallocates
-  g->winValid = false;
-  WinS W;
-  win_layout(static_cast<uint8_t *>(g->scr), K, n_pt[0], n_pt[1], &W);
+  const CallPlan plan = plan_window_call(K, n_pt[0], n_e[0], n_pt[1], n_e[1]);
+  WinOff wo;
+  plan_window(K, n_pt[0], n_pt[1], &wo);
+  scratch_window_begins(g->state);
   fb_covis_window out = *O;
   if (!bird) { out.cap_mpb = 0; out.cap_bobs = 0; }
   const fb_covis_map maps[2] = {*M, bird ? win_bird_map(*M, *T) : *M};
   Index ix[2];
-  FB_TRY(g->index(maps[0], 0, false, &ix[0], s, head, true));
-  const fb_covis::IndexAt front_at = g->at;
-  if (bird) FB_TRY(g->index(maps[1], 0, false, &ix[1], s, head + idx0, false));
-  g->at = front_at;   // the front side's index is the one a later reuse_index reads
+  IndexAsk front, back;
+  front.head = plan.front; front.tail = plan.total - plan.bird;   // the whole call is sized here: nothing below reallocates
+  back.head = plan.bird; back.ranks = false; back.kept = false;   // the front side's index is the one a later reuse_index reads
+  FB_TRY(g->acquire(maps[0], front, &ix[0], nullptr, s));
+  if (bird) FB_TRY(g->acquire(maps[1], back, &ix[1], nullptr, s));
+  WinS W;
+  win_map(g->scr, wo, &W);
   k_win_local<<<1, CV_NT, 0, s>>>(g->G, cur_slot, T->kf_bad, W);
   const int n_sides = bird ? 2 : 1;
   for (int sd = 0; sd < n_sides; sd++) {
@@ -427,21 +415,21 @@ int fb_covis_local_window_dev(fb_covis *g, const fb_covis_map *M, const fb_covis
   }
   k_win_header<<<1, 64, 0, s>>>(W, W.side[0].eoff + n_pt[0], bird ? W.side[1].eoff + n_pt[1] : nullptr, out);
   FB_HIP(hipGetLastError());
-  g->winValid = true;
-  g->winCapKf = out.cap_kf;
+  scratch_window_done(g->state, plan.front, out.cap_kf);
   return FB_OK;
 }
 
 int fb_covis_local_window_header(fb_covis *g, fb_covis_window_header *header, int32_t *kf_slot, uint8_t *kf_fixed, void *stream) {
   FB_ARG(g && header);
-  FB_ARG(g->winValid);
+  FB_ARG(g->state.win_valid);
   hipStream_t s = fb::as_stream(stream);
-  WinS W;
-  win_layout(static_cast<uint8_t *>(g->scr), g->K, 0, 0, &W);   // the key frame arrays lie in front of the per-point ones
-  const size_t n = (size_t)std::min(g->winCapKf, g->K);
-  FB_HIP(hipMemcpyAsync(header, W.hdr, sizeof(*header), hipMemcpyDeviceToHost, s));
-  if (kf_slot && n) FB_HIP(hipMemcpyAsync(kf_slot, W.wslot, n * 4, hipMemcpyDeviceToHost, s));
-  if (kf_fixed && n) FB_HIP(hipMemcpyAsync(kf_fixed, W.wfixed, n, hipMemcpyDeviceToHost, s));
+  Regions r;
+  WinOff wo;
+  win_kf_regions(r, g->K, &wo);
+  const size_t n = (size_t)std::min(g->state.win_cap_kf, g->K);
+  FB_HIP(hipMemcpyAsync(header, g->scr + wo.hdr, sizeof(*header), hipMemcpyDeviceToHost, s));
+  if (kf_slot && n) FB_HIP(hipMemcpyAsync(kf_slot, g->scr + wo.wslot, n * 4, hipMemcpyDeviceToHost, s));
+  if (kf_fixed && n) FB_HIP(hipMemcpyAsync(kf_fixed, g->scr + wo.wfixed, n, hipMemcpyDeviceToHost, s));
   FB_HIP(hipStreamSynchronize(s));
   if (header->overflow) { fb::set_error("fb_covis_local_window: a list is longer than its capacity"); return FB_ERR_CAPACITY; }
   return FB_OK;
@@ -486,8 +474,8 @@ int fb_covis_local_window(fb_covis *g, const fb_covis_map *HM, const fb_covis_kf
   st.out(O.header, sizeof(fb_covis_window_header), false);
   FB_TRY(st.commit(nullptr));
   T.kf_Tcw = const_cast<float *>(kf_Tcw); T.mp_xw = const_cast<float *>(mp_xw); T.mpb_xw = const_cast<float *>(mpb_xw);
+  IndexDropGuard drop(g->state);   // the index is of staged arrays
   FB_TRY(fb_covis_local_window_dev(g, &M, &T, cur_slot, with_bird, &O, nullptr));
-  g->at.valid = false;   // the index is of staged arrays
   FB_TRY(st.fetch(nullptr));
   if (HO->header->overflow) { fb::set_error("fb_covis_local_window: a list is longer than its capacity"); return FB_ERR_CAPACITY; }
   return FB_OK;

@@ -1071,7 +1071,11 @@ int fb_covis_local_window_dev(fb_covis *g, const fb_covis_map *map, const fb_cov
                               int32_t with_bird, const fb_covis_window *out, void *stream);
 /* The one synchronisation: the header of the handle's last fb_covis_local_window_dev, and kf_slot / kf_fixed (host
  * arrays of that call's cap_kf entries, either may be NULL; entries past n_local + n_fixed are -1 / 0), which
- * fb_local_ba_dev and the host's odometry chain need.  FB_ERR_CAPACITY when the window overflowed a capacity.           */
+ * fb_local_ba_dev and the host's odometry chain need.  FB_ERR_CAPACITY when the window overflowed a capacity.
+ * The header lives in the handle's scratch until a later call writes there: any map-taking call that builds its index
+ * (fb_covis_update_connections*, fb_covis_keyframe_culling*, fb_covis_process_new_keyframe*, fb_covis_map_point_culling*,
+ * and local_map / correct_loop / refresh_points unless reuse_index = 1 reuses the window's index), a call that grows the
+ * scratch, or the next window.  After one of them, and before the first window, this call is FB_ERR_ARG.                 */
 int fb_covis_local_window_header(fb_covis *g, fb_covis_window_header *header, int32_t *kf_slot, uint8_t *kf_fixed, void *stream);
 /* host pointers throughout (out->header included); FB_ERR_CAPACITY as above                                             */
 int fb_covis_local_window(fb_covis *g, const fb_covis_map *map, const fb_covis_kf_tables *tables, int32_t cur_slot,

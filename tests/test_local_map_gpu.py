@@ -243,6 +243,51 @@ def test_reuse_index_after_a_window_call_and_the_host_twin(planted):
     L.fb_covis_destroy(h)
 
 
+def test_window_header_ends_with_an_index_built_over_it(planted):
+    """The window's lists lie at the start of the scratch.  A local_map that reuses the window's index keeps them; an
+    update_connections or a keyframe_culling builds its index over them, and the header call then refuses."""
+    from fishbirdeyevisualslam_amd.covis import DeviceTables
+    p, m, G, M, g, t, kf_bad, rng = planted
+    frames = [_frame(rng, m, 40)]
+    T = DeviceTables(dict(p, **P.window_tables(p, 7)))
+    e0 = G.error_count()                                                         # (the handle is shared: earlier tests count on purpose)
+    G.reserve_local_map(M.n_mp, M.n_obs, n_q=1, batch=1, with_window=True)
+    G.local_window(M, T, p["cur"], False)
+    both(G, M, t, m, frames, kf_bad, reuse=True, what="reuse behind the window")
+    rc, hd, slots, fixed = G.window_header()
+    assert rc == cabi.FB_OK and hd["n_local"] >= 1 and slots[0] == p["cur"]
+    G.update_connections(M, [p["cur"]]); g.update_connections(m, p["cur"])
+    assert G.window_header()[0] == cabi.FB_ERR_ARG, "update_connections wrote its index over the window's lists"
+    G.local_window(M, T, p["cur"], False)
+    assert G.window_header()[0] == cabi.FB_OK
+    G.keyframe_culling(M, p["cur"])
+    assert G.window_header()[0] == cabi.FB_ERR_ARG, "keyframe_culling wrote its index over the window's lists"
+    assert G.error_count() == e0
+
+
+def test_reuse_index_whose_tail_does_not_fit_rebuilds_once():
+    """A fresh handle without a reserve: update_connections sizes the scratch for its index alone, so the local map's own
+    arrays do not fit behind it.  reuse_index = 1 then rebuilds (the scratch grows), and the next one reuses."""
+    p = P.make_covis_problem(1, K=70, S=96)
+    m = ref_map(p)
+    G, M = _dev(p, p["K"])
+    g = R.Graph(p["K"], p["kf_order"])
+    G.update_connections(M, p["used"])
+    for a in p["used"]:
+        g.update_connections(m, a)
+    t = LR.Tree(g)
+    kf_bad = np.zeros(p["K"], np.uint8)
+    rng = np.random.default_rng(11)
+    frames = [_frame(rng, m, 96), _frame(rng, m, 30)]
+    got1, _ = both(G, M, t, m, frames, kf_bad, reuse=True, what="reuse that has to grow")
+    got2, _ = both(G, M, t, m, frames, kf_bad, reuse=True, what="reuse again")
+    got0, _ = both(G, M, t, m, frames, kf_bad, reuse=False, what="rebuilt")
+    for k in got0:
+        assert np.array_equal(got0[k], got1[k]) and np.array_equal(got0[k], got2[k]), k
+    assert G.error_count() == 0
+    G.close()
+
+
 def test_tree_maintenance_chain_against_the_model():
     import torch
     p = P.make_covis_problem(1, K=70, S=96)
