@@ -79,6 +79,28 @@ def test_three_maxima():
     h = [0] * 30
     h[3] = h[4] = h[8] = 40  # ties: strict '>' cascade keeps the earliest bin first
     assert _maxima(h) == [3, 4, 8]
+    hist = lambda d: [d.get(i, 0) for i in range(30)]
+    # on the rule (ORBmatcher.cc:1937,1942): 0.1f*(float)max1 rounds to the float max1/10 exactly (0.1f is 1.5e-8 too big,
+    # half a float step at 1, 2, 3 is 6e-8 or more), and max2 < max1/10 is false when they are equal: the bin stays
+    assert _maxima(hist({0: 10, 4: 1})) == [0, 4, -1]          # 1 < 1.0f false
+    assert _maxima(hist({0: 20, 4: 2})) == [0, 4, -1]          # 2 < 2.0f false
+    assert _maxima(hist({0: 30, 4: 3})) == [0, 4, -1]          # 3 < 3.0f false
+    assert _maxima(hist({0: 11, 4: 1})) == [0, -1, -1]         # 1 < 1.1f
+    assert _maxima(hist({0: 21, 4: 2})) == [0, -1, -1]         # 2 < 2.1f
+    assert _maxima(hist({0: 10, 4: 5, 8: 1})) == [0, 4, 8]     # the same rule for the third
+    assert _maxima(hist({0: 20, 4: 5, 8: 2})) == [0, 4, 8]
+    assert _maxima(hist({0: 30, 4: 5, 8: 3})) == [0, 4, 8]
+    assert _maxima(hist({0: 11, 4: 5, 8: 1})) == [0, 4, -1]
+    assert _maxima(hist({0: 21, 4: 5, 8: 2})) == [0, 4, -1]
+    # ties, strict '>' at :1914,:1923,:1930: a bin that only equals a place does not take it, so the earlier bin stays ahead
+    assert _maxima(hist({1: 4, 3: 4, 6: 4, 9: 4})) == [1, 3, 6]        # a fourth bin equal to the third is dropped
+    assert _maxima(hist({1: 5, 3: 4, 6: 4, 9: 4})) == [1, 3, 6]        # tie for second among three
+    assert _maxima(hist({3: 4, 6: 4, 9: 4, 11: 5})) == [11, 3, 6]      # 11 takes first and pushes 3, 6 down; 9 falls out
+    assert _maxima(hist({1: 5, 3: 4, 6: 2, 9: 2})) == [1, 3, 6]        # tie for third
+    # 6 leads, 9 (equal) takes second; 10 then 11 push them down: 6 is third, 9 falls out although it equals 6
+    assert _maxima(hist({6: 2, 9: 2, 10: 5, 11: 4})) == [10, 11, 6]
+    assert _maxima(hist({3: 5})) == [3, -1, -1]
+    assert _maxima(hist({2: 5, 7: 3})) == [2, 7, -1]
 
 
 def test_huber_kernel():
