@@ -8,6 +8,7 @@
  * Edges are visited in insertion order (front, then bird) as g2o does after
  * sortVectorContainers (sparse_optimizer.cpp:166-190,482-487).
  */
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -160,6 +161,14 @@ inline void note_margin(float chi2, double thr) {
   g_decisions++;
 }
 
+// Per round of the four (Optimizer.cc:391,619,785): edges flagged at its end, and edges flagged after the round before that
+// this round clears again; rounds run.
+long g_rounds = 0, g_front_flagged[4], g_bird_flagged[4], g_front_readmitted[4], g_bird_readmitted[4];
+void round_trace_reset() {
+  g_rounds = 0;
+  for (int r = 0; r < 4; r++) g_front_flagged[r] = g_bird_flagged[r] = g_front_readmitted[r] = g_bird_readmitted[r] = 0;
+}
+
 int pose_opt_one(const fb_pose_opt_args *A, int bidx) {
   const int mode = A->mode;
   const size_t fo = (size_t)bidx * A->front_stride, bo = (size_t)bidx * A->bird_stride;
@@ -206,6 +215,8 @@ int pose_opt_one(const fb_pose_opt_args *A, int bidx) {
   for (int it = 0; it < 4; it++) {
     P.T = T0;           // vSE3->setEstimate(toSE3Quat(pFrame->mTcw))
     P.initialize();     // initializeOptimization(0)
+    g_lm_trace.ev('/');
+    g_rounds++;
     lm_optimize(P, 10);
     nBad = 0;
     for (int k = 0; k < nf; k++) {
@@ -217,6 +228,8 @@ int pose_opt_one(const fb_pose_opt_args *A, int bidx) {
       if (mode == FB_POSE_FRONT) bad = chi2 > chi2Mono;                         // :410-412
       else bad = chi2 > chi2Mono * ((double)A->wF + 1e-9);                       // :645
       note_margin(chi2, mode == FB_POSE_FRONT ? (double)chi2Mono : chi2Mono * ((double)A->wF + 1e-9));
+      if (it > 0 && e.level == 1 && !bad) g_front_readmitted[it]++;
+      if (bad) g_front_flagged[it]++;
       if (bad) { A->front_outlier[fo + i] = 1; e.level = 1; nBad++; }
       else { A->front_outlier[fo + i] = 0; e.level = 0; }
       if (it == 2) e.robust = false;
@@ -229,6 +242,8 @@ int pose_opt_one(const fb_pose_opt_args *A, int bidx) {
       const float chi2 = (float)PoseProblem::chi2(e);
       const float chi2Bad = (float)(chi2Bird * ((double)A->wB + 1e-9));          // :672, :806
       note_margin(chi2, (double)chi2Bad);
+      if (it > 0 && e.level == 1 && !(chi2 > chi2Bad)) g_bird_readmitted[it]++;
+      if (chi2 > chi2Bad) g_bird_flagged[it]++;
       if (chi2 > chi2Bad) { A->bird_outlier[bo + i] = 1; e.level = 1; nBadBird++; }
       else { A->bird_outlier[bo + i] = 0; e.level = 0; }
       if (it == 2) e.robust = false;
@@ -254,6 +269,29 @@ int orc_pose_opt(const fb_pose_opt_args *A) {
 
 void orc_pose_margin_reset() { g_min_margin = 1e300; g_decisions = 0; }
 int orc_pose_margin_get(double *min_margin, long *decisions) { *min_margin = g_min_margin; *decisions = g_decisions; return FB_OK; }
+
+// What the LM schedule and the rounds did since the last reset.  counters[0..7] = accepted steps, rejected steps, exits by
+// qmax == 10, by rho == 0, by nBadLM >= 3, failed solves, early returns for no active edge, rounds run; then for each
+// round r, counters[8 + 4 r ..] = front edges flagged, bird edges flagged, front edges re-admitted, bird edges re-admitted.
+// events (capacity cap, NUL-terminated) gets the event string of se3_oracle.h; returns its full length.
+void orc_lm_trace_reset() { g_lm_trace = LMTrace(); round_trace_reset(); }
+long orc_lm_trace_get(long *counters, char *events, long cap) {
+  const LMTrace &t = g_lm_trace;
+  const long head[8] = {t.accepted, t.rejected, t.exit_qmax, t.exit_rho0, t.exit_nbad, t.failed_solve, t.no_active, g_rounds};
+  for (int i = 0; i < 8; i++) counters[i] = head[i];
+  for (int r = 0; r < 4; r++) {
+    counters[8 + 4 * r] = g_front_flagged[r];
+    counters[9 + 4 * r] = g_bird_flagged[r];
+    counters[10 + 4 * r] = g_front_readmitted[r];
+    counters[11 + 4 * r] = g_bird_readmitted[r];
+  }
+  if (events && cap > 0) {
+    const long n = std::min<long>((long)t.events.size(), cap - 1);
+    std::memcpy(events, t.events.data(), (size_t)n);
+    events[n] = 0;
+  }
+  return (long)t.events.size();
+}
 
 // known-answer hooks -------------------------------------------------------------
 int orc_se3_exp(const double *u6, double *q4t3) {  // -> qx,qy,qz,qw,tx,ty,tz

@@ -140,7 +140,7 @@ inline SE3 se3_exp(const double u[6]) {
     for (int i = 0; i < 9; i++) { R[i] = I[i] + Om[i] + Om2[i]; V[i] = R[i]; }  // sic, no 1/2
   } else {
     const double s = std::sin(theta), c = std::cos(theta);
-    const double a = s / theta, b = (1 - c) / (theta * theta), d = (theta - s) / (theta * theta * theta);
+    const double a = s / theta, b = (1 - c) / (theta * theta), d = (theta - s) / std::pow(theta, 3);
     for (int i = 0; i < 9; i++) {
       R[i] = I[i] + a * Om[i] + b * Om2[i];
       V[i] = I[i] + b * Om[i] + d * Om2[i];
@@ -283,6 +283,17 @@ struct LMState {
   int nBad = 0;
 };
 
+// Test instrumentation: what the LM schedule did since the last reset.  Counters, and the same story as a string of events:
+// 'A' accepted step, 'R' rejected step ('F' = rejected because the solve failed), then how the iteration left: 'q' qmax ==
+// 10, 'z' rho == 0, 'b' nBad >= 3, '.' OK; 'n' = optimize() returned at once for want of an active edge; callers add their
+// own marks (pose_oracle.cpp: '/' in front of every round).
+struct LMTrace {
+  long accepted = 0, rejected = 0, exit_qmax = 0, exit_rho0 = 0, exit_nbad = 0, failed_solve = 0, no_active = 0;
+  std::vector<char> events;
+  void ev(char c) { if (events.size() < (1u << 20)) events.push_back(c); }
+};
+inline LMTrace g_lm_trace;
+
 // OptimizationAlgorithmLevenberg::solve, optimization_algorithm_levenberg.cpp:61-164.
 // returns 0 = OK, 1 = Terminate
 inline int lm_solve(LMProblem &P, LMState &S, int iteration) {
@@ -312,7 +323,10 @@ inline int lm_solve(LMProblem &P, LMState &S, int iteration) {
     scale += 1e-3;
     rho /= scale;
     if (trace) std::fprintf(stderr, "[orc]  it=%d q=%d lambda=%.17g tempChi=%.17g scale=%.17g rho=%.17g ok=%d\n", iteration, qmax, S.lambda, tempChi, scale, rho, (int)ok2);
+    if (!ok2) g_lm_trace.failed_solve++;
     if (rho > 0 && std::isfinite(tempChi)) {
+      g_lm_trace.accepted++;
+      g_lm_trace.ev('A');
       double alpha = 1. - std::pow((2 * rho - 1), 3);
       alpha = std::min(alpha, 2. / 3.);
       const double scaleFactor = std::max(1. / 3., alpha);
@@ -321,22 +335,29 @@ inline int lm_solve(LMProblem &P, LMState &S, int iteration) {
       currentChi = tempChi;
       P.discardTop();
     } else {
+      g_lm_trace.rejected++;
+      g_lm_trace.ev(ok2 ? 'R' : 'F');
       S.lambda *= S.ni;
       S.ni *= 2;
       P.pop();
     }
     qmax++;
   } while (rho < 0 && qmax < 10 && !P.terminate());
-  if (qmax == 10 || rho == 0) return 1;
+  if (qmax == 10 || rho == 0) {
+    if (qmax == 10) { g_lm_trace.exit_qmax++; g_lm_trace.ev('q'); }
+    else { g_lm_trace.exit_rho0++; g_lm_trace.ev('z'); }
+    return 1;
+  }
   if ((iniChi - currentChi) * 1e3 < iniChi) S.nBad++;
   else S.nBad = 0;
-  if (S.nBad >= 3) return 1;
+  if (S.nBad >= 3) { g_lm_trace.exit_nbad++; g_lm_trace.ev('b'); return 1; }
+  g_lm_trace.ev('.');
   return 0;
 }
 
 // SparseOptimizer::optimize, sparse_optimizer.cpp:354-419
 inline int lm_optimize(LMProblem &P, int iterations) {
-  if (!P.hasActive()) return -1;
+  if (!P.hasActive()) { g_lm_trace.no_active++; g_lm_trace.ev('n'); return -1; }
   LMState S;
   int cj = 0;
   bool ok = true;

@@ -8,6 +8,7 @@ import pytest
 
 import hip_lib as H
 import oracle_lib as O
+import pose_cases as PC
 from fishbirdeyevisualslam_amd import cabi, problems as P, synth
 
 pytestmark = pytest.mark.gpu
@@ -98,7 +99,8 @@ def test_pose_opt_other_kernel_variants(variant):
     env = dict(os.environ, FB_POSE_NT=variant)
     here = os.path.dirname(os.path.abspath(__file__))
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(here, "test_pose_gpu.py"), "-q", "-x", "-m", "gpu",
-                        "-k", "config3 or weights_and_masks or register_slot_boundary", "-p", "no:cacheprovider"],
+                        "-k", "config3 or weights_and_masks or register_slot_boundary or constructed_case or case_batch or "
+                        "generic_schedule_writes_the_bird_mask", "-p", "no:cacheprovider"],
                        env=env, cwd=os.path.dirname(here), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
 
@@ -144,7 +146,92 @@ def test_pose_opt_register_slot_boundary():
     _compare(out_o, out_h, cabi.FB_POSE_FRONT_BIRD)
     for b in range(5):
         n = len(fv[b])
-        # the front masks compared are not trivial (the generator's bird noise never reaches the bird threshold), and slots
-        # without an edge keep the prefill value
+        # the front masks compared are not trivial, and slots without an edge keep the prefill value
         assert 0 < np.count_nonzero(out_o["front_outlier"][b, :n][fv[b] == 1]) < n
         assert np.all(out_h["front_outlier"][b, :n][fv[b] == 0] == 9)
+
+
+# ---- the constructed cases of tests/pose_cases.py (proven on the CPU by tests/test_pose_cases.py) ---------------------------
+CASES = PC.cases()
+
+
+def _assert_case_masks_not_trivial(case, out_o, b=0):
+    """what makes the comparison of a case's masks worth something, on the oracle's side of it"""
+    n_b = len(case["prob"]["bird_xw"])
+    if "bird_flagged" in case["expect"] or "displaced_mixed" in case["expect"] or "displaced_all_flagged" in case["expect"]:
+        assert 0 < np.count_nonzero(out_o["bird_outlier"][b, :n_b] == 1) < n_b, case["id"]
+    if "bird_prefill_kept" in case["expect"]:
+        assert np.count_nonzero(out_o["bird_outlier"][b, :n_b] == PC.PREFILL) > 0, case["id"]
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c["id"] for c in CASES])
+def test_pose_opt_constructed_case(case):
+    out_o, out_h = _run([case["prob"]], **case["kw"])
+    _compare(out_o, out_h, case["kw"]["mode"])
+    # both masks whatever the mode: the one a mode does not own must come back as it went in
+    np.testing.assert_array_equal(out_h["front_outlier"], out_o["front_outlier"])
+    np.testing.assert_array_equal(out_h["bird_outlier"], out_o["bird_outlier"])
+    _assert_case_masks_not_trivial(case, out_o)
+
+
+def _front_bird_case_batch():
+    """every FRONT_BIRD case at unit weights as one batch: (cases, problems, keyword arguments with per-frame bird masks)"""
+    cs = [c for c in CASES if c["kw"]["mode"] == cabi.FB_POSE_FRONT_BIRD and set(c["kw"]) <= {"mode", "bird_valid", "bird_outlier_in"}]
+    assert len(cs) >= 12 and any("bird_outlier_in" in c["kw"] for c in cs) and any("bird_valid" in c["kw"] for c in cs)
+    bv = [c["kw"]["bird_valid"][0] if "bird_valid" in c["kw"] else np.ones(len(c["prob"]["bird_xw"]), np.uint8) for c in cs]
+    bo = [c["kw"]["bird_outlier_in"][0] if "bird_outlier_in" in c["kw"] else np.zeros(len(c["prob"]["bird_xw"]), np.uint8) for c in cs]
+    return cs, [c["prob"] for c in cs], dict(mode=cabi.FB_POSE_FRONT_BIRD, bird_valid=bv, bird_outlier_in=bo)
+
+
+def test_pose_opt_case_batch_of_64_takes_the_throughput_kernel():
+    """k_pose_opt_regs<256, 256> (batches of 64 or more) on the constructed cases mixed with ordinary frames"""
+    cs, probs, kw = _front_bird_case_batch()
+    extra = [synth.make_pose_problem(3600 + i, n_front=150 + 7 * (i % 9), n_bird=70 + 5 * (i % 7)) for i in range(64 - len(cs))]
+    order = np.argsort(synth.rng(11).random(64), kind="stable")            # cases spread among the ordinary frames
+    allp = probs + extra
+    bv = kw["bird_valid"] + [np.ones(len(p["bird_xw"]), np.uint8) for p in extra]
+    bo = kw["bird_outlier_in"] + [np.zeros(len(p["bird_xw"]), np.uint8) for p in extra]
+    out_o, out_h = _run([allp[i] for i in order], mode=cabi.FB_POSE_FRONT_BIRD, bird_valid=[bv[i] for i in order],
+                        bird_outlier_in=[bo[i] for i in order])
+    _compare(out_o, out_h, cabi.FB_POSE_FRONT_BIRD)
+    for b, i in enumerate(order):
+        if i < len(cs):
+            _assert_case_masks_not_trivial(cs[i], out_o, b)
+
+
+def test_pose_opt_case_batch_dev_on_a_callers_stream():
+    """fb_pose_opt_batch_dev takes bird_outlier as in/out device memory: flags set on entry, prefilled slots without an edge"""
+    import ctypes as C
+    from device_mirror import Mirror, _lib, _stream, _sync
+    cs, probs, kw = _front_bird_case_batch()
+    a, out_o, keep = P.pose_args(probs, **kw)
+    O.call("orc_pose_opt", a)
+    a2, out_h, keep2 = P.pose_args(probs, **kw)
+    mir = Mirror(out_h, keep2)
+    d = mir.struct(a2)
+    assert _lib().fb_pose_opt_batch_dev(C.byref(d), _stream()) == 0, _lib().fb_last_error()
+    _sync()
+    out_d = {k: mir.host(v) for k, v in out_h.items()}
+    _compare(out_o, out_d, cabi.FB_POSE_FRONT_BIRD)
+    for b, c in enumerate(cs):
+        _assert_case_masks_not_trivial(c, out_o, b)
+
+
+def test_pose_opt_generic_schedule_writes_the_bird_mask():
+    """One bird edge more than the register slots hold: the frame leaves through the in-kernel generic schedule, the only
+    other place that writes bird_outlier, with bird outliers displaced to both sides of the gate and holes in bird_valid."""
+    import os
+    B = 1536 if os.environ.get("FB_POSE_NT") in ("256", "512") else 1344
+    holes = 37
+    p = synth.make_pose_problem(3700, n_front=300, n_bird=B + 1 + holes)
+    p = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in p.items()}
+    PC._displace_bird(p, synth.rng(3701), np.nonzero(p["bird_is_outlier"])[0], 0.3, 2.0)
+    bv = PC.spread_valid(B + 1 + holes, holes)
+    bo = np.where(bv == 0, PC.PREFILL, 0).astype(np.uint8)
+    bo[np.nonzero(bv)[0][::5]] = 1                                         # and flags set on entry
+    out_o, out_h = _run([p], mode=cabi.FB_POSE_FRONT_BIRD, bird_valid=[bv], bird_outlier_in=[bo])
+    _compare(out_o, out_h, cabi.FB_POSE_FRONT_BIRD)
+    flags = out_o["bird_outlier"][0]
+    disp = p["bird_displaced"][bv[p["bird_displaced"]] == 1]
+    assert 0 < np.count_nonzero(flags[disp] == 1) < len(disp)
+    assert np.all(out_h["bird_outlier"][0][bv == 0] == PC.PREFILL)
