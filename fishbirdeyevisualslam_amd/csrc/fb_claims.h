@@ -8,7 +8,7 @@
  * the rounds converge to exactly the serial result (query 0 is final after round 0, query q after at most round q, hence
  * the bound of more()); in practice 2-3 rounds.  The rounds stop when no query changed its mind.
  *
- *   fb::Claims<AT> C(s_flags, lds, tStride, qStride, blocked0, nTargets, nQueries);
+ *   fb::Claims<AT> C(s_flags, owners, tStride, assigns, qStride, blocked0, nTargets, nQueries);   // ClaimsLds, match_plan.h
  *   C.start();
  *   for (int round = 0; C.more(round); round++) {
  *     C.begin_round();
@@ -51,11 +51,6 @@ struct Claims {
                                     const uint8_t *blocked, int nTargets, int nQueries)
       : f(flags), ownerA(owners), ownerB(owners + tStride), assignA(assigns), assignB(assigns + qStride),
         blocked0(blocked), nT(nTargets), nQ(nQueries) {}
-  // the usual carve: the assign arrays follow the owner arrays
-  __device__ __forceinline__ Claims(ClaimFlags &flags, void *lds, int tStride, int qStride, const uint8_t *blocked,
-                                    int nTargets, int nQueries)
-      : Claims(flags, static_cast<int *>(lds), tStride, reinterpret_cast<AT *>(static_cast<int *>(lds) + 2 * tStride),
-               qStride, blocked, nTargets, nQueries) {}
 
   __device__ __forceinline__ void reset(int *owner) const {
     for (int i = threadIdx.x; i < nT; i += blockDim.x) owner[i] = (blocked0 && blocked0[i]) ? BLOCKED : NONE;

@@ -49,15 +49,6 @@ int check_device();  // FB_OK or FB_ERR_NODEVICE (sets error)
     if (rc_ != FB_OK) return rc_; \
   } while (0)
 
-// LDS capacity of a workgroup (160 KiB on gfx950): the matchers that stage a whole frame check their plan against it
-inline int check_lds(size_t bytes, const char *what) {
-  if (bytes > 160 * 1024) {
-    set_error("%s: frame too large for the LDS-staged matcher (%zu B > 160 KiB)", what, bytes);
-    return FB_ERR_CAPACITY;
-  }
-  return FB_OK;
-}
-
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
 // ---- per-kernel timing (fb_prof_* in include/fishbird.h) ----

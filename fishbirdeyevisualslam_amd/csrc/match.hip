@@ -30,6 +30,7 @@
 #include "fb_frame_geom.h"
 #include "fb_primitives.h"
 #include "fb_rot_hist.h"
+#include "match_plan.h"
 
 namespace {
 
@@ -45,7 +46,6 @@ struct TargetLds {  // target frame staged in LDS
   const uint16_t *cs;    // [ncell+1]
   const uint32_t *items; // [n] key point index | octave << 16 in cell order: the level test of a walk needs no second load
   uint32_t descLds;      // LDS byte address of the descriptor table, or DESC_NOT_IN_LDS (then `desc` points into HBM / L2)
-  uint8_t *rest;         // first LDS byte after the staged frame (16-B aligned): the kernel's own arrays
 };
 constexpr uint32_t DESC_NOT_IN_LDS = 0xFFFFFFFFu;
 
@@ -152,24 +152,6 @@ __device__ __forceinline__ void xform(const float *T, const float *X, float *o) 
   for (int r = 0; r < 3; r++) o[r] = ((T[r * 4 + 0] * X[0] + T[r * 4 + 1] * X[1]) + T[r * 4 + 2] * X[2]) + T[r * 4 + 3];
 }
 
-// LDS carve for a target frame of n keypoints / ncell cells. All offsets 16-B aligned.
-struct Carve {
-  size_t desc, xy, oct, cs, items, end;
-  bool hasOct;
-  // withDesc = false: the descriptor table stays in HBM/L2 (frames too large for LDS, e.g. the 2*nFeatures
-  // initialisation extractor); only the key point positions, octaves and the grid are staged
-  __host__ __device__ Carve(int n, int ncell, bool withDesc = true, bool withOct = true) {
-    auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    hasOct = withOct;
-    desc = 0;
-    xy = up(desc + (withDesc ? (size_t)n * 32 : 0));
-    oct = up(xy + (size_t)n * 8);
-    cs = up(oct + (withOct ? (size_t)n : 0));
-    items = up(cs + (size_t)(ncell + 1) * 2);
-    end = up(items + (size_t)n * 4);
-  }
-};
-
 __device__ __forceinline__ TargetLds stage_target(uint8_t *smem, const Carve &cv, int n, int ncell,
                                                   const fb_keypoint *kps, const uint8_t *desc, const int32_t *cs,
                                                   const int32_t *items, bool withDesc = true) {
@@ -196,16 +178,20 @@ __device__ __forceinline__ TargetLds stage_target(uint8_t *smem, const Carve &cv
     litems[i] = (uint32_t)idx | ((uint32_t)(kps[idx].octave & 0xff) << 16);
   }
   TargetLds T{withDesc ? reinterpret_cast<const uint4 *>(ldesc) : src, lxy, cv.hasOct ? loct : nullptr, lcs, litems,
-              withDesc ? (uint32_t)(uintptr_t)ldesc : DESC_NOT_IN_LDS, smem + cv.end};
+              withDesc ? (uint32_t)(uintptr_t)ldesc : DESC_NOT_IN_LDS};
   return T;
 }
 
 // the staged target of the argument structs that call it cur_* (frame b of the batch)
 template <typename Args>
-__device__ __forceinline__ TargetLds stage_cur(uint8_t *smem, const Args &A, int b, bool descInLds, bool withOct = true) {
+__device__ __forceinline__ Carve cur_carve(const Args &A, bool descInLds, bool withOct = true) {
+  return Carve(A.cur_stride, A.grid.cols * A.grid.rows, descInLds, withOct);
+}
+template <typename Args>
+__device__ __forceinline__ TargetLds stage_cur(uint8_t *smem, const Carve &cv, const Args &A, int b, bool descInLds) {
   const int ncell = A.grid.cols * A.grid.rows;
   const size_t co = (size_t)b * A.cur_stride;
-  return stage_target(smem, Carve(A.cur_stride, ncell, descInLds, withOct), A.n_cur[b], ncell, A.cur_kps + co, A.cur_desc + co * 32,
+  return stage_target(smem, cv, A.n_cur[b], ncell, A.cur_kps + co, A.cur_desc + co * 32,
                       A.cur_cell_start + (size_t)b * (ncell + 1), A.cur_cell_items + co, descInLds);
 }
 
@@ -216,7 +202,6 @@ __device__ __forceinline__ TargetLds stage_cur(uint8_t *smem, const Args &A, int
 // (sorted by distance, ties in grid-walk order = the reference's "first minimum wins"), so the grid walk and the
 // Hamming distances are done once; a query whose cached candidates are all taken and whose cache is incomplete
 // falls back to the full walk.  cacheK = 0 (LDS too small) keeps the full walk every round.
-constexpr int CACHE_K = 4;
 // (Measured and dropped, round 3: round 0 -- projection, grid walk and distances of every query -- is 78 % of this kernel for
 // one frame (profiles/probes/m3_stamps.py), so it was moved to its own grid of 256-query workgroups with the serial rule
 // resolved on candidate lists afterwards, as M2 does.  Same results, no gain: 94 instead of 97 us per frame at batch 1 (a
@@ -234,29 +219,31 @@ __device__ unsigned long long g_m3_stamps[8];  // probe build only (block 0): st
 #endif
 
 // The body for frame b on a staged target T, whose cell lists came from the caller's arrays (k_proj_frame) or straight from
-// the LDS of the grid build (k_frame_tail_front).  Nothing of T.rest is written before the first barrier here, so a caller
-// may have staged from scratch arrays that lie there.  tail(matchL) runs once, by every thread, behind the stores of the
+// the LDS of the grid build (k_frame_tail_front).  `own` = the first LDS byte behind the staged frame (Carve::end): none of the
+// arrays there (M3Lds) is written before the first barrier here, so a caller may have staged from scratch arrays that lie there.  tail(matchL) runs once, by every thread, behind the stores of the
 // final match array (matchL[i], i < ncur, in LDS).
 template <typename Tail>
-__device__ __forceinline__ void proj_frame_body(const fb_proj_frame_args &A, const TargetLds &T, int b, int cacheK, Tail &&tail) {
+__device__ __forceinline__ void proj_frame_body(const fb_proj_frame_args &A, uint8_t *smem, size_t own, const TargetLds &T, int b,
+                                                int cacheK, Tail &&tail) {
   // (its callbacks never ask for a target key point's octave by index: no by-index octave array in LDS, Carve::withOct = false)
   typedef unsigned short u16;
   const int tid = threadIdx.x, nt = blockDim.x;
   const size_t co = (size_t)b * A.cur_stride, lo = (size_t)b * A.last_stride;
   const int ncur = A.n_cur[b], nlast = A.n_last[b];
   M3_T0()
-  int *owners = reinterpret_cast<int *>(T.rest);         // [2][cur_stride]
-  uint32_t *cache = reinterpret_cast<uint32_t *>(owners + 2 * A.cur_stride);  // [last_stride][cacheK]  dist << 16 | idx
-  u16 *assigns = reinterpret_cast<u16 *>(cache + (size_t)A.last_stride * cacheK);  // [2][last_stride]
-  u16 *perm = assigns + 2 * A.last_stride;               // [last_stride] queries sorted by octave (processing order)
-  uint8_t *meta = reinterpret_cast<uint8_t *>(perm + A.last_stride);  // [last_stride] cached count | complete << 7
-  __shared__ fb::ClaimFlags s_cf;
-  __shared__ int s_oct[FB_MAX_LEVELS + 1];
-  __shared__ fb::RotHist s_rot;
-  __shared__ float s_T[12];
+  M3Lds L;
+  m3_layout(L, own, A.cur_stride, A.last_stride, cacheK);
+  uint32_t *cache = lds_at<uint32_t>(smem, L.cache);
+  u16 *perm = lds_at<u16>(smem, L.perm);
+  uint8_t *meta = lds_at<uint8_t>(smem, L.meta);
+  struct Shared { fb::ClaimFlags cf; int oct[FB_MAX_LEVELS + 1]; fb::RotHist rot; float T[12]; };
+  __shared__ Shared s_;
+  static_assert(up16(sizeof(Shared)) == STATIC_M3, "match_plan.h");
+  auto &s_cf = s_.cf; auto &s_oct = s_.oct; auto &s_rot = s_.rot; auto &s_T = s_.T;
   if (tid < 12) s_T[tid] = A.cur_Tcw[(size_t)b * 12 + tid];
   if (tid <= FB_MAX_LEVELS) s_oct[tid] = 0;
-  fb::Claims<u16> C(s_cf, owners, A.cur_stride, assigns, A.last_stride, A.cur_blocked ? A.cur_blocked + co : nullptr, ncur, nlast);
+  fb::Claims<u16> C(s_cf, lds_at<int>(smem, L.owners), A.cur_stride, lds_at<u16>(smem, L.assigns), A.last_stride,
+                    A.cur_blocked ? A.cur_blocked + co : nullptr, ncur, nlast);
   float thEff = A.th;   // the second attempt (retry_below > 0 and fewer matches than that) searches with retry_th
   __syncthreads();
   M3_TICK(0)
@@ -394,8 +381,9 @@ __device__ __forceinline__ void proj_frame_body(const fb_proj_frame_args &A, con
 __global__ __launch_bounds__(MATCH_THREADS) void k_proj_frame(fb_proj_frame_args A, int cacheK, int descInLds) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int b = blockIdx.x;
-  const TargetLds T = stage_cur(smem, A, b, descInLds != 0, false);
-  proj_frame_body(A, T, b, cacheK, [](const int *) {});
+  const Carve cv = cur_carve(A, descInLds != 0, false);
+  const TargetLds T = stage_cur(smem, cv, A, b, descInLds != 0);
+  proj_frame_body(A, smem, cv.end, T, b, cacheK, [](const int *) {});
 }
 
 // ---------------------------------------------------------------------------------------
@@ -408,14 +396,18 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_proj_kf(fb_proj_kf_args A, in
   const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
   const size_t co = (size_t)b * A.cur_stride, ko = (size_t)b * A.kf_stride;
   const int ncur = A.n_cur[b], nkf = A.n_kf[b];
-  const TargetLds T = stage_cur(smem, A, b, descInLds != 0);
-  __shared__ fb::ClaimFlags s_cf;
-  __shared__ fb::RotHist s_rot;
-  __shared__ float s_T[12], s_Ow[3];
+  const Carve cv = cur_carve(A, descInLds != 0);
+  const TargetLds T = stage_cur(smem, cv, A, b, descInLds != 0);
+  struct Shared { fb::ClaimFlags cf; fb::RotHist rot; float T[12], Ow[3]; };
+  __shared__ Shared s_;
+  static_assert(up16(sizeof(Shared)) == STATIC_M4, "match_plan.h");
+  auto &s_cf = s_.cf; auto &s_rot = s_.rot; auto &s_T = s_.T; auto &s_Ow = s_.Ow;
   if (tid < 12) s_T[tid] = A.cur_Tcw[(size_t)b * 12 + tid];
   if (tid == 64) fb::camera_centre(A.cur_Tcw + (size_t)b * 12, s_Ow);
-  // owners [2][cur_stride] ints, then the chosen slot of each point [2][kf_stride] in 16 bits
-  fb::Claims<uint16_t> C(s_cf, T.rest, A.cur_stride, A.kf_stride, A.cur_blocked ? A.cur_blocked + co : nullptr, ncur, nkf);
+  ClaimsLds L;  // the chosen slot of each point in 16 bits
+  claims_layout(L, cv.end, A.cur_stride, A.kf_stride, 2, CLAIMS_U16_SLACK);
+  fb::Claims<uint16_t> C(s_cf, lds_at<int>(smem, L.owners), A.cur_stride, lds_at<uint16_t>(smem, L.assigns), A.kf_stride,
+                         A.cur_blocked ? A.cur_blocked + co : nullptr, ncur, nkf);
   C.start();
 
   // the geometric gates are cheap and are re-evaluated every round instead of being stored per point
@@ -488,45 +480,64 @@ struct M2Pick {
 #ifdef FB_MATCH_STAMPS
 __device__ int g_m2_rounds[4];  // probe build only: rounds / queries in view / launches of k_proj_points (block 0)
 #endif
-__global__ __launch_bounds__(MATCH_THREADS) void k_proj_points(fb_proj_points_args A, int descInLds) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+// the full grid walk of query q (point e = mo + q) against last round's claims
+__device__ __forceinline__ void m2_walk(const fb_proj_points_args &A, const TargetLds &T, const fb::Claims<int> &C, size_t e, int q,
+                                        M2Pick &pick) {
+  const int lvl = A.mp_level[e];
+  uint32_t d[8];
+  fb::load_desc(A.mp_desc + e * 32, d);
+  for_area<false>(A.grid, T, A.mp_proj[e * 2], A.mp_proj[e * 2 + 1], m2_radius(A, e, A.th != 1.0f, lvl), lvl - 1, lvl, [&](int idx) {
+    if (!C.taken(idx, q)) pick.take(idx, target_hamming(T, d, idx), (int)T.oct[idx]);
+  });
+}
+
+// M2 behind the staging of frame b: the rounds of the fixed point, the commit and the store of the results.  `own` = the
+// first LDS byte behind the staged frame (ClaimsLds).  pick(C, q) = how a query picks given last round's claims: its target
+// or NONE.  count: the probe counters (k_proj_points only).
+template <typename Pick>
+__device__ __forceinline__ void m2_rounds(const fb_proj_points_args &A, uint8_t *smem, size_t own, int b, bool count, Pick &&pick) {
+  const int tid = threadIdx.x, nt = blockDim.x;
   const size_t co = (size_t)b * A.cur_stride, mo = (size_t)b * A.mp_stride;
   const int ncur = A.n_cur[b], nmp = A.n_mp[b];
-  const TargetLds T = stage_cur(smem, A, b, descInLds != 0);
   __shared__ fb::ClaimFlags s_cf;
-  fb::Claims<int> C(s_cf, T.rest, A.cur_stride, A.mp_stride, A.cur_blocked ? A.cur_blocked + co : nullptr, ncur, nmp);
+  static_assert(up16(sizeof(s_cf)) == STATIC_M2, "match_plan.h");
+  ClaimsLds L;
+  claims_layout(L, own, A.cur_stride, A.mp_stride, 4, 0);
+  fb::Claims<int> C(s_cf, lds_at<int>(smem, L.owners), A.cur_stride, lds_at<int>(smem, L.assigns), A.mp_stride,
+                    A.cur_blocked ? A.cur_blocked + co : nullptr, ncur, nmp);
   C.start();
-  const bool bFactor = A.th != 1.0f;
   for (int round = 0; C.more(round); round++) {
     C.begin_round();
     for (int q = tid; q < nmp; q += nt) {
-      int best = NONE;
-      if (A.mp_track[mo + q]) {
-        const int lvl = A.mp_level[mo + q];
-        uint32_t d[8];
-        fb::load_desc(A.mp_desc + (mo + q) * 32, d);
-        M2Pick pick;
-        for_area<false>(A.grid, T, A.mp_proj[(mo + q) * 2], A.mp_proj[(mo + q) * 2 + 1], m2_radius(A, mo + q, bFactor, lvl),
-                        lvl - 1, lvl, [&](int idx) {
-          if (!C.taken(idx, q)) pick.take(idx, target_hamming(T, d, idx), (int)T.oct[idx]);
-        });
-        best = pick.result(A.matcher.nnratio);
-      }
+      const int best = pick(C, q);
       C.submit(q, best, best != NONE && A.mp_obs_pos[mo + q]);
     }
     const bool done = C.end_round();
 #ifdef FB_MATCH_STAMPS
-    if (b == 0 && tid == 0) atomicAdd(&g_m2_rounds[0], 1);
+    if (count && b == 0 && tid == 0) atomicAdd(&g_m2_rounds[0], 1);
 #endif
     if (done) break;
   }
 #ifdef FB_MATCH_STAMPS
-  if (b == 0 && tid == 0) { atomicAdd(&g_m2_rounds[2], 1); int c = 0; for (int q = 0; q < nmp; q++) c += A.mp_track[mo + q]; atomicAdd(&g_m2_rounds[1], c); }
+  if (count && b == 0 && tid == 0) { atomicAdd(&g_m2_rounds[2], 1); int c = 0; for (int q = 0; q < nmp; q++) c += A.mp_track[mo + q]; atomicAdd(&g_m2_rounds[1], c); }
 #endif
   const int *matchL = fb::commit_matches<true>(C, fb::QueryIndex());  // last writer wins
   for (int i = tid; i < ncur; i += nt) A.match_cur_to_mp[co + i] = matchL[i];
   if (tid == 0) A.nmatches[b] = s_cf.n;
+}
+
+__global__ __launch_bounds__(MATCH_THREADS) void k_proj_points(fb_proj_points_args A, int descInLds) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  const int b = blockIdx.x;
+  const size_t mo = (size_t)b * A.mp_stride;
+  const Carve cv = cur_carve(A, descInLds != 0);
+  const TargetLds T = stage_cur(smem, cv, A, b, descInLds != 0);
+  m2_rounds(A, smem, cv.end, b, true, [&](const fb::Claims<int> &C, int q) -> int {  // every round walks the grid
+    if (!A.mp_track[mo + q]) return NONE;
+    M2Pick pick;
+    m2_walk(A, T, C, mo + q, q, pick);
+    return pick.result(A.matcher.nnratio);
+  });
 }
 
 // ---------------------------------------------------------------------------------------
@@ -546,7 +557,7 @@ __global__ __launch_bounds__(M2_CAND_THREADS) void k_m2_candidates(fb_proj_point
   const size_t mo = (size_t)b * A.mp_stride;
   const int nmp = A.n_mp[b];
   if ((int)(blockIdx.x * M2_CAND_THREADS) >= nmp) return;
-  const TargetLds T = stage_cur(smem, A, b, false);  // the grid only: descriptors from HBM / L2
+  const TargetLds T = stage_cur(smem, cur_carve(A, false), A, b, false);  // the grid only: descriptors from HBM / L2
   __syncthreads();
   const int q = blockIdx.x * M2_CAND_THREADS + tid;
   if (q >= nmp) return;
@@ -571,68 +582,49 @@ __global__ __launch_bounds__(M2_CAND_THREADS) void k_m2_candidates(fb_proj_point
 
 __global__ __launch_bounds__(MATCH_THREADS) void k_m2_resolve(fb_proj_points_args A, const uint32_t *cand, const uint8_t *ncand) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
-  const size_t co = (size_t)b * A.cur_stride, mo = (size_t)b * A.mp_stride;
-  const int ncur = A.n_cur[b], nmp = A.n_mp[b];
-  const TargetLds T = stage_cur(smem, A, b, false);
-  __shared__ fb::ClaimFlags s_cf;
-  fb::Claims<int> C(s_cf, T.rest, A.cur_stride, A.mp_stride, A.cur_blocked ? A.cur_blocked + co : nullptr, ncur, nmp);
-  C.start();
-  const bool bFactor = A.th != 1.0f;
-  for (int round = 0; C.more(round); round++) {
-    C.begin_round();
-    for (int q = tid; q < nmp; q += nt) {
-      int best = NONE;
-      const int nc = ncand[mo + q];
-      if (nc > 0) {
-        M2Pick pick;
-        if (nc != M2_OVER) {
-          const uint4 *cq = reinterpret_cast<const uint4 *>(cand + (mo + q) * M2_K);
-          const uint4 c0 = cq[0];
-          uint32_t c[M2_K] = {c0.x, c0.y, c0.z, c0.w, 0, 0, 0, 0};
-          if (nc > 4) { const uint4 c1 = cq[1]; c[4] = c1.x; c[5] = c1.y; c[6] = c1.z; c[7] = c1.w; }
+  const int b = blockIdx.x;
+  const size_t mo = (size_t)b * A.mp_stride;
+  const Carve cv = cur_carve(A, false);
+  const TargetLds T = stage_cur(smem, cv, A, b, false);
+  m2_rounds(A, smem, cv.end, b, false, [&](const fb::Claims<int> &C, int q) -> int {  // a round reads the query's cached list
+    const int nc = ncand[mo + q];
+    if (nc == 0) return NONE;
+    M2Pick pick;
+    if (nc != M2_OVER) {
+      const uint4 *cq = reinterpret_cast<const uint4 *>(cand + (mo + q) * M2_K);
+      const uint4 c0 = cq[0];
+      uint32_t c[M2_K] = {c0.x, c0.y, c0.z, c0.w, 0, 0, 0, 0};
+      if (nc > 4) { const uint4 c1 = cq[1]; c[4] = c1.x; c[5] = c1.y; c[6] = c1.z; c[7] = c1.w; }
 #pragma unroll
-          for (int k = 0; k < M2_K; k++) {
-            if (k >= nc) break;
-            const int idx = (int)(c[k] & 0xFFFFu);
-            if (C.taken(idx, q)) continue;
-            pick.take(idx, (int)(c[k] >> 20), (int)((c[k] >> 16) & 0xF));
-          }
-        } else {  // more candidates than the cache holds: the full walk, descriptors from HBM / L2
-          const int lvl = A.mp_level[mo + q];
-          uint32_t d[8];
-          fb::load_desc(A.mp_desc + (mo + q) * 32, d);
-          for_area<false>(A.grid, T, A.mp_proj[(mo + q) * 2], A.mp_proj[(mo + q) * 2 + 1], m2_radius(A, mo + q, bFactor, lvl), lvl - 1, lvl,
-                          [&](int idx) {
-            if (!C.taken(idx, q)) pick.take(idx, target_hamming(T, d, idx), (int)T.oct[idx]);
-          });
-        }
-        best = pick.result(A.matcher.nnratio);
+      for (int k = 0; k < M2_K; k++) {
+        if (k >= nc) break;
+        const int idx = (int)(c[k] & 0xFFFFu);
+        if (C.taken(idx, q)) continue;
+        pick.take(idx, (int)(c[k] >> 20), (int)((c[k] >> 16) & 0xF));
       }
-      C.submit(q, best, best != NONE && A.mp_obs_pos[mo + q]);
+    } else {  // more candidates than the cache holds: the full walk, descriptors from HBM / L2
+      m2_walk(A, T, C, mo + q, q, pick);
     }
-    if (C.end_round()) break;
-  }
-  const int *matchL = fb::commit_matches<true>(C, fb::QueryIndex());  // last writer wins
-  for (int i = tid; i < ncur; i += nt) A.match_cur_to_mp[co + i] = matchL[i];
-  if (tid == 0) A.nmatches[b] = s_cf.n;
+    return pick.result(A.matcher.nnratio);
+  });
 }
 
 // ---------------------------------------------------------------------------------------
 // M9  BirdMapPointMatch
 // ---------------------------------------------------------------------------------------
-// The body for frame b on a staged target T (T.rest is not written before the first barrier here).  cam = the frame's
-// mvKeysBirdCamXYZ, [ncur][3], in global memory or LDS.  commit(writer) runs once, by every thread, behind the last barrier:
-// writer[i], i < ncur, is the reference point that took key point i, or -1.
+// The body for frame b on a staged target T.  writer = BirdLds::writer, not written before the first barrier here.  cam = the
+// frame's mvKeysBirdCamXYZ, [ncur][3], in global memory or LDS.  commit(writer) runs once, by every thread, behind the last
+// barrier: writer[i], i < ncur, is the reference point that took key point i, or -1.
 template <typename Commit>
-__device__ __forceinline__ void bird_mappoints_body(const fb_bird_mp_args &A, const TargetLds &T, int b, const float *cam,
+__device__ __forceinline__ void bird_mappoints_body(const fb_bird_mp_args &A, const TargetLds &T, int *writer, int b, const float *cam,
                                                     Commit &&commit) {
   const int tid = threadIdx.x, nt = blockDim.x;
   const size_t ro = (size_t)b * A.ref_stride;
   const int ncur = A.n_cur[b], nref = A.n_ref[b];
-  int *writer = reinterpret_cast<int *>(T.rest);  // [cur_stride]
-  __shared__ float s_Tcw[12], s_Tbw[12];
-  __shared__ int s_n;
+  struct Shared { float Tcw[12], Tbw[12]; int n; };
+  __shared__ Shared s_;
+  static_assert(up16(sizeof(Shared)) == STATIC_BIRD_MP, "match_plan.h");
+  auto &s_Tcw = s_.Tcw; auto &s_Tbw = s_.Tbw; auto &s_n = s_.n;
   if (tid < 12) s_Tcw[tid] = A.cur_Tcw[(size_t)b * 12 + tid];
   for (int i = tid; i < ncur; i += nt) writer[i] = -1;
   if (tid == 0) s_n = 0;
@@ -686,8 +678,11 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_bird_mappoints(fb_bird_mp_arg
   const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
   const size_t co = (size_t)b * A.cur_stride;
   const int ncur = A.n_cur[b];
-  const TargetLds T = stage_cur(smem, A, b, descInLds != 0);
-  bird_mappoints_body(A, T, b, A.cur_cam_xyz + co * 3, [&](const int *writer) {  // the caller pre-filled the match array
+  const Carve cv = cur_carve(A, descInLds != 0);
+  const TargetLds T = stage_cur(smem, cv, A, b, descInLds != 0);
+  BirdLds L;
+  bird_layout(L, cv.end, A.cur_stride, false);
+  bird_mappoints_body(A, T, lds_at<int>(smem, L.writer), b, A.cur_cam_xyz + co * 3, [&](const int *writer) {  // the caller pre-filled the match array
     for (int i = tid; i < ncur; i += nt)
       if (writer[i] >= 0) A.match_cur_to_ref[co + i] = writer[i];
   });
@@ -701,11 +696,16 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_birdview(fb_birdview_args A, 
   const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
   const size_t co = (size_t)b * A.cur_stride, ro = (size_t)b * A.ref_stride;
   const int ncur = A.n_cur[b], nref = A.n_ref[b];
-  const TargetLds T = stage_cur(smem, A, b, descInLds != 0);
-  int *m12 = reinterpret_cast<int *>(T.rest);  // [ref_stride]
-  int *bins = m12 + A.ref_stride;                      // [ref_stride] histogram bin of i1 or -1
-  __shared__ int s_n, s_nd;
-  __shared__ fb::RotHist s_rot;
+  const Carve cv = cur_carve(A, descInLds != 0);
+  const TargetLds T = stage_cur(smem, cv, A, b, descInLds != 0);
+  BirdviewLds L;
+  birdview_layout(L, cv.end, A.ref_stride);
+  int *m12 = lds_at<int>(smem, L.m12);
+  int *bins = lds_at<int>(smem, L.bins);  // histogram bin of i1 or -1
+  struct Shared { int n, nd; fb::RotHist rot; };
+  __shared__ Shared s_;
+  static_assert(up16(sizeof(Shared)) == STATIC_BIRDVIEW, "match_plan.h");
+  auto &s_n = s_.n; auto &s_nd = s_.nd; auto &s_rot = s_.rot;
   s_rot.clear();
   if (tid == 0) { s_n = 0; s_nd = 0; }
   __syncthreads();
@@ -780,6 +780,7 @@ __device__ __forceinline__ void grid_build_body(const fb_keypoint *__restrict__ 
   const int tid = threadIdx.x, nt = NT;
   const int ncell = g.cols * g.rows;
   __shared__ int s_part[NT / 64];
+  static_assert(sizeof(s_part) == (NT == 256 ? SCAN_PART_BYTES_256 : SCAN_PART_BYTES_1024), "match_plan.h");
   for (int i = tid; i <= ncell; i += nt) cnt[i] = 0;
   __syncthreads();
   auto cell_of = [&](const fb_keypoint &kp) -> int {
@@ -824,11 +825,6 @@ __device__ __forceinline__ void grid_build_body(const fb_keypoint *__restrict__ 
   __syncthreads();
 }
 
-// LDS ints of grid_build_body with the items in LDS / without
-__host__ __device__ inline size_t grid_lds_ints(int ncell, int kp_stride, bool itemsInLds) {
-  return (size_t)(2 * ncell + 1) + (itemsInLds ? (size_t)kp_stride : 0);
-}
-
 // the frame's CSR from LDS (or, for the items, from where they already are) to the caller's arrays
 __device__ __forceinline__ void grid_store(const int *cnt, const int *li, int ncell, int32_t *cs, int32_t *cig) {
   const int tid = threadIdx.x, nt = blockDim.x;
@@ -845,14 +841,14 @@ __global__ __launch_bounds__(256) void k_grid_build(const fb_keypoint *__restric
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int b = blockIdx.x;
   const int ncell = g.cols * g.rows;
-  int *cnt = reinterpret_cast<int *>(smem);  // [ncell+1]
-  int *fillp = cnt + ncell + 1;              // [ncell]
+  GridLds L;
+  grid_layout(L, 0, ncell, kp_stride, itemsInLds != 0);
+  int *cnt = lds_at<int>(smem, L.cnt);
   // the items are scattered, sorted per cell and written out from LDS (itemsInLds): the per-cell insertion sort on the
   // global array was a chain of dependent global accesses per cell, 12 cells per lane -- most of this kernel at batch 1
-  int *li = fillp + ncell;                   // [kp_stride] when itemsInLds
   int32_t *cig = cell_items + (size_t)b * kp_stride;
-  int *ci = itemsInLds ? li : cig;
-  grid_build_body<256>(kps + (size_t)b * kp_stride, min(max(n[b], 0), kp_stride), g, cnt, fillp, ci);
+  int *ci = itemsInLds ? lds_at<int>(smem, L.items) : cig;
+  grid_build_body<256>(kps + (size_t)b * kp_stride, min(max(n[b], 0), kp_stride), g, cnt, lds_at<int>(smem, L.fillp), ci);
   grid_store(cnt, ci, ncell, cell_start + (size_t)b * (ncell + 1), cig);
 }
 
@@ -885,19 +881,21 @@ __global__ void k_bird_keys_to_cam(const fb_keypoint *__restrict__ kps, const in
 //   front: AssignFeaturesToGrid -> M3 -> front edges of PoseOptimizationWithBird, n_front, SetPose(prediction)
 //   bird : AssignFeaturesToGrid -> mvKeysBirdCamXYZ -> M9 on a fresh mvpMapPointsBird -> bird edges, n_bird, fresh mvBirdOutlier
 // The cell lists are built in LDS and staged from there (they are still stored: callers read them); the grid's scratch arrays
-// lie where the matcher's own arrays (T.rest) begin and are dead before those are first written.
+// lie where the matcher's own arrays begin (GridLds at Carve::end) and are dead before those are first written.
 // ---------------------------------------------------------------------------------------
 struct GridScratch { int *cnt, *fillp, *items; };
-// builds frame b's grid at `at`, stores it to cell_start / cell_items (written here, whatever the struct's const says)
+// builds frame b's grid at LDS offset `at`, stores it to cell_start / cell_items (written here, whatever the struct's const says)
 template <typename Args>
-__device__ __forceinline__ GridScratch tail_grid(uint8_t *at, const Args &A, int b, bool itemsInLds) {
+__device__ __forceinline__ GridScratch tail_grid(uint8_t *smem, size_t at, const Args &A, int b, bool itemsInLds) {
   const int ncell = A.grid.cols * A.grid.rows;
   const size_t co = (size_t)b * A.cur_stride;
+  GridLds L;
+  grid_layout(L, at, ncell, A.cur_stride, itemsInLds);
   GridScratch G;
-  G.cnt = reinterpret_cast<int *>(at);
-  G.fillp = G.cnt + ncell + 1;
+  G.cnt = lds_at<int>(smem, L.cnt);
+  G.fillp = lds_at<int>(smem, L.fillp);
   int32_t *cig = const_cast<int32_t *>(A.cur_cell_items) + co;
-  G.items = itemsInLds ? G.fillp + ncell : cig;
+  G.items = itemsInLds ? lds_at<int>(smem, L.items) : cig;
   grid_build_body<MATCH_THREADS>(A.cur_kps + co, min(max(A.n_cur[b], 0), A.cur_stride), A.grid, G.cnt, G.fillp, G.items);
   grid_store(G.cnt, G.items, ncell, const_cast<int32_t *>(A.cur_cell_start) + (size_t)b * (ncell + 1), cig);
   return G;
@@ -912,12 +910,12 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_frame_tail_front(fb_frame_tai
   const size_t co = (size_t)b * A.cur_stride;
   const int ncur = A.n_cur[b];
   const Carve cv(A.cur_stride, ncell, descInLds != 0, false);
-  const GridScratch G = tail_grid(smem + cv.end, A, b, itemsInLds != 0);
+  const GridScratch G = tail_grid(smem, cv.end, A, b, itemsInLds != 0);
   if (!itemsInLds) __syncthreads();  // the items come back from the global array
   const TargetLds T = stage_target(smem, cv, ncur, ncell, A.cur_kps + co, A.cur_desc + co * 32, G.cnt, G.items, descInLds != 0);
   if (tid == 0) F.n_front[b] = ncur;
   if (tid < 12) F.Tcw[(size_t)b * 12 + tid] = A.cur_Tcw[(size_t)b * 12 + tid];  // SetPose(prediction), Tracking.cc:1314-1320
-  proj_frame_body(A, T, b, cacheK, [&](const int *matchL) {
+  proj_frame_body(A, smem, cv.end, T, b, cacheK, [&](const int *matchL) {
     const float *mp = A.last_xw + (size_t)b * A.last_stride * 3;
     for (int i = tid; i < A.cur_stride; i += nt)
       fb::gather_front_edge(co + i, i < ncur ? matchL[i] : -1, A.cur_kps, mp, F.edge, F.front_xw, F.front_obs, F.front_inv_sigma2,
@@ -934,13 +932,15 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_frame_tail_bird(fb_frame_tail
   const size_t co = (size_t)b * A.cur_stride;
   const int ncur = A.n_cur[b];
   const Carve cv(A.cur_stride, ncell, descInLds != 0);
-  const GridScratch G = tail_grid(smem + cv.end, A, b, itemsInLds != 0);
+  const GridScratch G = tail_grid(smem, cv.end, A, b, itemsInLds != 0);
   if (!itemsInLds) __syncthreads();
   const TargetLds T = stage_target(smem, cv, ncur, ncell, A.cur_kps + co, A.cur_desc + co * 32, G.cnt, G.items, descInLds != 0);
   __syncthreads();  // the grid's scratch is dead: the LDS copy of the camera positions lies over it
   // mvKeysBirdCamXYZ: stored for the caller; M9 and the edges read the LDS copy (behind the body's writer array) when it fits
+  BirdLds L;
+  bird_layout(L, cv.end, A.cur_stride, camInLds != 0);
   float *gcam = const_cast<float *>(A.cur_cam_xyz) + co * 3;
-  float *lcam = reinterpret_cast<float *>(T.rest) + A.cur_stride;
+  float *lcam = lds_at<float>(smem, L.cam);
   for (int i = tid; i < ncur; i += nt) {
     float o[3];
     bird_key_to_cam(A.cur_kps[co + i], K, o);
@@ -949,7 +949,7 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_frame_tail_bird(fb_frame_tail
   }
   if (tid == 0) F.n_bird[b] = ncur;
   const float *cam = camInLds ? lcam : gcam;
-  bird_mappoints_body(A, T, b, cam, [&](const int *writer) {
+  bird_mappoints_body(A, T, lds_at<int>(smem, L.writer), b, cam, [&](const int *writer) {
     const float *mp = A.ref_xw + (size_t)b * A.ref_stride * 3;
     for (int i = tid; i < A.cur_stride; i += nt) {
       const int m = i < ncur ? writer[i] : -1;   // a fresh mvpMapPointsBird: every slot of the stride is written
@@ -960,23 +960,11 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_frame_tail_bird(fb_frame_tail
   });
 }
 
-size_t match_lds_bytes(int cur_stride, int ncell, int extra_ints, bool withDesc = true, bool withOct = true) {
-  return Carve(cur_stride, ncell, withDesc, withOct).end + (size_t)extra_ints * 4;
-}
-
-// LDS plan of a matcher: the target frame's descriptor table goes to LDS when everything fits, otherwise it stays in
-// HBM/L2 (frames with more key points than ~2900, e.g. nFeatures = 4000) and only positions, octaves and the grid are staged
-struct LdsPlan { size_t bytes; int descInLds; };
-constexpr size_t LDS_BUDGET = 160 * 1024 - 512;  // leave room for the kernels' static __shared__ variables
-using fb::check_lds;
-int plan_lds(int cur_stride, int ncell, int extra_ints, const char *what, LdsPlan *p) {
-  p->descInLds = 1;
-  p->bytes = Carve(cur_stride, ncell, true).end + (size_t)extra_ints * 4;
-  if (p->bytes > LDS_BUDGET) {
-    p->descInLds = 0;
-    p->bytes = Carve(cur_stride, ncell, false).end + (size_t)extra_ints * 4;
-  }
-  return check_lds(p->bytes, what);
+// (The LDS plan of every matcher -- which frames keep their descriptor table in LDS, which leave it in HBM / L2 -- is
+// match_plan.h; DESIGN.md section 4 lists the variants and the shapes at which they change.)
+bool m3_no_cache() {  // measurements: every round of M3 walks the grid again
+  static const bool noCache = getenv("FB_M3_NO_CACHE") != nullptr;
+  return noCache;
 }
 
 template <typename K>
@@ -1019,13 +1007,11 @@ int fb_grid_build_batch_dev(const fb_keypoint *d_keypoints, const int32_t *d_n, 
   FB_ARG(geom && batch >= 0 && kp_stride > 0 && geom->cols > 0 && geom->rows > 0);
   if (batch == 0) return FB_OK;
   const int ncell = geom->cols * geom->rows;
-  size_t lds = (size_t)(2 * ncell + 1) * 4 + (size_t)kp_stride * 4;
-  int itemsInLds = 1;
-  if (lds > LDS_BUDGET) { itemsInLds = 0; lds = (size_t)(2 * ncell + 1) * 4; }
-  FB_TRY(check_lds(lds, "fb_grid_build_batch_dev"));
-  FB_TRY(set_max_lds(k_grid_build, lds));
+  const GridPlan gp = plan_grid(0, ncell, kp_stride);
+  FB_TRY(check_lds(gp.bytes, STATIC_GRID, "fb_grid_build_batch_dev"));
+  FB_TRY(set_max_lds(k_grid_build, gp.bytes));
   fb::ProfScope prof_(fb::P_GRID, fb::as_stream(stream));
-  k_grid_build<<<batch, 256, lds, fb::as_stream(stream)>>>(d_keypoints, d_n, kp_stride, *geom, d_cell_start, d_cell_items, itemsInLds);
+  k_grid_build<<<batch, 256, gp.bytes, fb::as_stream(stream)>>>(d_keypoints, d_n, kp_stride, *geom, d_cell_start, d_cell_items, gp.itemsInLds);
   FB_HIP(hipGetLastError());
   return FB_OK;
 }
@@ -1051,19 +1037,11 @@ int fb_match_projection_frame_dev(const fb_proj_frame_args *A, void *stream) {
   FB_ARG(A && A->batch >= 0 && A->cur_stride > 0 && A->last_stride >= 0 && A->cur_stride < 65536);
   if (A->batch == 0) return FB_OK;
   const int ncell = A->grid.cols * A->grid.rows;
-  // ints: two owner arrays; per query two u16 assignments + u16 processing order + one meta byte (2 ints) + the cache
-  const int base_ints = 2 * A->cur_stride + 2 * A->last_stride + 4;
-  // preference: descriptors in LDS + cache, descriptors in LDS, cache only, neither
-  static const bool noCache = getenv("FB_M3_NO_CACHE") != nullptr;  // measurements: every round walks the grid again
-  int cacheK = noCache ? 0 : CACHE_K, descInLds = 1;
-  size_t lds = match_lds_bytes(A->cur_stride, ncell, base_ints + cacheK * A->last_stride, true, false);
-  if (lds > LDS_BUDGET) { cacheK = 0; lds = match_lds_bytes(A->cur_stride, ncell, base_ints, true, false); }
-  if (lds > LDS_BUDGET) { cacheK = CACHE_K; descInLds = 0; lds = match_lds_bytes(A->cur_stride, ncell, base_ints + cacheK * A->last_stride, false, false); }
-  if (lds > LDS_BUDGET) { cacheK = 0; lds = match_lds_bytes(A->cur_stride, ncell, base_ints, false, false); }
-  FB_TRY(check_lds(lds, "fb_match_projection_frame"));
-  FB_TRY(set_max_lds(k_proj_frame, lds));
+  M3Plan p;
+  FB_TRY(plan_m3(A->cur_stride, A->last_stride, ncell, m3_no_cache(), "fb_match_projection_frame", &p));
+  FB_TRY(set_max_lds(k_proj_frame, p.bytes));
   fb::ProfScope prof_(fb::P_PROJ_FRAME, fb::as_stream(stream));
-  k_proj_frame<<<A->batch, MATCH_THREADS, lds, fb::as_stream(stream)>>>(*A, cacheK, descInLds);
+  k_proj_frame<<<A->batch, MATCH_THREADS, p.bytes, fb::as_stream(stream)>>>(*A, p.cacheK, p.descInLds);
   FB_HIP(hipGetLastError());
   return FB_OK;
 }
@@ -1074,8 +1052,10 @@ int fb_match_projection_keyframe_dev(const fb_proj_kf_args *A, void *stream) {
   FB_ARG(A->n_levels > 0 && A->n_levels <= FB_MAX_LEVELS);
   if (A->batch == 0) return FB_OK;
   const int ncell = A->grid.cols * A->grid.rows;
-  LdsPlan lp;
-  FB_TRY(plan_lds(A->cur_stride, ncell, 2 * A->cur_stride + A->kf_stride + 2, "fb_match_projection_keyframe", &lp));
+  DescPlan lp;
+  ClaimsLds L;
+  FB_TRY(plan_staged(A->cur_stride, ncell, [&](size_t at) { return claims_layout(L, at, A->cur_stride, A->kf_stride, 2, CLAIMS_U16_SLACK); },
+                     STATIC_M4, "fb_match_projection_keyframe", &lp));
   const size_t lds = lp.bytes;
   FB_TRY(set_max_lds(k_proj_kf, lds));
   fb::ProfScope prof_(fb::P_PROJ_KF, fb::as_stream(stream));
@@ -1105,28 +1085,24 @@ int fb_match_projection_points_dev(const fb_proj_points_args *A, void *stream) {
   if (A->batch == 0) return FB_OK;
   const int ncell = A->grid.cols * A->grid.rows;
   const size_t wsNeed = fb_match_projection_points_workspace(A->batch, A->mp_stride);
-  if (A->workspace && A->workspace_bytes >= wsNeed && A->mp_stride > 0 && A->batch <= 65535 && ((uintptr_t)A->workspace % 16) == 0) {
+  const bool haveWorkspace = A->workspace && A->workspace_bytes >= wsNeed && A->mp_stride > 0 && A->batch <= 65535 && ((uintptr_t)A->workspace % 16) == 0;
+  M2Plan p;
+  FB_TRY(plan_m2(A->cur_stride, A->mp_stride, ncell, haveWorkspace, "fb_match_projection_points", &p));
+  if (p.twoPhase) {
     // two phases: candidate lists by many workgroups, then the serial rule on the lists (see k_m2_candidates)
     uint32_t *cand = reinterpret_cast<uint32_t *>(A->workspace);
     uint8_t *ncand = reinterpret_cast<uint8_t *>(cand + (size_t)A->batch * A->mp_stride * M2_K);
-    const size_t ldsA = Carve(A->cur_stride, ncell, false).end;
-    const size_t ldsB = ldsA + ((size_t)2 * A->cur_stride + (size_t)2 * A->mp_stride) * 4;
-    if (ldsB <= LDS_BUDGET) {
-      FB_TRY(set_max_lds(k_m2_candidates, ldsA));
-      FB_TRY(set_max_lds(k_m2_resolve, ldsB));
-      fb::ProfScope prof_(fb::P_PROJ_POINTS, fb::as_stream(stream));
-      k_m2_candidates<<<dim3((A->mp_stride + M2_CAND_THREADS - 1) / M2_CAND_THREADS, A->batch), M2_CAND_THREADS, ldsA, fb::as_stream(stream)>>>(*A, cand, ncand);
-      k_m2_resolve<<<A->batch, MATCH_THREADS, ldsB, fb::as_stream(stream)>>>(*A, cand, ncand);
-      FB_HIP(hipGetLastError());
-      return FB_OK;
-    }
+    FB_TRY(set_max_lds(k_m2_candidates, p.candBytes));
+    FB_TRY(set_max_lds(k_m2_resolve, p.bytes));
+    fb::ProfScope prof_(fb::P_PROJ_POINTS, fb::as_stream(stream));
+    k_m2_candidates<<<dim3((A->mp_stride + M2_CAND_THREADS - 1) / M2_CAND_THREADS, A->batch), M2_CAND_THREADS, p.candBytes, fb::as_stream(stream)>>>(*A, cand, ncand);
+    k_m2_resolve<<<A->batch, MATCH_THREADS, p.bytes, fb::as_stream(stream)>>>(*A, cand, ncand);
+    FB_HIP(hipGetLastError());
+    return FB_OK;
   }
-  LdsPlan lp;
-  FB_TRY(plan_lds(A->cur_stride, ncell, 2 * A->cur_stride + 2 * A->mp_stride, "fb_match_projection_points", &lp));
-  const size_t lds = lp.bytes;
-  FB_TRY(set_max_lds(k_proj_points, lds));
+  FB_TRY(set_max_lds(k_proj_points, p.bytes));
   fb::ProfScope prof_(fb::P_PROJ_POINTS, fb::as_stream(stream));
-  k_proj_points<<<A->batch, MATCH_THREADS, lds, fb::as_stream(stream)>>>(*A, lp.descInLds);
+  k_proj_points<<<A->batch, MATCH_THREADS, p.bytes, fb::as_stream(stream)>>>(*A, p.descInLds);
   FB_HIP(hipGetLastError());
   return FB_OK;
 }
@@ -1141,8 +1117,10 @@ int fb_match_bird_mappoints_dev(const fb_bird_mp_args *A, void *stream) {
   FB_ARG(A && A->batch >= 0 && A->cur_stride > 0 && A->ref_stride >= 0 && A->cur_stride < 65536);
   if (A->batch == 0) return FB_OK;
   const int ncell = A->grid.cols * A->grid.rows;
-  LdsPlan lp;
-  FB_TRY(plan_lds(A->cur_stride, ncell, A->cur_stride, "fb_match_bird_mappoints", &lp));
+  DescPlan lp;
+  BirdLds L;
+  FB_TRY(plan_staged(A->cur_stride, ncell, [&](size_t at) { return bird_layout(L, at, A->cur_stride, false); }, STATIC_BIRD_MP,
+                     "fb_match_bird_mappoints", &lp));
   const size_t lds = lp.bytes;
   FB_TRY(set_max_lds(k_bird_mappoints, lds));
   fb::ProfScope prof_(fb::P_BIRD_MP, fb::as_stream(stream));
@@ -1162,22 +1140,11 @@ int fb_frame_tail_front_dev(const fb_frame_tail_front_args *F, void *stream) {
   const int ncell = A->grid.cols * A->grid.rows;
   // the matcher's plan is that of fb_match_projection_frame_dev; the grid's scratch shares the matcher's own arrays, with the
   // items in LDS when that fits (the bench's 64x48 cells at 2064 key points: descriptors, cache and items all in LDS)
-  const int base_ints = 2 * A->cur_stride + 2 * A->last_stride + 4;
-  static const bool noCache = getenv("FB_M3_NO_CACHE") != nullptr;
-  int cacheK = noCache ? 0 : CACHE_K, descInLds = 1;
-  size_t lds = match_lds_bytes(A->cur_stride, ncell, base_ints + cacheK * A->last_stride, true, false);
-  if (lds > LDS_BUDGET) { cacheK = 0; lds = match_lds_bytes(A->cur_stride, ncell, base_ints, true, false); }
-  if (lds > LDS_BUDGET) { cacheK = CACHE_K; descInLds = 0; lds = match_lds_bytes(A->cur_stride, ncell, base_ints + cacheK * A->last_stride, false, false); }
-  if (lds > LDS_BUDGET) { cacheK = 0; lds = match_lds_bytes(A->cur_stride, ncell, base_ints, false, false); }
-  const size_t staged = Carve(A->cur_stride, ncell, descInLds != 0, false).end;
-  int itemsInLds = 1;
-  size_t gridLds = staged + grid_lds_ints(ncell, A->cur_stride, true) * 4;
-  if (gridLds > LDS_BUDGET) { itemsInLds = 0; gridLds = staged + grid_lds_ints(ncell, A->cur_stride, false) * 4; }
-  if (gridLds > lds) lds = gridLds;
-  FB_TRY(check_lds(lds, "fb_frame_tail_front"));
-  FB_TRY(set_max_lds(k_frame_tail_front, lds));
+  TailFrontPlan p;
+  FB_TRY(plan_tail_front(A->cur_stride, A->last_stride, ncell, m3_no_cache(), "fb_frame_tail_front", &p));
+  FB_TRY(set_max_lds(k_frame_tail_front, p.bytes));
   fb::ProfScope prof_(fb::P_TAIL_FRONT, fb::as_stream(stream));
-  k_frame_tail_front<<<A->batch, MATCH_THREADS, lds, fb::as_stream(stream)>>>(*F, cacheK, descInLds, itemsInLds);
+  k_frame_tail_front<<<A->batch, MATCH_THREADS, p.bytes, fb::as_stream(stream)>>>(*F, p.cacheK, p.descInLds, p.itemsInLds);
   FB_HIP(hipGetLastError());
   return FB_OK;
 }
@@ -1192,24 +1159,14 @@ int fb_frame_tail_bird_dev(const fb_frame_tail_bird_args *F, void *stream) {
          F->bird_xc && F->bird_inv_sigma2 && F->bird_valid);
   if (A->batch == 0) return FB_OK;
   const int ncell = A->grid.cols * A->grid.rows;
-  // writer array + the camera positions in LDS when they fit beside the staged frame, else the matcher's own plan
-  int camInLds = 1;
-  LdsPlan lp;
-  lp.descInLds = 1;
-  lp.bytes = Carve(A->cur_stride, ncell, true).end + (size_t)A->cur_stride * 16;
-  if (lp.bytes > LDS_BUDGET) { camInLds = 0; FB_TRY(plan_lds(A->cur_stride, ncell, A->cur_stride, "fb_frame_tail_bird", &lp)); }
-  const size_t staged = Carve(A->cur_stride, ncell, lp.descInLds != 0).end;
-  int itemsInLds = 1;
-  size_t gridLds = staged + grid_lds_ints(ncell, A->cur_stride, true) * 4;
-  if (gridLds > LDS_BUDGET) { itemsInLds = 0; gridLds = staged + grid_lds_ints(ncell, A->cur_stride, false) * 4; }
-  size_t lds = lp.bytes > gridLds ? lp.bytes : gridLds;
-  FB_TRY(check_lds(lds, "fb_frame_tail_bird"));
-  FB_TRY(set_max_lds(k_frame_tail_bird, lds));
+  TailBirdPlan p;
+  FB_TRY(plan_tail_bird(A->cur_stride, ncell, "fb_frame_tail_bird", &p));
+  FB_TRY(set_max_lds(k_frame_tail_bird, p.bytes));
   BirdCamK K;
   K.cols = A->bird_cols; K.rows = A->bird_rows; K.pixel2meter = F->pixel2meter; K.rear = A->rear_axle_to_center;
   memcpy(K.Tcb, F->Tcb, sizeof(K.Tcb));
   fb::ProfScope prof_(fb::P_TAIL_BIRD, fb::as_stream(stream));
-  k_frame_tail_bird<<<A->batch, MATCH_THREADS, lds, fb::as_stream(stream)>>>(*F, K, lp.descInLds, itemsInLds, camInLds);
+  k_frame_tail_bird<<<A->batch, MATCH_THREADS, p.bytes, fb::as_stream(stream)>>>(*F, K, p.descInLds, p.itemsInLds, p.camInLds);
   FB_HIP(hipGetLastError());
   return FB_OK;
 }
@@ -1219,8 +1176,10 @@ int fb_match_birdview_dev(const fb_birdview_args *A, void *stream) {
   FB_ARG(A && A->batch >= 0 && A->cur_stride > 0 && A->ref_stride >= 0 && A->cur_stride < 65536);
   if (A->batch == 0) return FB_OK;
   const int ncell = A->grid.cols * A->grid.rows;
-  LdsPlan lp;
-  FB_TRY(plan_lds(A->cur_stride, ncell, 2 * A->ref_stride, "fb_match_birdview", &lp));
+  DescPlan lp;
+  BirdviewLds L;
+  FB_TRY(plan_staged(A->cur_stride, ncell, [&](size_t at) { return birdview_layout(L, at, A->ref_stride); }, STATIC_BIRDVIEW,
+                     "fb_match_birdview", &lp));
   const size_t lds = lp.bytes;
   FB_TRY(set_max_lds(k_birdview, lds));
   fb::ProfScope prof_(fb::P_BIRDVIEW, fb::as_stream(stream));

@@ -12,6 +12,7 @@
 // :210): resolved with the same fixed-point iteration as M2/M3 (fb_claims.h), claims here always block.
 #include "fb_common.h"
 #include "fb_claims.h"
+#include "match_plan.h"
 
 namespace {
 
@@ -69,14 +70,16 @@ __global__ __launch_bounds__(BOW_THREADS) void k_match_bow_t(fb_bow_args A, cons
   const int nF = A.n_f[b];
   const FVd K = fv_of(A.kf_fv, b), F = fv_of(A.f_fv, b);
   const int nQ = K.n > 0 ? K.start[K.n] : 0;  // flattened keyframe items = queries in serial order
-  // descriptor table of the candidate side: LDS when it fits, else read from HBM/L2 (frames with > ~3400 key points)
-  const size_t descBytes = descInLds ? (size_t)A.f_stride * 32 : 0;
+  // descriptor table of the candidate side: LDS (at 0) when it fits, else read from HBM/L2 (match_plan.h)
   const uint4 *fdesc = descInLds ? reinterpret_cast<const uint4 *>(smem) : reinterpret_cast<const uint4 *>(A.f_desc + fo * 32);
-  int *owners = reinterpret_cast<int *>(smem + descBytes);          // owner [2][f_stride], assign [2][kf item_stride]
-  int *fitems = owners + 2 * A.f_stride + 2 * A.kf_fv.item_stride;   // [f item_stride] F.mFeatVec's items: walked by every query in every round
-  __shared__ fb::ClaimFlags s_cf;
-  __shared__ fb::RotHist s_rot;
-  fb::Claims<int> C(s_cf, owners, A.f_stride, A.kf_fv.item_stride, nullptr, nF, nQ);
+  ClaimsLds L;
+  bow_layout(L, descInLds != 0, A.f_stride, A.kf_fv.item_stride, A.f_fv.item_stride);
+  int *fitems = lds_at<int>(smem, L.fitems);  // F.mFeatVec's items: walked by every query in every round
+  struct Shared { fb::ClaimFlags cf; fb::RotHist rot; };
+  __shared__ Shared s_;
+  static_assert(up16(sizeof(Shared)) == STATIC_BOW, "match_plan.h");
+  auto &s_cf = s_.cf; auto &s_rot = s_.rot;
+  fb::Claims<int> C(s_cf, lds_at<int>(smem, L.owners), A.f_stride, lds_at<int>(smem, L.assigns), A.kf_fv.item_stride, nullptr, nF, nQ);
   {
     const int nFi = F.n > 0 ? min(F.start[F.n], A.f_fv.item_stride) : 0;
     for (int i = tid; i < nFi; i += nt) fitems[i] = F.items[i];
@@ -168,14 +171,15 @@ __global__ __launch_bounds__(BOW_THREADS) void k_match_triangulation(fb_triangul
   const int n1 = A.n1[b1], n2 = A.n2[b];
   const FVd V1 = fv_of(A.fv1, b1), V2 = fv_of(A.fv2, b);
   const int nQ = V1.n > 0 ? V1.start[V1.n] : 0;
-  const size_t descBytes = descInLds ? (size_t)A.kf2_stride * 32 : 0;
   const uint4 *desc2 = descInLds ? reinterpret_cast<const uint4 *>(smem) : reinterpret_cast<const uint4 *>(A.desc2 + o2 * 32);
-  float4 *k2 = reinterpret_cast<float4 *>(smem + descBytes);                         // x, y, angle, octave
-  int *m12 = reinterpret_cast<int *>(smem + descBytes + (size_t)A.kf2_stride * 16);  // [kf1_stride]
-  int *bins = m12 + A.kf1_stride;                                                    // [kf1_stride]
-  __shared__ int s_n;
-  __shared__ fb::RotHist s_rot;
-  __shared__ float s_e[2], s_F[9];
+  TriangulationLds L;
+  triangulation_layout(L, descInLds != 0, A.kf1_stride, A.kf2_stride);
+  float4 *k2 = lds_at<float4>(smem, L.k2);  // x, y, angle, octave
+  int *m12 = lds_at<int>(smem, L.m12), *bins = lds_at<int>(smem, L.bins);
+  struct Shared { int n; fb::RotHist rot; float e[2], F[9]; };
+  __shared__ Shared s_;
+  static_assert(up16(sizeof(Shared)) == STATIC_TRIANGULATION, "match_plan.h");
+  auto &s_n = s_.n; auto &s_rot = s_.rot; auto &s_e = s_.e; auto &s_F = s_.F;
   {
     if (descInLds) {
       const uint4 *src = reinterpret_cast<const uint4 *>(A.desc2 + o2 * 32);
@@ -253,17 +257,24 @@ __global__ __launch_bounds__(BOW_THREADS) void k_match_triangulation(fb_triangul
   if (tid == 0) A.nmatches[b] = s_n;
 }
 
-using fb::check_lds;
+int plan_bow(const fb_bow_args &A, const char *what, DescPlan *p) {
+  ClaimsLds L;
+  return plan_desc([&](bool withDesc) { return bow_layout(L, withDesc, A.f_stride, A.kf_fv.item_stride, A.f_fv.item_stride); }, STATIC_BOW, what, p);
+}
+int plan_triangulation(const fb_triangulation_args &A, const char *what, DescPlan *p) {
+  TriangulationLds L;
+  return plan_desc([&](bool withDesc) { return triangulation_layout(L, withDesc, A.kf1_stride, A.kf2_stride); }, STATIC_TRIANGULATION, what, p);
+}
 
 }  // namespace
 
 namespace fb {
 // M7 for every neighbour of one key frame in one launch (fb_create_new_map_points_dev): KF1 shared, gated entries skipped
 int match_triangulation_shared(const fb_triangulation_args &A, const int32_t *skip, hipStream_t stream) {
-  size_t lds = (size_t)A.kf2_stride * 48 + (size_t)A.kf1_stride * 8 + 16;
-  const int descInLds = lds <= 160 * 1024 - 512;
-  if (!descInLds) lds -= (size_t)A.kf2_stride * 32;
-  FB_TRY(check_lds(lds, "fb_create_new_map_points"));
+  DescPlan lp;
+  FB_TRY(plan_triangulation(A, "fb_create_new_map_points", &lp));
+  const size_t lds = lp.bytes;
+  const int descInLds = lp.descInLds;
   FB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_match_triangulation), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   fb::ProfScope prof_(fb::P_NP_M7, stream);
   k_match_triangulation<<<A.batch, BOW_THREADS, lds, stream>>>(A, descInLds, 1, skip);
@@ -278,10 +289,10 @@ int fb_match_bow_dev(const fb_bow_args *A, void *stream) {
   FB_TRY(fb::check_device());
   FB_ARG(A && A->batch >= 0 && A->kf_stride > 0 && A->f_stride > 0 && A->kf_fv.item_stride >= 0 && A->f_fv.item_stride >= 0);
   if (A->batch == 0) return FB_OK;
-  size_t lds = (size_t)A->f_stride * 32 + (size_t)A->f_stride * 8 + (size_t)A->kf_fv.item_stride * 8 + (size_t)A->f_fv.item_stride * 4 + 16;
-  const int descInLds = lds <= 160 * 1024 - 512;
-  if (!descInLds) lds -= (size_t)A->f_stride * 32;
-  FB_TRY(check_lds(lds, "fb_match_bow"));
+  DescPlan lp;
+  FB_TRY(plan_bow(*A, "fb_match_bow", &lp));
+  const size_t lds = lp.bytes;
+  const int descInLds = lp.descInLds;
   FB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_match_bow_t<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   fb::ProfScope prof_(fb::P_BOW, fb::as_stream(stream));
   k_match_bow_t<false><<<A->batch, BOW_THREADS, lds, fb::as_stream(stream)>>>(*A, nullptr, nullptr, descInLds);
@@ -299,10 +310,10 @@ int fb_match_bow_kf_dev(const fb_bow_kf_args *K, void *stream) {
   A.n_kf = K->n1; A.kf_kps = K->kps1; A.kf_desc = K->desc1; A.kf_has_mp = K->has_mp1; A.kf_fv = K->fv1;
   A.n_f = K->n2; A.f_kps = K->kps2; A.f_desc = K->desc2; A.f_fv = K->fv2;
   A.matcher = K->matcher; A.match_f_to_kf = nullptr; A.nmatches = K->nmatches;
-  size_t lds = (size_t)A.f_stride * 32 + (size_t)A.f_stride * 8 + (size_t)A.kf_fv.item_stride * 8 + (size_t)A.f_fv.item_stride * 4 + 16;
-  const int descInLds = lds <= 160 * 1024 - 512;
-  if (!descInLds) lds -= (size_t)A.f_stride * 32;
-  FB_TRY(check_lds(lds, "fb_match_bow_kf"));
+  DescPlan lp;
+  FB_TRY(plan_bow(A, "fb_match_bow_kf", &lp));
+  const size_t lds = lp.bytes;
+  const int descInLds = lp.descInLds;
   FB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_match_bow_t<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   fb::ProfScope prof_(fb::P_BOW_KF, fb::as_stream(stream));
   k_match_bow_t<true><<<A.batch, BOW_THREADS, lds, fb::as_stream(stream)>>>(A, K->has_mp2, K->matches12, descInLds);
@@ -314,10 +325,10 @@ int fb_match_triangulation_dev(const fb_triangulation_args *A, void *stream) {
   FB_TRY(fb::check_device());
   FB_ARG(A && A->batch >= 0 && A->kf1_stride > 0 && A->kf2_stride > 0);
   if (A->batch == 0) return FB_OK;
-  size_t lds = (size_t)A->kf2_stride * 48 + (size_t)A->kf1_stride * 8 + 16;
-  const int descInLds = lds <= 160 * 1024 - 512;
-  if (!descInLds) lds -= (size_t)A->kf2_stride * 32;
-  FB_TRY(check_lds(lds, "fb_match_triangulation"));
+  DescPlan lp;
+  FB_TRY(plan_triangulation(*A, "fb_match_triangulation", &lp));
+  const size_t lds = lp.bytes;
+  const int descInLds = lp.descInLds;
   FB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_match_triangulation), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   fb::ProfScope prof_(fb::P_TRIANG, fb::as_stream(stream));
   k_match_triangulation<<<A->batch, BOW_THREADS, lds, fb::as_stream(stream)>>>(*A, descInLds, 0, nullptr);

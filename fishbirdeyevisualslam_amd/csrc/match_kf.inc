@@ -20,12 +20,15 @@ struct KfTargetLds {
   int n;
 };
 
-__device__ __forceinline__ KfTargetLds stage_kf(uint8_t *smem, const fb_kf_target &K, int b, bool withDesc) {
+__device__ __forceinline__ Carve kf_carve(const fb_kf_target &K, bool withDesc) {
+  return Carve(K.kf_stride, K.grid.cols * K.grid.rows, withDesc);
+}
+__device__ __forceinline__ KfTargetLds stage_kf(uint8_t *smem, const Carve &cv, const fb_kf_target &K, int b, bool withDesc) {
   const int ncell = K.grid.cols * K.grid.rows;
   const size_t o = (size_t)b * K.kf_stride;
   KfTargetLds r;
   r.n = K.n_kf[b];
-  r.T = stage_target(smem, Carve(K.kf_stride, ncell, withDesc), r.n, ncell, K.kf_kps + o, K.kf_desc + o * 32, K.kf_cell_start + (size_t)b * (ncell + 1),
+  r.T = stage_target(smem, cv, r.n, ncell, K.kf_kps + o, K.kf_desc + o * 32, K.kf_cell_start + (size_t)b * (ncell + 1),
                      K.kf_cell_items + o, withDesc);
   return r;
 }
@@ -100,8 +103,11 @@ template <int MODE>
 __global__ __launch_bounds__(MATCH_THREADS) void k_fuse_search(fb_fuse_args A, int descInLds) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
-  const KfTargetLds KT = stage_kf(smem, A.kf, b, descInLds != 0);
-  __shared__ float s_T[12], s_Ow[3];
+  const KfTargetLds KT = stage_kf(smem, kf_carve(A.kf, descInLds != 0), A.kf, b, descInLds != 0);
+  struct Shared { float T[12], Ow[3]; };
+  __shared__ Shared s_;
+  static_assert(up16(sizeof(Shared)) == STATIC_FUSE, "match_plan.h");
+  auto &s_T = s_.T; auto &s_Ow = s_.Ow;
   if (tid == 0) {
     if (MODE == MODE_FUSE) {
       for (int i = 0; i < 12; i++) s_T[i] = A.pose[(size_t)b * 12 + i];
@@ -129,16 +135,22 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_fuse_search(fb_fuse_args A, i
 __global__ __launch_bounds__(MATCH_THREADS) void k_proj_sim3(fb_proj_sim3_args A, int descInLds) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
-  const KfTargetLds KT = stage_kf(smem, A.kf, b, descInLds != 0);
+  const Carve cv = kf_carve(A.kf, descInLds != 0);
+  const KfTargetLds KT = stage_kf(smem, cv, A.kf, b, descInLds != 0);
   const int nkf = KT.n, ms = A.mp.mp_stride, ks = A.kf.kf_stride;
-  __shared__ float s_T[12], s_Ow[3];
-  __shared__ fb::ClaimFlags s_cf;
+  struct Shared { float T[12], Ow[3]; fb::ClaimFlags cf; };
+  __shared__ Shared s_;
+  static_assert(up16(sizeof(Shared)) == STATIC_PROJ_SIM3, "match_plan.h");
+  auto &s_T = s_.T; auto &s_Ow = s_.Ow; auto &s_cf = s_.cf;
   if (tid == 0) decompose_sim3(A.Scw + (size_t)b * 12, s_T, s_Ow);
   const size_t mo = (size_t)b * ms, ko = (size_t)b * ks;
   const int nmp = A.mp.n_mp[b];
-  // owners [2][ks]; per-point state is one u16 pair (vpPoints of a loop closure can be several thousand); the cheap
-  // geometric gates are re-evaluated every round instead of being stored
-  fb::Claims<uint16_t> C(s_cf, KT.T.rest, ks, ms, A.kf_matched ? A.kf_matched + ko : nullptr, nkf, nmp);
+  // per-point state is one u16 pair (vpPoints of a loop closure can be several thousand); the cheap geometric gates are
+  // re-evaluated every round instead of being stored
+  ClaimsLds L;
+  claims_layout(L, cv.end, ks, ms, 2, CLAIMS_U16_SLACK);
+  fb::Claims<uint16_t> C(s_cf, lds_at<int>(smem, L.owners), ks, lds_at<uint16_t>(smem, L.assigns), ms,
+                         A.kf_matched ? A.kf_matched + ko : nullptr, nkf, nmp);
   C.start();
   const float th = (float)A.th;
   for (int round = 0; C.more(round); round++) {
@@ -203,11 +215,14 @@ __device__ __forceinline__ void sim3_direction(const fb_kf_target &Kt, const Tar
 __global__ __launch_bounds__(MATCH_THREADS) void k_sim3(fb_sim3_args A, int carveStride, int carveCells, int descInLds) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
-  const Carve cv(carveStride, carveCells, descInLds != 0);
-  int *vnMatch1 = reinterpret_cast<int *>(smem + cv.end);  // [mp1 stride]
-  int *vnMatch2 = vnMatch1 + A.mp1.mp_stride;              // [mp2 stride]
-  __shared__ float s_sR12[9], s_sR21[9], s_t21[3], s_t12[3], s_T1[12], s_T2[12];
-  __shared__ int s_n;
+  Sim3Lds L;  // behind the carve of the larger key frame
+  sim3_layout(L, Carve(carveStride, carveCells, descInLds != 0).end, A.mp1.mp_stride, A.mp2.mp_stride);
+  int *vnMatch1 = lds_at<int>(smem, L.match1), *vnMatch2 = lds_at<int>(smem, L.match2);
+  struct Shared { float sR12[9], sR21[9], t21[3], t12[3], T1[12], T2[12]; int n; };
+  __shared__ Shared s_;
+  static_assert(up16(sizeof(Shared)) == STATIC_SIM3, "match_plan.h");
+  auto &s_sR12 = s_.sR12; auto &s_sR21 = s_.sR21; auto &s_t21 = s_.t21; auto &s_t12 = s_.t12; auto &s_T1 = s_.T1; auto &s_T2 = s_.T2;
+  auto &s_n = s_.n;
   if (tid == 0) {
     const float s12 = A.s12[b], *R12 = A.R12 + (size_t)b * 9, *t12 = A.t12 + (size_t)b * 3;
     const float inv = (float)(1.0 / (double)s12);
@@ -226,13 +241,13 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_sim3(fb_sim3_args A, int carv
   const int N1 = A.mp1.n_mp[b], N2 = A.mp2.n_mp[b];
   const size_t o1 = (size_t)b * A.mp1.mp_stride, o2 = (size_t)b * A.mp2.mp_stride;
   {  // KF1 points into KF2
-    const KfTargetLds KT = stage_kf(smem, A.kf2, b, descInLds != 0);
+    const KfTargetLds KT = stage_kf(smem, kf_carve(A.kf2, descInLds != 0), A.kf2, b, descInLds != 0);
     __syncthreads();
     sim3_direction(A.kf2, KT.T, A.mp1, o1, N1, s_T1, s_sR21, s_t21, A.th, vnMatch1);
   }
   __syncthreads();
   {  // KF2 points into KF1
-    const KfTargetLds KT = stage_kf(smem, A.kf1, b, descInLds != 0);
+    const KfTargetLds KT = stage_kf(smem, kf_carve(A.kf1, descInLds != 0), A.kf1, b, descInLds != 0);
     __syncthreads();
     sim3_direction(A.kf1, KT.T, A.mp2, o2, N2, s_T2, s_sR12, s_t12, A.th, vnMatch2);
   }
@@ -262,16 +277,16 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_init_match(fb_init_match_args
   // per-query state in 16 bits (indices < 65536, distances <= 256) so that 2 x 4000 key points fit
   typedef unsigned short u16;
   constexpr int NONE16 = 0xFFFF;
-  int *headA = reinterpret_cast<int *>(smem + cv.end);  // [f2_stride] first claimer of a target, -1 = none
-  int *headB = headA + A.f2_stride;
-  u16 *nextA = reinterpret_cast<u16 *>(headB + A.f2_stride);  // [f1_stride] next claimer, NONE16 = end
-  u16 *nextB = nextA + A.f1_stride;
-  u16 *assignA = nextB + A.f1_stride;                   // [f1_stride] target or NONE16
-  u16 *assignB = assignA + A.f1_stride;
-  u16 *distA = assignB + A.f1_stride;                   // [f1_stride] accepted distance
-  u16 *distB = distA + A.f1_stride;
-  __shared__ int s_changed, s_n;
-  __shared__ fb::RotHist s_rot;
+  InitLds L;
+  init_layout(L, cv.end, A.f1_stride, A.f2_stride);
+  int *headA = lds_at<int>(smem, L.headA), *headB = lds_at<int>(smem, L.headB);      // first claimer of a target, -1 = none
+  u16 *nextA = lds_at<u16>(smem, L.nextA), *nextB = lds_at<u16>(smem, L.nextB);      // next claimer, NONE16 = end
+  u16 *assignA = lds_at<u16>(smem, L.assignA), *assignB = lds_at<u16>(smem, L.assignB);  // target or NONE16
+  u16 *distA = lds_at<u16>(smem, L.distA), *distB = lds_at<u16>(smem, L.distB);      // accepted distance
+  struct Shared { int changed, n; fb::RotHist rot; };
+  __shared__ Shared s_;
+  static_assert(up16(sizeof(Shared)) == STATIC_INIT, "match_plan.h");
+  auto &s_changed = s_.changed; auto &s_n = s_.n; auto &s_rot = s_.rot;
   for (int i = tid; i < n2; i += nt) headA[i] = -1;
   for (int q = tid; q < n1; q += nt) { assignA[q] = NONE16; distA[q] = 0; nextA[q] = NONE16; }
   __syncthreads();
@@ -401,8 +416,8 @@ int fuse_dev(const fb_fuse_args *A, void *stream, const char *what) {
   FB_ARG(MODE != MODE_FUSE || A->Ow);
   if (A->batch == 0 || A->mp.mp_stride == 0) return FB_OK;
   const int ncell = A->kf.grid.cols * A->kf.grid.rows;
-  LdsPlan lp;
-  FB_TRY(plan_lds(A->kf.kf_stride, ncell, 0, what, &lp));
+  DescPlan lp;
+  FB_TRY(plan_staged(A->kf.kf_stride, ncell, [](size_t at) { return at; }, STATIC_FUSE, what, &lp));
   const size_t lds = lp.bytes;
   FB_TRY(set_max_lds(k_fuse_search<MODE>, lds));
   fb::ProfScope prof_(fb::P_FUSE, fb::as_stream(stream));
@@ -443,8 +458,10 @@ int fb_match_projection_sim3_dev(const fb_proj_sim3_args *A, void *stream) {
   FB_ARG(A && A->batch >= 0 && kf_target_ok(A->kf) && A->mp.mp_stride >= 0 && A->Scw && A->match_kf_to_mp && A->nmatches);
   if (A->batch == 0) return FB_OK;
   const int ncell = A->kf.grid.cols * A->kf.grid.rows;
-  LdsPlan lp;
-  FB_TRY(plan_lds(A->kf.kf_stride, ncell, 2 * A->kf.kf_stride + A->mp.mp_stride + 2, "fb_match_projection_sim3", &lp));
+  DescPlan lp;
+  ClaimsLds L;
+  FB_TRY(plan_staged(A->kf.kf_stride, ncell, [&](size_t at) { return claims_layout(L, at, A->kf.kf_stride, A->mp.mp_stride, 2, CLAIMS_U16_SLACK); },
+                     STATIC_PROJ_SIM3, "fb_match_projection_sim3", &lp));
   const size_t lds = lp.bytes;
   FB_TRY(set_max_lds(k_proj_sim3, lds));
   fb::ProfScope prof_(fb::P_FUSE, fb::as_stream(stream));
@@ -478,8 +495,9 @@ int fb_match_sim3_dev(const fb_sim3_args *A, void *stream) {
   if (A->batch == 0) return FB_OK;
   const int nc1 = A->kf1.grid.cols * A->kf1.grid.rows, nc2 = A->kf2.grid.cols * A->kf2.grid.rows;
   const int cs = A->kf1.kf_stride > A->kf2.kf_stride ? A->kf1.kf_stride : A->kf2.kf_stride, cc = nc1 > nc2 ? nc1 : nc2;
-  LdsPlan lp;
-  FB_TRY(plan_lds(cs, cc, A->mp1.mp_stride + A->mp2.mp_stride, "fb_match_sim3", &lp));
+  DescPlan lp;
+  Sim3Lds L;
+  FB_TRY(plan_staged(cs, cc, [&](size_t at) { return sim3_layout(L, at, A->mp1.mp_stride, A->mp2.mp_stride); }, STATIC_SIM3, "fb_match_sim3", &lp));
   const size_t lds = lp.bytes;
   FB_TRY(set_max_lds(k_sim3, lds));
   fb::ProfScope prof_(fb::P_FUSE, fb::as_stream(stream));
@@ -514,11 +532,12 @@ int fb_match_initialization_dev(const fb_init_match_args *A, void *stream) {
   if (A->batch == 0) return FB_OK;
   const int ncell = A->grid.cols * A->grid.rows;
   FB_ARG(A->f1_stride < 65535);
-  const int extra = 2 * A->f2_stride + 3 * A->f1_stride + 2;  // two int heads per target, six u16 per query
-  size_t lds = match_lds_bytes(A->f2_stride, ncell, extra);
-  const int descInLds = lds <= 160 * 1024;  // 2 x 4000 key points of the initialisation extractor do not fit with descriptors
-  if (!descInLds) lds = match_lds_bytes(A->f2_stride, ncell, extra, false);
-  FB_TRY(check_lds(lds, "fb_match_initialization"));
+  DescPlan lp;  // 2 x 4000 key points of the initialisation extractor do not fit with descriptors
+  InitLds L;
+  FB_TRY(plan_staged(A->f2_stride, ncell, [&](size_t at) { return init_layout(L, at, A->f1_stride, A->f2_stride); }, STATIC_INIT,
+                     "fb_match_initialization", &lp));
+  const size_t lds = lp.bytes;
+  const int descInLds = lp.descInLds;
   FB_TRY(set_max_lds(k_init_match, lds));
   fb::ProfScope prof_(fb::P_FUSE, fb::as_stream(stream));
   k_init_match<<<A->batch, MATCH_THREADS, lds, fb::as_stream(stream)>>>(*A, descInLds);

@@ -43,13 +43,13 @@ def _vp(t):
     return C.c_void_p(t.data_ptr())
 
 
-def _make_pipe(B, seed=0):
+def _make_pipe(B, seed=0, **kw):
     import torch  # noqa: F401
     from fishbirdeyevisualslam_amd import synth
     from fishbirdeyevisualslam_amd.pipeline import FramePipeline
     front = np.stack([synth.synth_image(3100 + seed + i, *FRONT_WH) for i in range(B)])
     bird = np.stack([synth.synth_image(3600 + seed + i, *BIRD_WH) for i in range(B)])
-    pipe = FramePipeline(B, FRONT_WH, BIRD_WH, device="cuda:0", fx=120.0, fy=120.0)
+    pipe = FramePipeline(B, FRONT_WH, BIRD_WH, device="cuda:0", fx=120.0, fy=120.0, **kw)
     pipe.set_images(front, bird)
     pipe.build_world(seed=7300 + seed)
     return pipe
@@ -58,10 +58,10 @@ def _make_pipe(B, seed=0):
 class _Bed:
     """One pipeline and a pristine copy of its extraction and world: set 0 runs the separate entry points, set 1 the fused ones."""
 
-    def __init__(self, B):
+    def __init__(self, B, **kw):
         import torch
         self.torch = torch
-        self.pipe = _make_pipe(B)
+        self.pipe = _make_pipe(B, **kw)
         p = self.pipe
         torch.cuda.synchronize()
         self.pristine = {k: p._sets[0][k].clone() for k in INPUTS}
@@ -213,6 +213,49 @@ def test_frame_at_capacity(bed3):
         _put_frame(bed3, 1, side, _crafted_kps(g, cap, wh, nlevels=nl), g.integers(0, 256, (cap, 32), dtype=np.uint8))
     sep = bed3.check()
     assert sep["e_nf"][1] == cap and sep["e_nb"][1] == cap
+
+
+def _large_stride_bed(nfeatures, side, **kw):
+    """Batch 2 at a key-point stride of nfeatures + 64, where the 160 KiB of LDS decide the variant (the stride decides, not
+    the count).  Frame 0 is the real extraction; frame 1 of `side` is filled to the stride behind its real key points, so
+    that every array of the launch is used to its end while the matches of the real key points stay."""
+    from fishbirdeyevisualslam_amd import synth
+    bed = _Bed(2, orb=dict(synth.ORB_DEFAULT, nfeatures=nfeatures), **kw)
+    p = bed.pipe
+    assert p.cap == nfeatures + 64
+    S = p._sets[0]
+    n = int(S[side + "_n"][1])
+    k = S[side + "_kps"][1].cpu().numpy().view(cabi.KP_DTYPE)[:n]
+    d = S[side + "_desc"][1, :n].cpu().numpy()
+    g = np.random.default_rng(13)
+    fill = _crafted_kps(g, p.cap - n, FRONT_WH if side == "f" else BIRD_WH, nlevels=p.params.nlevels)
+    _put_frame(bed, 1, side, np.concatenate([k, fill]), np.concatenate([d, g.integers(0, 256, (p.cap - n, 32), dtype=np.uint8)]))
+    return bed
+
+
+@pytest.mark.gpu
+def test_front_tail_with_the_grid_items_outside_lds():
+    """cur 2800 / last 1400 on the 64 x 48 grid: the staged frame and the grid's counters fit the LDS, the 2800 items of the
+    build do not (itemsInLds = 0; tests/cpp/match_plan_test.cpp pins the shape), so they are sorted in the caller's array
+    and staged from there."""
+    bed = _large_stride_bed(2736, "f", n_last=1400)
+    try:
+        sep = bed.check()
+        assert sep["e_nf"].tolist()[1] == 2800 and (sep["nm_front"] > 0).all(), sep["nm_front"]
+    finally:
+        bed.pipe.close()
+
+
+@pytest.mark.gpu
+def test_bird_tail_with_items_and_camera_copy_outside_lds():
+    """Stride 3200 on the 32 x 32 bird grid: descriptors in LDS, but neither the grid items nor the LDS copy of the camera
+    positions fit beside them (itemsInLds = 0, camInLds = 0; pinned in tests/cpp/match_plan_test.cpp)."""
+    bed = _large_stride_bed(3136, "b")
+    try:
+        sep = bed.check()
+        assert sep["e_nb"].tolist()[1] == 3200 and (sep["nm_bird"] > 0).all(), sep["nm_bird"]
+    finally:
+        bed.pipe.close()
 
 
 @pytest.mark.gpu

@@ -1,5 +1,6 @@
-"""Frames with more key points than the LDS-staged descriptor table holds (~2900): the matchers keep the descriptors in
-HBM/L2 and stage only positions, octaves and the grid.  Same bit-exact parity as the regular sizes."""
+"""Frames with more key points than the LDS-staged descriptor table holds (DESIGN.md section 4 lists, per kernel, the
+variants and the shapes at which they change): the matchers keep the descriptors in HBM/L2 and stage only positions, octaves
+and the grid.  Same bit-exact parity as the regular sizes."""
 import numpy as np
 import pytest
 
@@ -36,6 +37,17 @@ def test_front_matchers_large(n):
     cs, ci = P.build_grid_host([p["cur_kps"] for p in probs], geom, O.grid_build, n)
     _both(lambda: M.proj_kf_args(probs, cs, ci), "orc_match_projection_keyframe", "fb_match_projection_keyframe",
           ["match_cur_to_kf", "nmatches"])
+
+
+def test_m3_descriptors_in_lds_without_the_cache():
+    """cur 2000 / last 2400: the second rung of the M3 ladder -- the descriptor table fits the LDS, the 2400 x 4 cached
+    candidates beside it do not, so every round walks the grid again (pinned in tests/cpp/match_plan_test.cpp)."""
+    geom = P.grid_geom(synth.front_grid_geom(1280, 720))
+    probs = [synth.make_proj_frame_problem(2650 + i, 2000, 2400, dup_frac=0.2) for i in range(2)]
+    cs, ci = P.build_grid_host([p["cur_kps"] for p in probs], geom, O.grid_build, 2000)
+    out = _both(lambda: P.proj_frame_args(probs, cs, ci), "orc_match_projection_frame", "fb_match_projection_frame",
+                ["match_cur_to_last", "nmatches"])
+    assert out["nmatches"].min() > 500
 
 
 def test_bird_matchers_large():
