@@ -24,6 +24,20 @@ COUNTS = [63, 64, 65, 127,
           0, 1, 66, 2]
 
 
+def params(**kw):
+    """The thresholds the counts of this file are computed at, passed explicitly (the package default is 15 / 5)."""
+    return O.orb_params(ini_th_fast=INI_TH, min_th_fast=MIN_TH, **kw)
+
+
+def redone_cells_hold_low_responses(c, w, h, counts):
+    """Evidence that the redo pass, not the first pass, produced the candidates of the large cells: every cell with 63 or
+    more spots holds candidates whose response lies below 15 (a first pass at any threshold >= 15 finds none of them)."""
+    for k, (x0, y0, x1, y1) in enumerate(interiors(w, h)):
+        if counts[k] >= 63:
+            r = c[(c[:, 0] >= x0) & (c[:, 0] < x1) & (c[:, 1] >= y0) & (c[:, 1] < y1), 2]
+            assert len(r) > 0 and r.min() < 15, (k, counts[k], len(r))
+
+
 def grid(w, h):
     """Level-0 cell grid of ComputeKeyPointsOctTree: (nCols, nRows, wCell, hCell)."""
     width, height = w - 2 * BORDER, h - 2 * BORDER
@@ -103,7 +117,7 @@ def test_trip_boundaries_at_ini_threshold(nlevels):
     assert grid(152, 122) == (4, 3, 30, 30)
     img = spots_image(152, 122, COUNTS, 30, 150, seed=1)
     assert cell_counts(img, INI_TH) == COUNTS
-    c = check_image(O.orb_params(nfeatures=1500 if nlevels == 1 else 3000, nlevels=nlevels), img)
+    c = check_image(params(nfeatures=1500 if nlevels == 1 else 3000, nlevels=nlevels), img)
     assert 0 < len(c) <= sum(COUNTS)  # a spot with spots on its ring (lattice diagonals) may be listed and still be no corner
 
 
@@ -112,8 +126,9 @@ def test_trip_boundaries_of_the_redo_pass():
     minThFAST and scores list B only."""
     img = spots_image(152, 122, COUNTS, 9, 20, seed=2)
     assert cell_counts(img, INI_TH) == [0] * 12 and cell_counts(img, MIN_TH) == COUNTS
-    c = check_image(O.orb_params(nfeatures=1500, nlevels=1), img)
+    c = check_image(params(nfeatures=1500, nlevels=1), img)
     assert 0 < len(c) <= sum(COUNTS) and c[:, 2].max() < INI_TH
+    redone_cells_hold_low_responses(c, 152, 122, COUNTS)
 
 
 def test_redo_pass_with_both_lists():
@@ -129,8 +144,9 @@ def test_redo_pass_with_both_lists():
     a, b = cell_counts(img, INI_TH), cell_counts(img, MIN_TH)
     crossed = [k for k in range(12) if a[k] > 0]
     assert len(crossed) >= 4 and all(b[k] > a[k] for k in crossed if COUNTS[k] >= 63)
-    c = check_image(O.orb_params(nfeatures=1500, nlevels=1), img)
+    c = check_image(params(nfeatures=1500, nlevels=1), img)
     assert len(c) > 100 and c[:, 2].max() < INI_TH   # no cell kept a corner at iniThFAST
+    redone_cells_hold_low_responses(c, 152, 122, COUNTS)
 
 
 def test_more_than_256_listed_pixels():
@@ -140,8 +156,8 @@ def test_more_than_256_listed_pixels():
     img = spots_image(152, 122, COUNTS, 30, 150, seed=4, noise_cells=noise)
     got = cell_counts(img, INI_TH)
     assert min(got[k] for k in noise) > 256, got
-    check_image(O.orb_params(nfeatures=1500, nlevels=1), img)
-    check_image(O.orb_params(nfeatures=3000), img)
+    check_image(params(nfeatures=1500, nlevels=1), img)
+    check_image(params(nfeatures=3000), img)
 
 
 @pytest.mark.parametrize("w,h,pitch,counts", [
@@ -156,16 +172,17 @@ def test_wide_cells(w, h, pitch, counts):
     assert (44 if pitch == 56 else 56) < ((wc + 12) & ~3) <= pitch
     img = spots_image(w, h, counts, 30, 150, seed=5)
     assert cell_counts(img, INI_TH) == counts
-    c = check_image(O.orb_params(nfeatures=1500, nlevels=1), img)
+    c = check_image(params(nfeatures=1500, nlevels=1), img)
     assert 0 < len(c) <= sum(counts)
     img2 = spots_image(w, h, counts, 9, 20, seed=6)  # and through the redo pass
     assert cell_counts(img2, MIN_TH) == counts and sum(cell_counts(img2, INI_TH)) == 0
-    c = check_image(O.orb_params(nfeatures=1500, nlevels=1), img2)
+    c = check_image(params(nfeatures=1500, nlevels=1), img2)
     assert 0 < len(c) <= sum(counts)
+    redone_cells_hold_low_responses(c, w, h, counts)
 
 
 def test_scene_crop_with_wide_cells():
     """A crop of a synthetic scene, 209 x 91 at one level: 5 x 1 cells of 36 x 59 (56-byte pitch, tall cells)."""
     img = synth.synth_image(1000, 640, 480)[100:191, 200:409].copy()
     assert grid(209, 91) == (5, 1, 36, 59)
-    check_image(O.orb_params(nfeatures=1500, nlevels=1), img)
+    check_image(params(nfeatures=1500, nlevels=1), img)
