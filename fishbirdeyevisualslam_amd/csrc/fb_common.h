@@ -187,6 +187,25 @@ inline void stage(Stager &st, fb_feature_vector &d, size_t n) {
   st.in(d.items, n * (size_t)d.item_stride * 4);
 }
 
+// The key-frame pair of the two Sim3 stages (fb_sim3_solver_args / fb_optimize_sim3_args: pKF1 with batch 1, C candidates
+// pKF2) joins the call's staged upload: what the kernels read of kf1 / kf2 / mp1 / mp2, T1w / T2w and kf2_index.  The unread
+// pointer fields are set to nullptr, so that none holds a host address.
+template <typename Args>
+inline void stage_sim3_pair(Stager &st, Args &D, size_t C) {
+  const size_t s1 = D.kf1.kf_stride, s2 = D.kf2.kf_stride;
+  st.in(D.kf1.n_kf, 4); st.in(D.kf1.kf_kps, s1 * sizeof(fb_keypoint));
+  st.in(D.kf2.kf_kps, C * s2 * sizeof(fb_keypoint));
+  D.kf2.n_kf = nullptr;
+  for (fb_kf_target *k : {&D.kf1, &D.kf2}) { k->kf_desc = nullptr; k->kf_cell_start = nullptr; k->kf_cell_items = nullptr; }
+  st.in(D.mp1.mp_valid, s1); st.in(D.mp1.mp_xw, s1 * 12);
+  st.in(D.mp2.mp_valid, C * s2); st.in(D.mp2.mp_xw, C * s2 * 12);
+  for (fb_mp_list *m : {&D.mp1, &D.mp2}) {
+    m->n_mp = nullptr; m->mp_normal = nullptr; m->mp_max_dist = nullptr; m->mp_min_dist = nullptr; m->mp_desc = nullptr;
+  }
+  st.in(D.T1w, 48); st.in(D.T2w, C * 48);
+  st.in(D.kf2_index, C * s2 * 4);
+}
+
 // v of the lane selected by the DPP control, +0.0 where there is none
 template <int CTRL>
 __device__ __forceinline__ double dpp_f64(double v) {

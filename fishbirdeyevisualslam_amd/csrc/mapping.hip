@@ -22,6 +22,7 @@
 // cv::Mat::dot return double.  Parity with OpenCV itself is unpinned for the pieces OpenCV computes internally (3x3 inverse,
 // the 4x4 SVD, Mat / scalar): OpenCV is not vendored.  The host restatement under tests/ repeats every expression below.
 #include "fb_common.h"
+#include "sim3_plan.h"  // s3::up256, s3::check_workspace
 
 namespace fb {
 int match_triangulation_shared(const fb_triangulation_args &A, const int32_t *skip, hipStream_t stream);  // match_bow.hip
@@ -51,7 +52,7 @@ struct WS {          // per neighbour arrays written by k_np_prep, packed the wa
   float *win_xw;     // [kf1_stride][3]
 };
 
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+using s3::up256;
 
 size_t carve(uint8_t *p, int n_nb, int s1, WS *w) {
   size_t off = 0;
@@ -427,11 +428,7 @@ int fb_create_new_map_points_dev(const fb_new_points_args *A, void *stream) {
   }
   FB_ARG(A->n2 && A->kps2 && A->desc2 && A->Tcw2 && A->has_mp2 && A->nb_mp_xw && A->nb_before_kf1 && A->xw && A->normal &&
          A->max_dist && A->min_dist && A->desc && A->idx1 && A->nb && A->idx2 && A->kf2_new && A->nb_matches && A->nb_new && A->nb_skipped);
-  const size_t need = carve(nullptr, A->n_nb, A->kf1_stride, nullptr);
-  if (!A->workspace || A->workspace_bytes < need || ((uintptr_t)A->workspace % 16) != 0) {
-    fb::set_error("fb_create_new_map_points_dev: workspace of %zu bytes (16-byte aligned) needed", need);
-    return FB_ERR_ARG;
-  }
+  FB_TRY(s3::check_workspace("fb_create_new_map_points_dev", A->workspace, A->workspace_bytes, carve(nullptr, A->n_nb, A->kf1_stride, nullptr)));
   WS W;
   carve(static_cast<uint8_t *>(A->workspace), A->n_nb, A->kf1_stride, &W);
   NbStarts S;

@@ -26,18 +26,15 @@
 // reciprocal shortcuts of pose.hip are not taken here.
 #include "fb_common.h"
 #include "fb_lm.h"
-#include "fb_primitives.h"
 #include "fb_se3.h"
-
-#include <atomic>
+#include "fb_sim3_pairs.h"
 
 namespace {
 
-constexpr int NT = 256;                 // one wave per SIMD: the whole register file for the 15-estimate edge pass
+constexpr int NT = s3::OPT_THREADS;     // one wave per SIMD: the whole register file for the 15-estimate edge pass
 constexpr int NW = NT / 64;
-constexpr int NCOL = 13;                // dword columns of a correspondence
+constexpr int NCOL = s3::OPT_NCOL;      // dword columns of a correspondence
 constexpr int NACC = 1 + 28 + 7;        // chi2, 28 x H upper, 7 x b
-constexpr size_t LDS_BUDGET = 160 * 1024 - 40 * 1024;  // what the columns may take beside the fixed state (4 KB) and s_J (28 KB)
 
 using fb::Sim3d;
 
@@ -51,6 +48,11 @@ struct Sim3Lds {  // the St of fb_lm.h
   Sim3d P[15], Pinv[15];  // [2 d] = Sim3(+delta e_d) * T, [2 d + 1] = Sim3(-delta e_d) * T, [14] = T
 };
 
+// Every static __shared__ byte of k_optimize_sim3 is its three objects S, s_J and s_wv.  They stay three objects: as members of
+// one struct the compiler assigned the registers of the whole kernel anew and it ran 1 % longer.
+static_assert(sizeof(Sim3Lds) == s3::OPT_STATE_BYTES && sizeof(Sim3Lds) + sizeof(double[14 * NT]) + sizeof(int[NW]) == s3::STATIC_OPTIMIZE,
+              "sim3_plan.h states the static LDS of k_optimize_sim3");
+
 struct SolveSim3 {
   int fix_scale;
   __device__ __forceinline__ bool solve(const double *H, double lambda, const double *b, double *x) const { return fb::ldlt<7>(H, lambda, b, x); }
@@ -59,9 +61,6 @@ struct SolveSim3 {
     return fb::sim3_mul(fb::sim3_exp(x), T);
   }
 };
-
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-size_t ws_bytes(int C, int s1) { return up256((size_t)C * NCOL * s1 * 4); }
 
 // one row of the columns (cols[f * cap + r])
 struct Corr { float p1[3], p2[3], o1[2], o2[2], inf1, inf2; };
@@ -73,12 +72,6 @@ __device__ __forceinline__ Corr load_corr(const uint32_t *cols, int cap, int r) 
   c.o2[0] = __uint_as_float(cols[8 * cap + r]); c.o2[1] = __uint_as_float(cols[9 * cap + r]);
   c.inf1 = __uint_as_float(cols[10 * cap + r]); c.inf2 = __uint_as_float(cols[11 * cap + r]);
   return c;
-}
-
-// R*Xw + t of a cv::Mat 3x3 * 3x1 product in float, row r of the row-major 3x4 T
-__device__ __forceinline__ float rowmul(const float *T, int r, float X, float Y, float Z) {
-#pragma clang fp contract(off)
-  return ((T[r * 4] * X + T[r * 4 + 1] * Y) + T[r * 4 + 2] * Z) + T[r * 4 + 3];
 }
 
 struct Cams { double fx1, fy1, cx1, cy1, fx2, fy2, cx2, cy2; };
@@ -206,7 +199,8 @@ __global__ __launch_bounds__(NT) void k_optimize_sim3(fb_optimize_sim3_args A, u
   const int s1 = A.kf1.kf_stride, s2 = A.kf2.kf_stride, cap = s1;
   uint32_t *cols = IN_LDS ? s_cols : ws + (size_t)c * NCOL * s1;
   int32_t *m12 = A.matches12 + (size_t)c * s1;
-  // ---- gather (Optimizer.cc:1613-1692)
+  // ---- gather (Optimizer.cc:1613-1692).  The walk of s3::walk_pairs written out: through the shared function this kernel ran
+  // 1 % longer.  Which pair is kept is s3::keep_pair with pKF1's index = i itself (:1624).
   int n1 = A.kf1.n_kf[0];
   n1 = n1 < 0 ? 0 : (n1 > s1 ? s1 : n1);
   int ncorr = 0;
@@ -236,8 +230,8 @@ __global__ __launch_bounds__(NT) void k_optimize_sim3(fb_optimize_sim3_args A, u
       if (keep) {  // row < cap: at most one row per i1 < n1 <= s1
         const float *X1 = A.mp1.mp_xw + (size_t)i1 * 3, *X2 = xw2 + (size_t)j * 3;
         for (int q = 0; q < 3; q++) {
-          cols[q * cap + row] = __float_as_uint(rowmul(A.T1w, q, X1[0], X1[1], X1[2]));
-          cols[(3 + q) * cap + row] = __float_as_uint(rowmul(T2, q, X2[0], X2[1], X2[2]));
+          cols[q * cap + row] = __float_as_uint(s3::rowmul(A.T1w, q, X1[0], X1[1], X1[2]));
+          cols[(3 + q) * cap + row] = __float_as_uint(s3::rowmul(T2, q, X2[0], X2[1], X2[2]));
         }
         cols[6 * cap + row] = __float_as_uint(A.kf1.kf_kps[i1].x); cols[7 * cap + row] = __float_as_uint(A.kf1.kf_kps[i1].y);
         cols[8 * cap + row] = __float_as_uint(kps2[i2].x); cols[9 * cap + row] = __float_as_uint(kps2[i2].y);
@@ -415,40 +409,26 @@ int check_args(const fb_optimize_sim3_args *A) {
   return FB_OK;
 }
 
-bool fits_lds(int s1) { return (size_t)s1 * NCOL * 4 <= LDS_BUDGET; }
-
-int allow_large_lds() {
-  static std::atomic<int> done{0};
-  if (done.load()) return FB_OK;
-  FB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_optimize_sim3<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BUDGET));
-  done.store(1);
-  return FB_OK;
-}
-
 }  // namespace
 
 extern "C" {
 
 size_t fb_optimize_sim3_workspace(int n_cand, int kf1_stride) {
   if (n_cand < 0 || kf1_stride < 0) return 0;
-  return fits_lds(kf1_stride) ? 256 : ws_bytes(n_cand, kf1_stride);
+  return s3::optimize_workspace(n_cand, kf1_stride);
 }
 
 int fb_optimize_sim3_dev(const fb_optimize_sim3_args *A, void *stream) {
   FB_TRY(fb::check_device());
   FB_TRY(check_args(A));
   const int C = A->n_cand, s1 = A->kf1.kf_stride;
-  const size_t need = fb_optimize_sim3_workspace(C, s1);
-  const bool inLds = fits_lds(s1);
-  if (!inLds && (!A->workspace || A->workspace_bytes < need || ((uintptr_t)A->workspace % 16) != 0)) {
-    fb::set_error("fb_optimize_sim3_dev: workspace of %zu bytes (16-byte aligned) needed", need);
-    return FB_ERR_ARG;
-  }
+  const s3::LdsPlan plan = s3::plan_optimize(s1);
+  if (!plan.inLds) FB_TRY(s3::check_workspace("fb_optimize_sim3_dev", A->workspace, A->workspace_bytes, s3::optimize_workspace(C, s1)));
   const hipStream_t s = fb::as_stream(stream);
   fb::ProfScope prof_(fb::P_OPT_SIM3, s);
-  if (inLds) {
-    FB_TRY(allow_large_lds());
-    k_optimize_sim3<true><<<C, NT, (size_t)s1 * NCOL * 4, s>>>(*A, nullptr);
+  if (plan.inLds) {
+    FB_TRY(s3::allow_large_lds<&k_optimize_sim3<true>>(s3::OPT_LDS_BUDGET));
+    k_optimize_sim3<true><<<C, NT, plan.bytes, s>>>(*A, nullptr);
   } else {
     k_optimize_sim3<false><<<C, NT, 0, s>>>(*A, static_cast<uint32_t *>(A->workspace));
   }
@@ -461,19 +441,10 @@ int fb_optimize_sim3(const fb_optimize_sim3_args *H) {
   FB_TRY(fb::check_device());
   FB_TRY(check_args(H));
   fb_optimize_sim3_args D = *H;
-  const size_t C = H->n_cand, s1 = H->kf1.kf_stride, s2 = H->kf2.kf_stride, hs = H->hyp_stride > 0 ? H->hyp_stride : 1;
+  const size_t C = H->n_cand, s1 = H->kf1.kf_stride, hs = H->hyp_stride > 0 ? H->hyp_stride : 1;
   fb::DevBuf ws;  // (declared first: it goes back to the pool after the Stager has waited)
   fb::Stager st;
-  st.in(D.kf1.n_kf, 4); st.in(D.kf1.kf_kps, s1 * sizeof(fb_keypoint));
-  st.in(D.kf2.kf_kps, C * s2 * sizeof(fb_keypoint));
-  D.kf1.kf_desc = nullptr; D.kf1.kf_cell_start = nullptr; D.kf1.kf_cell_items = nullptr;  // unread fields hold no host address
-  D.kf2.n_kf = nullptr; D.kf2.kf_desc = nullptr; D.kf2.kf_cell_start = nullptr; D.kf2.kf_cell_items = nullptr;
-  st.in(D.mp1.mp_valid, s1); st.in(D.mp1.mp_xw, s1 * 12);
-  st.in(D.mp2.mp_valid, C * s2); st.in(D.mp2.mp_xw, C * s2 * 12);
-  D.mp1.n_mp = nullptr; D.mp1.mp_normal = nullptr; D.mp1.mp_max_dist = nullptr; D.mp1.mp_min_dist = nullptr; D.mp1.mp_desc = nullptr;
-  D.mp2.n_mp = nullptr; D.mp2.mp_normal = nullptr; D.mp2.mp_max_dist = nullptr; D.mp2.mp_min_dist = nullptr; D.mp2.mp_desc = nullptr;
-  st.in(D.T1w, 48); st.in(D.T2w, C * 48);
-  st.in(D.kf2_index, C * s2 * 4);
+  fb::stage_sim3_pair(st, D, C);
   st.in(D.s12, ((C - 1) * hs + 1) * 4); st.in(D.R12, ((C - 1) * hs + 1) * 36); st.in(D.t12, ((C - 1) * hs + 1) * 12);
   st.out(D.matches12, C * s1 * 4, true);
   st.out(D.n_inliers, C * 4, false); st.out(D.n_correspondences, C * 4, false); st.out(D.n_bad, C * 4, false);

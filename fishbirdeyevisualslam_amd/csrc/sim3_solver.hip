@@ -22,20 +22,19 @@
 // quaternion in double, rounded once to float (the same rotation).  den == 0, |vec| == 0 and z == 0 give
 // inf / NaN as in the reference, and every comparison with them is false.
 #include "fb_common.h"
-#include "fb_primitives.h"
+#include "fb_sim3_pairs.h"
 
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 
 namespace {
 
 constexpr int MAXH = FB_SIM3_MAX_HYP;
-constexpr int PREP_THREADS = 256;
+constexpr int PREP_THREADS = s3::PREP_THREADS;
 constexpr int HYP_THREADS = 256;             // 4 waves
 constexpr int HYP_PER_WAVE = 4;
 constexpr int HYP_PER_BLOCK = HYP_THREADS / 64 * HYP_PER_WAVE;  // 16: 12 candidates x 300 -> 228 workgroups on 256 CUs
-constexpr int NF = 12;                       // dwords per correspondence (fb_sim3_corr)
+constexpr int NF = s3::SOLVER_NF;            // dwords per correspondence (fb_sim3_corr)
 constexpr int JACOBI_SWEEPS = 8;
 
 // SetRansacParameters as a step function of N: first_n[v] = the smallest N >= min_inliers (and <= the KF1 stride) whose
@@ -47,76 +46,39 @@ struct WS {
   uint32_t *soa;  // [C][NF][s1]: the correspondences field by field (lane i reads consecutive words)
 };
 
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-size_t ws_bytes(int C, int s1) { return up256((size_t)C * NF * s1 * 4); }
-
-// Rcw*X + tcw of a cv::Mat 3x3 * 3x1 product in float, row r of the row-major 3x4 T
-__device__ __forceinline__ float rowmul(const float *T, int r, float X, float Y, float Z) {
-  return ((T[r * 4] * X + T[r * 4 + 1] * Y) + T[r * 4 + 2] * Z) + T[r * 4 + 3];
-}
-
 // ---- k_sim3_prepare -------------------------------------------------------------------------------------------------
+struct PrepLds { int wv[PREP_THREADS / 64]; };  // the scan scratch of s3::walk_pairs
+static_assert(sizeof(PrepLds) == s3::STATIC_PREPARE, "sim3_plan.h states the static LDS of k_sim3_prepare");
+
 __global__ __launch_bounds__(PREP_THREADS) void k_sim3_prepare(fb_sim3_solver_args A, ItsTable its, WS W) {
   const int c = blockIdx.x, tid = threadIdx.x;
-  const int s1 = A.kf1.kf_stride, s2 = A.kf2.kf_stride;
-  __shared__ int s_wv[PREP_THREADS / 64];
-  int n1 = A.kf1.n_kf[0];
-  n1 = n1 < 0 ? 0 : (n1 > s1 ? s1 : n1);
-  const int32_t *m12 = A.matches12 + (size_t)c * s1;
-  const uint8_t *v2 = A.mp2.mp_valid + (size_t)c * s2;
-  const float *xw2 = A.mp2.mp_xw + (size_t)c * s2 * 3;
-  const fb_keypoint *kps2 = A.kf2.kf_kps + (size_t)c * s2;
-  const int32_t *ix2 = A.kf2_index ? A.kf2_index + (size_t)c * s2 : nullptr;
-  const float *T2 = A.T2w + (size_t)c * 12;
-  uint32_t *soa = W.soa + (size_t)c * NF * s1;
-  int base = 0;
-  for (int c0 = 0; c0 < n1; c0 += PREP_THREADS) {
-    const int i1 = c0 + tid;
-    bool keep = false;
-    int j = -1, k1 = -1, k2 = -1, o1 = 0, o2 = 0;
-    if (i1 < n1) {
-      j = m12[i1];
-      if (j >= 0 && j < s2 && A.mp1.mp_valid[i1] && v2[j]) {  // vpMatched12[i1], pMP1, !isBad() x 2 (:64-73)
-        k1 = A.kf1_index ? A.kf1_index[i1] : i1;              // GetIndexInKeyFrame (:75-79)
-        k2 = ix2 ? ix2[j] : j;
-        if (k1 >= 0 && k2 >= 0 && k1 < s1 && k2 < s2) {
-          o1 = A.kf1.kf_kps[k1].octave;
-          o2 = kps2[k2].octave;
-          keep = o1 >= 0 && o1 < FB_MAX_LEVELS && o2 >= 0 && o2 < FB_MAX_LEVELS;
+  const int s1 = A.kf1.kf_stride;
+  __shared__ PrepLds L;
+  const int N = s3::walk_pairs<PREP_THREADS>(
+      A.kf1, A.kf2, A.mp1, A.mp2, A.T1w, A.T2w, c, A.matches12, A.kf1_index, A.kf2_index, L.wv,
+      [&](int row, int i1, int, int, int o1, int o2, const float (&P1c)[3], const float (&P2c)[3]) {
+        fb_sim3_corr r;
+        for (int q = 0; q < 3; q++) { r.x3dc1[q] = P1c[q]; r.x3dc2[q] = P2c[q]; }
+        {  // FromCameraToImage (:429-447)
+          const float invz = 1 / r.x3dc1[2];
+          r.p1im1[0] = A.kf1.cam.fx * (r.x3dc1[0] * invz) + A.kf1.cam.cx;
+          r.p1im1[1] = A.kf1.cam.fy * (r.x3dc1[1] * invz) + A.kf1.cam.cy;
         }
-      }
-    }
-    int tot;
-    const int row = base + fb::block_excl_scan<PREP_THREADS>(keep ? 1 : 0, s_wv, &tot);
-    if (keep) {
-      fb_sim3_corr r;
-      const float *X1 = A.mp1.mp_xw + (size_t)i1 * 3, *X2 = xw2 + (size_t)j * 3;
-      for (int q = 0; q < 3; q++) {
-        r.x3dc1[q] = rowmul(A.T1w, q, X1[0], X1[1], X1[2]);
-        r.x3dc2[q] = rowmul(T2, q, X2[0], X2[1], X2[2]);
-      }
-      {  // FromCameraToImage (:429-447)
-        const float invz = 1 / r.x3dc1[2];
-        r.p1im1[0] = A.kf1.cam.fx * (r.x3dc1[0] * invz) + A.kf1.cam.cx;
-        r.p1im1[1] = A.kf1.cam.fy * (r.x3dc1[1] * invz) + A.kf1.cam.cy;
-      }
-      {
-        const float invz = 1 / r.x3dc2[2];
-        r.p2im2[0] = A.kf2.cam.fx * (r.x3dc2[0] * invz) + A.kf2.cam.cx;
-        r.p2im2[1] = A.kf2.cam.fy * (r.x3dc2[1] * invz) + A.kf2.cam.cy;
-      }
-      r.max_err1 = (int32_t)(9.210 * (double)A.level_sigma2[o1]);  // a double product stored into a size_t (:87-88)
-      r.max_err2 = (int32_t)(9.210 * (double)A.level_sigma2[o2]);
-      A.indices1[(size_t)c * s1 + row] = i1;
-      if (A.corr) A.corr[(size_t)c * s1 + row] = r;
-      const uint32_t *rw = reinterpret_cast<const uint32_t *>(&r);
+        {
+          const float invz = 1 / r.x3dc2[2];
+          r.p2im2[0] = A.kf2.cam.fx * (r.x3dc2[0] * invz) + A.kf2.cam.cx;
+          r.p2im2[1] = A.kf2.cam.fy * (r.x3dc2[1] * invz) + A.kf2.cam.cy;
+        }
+        r.max_err1 = (int32_t)(9.210 * (double)A.level_sigma2[o1]);  // a double product stored into a size_t (:87-88)
+        r.max_err2 = (int32_t)(9.210 * (double)A.level_sigma2[o2]);
+        A.indices1[(size_t)c * s1 + row] = i1;
+        if (A.corr) A.corr[(size_t)c * s1 + row] = r;
+        const uint32_t *rw = reinterpret_cast<const uint32_t *>(&r);
+        uint32_t *soa = W.soa + (size_t)c * NF * s1;
 #pragma unroll
-      for (int f = 0; f < NF; f++) soa[(size_t)f * s1 + row] = rw[f];
-    }
-    base += tot;
-  }
+        for (int f = 0; f < NF; f++) soa[(size_t)f * s1 + row] = rw[f];
+      });
   if (tid == 0) {
-    const int N = base;
     int mi = 0;  // SetRansacParameters (:114-138); iterate returns at once when N < mRansacMinInliers (:146-150)
     if (N >= A.min_inliers)
       for (int v = 1; v <= A.max_iterations; v++) mi += its.first_n[v] <= N ? 1 : 0;
@@ -249,10 +211,11 @@ __device__ __forceinline__ void compute_sim3(const float (&P1)[3][3], const floa
     o.T21[i * 4 + 3] = -((o.T21[i * 4] * o.t[0] + o.T21[i * 4 + 1] * o.t[1]) + o.T21[i * 4 + 2] * o.t[2]);
 }
 
-// Sim3Solver::Project (:406-427) + the squared distance of CheckInliers (:374-378): err = dist.dot(dist) stored as float
+// Sim3Solver::Project (:406-427) + the squared distance of CheckInliers (:374-378): err = dist.dot(dist) stored as float.  (The
+// walk's rowmul has the text of the copy this file had; its contract(off) pragma changes nothing in a file built unfused.)
 __device__ __forceinline__ float reproj_err(const float *T, float X, float Y, float Z, float fx, float fy, float cx, float cy,
                                             float u0, float v0, bool firstMinusSecond) {
-  const float xc = rowmul(T, 0, X, Y, Z), yc = rowmul(T, 1, X, Y, Z), zc = rowmul(T, 2, X, Y, Z);
+  const float xc = s3::rowmul(T, 0, X, Y, Z), yc = s3::rowmul(T, 1, X, Y, Z), zc = s3::rowmul(T, 2, X, Y, Z);
   const float invz = 1 / zc;
   const float u = fx * (xc * invz) + cx, v = fy * (yc * invz) + cy;
   const float dx = firstMinusSecond ? u0 - u : u - u0, dy = firstMinusSecond ? v0 - v : v - v0;
@@ -378,17 +341,6 @@ int ransac_max_its(int N, double prob, int minInliers, int maxIterations) {
   return std::max(1, std::min(nIterations, maxIterations));
 }
 
-// the LDS-staged kernel may use up to the whole LDS of a CU: told to the runtime once per device and process
-int allow_large_lds() {
-  static std::atomic<bool> done[64];
-  int dev = 0;
-  FB_HIP(hipGetDevice(&dev));
-  if (dev >= 0 && dev < 64 && done[dev].load()) return FB_OK;
-  FB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_sim3_hypotheses<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512));
-  if (dev >= 0 && dev < 64) done[dev].store(true);
-  return FB_OK;
-}
-
 int check_args(const fb_sim3_solver_args *A) {
   FB_ARG(A && A->n_cand >= 1 && A->kf1.kf_stride > 0 && A->kf2.kf_stride > 0);
   FB_ARG(A->mp1.mp_stride == A->kf1.kf_stride && A->mp2.mp_stride == A->kf2.kf_stride);
@@ -407,18 +359,14 @@ extern "C" {
 
 size_t fb_sim3_solver_workspace(int n_cand, int n1_stride) {
   if (n_cand < 0 || n1_stride < 0) return 0;
-  return ws_bytes(n_cand, n1_stride);
+  return s3::solver_workspace(n_cand, n1_stride);
 }
 
 int fb_sim3_solver_dev(const fb_sim3_solver_args *A, void *stream) {
   FB_TRY(fb::check_device());
   FB_TRY(check_args(A));
   const int C = A->n_cand, s1 = A->kf1.kf_stride;
-  const size_t need = ws_bytes(C, s1);
-  if (!A->workspace || A->workspace_bytes < need || ((uintptr_t)A->workspace % 16) != 0) {
-    fb::set_error("fb_sim3_solver_dev: workspace of %zu bytes (16-byte aligned) needed", need);
-    return FB_ERR_ARG;
-  }
+  FB_TRY(s3::check_workspace("fb_sim3_solver_dev", A->workspace, A->workspace_bytes, s3::solver_workspace(C, s1)));
   const hipStream_t s = fb::as_stream(stream);
   WS W;
   W.soa = static_cast<uint32_t *>(A->workspace);
@@ -434,12 +382,11 @@ int fb_sim3_solver_dev(const fb_sim3_solver_args *A, void *stream) {
     FB_HIP(hipGetLastError());
   }
   {
-    const size_t lds = (size_t)s1 * NF * 4;
-    const bool inLds = lds <= 160 * 1024 - 512;
+    const s3::LdsPlan plan = s3::plan_solver(s1);
     const dim3 grid((A->max_iterations + HYP_PER_BLOCK - 1) / HYP_PER_BLOCK, C);
-    if (inLds) FB_TRY(allow_large_lds());
+    if (plan.inLds) FB_TRY(s3::allow_large_lds<&k_sim3_hypotheses<true>>(s3::SOLVER_LDS_BUDGET));
     fb::ProfScope prof_(fb::P_SIM3_HYP, s);
-    if (inLds) k_sim3_hypotheses<true><<<grid, HYP_THREADS, lds, s>>>(*A, W);
+    if (plan.inLds) k_sim3_hypotheses<true><<<grid, HYP_THREADS, plan.bytes, s>>>(*A, W);
     else k_sim3_hypotheses<false><<<grid, HYP_THREADS, 0, s>>>(*A, W);
     FB_HIP(hipGetLastError());
   }
@@ -456,19 +403,11 @@ int fb_sim3_solver(const fb_sim3_solver_args *H) {
   FB_TRY(fb::check_device());
   FB_TRY(check_args(H));
   fb_sim3_solver_args D = *H;
-  const size_t C = H->n_cand, s1 = H->kf1.kf_stride, s2 = H->kf2.kf_stride, mw = (s1 + 31) / 32;
+  const size_t C = H->n_cand, s1 = H->kf1.kf_stride, mw = (s1 + 31) / 32;
   fb::DevBuf ws;  // (declared first: it goes back to the pool after the Stager has waited)
   fb::Stager st;
-  st.in(D.kf1.n_kf, 4); st.in(D.kf1.kf_kps, s1 * sizeof(fb_keypoint));
-  st.in(D.kf2.kf_kps, C * s2 * sizeof(fb_keypoint));
-  D.kf1.kf_desc = nullptr; D.kf1.kf_cell_start = nullptr; D.kf1.kf_cell_items = nullptr;  // unread fields hold no host address
-  D.kf2.n_kf = nullptr; D.kf2.kf_desc = nullptr; D.kf2.kf_cell_start = nullptr; D.kf2.kf_cell_items = nullptr;
-  st.in(D.mp1.mp_valid, s1); st.in(D.mp1.mp_xw, s1 * 12);
-  st.in(D.mp2.mp_valid, C * s2); st.in(D.mp2.mp_xw, C * s2 * 12);
-  D.mp1.n_mp = nullptr; D.mp1.mp_normal = nullptr; D.mp1.mp_max_dist = nullptr; D.mp1.mp_min_dist = nullptr; D.mp1.mp_desc = nullptr;
-  D.mp2.n_mp = nullptr; D.mp2.mp_normal = nullptr; D.mp2.mp_max_dist = nullptr; D.mp2.mp_min_dist = nullptr; D.mp2.mp_desc = nullptr;
-  st.in(D.T1w, 48); st.in(D.T2w, C * 48);
-  st.in(D.kf1_index, s1 * 4); st.in(D.kf2_index, C * s2 * 4);
+  fb::stage_sim3_pair(st, D, C);
+  st.in(D.kf1_index, s1 * 4);
   st.in(D.matches12, C * s1 * 4);
   st.in(D.accept_above, C * 4);
   st.in(D.rand_idx, C * MAXH * 3 * 4);

@@ -1015,6 +1015,23 @@ struct Sim3KeyFrame {             // what Sim3Solver reads of a KeyFrame
   long mnFrameId = 0;
 };
 
+// the key-frame pair of fb_sim3_solver_args / fb_optimize_sim3_args: n_cand = 1 (one pKF2), kf1 / kf2 / mp1 / mp2, the
+// cameras, T1w / T2w and kf2_index.  n1 must outlive the call (kf1.n_kf points at it).
+template <typename Args>
+inline void fill_sim3_pair(Args &a, const Sim3KeyFrame &kf1, const Sim3KeyFrame &kf2, const int32_t *n1) {
+  const Sim3KeyFrame *kf[2] = {&kf1, &kf2};
+  fb_kf_target *k[2] = {&a.kf1, &a.kf2};
+  fb_mp_list *m[2] = {&a.mp1, &a.mp2};
+  for (int i = 0; i < 2; i++) {
+    k[i]->kf_stride = kf[i]->N; k[i]->kf_kps = kf[i]->mvKeysUn;
+    k[i]->cam.fx = kf[i]->fx; k[i]->cam.fy = kf[i]->fy; k[i]->cam.cx = kf[i]->cx; k[i]->cam.cy = kf[i]->cy;
+    m[i]->mp_stride = kf[i]->N; m[i]->mp_valid = kf[i]->mpValid; m[i]->mp_xw = kf[i]->mpWorldPos;
+  }
+  a.n_cand = 1;
+  a.kf1.n_kf = n1;
+  a.T1w = kf1.Tcw; a.T2w = kf2.Tcw; a.kf2_index = kf2.indexInKeyFrame;
+}
+
 class Sim3Solver {
  public:
   typedef int (*RandomIntFn)(int min, int max);
@@ -1102,7 +1119,7 @@ class Sim3Solver {
 
  private:
   void fill() {
-    const int s1 = kf1_.N, s2 = kf2_.N;
+    const int s1 = kf1_.N;
     mw_ = (s1 + 31) / 32;
     std::vector<int32_t> m12(s1, -1), rnd((size_t)FB_SIM3_MAX_HYP * 3, 0);
     std::copy(m12_.begin(), m12_.end(), m12.begin());
@@ -1118,14 +1135,8 @@ class Sim3Solver {
     int32_t Ndev = 0, maxIts = 0, done = 0, first = 0, noMore = 0;
     fb_sim3_solver_args a;
     memset(&a, 0, sizeof(a));
-    a.n_cand = 1;
-    a.kf1.kf_stride = s1; a.kf1.n_kf = &n1; a.kf1.kf_kps = kf1_.mvKeysUn;
-    a.kf2.kf_stride = s2; a.kf2.kf_kps = kf2_.mvKeysUn;
-    a.kf1.cam.fx = kf1_.fx; a.kf1.cam.fy = kf1_.fy; a.kf1.cam.cx = kf1_.cx; a.kf1.cam.cy = kf1_.cy;
-    a.kf2.cam.fx = kf2_.fx; a.kf2.cam.fy = kf2_.fy; a.kf2.cam.cx = kf2_.cx; a.kf2.cam.cy = kf2_.cy;
-    a.mp1.mp_stride = s1; a.mp1.mp_valid = kf1_.mpValid; a.mp1.mp_xw = kf1_.mpWorldPos;
-    a.mp2.mp_stride = s2; a.mp2.mp_valid = kf2_.mpValid; a.mp2.mp_xw = kf2_.mpWorldPos;
-    a.T1w = kf1_.Tcw; a.T2w = kf2_.Tcw; a.kf1_index = kf1_.indexInKeyFrame; a.kf2_index = kf2_.indexInKeyFrame;
+    fill_sim3_pair(a, kf1_, kf2_, &n1);
+    a.kf1_index = kf1_.indexInKeyFrame;
     a.matches12 = m12.data();
     for (int l = 0; l < FB_MAX_LEVELS; l++) a.level_sigma2[l] = sigma2_[l];
     a.fix_scale = fixScale_ ? 1 : 0;
@@ -1163,14 +1174,7 @@ inline int Optimizer::OptimizeSim3(const Sim3KeyFrame &kf1, const Sim3KeyFrame &
   float scwRows[12];
   fb_optimize_sim3_args a;
   memset(&a, 0, sizeof(a));
-  a.n_cand = 1;
-  a.kf1.kf_stride = kf1.N; a.kf1.n_kf = &n1; a.kf1.kf_kps = kf1.mvKeysUn;
-  a.kf2.kf_stride = kf2.N; a.kf2.kf_kps = kf2.mvKeysUn;
-  a.kf1.cam.fx = kf1.fx; a.kf1.cam.fy = kf1.fy; a.kf1.cam.cx = kf1.cx; a.kf1.cam.cy = kf1.cy;
-  a.kf2.cam.fx = kf2.fx; a.kf2.cam.fy = kf2.fy; a.kf2.cam.cx = kf2.cx; a.kf2.cam.cy = kf2.cy;
-  a.mp1.mp_stride = kf1.N; a.mp1.mp_valid = kf1.mpValid; a.mp1.mp_xw = kf1.mpWorldPos;
-  a.mp2.mp_stride = kf2.N; a.mp2.mp_valid = kf2.mpValid; a.mp2.mp_xw = kf2.mpWorldPos;
-  a.T1w = kf1.Tcw; a.T2w = kf2.Tcw; a.kf2_index = kf2.indexInKeyFrame;
+  fill_sim3_pair(a, kf1, kf2, &n1);
   for (int l = 0; l < FB_MAX_LEVELS; l++) a.inv_level_sigma2[l] = l < nLevels ? mvInvLevelSigma2[l] : 0.0f;
   a.matches12 = vnMatches1.data();
   a.s12 = &s12; a.R12 = R12; a.t12 = t12; a.hyp_stride = 1;

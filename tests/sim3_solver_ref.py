@@ -165,3 +165,37 @@ PARITY_PROBLEMS = [
     (206, [700, 19, 333, 20, 64, 65, 128, 500, 31, 257, 1000, 23], dict(n1=1500, n2=1300, outlier_share=0.1, pixel_noise=0.15)),
 ]
 RAZOR_DECISION_CAP, RAZOR_HYPOTHESIS_CAP = 1e-3, 2e-2
+
+# kept counts at the workgroup size of k_sim3_prepare (256 threads) and its neighbours: the seams of the compaction
+SEAM_PROBLEM = (220, [255, 256, 257], dict(n1=700, n2=640, outlier_share=0.3, pixel_noise=0.2))
+# the last KF1 stride whose correspondences k_sim3_hypotheses stages in LDS and the first it reads from the workspace
+LDS_BOUNDARY_STRIDES = (3402, 3403)
+UNSAFE_CLAUSES = ("match = s2", "index1 = s1", "index2 = s2", "octave1 = -1", "octave1 = FB_MAX_LEVELS", "octave2 = -1",
+                  "octave2 = FB_MAX_LEVELS")
+
+
+def skip_clause_problem(seed=221, n_corr=90, n1=300, n2=280):
+    """One candidate in which every skip clause of the walk occurs.  make_problem plants the reference's own (no match, NULL /
+    bad pMP1, bad pMP2, GetIndexInKeyFrame = -1 on either side); here seven otherwise kept pairs get the values that the
+    project skips for memory safety (UNSAFE_CLAUSES), one each.  The reference, and so the restatement, would index out of
+    bounds with them, so the restatement gets the same problem with those seven matches removed: skipping them is the
+    specification.  -> (problem for the device, problem for the restatement, N both must find)"""
+    import copy
+    from fishbirdeyevisualslam_amd import sim3_problem as SP
+    p = SP.make_problem(seed, [n_corr], n1=n1, n2=n2, pixel_noise=0.2, n_outliers=[0])
+    cd, tr = p["cands"][0], p["truth"][0]
+    i1 = [int(v) for v in tr["i1"][:len(UNSAFE_CLAUSES)]]
+    j = [int(cd["matches12"][i]) for i in i1]
+    assert len(set(j)) == len(j) and all(p["index1"][i] == i for i in i1) and all(cd["index2"][v] == v for v in j)
+    cd["matches12"][i1[0]] = n2
+    p["index1"][i1[1]] = n1
+    cd["index2"][j[2]] = n2
+    p["kps1"]["octave"][i1[3]] = -1
+    p["kps1"]["octave"][i1[4]] = cabi.FB_MAX_LEVELS
+    cd["kps2"]["octave"][j[5]] = -1
+    cd["kps2"]["octave"][j[6]] = cabi.FB_MAX_LEVELS
+    N = n_corr - len(UNSAFE_CLAUSES)
+    p["rand_idx"] = SP.random_int_table(np.random.default_rng(seed + 1), N)[None]
+    ref = copy.deepcopy(p)
+    ref["cands"][0]["matches12"][i1] = -1
+    return p, ref, N

@@ -147,6 +147,29 @@ def test_key_frame_too_large_for_lds_reads_the_workspace():
     assert rc == cabi.FB_ERR_ARG and (got["n_inliers"] == -7).all()
 
 
+@pytest.mark.parametrize("n1", [2363, 2364])
+def test_last_stride_in_lds_and_first_on_the_workspace(n1):
+    """KF1 strides 2363 and 2364: 122 876 B of columns are the last that fit the 120 KiB the kernel may take beside its 32.8 KB
+    of static LDS, 122 928 B the first that do not (csrc/sim3_plan.h).  One candidate with 40 kept pairs, 3 of them wrong (the
+    10-iteration branch); the parity test's model and bounds.  Measured on one MI355X, identical with the library of the commit
+    before the shared walk: s 1.7e-8 / 2.1e-8, t 7.1e-9 / 6.9e-9, Scw 6.0e-8 / 1.2e-7 at the two strides.
+
+    One candidate on purpose, not a narrowed check: which variant runs depends on the stride alone, and the candidates of a call
+    are independent workgroups.  A second candidate of 12 kept pairs was tried and left out: so few pairs condition the scale
+    badly, and the comparison with the model gave s 5.2e-7 against the bound 9.6e-8, the same figure on the library of the commit
+    before."""
+    p = OP.make_problem(23, [40], n1=n1, n2=300, n_outliers=[3])
+    worst = dict(q=0.0, t=0.0, s=0.0, scw_q=0.0, scw_t=0.0, scw_s=0.0, Scw=0.0, gap=np.inf)
+    counts = [0, 0]
+    rc, got = _run_dev(p)
+    assert rc == 0
+    _check(p, got, worst, counts)
+    print("opt_sim3 stride %d: worst " % n1 + " ".join("%s %.3g" % kv for kv in worst.items()))
+    assert counts == [1, 0] and got["n_correspondences"].tolist() == [40] and int(got["n_bad"][0]) == 3
+    for k, tol in TOL.items():
+        assert worst[k] <= tol, (k, worst[k])
+
+
 def test_non_finite_candidate_keeps_its_input_sim3():
     """A NaN map point makes the 7x7 system non-finite on the first step: no trial is accepted (as in g2o, where every
     comparison with NaN is false) and the Sim3 stays at its input; the candidate beside it is untouched by it."""

@@ -218,3 +218,28 @@ def test_razor_share_of_the_gpu_problems_stays_inside_the_caps(seed, n_corr, kw)
     dec, hyp = R.razor_shares(p, tab)
     print("razor shares", seed, dec, hyp)
     assert dec <= R.RAZOR_DECISION_CAP and hyp <= R.RAZOR_HYPOTHESIS_CAP
+
+
+def test_restatement_alone_yields_the_seam_and_skip_clause_counts():
+    """The inputs of the GPU tests of the shared walk, on the CPU: the restatement's constructor keeps exactly 255 / 256 / 257
+    pairs (the workgroup size of k_sim3_prepare and its neighbours), a few dozen at the two strides around the LDS threshold,
+    and N of the problem in which every skip clause occurs; that problem differs from the restatement's copy in nothing but the
+    seven removed matches."""
+    seed, n_corr, kw = R.SEAM_PROBLEM
+    p = SP.make_problem(seed, n_corr, **kw)
+    assert [R.Solver(p, c).N for c in range(p["C"])] == [255, 256, 257]
+    for n1 in R.LDS_BOUNDARY_STRIDES:
+        p = SP.make_problem(219, [60, 25], n1=n1, n2=300, outlier_share=0.3, pixel_noise=0.2)
+        assert [R.Solver(p, c).N for c in range(2)] == [60, 25]
+        dec, hyp = R.razor_shares(p, R.full_table(p))
+        assert dec <= R.RAZOR_DECISION_CAP and hyp <= R.RAZOR_HYPOTHESIS_CAP
+    p, ref, N = R.skip_clause_problem()
+    assert R.Solver(ref, 0).N == N == 83
+    pl = p["truth"][0]["plant"]
+    assert all(len(pl[k]) == 6 for k in ("null1", "index1", "bad2", "index2"))  # the reference's own clauses are planted too
+    m, mr = p["cands"][0]["matches12"], ref["cands"][0]["matches12"]
+    assert (m != mr).sum() == len(R.UNSAFE_CLAUSES) and (mr[m != mr] == -1).all() and (m == p["n2"]).sum() == 1
+    assert (p["index1"] == p["n1"]).sum() == 1 and (p["cands"][0]["index2"] == p["n2"]).sum() == 1
+    assert sorted(p["kps1"]["octave"][(p["kps1"]["octave"] < 0) | (p["kps1"]["octave"] >= cabi.FB_MAX_LEVELS)].tolist()) == [-1, cabi.FB_MAX_LEVELS]
+    o2 = p["cands"][0]["kps2"]["octave"]
+    assert sorted(o2[(o2 < 0) | (o2 >= cabi.FB_MAX_LEVELS)].tolist()) == [-1, cabi.FB_MAX_LEVELS]

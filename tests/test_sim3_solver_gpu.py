@@ -177,6 +177,50 @@ def test_key_frame_too_large_for_lds_reads_the_workspace():
     assert tab[0]["first_accept"] >= 0 and tab[2]["first_accept"] >= 0
 
 
+@pytest.mark.parametrize("n1", R.LDS_BOUNDARY_STRIDES)
+def test_last_stride_in_lds_and_first_on_the_workspace(n1):
+    """KF1 strides 3402 and 3403: 163 296 B of correspondence fields are the last that fit beside k_sim3_hypotheses' LDS budget
+    (160 KiB - 512 B), 163 344 B the first that do not (csrc/sim3_plan.h).  A few dozen kept pairs; the parity test's checks."""
+    p = SP.make_problem(219, [60, 25], n1=n1, n2=300, outlier_share=0.3, pixel_noise=0.2)
+    tab = R.full_table(p)
+    rc, got, _ = _run_dev(p)
+    assert rc == 0
+    worst = _check(p, got, tab)
+    print("sim3 solver stride %d worst |dR| %.3g |dt|/max(1,|t|) %.3g |ds|/s %.3g" % (n1, worst["R"], worst["t"], worst["s"]))
+    for k in ("R", "t", "s"):
+        assert worst[k] <= SRT_TOL[k], (k, worst[k])
+    assert [t["N"] for t in tab] == [60, 25] and tab[0]["first_accept"] >= 0
+
+
+def _check_walk(got, tab):
+    for c, T in enumerate(tab):
+        N = T["N"]
+        assert int(got["N"][c]) == N
+        np.testing.assert_array_equal(got["indices1"][c, :N], T["indices1"])
+        assert (got["indices1"][c, N:] == -7).all()  # rows past N are not written
+        for f in cabi.SIM3_CORR_DTYPE.names:
+            assert np.array_equal(got["corr"][c, :N][f], T["corr"][f], equal_nan=True), (c, f)
+
+
+def test_walk_at_the_block_seams_and_with_every_skip_clause():
+    """The walk of k_sim3_prepare (s3::walk_pairs): kept counts 255 / 256 / 257 around the 256 threads of k_sim3_prepare,
+    and one candidate in which every clause of s3::keep_pair skips a pair.  N, indices1 and corr equal the restatement's."""
+    seed, n_corr, kw = R.SEAM_PROBLEM
+    p = SP.make_problem(seed, n_corr, **kw)
+    tab = R.full_table(p)
+    assert [t["N"] for t in tab] == [255, 256, 257]
+    rc, got, _ = _run_dev(p)
+    assert rc == 0
+    _check_walk(got, tab)
+    p, ref, N = R.skip_clause_problem()
+    tab = R.full_table(ref)
+    assert tab[0]["N"] == N
+    rc, got, _ = _run_dev(p)
+    assert rc == 0
+    _check_walk(got, tab)
+    _check(ref, got, tab)
+
+
 def test_other_ransac_parameters_follow_set_ransac_parameters():
     """mRansacMaxIts for min_inliers = 100 and a cap of 150 (N at, just above and far above min_inliers), and p = 0.9."""
     for prob, mi, cap in ((0.99, 100, 150), (0.9, 40, 300)):
