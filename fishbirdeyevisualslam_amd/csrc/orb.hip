@@ -96,6 +96,7 @@ struct fb_orb {
   const uint8_t *lastImg = nullptr;
   long long lastImgStride = 0;
   int lastPitch0 = 0;
+  int lastRoute[FB_MAX_LEVELS] = {};  // the resize kernel that built level l >= 1: 0 k_resize, 1 k_resize_rows, 2 k_resize_merge
   fb::DevBuf ownedImg;
 };
 
@@ -122,6 +123,7 @@ void launch_resize(fb_orb *o, int l, const OrbCall &c) {
   auto grid = [&](int rowsPerThread) { return dim3((D.pitch / 4 + 63) / 64, (D.h + 4 * rowsPerThread - 1) / (4 * rowsPerThread), c.batch); };
   fb::ProfScope prof_(fb::P_RESIZE, c.s);
   const bool rows = ws.rowsOK[l] && spitch >= 12 && ((reinterpret_cast<uintptr_t>(src) | (uintptr_t)spitch | (uintptr_t)sstr) & 3) == 0;
+  o->lastRoute[l] = rows ? (ws.mergeOK[l] ? 2 : 1) : 0;  // fb_orb_debug_resize_route
   if (rows && ws.mergeOK[l])
     k_resize_merge<<<grid(RM_ROWS), blk, 0, c.s>>>(src, sstr, S.w, S.h, spitch, dst, K.pyrStride, D.w, D.h, D.pitch, ws.rt[l]);
   else if (rows)
@@ -460,6 +462,11 @@ int fb_orb_debug_candidates(fb_orb *o, int b, int level, uint32_t *dst, int cap)
   if (dst && m > 0)
     FB_HIP(hipMemcpy(dst, o->ws.cand.as<uint32_t>() + (size_t)b * o->ws.K.candStride + L.candBase, (size_t)m * 4, hipMemcpyDeviceToHost));
   return n;
+}
+
+int fb_orb_debug_resize_route(fb_orb *o, int level) {
+  FB_ARG(o && o->lastImg && level >= 1 && level < o->p.nlevels);
+  return o->lastRoute[level];
 }
 
 int fb_orb_get_level(fb_orb *o, int b, int level, uint8_t *dst, int *w, int *hgt) {

@@ -147,6 +147,10 @@ int fb_orb_get_blurred_level(fb_orb *h, int b, int level, uint8_t *dst);
  * DistributeOctTree (vToDistributeKeys, ORBextractor.cc:822-824), packed
  * x | y<<12 | response<<24 in level coordinates, unordered.  Returns the count (>=0). */
 int fb_orb_debug_candidates(fb_orb *h, int b, int level, uint32_t *dst, int cap);
+/* debug/parity: which resize kernel built pyramid level `level` (1 .. nlevels-1) in the last call: 0 = k_resize (any
+ * source), 1 = k_resize_rows, 2 = k_resize_merge (both need a source whose pointer, row stride and image stride are
+ * multiples of 4 and level sizes that keep their windows).  Host state only; a negative value is an error code. */
+int fb_orb_debug_resize_route(fb_orb *h, int level);
 /* profiling aid: with FB_FAST_DBG=20 one k_fast workgroup in 16 accumulates shader-clock cycles per phase
  * (0 address set-up + load issue, 1 tile wait, 2 sweep, 3/4/5 score/NMS/slot reservation at iniThFAST, 6/7/8 the same
  * at minThFAST, 9 cell decode, 10 whole wave, 11 number of timed waves); reading resets the counters.          */

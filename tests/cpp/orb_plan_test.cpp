@@ -157,6 +157,112 @@ static void known_answers() {
   CHECK(plan_orb(p, t2, 640, 480, 4096, Q) == FB_OK && Q.K.kpStride == 4096 && Q.K.capOut == 2064, "an output stride of 4096 gives kpStride %d", Q.K.kpStride);
 }
 
+// Which resize kernel may build each level >= 1 of the constructed image cases (tests/orb_image_cases.py), for an aligned
+// source: g = not rowsOK (k_resize), r = rowsOK without mergeOK (k_resize_rows), m = mergeOK (k_resize_merge).  The same
+// literals are held to the numpy restatement by tests/test_orb_image_cases.py, so orb_plan.h and the model answer to one list.
+struct RouteRow { int w, h; float scale; int nlevels; const char *routes; };
+static const RouteRow ROUTE_TABLE[] = {
+    {131, 77, 1.25f, 3, "mm"},
+    {131, 77, 1.26f, 3, "mm"},
+    {131, 77, 1.3f, 3, "rr"},
+    {131, 77, 2.0f, 3, "rr"},
+    {131, 77, 2.01f, 3, "rr"},
+    {131, 77, 2.5f, 3, "gg"},
+    {131, 77, 3.0f, 3, "gg"},
+    {131, 77, 4.0f, 2, "g"},
+    {128, 96, 1.3334f, 2, "m"},
+    {131, 77, 1.3f, 4, "rrr"},
+    {64, 51, 1.25f, 8, "mmmmmmm"},
+    {64, 45, 1.25f, 7, "mmmmmm"},
+    {64, 48, 1.25f, 7, "mmmmmm"},
+    {64, 56, 1.2f, 2, "m"},
+    {64, 57, 1.2f, 2, "m"},
+    {64, 59, 1.2f, 2, "m"},
+    {45, 188, 2.25f, 5, "gggr"},
+    {64, 67, 2.0f, 4, "rrr"},
+    {64, 69, 2.0f, 4, "rrr"},
+    {64, 46, 1.5f, 2, "r"},
+    {64, 48, 1.5f, 2, "r"},
+    {64, 49, 1.5f, 2, "r"},
+    {100, 80, 2.0f, 7, "rrgmmm"},
+    {100, 80, 2.0f, 8, "rrgmmmm"},
+    {48, 64, 1.2f, 2, "m"},
+    {49, 64, 1.2f, 2, "m"},
+    {45, 64, 1.2f, 2, "m"},
+    {47, 64, 1.2f, 2, "m"},
+    {48, 64, 1.5f, 2, "r"},
+    {49, 64, 1.5f, 2, "r"},
+    {45, 64, 1.5f, 2, "r"},
+    {46, 64, 1.5f, 2, "r"},
+    {49, 64, 2.5f, 2, "g"},
+    {52, 64, 2.5f, 2, "g"},
+    {45, 64, 2.5f, 2, "g"},
+    {47, 64, 2.5f, 2, "g"},
+    {45, 48, 1.2f, 3, "mm"},
+    {46, 48, 1.2f, 3, "mm"},
+    {47, 48, 1.2f, 3, "mm"},
+    {48, 48, 1.2f, 3, "mm"},
+    {49, 48, 1.2f, 3, "mm"},
+    {50, 48, 1.2f, 3, "mm"},
+    {51, 48, 1.2f, 3, "mm"},
+    {52, 48, 1.2f, 3, "mm"},
+    {56, 48, 1.2f, 3, "mm"},
+    {60, 48, 1.2f, 3, "mm"},
+    {64, 48, 1.2f, 3, "mm"},
+    {72, 48, 1.2f, 3, "mm"},
+    {76, 48, 1.2f, 3, "mm"},
+    {513, 45, 1.2f, 2, "m"},
+    {64, 48, 1.2f, 2, "m"},
+    {260, 45, 1.2f, 2, "m"},
+    {50, 47, 1.5f, 2, "r"},
+    {51, 46, 2.0f, 2, "r"},
+    {45, 45, 1.2f, 1, ""},
+    {46, 45, 1.2f, 1, ""},
+    {47, 45, 1.2f, 1, ""},
+    {48, 45, 1.2f, 1, ""},
+    {49, 45, 1.2f, 1, ""},
+    {50, 45, 1.2f, 1, ""},
+    {51, 45, 1.2f, 1, ""},
+    {52, 45, 1.2f, 1, ""},
+    {255, 45, 1.2f, 1, ""},
+    {256, 45, 1.2f, 1, ""},
+    {257, 45, 1.2f, 1, ""},
+    {258, 45, 1.2f, 1, ""},
+    {259, 45, 1.2f, 1, ""},
+    {260, 45, 1.2f, 1, ""},
+    {263, 45, 1.2f, 1, ""},
+    {264, 45, 1.2f, 1, ""},
+    {511, 45, 1.2f, 1, ""},
+    {512, 45, 1.2f, 1, ""},
+    {513, 45, 1.2f, 1, ""},
+    {48, 63, 1.2f, 1, ""},
+    {48, 64, 1.2f, 1, ""},
+    {48, 65, 1.2f, 1, ""},
+    {48, 66, 1.2f, 1, ""},
+    {48, 67, 1.2f, 1, ""},
+    {48, 70, 1.2f, 1, ""},
+    {48, 95, 1.2f, 1, ""},
+    {48, 96, 1.2f, 1, ""},
+    {48, 97, 1.2f, 1, ""},
+    {45, 45, 1.027f, 8, "mmmmmmm"},
+    {64, 52, 1.2f, 4, "mmm"},
+    {132, 77, 1.25f, 3, "mm"},
+    {132, 77, 2.0f, 3, "rr"},
+    {132, 77, 2.5f, 3, "gg"},
+};
+
+static void route_table() {
+  for (const RouteRow &r : ROUTE_TABLE) {
+    OrbPlan P;
+    if (run(params(300, r.scale, r.nlevels), r.w, r.h, P) != FB_OK) { CHECK(false, "%dx%d scale %.4f is refused", r.w, r.h, (double)r.scale); continue; }
+    CHECK((int)strlen(r.routes) == r.nlevels - 1, "%dx%d scale %.4f: %zu routes for %d levels", r.w, r.h, (double)r.scale, strlen(r.routes), r.nlevels);
+    for (int l = 1; l < r.nlevels; l++) {
+      const char got = P.mergeOK[l] ? 'm' : P.rowsOK[l] ? 'r' : 'g';
+      CHECK(got == r.routes[l - 1], "%dx%d scale %.4f level %d (%dx%d): plan says %c, table %c", r.w, r.h, (double)r.scale, l, P.K.L[l].w, P.K.L[l].h, got, r.routes[l - 1]);
+    }
+  }
+}
+
 int main() {
   OrbPlan P;
   // the sizes and parameter sets of the GPU tests
@@ -186,6 +292,7 @@ int main() {
   check_refusal(params(60000, 1.2f, 1), 640, 480, FB_ERR_CAPACITY, "nfeatures too large for the LDS quadtree");
   check_refusal(params(3000, 1.759f, 1), 501, 431, FB_ERR_CAPACITY, "nfeatures too large for the LDS quadtree");
   known_answers();
+  route_table();
   std::printf("cases=%ld refused=%ld failures=%ld\n", g_cases, g_refused, g_failures);
   return g_failures ? 1 : 0;
 }

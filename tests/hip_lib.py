@@ -46,6 +46,44 @@ class Orb:
                  "fb_orb_get_level")
         return buf[: w.value * h.value].reshape(h.value, w.value).copy()
 
+    def level_size(self, level):
+        w, h = C.c_int(0), C.c_int(0)
+        fb.check(fb.lib().fb_orb_get_level(self.h, 0, level, None, C.byref(w), C.byref(h)), "fb_orb_get_level")
+        return w.value, h.value
+
+    def blurred_level(self, b, level):
+        w, h = self.level_size(level)
+        buf = np.zeros((h, w), np.uint8)
+        fb.check(fb.lib().fb_orb_get_blurred_level(self.h, b, level, C.c_void_p(buf.ctypes.data)), "fb_orb_get_blurred_level")
+        return buf
+
+    def resize_route(self, level):
+        """0 k_resize, 1 k_resize_rows, 2 k_resize_merge: the kernel that built `level` in the last call."""
+        r = fb.lib().fb_orb_debug_resize_route(self.h, level)
+        fb.check(min(r, 0), "fb_orb_debug_resize_route")
+        return r
+
+    def extract_batch_dev(self, buf, batch, w, h, stride, image_stride, offset=0):
+        """fb_orb_extract_batch_dev on a flat byte buffer: image b starts `offset + b * image_stride` bytes into it (the
+        device pointer handed over is the allocation's + offset).  Returns [(key points, descriptors)] per image; the
+        device copy of the buffer stays alive for level() / blurred_level()."""
+        import torch
+        dev = torch.device("cuda:0")
+        self._img = torch.from_numpy(np.ascontiguousarray(buf)).to(dev)
+        assert self._img.numel() >= offset + (batch - 1) * image_stride + stride * h
+        d_kps = torch.zeros(batch * self.cap * cabi.KP_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        d_desc = torch.zeros(batch * self.cap * 32, dtype=torch.uint8, device=dev)
+        d_n = torch.zeros(batch, dtype=torch.int32, device=dev)
+        fb.check(fb.lib().fb_orb_extract_batch_dev(self.h, C.c_void_p(self._img.data_ptr() + offset), batch, w, h, stride,
+                                                   C.c_size_t(image_stride), C.c_void_p(d_kps.data_ptr()),
+                                                   C.c_void_p(d_desc.data_ptr()), C.c_void_p(d_n.data_ptr()),
+                                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)), "fb_orb_extract_batch_dev")
+        torch.cuda.synchronize()
+        n = d_n.cpu().numpy()
+        kps = d_kps.cpu().numpy().view(cabi.KP_DTYPE).reshape(batch, self.cap)
+        desc = d_desc.cpu().numpy().reshape(batch, self.cap, 32)
+        return [(kps[b, : n[b]].copy(), desc[b, : n[b]].copy()) for b in range(batch)]
+
 
 def grid_build(kps, n, batch, stride, geom, cs, ci):
     """fb_grid_build_batch_dev through torch device buffers."""

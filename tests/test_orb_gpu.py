@@ -20,7 +20,7 @@ def _cands(orb, b, level, cap=400000):
     return np.stack([r & 0xFFF, (r >> 12) & 0xFFF, r >> 24], 1).astype(np.int32)
 
 
-def _check_image(params, img, stagewise=True):
+def _check_image(params, img, stagewise=True, blur_where_planned=False):
     orb = H.Orb(params)
     try:
         k_h, d_h = orb.extract(img)
@@ -29,11 +29,13 @@ def _check_image(params, img, stagewise=True):
                 lv_o = O.orb_level(params, img, l)
                 lv_h = orb.level(0, l, img.size)
                 np.testing.assert_array_equal(lv_h, lv_o, err_msg="pyramid level %d" % l)
-                bl_o = np.zeros_like(lv_o)
-                O.lib().orc_gaussian_blur7(C.c_void_p(lv_o.ctypes.data), lv_o.shape[1], lv_o.shape[0], C.c_void_p(bl_o.ctypes.data))
-                bl_h = np.zeros_like(lv_o)
-                fb.check(fb.lib().fb_orb_get_blurred_level(orb.h, 0, l, C.c_void_p(bl_h.ctypes.data)), "blurred level")
-                np.testing.assert_array_equal(bl_h, bl_o, err_msg="blurred level %d" % l)
+                # (the plan gives a level that cannot hold a key point no blur strips; the oracle blurs every level)
+                if not (blur_where_planned and min(lv_o.shape) < 38):
+                    bl_o = np.zeros_like(lv_o)
+                    O.lib().orc_gaussian_blur7(C.c_void_p(lv_o.ctypes.data), lv_o.shape[1], lv_o.shape[0], C.c_void_p(bl_o.ctypes.data))
+                    bl_h = np.zeros_like(lv_o)
+                    fb.check(fb.lib().fb_orb_get_blurred_level(orb.h, 0, l, C.c_void_p(bl_h.ctypes.data)), "blurred level")
+                    np.testing.assert_array_equal(bl_h, bl_o, err_msg="blurred level %d" % l)
                 c_o = O.orb_candidates(params, img, l)
                 c_h = _cands(orb, 0, l)
                 so = c_o[np.lexsort((c_o[:, 0], c_o[:, 1]))]
@@ -96,7 +98,7 @@ def test_extract_degenerate_pyramid_levels():
     """Levels too small to hold a key point (a few pixels wide) are still resized for the chain but never blurred or
     sampled; a level that rounds to 0 px is refused (cv::resize asserts on an empty Size in the reference too)."""
     img = synth.synth_image(5, 100, 80)
-    _check_image(O.orb_params(nfeatures=500, scale_factor=2.0, nlevels=7), img, stagewise=False)
+    _check_image(O.orb_params(nfeatures=500, scale_factor=2.0, nlevels=7), img, stagewise=True, blur_where_planned=True)
     orb = H.Orb(O.orb_params(nfeatures=500, scale_factor=2.2, nlevels=8))
     try:
         with pytest.raises(RuntimeError, match="is empty"):
