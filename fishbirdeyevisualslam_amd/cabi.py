@@ -64,6 +64,16 @@ class BirdGuidanceArgs(C.Structure):
                 ("edge_cap", _i32), ("n_edge_sign", _vp), ("n_edge_free", _vp), ("edge_sign", _vp), ("edge_free", _vp)]
 
 
+FB_SUBPIX_EXIT_EPS, FB_SUBPIX_EXIT_ITER, FB_SUBPIX_EXIT_DET, FB_SUBPIX_EXIT_OUT, FB_SUBPIX_REVERTED = 0, 1, 2, 3, 4
+
+
+class CornerSubpixArgs(C.Structure):
+    _fields_ = [("batch", _i32), ("kp_stride", _i32), ("cols", _i32), ("rows", _i32), ("pitch", _i32),
+                ("image_stride", C.c_size_t), ("image", _vp), ("n", _vp), ("kps", _vp),
+                ("half_win_x", _i32), ("half_win_y", _i32), ("max_iter", _i32), ("eps", C.c_double),
+                ("iters", _vp), ("exit_code", _vp)]
+
+
 class MatcherParams(C.Structure):
     _fields_ = [("nnratio", _f32), ("check_orientation", _i32)]
 
@@ -427,6 +437,7 @@ EXPORTS = [
     "fb_prof_enable", "fb_prof_only", "fb_prof_reset", "fb_prof_report",
     "fb_orb_create", "fb_orb_destroy", "fb_orb_get_tables", "fb_orb_capacity", "fb_orb_set_output_stride", "fb_orb_extract", "fb_orb_extract_batch_dev",
     "fb_orb_get_level", "fb_orb_get_blurred_level", "fb_orb_debug_candidates", "fb_orb_debug_resize_route", "fb_orb_debug_timers", "fb_grid_build_batch_dev", "fb_bird_keys_to_cam_dev", "fb_bird_guidance", "fb_bird_guidance_dev",
+    "fb_corner_subpix", "fb_corner_subpix_dev", "fb_frame_set_bird_subpix", "fb_frame_download_bird_grid",
     "fb_descriptor_distance_dev", "fb_descriptor_distance",
     "fb_match_projection_frame_dev", "fb_match_projection_frame",
     "fb_match_bird_mappoints_dev", "fb_match_bird_mappoints",

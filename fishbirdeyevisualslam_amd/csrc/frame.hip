@@ -5,12 +5,16 @@
 //   Frame::UndistortKeyPoints     src/Frame.cc:636-669 (cv::fisheye::undistortPoints, R = I, P = K)
 //   Frame::ComputeImageBounds     src/Frame.cc:741-795
 //   Frame::GuidenceKeyBirdPts     src/Frame.cc:671-684 with nearEdges :717-739 and genEdgesPC :686-715 (bird key point filter)
+//   cv::cornerSubPix              src/Frame.cc:345-352 on the bird key points (k_corner_subpix below; LDS plan: subpix_plan.h)
 //
-// Both kernels are one-lane-per-element streaming maps (28-44 B in, 1-21 B out per element): HBM-bound by
+// The frustum and undistort kernels are one-lane-per-element streaming maps (28-44 B in, 1-21 B out per element): HBM-bound by
 // construction, no LDS needed.  Per-problem constants (pose, camera centre) sit in SGPRs via uniform loads.
 #include "fb_common.h"
 #include "fb_frame_geom.h"
 #include "fb_primitives.h"
+#include "subpix_plan.h"
+
+#include <cmath>
 
 namespace {
 
@@ -270,6 +274,114 @@ __global__ __launch_bounds__(GUIDE_THREADS) void k_bird_edges(fb_bird_guidance_a
   if (tid == 0) { A.n_edge_sign[b] = ts; A.n_edge_free[b] = tf; }
 }
 
+// ---- cv::cornerSubPix on the bird key points (Frame.cc:345-352; the rules are restated at fb_corner_subpix_args) -----------
+// One wave per key point, SUBPIX_WAVES of them in a workgroup, no workgroup barrier: a wave whose point has ended leaves.
+// Every lane carries the same centre, so the loop is wave-uniform.  A round: the (2w+3) x (2h+3) patch, pixel p = lane,
+// lane + 64, ... (4 byte loads and 3-4 float operations each), goes to the wave's LDS slice; window term k = lane, lane + 64,
+// ... reads its four neighbours from there and adds its five fp64 products to the lane's partial sums in ascending k; five
+// butterfly sums (fb::wave_sum) give every lane the same totals, bit for bit, and every lane does the 2 x 2 solve.  The
+// separable weights come as two host-computed tables in the kernel arguments and are multiplied out into LDS once.
+struct SubpixK {
+  fb_corner_subpix_args A;
+  float wx[2 * SUBPIX_MAX_HALF + 1], wy[2 * SUBPIX_MAX_HALF + 1];
+  double eps2;
+};
+
+__device__ __forceinline__ void wave_lds_sync() {  // LDS written by the wave's lanes is visible to all of them
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__global__ __launch_bounds__(SUBPIX_THREADS) void k_corner_subpix(SubpixK K) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  const fb_corner_subpix_args &A = K.A;
+  const int b = blockIdx.y, wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int i = blockIdx.x * SUBPIX_WAVES + wv;
+  if (i >= min(max(A.n[b], 0), A.kp_stride)) return;
+  SubpixLds L;
+  subpix_layout(L, A.half_win_x, A.half_win_y);
+  float *patch = reinterpret_cast<float *>(smem + (size_t)wv * L.slice + L.patch);
+  float *weight = reinterpret_cast<float *>(smem + (size_t)wv * L.slice + L.weight);
+  const int pw = L.pw, ph = L.ph, ww = L.ww, wh = L.wh, cols = A.cols, rows = A.rows;
+  const uint8_t *img = A.image + (size_t)b * A.image_stride;
+  const size_t e = (size_t)b * A.kp_stride + i;
+  for (int k = lane; k < ww * wh; k += 64) {
+    const int r = k / ww, c = k - r * ww;
+    float vx = 0.f, vy = 0.f;
+#pragma unroll
+    for (int t = 0; t < 2 * SUBPIX_MAX_HALF + 1; t++) {  // the tables are kernel arguments: selected, not indexed
+      if (c == t) vx = K.wx[t];
+      if (r == t) vy = K.wy[t];
+    }
+    weight[k] = vy * vx;
+  }
+  const float tx = A.kps[e].x, ty = A.kps[e].y;
+  float cx = tx, cy = ty;
+  int iter = 0, code = FB_SUBPIX_EXIT_EPS;
+  double err = 0.0;
+  do {
+    // getRectSubPix: the patch's top-left corner, its floor and fraction
+    const float ox = cx - (float)(pw - 1) * 0.5f, oy = cy - (float)(ph - 1) * 0.5f;
+    const float fx = floorf(ox), fy = floorf(oy);
+    const float ax = ox - fx, ay = oy - fy;
+    // (a corner further out than this sees the replicated border only: the clamp keeps the integer sums below in range)
+    const int ipx = (int)fminf(fmaxf(fx, -1048576.f), 1048576.f), ipy = (int)fminf(fmaxf(fy, -1048576.f), 1048576.f);
+    const float a11 = (1.f - ax) * (1.f - ay), a12 = ax * (1.f - ay), a21 = (1.f - ax) * ay, a22 = ax * ay;
+    const float b1 = 1.f - ay, b2 = ay;
+    for (int p = lane; p < pw * ph; p += 64) {
+      const int r = p / pw, c = p - r * pw;
+      const int sx = ipx + c, sy = ipy + r;
+      const int x0 = min(max(sx, 0), cols - 1), x1 = min(max(sx + 1, 0), cols - 1);
+      const int y0 = min(max(sy, 0), rows - 1), y1 = min(max(sy + 1, 0), rows - 1);
+      const uint8_t *r0 = img + (size_t)y0 * A.pitch, *r1 = img + (size_t)y1 * A.pitch;
+      const float p00 = (float)r0[x0], p01 = (float)r0[x1], p10 = (float)r1[x0], p11 = (float)r1[x1];
+      patch[p] = (sx < 0 || sx >= cols - 1) ? p00 * b1 + p10 * b2 : p00 * a11 + p01 * a12 + p10 * a21 + p11 * a22;
+    }
+    wave_lds_sync();
+    double sa = 0.0, sb = 0.0, sc = 0.0, s1 = 0.0, s2 = 0.0;
+    for (int k = lane; k < ww * wh; k += 64) {
+      const int r = k / ww, c = k - r * ww;
+      const float *q = patch + (r + 1) * pw + (c + 1);
+      const double m = (double)weight[k];
+      const double tgx = (double)(q[1] - q[-1]), tgy = (double)(q[pw] - q[-pw]);
+      const double gxx = tgx * tgx * m, gxy = tgx * tgy * m, gyy = tgy * tgy * m;
+      const double px = (double)(c - A.half_win_x), py = (double)(r - A.half_win_y);
+      sa += gxx; sb += gxy; sc += gyy;
+      s1 += gxx * px + gxy * py;
+      s2 += gxy * px + gyy * py;
+    }
+    sa = fb::wave_sum(sa); sb = fb::wave_sum(sb); sc = fb::wave_sum(sc); s1 = fb::wave_sum(s1); s2 = fb::wave_sum(s2);
+    wave_lds_sync();  // every lane has read the patch before the next round overwrites it
+    const double det = sa * sc - sb * sb;
+    if (fabs(det) <= 2.220446049250313e-16 * 2.220446049250313e-16) { code = FB_SUBPIX_EXIT_DET; break; }
+    const double scale = 1.0 / det;
+    const float nx = (float)((double)cx + sc * scale * s1 - sb * scale * s2);
+    const float ny = (float)((double)cy - sb * scale * s1 + sa * scale * s2);
+    const float dx = nx - cx, dy = ny - cy;
+    err = (double)(dx * dx + dy * dy);
+    cx = nx; cy = ny;
+    if (cx < 0.f || cx >= (float)cols || cy < 0.f || cy >= (float)rows) { code = FB_SUBPIX_EXIT_OUT; break; }
+    if (++iter >= A.max_iter) { code = FB_SUBPIX_EXIT_ITER; break; }
+  } while (err > K.eps2);
+  if (fabsf(cx - tx) > (float)A.half_win_x || fabsf(cy - ty) > (float)A.half_win_y) { cx = tx; cy = ty; code |= FB_SUBPIX_REVERTED; }
+  if (lane == 0) {
+    A.kps[e].x = cx; A.kps[e].y = cy;
+    if (A.iters) A.iters[e] = iter;
+    if (A.exit_code) A.exit_code[e] = (uint8_t)code;
+  }
+}
+
+int subpix_check(const fb_corner_subpix_args *A, const char *what, SubpixLds *L, size_t *bytes) {
+  FB_ARG(A && A->batch >= 0 && A->batch <= 65535 && A->kp_stride >= 0 && A->cols > 0 && A->rows > 0 && A->pitch >= A->cols);
+  FB_TRY(plan_subpix(A->half_win_x, A->half_win_y, what, L, bytes));
+  FB_ARG(A->max_iter >= 1 && A->max_iter <= SUBPIX_MAX_ITERS && A->eps >= 0.0);
+  FB_ARG(A->batch <= 1 || A->image_stride >= (size_t)A->rows * A->pitch);
+  if (A->batch == 0 || A->kp_stride == 0) return FB_OK;
+  FB_ARG(A->image && A->n && A->kps);
+  return FB_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -333,6 +445,46 @@ int fb_bird_guidance(const fb_bird_guidance_args *H) {
   }
   FB_TRY(st.commit(nullptr));
   FB_TRY(fb_bird_guidance_dev(&D, nullptr));
+  return st.fetch(nullptr);
+}
+
+int fb_corner_subpix_dev(const fb_corner_subpix_args *A, void *stream) {
+  FB_TRY(fb::check_device());
+  SubpixLds L;
+  size_t lds = 0;
+  FB_TRY(subpix_check(A, "fb_corner_subpix", &L, &lds));
+  if (A->batch == 0 || A->kp_stride == 0) return FB_OK;
+  SubpixK K;
+  memset(&K, 0, sizeof(K));
+  K.A = *A;
+  // the separable weights exp(-x*x), x = (j - w) / w in float; std::exp(float) of OpenCV, taken through the double exp so that
+  // every host gives the same table
+  for (int j = 0; j < L.ww; j++) { const float x = (float)(j - A->half_win_x) / (float)A->half_win_x; K.wx[j] = (float)std::exp((double)(-x * x)); }
+  for (int i = 0; i < L.wh; i++) { const float y = (float)(i - A->half_win_y) / (float)A->half_win_y; K.wy[i] = (float)std::exp((double)(-y * y)); }
+  K.eps2 = A->eps * A->eps;
+  fb::ProfScope prof_(fb::P_BIRDCAM, fb::as_stream(stream));
+  const dim3 grid((A->kp_stride + SUBPIX_WAVES - 1) / SUBPIX_WAVES, A->batch);
+  k_corner_subpix<<<grid, SUBPIX_THREADS, lds, fb::as_stream(stream)>>>(K);
+  FB_HIP(hipGetLastError());
+  return FB_OK;
+}
+
+int fb_corner_subpix(const fb_corner_subpix_args *H) {
+  FB_TRY(fb::check_device());
+  SubpixLds L;
+  size_t lds = 0;
+  FB_TRY(subpix_check(H, "fb_corner_subpix", &L, &lds));
+  if (H->batch == 0 || H->kp_stride == 0) return FB_OK;
+  for (int b = 0; b < H->batch; b++) FB_ARG(H->n[b] >= 0 && H->n[b] <= H->kp_stride);
+  fb_corner_subpix_args D = *H;
+  const size_t B = H->batch, ks = H->kp_stride;
+  fb::Stager st;
+  st.in(D.image, (B - 1) * H->image_stride + (size_t)H->rows * H->pitch); st.in(D.n, B * 4);
+  // in/out: only x / y of the first n entries are written
+  st.out(D.kps, B * ks * sizeof(fb_keypoint), true);
+  st.out(D.iters, B * ks * 4, true); st.out(D.exit_code, B * ks, true);
+  FB_TRY(st.commit(nullptr));
+  FB_TRY(fb_corner_subpix_dev(&D, nullptr));
   return st.fetch(nullptr);
 }
 

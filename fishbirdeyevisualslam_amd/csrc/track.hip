@@ -55,6 +55,9 @@ struct fb_frame {
   void *m2_ws;
   bool bowDone = false;   // !mBowVec.empty() (in the order the calls were enqueued)
   int minInliers = 30;    // the threshold the last end-of-Track clean-up used (fb_frame_drop_outliers_dev follows it)
+  // cv::cornerSubPix on the bird key points (Frame.cc:345-352): half window 0 = not run (fb_frame_set_bird_subpix)
+  int subpixHalf = 0, subpixIters = 40;
+  double subpixEps = 0.001;
   // images from host callers
   fb::DevBuf img_f, img_b, img_c, img_m;
   uint8_t *pin = nullptr;
@@ -207,6 +210,14 @@ int fb_frame_extract_dev(fb_frame *f, fb_orb *of, fb_orb *ob, const uint8_t *d_f
       G.keep = f->pre.keep;  // [batch][cap]: the verdicts are computed by many workgroups
       FB_TRY(fb_bird_guidance_dev(&G, sb));
     }
+    if (f->subpixHalf > 0) {  // Frame.cc:345-352: mvKeysBird[k].pt refined before the camera positions and the grid
+      fb_corner_subpix_args S;
+      memset(&S, 0, sizeof(S));
+      S.batch = B; S.kp_stride = cap; S.cols = f->P.bird_width; S.rows = f->P.bird_height; S.pitch = bird_stride;
+      S.image_stride = bird_image_stride; S.image = d_bird; S.n = F.nb; S.kps = F.bkps;
+      S.half_win_x = S.half_win_y = f->subpixHalf; S.max_iter = f->subpixIters; S.eps = f->subpixEps;
+      FB_TRY(fb_corner_subpix_dev(&S, sb));
+    }
     FB_TRY(fb_bird_keys_to_cam_dev(F.bkps, F.nb, B, cap, f->P.bird_width, f->P.bird_height, f->P.pixel2meter, f->P.rear_axle_to_center,
                                    f->P.Tcb, F.bcam, sb));
     FB_TRY(fb_grid_build_batch_dev(F.bkps, F.nb, B, cap, &f->gB, f->bcs, f->bci, sb));
@@ -251,6 +262,24 @@ int fb_frame_extract(fb_frame *f, fb_orb *of, fb_orb *ob, const uint8_t *front, 
   if (mask) FB_HIP(hipMemcpyAsync(f->img_m.p, pm, B * bb, hipMemcpyHostToDevice, s));
   FB_HIP(hipEventRecord(f->evCopy, s));
   return fb_frame_extract_dev(f, of, ob, df, front_stride, fb_, db, bird_stride, bb, contour ? dc : nullptr, mask ? dm : nullptr, stream);
+}
+
+int fb_frame_set_bird_subpix(fb_frame *f, int32_t half_win, int32_t max_iter, double eps) {
+  FB_ARG(f && half_win >= 0 && half_win <= 8);
+  if (half_win > 0) FB_ARG(max_iter >= 1 && max_iter <= 100 && eps >= 0.0);  // what fb_corner_subpix_dev accepts
+  f->subpixHalf = half_win;
+  if (half_win > 0) { f->subpixIters = max_iter; f->subpixEps = eps; }
+  return FB_OK;
+}
+
+int fb_frame_download_bird_grid(fb_frame *f, int32_t *host_cell_start, int32_t *host_cell_items, void *stream) {
+  FB_TRY(fb::check_device());
+  FB_ARG(f && host_cell_start && host_cell_items);
+  hipStream_t s = fb::as_stream(stream);
+  FB_HIP(hipMemcpyAsync(host_cell_start, f->bcs, f->plan.r[FR_bcs].bytes, hipMemcpyDeviceToHost, s));
+  FB_HIP(hipMemcpyAsync(host_cell_items, f->bci, f->plan.r[FR_bci].bytes, hipMemcpyDeviceToHost, s));
+  FB_HIP(hipStreamSynchronize(s));
+  return FB_OK;
 }
 
 int fb_frame_set_pose_dev(fb_frame *f, const float *d_Tcw, void *stream) {

@@ -507,6 +507,21 @@ class Optimizer {
   }
 };
 
+// cv::cornerSubPix(image, corners, winSize, Size(-1,-1), {EPS + MAX_ITER, maxCount, epsilon}) on a u8 image (Frame.cc:345-352
+// calls it on mBirdviewImg with winSize (5,5), 40, 0.001): corners = [n][2] floats (cv::Point2f), refined in place.
+inline void cornerSubPix(const uint8_t *image, int cols, int rows, int step, float *corners, int n, int winW = 5, int winH = 5,
+                         int maxCount = 40, double epsilon = 0.001) {
+  std::vector<fb_keypoint> k((size_t)n);
+  for (int i = 0; i < n; i++) { k[i] = fb_keypoint{}; k[i].x = corners[2 * i]; k[i].y = corners[2 * i + 1]; }
+  const int32_t cnt = n;
+  fb_corner_subpix_args a{};
+  a.batch = 1; a.kp_stride = n; a.cols = cols; a.rows = rows; a.pitch = step; a.image_stride = (size_t)rows * step;
+  a.image = image; a.n = &cnt; a.kps = k.data();
+  a.half_win_x = winW; a.half_win_y = winH; a.max_iter = maxCount; a.eps = epsilon;
+  check(fb_corner_subpix(&a));
+  for (int i = 0; i < n; i++) { corners[2 * i] = k[i].x; corners[2 * i + 1] = k[i].y; }
+}
+
 // ---- the device-resident Frame and the per-frame chain ------------------------------------------------------------
 // DeviceFrame = the reference's Frame with its per-key-point members in HBM (fb_frame, include/fishbird.h); the methods
 // below carry the names of the reference functions they stand for and only ENQUEUE on `stream`.  TrackedFrame() is what
@@ -533,6 +548,8 @@ class DeviceFrame {
                  const uint8_t *contourICP, const uint8_t *mask, void *stream = nullptr) {
     check(fb_frame_extract(h_, front.handle(), bird.handle(), imGray, stride, birdGray, birdStride, contourICP, mask, stream));
   }
+  // cv::cornerSubPix on the bird key points inside every later Construct (Frame.cc:345-352); halfWin = 0: off (the default)
+  void SetBirdSubPix(int halfWin = 5, int maxCount = 40, double epsilon = 0.001) { check(fb_frame_set_bird_subpix(h_, halfWin, maxCount, epsilon)); }
   void SetPose(const float *d_Tcw, void *stream = nullptr) { check(fb_frame_set_pose_dev(h_, d_Tcw, stream)); }
 
   struct TrackResult {             // what Tracking reads after a frame (one synchronisation)

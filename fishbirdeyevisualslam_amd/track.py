@@ -177,6 +177,18 @@ class TrackChain:
         check(self.L.fb_frame_extract_dev(f, self.orb_f, self.orb_b, vp(front), self.fw, C.c_size_t(self.fw * self.fh), vp(bird), self.bw,
                                           C.c_size_t(self.bw * self.bh), vp(contour), vp(mask), self._stream()), "fb_frame_extract_dev")
 
+    def set_bird_subpix(self, half_win=5, max_iter=40, eps=0.001, frames=None):
+        """cv::cornerSubPix on the bird key points of every later extraction (Frame.cc:345-352); half_win = 0 switches it off."""
+        for f in (frames if frames is not None else self.frames):
+            check(self.L.fb_frame_set_bird_subpix(f, int(half_win), int(max_iter), C.c_double(eps)), "fb_frame_set_bird_subpix")
+
+    def bird_grid(self, which="cur"):
+        """mGridBirdview of a frame as host arrays (cell_start [B][1025], cell_items [B][cap])."""
+        cs, ci = np.zeros((self.B, 32 * 32 + 1), np.int32), np.zeros((self.B, self.cap), np.int32)
+        check(self.L.fb_frame_download_bird_grid(self._which(which), C.c_void_p(cs.ctypes.data), C.c_void_p(ci.ctypes.data), self._stream()),
+              "fb_frame_download_bird_grid")
+        return cs, ci
+
     def init_first(self, mp0, mpb0, Tcw0):
         """The current frame enters the chain as an already tracked frame (what initialisation leaves behind)."""
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)

@@ -215,6 +215,50 @@ typedef struct fb_bird_guidance_args {
 int fb_bird_guidance(const fb_bird_guidance_args *a);                    /* host pointers  */
 int fb_bird_guidance_dev(const fb_bird_guidance_args *a, void *stream);  /* device pointers */
 
+/* cv::cornerSubPix(mBirdviewImg, vKeysBird, Size(5,5), Size(-1,-1), {EPS+MAX_ITER, 40, 0.001}) (src/Frame.cc:345-352,
+ * between GuidenceKeyBirdPts and the bird compute step): OpenCV 3's imgproc/src/cornersubpix.cpp with no zero zone, on a
+ * u8 image, restated.  With w = half_win_x, h = half_win_y, per key point, start cT = (x, y), cI = cT, iter = 0:
+ *   do {
+ *     patch = getRectSubPix(image, (2w+3) x (2h+3), cI) as float (imgproc/src/samplers.cpp, 8u -> 32f): top-left corner
+ *             t = cI - (size-1)*0.5f, ip = floor(t), (a, b) = t - ip (float); pixel (r, c) of the patch, with the source
+ *             columns x0 = ip.x + c, x0 + 1 and rows y0 = ip.y + r, y0 + 1 each clamped into the image (replicate):
+ *               0 <= x0 < cols-1 :  ((p00*a11 + p01*a12) + p10*a21) + p11*a22,  a11 = (1-a)(1-b), a12 = a(1-b),
+ *                                                                               a21 = (1-a)b,     a22 = ab
+ *               otherwise        :  p00*(1-b) + p10*b         (the border path's two-coefficient columns)
+ *             float multiplies and adds in that order, none fused.
+ *     over the (2w+1) x (2h+1) window, (i, j) row / column, px = j - w, py = i - h, in double:
+ *       tgx = patch[i+1][j+2] - patch[i+1][j], tgy = patch[i+2][j+1] - patch[i][j+1]  (float differences)
+ *       m = weight[i][j] = float(exp(-y*y)) * float(exp(-x*x)) as a float product, x = (j-w)/w, y = (i-h)/h in float
+ *       gxx = tgx*tgx*m, gxy = tgx*tgy*m, gyy = tgy*tgy*m
+ *       a += gxx, b += gxy, c += gyy, bb1 += gxx*px + gxy*py, bb2 += gxy*px + gyy*py
+ *     det = a*c - b*b;  if (|det| <= DBL_EPSILON^2) break;                                     -- FB_SUBPIX_EXIT_DET
+ *     scale = 1/det;  cI2 = float(cI.x + c*scale*bb1 - b*scale*bb2, cI.y - b*scale*bb1 + a*scale*bb2)
+ *     err = (cI2.x-cI.x)^2 + (cI2.y-cI.y)^2 in float;  cI = cI2
+ *     if (cI.x < 0 || cI.x >= cols || cI.y < 0 || cI.y >= rows) break;                         -- FB_SUBPIX_EXIT_OUT
+ *   } while (++iter < max_iter                                                            -- else FB_SUBPIX_EXIT_ITER
+ *            && err > eps*eps);                                                           -- else FB_SUBPIX_EXIT_EPS
+ *   if (|cI.x - cT.x| > w || |cI.y - cT.y| > h) cI = cT;                                   -- | FB_SUBPIX_REVERTED
+ * x / y of kps[b][i], i < n[b], are replaced by cI; no other byte of kps is written.  iters = `iter` on leaving the loop
+ * (a round left by a break is not counted).  A point that left the image keeps its outside position unless the last rule
+ * reverts it; the position is then at most w / h beyond the border.  The window sums are taken over the 64 lanes of a
+ * wave, so they differ from a serial sum in the last bits; starts are expected to be finite. */
+enum { FB_SUBPIX_EXIT_EPS = 0, FB_SUBPIX_EXIT_ITER = 1, FB_SUBPIX_EXIT_DET = 2, FB_SUBPIX_EXIT_OUT = 3, FB_SUBPIX_REVERTED = 4 };
+typedef struct fb_corner_subpix_args {
+  int32_t batch, kp_stride;
+  int32_t cols, rows, pitch;            /* u8 image geometry; image b starts b * image_stride bytes after the base */
+  size_t image_stride;
+  const uint8_t *image;
+  const int32_t *n;                     /* [batch]                                                               */
+  fb_keypoint *kps;                     /* [batch][kp_stride]  x / y refined in place                            */
+  int32_t half_win_x, half_win_y;       /* 1..8 (5, 5 in the reference)                                          */
+  int32_t max_iter;                     /* 1..100 (40)                                                           */
+  double eps;                           /* >= 0 (0.001); squared inside                                          */
+  int32_t *iters;                       /* optional [batch][kp_stride]                                           */
+  uint8_t *exit_code;                   /* optional [batch][kp_stride]  FB_SUBPIX_EXIT_* | FB_SUBPIX_REVERTED    */
+} fb_corner_subpix_args;
+int fb_corner_subpix(const fb_corner_subpix_args *a);                    /* host pointers  */
+int fb_corner_subpix_dev(const fb_corner_subpix_args *a, void *stream);  /* device pointers */
+
 /* ======================================================================== */
 /* ORBmatcher (include/ORBmatcher.h:41-88, src/ORBmatcher.cc)                */
 /* ======================================================================== */
@@ -1624,6 +1668,14 @@ int fb_frame_extract_dev(fb_frame *f, fb_orb *front_extractor, fb_orb *bird_extr
 int fb_frame_extract(fb_frame *f, fb_orb *front_extractor, fb_orb *bird_extractor, const uint8_t *front, int front_stride,
                      const uint8_t *bird, int bird_stride, const uint8_t *contour, const uint8_t *mask, void *stream);
 
+/* cv::cornerSubPix on the bird key points inside fb_frame_extract[_dev] (Frame.cc:345-352): with half_win in 1..8 every
+ * later extraction runs fb_corner_subpix_dev(half_win, half_win, max_iter, eps) on the handle's bird stream after the
+ * guidance filter (straight after the extraction when there is no contour) and before mvKeysBirdCamXYZ and the bird grid,
+ * which are therefore built from the refined positions.  half_win = 0 switches it off again; off is the state of a new
+ * handle.  Descriptors stay those of the unrefined positions.  A refined point outside the image stays a key point and
+ * falls in no grid cell (PosInGridBirdview).                                                                             */
+int fb_frame_set_bird_subpix(fb_frame *f, int32_t half_win, int32_t max_iter, double eps);
+
 /* Frame::SetPose(Tcw) + UpdatePoseMatrices (Frame.cc:421-433): d_Tcw [batch][12] device.                                */
 int fb_frame_set_pose_dev(fb_frame *f, const float *d_Tcw, void *stream);
 /* mCurrentFrame.SetPose(detlaT * mLastFrame.mTcw) (Tracking.cc:1314-1320): d_delta [batch][12] = rows 0..2 of detlaT.   */
@@ -1773,6 +1825,9 @@ typedef struct fb_frame_view {
   int32_t *counts;                  /* [FB_CNT_COUNT][batch] (slot-major: every kernel writes one contiguous row)      */
 } fb_frame_view;
 int fb_frame_view_dev(fb_frame *f, fb_frame_view *out);
+/* mGridBirdview as the CSR fb_grid_build_batch_dev writes (32 x 32 cells) into host buffers [batch][1025] and
+ * [batch][kp_stride]; synchronises `stream`.                                                                              */
+int fb_frame_download_bird_grid(fb_frame *f, int32_t *host_cell_start, int32_t *host_cell_items, void *stream);
 int fb_frame_download(fb_frame *f, const fb_frame_view *host, void *stream); /* synchronises `stream`                  */
 int fb_frame_counts(fb_frame *f, int32_t *host_counts /* [FB_CNT_COUNT][batch] */, float *host_Tcw /* [batch][12] or NULL */,
                     void *stream);                                              /* synchronises `stream`                 */
