@@ -20,7 +20,7 @@
 //                   v_mfma_f64_16x16x4_f64; upper-triangular 16x16 tiles only, like g2o
 //   k_ba_sumparts_c the workgroup partials of the Schur complement summed in a fixed order
 //   k_ba_solve_c    S = Hpp + lambda I - sum S_part, dense LDL^T in LDS with look-ahead, backward substitution in one wave
-//                   (more than 23 free key frames: the reduced system lives in HBM, the kernels of ba_big.inc take these three places)
+//                   (more than MAX_FREE_KF_LDS free key frames: the reduced system lives in HBM, the kernels of ba_big.inc take these three places)
 //   k_ba_update_c   landmark back-substitution, exp-map pose update, trial state, scale term; the chi2 gate between the rounds
 //   k_ba_lin_c      the linearisation at the trial state in one launch of three roles: four lanes per landmark (residuals,
 //                   Huber weights, Hll, bl, the 6x3 blocks W_e, partial chi2), a quarter of a free key frame's edges per
@@ -29,13 +29,15 @@
 // This file holds the kernels; the host side of the translation unit is included at its end:
 //   ba_exchange.inc  RCCL / callback transport of the landmark-sharded BA, fb_rccl_*
 //   ba_big.inc       kernels and host pieces of the HBM-resident reduced system
-//   ba_graph.inc     layout of the staged graph, host builder, device builder (k_bld_*), odometry CSR, argument agreement
+//   ba_plan.h        constants, LDS layouts, the plan of a call, the layouts of its two device blocks (no HIP: swept on the CPU)
+//   ba_graph.inc     host builder, device builder (k_bld_*), odometry CSR, argument agreement
 //   ba_driver.inc    plan, device binding, the slot loop, result hand-over, local_ba_impl, the extern "C" entry points
 #include "fb_common.h"
 #include "fb_primitives.h"
 
 #include <thread>
 #include "fb_se3.h"
+#include "ba_plan.h"
 
 #include <algorithm>
 #include <chrono>
@@ -46,12 +48,8 @@ namespace {
 using fb::SE3;
 
 constexpr int T_PROJ = 0, T_XYZ = 1;
-constexpr int LIN_THREADS = 128;
 constexpr int POSE_THREADS = 256;
-constexpr int SCHUR_THREADS = 256;
-constexpr int CHUNK = 16;  // landmarks per MFMA panel (K = 48)
-constexpr int KP = 3 * CHUNK;
-constexpr int KPAD = KP + 2;  // LDS row stride in doubles (breaks the 2-way bank conflict of stride 48)
+// thread counts, panel widths, LDS layouts and the records shared with the host: ba_plan.h
 
 struct BADev {  // device pointers + sizes, passed by value
   int n_kf, np, npt, nE, nO, quat;
@@ -344,15 +342,14 @@ __device__ __forceinline__ void pose_body(const BADev &D, const State &S, int ro
 // residual and Jacobians into LDS; phase b: one lane per (free pose, row) adds the pose-pose blocks into HppO / bpO
 // in edge order (deterministic).
 // ------------------------------------------------------------------------------------------
-struct OdomLin { double A[36], Bm[36], err[6]; };
-constexpr int ODOM_DENSE_CLEAR_P6 = 138;  // 23 free key frames, the largest LDS-resident system (plan() in ba_driver.inc)
+constexpr int ODOM_DENSE_CLEAR_P6 = 6 * MAX_FREE_KF_LDS;  // the largest LDS-resident system (ba_plan.h)
 
 template <bool GLOBAL>  // GLOBAL: the per-edge linearisations live in HBM scratch (they do not fit LDS)
 __device__ __forceinline__ void odom_body(const BADev &D, const State &S, const LinBuf &B, int P6, int chiSlot, OdomLin *ol, double *s_chi,
                                           double *HppO, double *bpO, double *tmp) {
   const int tid = threadIdx.x;
   double chi = 0;
-  // tmp != nullptr (LDS, 108 doubles per edge: adj(T2) | adj(T1^-1) | J adj(T2)): the two 6x6x6 products of an edge are
+  // tmp != nullptr (LDS, ODOM_TMP_DOUBLES per edge: adj(T2) | adj(T1^-1) | J adj(T2)): the two 6x6x6 products of an edge are
   // spread over 36 lanes each instead of running serially on the edge's lane (same sums in the same order)
   for (int e = tid; e < D.nO; e += 256) {
     const SE3 T1 = S.pose[D.o_i[e]], T2 = S.pose[D.o_j[e]];
@@ -374,8 +371,8 @@ __device__ __forceinline__ void odom_body(const BADev &D, const State &S, const 
     fb::se3_adj(T2, a2);
     fb::se3_adj(fb::se3_inverse(T1), a1);
     if (tmp) {
-      double *q = tmp + (size_t)e * 108;
-      for (int i = 0; i < 36; i++) { q[i] = a2[i]; q[36 + i] = a1[i]; }
+      double *q = tmp + (size_t)e * ODOM_TMP_DOUBLES;
+      for (int i = 0; i < 36; i++) { q[ODOM_TMP_ADJ2 + i] = a2[i]; q[ODOM_TMP_ADJ1 + i] = a1[i]; }
     } else {
       for (int i = 0; i < 6; i++)
         for (int j = 0; j < 6; j++) {
@@ -399,17 +396,17 @@ __device__ __forceinline__ void odom_body(const BADev &D, const State &S, const 
     __syncthreads();
     for (int idx = tid; idx < D.nO * 36; idx += 256) {  // J adj(T2), J = -Bm
       const int e = idx / 36, ij = idx - e * 36, i = ij / 6, j = ij - i * 6;
-      const double *q = tmp + (size_t)e * 108;
+      const double *q = tmp + (size_t)e * ODOM_TMP_DOUBLES;
       double s2 = 0;
-      for (int k = 0; k < 6; k++) s2 += (-ol[e].Bm[i * 6 + k]) * q[k * 6 + j];
-      tmp[(size_t)e * 108 + 72 + ij] = s2;
+      for (int k = 0; k < 6; k++) s2 += (-ol[e].Bm[i * 6 + k]) * q[ODOM_TMP_ADJ2 + k * 6 + j];
+      tmp[(size_t)e * ODOM_TMP_DOUBLES + ODOM_TMP_JADJ2 + ij] = s2;
     }
     __syncthreads();
     for (int idx = tid; idx < D.nO * 36; idx += 256) {  // (J adj(T2)) adj(T1^-1)
       const int e = idx / 36, ij = idx - e * 36, i = ij / 6, j = ij - i * 6;
-      const double *q = tmp + (size_t)e * 108;
+      const double *q = tmp + (size_t)e * ODOM_TMP_DOUBLES;
       double s2 = 0;
-      for (int k = 0; k < 6; k++) s2 += q[72 + i * 6 + k] * q[36 + k * 6 + j];
+      for (int k = 0; k < 6; k++) s2 += q[ODOM_TMP_JADJ2 + i * 6 + k] * q[ODOM_TMP_ADJ1 + k * 6 + j];
       ol[e].A[ij] = s2;
     }
   }
@@ -500,8 +497,8 @@ template <int MAXT>  // accumulator tiles per wave (compile-time so the C tiles 
 __device__ __forceinline__ void schur_body(const BADev &D, const LinBuf &B, double lambda, double *Dinv, double *Spart,
                                            int P6, int NT, int lmPerWg, uint8_t *smem) {
   const int rows = NT * 16;
-  double *Yp = reinterpret_cast<double *>(smem);  // [rows][KPAD]
-  double *Wp = Yp + (size_t)rows * KPAD;           // [rows][KPAD]
+  const SchurLds lds = schur_lds(rows);
+  double *Yp = reinterpret_cast<double *>(smem) + lds.Yp, *Wp = reinterpret_cast<double *>(smem) + lds.Wp;  // [rows][KPAD] each
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int l0 = blockIdx.x * lmPerWg, l1 = min(l0 + lmPerWg, D.npt);
   // upper-triangular tiles, dealt round-robin to the 4 waves
@@ -635,17 +632,16 @@ __device__ __forceinline__ void solve_lookahead(const LinBuf &B, double lambda, 
                                                 uint8_t *smem, int &s_ok, const double *HppO) {
   const int ld = P6 + 1, rows = NT * 16, tid = threadIdx.x;
   BA_T0()
-  double *A = reinterpret_cast<double *>(smem);   // [P6 + 1][ld], lower triangle; row P6 = right-hand side
-  double *Up = A + (size_t)(P6 + 1) * ld;         // [P6 + 1][6] panel u = l * d of the current step
-  double *fact2 = Up + (size_t)(P6 + 1) * 6;      // two buffers (even / odd block) of 36 L (row-major, lower) | 6 d | 6 1/d
-  double *rhs = fact2 + 96;                       // [P6] backward substitution
+  const SolveLds lds = solve_lds(P6);  // A: lower triangle, row P6 = right-hand side; Up: panel u = l * d; fact2: 36 L | 6 d | 6 1/d, twice; rhs
+  double *A = reinterpret_cast<double *>(smem) + lds.A, *Up = reinterpret_cast<double *>(smem) + lds.Up;
+  double *fact2 = reinterpret_cast<double *>(smem) + lds.fact2, *rhs = reinterpret_cast<double *>(smem) + lds.rhs;
   if (tid == 0) s_ok = 1;
   {
     // A[i][j] = S[j][i] for i >= j (the upper triangle, as g2o's solver reads it): 16 lanes walk a row j of the upper
     // triangle (contiguous in memory), 16 row groups, four rows in flight per thread.  (The phase stamps had a quarter of the
     // solve in this loop when it divided a flat index and waited for each element's three loads in turn.)
     const int tr = tid >> 4, tc = tid & 15;
-    constexpr int MAXM = 9;  // ceil(138 / 16): the LDS-resident system has at most 23 free key frames
+    constexpr int MAXM = (6 * MAX_FREE_KF_LDS + 15) / 16;  // 16-wide segments of the longest row of an LDS-resident system
     for (int j = tr; j < P6; j += TS / 16) {
       const int jb = j / 6;
       const double *srow = Spart + (size_t)j * rows, *orow = HppO + (size_t)j * P6, *hrow = B.Hpp + (size_t)j * P6;
@@ -674,7 +670,7 @@ __device__ __forceinline__ void solve_lookahead(const LinBuf &B, double lambda, 
   // factor the 6x6 diagonal block at c0 (wave-redundant in registers), lane `wlane` 0 publishes it
   auto factor_block = [&](int c0) {
 #pragma clang fp contract(fast)
-    double *fact = fact2 + 48 * ((c0 / 6) & 1);  // wave 0 publishes block J + 1 while slower waves may still read block J's
+    double *fact = fact2 + SOLVE_FACT_DOUBLES * ((c0 / 6) & 1);  // wave 0 publishes block J + 1 while slower waves may still read block J's
     // the dependent chain of this routine is the critical path of every block step: fused multiply-adds and the products
     // U[c][m] = L[c][m] d[m] kept next to L halve its length (the BA is tolerance-held)
     double Lb[6][6], Ub[6][6], d[6], dinv[6];
@@ -876,9 +872,9 @@ __device__ __forceinline__ void update_body(const BADev &D, const LinBuf &B, con
 // 256-thread workgroups: 64 consecutive elements x 4 quarters of the partials (a wave = one quarter, so its loads are
 // contiguous); the quarters meet in LDS in a fixed order.  One thread per element over all nWg partials kept only 64
 // workgroups busy on 19 MB.
-constexpr int SUMPARTS_ELEMS = 64;
 __device__ __forceinline__ void sumparts_body(double *Spart, int nWg, int n, int rows) {
   __shared__ double s_q[3][SUMPARTS_ELEMS];
+  static_assert(sizeof(s_q) == STATIC_SUMPARTS, "ba_plan.h states this kernel's static LDS");
   const int lane = threadIdx.x & 63, q = threadIdx.x >> 6;
   const int i = blockIdx.x * SUMPARTS_ELEMS + lane;
   bool live = i < n;
@@ -938,33 +934,10 @@ __device__ __forceinline__ void gate_edge(const BADev &D, const State &S, int se
 // host enqueues identical "slots" of kernels without reading anything back; every kernel of a slot looks at BACtl and
 // does nothing once the schedule has finished.  A slot is either the linearisation that opens an optimize() (needInit:
 // chi2_0, lambda_0 = 1e-5 max diag) or one LM trial: Schur + solve at (cur, lambda) -> trial state -> its linearisation ->
-// k_ba_control decides.  pbStopFlag: the host writes `abort` from a side stream while it waits.
-struct BACtl {
-  double lambda, ni, currentChi, iniChi;
-  int phase;     // 0 = first optimize(), 1 = second optimize() (after the chi2 gate), 2 = finished
-  int it, qmax, nBad;
-  int cur;       // index of the accepted state and of its linearisation
-  int needInit;  // this slot linearises the accepted state instead of running a trial
-  int needGate;  // this slot starts with the chi2 gate
-  int abort;     // terminate(): set by the host when it sees *pbStopFlag
-  int trials, slots;
-  int badArgs;   // device-side graph builder (fb_local_ba_dev): 1 = index out of range, 2 = duplicate (key frame, point)
-  double trChi, trScale, trRho;  // FB_BA_TRACE: tempChi, scale and rho of the last trial (after an opening linearisation: chi2_0, max diagonal, 0)
-};
-struct BASched { int its1, robust1, gate, its2; };
+// k_ba_control decides.  pbStopFlag: the host writes `abort` from a side stream while it waits.  (BACtl, BASched and the
+// exchange block XBLay are in ba_plan.h.)
 struct St2 { State s[2]; };
 struct Lb2 { LinBuf b[2]; };
-// The per-linearisation "exchange block" (one per buffer t, `stride` doubles apart): everything a rank contributes to the
-// pose system of a linearisation, contiguous so that the sharded BA sums it over the ranks with ONE all-reduce:
-//   [0, oH) key-frame parts (np x POSE_PARTS x 27) | [oH, oB) HppO (P6 x P6) | [oB, oS) bpO (P6) |
-//   [oS, oM) chi2, scale term, abort request, spare | [oM, stride) max |diag Hll| of each rank (own slot, others 0)
-struct XBLay {
-  double *base;
-  int stride, oH, oB, oS, oM;
-  __host__ __device__ double *at(int t) const { return base + (size_t)t * stride; }
-};
-
-
 template <int MAXT>
 __global__ __launch_bounds__(SCHUR_THREADS) void k_ba_schur_c(BADev D, Lb2 lb, const BACtl *c, double *Dinv, double *Spart, int P6, int NT, int lmPerWg) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -975,17 +948,18 @@ __global__ void k_ba_sumparts_c(const BACtl *c, double *Spart, int nWg, int n, i
   if (c->phase == 2 || c->needInit) return;
   sumparts_body(Spart, nWg, n, rows);
 }
-constexpr int SOLVE_C_THREADS = 512;  // wave 0 factors the next diagonal block, seven waves share the trailing update
 __global__ __launch_bounds__(SOLVE_C_THREADS) void k_ba_solve_c(Lb2 lb, const BACtl *c, const double *Spart, int P6, int NT, double *xp, double *okFlag,
                                                                 XBLay xb) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   __shared__ int s_ok;
+  static_assert(sizeof(s_ok) == STATIC_SOLVE, "ba_plan.h states this kernel's static LDS");
   if (c->phase == 2 || c->needInit) return;
   solve_lookahead<SOLVE_C_THREADS>(lb.b[c->cur], c->lambda, Spart, P6, NT, xp, okFlag, smem, s_ok, xb.at(c->cur) + xb.oH);
 }
 __global__ __launch_bounds__(LIN_THREADS) void k_ba_update_c(BADev D, Lb2 lb, St2 st, const BACtl *c, const double *Dinv, const double *xp, double *scalePart,
                                                              int countPoses) {
   __shared__ double s_part[LIN_THREADS / 64];
+  static_assert(sizeof(s_part) == STATIC_UPDATE, "ba_plan.h states this kernel's static LDS");
   if (c->phase == 2) return;
   if (c->needInit) {
     if (c->needGate)  // edges beyond chi2 5.991 (or behind the camera) go to level 1 (Optimizer.cc:1059-1073 / 2534-2565)
@@ -994,7 +968,6 @@ __global__ __launch_bounds__(LIN_THREADS) void k_ba_update_c(BADev D, Lb2 lb, St
   }
   update_body(D, lb.b[c->cur], st.s[c->cur], st.s[1 - c->cur], Dinv, xp, c->lambda, scalePart, countPoses, s_part);
 }
-constexpr int POSE_PARTS = 4;
 // The decision at the end of a slot (one workgroup): assemble the key frames' diagonal blocks and bp from the parts, sum the
 // chi2 / scale partials in index order (thread 0, from LDS), maximum of the diagonal (computeLambdaInit,
 // optimization_algorithm_levenberg.cpp:166-180), then the LM state machine.
@@ -1003,6 +976,7 @@ constexpr int POSE_PARTS = 4;
 __global__ __launch_bounds__(256) void k_ba_prex(BADev D, Lb2 lb, const BACtl *c, int nLin, int chiSlot, const double *scalePart, int nScale, XBLay xb,
                                                  const int *abortLocal, int rank, int world) {
   __shared__ double s_m[256];
+  static_assert(sizeof(s_m) == STATIC_PREX, "ba_plan.h states this kernel's static LDS");
   const int tid = threadIdx.x;
   const int init = c->needInit, t = init ? c->cur : 1 - c->cur;
   double *X = xb.at(t);
@@ -1146,6 +1120,7 @@ __global__ __launch_bounds__(256) void k_ba_control(BADev D, Lb2 lb, BACtl *c, B
                                                     const double *okFlag, int P6, XBLay xb, const int *abortLocal, int world) {
   __shared__ double s_m[256];
   __shared__ double s_chiP[512], s_scaleP[512];
+  static_assert(sizeof(s_m) + sizeof(s_chiP) + sizeof(s_scaleP) == STATIC_CONTROL, "ba_plan.h states this kernel's static LDS");
   control_body<SHARDED>(D, lb, c, sc, nLin, chiSlot, scalePart, nScale, okFlag, P6, xb, abortLocal, world, s_m, s_chiP, s_scaleP);
 }
 
@@ -1158,10 +1133,11 @@ __global__ __launch_bounds__(256) void k_ba_control(BADev D, Lb2 lb, BACtl *c, B
 // decision itself instead of a k_ba_control launch.  A device-scope release / acquire on this part writes back and invalidates
 // the XCD's L2 (buffer_wbl2 sc1 / buffer_inv sc1), once per workgroup: the linearisation went from 21 to 49 us.)
 template <bool GLOBAL>
-__global__ __launch_bounds__(256) void k_ba_lin_c(BADev D, St2 st, Lb2 lb, const BACtl *c, BASched sc, int P6, int nLin, int chiSlot, OdomLin *olGlobal,
+__global__ __launch_bounds__(LIN_C_THREADS) void k_ba_lin_c(BADev D, St2 st, Lb2 lb, const BACtl *c, BASched sc, int P6, int nLin, int chiSlot, OdomLin *olGlobal,
                                                   XBLay xb) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  __shared__ double s_buf[256];
+  __shared__ double s_buf[LIN_C_THREADS];
+  static_assert(sizeof(s_buf) == STATIC_LIN, "ba_plan.h states this kernel's static LDS");
   if (c->phase == 2) return;
   const int t = c->needInit ? c->cur : 1 - c->cur;
   const int robust = c->phase == 0 ? sc.robust1 : 0;
@@ -1173,7 +1149,7 @@ __global__ __launch_bounds__(256) void k_ba_lin_c(BADev D, St2 st, Lb2 lb, const
     pose_body(D, st.s[t], robust, reinterpret_cast<double(*)[27]>(s_buf), k, part, POSE_PARTS, xb.at(t) + (size_t)q * 27);
   } else {
     OdomLin *ol = GLOBAL ? olGlobal : reinterpret_cast<OdomLin *>(smem);
-    double *tmp = GLOBAL ? nullptr : reinterpret_cast<double *>(ol + max(D.nO, 1));  // the launch reserves 108 doubles per edge behind the records
+    double *tmp = GLOBAL ? nullptr : reinterpret_cast<double *>(ol + lin_lds_records(D.nO));  // LDS route: the records, then the products' scratch
     odom_body<GLOBAL>(D, st.s[t], lb.b[t], P6, chiSlot, ol, s_buf, xb.at(t) + xb.oH, xb.at(t) + xb.oB, tmp);
   }
 }

@@ -1,4 +1,4 @@
-// ba_big.inc -- the reduced pose system beyond the LDS-resident limit (more than 23 free key frames; included by ba.hip).
+// ba_big.inc -- the reduced pose system beyond the LDS-resident limit (more than MAX_FREE_KF_LDS free key frames; included by ba.hip).
 // The kernels first, the host side (pair lists, the Schur complement + solve part of a slot) at the end of the file.
 //
 // Same mathematics as k_ba_schur_c / k_ba_solve_c (BlockSolver::solve with the Schur complement, block_solver.hpp:354-486,
@@ -15,8 +15,7 @@
 //   k_big_solve          one workgroup: blocked forward / diagonal / backward substitution, vector in LDS; the triangular
 //                        solve inside a panel runs in one wave with shuffles
 
-constexpr int BIG_NB = 48;  // panel width (8 key frames)
-
+// (BIG_NB, the panel width, is in ba_plan.h: the plan sizes U by it.)
 __device__ __forceinline__ bool big_idle(const BACtl *c) { return c->phase == 2 || c->needInit; }  // no trial in this slot
 
 __global__ __launch_bounds__(256) void k_ba_dinv(BADev D, Lb2 lb, const BACtl *c, double *Dinv) {
@@ -130,6 +129,7 @@ __global__ __launch_bounds__(256) void k_big_panel(const BACtl *c, double *M, in
   __shared__ double Ld[BIG_NB][BIG_NB + 1];
   __shared__ double dd[BIG_NB];
   __shared__ int s_neg;
+  static_assert(sizeof(Ld) + sizeof(dd) + sizeof(s_neg) == STATIC_BIG_PANEL, "ba_plan.h states this kernel's static LDS");
   if (big_idle(c)) return;
   const int tid = threadIdx.x;
   if (tid == 0) s_neg = 0;
@@ -181,6 +181,7 @@ __global__ __launch_bounds__(256) void k_big_panel(const BACtl *c, double *M, in
 // trailing update of the lower triangle: tile (bi, bj), bj <= bi, of the rows >= k0 + kw
 __global__ __launch_bounds__(256) void k_big_update(const BACtl *c, double *M, int P6, int k0, int kw, const double *U) {
   __shared__ double Lt[BIG_NB][BIG_NB + 1], Ut[BIG_NB][BIG_NB + 1];
+  static_assert(sizeof(Lt) + sizeof(Ut) == STATIC_BIG_UPDATE, "ba_plan.h states this kernel's static LDS");
   if (big_idle(c)) return;
   const int t0 = k0 + kw;
   const int nb = (P6 - t0 + BIG_NB - 1) / BIG_NB;
@@ -213,6 +214,7 @@ __global__ __launch_bounds__(256) void k_big_solve(const BACtl *c, const double 
   if (big_idle(c)) return;
   double *y = reinterpret_cast<double *>(smem);   // [P6]
   __shared__ double Lp[BIG_NB][BIG_NB + 1];       // diagonal block of the current panel
+  static_assert(sizeof(Lp) == STATIC_BIG_SOLVE, "ba_plan.h states this kernel's static LDS");
   const int tid = threadIdx.x, lane = tid & 63;
   for (int i = tid; i < P6; i += 256) y[i] = rhs[i];
   const int nblk = (P6 + BIG_NB - 1) / BIG_NB;
@@ -274,17 +276,14 @@ __global__ __launch_bounds__(256) void k_big_solve(const BACtl *c, const double 
 // ---- host side of the HBM-resident path -----------------------------------------------------------------------------------
 namespace {
 struct BigSys {
-  fb::DevBuf S, M, U;  // S | r,  M | rhs,  the panel's L D
+  double *S = nullptr, *M = nullptr, *U = nullptr;  // S | r,  M | rhs,  the panel's L D: slots of the call's scratch block
   fb::DevBuf blkStart, blkPr, blkPc, entEr, entEc;
   BigLists lists{};
 };
 
 // (row key frame <= column key frame) -> the edge pairs of the landmarks both observe; counting sort by block.  Reads the
 // HOST copy of the staged graph.
-int big_prepare(BigSys &B, int np, int npt, int P6, const int *poseIdx, const int *e_kf, const int *lm_start, const int *lm_edges) {
-  FB_TRY(B.S.alloc((size_t)P6 * P6 * 8 + (size_t)P6 * 8));
-  FB_TRY(B.M.alloc((size_t)P6 * P6 * 8 + (size_t)P6 * 8));
-  FB_TRY(B.U.alloc((size_t)P6 * BIG_NB * 8));
+int big_prepare(BigSys &B, int np, int npt, const int *poseIdx, const int *e_kf, const int *lm_start, const int *lm_edges) {
   std::vector<int> cnt((size_t)np * np + 1, 0);
   auto for_pairs = [&](auto &&f) {
     for (int l = 0; l < npt; l++)
@@ -326,7 +325,7 @@ int big_prepare(BigSys &B, int np, int npt, int P6, const int *poseIdx, const in
 // reduced system S | r is summed over the ranks on the stream (exchange 1).
 int big_slot_solve(const BigSys &B, const BADev &D, const Lb2 &lb, const BACtl *ctl, const XBLay &xr, int P6, double *Dinv, double *xp, double *okFlag,
                    const Xchg &X, std::vector<double> &hostScratch, hipStream_t s0) {
-  double *S = B.S.as<double>(), *rS = S + (size_t)P6 * P6, *M = B.M.as<double>(), *rhs = M + (size_t)P6 * P6;
+  double *S = B.S, *rS = S + (size_t)P6 * P6, *M = B.M, *rhs = M + (size_t)P6 * P6;
   const size_t nS = (size_t)P6 * P6 + P6;
   { fb::ProfScope pr(fb::P_BA_SCHUR, s0);
     FB_HIP(hipMemsetAsync(S, 0, nS * 8, s0));  // blocks without a shared landmark stay 0
@@ -338,9 +337,9 @@ int big_slot_solve(const BigSys &B, const BADev &D, const Lb2 &lb, const BACtl *
   k_big_assemble<<<(unsigned)(((long long)P6 * P6 + 255) / 256), 256, 0, s0>>>(lb, ctl, xr, S, rS, M, rhs, P6, okFlag);
   for (int k0 = 0; k0 < P6; k0 += BIG_NB) {
     const int kw = std::min(BIG_NB, P6 - k0);
-    k_big_panel<<<1, 256, 0, s0>>>(ctl, M, P6, k0, kw, B.U.as<double>(), okFlag);
+    k_big_panel<<<1, 256, 0, s0>>>(ctl, M, P6, k0, kw, B.U, okFlag);
     const int nbt = (P6 - k0 - kw + BIG_NB - 1) / BIG_NB;
-    if (nbt > 0) k_big_update<<<nbt * (nbt + 1) / 2, 256, 0, s0>>>(ctl, M, P6, k0, kw, B.U.as<double>());
+    if (nbt > 0) k_big_update<<<nbt * (nbt + 1) / 2, 256, 0, s0>>>(ctl, M, P6, k0, kw, B.U);
   }
   k_big_solve<<<1, 256, (size_t)P6 * 8, s0>>>(ctl, M, rhs, P6, xp);
   return FB_OK;

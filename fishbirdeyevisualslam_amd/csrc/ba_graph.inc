@@ -1,70 +1,16 @@
-// ba_graph.inc -- the staged graph of a bundle adjustment (included by ba.hip): what the kernels read, where it lies in the
-// one block that travels to the device (GraphLayout), the argument agreement, and the builders that fill the block: header,
+// ba_graph.inc -- the staged graph of a bundle adjustment (included by ba.hip): the argument agreement and the builders that
+// fill the one block that travels to the device (GraphLayout in ba_plan.h): header,
 // host builder (fb_local_ba & co.), k_bld_* + device builder (fb_local_ba_dev), odometry edges and their CSR.
 namespace {
 
-template <typename T> struct Slot {  // an array of T at a byte offset of some block
-  size_t off = 0;
-  T *at(void *base) const { return reinterpret_cast<T *>(static_cast<uint8_t *>(base) + off); }
-};
-struct Carver {  // hands out consecutive 256-byte-aligned slots
-  size_t bytes = 0;
-  template <typename T> Slot<T> take(size_t count) {
-    Slot<T> s;
-    s.off = bytes;
-    bytes += (count * sizeof(T) + 255) & ~(size_t)255;
-    return s;
-  }
-};
-
-struct BADims {  // the sizes of the graph, from the arguments alone
-  bool odom;
-  int n_kf, n_mp, npt;  // npt = n_mp + n_mpb: bird points keep their slots even when unused
-  int nF, nB, nE, nO;   // front / bird observations, both, odometry edges (sharded: they live on rank 0)
-  int np;               // free key frames
-};
 BADims dims_of(const fb_local_ba_args *A, int rank) {
   BADims d;
   d.odom = A->with_odom != 0;
   d.n_kf = A->n_kf; d.n_mp = A->n_mp; d.npt = A->n_mp + A->n_mpb;
-  d.nF = A->n_obs; d.nB = d.odom ? A->n_bobs : 0; d.nE = d.nF + d.nB; d.nO = (d.odom && rank == 0) ? A->n_odom : 0;
+  d.nF = A->n_obs; d.nB = d.odom ? A->n_bobs : 0; d.nE = d.nF + d.nB; d.nOAll = d.odom ? A->n_odom : 0; d.nO = rank == 0 ? d.nOAll : 0;
   d.np = 0;
   for (int k = 0; k < d.n_kf; k++) d.np += A->kf_fixed[k] ? 0 : 1;
   return d;
-}
-
-// Everything the kernels read is laid out in ONE staging block and goes to the device with one copy (two dozen small
-// synchronous copies were a quarter of a millisecond).  The small host-built arrays come first: the device-input variant
-// uploads only this header (the control block and the abort word ride in it: no separate synchronous copies).
-struct GraphLayout {
-  Slot<int> poseIdx;  // [n_kf] free index or -1
-  Slot<uint8_t> fixed;
-  Slot<int> o_i, o_j; Slot<SE3> o_Zinv; Slot<double> o_info; Slot<int> od_start, od_edges;
-  Slot<BACtl> ctl; Slot<int> abort;
-  size_t headerBytes;
-  Slot<int> lm_start, ps_start;  // ADJACENT, in this order: the device builder zeroes both with one memset up to e_pt
-  Slot<int> e_pt, e_kf, e_pj; Slot<uint8_t> e_type, e_level; Slot<float> e_meas; Slot<double> e_info; Slot<int> lm_edges, ps_edges;
-  Slot<SE3> poses; Slot<double> pts;
-  Slot<float> kfT;  // the caller's float poses (fixed key frames are returned untouched)
-  size_t bytes;
-};
-GraphLayout graph_layout(const BADims &d) {
-  const size_t nE1 = std::max(d.nE, 1), nO1 = std::max(d.nO, 1), npt1 = std::max(d.npt, 1);
-  GraphLayout G;
-  Carver c;
-  G.poseIdx = c.take<int>(d.n_kf); G.fixed = c.take<uint8_t>(d.n_kf);
-  G.o_i = c.take<int>(nO1); G.o_j = c.take<int>(nO1); G.o_Zinv = c.take<SE3>(nO1); G.o_info = c.take<double>(nO1);
-  G.od_start = c.take<int>(d.np + 1); G.od_edges = c.take<int>(2 * nO1);
-  G.ctl = c.take<BACtl>(1); G.abort = c.take<int>(4);
-  G.headerBytes = c.bytes;
-  G.lm_start = c.take<int>(d.npt + 1); G.ps_start = c.take<int>(d.np + 1);
-  G.e_pt = c.take<int>(nE1); G.e_kf = c.take<int>(nE1); G.e_pj = c.take<int>(nE1);
-  G.e_type = c.take<uint8_t>(nE1); G.e_level = c.take<uint8_t>(nE1);
-  G.e_meas = c.take<float>(3 * nE1); G.e_info = c.take<double>(nE1);
-  G.lm_edges = c.take<int>(nE1); G.ps_edges = c.take<int>(nE1);
-  G.poses = c.take<SE3>(d.n_kf); G.pts = c.take<double>(3 * npt1); G.kfT = c.take<float>((size_t)12 * d.n_kf);
-  G.bytes = c.bytes;
-  return G;
 }
 
 // ---- index predicates: the agreement block and the builder pass ask the same questions ------------------------------
@@ -92,7 +38,7 @@ int agree_on_arguments(const fb_local_ba_args *A, int rank, const Xchg &X) {
     const bool od = A->with_odom != 0;
     int free = 0;
     for (int k = 0; k < A->n_kf; k++) free += A->kf_fixed[k] ? 0 : 1;
-    if (6 * free > 4096) bad = 1;
+    if (6 * free > MAX_P6) bad = 1;
     std::vector<long long> pairs;
     pairs.reserve((size_t)A->n_obs + (od ? A->n_bobs : 0));
     for (int i = 0; i < A->n_obs && !bad; i++) {
@@ -293,6 +239,7 @@ __global__ void k_bld_state(BuildIn I, SE3 *poses, double *pts, float *kfT) {
 // in-place: cnt[0] = 0, cnt[i + 1] = count of bucket i  ->  exclusive starts; one workgroup, n up to millions
 __global__ __launch_bounds__(1024) void k_bld_scan(int *cnt, int n, int *fill) {
   __shared__ int s_w[16], s_run;
+  static_assert(sizeof(s_w) + sizeof(s_run) == STATIC_BLD_SCAN, "ba_plan.h states this kernel's static LDS");
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   if (tid == 0) s_run = 0;
   __syncthreads();

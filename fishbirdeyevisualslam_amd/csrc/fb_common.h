@@ -78,6 +78,7 @@ struct ProfScope {  // (the record list is mutex-protected and a scope closes it
 void *pool_take(size_t bytes, size_t *granted, bool exact = false);  // nullptr on failure (error set)
 void pool_give(void *p, size_t granted);
 void pool_release();  // frees every idle block (fb_shutdown)
+void ba_release_thread();  // ba.hip: the calling thread's per-device stream, event and pinned control block (fb_shutdown)
 
 struct DevBuf {
   void *p = nullptr;

@@ -184,6 +184,13 @@ int fb_prof_report(fb_prof_entry *out, int cap) {
   return n;
 }
 
+// the calling thread's per-device BA objects (stream, event, pinned control block), its staging block, every idle pool block
+int fb_shutdown(void) {
+  fb::ba_release_thread();
+  fb::pool_release();
+  return FB_OK;
+}
+
 int fb_abi_version(void) { return FB_ABI_VERSION; }
 
 const char *fb_last_error(void) { return fb::g_err; }

@@ -219,11 +219,12 @@ def free_count(f, seed=None):
     return p, dict(with_odom=1, front_flags={}, special=np.zeros(0, int))
 
 
-# plan() in ba_driver.inc: nWg = min(256, ceil(npt / 16)); lmPerWg = ceil(ceil(npt / nWg) / 16) * 16; nWg = ceil(npt / lmPerWg).
+# plan() in csrc/ba_plan.h: nWg = min(256, ceil(npt / 16)); lmPerWg = ceil(ceil(npt / nWg) / 16) * 16; nWg = ceil(npt / lmPerWg).
 # Up to 4096 points lmPerWg is 16 = CHUNK, so the last workgroup (= its only chunk) is partial whenever npt % 16 != 0:
 # 1, 15, 17, 33 and 100 (seven workgroups, the last with four landmarks); 16 is the exact fit.  FB_BA_NWG caps nWg: with 2 and
 # npt = 100, lmPerWg = 64 and the second workgroup holds [64, 100): two full chunks and a tail of four, the only way to a
-# workgroup with several chunks (the clear-after-MFMA traversal) at test size.
+# workgroup with several chunks (the clear-after-MFMA traversal) at test size.  (tests/cpp/ba_plan_test.cpp has this case as a
+# row of its sweep over the header: lmPerWg 64 and two workgroups under the cap, 16 and seven without.)
 POINT_COUNTS = (1, 15, 16, 17, 33, 100)
 NWG_CAP_FOR_CHUNKS = 2
 

@@ -314,6 +314,22 @@ def test_local_ba_plan_boundary_23_24_free_key_frames():
     _compare(p, out_o, out_h, 1)
 
 
+@pytest.mark.parametrize("n_odom", [103, 104])
+def test_local_ba_odometry_records_boundary_lds_hbm(n_odom):
+    """The plan's threshold for the odometry records (csrc/ba_plan.h, odom_home): up to 103 edges the records and the
+    products' scratch lie in LDS (k_ba_lin_c<false>), from 104 the records lie in the scratch block and an edge's products run
+    on its lane (k_ba_lin_c<true>).  23 free key frames, so both sides use the LDS-resident reduced system.  The generator
+    makes 3 n_kf - 6 edges (105 at 37 key frames): the chain is cut to the count."""
+    p = synth.make_ba_problem(4230, n_kf=37, n_fixed=14, n_mp=300, n_mpb=60)
+    assert int((p["kf_fixed"] == 0).sum()) == 23 and len(p["odom_kf_i"]) == 105
+    for k in ("odom_kf_i", "odom_kf_j", "odom_Tij", "odom_info"):
+        p[k] = np.ascontiguousarray(p[k][:n_odom])
+    a, _, keep = ba_problem.local_ba_args(p, with_odom=1)
+    assert a.n_odom == n_odom
+    out_o, out_h, _, _ = _run(p, with_odom=1)
+    _compare(p, out_o, out_h, 1)
+
+
 def test_triangulation_matches_feed_the_ba_on_the_device():
     """LocalMapping's hand-over without a host copy (LocalMapping.cc:231-476 -> :87-96): SearchForTriangulation (M7) runs on
     the device, its match array is turned into new points and observations by device code (torch ops standing in for the host's
