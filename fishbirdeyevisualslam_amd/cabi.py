@@ -74,6 +74,15 @@ class CornerSubpixArgs(C.Structure):
                 ("iters", _vp), ("exit_code", _vp)]
 
 
+class OrbDescribeArgs(C.Structure):
+    _fields_ = [("batch", _i32), ("kp_stride", _i32), ("n", _vp), ("kps", _vp), ("desc", _vp), ("status", _vp),
+                ("angle_mode", _i32), ("images", _vp), ("stride", _i32), ("image_stride", C.c_size_t)]
+
+
+FB_DESCRIBE_OK, FB_DESCRIBE_BORDER, FB_DESCRIBE_LEVEL = 0, 1, 2
+FB_DESCRIBE_KEEP_ANGLE, FB_DESCRIBE_IC_ANGLE = 0, 1
+
+
 class MatcherParams(C.Structure):
     _fields_ = [("nnratio", _f32), ("check_orientation", _i32)]
 
@@ -438,6 +447,7 @@ EXPORTS = [
     "fb_orb_create", "fb_orb_destroy", "fb_orb_get_tables", "fb_orb_capacity", "fb_orb_set_output_stride", "fb_orb_extract", "fb_orb_extract_batch_dev",
     "fb_orb_get_level", "fb_orb_get_blurred_level", "fb_orb_debug_candidates", "fb_orb_debug_resize_route", "fb_orb_debug_timers", "fb_grid_build_batch_dev", "fb_bird_keys_to_cam_dev", "fb_bird_guidance", "fb_bird_guidance_dev",
     "fb_corner_subpix", "fb_corner_subpix_dev", "fb_frame_set_bird_subpix", "fb_frame_download_bird_grid",
+    "fb_orb_describe", "fb_orb_describe_dev", "fb_frame_set_bird_redescribe", "fb_frame_download_bird_describe_status",
     "fb_descriptor_distance_dev", "fb_descriptor_distance",
     "fb_match_projection_frame_dev", "fb_match_projection_frame",
     "fb_match_bird_mappoints_dev", "fb_match_bird_mappoints",

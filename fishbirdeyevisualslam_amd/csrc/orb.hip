@@ -10,6 +10,8 @@
 //   IC_Angle / computeOrbDescriptor   :77-147      -> k_describe (one wave per two key points: raw and
 //        blurred patches staged in LDS -> moments, 256 rBRIEF tests)
 //   ORBextractor::operator()          :1043-1105   -> fb_orb_extract*
+//   computeDescriptors on a caller's key points (cv::ORB::compute)   -> k_describe_at (one wave per key point, the level
+//        from its record) -> fb_orb_describe*
 //
 // HBM layout per image: level 0 is the caller's image (never copied); levels 1..n-1 live in
 // one pitched buffer (pitch % 64 == 0), the blurred levels in a second one of the same geometry.
@@ -25,6 +27,7 @@
 #include "fb_primitives.h"
 
 #include "orb_plan.h"
+#include "orb_describe_at_plan.h"
 
 namespace {
 
@@ -57,6 +60,7 @@ __constant__ PackedPattern c_pattern = pack_pattern();
 #include "orb_fast.inc"
 #include "orb_octree.inc"
 #include "orb_describe.inc"
+#include "orb_describe_at.inc"
 
 // ------------------------------------------------------------------------------------------
 // host side
@@ -92,7 +96,8 @@ struct fb_orb {
   }
   int kpStride = 0;  // fb_orb_set_output_stride (0 = the capacity)
   Workspace ws;
-  // last call (for fb_orb_get_level)
+  // last call (for fb_orb_get_level and fb_orb_describe)
+  int lastBatch = 0;
   const uint8_t *lastImg = nullptr;
   long long lastImgStride = 0;
   int lastPitch0 = 0;
@@ -310,7 +315,15 @@ int prepare(fb_orb *o, int w, int h, int batch) {
   FB_TRY(allow_octree_lds<256>());
   ws.w = w; ws.h = h; ws.batchCap = batch;
   o->ws = std::move(ws);  // the commit: moves of plain data and of buffer ownership, nothing that can fail
+  o->lastBatch = 0;       // the new buffers hold no pyramid yet (fb_orb_describe)
   return FB_OK;
+}
+
+
+// fb_orb_describe[_dev]: the argument checks of orb_describe_at_plan.h against the handle's last extract call
+int describe_check(const fb_orb *o, const fb_orb_describe_args *A, size_t *lds) {
+  FB_ARG(o);
+  return check_describe_at(A, o->lastBatch, o->ws.w, o->ws.h, "fb_orb_describe", lds);
 }
 
 }  // namespace
@@ -371,6 +384,7 @@ int fb_orb_extract_batch_dev(fb_orb *o, const uint8_t *d_images, int batch, int 
   FB_TRY(blur.join_before_describe(c.s));
   launch_describe(o, c, d_keypoints, d_descriptors, d_n);
   FB_HIP(hipGetLastError());
+  o->lastBatch = batch;
   o->lastImg = d_images;
   o->lastImgStride = (long long)image_stride;
   o->lastPitch0 = stride;
@@ -427,6 +441,53 @@ int fb_orb_extract(fb_orb *o, const uint8_t *image, int width, int height, int s
   memcpy(keypoints, pout + oK, (size_t)*n_out * sizeof(fb_keypoint));
   memcpy(descriptors, pout + oD, (size_t)*n_out * 32);
   return FB_OK;
+}
+
+// ---- computeDescriptors at key points the caller supplies (the rules are restated at fb_orb_describe_args) ----------------
+int fb_orb_describe_dev(fb_orb *o, const fb_orb_describe_args *A, void *stream) {
+  FB_TRY(fb::check_device());
+  size_t lds = 0;
+  FB_TRY(describe_check(o, A, &lds));
+  if (A->batch == 0 || A->kp_stride == 0) return FB_OK;
+  FB_ARG(((uintptr_t)A->kps | (uintptr_t)A->desc | (uintptr_t)A->n) % 4 == 0);
+  const Workspace &ws = o->ws;
+  DescAtK K;
+  memset(&K, 0, sizeof(K));
+  K.nlevels = ws.K.nlevels; K.kp_stride = A->kp_stride; K.angle_mode = A->angle_mode;
+  K.pitch0 = A->stride; K.img_stride = (long long)A->image_stride; K.pyr_stride = ws.K.pyrStride; K.blur_stride = ws.K.blurStride;
+  K.n = A->n; K.kps = A->kps; K.desc = A->desc; K.status = A->status;
+  K.img0 = A->angle_mode == FB_DESCRIBE_IC_ANGLE ? A->images : nullptr;
+  K.pyr = ws.pyr.as<uint8_t>(); K.blur = ws.blur.as<uint8_t>(); K.ang_tab = ws.angTab.p;
+  for (int l = 0; l < K.nlevels; l++) {
+    const LevelInfo &L = ws.K.L[l];
+    K.L[l] = DescAtLevel{L.w, L.h, L.pitch, o->t.inv_scale_factor[l], L.off, L.boff};
+  }
+  hipStream_t s = fb::as_stream(stream);
+  fb::ProfScope prof_(fb::P_DESCRIBE_AT, s);
+  k_describe_at<<<dim3((A->kp_stride + DESCAT_WAVES - 1) / DESCAT_WAVES, A->batch), DESCAT_THREADS, lds, s>>>(K);
+  FB_HIP(hipGetLastError());
+  return FB_OK;
+}
+
+int fb_orb_describe(fb_orb *o, const fb_orb_describe_args *H) {
+  FB_TRY(fb::check_device());
+  size_t lds = 0;
+  FB_TRY(describe_check(o, H, &lds));
+  if (H->batch == 0 || H->kp_stride == 0) return FB_OK;
+  for (int b = 0; b < H->batch; b++) FB_ARG(H->n[b] >= 0 && H->n[b] <= H->kp_stride);
+  fb_orb_describe_args D = *H;
+  const DescAtStage z = describe_at_stage(*H, o->ws.h);
+  fb::Stager st;
+  if (z.images) st.in(D.images, z.images);
+  else D.images = nullptr;
+  st.in(D.n, z.n);
+  // in/out: only .angle of an accepted key point is written (IC mode), and only the rows of accepted key points
+  st.out(D.kps, z.kps, true);
+  st.out(D.desc, z.desc, true);
+  st.out(D.status, z.status, true);
+  FB_TRY(st.commit(nullptr));
+  FB_TRY(fb_orb_describe_dev(o, &D, nullptr));
+  return st.fetch(nullptr);
 }
 
 int fb_orb_debug_timers(fb_orb *o, uint64_t *dst16) {

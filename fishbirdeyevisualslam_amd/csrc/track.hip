@@ -58,6 +58,9 @@ struct fb_frame {
   // cv::cornerSubPix on the bird key points (Frame.cc:345-352): half window 0 = not run (fb_frame_set_bird_subpix)
   int subpixHalf = 0, subpixIters = 40;
   double subpixEps = 0.001;
+  // extractorBird->compute at the refined positions (Frame.cc:352-355, fb_frame_set_bird_redescribe): runs only with subpix on
+  bool redescribe = false, redescribed = false;  // the switch; the last extraction ran it
+  fb::DevBuf describeStatus;                     // [B][cap] FB_DESCRIBE_*, plan_redescribe_status(); allocated by the switch
   // images from host callers
   fb::DevBuf img_f, img_b, img_c, img_m;
   uint8_t *pin = nullptr;
@@ -217,7 +220,15 @@ int fb_frame_extract_dev(fb_frame *f, fb_orb *of, fb_orb *ob, const uint8_t *d_f
       S.image_stride = bird_image_stride; S.image = d_bird; S.n = F.nb; S.kps = F.bkps;
       S.half_win_x = S.half_win_y = f->subpixHalf; S.max_iter = f->subpixIters; S.eps = f->subpixEps;
       FB_TRY(fb_corner_subpix_dev(&S, sb));
+      if (f->redescribe) {  // Frame.cc:352-355: the descriptors of the refined positions, on the bird extractor's blurred pyramid
+        fb_orb_describe_args R;
+        memset(&R, 0, sizeof(R));
+        R.batch = B; R.kp_stride = cap; R.n = F.nb; R.kps = F.bkps; R.desc = F.bdesc; R.status = f->describeStatus.as<uint8_t>();
+        R.angle_mode = FB_DESCRIBE_KEEP_ANGLE;
+        FB_TRY(fb_orb_describe_dev(ob, &R, sb));
+      }
     }
+    f->redescribed = f->subpixHalf > 0 && f->redescribe;
     FB_TRY(fb_bird_keys_to_cam_dev(F.bkps, F.nb, B, cap, f->P.bird_width, f->P.bird_height, f->P.pixel2meter, f->P.rear_axle_to_center,
                                    f->P.Tcb, F.bcam, sb));
     FB_TRY(fb_grid_build_batch_dev(F.bkps, F.nb, B, cap, &f->gB, f->bcs, f->bci, sb));
@@ -269,6 +280,26 @@ int fb_frame_set_bird_subpix(fb_frame *f, int32_t half_win, int32_t max_iter, do
   if (half_win > 0) FB_ARG(max_iter >= 1 && max_iter <= 100 && eps >= 0.0);  // what fb_corner_subpix_dev accepts
   f->subpixHalf = half_win;
   if (half_win > 0) { f->subpixIters = max_iter; f->subpixEps = eps; }
+  return FB_OK;
+}
+
+int fb_frame_set_bird_redescribe(fb_frame *f, int32_t on) {
+  FB_ARG(f);
+  if (on && !f->describeStatus.p) {
+    FB_TRY(fb::check_device());
+    FB_TRY(f->describeStatus.alloc(plan_redescribe_status(f->P, f->cap), true));
+  }
+  f->redescribe = on != 0;
+  return FB_OK;
+}
+
+int fb_frame_download_bird_describe_status(fb_frame *f, uint8_t *host_status, void *stream) {
+  FB_TRY(fb::check_device());
+  FB_ARG(f && host_status);
+  if (!f->redescribed) { fb::set_error("fb_frame_download_bird_describe_status: the frame's last extraction did not re-describe"); return FB_ERR_ARG; }
+  hipStream_t s = fb::as_stream(stream);
+  FB_HIP(hipMemcpyAsync(host_status, f->describeStatus.p, plan_redescribe_status(f->P, f->cap), hipMemcpyDeviceToHost, s));
+  FB_HIP(hipStreamSynchronize(s));
   return FB_OK;
 }
 

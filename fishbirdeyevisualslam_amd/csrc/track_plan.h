@@ -6,6 +6,7 @@
 //            its join (SideStream, fb_frame_extract_dev) the caller's stream touches FRONT regions only and the handle's
 //            stream BIRD regions only.  Two regions are lent out under a second name; nothing else overlaps.
 // Every region starts on a 256-byte boundary (descriptor rows are read as uint4).
+// One optional block lies outside the arenas: plan_redescribe_status() at the end of this file.
 //
 // No HIP header and no handle: plan_frame() is plain host code (tests/cpp/track_plan_test.cpp compiles it with g++).  It
 // fills a local plan and assigns the caller's only on success.  Unnamed namespace: one translation unit at a time.
@@ -157,6 +158,11 @@ inline int plan_frame(const fb_frame_params &p, int cap_, FramePlan *out) {
   *out = P;
   return FB_OK;
 }
+
+// The status bytes of fb_frame_set_bird_redescribe (one per bird slot, written by k_describe_at on the handle's stream): not
+// a region of the scratch arena but a block of its own, allocated when the switch is first turned on -- like the BoW arena, a
+// handle that never asks for it holds none of it, and the region list above stays the list of what every handle holds.
+inline size_t plan_redescribe_status(const fb_frame_params &p, int cap) { return (size_t)p.batch * (size_t)cap; }
 
 }  // namespace
 

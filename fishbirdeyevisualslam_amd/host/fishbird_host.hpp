@@ -184,6 +184,23 @@ class ORBextractor {
     keypoints.resize(n);
     descriptors.resize((size_t)n * 32);
   }
+  // compute(image, keypoints, descriptors) of cv::ORB on key points the caller supplies (Frame.cc:352-355 after cornerSubPix):
+  // descriptors of `keys` on the pyramid of the LAST operator() call, keys[i].octave selecting the level.  The angles are
+  // kept as given (OpenCV 3); with icAngle they are recomputed on `image`, which must be the image of that call.  Nothing
+  // is erased: status[i] (FB_DESCRIBE_*) tells which rows were written (fb_orb_describe_args).
+  void compute(std::vector<fb_keypoint> &keys, std::vector<uint8_t> &descriptors, std::vector<uint8_t> *status = nullptr,
+               bool icAngle = false, const uint8_t *image = nullptr, int stride = 0) {
+    descriptors.resize(keys.size() * 32);
+    if (status) status->assign(keys.size(), FB_DESCRIBE_OK);
+    if (keys.empty()) return;
+    const int32_t n = (int32_t)keys.size();
+    fb_orb_describe_args a{};
+    a.batch = 1; a.kp_stride = n; a.n = &n; a.kps = keys.data(); a.desc = descriptors.data();
+    a.status = status ? status->data() : nullptr;
+    a.angle_mode = icAngle ? FB_DESCRIBE_IC_ANGLE : FB_DESCRIBE_KEEP_ANGLE;
+    a.images = image; a.stride = stride;
+    check(fb_orb_describe(h_, &a));
+  }
   int GetLevels() const { return p_.nlevels; }
   float GetScaleFactor() const { return p_.scale_factor; }
   std::vector<float> GetScaleFactors() const { return {t_.scale_factor, t_.scale_factor + p_.nlevels}; }
@@ -550,6 +567,8 @@ class DeviceFrame {
   }
   // cv::cornerSubPix on the bird key points inside every later Construct (Frame.cc:345-352); halfWin = 0: off (the default)
   void SetBirdSubPix(int halfWin = 5, int maxCount = 40, double epsilon = 0.001) { check(fb_frame_set_bird_subpix(h_, halfWin, maxCount, epsilon)); }
+  // extractorBird->compute at the refined positions (Frame.cc:352-355): runs inside Construct while SetBirdSubPix is on
+  void SetBirdRedescribe(bool on = true) { check(fb_frame_set_bird_redescribe(h_, on ? 1 : 0)); }
   void SetPose(const float *d_Tcw, void *stream = nullptr) { check(fb_frame_set_pose_dev(h_, d_Tcw, stream)); }
 
   struct TrackResult {             // what Tracking reads after a frame (one synchronisation)

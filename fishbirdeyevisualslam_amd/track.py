@@ -182,6 +182,18 @@ class TrackChain:
         for f in (frames if frames is not None else self.frames):
             check(self.L.fb_frame_set_bird_subpix(f, int(half_win), int(max_iter), C.c_double(eps)), "fb_frame_set_bird_subpix")
 
+    def set_bird_redescribe(self, on=True, frames=None):
+        """extractorBird->compute at the refined bird positions (Frame.cc:352-355); runs only while set_bird_subpix is on."""
+        for f in (frames if frames is not None else self.frames):
+            check(self.L.fb_frame_set_bird_redescribe(f, int(bool(on))), "fb_frame_set_bird_redescribe")
+
+    def bird_describe_status(self, which="cur"):
+        """FB_DESCRIBE_* of the bird key points of the last extraction that re-described, [B][cap] (meaningful below n_bird)."""
+        st = np.zeros((self.B, self.cap), np.uint8)
+        check(self.L.fb_frame_download_bird_describe_status(self._which(which), C.c_void_p(st.ctypes.data), self._stream()),
+              "fb_frame_download_bird_describe_status")
+        return st
+
     def bird_grid(self, which="cur"):
         """mGridBirdview of a frame as host arrays (cell_start [B][1025], cell_items [B][cap])."""
         cs, ci = np.zeros((self.B, 32 * 32 + 1), np.int32), np.zeros((self.B, self.cap), np.int32)

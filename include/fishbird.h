@@ -137,6 +137,46 @@ int fb_orb_extract_batch_dev(fb_orb *h, const uint8_t *d_images, int batch, int 
                              int stride, size_t image_stride, fb_keypoint *d_keypoints,
                              uint8_t *d_descriptors, int32_t *d_n, void *stream);
 
+/* ORB descriptors at key points the CALLER supplies: ORBextractor::computeDescriptors on a given list, cv::ORB::compute of
+ * OpenCV 3 (features2d/src/orb.cpp), restated.  Frame.cc:352-355 calls it on the bird key points after cv::cornerSubPix has
+ * moved them.  The call works on the pyramid and the blurred pyramid the handle holds from its LAST extract call (images
+ * b < batch of that call), and returns FB_ERR_ARG when nothing has been extracted yet, when `batch` exceeds that call's
+ * batch, or when FB_DESCRIBE_IC_ANGLE is asked for without `images`.  For key point i < min(n[b], kp_stride) of image b:
+ *   level     l = octave.  l < 0 or l >= nlevels: status FB_DESCRIBE_LEVEL, nothing of the key point is written.
+ *   position  px = cvRound(x * inv_scale_factor[l]), py = cvRound(y * inv_scale_factor[l]): the product in float, rounded
+ *             to nearest with halves to even (OpenCV 3: cvRound(kpt.pt.x * scale), scale = 1 / getScale(octave)).
+ *   border    unless 19 <= px <= w_l - 20 and 19 <= py <= h_l - 20 (EDGE_THRESHOLD: the range in which the extractor
+ *             itself places key points, so that neither patch leaves the level): status FB_DESCRIBE_BORDER, the descriptor
+ *             row and the angle stay as they were.  The test is made on the rounded float before it becomes an integer:
+ *             NaN and +-inf coordinates are FB_DESCRIBE_BORDER.
+ *   angle     FB_DESCRIBE_KEEP_ANGLE: kps[i].angle as given (degrees; OpenCV 3 does not re-orient supplied key points).
+ *             It is expected to be finite; a non-finite angle gives an unspecified descriptor and no out-of-range access.
+ *             FB_DESCRIBE_IC_ANGLE: IC_Angle (ORBextractor.cc:77-104, cv::fastAtan2) on the RAW level l at (px, py),
+ *             written to kps[i].angle.  Level 0 of the raw pyramid is the caller's image, which the handle never copies:
+ *             `images`, `stride` and `image_stride` are those of the extract call (any alignment).
+ *   desc      computeOrbDescriptor (ORBextractor.cc:107-147) on the BLURRED level l at (px, py) with that angle: 32 bytes,
+ *             status FB_DESCRIBE_OK.
+ * x, y, size, response, octave and every entry at or past n[b] are never written.
+ * There is NO compaction: cv::ORB::compute erases the key points too close to the border (KeyPointsFilter::runByImageBorder)
+ * and thereby shifts every index behind them; here the count and the indices stay -- arrays that run beside the key points
+ * (map points, grid cells) keep their meaning -- and the caller reads the status byte instead.
+ * kps, desc and n are 4-byte aligned (_dev).  One wave per key point: DESIGN.md section 4. */
+enum { FB_DESCRIBE_OK = 0, FB_DESCRIBE_BORDER = 1, FB_DESCRIBE_LEVEL = 2 };
+enum { FB_DESCRIBE_KEEP_ANGLE = 0, FB_DESCRIBE_IC_ANGLE = 1 };
+typedef struct fb_orb_describe_args {
+  int32_t batch, kp_stride;
+  const int32_t *n;                     /* [batch]                                                               */
+  fb_keypoint *kps;                     /* [batch][kp_stride]  only .angle is ever written, only in IC mode      */
+  uint8_t *desc;                        /* [batch][kp_stride][32]                                                */
+  uint8_t *status;                      /* optional [batch][kp_stride]  FB_DESCRIBE_*                            */
+  int32_t angle_mode;                   /* FB_DESCRIBE_KEEP_ANGLE / FB_DESCRIBE_IC_ANGLE                         */
+  const uint8_t *images;                /* the images of the extract call; needed for IC mode only               */
+  int32_t stride;                       /* their bytes per row                                                   */
+  size_t image_stride;                  /* image b starts b * image_stride bytes after `images`                  */
+} fb_orb_describe_args;
+int fb_orb_describe_dev(fb_orb *h, const fb_orb_describe_args *a, void *stream);  /* device pointers */
+int fb_orb_describe(fb_orb *h, const fb_orb_describe_args *a);                    /* host pointers   */
+
 /* debug/parity access to the pyramid level of image `b` of the last batch
  * (public member mvImagePyramid, ORBextractor.h:85). dst is host, w*h bytes.  */
 int fb_orb_get_level(fb_orb *h, int b, int level, uint8_t *dst, int *w, int *hgt);
@@ -1672,9 +1712,23 @@ int fb_frame_extract(fb_frame *f, fb_orb *front_extractor, fb_orb *bird_extracto
  * later extraction runs fb_corner_subpix_dev(half_win, half_win, max_iter, eps) on the handle's bird stream after the
  * guidance filter (straight after the extraction when there is no contour) and before mvKeysBirdCamXYZ and the bird grid,
  * which are therefore built from the refined positions.  half_win = 0 switches it off again; off is the state of a new
- * handle.  Descriptors stay those of the unrefined positions.  A refined point outside the image stays a key point and
- * falls in no grid cell (PosInGridBirdview).                                                                             */
+ * handle.  Descriptors stay those of the unrefined positions unless fb_frame_set_bird_redescribe is on as well.  A
+ * refined point outside the image stays a key point and falls in no grid cell (PosInGridBirdview).                       */
 int fb_frame_set_bird_subpix(fb_frame *f, int32_t half_win, int32_t max_iter, double eps);
+
+/* extractorBird->compute(BirdGray, mvKeysBird, mDescriptorsBird) at the refined positions (Frame.cc:352-355): with on != 0
+ * AND fb_frame_set_bird_subpix on, every later extraction runs fb_orb_describe_dev(bird_extractor, FB_DESCRIBE_KEEP_ANGLE)
+ * on the frame's bird key points and descriptors (the arrays the guidance filter has compacted) on the handle's bird
+ * stream, straight after fb_corner_subpix_dev.  A key point whose refined position lies outside the 19-px border of its
+ * level keeps the descriptor of its unrefined position, stays a key point at its index (no compaction, see
+ * fb_orb_describe_args) and has the status FB_DESCRIBE_BORDER.  With cornerSubPix off the switch does nothing: the
+ * descriptors are already those of the positions.  Off is the state of a new handle; turning it on allocates the
+ * [batch][fb_orb_capacity] status bytes the handle owns.                                                                 */
+int fb_frame_set_bird_redescribe(fb_frame *f, int32_t on);
+/* The status bytes (FB_DESCRIBE_*) of the last extraction that re-described, host_status [batch][fb_orb_capacity]; only
+ * the entries below n_bird are meaningful.  FB_ERR_ARG when the frame's last extraction did not re-describe.
+ * Synchronises `stream`.                                                                                                 */
+int fb_frame_download_bird_describe_status(fb_frame *f, uint8_t *host_status, void *stream);
 
 /* Frame::SetPose(Tcw) + UpdatePoseMatrices (Frame.cc:421-433): d_Tcw [batch][12] device.                                */
 int fb_frame_set_pose_dev(fb_frame *f, const float *d_Tcw, void *stream);
