@@ -81,6 +81,13 @@ class OrbDescribeArgs(C.Structure):
 
 FB_DESCRIBE_OK, FB_DESCRIBE_BORDER, FB_DESCRIBE_LEVEL = 0, 1, 2
 FB_DESCRIBE_KEEP_ANGLE, FB_DESCRIBE_IC_ANGLE = 0, 1
+FB_BIRD_DETECT_ORBEXTRACTOR, FB_BIRD_DETECT_CVORB = 0, 1
+
+
+class OrbDetectArgs(C.Structure):
+    _fields_ = [("batch", _i32), ("width", _i32), ("height", _i32), ("stride", _i32), ("image_stride", C.c_size_t),
+                ("images", _vp), ("mask", _vp), ("mask_stride", _i32), ("fast_threshold", _i32), ("kp_stride", _i32),
+                ("kps", _vp), ("n", _vp), ("n_true", _vp)]
 
 
 class MatcherParams(C.Structure):
@@ -448,6 +455,7 @@ EXPORTS = [
     "fb_orb_get_level", "fb_orb_get_blurred_level", "fb_orb_debug_candidates", "fb_orb_debug_resize_route", "fb_orb_debug_timers", "fb_grid_build_batch_dev", "fb_bird_keys_to_cam_dev", "fb_bird_guidance", "fb_bird_guidance_dev",
     "fb_corner_subpix", "fb_corner_subpix_dev", "fb_frame_set_bird_subpix", "fb_frame_download_bird_grid",
     "fb_orb_describe", "fb_orb_describe_dev", "fb_frame_set_bird_redescribe", "fb_frame_download_bird_describe_status",
+    "fb_orb_detect", "fb_orb_detect_dev", "fb_orb_detect_masks_dev", "fb_frame_set_bird_detector",
     "fb_descriptor_distance_dev", "fb_descriptor_distance",
     "fb_match_projection_frame_dev", "fb_match_projection_frame",
     "fb_match_bird_mappoints_dev", "fb_match_bird_mappoints",

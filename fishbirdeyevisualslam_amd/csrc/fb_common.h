@@ -57,7 +57,7 @@ enum ProfId {
   P_BIRDVIEW, P_BOW, P_TRIANG, P_POSE, P_GATHER, P_BA_LINEARIZE, P_BA_SCHUR, P_BA_SOLVE, P_BA_UPDATE, P_BA_MISC,
   P_PROJ_KF, P_BOW_KF, P_FRUSTUM, P_UNDISTORT, P_BLUR, P_FUSE, P_DISTINCT, P_BOWT, P_FAST56, P_FAST72, P_TRACK_GLUE,
   P_NP_PREP, P_NP_M7, P_NP_CLAIM, P_NP_EMIT, P_KFDB, P_SIM3_PREP, P_SIM3_HYP, P_SIM3_ACCEPT, P_TAIL_FRONT,
-  P_TAIL_BIRD, P_OPT_SIM3, P_DESCRIBE_AT, P_COUNT
+  P_TAIL_BIRD, P_OPT_SIM3, P_DESCRIBE_AT, P_DET_FAST, P_DET_SELECT, P_DET_EMIT, P_COUNT
 };
 extern bool g_prof_on;
 extern int g_prof_only;  // -1 = every kernel, else only this ProfId is bracketed

@@ -12,6 +12,8 @@
 //   ORBextractor::operator()          :1043-1105   -> fb_orb_extract*
 //   computeDescriptors on a caller's key points (cv::ORB::compute)   -> k_describe_at (one wave per key point, the level
 //        from its record) -> fb_orb_describe*
+//   cv::ORB::detect (OpenCV 3 orb.cpp computeKeyPoints: FAST, Harris, retainBest, IC_Angle)   -> k_det_fast, k_det_select,
+//        k_det_emit on the same raw pyramid -> fb_orb_detect*
 //
 // HBM layout per image: level 0 is the caller's image (never copied); levels 1..n-1 live in
 // one pitched buffer (pitch % 64 == 0), the blurred levels in a second one of the same geometry.
@@ -28,6 +30,7 @@
 
 #include "orb_plan.h"
 #include "orb_describe_at_plan.h"
+#include "orb_detect_plan.h"
 
 namespace {
 
@@ -61,6 +64,7 @@ __constant__ PackedPattern c_pattern = pack_pattern();
 #include "orb_octree.inc"
 #include "orb_describe.inc"
 #include "orb_describe_at.inc"
+#include "orb_detect.inc"
 
 // ------------------------------------------------------------------------------------------
 // host side
@@ -76,6 +80,13 @@ struct Workspace {
   bool rowsOK[FB_MAX_LEVELS] = {}, mergeOK[FB_MAX_LEVELS] = {};  // see resize_rows_ok / resize_merge_ok
   ResizeTabs rt[FB_MAX_LEVELS] = {};
   fb::DevBuf pyr, blur, cand, cellCand, cellCount, nodeOf, counts, lvlOut, tabs, angTab, timers;
+};
+
+// What fb_orb_detect adds for one (w, h, batchCap), built by its first call at that size (orb_detect_plan.h)
+struct DetectWs {
+  int w = 0, h = 0, batchCap = 0, maskCap = 0;  // maskCap: mask pyramids `maskpyr` holds
+  DetK K = {};
+  fb::DevBuf map, hist, pos, resp, cnt, maskpyr;
 };
 
 }  // namespace
@@ -96,6 +107,7 @@ struct fb_orb {
   }
   int kpStride = 0;  // fb_orb_set_output_stride (0 = the capacity)
   Workspace ws;
+  DetectWs det;
   // last call (for fb_orb_get_level and fb_orb_describe)
   int lastBatch = 0;
   const uint8_t *lastImg = nullptr;
@@ -303,22 +315,83 @@ int build_workspace(const OrbPlan &P, int batch, Workspace &ws) {
   return FB_OK;
 }
 
-// (re)build the workspace for images of w x h, up to `batch` per call: plan, allocate, commit.  Until the commit nothing of
-// the handle is written, so a refusal or a HIP error leaves it usable at its previous size.
-int prepare(fb_orb *o, int w, int h, int batch) {
-  if (o->ws.w == w && o->ws.h == h && batch <= o->ws.batchCap) return FB_OK;
+// (re)build the workspace for images of w x h, up to `batch` per call: plan, allocate (make_workspace), commit.  Until the
+// commit nothing of the handle is written, so a refusal or a HIP error leaves it usable at its previous size.
+bool workspace_fits(const fb_orb *o, int w, int h, int batch) { return o->ws.w == w && o->ws.h == h && batch <= o->ws.batchCap; }
+int make_workspace(fb_orb *o, int w, int h, int batch, Workspace &ws) {
   OrbPlan P;
   FB_TRY(plan_orb(o->p, o->t, w, h, o->kpStride, P));
-  Workspace ws;
   FB_TRY(build_workspace(P, batch, ws));
   FB_TRY(allow_octree_lds<1024>());
   FB_TRY(allow_octree_lds<256>());
   ws.w = w; ws.h = h; ws.batchCap = batch;
+  return FB_OK;
+}
+void commit_workspace(fb_orb *o, Workspace &ws) {
   o->ws = std::move(ws);  // the commit: moves of plain data and of buffer ownership, nothing that can fail
   o->lastBatch = 0;       // the new buffers hold no pyramid yet (fb_orb_describe)
+}
+int prepare(fb_orb *o, int w, int h, int batch) {
+  if (workspace_fits(o, w, h, batch)) return FB_OK;
+  Workspace ws;
+  FB_TRY(make_workspace(o, w, h, batch, ws));
+  commit_workspace(o, ws);
   return FB_OK;
 }
 
+// fb_orb_detect: the extractor's workspace AND the detector's buffers for images of w x h, up to `batch` per call and `masks`
+// mask pyramids.  Both are planned and allocated before either is committed, so a refused call leaves the handle as it was.
+int prepare_detect(fb_orb *o, int w, int h, int batch, int masks) {
+  const bool needWs = !workspace_fits(o, w, h, batch);
+  const bool needDet = !(o->det.w == w && o->det.h == h && batch <= o->det.batchCap && masks <= o->det.maskCap);
+  Workspace ws;
+  DetectWs d;
+  if (needWs) FB_TRY(make_workspace(o, w, h, batch, ws));
+  if (needDet) {
+    OrbPlan P;
+    FB_TRY(plan_orb(o->p, o->t, w, h, o->kpStride, P));
+    DetPlan D;
+    FB_TRY(plan_detect(P, o->t, D));
+    d.K = D.K;
+    // (never smaller than what the handle holds at this size: a call with fewer images or masks later fits again)
+    const bool same = o->det.w == w && o->det.h == h;
+    d.batchCap = same ? std::max(batch, o->det.batchCap) : batch;
+    d.maskCap = same ? std::max(masks, o->det.maskCap) : masks;
+    const DetSizes z = D.sizes(d.batchCap, d.maskCap);
+    FB_TRY(d.map.alloc(z.map));
+    FB_TRY(d.hist.alloc(z.hist));
+    FB_TRY(d.pos.alloc(z.pos));
+    FB_TRY(d.resp.alloc(z.resp));
+    FB_TRY(d.cnt.alloc(z.cnt));
+    FB_TRY(d.maskpyr.alloc(z.maskpyr));
+    d.w = w; d.h = h;
+  }
+  if (needWs) commit_workspace(o, ws);
+  if (needDet) o->det = std::move(d);
+  return FB_OK;
+}
+
+// the mask pyramid(s) of one call: m_l = tozero_254(resize(m_{l-1})), with the image levels' own resize tables; `masks`
+// pyramids, the caller's masks `maskImgStride` bytes apart
+int launch_mask_pyramid(fb_orb *o, const fb_orb_detect_args *A, int masks, long long maskImgStride, hipStream_t s) {
+  const Workspace &ws = o->ws;
+  uint8_t *mp = o->det.maskpyr.as<uint8_t>();
+  const long long mpStride = ws.K.pyrStride;
+  for (int l = 1; l < ws.K.nlevels; l++) {
+    const LevelInfo &D = ws.K.L[l], &S = ws.K.L[l - 1];
+    const uint8_t *src = l == 1 ? A->mask : mp + S.off;
+    const int spitch = l == 1 ? A->mask_stride : S.pitch;
+    {
+      fb::ProfScope prof_(fb::P_RESIZE, s);
+      k_resize<<<dim3((D.pitch / 4 + 63) / 64, (D.h + 3) / 4, masks), dim3(64, 4), 0, s>>>(src, l == 1 ? maskImgStride : mpStride, S.w, S.h, spitch, mp + D.off, mpStride,
+                                                                                         D.w, D.h, D.pitch, ws.rt[l]);
+    }
+    const int dwords = D.pitch / 4 * D.h;
+    k_det_mask<<<dim3((dwords + 255) / 256, masks), 256, 0, s>>>(mp + D.off, mpStride, dwords);
+  }
+  FB_HIP(hipGetLastError());
+  return FB_OK;
+}
 
 // fb_orb_describe[_dev]: the argument checks of orb_describe_at_plan.h against the handle's last extract call
 int describe_check(const fb_orb *o, const fb_orb_describe_args *A, size_t *lds) {
@@ -487,6 +560,79 @@ int fb_orb_describe(fb_orb *o, const fb_orb_describe_args *H) {
   st.out(D.status, z.status, true);
   FB_TRY(st.commit(nullptr));
   FB_TRY(fb_orb_describe_dev(o, &D, nullptr));
+  return st.fetch(nullptr);
+}
+
+// ---- cv::ORB's detector on the handle's pyramid (the rules are restated at fb_orb_detect_args) ----------------------------
+int fb_orb_detect_dev(fb_orb *o, const fb_orb_detect_args *A, void *stream) { return fb_orb_detect_masks_dev(o, A, 0, stream); }
+
+int fb_orb_detect_masks_dev(fb_orb *o, const fb_orb_detect_args *A, size_t mask_image_stride, void *stream) {
+  FB_TRY(fb::check_device());
+  FB_ARG(o);
+  bool noop = false;
+  FB_TRY(check_detect(A, mask_image_stride, "fb_orb_detect", &noop));
+  if (noop) return FB_OK;
+  FB_ARG(((uintptr_t)A->kps | (uintptr_t)A->n | (uintptr_t)A->n_true) % 4 == 0);
+  const int masks = !A->mask ? 0 : mask_image_stride ? A->batch : 1;
+  FB_TRY(prepare_detect(o, A->width, A->height, A->batch, std::max(masks, 1)));
+  const Workspace &ws = o->ws;
+  const OrbCall c = {A->images, (long long)A->image_stride, A->stride, A->batch, fb::as_stream(stream)};
+  BlurSchedule blur(o, c);
+  FB_TRY(blur.begin(c.s));
+  FB_HIP(hipMemsetAsync(o->det.hist.p, 0, (size_t)A->batch * ws.K.nlevels * 256 * 4, c.s));
+  for (int l = 0; l < ws.K.nlevels; l++) {  // the raw and the blurred pyramid, exactly as an extract call builds them
+    if (l > 0) launch_resize(o, l, c);
+    FB_TRY(blur.behind_level(l));
+  }
+  if (A->mask) FB_TRY(launch_mask_pyramid(o, A, masks, (long long)mask_image_stride, c.s));
+  DetK K = o->det.K;
+  K.thr = A->fast_threshold; K.pitch0 = A->stride; K.kp_stride = A->kp_stride; K.mask_pitch0 = A->mask_stride;
+  K.img_stride = (long long)A->image_stride;
+  K.mask_img_stride = (long long)mask_image_stride; K.maskpyr_stride = mask_image_stride ? ws.K.pyrStride : 0;
+  K.img0 = A->images; K.pyr = ws.pyr.as<uint8_t>();
+  K.mask0 = A->mask; K.maskpyr = o->det.maskpyr.as<uint8_t>();
+  K.map = o->det.map.as<uint8_t>(); K.hist = o->det.hist.as<unsigned>(); K.pos = o->det.pos.as<uint32_t>();
+  K.resp = o->det.resp.as<float>(); K.cnt = o->det.cnt.as<int32_t>(); K.ang_tab = ws.angTab.p;
+  K.kps = A->kps; K.n = A->n; K.n_true = A->n_true;
+  DetSelLds S;
+  const size_t selLds = det_select_layout(S);
+  if (K.tileBase[K.nlevels] > 0) {
+    fb::ProfScope prof_(fb::P_DET_FAST, c.s);
+    k_det_fast<<<dim3(K.tileBase[K.nlevels], A->batch), DET_FAST_THREADS, 0, c.s>>>(K);
+  }
+  {
+    fb::ProfScope prof_(fb::P_DET_SELECT, c.s);
+    k_det_select<<<dim3(K.nlevels, A->batch), DET_SEL_THREADS, selLds, c.s>>>(K);
+  }
+  FB_TRY(blur.join_before_describe(c.s));
+  {
+    fb::ProfScope prof_(fb::P_DET_EMIT, c.s);
+    k_det_emit<<<dim3((A->kp_stride + DET_EMIT_WAVES - 1) / DET_EMIT_WAVES, A->batch), DET_EMIT_WAVES * 64, 0, c.s>>>(K);
+  }
+  FB_HIP(hipGetLastError());
+  o->lastBatch = A->batch;  // the pyramids are this call's: fb_orb_describe and fb_orb_get_level work on them
+  o->lastImg = A->images;
+  o->lastImgStride = (long long)A->image_stride;
+  o->lastPitch0 = A->stride;
+  return FB_OK;
+}
+
+int fb_orb_detect(fb_orb *o, const fb_orb_detect_args *H) {
+  FB_TRY(fb::check_device());
+  FB_ARG(o);
+  bool noop = false;
+  FB_TRY(check_detect(H, 0, "fb_orb_detect", &noop));
+  if (noop) return FB_OK;
+  fb_orb_detect_args D = *H;
+  const DetStage z = detect_stage(*H);
+  fb::Stager st;
+  st.in(D.images, z.images);
+  st.in(D.mask, z.mask);
+  st.out(D.kps, z.kps, true);  // in/out: the entries at or past n[b] keep the caller's contents
+  st.out(D.n, z.n, false);
+  st.out(D.n_true, z.n_true, false);
+  FB_TRY(st.commit(nullptr));
+  FB_TRY(fb_orb_detect_dev(o, &D, nullptr));
   return st.fetch(nullptr);
 }
 

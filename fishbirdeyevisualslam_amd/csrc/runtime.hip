@@ -117,7 +117,8 @@ const char *kProfNames[P_COUNT] = {"k_resize", "k_fast<44>", "k_octree", "k_desc
                                    "k_ba_solve", "k_ba_update", "k_ba_misc", "k_proj_kf", "k_match_bow_kf", "k_in_frustum",
                                    "k_undistort", "k_blur", "k_kf_search", "k_distinctive", "k_bow_transform", "k_fast<56>", "k_fast<72>", "k_track_glue",
                                    "k_np_prep", "k_match_triangulation[np]", "k_np_claim", "k_np_emit", "k_kfdb_query",
-                                   "k_sim3_prepare", "k_sim3_hypotheses", "k_sim3_accept", "k_frame_tail_front", "k_frame_tail_bird", "k_optimize_sim3", "k_describe_at"};
+                                   "k_sim3_prepare", "k_sim3_hypotheses", "k_sim3_accept", "k_frame_tail_front", "k_frame_tail_bird", "k_optimize_sim3", "k_describe_at",
+                                   "k_det_fast", "k_det_select", "k_det_emit"};
 struct ProfRec { int id; hipEvent_t a, b; };
 std::mutex g_prof_mu;
 std::vector<ProfRec> g_recs;

@@ -61,6 +61,8 @@ struct fb_frame {
   // extractorBird->compute at the refined positions (Frame.cc:352-355, fb_frame_set_bird_redescribe): runs only with subpix on
   bool redescribe = false, redescribed = false;  // the switch; the last extraction ran it
   fb::DevBuf describeStatus;                     // [B][cap] FB_DESCRIBE_*, plan_redescribe_status(); allocated by the switch
+  // cv::ORB's detector instead of ORBextractor on the bird image (Frame.cc:337-340, fb_frame_set_bird_detector)
+  int detectMode = FB_BIRD_DETECT_ORBEXTRACTOR, detectThr = 20;
   // images from host callers
   fb::DevBuf img_f, img_b, img_c, img_m;
   uint8_t *pin = nullptr;
@@ -203,13 +205,23 @@ int fb_frame_extract_dev(fb_frame *f, fb_orb *of, fb_orb *ob, const uint8_t *d_f
     fb_keypoint *k0 = d_contour ? f->pre.kps : F.bkps;
     uint8_t *d0 = d_contour ? f->pre.desc : F.bdesc;
     int32_t *n0 = d_contour ? f->pre.n : F.nb;
-    FB_TRY(fb_orb_extract_batch_dev(ob, d_bird, B, f->P.bird_width, f->P.bird_height, bird_stride, bird_image_stride, k0, d0, n0, sb));
+    const bool cvorb = f->detectMode == FB_BIRD_DETECT_CVORB;
+    if (cvorb) {  // Frame.cc:337-340: cv::ORB::detect(bird, mask); the descriptors follow at the end of the chain
+      fb_orb_detect_args E;
+      memset(&E, 0, sizeof(E));
+      E.batch = B; E.width = f->P.bird_width; E.height = f->P.bird_height; E.stride = bird_stride; E.image_stride = bird_image_stride;
+      E.images = d_bird; E.mask = d_mask; E.mask_stride = bird_stride; E.fast_threshold = f->detectThr;
+      E.kp_stride = cap; E.kps = k0; E.n = n0;
+      FB_TRY(fb_orb_detect_masks_dev(ob, &E, d_mask ? bird_image_stride : 0, sb));
+    } else {
+      FB_TRY(fb_orb_extract_batch_dev(ob, d_bird, B, f->P.bird_width, f->P.bird_height, bird_stride, bird_image_stride, k0, d0, n0, sb));
+    }
     if (d_contour) {
       fb_bird_guidance_args G;
       memset(&G, 0, sizeof(G));
       G.batch = B; G.kp_stride = cap; G.cols = f->P.bird_width; G.rows = f->P.bird_height; G.pitch = bird_stride;
-      G.contour = d_contour; G.mask = d_mask; G.n_in = n0; G.kps_in = k0; G.desc_in = d0;
-      G.n_out = F.nb; G.kps_out = F.bkps; G.desc_out = F.bdesc;
+      G.contour = d_contour; G.mask = cvorb ? nullptr : d_mask; G.n_in = n0; G.kps_in = k0; G.desc_in = cvorb ? nullptr : d0;
+      G.n_out = F.nb; G.kps_out = F.bkps; G.desc_out = cvorb ? nullptr : F.bdesc;
       G.keep = f->pre.keep;  // [batch][cap]: the verdicts are computed by many workgroups
       FB_TRY(fb_bird_guidance_dev(&G, sb));
     }
@@ -220,7 +232,7 @@ int fb_frame_extract_dev(fb_frame *f, fb_orb *of, fb_orb *ob, const uint8_t *d_f
       S.image_stride = bird_image_stride; S.image = d_bird; S.n = F.nb; S.kps = F.bkps;
       S.half_win_x = S.half_win_y = f->subpixHalf; S.max_iter = f->subpixIters; S.eps = f->subpixEps;
       FB_TRY(fb_corner_subpix_dev(&S, sb));
-      if (f->redescribe) {  // Frame.cc:352-355: the descriptors of the refined positions, on the bird extractor's blurred pyramid
+      if (f->redescribe && !cvorb) {  // Frame.cc:352-355: the descriptors of the refined positions, on the bird extractor's blurred pyramid
         fb_orb_describe_args R;
         memset(&R, 0, sizeof(R));
         R.batch = B; R.kp_stride = cap; R.n = F.nb; R.kps = F.bkps; R.desc = F.bdesc; R.status = f->describeStatus.as<uint8_t>();
@@ -228,7 +240,14 @@ int fb_frame_extract_dev(fb_frame *f, fb_orb *of, fb_orb *ob, const uint8_t *d_f
         FB_TRY(fb_orb_describe_dev(ob, &R, sb));
       }
     }
-    f->redescribed = f->subpixHalf > 0 && f->redescribe;
+    if (cvorb) {  // Frame.cc:352-355: extractorBird->compute, here the only source of the descriptors
+      fb_orb_describe_args R;
+      memset(&R, 0, sizeof(R));
+      R.batch = B; R.kp_stride = cap; R.n = F.nb; R.kps = F.bkps; R.desc = F.bdesc; R.status = f->describeStatus.as<uint8_t>();
+      R.angle_mode = FB_DESCRIBE_KEEP_ANGLE;
+      FB_TRY(fb_orb_describe_dev(ob, &R, sb));
+    }
+    f->redescribed = cvorb || (f->subpixHalf > 0 && f->redescribe);
     FB_TRY(fb_bird_keys_to_cam_dev(F.bkps, F.nb, B, cap, f->P.bird_width, f->P.bird_height, f->P.pixel2meter, f->P.rear_axle_to_center,
                                    f->P.Tcb, F.bcam, sb));
     FB_TRY(fb_grid_build_batch_dev(F.bkps, F.nb, B, cap, &f->gB, f->bcs, f->bci, sb));
@@ -290,6 +309,20 @@ int fb_frame_set_bird_redescribe(fb_frame *f, int32_t on) {
     FB_TRY(f->describeStatus.alloc(plan_redescribe_status(f->P, f->cap), true));
   }
   f->redescribe = on != 0;
+  return FB_OK;
+}
+
+int fb_frame_set_bird_detector(fb_frame *f, int32_t mode, int32_t fast_threshold) {
+  FB_ARG(f && (mode == FB_BIRD_DETECT_ORBEXTRACTOR || mode == FB_BIRD_DETECT_CVORB));
+  if (mode == FB_BIRD_DETECT_CVORB) {
+    FB_ARG(fast_threshold >= 1 && fast_threshold <= 255);
+    if (!f->describeStatus.p) {
+      FB_TRY(fb::check_device());
+      FB_TRY(f->describeStatus.alloc(plan_redescribe_status(f->P, f->cap), true));
+    }
+    f->detectThr = fast_threshold;
+  }
+  f->detectMode = mode;
   return FB_OK;
 }
 

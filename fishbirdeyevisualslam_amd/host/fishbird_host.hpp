@@ -184,6 +184,27 @@ class ORBextractor {
     keypoints.resize(n);
     descriptors.resize((size_t)n * 32);
   }
+  // detect(image, keypoints, mask) of cv::ORB (Frame.cc:337: cv::ORB::create(nfeatures)->detect(bird, mask)): FAST at one
+  // threshold over every level, Harris responses, the best nfeatures split over the levels, IC_Angle; no descriptors (follow
+  // it with compute()).  The rules are at fb_orb_detect_args.  Ties at a cut all stay: a result above the capacity is fetched
+  // whole by a second call.
+  void detect(const uint8_t *image, int width, int height, int stride, std::vector<fb_keypoint> &keypoints,
+              const uint8_t *mask = nullptr, int maskStride = 0, int fastThreshold = 20) {
+    keypoints.clear();
+    if (!image || width <= 0 || height <= 0) return;
+    int32_t n = 0, nTrue = 0;
+    fb_orb_detect_args a{};
+    a.batch = 1; a.width = width; a.height = height; a.stride = stride; a.images = image;
+    a.mask = mask; a.mask_stride = maskStride; a.fast_threshold = fastThreshold;
+    a.n = &n; a.n_true = &nTrue;
+    for (int cap = fb_orb_capacity(&p_);; cap = nTrue) {
+      keypoints.resize(cap);
+      a.kp_stride = cap; a.kps = keypoints.data();
+      check(fb_orb_detect(h_, &a));
+      if (nTrue <= cap) break;
+    }
+    keypoints.resize(n);
+  }
   // compute(image, keypoints, descriptors) of cv::ORB on key points the caller supplies (Frame.cc:352-355 after cornerSubPix):
   // descriptors of `keys` on the pyramid of the LAST operator() call, keys[i].octave selecting the level.  The angles are
   // kept as given (OpenCV 3); with icAngle they are recomputed on `image`, which must be the image of that call.  Nothing
@@ -569,6 +590,10 @@ class DeviceFrame {
   void SetBirdSubPix(int halfWin = 5, int maxCount = 40, double epsilon = 0.001) { check(fb_frame_set_bird_subpix(h_, halfWin, maxCount, epsilon)); }
   // extractorBird->compute at the refined positions (Frame.cc:352-355): runs inside Construct while SetBirdSubPix is on
   void SetBirdRedescribe(bool on = true) { check(fb_frame_set_bird_redescribe(h_, on ? 1 : 0)); }
+  // cv::ORB's detector instead of ORBextractor on the bird image inside every later Construct (Frame.cc:337-355)
+  void SetBirdDetector(bool cvOrb = true, int fastThreshold = 20) {
+    check(fb_frame_set_bird_detector(h_, cvOrb ? FB_BIRD_DETECT_CVORB : FB_BIRD_DETECT_ORBEXTRACTOR, fastThreshold));
+  }
   void SetPose(const float *d_Tcw, void *stream = nullptr) { check(fb_frame_set_pose_dev(h_, d_Tcw, stream)); }
 
   struct TrackResult {             // what Tracking reads after a frame (one synchronisation)

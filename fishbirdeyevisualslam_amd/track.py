@@ -187,6 +187,12 @@ class TrackChain:
         for f in (frames if frames is not None else self.frames):
             check(self.L.fb_frame_set_bird_redescribe(f, int(bool(on))), "fb_frame_set_bird_redescribe")
 
+    def set_bird_detector(self, cvorb=True, fast_threshold=20, frames=None):
+        """cv::ORB's detector (fb_orb_detect) instead of ORBextractor on the bird image of every later extraction (Frame.cc:337-355)."""
+        mode = cabi.FB_BIRD_DETECT_CVORB if cvorb else cabi.FB_BIRD_DETECT_ORBEXTRACTOR
+        for f in (frames if frames is not None else self.frames):
+            check(self.L.fb_frame_set_bird_detector(f, mode, int(fast_threshold)), "fb_frame_set_bird_detector")
+
     def bird_describe_status(self, which="cur"):
         """FB_DESCRIBE_* of the bird key points of the last extraction that re-described, [B][cap] (meaningful below n_bird)."""
         st = np.zeros((self.B, self.cap), np.uint8)

@@ -177,6 +177,63 @@ typedef struct fb_orb_describe_args {
 int fb_orb_describe_dev(fb_orb *h, const fb_orb_describe_args *a, void *stream);  /* device pointers */
 int fb_orb_describe(fb_orb *h, const fb_orb_describe_args *a);                    /* host pointers   */
 
+/* cv::ORB's detector: cv::ORB::create(nfeatures)->detect(image, mask) of OpenCV 3 (features2d/src/orb.cpp computeKeyPoints,
+ * HarrisResponses, ICAngles, KeyPointsFilter::retainBest / runByImageBorder / runByPixelsMask, and cv::FAST with
+ * nonmaxSuppression), restated; OpenCV is not vendored, so parity with it is unpinned like cornerSubPix and
+ * fb_orb_describe.  Frame.cc:337 calls it on the bird image.  nfeatures, nlevels and scale_factor are the handle's;
+ * ini_th_fast and min_th_fast are unused.  Per image b and per level l of the handle's pyramid:
+ *   pyramid   the handle's own raw levels (ORBextractor::ComputePyramid, the tables of fb_orb_get_tables).  cv::ORB sizes
+ *             its levels with cvRound(cols / (float)pow(scaleFactor, l)) and scales pt and size by that power; here the
+ *             sizes are cvRound(cols * inv_scale_factor[l]) and the scale is scale_factor[l].
+ *   mask      optional, u8, `height` rows of `mask_stride` bytes, shared by the batch.  m_0 = mask; for l >= 1
+ *             m_l = tozero_254(resize(m_{l-1})): the bilinear resize of the image levels applied to the already
+ *             thresholded previous level, then a value is kept iff it is > 254 (THRESH_TOZERO at 254), else 0.  A
+ *             candidate at integer (px, py) of level l survives iff m_l[py][px] != 0: at level 0 any nonzero value passes,
+ *             above it only pixels that interpolate to exactly 255.  The mask levels are rebuilt on every call, in a buffer
+ *             of the handle: like the pyramids they serve one caller at a time.
+ *   FAST      FAST-9-16 at the one threshold `fast_threshold` on the pixels [3, w_l - 3) x [3, h_l - 3) of the whole level
+ *             (a pixel outside counts as score 0), the corner test and cornerScore of the extractor; 3x3 non-maximum
+ *             suppression, strictly greater than all 8 neighbours (two equal neighbours drop each other).
+ *   border    kept iff 31 <= px < w_l - 31 and 31 <= py < h_l - 31; a level with w_l <= 62 or h_l <= 62 yields nothing.
+ *   cut 1     K1 = 2 * features_per_level[l]: with more than K1 candidates, exactly those whose FAST score is >= the
+ *             K1-th largest score stay -- ties at the cut all stay, so more than K1 may (retainBest).  K = 0 keeps none.
+ *   Harris    integer sums a = sum Ix^2, b = sum Iy^2, c = sum Ix Iy of the 3x3 Sobel derivatives over the 7 x 7 block
+ *             around (px, py); response = ((float)a*(float)b - (float)c*(float)c - k*((float)a+(float)b)*((float)a+(float)b))
+ *             * s4, k = 0.04f, s = 1.f/(4*7*255.f), s4 = s*s*s*s, every float operation rounded on its own, left to right.
+ *   cut 2     K2 = features_per_level[l], the same rule on the Harris response compared as floats (-0.0 equals 0.0).
+ *   angle     IC_Angle on the raw level at (px, py) (what FB_DESCRIBE_IC_ANGLE computes).
+ *   output    x = (float)px * scale_factor[l], y likewise, size = 31.f * scale_factor[l], angle, response = Harris,
+ *             octave = l.  cvRound(x * inv_scale_factor[l]) == px, so fb_orb_describe lands on the detected pixel.
+ *   order     levels ascending, raster order (py, then px) within a level.  (OpenCV's order after nth_element is
+ *             implementation-defined: the SET is what is shared with it, the order is this library's choice.)
+ *   capacity  kps holds kp_stride entries per image (fb_orb_capacity() is the recommended value).  Ties can make the
+ *             total exceed it: the first kp_stride entries in output order are written, n[b] = kp_stride, and n_true[b]
+ *             (optional) receives the untruncated total.  Entries at or past n[b] are never written.
+ * The call builds the handle's raw and blurred pyramid as an extract call does and counts as the handle's last extraction:
+ * fb_orb_detect followed by fb_orb_describe(FB_DESCRIBE_KEEP_ANGLE) is cv::ORB::detectAndCompute without the compaction.
+ * Workspace and failure behaviour are those of fb_orb_extract_batch_dev (the first call at a size allocates; a refused call
+ * leaves the handle as it was); a later extract call on the handle gives what it gave before.  batch = 0 is a no-op.
+ * No host round trip and no synchronisation inside the _dev call.  kps, n and n_true are 4-byte aligned (_dev).
+ * Kernels: DESIGN.md section 4.                                                                                          */
+typedef struct fb_orb_detect_args {
+  int32_t batch, width, height, stride; /* `batch` u8 images of width x height, `stride` bytes per row                   */
+  size_t image_stride;                  /* image b starts b * image_stride bytes after `images`                          */
+  const uint8_t *images;
+  const uint8_t *mask;                  /* optional: one mask of `height` rows, `mask_stride` bytes apart, for the batch */
+  int32_t mask_stride;
+  int32_t fast_threshold;               /* cv::ORB default 20; 1..255                                                    */
+  int32_t kp_stride;
+  fb_keypoint *kps;                     /* [batch][kp_stride]                                                            */
+  int32_t *n;                           /* [batch]                                                                       */
+  int32_t *n_true;                      /* optional [batch]                                                              */
+} fb_orb_detect_args;
+int fb_orb_detect_dev(fb_orb *h, const fb_orb_detect_args *a, void *stream);  /* device pointers */
+int fb_orb_detect(fb_orb *h, const fb_orb_detect_args *a);                    /* host pointers, through the Stager */
+/* The same with one mask PER IMAGE: the mask of image b starts b * mask_image_stride bytes after a->mask (at least
+ * mask_stride * height; 0 = one mask shared by the batch, which is fb_orb_detect_dev).  The handle then holds one mask
+ * pyramid per image.  fb_frame_extract_dev uses it: a frame's detect masks are per image.                               */
+int fb_orb_detect_masks_dev(fb_orb *h, const fb_orb_detect_args *a, size_t mask_image_stride, void *stream);
+
 /* debug/parity access to the pyramid level of image `b` of the last batch
  * (public member mvImagePyramid, ORBextractor.h:85). dst is host, w*h bytes.  */
 int fb_orb_get_level(fb_orb *h, int b, int level, uint8_t *dst, int *w, int *hgt);
@@ -1725,6 +1782,21 @@ int fb_frame_set_bird_subpix(fb_frame *f, int32_t half_win, int32_t max_iter, do
  * descriptors are already those of the positions.  Off is the state of a new handle; turning it on allocates the
  * [batch][fb_orb_capacity] status bytes the handle owns.                                                                 */
 int fb_frame_set_bird_redescribe(fb_frame *f, int32_t on);
+/* The detector of the bird image (Frame.cc:337-340).  FB_BIRD_DETECT_ORBEXTRACTOR (the state of a new handle): the bird
+ * extractor's own fb_orb_extract_batch_dev, as always.  FB_BIRD_DETECT_CVORB: every later extraction runs, on
+ * the handle's bird stream and with no added synchronisation, the reference's chain Frame.cc:337-355 on the bird extractor:
+ *   fb_orb_detect_masks_dev(fast_threshold) with the detect mask of each image applied at every level (cv::ORB::detect);
+ *   fb_bird_guidance_dev with mask = NULL (the mask is already applied) when there is a contour image;
+ *   fb_corner_subpix_dev when fb_frame_set_bird_subpix is on;
+ *   fb_orb_describe_dev(FB_DESCRIBE_KEEP_ANGLE), always: this detector does not describe.  It runs whatever
+ *   fb_frame_set_bird_redescribe says, and fb_frame_download_bird_describe_status returns its status bytes (a point that
+ *   cornerSubPix moved outside the 19-px border of its level is FB_DESCRIBE_BORDER and its descriptor row is unspecified).
+ * nfeatures, nlevels and scale_factor are the bird extractor's; at most fb_orb_capacity entries per image are kept (ties
+ * beyond it are cut off in output order).  A detect mask without a contour image is refused as before.  Turning CVORB on
+ * allocates the status bytes the handle owns.  fast_threshold: 1..255 (cv::ORB's default is 20).                         */
+enum { FB_BIRD_DETECT_ORBEXTRACTOR = 0, FB_BIRD_DETECT_CVORB = 1 };
+int fb_frame_set_bird_detector(fb_frame *f, int32_t mode, int32_t fast_threshold);
+
 /* The status bytes (FB_DESCRIBE_*) of the last extraction that re-described, host_status [batch][fb_orb_capacity]; only
  * the entries below n_bird are meaningful.  FB_ERR_ARG when the frame's last extraction did not re-describe.
  * Synchronises `stream`.                                                                                                 */
