@@ -315,6 +315,14 @@ class LocalMapArgs(C.Structure):
                 ("gate_min", _i32), ("reuse_index", _i32)]
 
 
+FB_COVIS_BIRD_TH = 2
+
+
+class LocalBirdMapArgs(C.Structure):
+    _fields_ = [("new_slot", _i32), ("d_kf_ow", _vp), ("d_mpb_order", _vp), ("cap_kf", _i32), ("d_local_kf_bird", _vp),
+                ("d_n_local_kf_bird", _vp), ("cap_mpb", _i32), ("d_local_mpb", _vp), ("d_n_local_mpb", _vp), ("d_overflow", _vp)]
+
+
 class CorrectLoopArgs(C.Structure):
     _fields_ = [("q", C.c_double * 4), ("t", C.c_double * 3), ("s", C.c_double), ("cur_slot", _i32), ("reuse_index", _i32),
                 ("scale_factors", _vp), ("mp_ref_kf", _vp), ("mp_normal", _vp), ("mp_min_dist", _vp), ("mp_max_dist", _vp),
@@ -483,6 +491,8 @@ EXPORTS = [
     "fb_covis_tree_set_dev", "fb_covis_tree_get_dev", "fb_covis_tree_get", "fb_covis_change_parent_dev", "fb_covis_erase_child_dev",
     "fb_covis_children_dev", "fb_covis_children", "fb_covis_parent_dev", "fb_covis_first_connection_dev",
     "fb_covis_tree_erase_keyframe_dev", "fb_covis_local_map_dev", "fb_covis_local_map", "fb_covis_reserve_local_map",
+    "fb_covis_update_bird_connections_dev", "fb_covis_update_bird_connections", "fb_covis_bird_connected_dev",
+    "fb_covis_bird_connected", "fb_covis_local_bird_map_dev", "fb_covis_local_bird_map", "fb_covis_reserve_local_bird_map",
     "fb_covis_correct_loop_dev", "fb_covis_correct_loop", "fb_covis_reserve_correct_loop", "fb_covis_propagate_gba_dev",
     "fb_covis_propagate_gba",
     "fb_covis_refresh_points_dev", "fb_covis_refresh_points", "fb_covis_reserve_refresh_points",

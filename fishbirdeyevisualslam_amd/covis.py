@@ -79,6 +79,30 @@ class DeviceTables:
                   n_mpb=self.n_mpb, n_bobs=self.n_bobs, **self.t)
 
 
+class DeviceBirdTables:
+    """What the bird calls (update_bird_connections, local_bird_map) read, over device tensors: a fb_covis_map that carries
+    max_keyframes and kf_order only, and a fb_covis_kf_tables with kf_nb, kf_mpb, mpb_bad, the bird edge list and, when given,
+    kf_Tcw.  `arrays` holds kf_order, kf_nb, kf_mpb [K][bird_stride], mpb_bad, bobs_mpb, bobs_kf, bobs_idx (+ kf_Tcw)."""
+    FIELDS = (("kf_nb", np.int32), ("kf_mpb", np.int32), ("mpb_bad", np.uint8), ("bobs_mpb", np.int32), ("bobs_kf", np.int32),
+              ("bobs_idx", np.int32))
+
+    def __init__(self, arrays, device="cuda:0"):
+        self.device = torch.device(device)
+        self.K, self.BS = np.asarray(arrays["kf_mpb"]).shape
+        self.n_mpb, self.n_bobs = len(arrays["mpb_bad"]), len(arrays["bobs_kf"])
+        self.t = {}
+        for name, dt in self.FIELDS + ((("kf_Tcw", np.float32),) if "kf_Tcw" in arrays else ()):
+            a = np.ascontiguousarray(arrays[name], dt)
+            if a.size == 0:
+                a = np.zeros(1, dt)
+            self.t[name] = torch.from_numpy(a.copy()).to(self.device)
+        self.order = torch.from_numpy(np.ascontiguousarray(arrays["kf_order"], np.uint64).view(np.int64).copy()).to(self.device)
+        self.c = cabi.CovisKfTables()
+        cabi.fill(self.c, bird_stride=self.BS, n_mpb=self.n_mpb, n_bobs=self.n_bobs, **self.t)
+        self.map = cabi.CovisMap()
+        cabi.fill(self.map, max_keyframes=self.K, kp_stride=1, kf_order=self.order)
+
+
 WINDOW_ARRAYS = (("kf_slot", "cap_kf", 1, torch.int32), ("kf_fixed", "cap_kf", 1, torch.uint8), ("kf_Tcw", "cap_kf", 12, torch.float32),
                  ("mp_index", "cap_mp", 1, torch.int32), ("mp_xw", "cap_mp", 3, torch.float32), ("obs_kf", "cap_obs", 1, torch.int32),
                  ("obs_mp", "cap_obs", 1, torch.int32), ("obs_src", "cap_obs", 1, torch.int32), ("obs_uv", "cap_obs", 2, torch.float32),
@@ -441,3 +465,51 @@ class CovisibilityGraph:
         check(lib().fb_covis_map_point_culling_dev(self.h, C.byref(m.c), C.byref(a), _stream()), "fb_covis_map_point_culling_dev")
         self._keep = (m, a, t, recent, n_recent, out)
         return out
+
+    # ---- the bird side: UpdateBirdConnections and the local bird map ------------------------------------------------------------
+    def reserve_local_bird_map(self, n_mpb, n_bobs):
+        check(lib().fb_covis_reserve_local_bird_map(self.h, int(n_mpb), int(n_bobs)), "fb_covis_reserve_local_bird_map")
+
+    def update_bird_connections(self, m, t, slots, n_counter=None, now_state=0, id0_slot=-1, kf_frame_id=None, kf_in_map=None):
+        """KeyFrame::UpdateBirdConnections(now_state) of the listed slots -> (n_bird_counter, bird_front) device int32 tensors.
+        m: a cabi.CovisMap or an object with one under .c (only max_keyframes and kf_order are read); t: DeviceTables with
+        the bird side or DeviceBirdTables; n_counter: the front update_connections' output for the same slots, None = all act."""
+        slots = self._dev(slots).reshape(-1)
+        n = slots.numel()
+        fid = None if kf_frame_id is None else self._dev(kf_frame_id)
+        inm = None if kf_in_map is None else self._dev(kf_in_map, torch.uint8)
+        nbc, bf = self._i32(n, -7), self._i32(n, -7)
+        mc = m if isinstance(m, cabi.CovisMap) else m.c
+        check(lib().fb_covis_update_bird_connections_dev(self.h, C.byref(mc), C.byref(t.c), n, _p(slots), _p(n_counter), int(now_state),
+                                                         int(id0_slot), _p(fid), _p(inm), _p(nbc), _p(bf), _stream()),
+              "fb_covis_update_bird_connections_dev")
+        self._keep = (m, t, slots, n_counter, fid, inm)
+        return nbc[:n], bf[:n]
+
+    def bird_connected(self, slot):
+        """GetBirdConnectedBirdKeyFrames + the bird weights -> (n[1], slots[K], weights[K])"""
+        n, s, w = self._i32(1), self._i32(self.K, -1), self._i32(self.K, -1)
+        check(lib().fb_covis_bird_connected_dev(self.h, int(slot), _p(n), _p(s), _p(w), _stream()), "fb_covis_bird_connected_dev")
+        return n, s, w
+
+    def local_bird_map_arrays(self, cap_kf, cap_mpb, kf_ow=None, mpb_order=None, guard=0):
+        """Device arrays of a fb_local_bird_map_args with an empty localKFbird; each list is followed by `guard` elements the
+        library never sees -> (dict of tensors, cabi.LocalBirdMapArgs)"""
+        t = dict(d_local_kf_bird=torch.full((int(cap_kf) + guard + 1,), -5, dtype=torch.int32, device=self.device), d_n_local_kf_bird=self._i32(1),
+                 d_local_mpb=torch.full((int(cap_mpb) + guard + 1,), -5, dtype=torch.int32, device=self.device), d_n_local_mpb=self._i32(1, -5),
+                 d_overflow=self._i32(1, -5))
+        if kf_ow is not None:
+            t["d_kf_ow"] = self._dev(kf_ow, torch.float32).reshape(-1)
+        if mpb_order is not None:
+            t["d_mpb_order"] = torch.from_numpy(np.ascontiguousarray(mpb_order, np.uint64).view(np.int64).copy()).to(self.device)
+        a = cabi.LocalBirdMapArgs()
+        cabi.fill(a, new_slot=0, cap_kf=int(cap_kf), cap_mpb=int(cap_mpb), **t)
+        return t, a
+
+    def local_bird_map(self, m, t, a, new_slot):
+        """The bird block of Map::AddKeyFrame(new_slot) + Map::UpdateLocalBirdMap on the arrays of local_bird_map_arrays.
+        Enqueues only."""
+        a.new_slot = int(new_slot)
+        mc = m if isinstance(m, cabi.CovisMap) else m.c
+        check(lib().fb_covis_local_bird_map_dev(self.h, C.byref(mc), C.byref(t.c), C.byref(a), _stream()), "fb_covis_local_bird_map_dev")
+        self._keep = (m, t, a)

@@ -1,7 +1,7 @@
 """Synthetic maps for the covisibility graph (fb_covis_*): key frames, map points and the observation edge list as the arrays
 of fb_covis_map, with the reference's quirks planted.
 
-    python -m fishbirdeyevisualslam_amd.covis_problem --probe     # times UpdateConnections / KeyFrameCulling / the window / the local
+    python -m fishbirdeyevisualslam_amd.covis_problem --probe     # times UpdateConnections (front and bird) / KeyFrameCulling / the window / the local
                                                                   # map, the tree calls, the two map correction calls and the
                                                                   # per-point calls at a LocalMapping-like size
     python -m fishbirdeyevisualslam_amd.covis_problem --probe-points   # the local map and the per-point calls alone
@@ -503,8 +503,11 @@ def _probe():
         return (time.perf_counter() - t) / reps * 1e3
     G.update_connections(m, list(range(p["K"])))
     cur = p["K"] // 2
-    print("device update_connections(1 key frame):   %.3f ms" % timed(lambda: G.update_connections(m, [cur])))
-    print("device update_connections(30 key frames): %.3f ms" % timed(lambda: G.update_connections(m, list(range(cur - 15, cur + 15)))))
+    front1 = timed(lambda: G.update_connections(m, [cur]))
+    front30 = timed(lambda: G.update_connections(m, list(range(cur - 15, cur + 15))))
+    print("device update_connections(1 key frame):   %.3f ms" % front1)
+    print("device update_connections(30 key frames): %.3f ms" % front30)
+    _probe_bird(p, G, cur, timed, front1, front30)
     print("device keyframe_culling:                  %.3f ms" % timed(lambda: G.keyframe_culling(m, cur)))
     from .covis import DeviceTables
     t = DeviceTables(dict(p, **window_tables(p, 7)))
@@ -520,6 +523,42 @@ def _probe():
     G.close()
     _probe_points(p, cur)
     _probe_host(p, cur)
+
+
+def probe_bird_tables(K, BS=256, step=40):
+    """Bird tables for the probe's K key frames: key frame j holds the BS points from j * step on, so it shares points with the
+    BS / step key frames on either side; the camera centres lie 0.8 m apart on a line."""
+    n_mpb = (K - 1) * step + BS
+    kf_mpb = (np.arange(K, dtype=np.int32)[:, None] * step + np.arange(BS, dtype=np.int32)[None, :]).astype(np.int32)
+    kf_ow = np.zeros((K, 3), np.float32)
+    kf_ow[:, 0] = 0.8 * np.arange(K)
+    return dict(kf_nb=np.full(K, BS, np.int32), kf_mpb=kf_mpb, mpb_bad=np.zeros(n_mpb, np.uint8), bobs_mpb=kf_mpb.reshape(-1).copy(),
+                bobs_kf=np.repeat(np.arange(K, dtype=np.int32), BS), bobs_idx=np.tile(np.arange(BS, dtype=np.int32), K), kf_ow=kf_ow)
+
+
+def _probe_bird(p, G, cur, timed, front1, front30):
+    """fb_covis_update_bird_connections_dev and fb_covis_local_bird_map_dev on the probe's key frames with bird tables added; the
+    front update_connections of the same run beside them for scale"""
+    from .covis import DeviceBirdTables
+    b = probe_bird_tables(p["K"])
+    T = DeviceBirdTables(dict(b, kf_order=p["kf_order"]))
+    G.reserve_local_bird_map(T.n_mpb, T.n_bobs)
+    print("bird tables: %d features per key frame, %d bird points, %d bird edges" % (T.BS, T.n_mpb, T.n_bobs))
+    batch = list(range(cur - 15, cur + 15))
+    print("device update_bird_connections(1 key frame):   %.3f ms   (front update_connections: %.3f ms)"
+          % (timed(lambda: G.update_bird_connections(T.map, T, [cur], None, 1)), front1))
+    print("device update_bird_connections(30 key frames): %.3f ms   (front update_connections: %.3f ms)"
+          % (timed(lambda: G.update_bird_connections(T.map, T, batch, None, 1)), front30))
+    t, a = G.local_bird_map_arrays(p["K"], T.n_mpb, kf_ow=b["kf_ow"])
+    before = list(range(cur - 1, cur - 9, -1))
+
+    def add():
+        t["d_local_kf_bird"][:len(before)] = G._dev(before)
+        t["d_n_local_kf_bird"][0] = len(before)
+        G.local_bird_map(T.map, T, a, cur)
+    ms = timed(add)
+    print("device local_bird_map (8 members + the new one, list reset included): %.3f ms   -> %d key frames, %d points"
+          % (ms, int(t["d_n_local_kf_bird"].cpu()[0]), int(t["d_n_local_mpb"].cpu()[0])))
 
 
 def local_map_frame(p, cur, n=2000):

@@ -9,6 +9,7 @@
 //   MapPoint::EraseObservation (its effect on later key frames)    src/MapPoint.cc:111-137
 //   the spanning tree and Tracking::UpdateLocalMap                  covis_tree.inc
 //   LoopClosing::CorrectLoop and the map update after the global BA  covis_correct.inc
+//   KeyFrame::UpdateBirdConnections and Map::UpdateLocalBirdMap      covis_bird.inc
 //
 // State: one dense row of uint16 per key frame, W[a][b] = weight (bits 0..14, 0 = no entry) | member of the ordered vector
 // (bit 15).  mvpOrderedConnectedKeyFrames is always "descending by (weight, kf_order)" over the members, so it is derived
@@ -412,6 +413,8 @@ struct fb_covis {
   int K = 0;
   void *block = nullptr;
   Gr G{};
+  void *bird_block = nullptr;   // the bird lists (covis_bird.inc), allocated by the first bird call
+  uint16_t *WB = nullptr;       // [K][K] mvpBirdConnectedKeyFrames in the format of W: weight | CV_MEMBER, members only
   uint8_t *scr = nullptr;
   ScratchState state{};   // what scr holds; written by the scratch_*() of covis_plan.h only
   int ensure() {
@@ -428,6 +431,25 @@ struct fb_covis {
     k_cv_tree_reset<<<(K + 255) / 256, 256>>>(G);
     FB_HIP(hipGetLastError());
     FB_HIP(hipDeviceSynchronize());   // creation is rare; orders the default stream's work before every other stream
+    return FB_OK;
+  }
+  int ensure_bird() {
+    FB_TRY(ensure());
+    if (bird_block) return FB_OK;
+    BirdGraphOff o;
+    const size_t total = plan_bird_graph(K, &o);
+    FB_HIP(hipMalloc(&bird_block, total));
+    WB = (uint16_t *)(static_cast<uint8_t *>(bird_block) + o.WB);
+    FB_HIP(hipMemset(bird_block, 0, total));
+    FB_HIP(hipDeviceSynchronize());   // as ensure(): rare, and ordered before every stream
+    return FB_OK;
+  }
+  // scratch of a call that keeps nothing and builds no index: behind the recorded index, which a later reuse_index still finds
+  int behind_index(size_t bytes, uint8_t **p) {
+    const size_t at = scratch_behind_index(state);
+    FB_TRY(need(at + bytes));
+    scratch_build_begins(state, at, false);
+    *p = scr + at;
     return FB_OK;
   }
   int need(size_t bytes) {
@@ -541,9 +563,10 @@ int fb_covis_create(int32_t max_keyframes, fb_covis **out) {
 
 int fb_covis_destroy(fb_covis *g) {
   if (!g) return FB_OK;
-  if (g->block || g->scr) {
+  if (g->block || g->scr || g->bird_block) {
     (void)hipDeviceSynchronize();
     if (g->block) (void)hipFree(g->block);
+    if (g->bird_block) (void)hipFree(g->bird_block);
     if (g->scr) (void)hipFree(g->scr);
     (void)hipGetLastError();
   }
@@ -557,6 +580,7 @@ int fb_covis_clear(fb_covis *g, void *stream) {
   hipStream_t s = fb::as_stream(stream);
   FB_HIP(hipMemsetAsync(g->G.W, 0, (size_t)g->K * g->K * 2, s));
   FB_HIP(hipMemsetAsync(g->G.err, 0, 4, s));
+  if (g->WB) FB_HIP(hipMemsetAsync(g->WB, 0, (size_t)g->K * g->K * 2, s));
   k_cv_tree_reset<<<(g->K + 255) / 256, 256, 0, s>>>(g->G);
   FB_HIP(hipGetLastError());
   return FB_OK;
@@ -770,3 +794,4 @@ int fb_covis_keyframe_culling(fb_covis *g, const fb_covis_map *H, int32_t cur_sl
 #include "covis_tree.inc"
 #include "covis_points.inc"
 #include "covis_correct.inc"
+#include "covis_bird.inc"

@@ -118,6 +118,24 @@ inline size_t plan_new_keyframe(size_t n_features, PnkOff *o) {
   return r.off;
 }
 
+// the bird lists of every key frame (mvpBirdConnectedKeyFrames and their weights), in the format of W: a block of its own,
+// allocated by the first bird call, so that plan_graph stays what a handle without the bird side pays
+struct BirdGraphOff { size_t WB; };
+inline size_t plan_bird_graph(size_t K, BirdGraphOff *o) {
+  Regions r;
+  o->WB = r.take(K * K * 2);
+  return r.off;
+}
+
+// fb_covis_local_bird_map_dev: the list after the push_front holds at most K + 1 members
+struct LbOff { size_t hdr, wlist, wnear, cnt, pos, eoff, plist, bsum; };
+inline size_t plan_local_bird_map(size_t K, size_t n_mpb, LbOff *o) {
+  Regions r;
+  o->hdr = r.take(256); o->wlist = r.take((K + 1) * 4); o->wnear = r.take(K + 1); o->cnt = r.take((K + 1) * 4);
+  o->pos = r.take(n_mpb * 4); o->eoff = r.take((n_mpb + 1) * 4); o->plist = r.take(n_mpb * 4); o->bsum = r.take(scan_tiles(n_mpb) * 4);
+  return r.off;
+}
+
 // ---- one call -------------------------------------------------------------------------------------------------------------
 struct CallPlan { size_t head, front, bird, tail, total; };   // where each part begins (an absent part is empty)
 inline CallPlan plan_call(size_t head_bytes, size_t front_bytes, size_t bird_bytes, size_t tail_bytes) {
@@ -143,6 +161,15 @@ inline CallPlan plan_local_map_call(size_t K, size_t n_mp, size_t n_obs, size_t 
   IndexOff io;
   LmOff lo;
   return plan_call(with_window ? plan_window(K, n_mp, 0, &wo) : 0, plan_index(n_mp, n_obs, n_q, K, &io), 0, plan_local_map(batch, K, n_mp, &lo));
+}
+
+// The bird calls (update_bird_connections, local_bird_map) behind whatever the scratch holds up to `behind` (the end of the
+// front index that a later reuse_index reads, or 0): [..behind][bird index][local bird map].  Neither call keeps anything
+// from one call to the next, so the two share the plan: the first uses the index only, the second the tail only.
+inline CallPlan plan_bird_call(size_t behind, size_t K, size_t n_mpb, size_t n_bobs) {
+  IndexOff io;
+  LbOff lo;
+  return plan_call(behind, 0, plan_index(n_mpb, n_bobs, 0, K, &io), plan_local_bird_map(K, n_mpb, &lo));
 }
 
 // ---- what the scratch holds -----------------------------------------------------------------------------------------------
@@ -199,6 +226,8 @@ inline void scratch_build_done(ScratchState &S, size_t at, size_t end, const fb_
 // The index is of arrays that are gone (a host-pointer call's staged copies) or were edited (process_new_keyframe,
 // map_point_culling): a later reuse_index rebuilds.
 inline void scratch_drop_index(ScratchState &S) { S.index_valid = false; }
+// where a call that keeps nothing puts its own arrays: behind the recorded index, so that a later reuse_index still finds it
+inline size_t scratch_behind_index(const ScratchState &S) { return S.index_valid ? S.index_end : 0; }
 inline void scratch_window_begins(ScratchState &S) { S.win_valid = false; }
 // every launch of the window call was enqueued without error
 inline void scratch_window_done(ScratchState &S, size_t head_bytes, int cap_kf) { S.win_valid = true; S.win_bytes = head_bytes; S.win_cap_kf = cap_kf; }

@@ -77,6 +77,23 @@ __global__ __launch_bounds__(CV_NT) void k_tree_children(Gr G, int slot, int32_t
   if (threadIdx.x == 0) *d_n = n;
 }
 
+// The nearest-earlier search of KeyFrame.cc:673-684 (and of UpdateBirdConnections, :453-465, :535-547): the key frame of
+// the map with the largest mnFrameId strictly between 0 and `mine`; -1 when nothing qualifies.  Every thread of the
+// workgroup calls it and gets the answer.
+__device__ __forceinline__ int nearest_earlier(const Gr &G, int mine, const int32_t *fid, const uint8_t *in_map, uint32_t *s_mx) {
+  const int tid = threadIdx.x, K = G.K;
+  uint32_t best = 0;
+  for (int i = tid; i < K; i += CV_NT)
+    if (in_map[i] && fid[i] > 0 && fid[i] < mine) best = max(best, (uint32_t)fid[i]);
+  best = block_max_u32(best, s_mx);
+  if (!best) return -1;
+  uint32_t r = 0;                                                   // strict > in set order: the smallest kf_order among equal ids
+  for (int i = tid; i < K; i += CV_NT)
+    if (in_map[i] && (uint32_t)fid[i] == best) r = max(r, (uint32_t)(4096 - G.rank[i]));
+  r = block_max_u32(r, s_mx);
+  return G.inv[4096 - r];
+}
+
 // KeyFrame.cc:665-690 for the queries of one update_connections batch, one after the other, by one workgroup
 __global__ __launch_bounds__(CV_NT) void k_tree_first(Gr G, int n_q, const int32_t *slots, const int32_t *n_counter, const int32_t *front,
                                                       int id0, int state4, const int32_t *fid, const uint8_t *in_map) {
@@ -93,18 +110,8 @@ __global__ __launch_bounds__(CV_NT) void k_tree_first(Gr G, int n_q, const int32
     }
     int t = f;
     if (state4 && fid[f] > fid[a]) {                                // :669-684
-      const int mine = fid[a];
-      uint32_t best = 0;
-      for (int i = tid; i < K; i += CV_NT)
-        if (in_map[i] && fid[i] > 0 && fid[i] < mine) best = max(best, (uint32_t)fid[i]);
-      best = block_max_u32(best, s_mx);
-      if (best) {                                                   // strict > in set order: the smallest kf_order among equal ids
-        uint32_t r = 0;
-        for (int i = tid; i < K; i += CV_NT)
-          if (in_map[i] && (uint32_t)fid[i] == best) r = max(r, (uint32_t)(4096 - G.rank[i]));
-        r = block_max_u32(r, s_mx);
-        t = G.inv[4096 - r];
-      }
+      const int near = nearest_earlier(G, fid[a], fid, in_map, s_mx);
+      if (near >= 0) t = near;
     }
     if (tid == 0) { st(&G.parent[a], (int32_t)t); st(&G.linked[a], (uint8_t)1); st(&G.first[a], (uint8_t)0); }
     group_sync();

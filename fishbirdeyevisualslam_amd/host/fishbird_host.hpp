@@ -761,7 +761,8 @@ class KeyFrameDatabase {
 // CovisibilityMap is what the graph reads of the caller's Map: per key frame N, mvpMapPoints and mvKeysUn[i].octave, per
 // map point isBad(), and every MapPoint::mObservations entry as one edge list (erase = obs_kf < 0).  The methods carry
 // the reference's names with the key frame's slot as first argument; each one is one call of fb_covis_* with host
-// pointers.  The spanning tree stays with the caller: UpdateConnections returns front() for it.
+// pointers.  UpdateConnections returns front() for the spanning tree's first connection; UpdateBirdConnections sets its
+// parents in the handle.
 struct CovisibilityMap {
   int maxKeyFrames, kpStride;
   std::vector<int32_t> kfN, kfMapPoints;            // [K], [K][kpStride] (-1 = NULL)
@@ -866,6 +867,26 @@ struct CovisibilityMap {
     for (int r = 0; r < nErased; r++) out.erased.push_back({rows[(size_t)r * 4], rows[(size_t)r * 4 + 1], rows[(size_t)r * 4 + 2], rows[(size_t)r * 4 + 3]});
     return out;
   }
+
+  // The bird block of Map::AddKeyFrame(pKF) (Map.cc:41-46) with Map::UpdateLocalBirdMap (:97-153): localKFbird (front first)
+  // is updated in place and localMapPointBirds is returned, in the std::set's order when mpbOrder ((uintptr_t)pMPB per bird
+  // point) is given, else in index order.  `tables` is WindowTables::view() with the bird side; the camera centres come
+  // from its kf_Tcw.
+  std::vector<int> UpdateLocalBirdMap(fb_covis *g, const fb_covis_kf_tables &tables, int pKF, std::vector<int> &localKFbird,
+                                      const std::vector<uint64_t> *mpbOrder = nullptr) const {
+    const fb_covis_map m = view();
+    fb_local_bird_map_args a;
+    memset(&a, 0, sizeof(a));
+    std::vector<int32_t> kfs((size_t)maxKeyFrames, -1), pts((size_t)tables.n_mpb + 1, -1);
+    int32_t nKf = (int32_t)std::min(localKFbird.size(), kfs.size()), nPts = 0, overflow = 0;
+    std::copy(localKFbird.begin(), localKFbird.begin() + nKf, kfs.begin());
+    a.new_slot = pKF; a.d_mpb_order = mpbOrder ? mpbOrder->data() : nullptr;
+    a.cap_kf = maxKeyFrames; a.d_local_kf_bird = kfs.data(); a.d_n_local_kf_bird = &nKf;
+    a.cap_mpb = tables.n_mpb; a.d_local_mpb = pts.data(); a.d_n_local_mpb = &nPts; a.d_overflow = &overflow;
+    check(fb_covis_local_bird_map(g, &m, &tables, &a));
+    localKFbird.assign(kfs.begin(), kfs.begin() + nKf);
+    return std::vector<int>(pts.begin(), pts.begin() + nPts);
+  }
 };
 
 class CovisibilityGraph {
@@ -887,6 +908,32 @@ class CovisibilityGraph {
     return r;
   }
   Updated UpdateConnections(const CovisibilityMap &map, int slot) { return UpdateConnections(map, std::vector<int>(1, slot))[0]; }
+  struct BirdUpdated { int nBirdCounter, front; };  // the bird KFcounter.size(), mvpBirdConnectedKeyFrames.front() (-1 = empty)
+  // pKF->UpdateBirdConnections(nowState) for each listed key frame (KeyFrame.cc:418-562), as UpdateConnections calls it: with
+  // `front` (the result of UpdateConnections for the same slots) a key frame whose front counter was empty acts only when
+  // nowState >= 3 (:608-609); NULL = every key frame acts.  `tables` is WindowTables::view() with the bird side; kfFrameId
+  // (mnFrameId) and kfInMap (the key frame is in mpMap) are read when nowState >= 3.  The parents it sets are in the
+  // handle's tree (fb_covis_tree_get).
+  std::vector<BirdUpdated> UpdateBirdConnections(const CovisibilityMap &map, const fb_covis_kf_tables &tables, const std::vector<int> &slots,
+                                                 const std::vector<Updated> *front, int nowState, int id0Slot,
+                                                 const std::vector<int32_t> &kfFrameId, const std::vector<uint8_t> &kfInMap) {
+    const fb_covis_map m = map.view();
+    std::vector<int32_t> nc(slots.size()), n(slots.size()), f(slots.size());
+    if (front) for (size_t i = 0; i < slots.size(); i++) nc[i] = (*front)[i].nCounter;
+    check(fb_covis_update_bird_connections(g_, &m, &tables, (int32_t)slots.size(), slots.data(), front ? nc.data() : nullptr, nowState, id0Slot,
+                                           kfFrameId.empty() ? nullptr : kfFrameId.data(), kfInMap.empty() ? nullptr : kfInMap.data(),
+                                           n.data(), f.data()));
+    std::vector<BirdUpdated> r(slots.size());
+    for (size_t i = 0; i < r.size(); i++) r[i] = {n[i], f[i]};
+    return r;
+  }
+  std::vector<int> GetBirdConnectedBirdKeyFrames(int slot, std::vector<int> *weights = nullptr) {
+    int32_t n = 0;
+    std::vector<int32_t> s(K_), w(K_);
+    check(fb_covis_bird_connected(g_, slot, &n, s.data(), w.data()));
+    if (weights) weights->assign(w.begin(), w.begin() + n);
+    return std::vector<int>(s.begin(), s.begin() + n);
+  }
   void AddConnection(int slot, int pKF, int weight) { check(fb_covis_add_connection_dev(g_, slot, pKF, weight, nullptr)); }
   void EraseConnection(int slot, int pKF) { check(fb_covis_erase_connection_dev(g_, slot, pKF, nullptr)); }
   void SetBadFlag(int slot) { check(fb_covis_erase_keyframe_dev(g_, slot, nullptr)); }   // the graph part (:797-798, :807-808)

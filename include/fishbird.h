@@ -1100,7 +1100,8 @@ int fb_covis_error_count(fb_covis *g, int32_t *count, void *stream);
  * its ordered list are the entries >= FB_COVIS_TH, or pKFmax alone (the smallest kf_order among the maxima, :627-643);
  * every member b gets AddConnection(a, w).  An empty counter changes nothing (:604-612).  d_n_counter[q] =
  * KFcounter.size(), d_front[q] = mvpOrderedConnectedKeyFrames.front() afterwards (-1: the vector is empty).  The spanning
- * tree (mpParent, mbFirstConnection) follows with fb_covis_first_connection_dev; UpdateBirdConnections is not restated. */
+ * tree (mpParent, mbFirstConnection) follows with fb_covis_first_connection_dev, and the UpdateBirdConnections that ends
+ * the function (:701, :608-609) with fb_covis_update_bird_connections_dev on the same batch.                            */
 int fb_covis_update_connections_dev(fb_covis *g, const fb_covis_map *map, int32_t n_q, const int32_t *d_slots,
                                     int32_t *d_n_counter, int32_t *d_front, void *stream);
 int fb_covis_update_connections(fb_covis *g, const fb_covis_map *map, int32_t n_q, const int32_t *slots, int32_t *n_counter,
@@ -1248,7 +1249,8 @@ int fb_covis_window_scatter_dev(fb_covis *g, const fb_covis_map *map, const fb_c
 int fb_covis_tree_set_dev(fb_covis *g, const int32_t *d_parent, const uint8_t *d_linked, const uint8_t *d_first, void *stream);
 int fb_covis_tree_get_dev(fb_covis *g, int32_t *d_parent, uint8_t *d_linked, uint8_t *d_first, void *stream);
 int fb_covis_tree_get(fb_covis *g, int32_t *parent, uint8_t *linked, uint8_t *first); /* host pointers; synchronises     */
-/* slot->ChangeParent(parent) (:724-729).  Also how the host mirrors the parents UpdateBirdConnections sets (:470-556).  */
+/* slot->ChangeParent(parent) (:724-729).  (The parents UpdateBirdConnections sets, :468-556, are set on the device by
+ * fb_covis_update_bird_connections_dev.)                                                                                */
 int fb_covis_change_parent_dev(fb_covis *g, int32_t slot, int32_t parent, void *stream);
 /* parent->EraseChild(slot) (:718-722): linked is cleared only if parent[slot] == parent                                 */
 int fb_covis_erase_child_dev(fb_covis *g, int32_t parent, int32_t slot, void *stream);
@@ -1328,6 +1330,83 @@ int fb_covis_local_map(fb_covis *g, const fb_covis_map *map, const fb_local_map_
  * reused, with_window != 0 sizes the head for a fb_covis_local_window_dev on the same map (front side).  If the scratch
  * has to grow, the index is lost and reuse_index = 1 rebuilds it once.                                                  */
 int fb_covis_reserve_local_map(fb_covis *g, int32_t n_mp, int32_t n_obs, int32_t n_q, int32_t batch, int32_t with_window);
+
+/* ---- the bird side of the graph: KeyFrame::UpdateBirdConnections (KeyFrame.cc:418-562) ---------------------------------
+ * mvpBirdConnectedKeyFrames of every key frame, kept by the handle in the front rows' format (descending by (weight,
+ * kf_order), derived on read); fb_covis_clear empties it, fb_covis_erase_keyframe_dev leaves it alone (SetBadFlag never
+ * edits another key frame's bird list).  Of `map` only max_keyframes and kf_order are read; of `tables` kf_nb, kf_mpb,
+ * mpb_bad and the bird edge list (one live edge per (point, key frame) pair, as for the front list).                    */
+#define FB_COVIS_BIRD_TH 2        /* th of KeyFrame::UpdateBirdConnections (KeyFrame.cc:483); there is no pKFmax fallback */
+/* UpdateBirdConnections(now_state) for the n_q key frames d_slots[0..n_q), with the result of calling them one after
+ * another in list order (no other key frame's list is written, so the queries are independent).  Query q acts iff
+ * d_n_counter[q] != 0 (the call that ends UpdateConnections, :701; d_n_counter is the output of the front call on the same
+ * batch, NULL = every query acts) or now_state >= 3 (the empty-counter exit, :608-609); one that does not act writes
+ * d_n_bird_counter[q] = 0 and d_bird_front[q] = the front of its unchanged list and nothing else.
+ * Counter (:424-445): every feature i < kf_nb with a point that is not bad, every live bird edge of that point whose key
+ * frame is not the slot itself; a point held at two features counts twice; the observer's isBad is not tested.
+ * d_n_bird_counter[q] = KFcounter.size().
+ * Empty counter (:447-480): the list stays; if now_state >= 3 and parent == -1 the nearest-earlier key frame becomes the
+ * parent (:453-476): d_kf_in_map != 0, the largest frame id with 0 < id < this key frame's, the smaller kf_order among
+ * equal ids (the rule of fb_covis_first_connection_dev); linked = 1, first = 0.  Where nothing qualifies the reference
+ * dereferences an uninitialised pointer: nothing is done and the error counter goes up.
+ * Otherwise (:483-559) the entries >= FB_COVIS_BIRD_TH, descending by (weight, kf_order), replace the list (also when there
+ * are none); then, if parent == -1 or first != 0, and the slot is not id0_slot (mnId == 0, :516; -1 = none): parent = the
+ * list's front when it has one, else the nearest-earlier key frame when now_state >= 3 (same rule); linked = 1, first = 0.
+ * A slot whose parent is set while first != 0 gets the new parent in its place (the state holds one parent per slot).
+ * d_bird_front[q] = mvpBirdConnectedKeyFrames.front() afterwards, -1 = empty.  d_kf_frame_id [max_keyframes] int32 and
+ * d_kf_in_map [max_keyframes] uint8 may be NULL when now_state < 3.  mvOrderedWeights, which :512 overwrites with the bird
+ * weights, is NOT touched: fb_covis_ordered / fb_covis_by_weight keep the front's weights.  Out-of-range entries and query
+ * slots are skipped and counted.  Every call builds the bird edge index anew (the call keeps none), so an out-of-range
+ * bird edge is counted once per CALL, not once per entry, like an out-of-range front edge by every front call that builds
+ * its index; an out-of-range kf_mpb entry is counted once per acting query that walks it.  Scratch: behind the handle's index, see fb_covis_reserve_local_bird_map; the front
+ * index a later reuse_index reads stays valid unless the scratch has to grow.  Enqueues only.                          */
+int fb_covis_update_bird_connections_dev(fb_covis *g, const fb_covis_map *map, const fb_covis_kf_tables *tables, int32_t n_q,
+                                         const int32_t *d_slots, const int32_t *d_n_counter, int32_t now_state,
+                                         int32_t id0_slot, const int32_t *d_kf_frame_id, const uint8_t *d_kf_in_map,
+                                         int32_t *d_n_bird_counter, int32_t *d_bird_front, void *stream);
+int fb_covis_update_bird_connections(fb_covis *g, const fb_covis_map *map, const fb_covis_kf_tables *tables, int32_t n_q,
+                                     const int32_t *slots, const int32_t *n_counter, int32_t now_state, int32_t id0_slot,
+                                     const int32_t *kf_frame_id, const uint8_t *kf_in_map, int32_t *n_bird_counter,
+                                     int32_t *bird_front); /* host pointers, the tables' arrays included */
+/* GetBirdConnectedBirdKeyFrames() and the bird weights (d_weights may be NULL); arrays of max_keyframes entries, entries
+ * past *d_n are left as they are                                                                                        */
+int fb_covis_bird_connected_dev(fb_covis *g, int32_t slot, int32_t *d_n, int32_t *d_slots, int32_t *d_weights, void *stream);
+int fb_covis_bird_connected(fb_covis *g, int32_t slot, int32_t *n, int32_t *slots, int32_t *weights);
+
+/* ---- the local bird map: the bird block of Map::AddKeyFrame (Map.cc:41-46) and Map::UpdateLocalBirdMap (:97-153) ----------
+ * The list after the push_front has new_slot at position 0.  Member j is near iff !(dis > 5) (:104-106), dis =
+ * cv::norm(refTw - curTw, NORM_L2) of CV_32F: per component d = (double)(float)(ow[j] - ow[new]), dis = sqrt(d0 * d0 +
+ * d1 * d1 + d2 * d2) in double, summed in that order.  The first holder of a bird point is the smallest position among the
+ * near members that hold it in kf_mpb (only -1 is skipped; mpb_bad is not tested, :117); pMP_sum[j] = the distinct points
+ * whose first holder is j; member j stays iff it is near and pMP_sum[j] >= 10 (:127), in the order it had.  The local
+ * points are those held by ANY near member, the ones dropped for pMP_sum < 10 included (:120-128 inserts before the
+ * test), in ascending d_mpb_order (the std::set's order).  Of `map` only max_keyframes is used; of `tables` kf_nb, kf_mpb,
+ * n_mpb and, when d_kf_ow is NULL, kf_Tcw.                                                                                */
+typedef struct fb_local_bird_map_args {
+  int32_t new_slot;              /* pKF of AddKeyFrame: push_front, curTw = its camera centre (:43-44)                     */
+  const float *d_kf_ow;          /* [max_keyframes][3] KeyFrame::GetCameraCenter() (:103); NULL: -Rcw^T tcw of
+                                    tables->kf_Tcw, products and sum in double, as UpdateNormalAndDepth derives it         */
+  const uint64_t *d_mpb_order;   /* [n_mpb] (uintptr_t)pMPB, the order of setlocalMapPointBirds (:99, :135); NULL: index   */
+  int32_t cap_kf;                /* 1 .. max_keyframes                                                                     */
+  int32_t *d_local_kf_bird;      /* [cap_kf] in/out: localKFbird, front first (:43, :108, :128)                            */
+  int32_t *d_n_local_kf_bird;    /* [1] in/out                                                                             */
+  int32_t cap_mpb;
+  int32_t *d_local_mpb;          /* [cap_mpb] out: localMapPointBirds (:134-143) = fb_track_args.d_local_mpb               */
+  int32_t *d_n_local_mpb;        /* [1] out, at most cap_mpb           = fb_track_args.d_n_local_mpb                       */
+  int32_t *d_overflow;           /* [1] != 0: a result was longer than its capacity; what fitted is its prefix             */
+} fb_local_bird_map_args;
+/* An incoming list longer than cap_kf is read up to cap_kf; a member outside the slots is dropped and counted, as is a
+ * kf_mpb entry >= n_mpb.  The `> 10` gate of Tracking::GetLocalMapForBird (Tracking.cc:2004) stays with the consumer
+ * (fb_frame_track_dev).  The points are ranked among themselves by d_mpb_order: work quadratic in the local points, not
+ * in the map.  Enqueues only.                                                                                           */
+int fb_covis_local_bird_map_dev(fb_covis *g, const fb_covis_map *map, const fb_covis_kf_tables *tables,
+                                const fb_local_bird_map_args *a, void *stream);
+int fb_covis_local_bird_map(fb_covis *g, const fb_covis_map *map, const fb_covis_kf_tables *tables,
+                            const fb_local_bird_map_args *a); /* host pointers throughout */
+/* Scratch for the two bird calls ahead of time: a bird edge index of (n_mpb, n_bobs) and the local bird map's arrays,
+ * BEHIND the index the handle holds at the time of the call (so call it after the front calls' reserve and first use; a
+ * later growth loses that index once, as for fb_covis_reserve_local_map).  Also allocates the bird lists.               */
+int fb_covis_reserve_local_bird_map(fb_covis *g, int32_t n_mpb, int32_t n_bobs);
 
 /* ---- map correction: LoopClosing::CorrectLoop (LoopClosing.cc:438-541) and the map update that ends
  * LoopClosing::RunGlobalBundleAdjustment (:714-825), on fb_covis_map / fb_covis_kf_tables ---------------------------------
