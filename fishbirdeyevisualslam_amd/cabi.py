@@ -326,7 +326,7 @@ class LocalBirdMapArgs(C.Structure):
 class CorrectLoopArgs(C.Structure):
     _fields_ = [("q", C.c_double * 4), ("t", C.c_double * 3), ("s", C.c_double), ("cur_slot", _i32), ("reuse_index", _i32),
                 ("scale_factors", _vp), ("mp_ref_kf", _vp), ("mp_normal", _vp), ("mp_min_dist", _vp), ("mp_max_dist", _vp),
-                ("d_mp_corrected_ref", _vp), ("d_n_set", _vp), ("d_set_slots", _vp)]
+                ("d_mp_corrected_ref", _vp), ("d_n_set", _vp), ("d_set_slots", _vp), ("d_set_Scw", _vp)]
 
 
 class PropagateGbaArgs(C.Structure):
@@ -353,6 +353,29 @@ class MapPointCullingArgs(C.Structure):
     _fields_ = [("cur_kf_id", _i32), ("n_th_obs", _i32), ("mp_first_kf_id", _vp), ("mp_found", _vp), ("mp_visible", _vp),
                 ("recent_cap", _i32), ("d_recent", _vp), ("d_n_recent", _vp), ("kf_mp", _vp), ("mp_bad", _vp), ("obs_kf", _vp),
                 ("d_n_culled", _vp), ("d_culled", _vp), ("d_n_erased", _vp), ("erased_cap", _i32), ("d_erased", _vp)]
+
+
+class PointFuseArrays(C.Structure):
+    _fields_ = [("kf_mp", _vp), ("mp_bad", _vp), ("obs_mp", _vp), ("obs_kf", _vp), ("mp_found", _vp), ("mp_visible", _vp),
+                ("mp_replaced", _vp), ("kf_bad", _vp), ("kf_desc", _vp), ("mp_desc", _vp), ("d_n_replaced", _vp), ("replaced_cap", _i32),
+                ("d_replaced", _vp)]
+
+
+class ReplacePointsArgs(C.Structure):
+    _fields_ = [("n_pairs", _i32), ("d_n_pairs", _vp), ("d_from", _vp), ("d_to", _vp), ("map", PointFuseArrays)]
+
+
+class LoopFuseArgs(C.Structure):
+    _fields_ = [("cur_slot", _i32), ("n_features", _i32), ("d_matched", _vp), ("obs_cap", _i32), ("obs_idx", _vp), ("d_n_added", _vp),
+                ("added_cap", _i32), ("d_added", _vp), ("map", PointFuseArrays)]
+
+
+class SearchAndFuseArgs(C.Structure):
+    _fields_ = [("n_set", _i32), ("d_set_slots", _vp), ("d_set_Scw", _vp), ("n_loop", _i32), ("d_loop_mp", _vp), ("th", _f32),
+                ("cam", Camera), ("grid", GridGeom), ("scale_factors", _f32 * FB_MAX_LEVELS), ("inv_level_sigma2", _f32 * FB_MAX_LEVELS),
+                ("log_scale_factor", _f32), ("n_levels", _i32), ("kf_keys_un", _vp), ("mp_xw", _vp), ("mp_normal", _vp),
+                ("mp_min_dist", _vp), ("mp_max_dist", _vp), ("obs_cap", _i32), ("obs_idx", _vp), ("d_n_fused", _vp), ("d_n_added", _vp),
+                ("added_cap", _i32), ("d_added", _vp), ("map", PointFuseArrays)]
 
 
 class BirdFilterArgs(C.Structure):
@@ -498,6 +521,9 @@ EXPORTS = [
     "fb_covis_refresh_points_dev", "fb_covis_refresh_points", "fb_covis_reserve_refresh_points",
     "fb_covis_process_new_keyframe_dev", "fb_covis_process_new_keyframe", "fb_covis_reserve_process_new_keyframe",
     "fb_covis_map_point_culling_dev", "fb_covis_map_point_culling", "fb_covis_reserve_map_point_culling",
+    "fb_covis_replace_points_dev", "fb_covis_replace_points", "fb_covis_reserve_replace_points",
+    "fb_covis_loop_fuse_dev", "fb_covis_loop_fuse", "fb_covis_reserve_loop_fuse",
+    "fb_covis_search_and_fuse_dev", "fb_covis_search_and_fuse", "fb_covis_reserve_search_and_fuse",
     "fb_in_frustum_dev", "fb_in_frustum", "fb_undistort_keypoints_dev", "fb_undistort_keypoints", "fb_image_bounds",
     "fb_pose_opt_batch_dev", "fb_pose_opt", "fb_pose_gather_front_dev", "fb_pose_gather_bird_dev",
     "fb_frame_tail_front_dev", "fb_frame_tail_bird_dev",

@@ -349,14 +349,17 @@ class CovisibilityGraph:
             out[:n] = self._dev(x, dtype).reshape(-1)
         return out
 
-    def correct_loop_arrays(self, m, scale_factors, mp_ref_kf, mp_normal, mp_min_dist, mp_max_dist):
-        """Device arrays of a fb_correct_loop_args for the map m: the in/out MapPoint members and the outputs.
+    def correct_loop_arrays(self, m, scale_factors, mp_ref_kf, mp_normal, mp_min_dist, mp_max_dist, with_set_scw=False, guard=0):
+        """Device arrays of a fb_correct_loop_args for the map m: the in/out MapPoint members and the outputs; with_set_scw:
+        also d_set_Scw [K][12] (the corrected Sim3 of every set member for SearchAndFuse), followed by `guard` floats.
         -> (dict of tensors, cabi.CorrectLoopArgs)"""
         n = m.n_mp
         t = dict(scale_factors=self._dev(scale_factors, torch.float32).reshape(-1), mp_ref_kf=self._filled(mp_ref_kf, torch.int32, n, -1),
                  mp_normal=self._filled(mp_normal, torch.float32, 3 * n), mp_min_dist=self._filled(mp_min_dist, torch.float32, n),
                  mp_max_dist=self._filled(mp_max_dist, torch.float32, n), d_mp_corrected_ref=self._i32(n, -1), d_n_set=self._i32(1),
                  d_set_slots=self._i32(self.K, -1))
+        if with_set_scw:
+            t["d_set_Scw"] = torch.full((12 * self.K + guard,), 7.0, dtype=torch.float32, device=self.device)
         a = cabi.CorrectLoopArgs()
         cabi.fill(a, reuse_index=0, **t)
         return t, a
@@ -465,6 +468,92 @@ class CovisibilityGraph:
         check(lib().fb_covis_map_point_culling_dev(self.h, C.byref(m.c), C.byref(a), _stream()), "fb_covis_map_point_culling_dev")
         self._keep = (m, a, t, recent, n_recent, out)
         return out
+
+    # ---- MapPoint::Replace and the loop fusion of CorrectLoop ---------------------------------------------------------------------
+    def reserve_replace_points(self, n_mp, n_obs, n_q=0):
+        check(lib().fb_covis_reserve_replace_points(self.h, int(n_mp), int(n_obs), int(n_q)), "fb_covis_reserve_replace_points")
+
+    def reserve_loop_fuse(self, n_mp, n_obs, n_features, n_q=0):
+        check(lib().fb_covis_reserve_loop_fuse(self.h, int(n_mp), int(n_obs), int(n_q), int(n_features)), "fb_covis_reserve_loop_fuse")
+
+    def point_fuse_arrays(self, m, kf_bad, kf_desc, mp_desc, mp_found, mp_visible, mp_replaced=None, replaced_cap=0, guard=0):
+        """Device arrays of a fb_point_fuse_arrays for the map m (kf_mp, mp_bad, obs_mp and obs_kf are m's own tensors); the
+        per-point in/out arrays and d_replaced are followed by `guard` rows the library never sees
+        -> (dict of tensors, cabi.PointFuseArrays)"""
+        n, K, S = m.n_mp, self.K, m.S
+
+        def padded(x, dtype, rows, width, fill):
+            out = torch.full(((max(rows, 1) + guard) * width,), fill, dtype=dtype, device=self.device)
+            if x is not None and rows:
+                out[:rows * width] = self._dev(x, dtype).reshape(-1)
+            return out
+        t = dict(kf_bad=self._filled(kf_bad, torch.uint8, K), kf_desc=self._filled(kf_desc, torch.uint8, 32 * K * S),
+                 mp_desc=padded(mp_desc, torch.uint8, n, 32, 0xEE), mp_found=padded(mp_found, torch.int32, n, 1, -5),
+                 mp_visible=padded(mp_visible, torch.int32, n, 1, -5),
+                 mp_replaced=padded(np.full(n, -1, np.int32) if mp_replaced is None else mp_replaced, torch.int32, n, 1, -5),
+                 d_n_replaced=self._i32(1, -1), d_replaced=padded(None, torch.int32, int(replaced_cap), 2, -5))
+        a = cabi.PointFuseArrays()
+        cabi.fill(a, kf_mp=m.t["kf_mp"], mp_bad=m.t["mp_bad"], obs_mp=m.t["obs_mp"], obs_kf=m.t["obs_kf"], replaced_cap=int(replaced_cap), **t)
+        return t, a
+
+    def replace_points(self, m, fuse, pairs_from, pairs_to, n_pairs=None):
+        """from[i]->Replace(to[i]) (MapPoint.cc:177-215) for the listed pairs, one after another, on m and the arrays of
+        point_fuse_arrays; from[i] < 0 is skipped; n_pairs: a device int32[1] that holds the list's length.  The rows that
+        took effect land in fuse's d_replaced / d_n_replaced.  Enqueues only."""
+        f, t = self._dev(pairs_from).reshape(-1), self._dev(pairs_to).reshape(-1)
+        assert f.numel() == t.numel()
+        n = int(f.numel())
+        if n == 0:
+            f, t = self._i32(1, -1), self._i32(1, -1)
+        a = cabi.ReplacePointsArgs()
+        cabi.fill(a, n_pairs=n, d_n_pairs=n_pairs, d_from=f, d_to=t)
+        a.map = fuse
+        check(lib().fb_covis_replace_points_dev(self.h, C.byref(m.c), C.byref(a), _stream()), "fb_covis_replace_points_dev")
+        self._keep = (m, a, fuse, f, t, n_pairs)
+
+    def loop_fuse(self, m, fuse, cur_slot, matched, added_cap=None, guard=0):
+        """The loop fusion of LoopClosing::CorrectLoop (:545-560) for the key frame in cur_slot of m (a DeviceMap with obs_spare)
+        and mvpCurrentMatchedPoints as point indices (-1 = NULL) -> (d_n_added int32[1], d_added [added_cap][4] rows of
+        key frame slot, point, feature, edge).  The edge list of m is len(matched) longer afterwards (m.grow).  Enqueues only."""
+        mt = self._dev(matched).reshape(-1)
+        nf = int(mt.numel())
+        cap = nf if added_cap is None else int(added_cap)
+        n_added = self._i32(1, -1)
+        added = torch.full(((max(cap, 1) + guard) * 4,), -5, dtype=torch.int32, device=self.device)
+        a = cabi.LoopFuseArgs()
+        cabi.fill(a, cur_slot=int(cur_slot), n_features=nf, d_matched=mt if nf else self._i32(1, -1), obs_cap=int(m.obs_cap),
+                  obs_idx=m.t["obs_idx"], d_n_added=n_added, added_cap=cap, d_added=added)
+        a.map = fuse
+        check(lib().fb_covis_loop_fuse_dev(self.h, C.byref(m.c), C.byref(a), _stream()), "fb_covis_loop_fuse_dev")
+        m.grow(nf)
+        self._keep = (m, a, fuse, mt, n_added, added)
+        return n_added, added
+
+    def search_and_fuse(self, m, fuse, target, set_slots, set_scw, loop_mp, kf_keys_un, mp_xw, mp_normal, mp_min_dist, mp_max_dist, th=4.0,
+                        added_cap=None, guard=0):
+        """LoopClosing::SearchAndFuse (:616-642) for the key frames set_slots (a list or a device tensor, in the order given)
+        with their Scw rows set_scw [n_set][12] and mvpLoopMapPoints loop_mp as point indices; target: a cabi.KfTarget whose
+        cam, grid, scale tables and n_levels are read.  -> (d_n_fused [n_set], d_n_added [1], d_added rows).  The edge list
+        of m is n_set * kp_stride longer afterwards (m.grow).  Enqueues only."""
+        slots = self._dev(set_slots).reshape(-1)
+        n_set, n = int(slots.numel()), m.n_mp
+        lp = self._dev(loop_mp).reshape(-1)
+        n_loop = int(lp.numel())
+        kp = kf_keys_un if torch.is_tensor(kf_keys_un) else torch.from_numpy(np.ascontiguousarray(kf_keys_un).view(np.uint8).reshape(-1).copy()).to(self.device)
+        cap = n_set * m.S if added_cap is None else int(added_cap)
+        t = dict(d_set_slots=slots if n_set else self._i32(1), d_set_Scw=self._filled(set_scw, torch.float32, 12 * n_set),
+                 d_loop_mp=lp if n_loop else self._i32(1), kf_keys_un=kp, mp_xw=self._filled(mp_xw, torch.float32, 3 * n),
+                 mp_normal=self._filled(mp_normal, torch.float32, 3 * n), mp_min_dist=self._filled(mp_min_dist, torch.float32, n),
+                 mp_max_dist=self._filled(mp_max_dist, torch.float32, n), d_n_fused=self._i32(n_set + guard, -5), d_n_added=self._i32(1, -1),
+                 d_added=torch.full(((max(cap, 1) + guard) * 4,), -5, dtype=torch.int32, device=self.device))
+        a = cabi.SearchAndFuseArgs()
+        cabi.fill(a, n_set=n_set, n_loop=n_loop, th=float(th), log_scale_factor=target.log_scale_factor, n_levels=target.n_levels,
+                  obs_cap=int(m.obs_cap), obs_idx=m.t["obs_idx"], added_cap=cap, **t)
+        a.cam, a.grid, a.scale_factors, a.inv_level_sigma2, a.map = target.cam, target.grid, target.scale_factors, target.inv_level_sigma2, fuse
+        check(lib().fb_covis_search_and_fuse_dev(self.h, C.byref(m.c), C.byref(a), _stream()), "fb_covis_search_and_fuse_dev")
+        m.grow(n_set * m.S)
+        self._keep = (m, a, fuse, t)
+        return t["d_n_fused"], t["d_n_added"], t["d_added"]
 
     # ---- the bird side: UpdateBirdConnections and the local bird map ------------------------------------------------------------
     def reserve_local_bird_map(self, n_mpb, n_bobs):

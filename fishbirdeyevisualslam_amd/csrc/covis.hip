@@ -10,6 +10,7 @@
 //   the spanning tree and Tracking::UpdateLocalMap                  covis_tree.inc
 //   LoopClosing::CorrectLoop and the map update after the global BA  covis_correct.inc
 //   KeyFrame::UpdateBirdConnections and Map::UpdateLocalBirdMap      covis_bird.inc
+//   MapPoint::Replace and the loop fusion of CorrectLoop             covis_fuse.inc
 //
 // State: one dense row of uint16 per key frame, W[a][b] = weight (bits 0..14, 0 = no entry) | member of the ordered vector
 // (bit 15).  mvpOrderedConnectedKeyFrames is always "descending by (weight, kf_order)" over the members, so it is derived
@@ -793,5 +794,6 @@ int fb_covis_keyframe_culling(fb_covis *g, const fb_covis_map *H, int32_t cur_sl
 #include "covis_window.inc"
 #include "covis_tree.inc"
 #include "covis_points.inc"
+#include "covis_fuse.inc"
 #include "covis_correct.inc"
 #include "covis_bird.inc"

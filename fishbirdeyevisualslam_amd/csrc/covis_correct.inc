@@ -158,6 +158,13 @@ __global__ __launch_bounds__(CV_NT) void k_cl_set(Gr G, const float *kf_Tcw, fb_
     }
     E.inv_s = inv.s;
     fb::camera_centre(E.Tcw, E.ow_new);
+    if (A.d_set_Scw) {                                                  // Converter::toCvMat(CorrectedSim3): s * R | t, cast once
+      float *o = A.d_set_Scw + (size_t)p * 12;
+      for (int r = 0; r < 3; r++) {
+        for (int c = 0; c < 3; c++) o[r * 4 + c] = (float)(cor.s * R[r * 3 + c]);
+        o[r * 4 + 3] = (float)cor.t[r];
+      }
+    }
   }
 }
 
@@ -454,6 +461,7 @@ int fb_covis_correct_loop(fb_covis *g, const fb_covis_map *HM, const fb_covis_kf
   st.out(T.kf_Tcw, K * 48, true); st.out(T.mp_xw, n_mp * 12, true);
   st.out(A.mp_normal, n_mp * 12, true); st.out(A.mp_min_dist, n_mp * 4, true); st.out(A.mp_max_dist, n_mp * 4, true);
   st.out(A.d_mp_corrected_ref, n_mp * 4, false); st.out(A.d_n_set, 4, false); st.out(A.d_set_slots, K * 4, true);
+  st.out(A.d_set_Scw, K * 48, true);
   if (cl_has_bird(HT)) {
     T.bird_stride = HT->bird_stride; T.n_mpb = HT->n_mpb; T.kf_nb = HT->kf_nb; T.kf_mpb = HT->kf_mpb; T.mpb_bad = HT->mpb_bad;
     T.mpb_xw = HT->mpb_xw;

@@ -118,6 +118,27 @@ inline size_t plan_new_keyframe(size_t n_features, PnkOff *o) {
   return r.off;
 }
 
+// fb_covis_replace_points_dev / fb_covis_loop_fuse_dev: the log of the edges that changed owner or were added in this call.
+// head[mp] / next[e]: the edges a point gained, as a linked list; home[e]: obs_mp as it came in (the index's owner of e).
+struct FzOff { size_t head, next, home; };
+inline size_t plan_point_fuse(size_t n_mp, size_t n_obs, size_t n_new, FzOff *o) {
+  Regions r;
+  o->head = r.take(n_mp * 4); o->next = r.take((n_obs + n_new) * 4); o->home = r.take(n_obs * 4);
+  return r.off;
+}
+
+// fb_covis_search_and_fuse_dev, behind the log: one key frame's copy (key points, descriptors, N, Scw, grid) and the loop
+// points as the search's lists; used again for every key frame of the set
+struct SafOff { size_t mark, kps, kdesc, n_kf, n_list, pose, cell_start, cell_items, valid, xw, normal, mind, maxd, desc, best, rep; };
+inline size_t plan_search_and_fuse(size_t n_mp, size_t S, size_t n_loop, size_t cells, SafOff *o) {
+  Regions r;
+  o->mark = r.take(n_mp * 4); o->kps = r.take(S * 24); o->kdesc = r.take(S * 32); o->n_kf = r.take(4); o->n_list = r.take(4);
+  o->pose = r.take(48); o->cell_start = r.take((cells + 1) * 4); o->cell_items = r.take(S * 4); o->valid = r.take(n_loop);
+  o->xw = r.take(n_loop * 12); o->normal = r.take(n_loop * 12); o->mind = r.take(n_loop * 4); o->maxd = r.take(n_loop * 4);
+  o->desc = r.take(n_loop * 32); o->best = r.take(n_loop * 4); o->rep = r.take(n_loop * 4);
+  return r.off;
+}
+
 // the bird lists of every key frame (mvpBirdConnectedKeyFrames and their weights), in the format of W: a block of its own,
 // allocated by the first bird call, so that plan_graph stays what a handle without the bird side pays
 struct BirdGraphOff { size_t WB; };

@@ -62,6 +62,42 @@ __device__ __forceinline__ void pt_sort(KT *s_key, int n, int lane) {
   fb::bitonic_sort(s_key, n2, lane, 64);
 }
 
+// ComputeDistinctiveDescriptors (:261-307) of one point by one wave, from its n observers as sorted keys (rank << 15 | feature)
+// in s_key: the observers of key frames that are not bad (:265) are compacted in place in observer order as rows of kf_desc,
+// and the pick gives its 32 bytes to dst.  D: [PT_STAGE][32] of LDS.
+__device__ __forceinline__ void pt_descriptor(const uint8_t *kf_bad, const uint8_t *kf_desc, uint8_t *dst_row, const Gr &G, int S, uint32_t *s_key,
+                                              uint4 *D, int n, int lane) {
+  int N = 0;
+  for (int base = 0; base < n; base += 64) {
+    const int j = base + lane;
+    bool keep = false;
+    uint32_t row = 0;
+    if (j < n) {
+      const uint32_t key = s_key[j];
+      const int kf = G.inv[key >> 15];
+      keep = !kf_bad[kf];
+      row = (uint32_t)kf * (uint32_t)S + (key & PT_IDX);
+    }
+    const unsigned long long mask = __ballot(keep);
+    __syncthreads();                                                    // the chunk is read: the writes land at or before it
+    if (keep) s_key[N + __popcll(mask & ((1ull << lane) - 1ull))] = row;
+    N += __popcll(mask);
+  }
+  __syncthreads();
+  if (N == 0) return;                                                   // vDescriptors.empty()
+  uint4 *dst = reinterpret_cast<uint4 *>(dst_row);
+  if (N <= PT_STAGE) {
+    for (int t = lane; t < N * 2; t += 64) D[t] = reinterpret_cast<const uint4 *>(kf_desc + (size_t)s_key[t >> 1] * 32)[t & 1];
+    __syncthreads();
+    const int best = fb::distinctive_pick(lane, N, [&](int j) { return (const uint4 *)(D + j * 2); });
+    if (lane < 2) dst[lane] = D[best * 2 + lane];
+  } else {
+    auto at = [&](int j) { return reinterpret_cast<const uint4 *>(kf_desc + (size_t)s_key[j] * 32); };
+    const int best = fb::distinctive_pick(lane, N, at);
+    if (lane < 2) dst[lane] = at(best)[lane];
+  }
+}
+
 struct PtRun {
   fb_point_refresh_args A;
   const int32_t *list, *d_n;   // list == NULL: every point
@@ -138,36 +174,7 @@ __global__ __launch_bounds__(64) void k_pt_refresh(fb_covis_map M, Gr G, const i
   }
   if (!(A.what & FB_REFRESH_DESCRIPTOR)) return;
 
-  // the observers of key frames that are not bad (:265), compacted in place in observer order as rows of kf_desc
-  int N = 0;
-  for (int base = 0; base < n; base += 64) {
-    const int j = base + lane;
-    bool keep = false;
-    uint32_t row = 0;
-    if (j < n) {
-      const uint32_t key = s_key[j];
-      const int kf = G.inv[key >> 15];
-      keep = !A.kf_bad[kf];
-      row = (uint32_t)kf * (uint32_t)S + (key & PT_IDX);
-    }
-    const unsigned long long mask = __ballot(keep);
-    __syncthreads();                                                    // the chunk is read: the writes land at or before it
-    if (keep) s_key[N + __popcll(mask & ((1ull << lane) - 1ull))] = row;
-    N += __popcll(mask);
-  }
-  __syncthreads();
-  if (N == 0) return;                                                   // vDescriptors.empty()
-  uint4 *dst = reinterpret_cast<uint4 *>(A.mp_desc + (size_t)mp * 32);
-  if (N <= PT_STAGE) {
-    for (int t = lane; t < N * 2; t += 64) D[t] = reinterpret_cast<const uint4 *>(A.kf_desc + (size_t)s_key[t >> 1] * 32)[t & 1];
-    __syncthreads();
-    const int best = fb::distinctive_pick(lane, N, [&](int j) { return (const uint4 *)(D + j * 2); });
-    if (lane < 2) dst[lane] = D[best * 2 + lane];
-  } else {
-    auto at = [&](int j) { return reinterpret_cast<const uint4 *>(A.kf_desc + (size_t)s_key[j] * 32); };
-    const int best = fb::distinctive_pick(lane, N, at);
-    if (lane < 2) dst[lane] = at(best)[lane];
-  }
+  pt_descriptor(A.kf_bad, A.kf_desc, A.mp_desc + (size_t)mp * 32, G, S, s_key, D, n, lane);
 }
 
 // ---- ProcessNewKeyFrame ---------------------------------------------------------------------------------------------------

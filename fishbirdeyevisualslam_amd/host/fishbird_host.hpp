@@ -794,6 +794,7 @@ struct CovisibilityMap {
     std::vector<float> kfTcw, scaleFactors, mpXw, mpNormal, mpMinDist, mpMaxDist;   // [K][12], [levels], [points][3], [points][3], [points] x 2
     std::vector<uint8_t> kfBad, kfDesc, mpDesc;                                     // [K], [K][kpStride][32], [points][32]
     std::vector<int32_t> mpRefKF, mpFound, mpVisible, mpFirstKFid;                  // [points]
+    std::vector<int32_t> mpReplaced;                                                // [points] mpReplaced as a point index, -1 = NULL
     PointTables(const CovisibilityMap &m, int nLevels)
         : kfTcw((size_t)m.maxKeyFrames * 12, 0.f), scaleFactors(nLevels, 1.f), kfBad(m.maxKeyFrames, 0),
           kfDesc((size_t)m.maxKeyFrames * m.kpStride * 32, 0) {
@@ -802,7 +803,7 @@ struct CovisibilityMap {
     }
     void resize(size_t n) {   // after CovisibilityMap::NewMapPoint
       mpXw.resize(n * 3, 0.f); mpNormal.resize(n * 3, 0.f); mpMinDist.resize(n, 0.f); mpMaxDist.resize(n, 0.f); mpDesc.resize(n * 32, 0);
-      mpRefKF.resize(n, 0); mpFound.resize(n, 1); mpVisible.resize(n, 1); mpFirstKFid.resize(n, 0);
+      mpRefKF.resize(n, 0); mpFound.resize(n, 1); mpVisible.resize(n, 1); mpFirstKFid.resize(n, 0); mpReplaced.resize(n, -1);
     }
     fb_point_refresh_args view() {
       fb_point_refresh_args a;
@@ -868,6 +869,106 @@ struct CovisibilityMap {
     return out;
   }
 
+  // ---- MapPoint::Replace, the loop fusion and SearchAndFuse of LoopClosing (MapPoint.cc:177-215; LoopClosing.cc:545-560, :616-642) ----
+  struct Fused {
+    std::vector<std::pair<int, int> > replaced;       // (from, to) in execution order: mpMap->EraseMapPoint(from) for each
+    struct Row { int kf, point, idx, edge; };         // the new observations in execution order
+    std::vector<Row> added;
+    std::vector<int> nFused;                          // SearchAndFuse: the return value of each Fuse
+  };
+  // from[i]->Replace(to[i]) one after another; from[i] < 0 is skipped.  Edits kfMapPoints, mpBad, obsMp, obsKf, mpFound,
+  // mpVisible, mpReplaced and mpDesc.
+  Fused ReplacePoints(fb_covis *g, PointTables &t, const std::vector<int> &from, const std::vector<int> &to) {
+    Fused out;
+    if (from.empty() || from.size() != to.size()) return out;
+    const fb_covis_map m = view();
+    fb_replace_points_args a;
+    memset(&a, 0, sizeof(a));
+    int32_t nRep = 0;
+    std::vector<int32_t> rows(from.size() * 2, -1);
+    a.n_pairs = (int32_t)from.size(); a.d_from = from.data(); a.d_to = to.data();
+    a.map = fuseView(t, &nRep, rows);
+    check(fb_covis_replace_points(g, &m, &a));
+    for (int r = 0; r < nRep; r++) out.replaced.push_back(std::make_pair(rows[(size_t)r * 2], rows[(size_t)r * 2 + 1]));
+    return out;
+  }
+  // The loop fusion for mpCurrentKF = cur and mvpCurrentMatchedPoints as point indices (-1 = NULL; kfN[cur] entries).  The
+  // edge list grows by kfN[cur] entries, new edges first, then tombstones.
+  Fused LoopFuse(fb_covis *g, PointTables &t, int cur, const std::vector<int> &matched) {
+    Fused out;
+    const int N = kfN[cur];
+    if ((int)matched.size() != N) throw std::runtime_error("LoopFuse: matched.size() != kfN[cur]");
+    const int32_t n0 = (int32_t)obsKf.size();
+    obsMp.resize((size_t)n0 + N, -1); obsKf.resize((size_t)n0 + N, -1); obsIdx.resize((size_t)n0 + N, -1);
+    fb_covis_map m = view();
+    m.n_obs = n0;
+    fb_loop_fuse_args a;
+    memset(&a, 0, sizeof(a));
+    int32_t nRep = 0, nAdded = 0;
+    std::vector<int32_t> rows((size_t)N * 2 + 2, -1), added((size_t)N * 4 + 4, -1);
+    a.cur_slot = cur; a.n_features = N; a.d_matched = matched.data(); a.obs_cap = (int32_t)obsKf.size(); a.obs_idx = obsIdx.data();
+    a.d_n_added = &nAdded; a.added_cap = N; a.d_added = added.data();
+    a.map = fuseView(t, &nRep, rows);
+    check(fb_covis_loop_fuse(g, &m, &a));
+    collect(out, nRep, rows, nAdded, added);
+    return out;
+  }
+  // What Fuse reads of a key frame that is the same for all (KeyFrame.h members), and mvKeysUn by slot
+  struct FuseTarget {
+    fb_camera cam;
+    fb_grid_geom grid;
+    float scaleFactors[FB_MAX_LEVELS], invLevelSigma2[FB_MAX_LEVELS], logScaleFactor;
+    int nLevels;
+    std::vector<fb_keypoint> keysUn;                  // [K][kpStride]
+  };
+  // LoopClosing::SearchAndFuse: slots / Scw ([n][12], rows 0..2 of toCvMat(CorrectedSim3)) in the order of CorrectedPosesMap,
+  // loopPoints = mvpLoopMapPoints.  The edge list grows by slots.size() * kpStride entries.
+  Fused SearchAndFuse(fb_covis *g, PointTables &t, const FuseTarget &target, const std::vector<int> &slots, const std::vector<float> &Scw,
+                      const std::vector<int> &loopPoints, float th = 4.0f) {
+    Fused out;
+    const size_t nSet = slots.size(), grow = nSet * (size_t)kpStride;
+    if (nSet == 0) return out;
+    if (Scw.size() != nSet * 12) throw std::runtime_error("SearchAndFuse: Scw.size() != 12 * slots.size()");
+    const int32_t n0 = (int32_t)obsKf.size();
+    obsMp.resize((size_t)n0 + grow, -1); obsKf.resize((size_t)n0 + grow, -1); obsIdx.resize((size_t)n0 + grow, -1);
+    fb_covis_map m = view();
+    m.n_obs = n0;
+    fb_search_and_fuse_args a;
+    memset(&a, 0, sizeof(a));
+    int32_t nRep = 0, nAdded = 0;
+    std::vector<int32_t> rows(nSet * loopPoints.size() * 2 + 2, -1), added(grow * 4 + 4, -1), nFused(nSet, 0);
+    a.n_set = (int32_t)nSet; a.d_set_slots = slots.data(); a.d_set_Scw = Scw.data(); a.n_loop = (int32_t)loopPoints.size();
+    a.d_loop_mp = loopPoints.data(); a.th = th; a.cam = target.cam; a.grid = target.grid; a.log_scale_factor = target.logScaleFactor;
+    a.n_levels = target.nLevels; a.kf_keys_un = target.keysUn.data();
+    memcpy(a.scale_factors, target.scaleFactors, sizeof(a.scale_factors));
+    memcpy(a.inv_level_sigma2, target.invLevelSigma2, sizeof(a.inv_level_sigma2));
+    a.mp_xw = t.mpXw.data(); a.mp_normal = t.mpNormal.data(); a.mp_min_dist = t.mpMinDist.data(); a.mp_max_dist = t.mpMaxDist.data();
+    a.obs_cap = (int32_t)obsKf.size(); a.obs_idx = obsIdx.data(); a.d_n_fused = nFused.data(); a.d_n_added = &nAdded;
+    a.added_cap = (int32_t)grow; a.d_added = added.data();
+    a.map = fuseView(t, &nRep, rows);
+    check(fb_covis_search_and_fuse(g, &m, &a));
+    collect(out, nRep, rows, nAdded, added);
+    out.nFused.assign(nFused.begin(), nFused.end());
+    return out;
+  }
+
+ private:
+  fb_point_fuse_arrays fuseView(PointTables &t, int32_t *nRep, std::vector<int32_t> &rows) {
+    fb_point_fuse_arrays f;
+    memset(&f, 0, sizeof(f));
+    f.kf_mp = kfMapPoints.data(); f.mp_bad = mpBad.data(); f.obs_mp = obsMp.data(); f.obs_kf = obsKf.data();
+    f.mp_found = t.mpFound.data(); f.mp_visible = t.mpVisible.data(); f.mp_replaced = t.mpReplaced.data();
+    f.kf_bad = t.kfBad.data(); f.kf_desc = t.kfDesc.data(); f.mp_desc = t.mpDesc.data();
+    f.d_n_replaced = nRep; f.replaced_cap = (int32_t)(rows.size() / 2); f.d_replaced = rows.data();
+    return f;
+  }
+  static void collect(Fused &out, int nRep, const std::vector<int32_t> &rows, int nAdded, const std::vector<int32_t> &added) {
+    for (int r = 0; r < nRep && (size_t)r * 2 + 1 < rows.size(); r++) out.replaced.push_back(std::make_pair(rows[(size_t)r * 2], rows[(size_t)r * 2 + 1]));
+    for (int r = 0; r < nAdded && (size_t)r * 4 + 3 < added.size(); r++)
+      out.added.push_back({added[(size_t)r * 4], added[(size_t)r * 4 + 1], added[(size_t)r * 4 + 2], added[(size_t)r * 4 + 3]});
+  }
+
+ public:
   // The bird block of Map::AddKeyFrame(pKF) (Map.cc:41-46) with Map::UpdateLocalBirdMap (:97-153): localKFbird (front first)
   // is updated in place and localMapPointBirds is returned, in the std::set's order when mpbOrder ((uintptr_t)pMPB per bird
   // point) is given, else in index order.  `tables` is WindowTables::view() with the bird side; the camera centres come

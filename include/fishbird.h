@@ -1423,6 +1423,7 @@ typedef struct fb_correct_loop_args {
   int32_t *d_mp_corrected_ref;  /* [map.n_mp] mnCorrectedReference as a slot, -1: the point was not touched            */
   int32_t *d_n_set;             /* [1] mvpCurrentConnectedKFs.size()                                                   */
   int32_t *d_set_slots;         /* [max_keyframes] the set in ascending kf_order; entries past *d_n_set are left alone  */
+  float *d_set_Scw;             /* [max_keyframes][12] or NULL: the corrected Sim3 of each set member, see below        */
 } fb_correct_loop_args;
 /* Precondition: the graph row of cur_slot is current (the reference calls UpdateConnections on it at :435; the caller
  * does that with fb_covis_update_connections_dev).  Reads of tables: kf_Tcw, n_levels, mp_xw and, unless kf_mpb is NULL
@@ -1452,7 +1453,11 @@ typedef struct fb_correct_loop_args {
  * depend on no pose, so one batched call after this one equals the interleaved calls.
  * Out-of-range entries (kf_mp, kf_mpb, and for a moved point with a live edge mp_ref_kf and the octave, which then keeps
  * its normal and distances) are skipped and counted (fb_covis_error_count), never used as an index.
- * Not restated: the loop fusion (:545-560), SearchAndFuse, OptimizeEssentialGraph.  Enqueues only.                      */
+ * d_set_Scw, when not NULL: row k = rows 0..2 of Converter::toCvMat(CorrectedSim3[d_set_slots[k]]), s * R and t of the
+ * double Sim3, each cast to float once: the Scw that SearchAndFuse projects with.  It cannot be recovered afterwards (the
+ * poses are overwritten and hold [R | t / s] rounded).  NULL: not written, nothing else changes.
+ * Not restated: LoopConnections (:571-589), OptimizeEssentialGraph; the loop fusion (:545-560) is fb_covis_loop_fuse_dev,
+ * SearchAndFuse fb_covis_search_and_fuse_dev.  Enqueues only.                                                                              */
 int fb_covis_correct_loop_dev(fb_covis *g, const fb_covis_map *map, const fb_covis_kf_tables *tables,
                               const fb_correct_loop_args *a, void *stream);
 int fb_covis_correct_loop(fb_covis *g, const fb_covis_map *map, const fb_covis_kf_tables *tables,
@@ -1592,6 +1597,118 @@ typedef struct fb_map_point_culling_args {
 int fb_covis_map_point_culling_dev(fb_covis *g, const fb_covis_map *map, const fb_map_point_culling_args *a, void *stream);
 int fb_covis_map_point_culling(fb_covis *g, const fb_covis_map *map, const fb_map_point_culling_args *a); /* host pointers */
 int fb_covis_reserve_map_point_culling(fb_covis *g, int32_t n_mp, int32_t n_obs, int32_t n_q, int32_t recent_cap);
+
+/* ---- MapPoint::Replace (MapPoint.cc:177-215) and the loop fusion of LoopClosing::CorrectLoop (LoopClosing.cc:545-560) on
+ * fb_covis_map.  Integer and byte work throughout; the descriptor is the rule of fb_covis_refresh_points.               */
+typedef struct fb_point_fuse_arrays {
+  int32_t *kf_mp;               /* } the map's arrays, writable (the same pointers as in map)                          */
+  uint8_t *mp_bad;              /* }                                                                                   */
+  int32_t *obs_mp, *obs_kf;     /* }                                                                                   */
+  int32_t *mp_found;            /* [map.n_mp] in/out: mnFound                                                          */
+  int32_t *mp_visible;          /* [map.n_mp] in/out: mnVisible                                                        */
+  int32_t *mp_replaced;         /* [map.n_mp] in/out: mpReplaced as a point index, -1 = NULL                           */
+  const uint8_t *kf_bad;        /* [max_keyframes] KeyFrame::isBad()                                                   */
+  const uint8_t *kf_desc;       /* [max_keyframes][kp_stride][32] mDescriptors; 16-byte aligned                        */
+  uint8_t *mp_desc;             /* [map.n_mp][32] in/out: mDescriptor; 16-byte aligned                                 */
+  int32_t *d_n_replaced;        /* [1] rows wanted; rows past replaced_cap are not written                             */
+  int32_t replaced_cap;
+  int32_t *d_replaced;          /* [replaced_cap][2] the (from, to) pairs that took effect, in execution order (for
+                                   Map::EraseMapPoint and the host's objects)                                          */
+} fb_point_fuse_arrays;
+
+typedef struct fb_replace_points_args {
+  int32_t n_pairs;              /* the list's length, or its capacity when d_n_pairs is given                          */
+  const int32_t *d_n_pairs;     /* [1] the length on the device (clamped to n_pairs), or NULL                          */
+  const int32_t *d_from, *d_to; /* [n_pairs] from[i]->Replace(to[i]); from[i] < 0: skipped (a NULL of vpReplacePoints)  */
+  fb_point_fuse_arrays map;
+} fb_replace_points_args;
+/* The pairs applied one after another in list order, each exactly as MapPoint.cc:177-215.  from == to: nothing (mnId
+ * equality is index equality).  Otherwise the live edges of `from` are taken; mp_bad[from] = 1, mp_replaced[from] = to; for
+ * each taken edge (kf, idx): if `to` has no live edge to kf (IsInKeyFrame is decided by edges, not by kf_mp), kf_mp[kf][idx]
+ * = to and the edge becomes to's (obs_mp[e] = to in place), else kf_mp[kf][idx] = -1 and the edge becomes a tombstone
+ * (obs_kf[e] = -1); then found[to] += found[from], visible[to] += visible[from], and ComputeDistinctiveDescriptors(to) on
+ * the edited map at that moment, with the rule of fb_covis_refresh_points (a bad `to` and a `to` without a live edge keep
+ * their descriptor).  Neither point is tested for isBad: a `from` that an earlier pair replaced has no edges left, is
+ * marked again (mp_replaced takes the later `to`), adds its found / visible a second time and refreshes the second `to`.
+ * UpdateNormalAndDepth is not called: normal and distances stay.  The order in which one pair's edges are taken does not
+ * show, by the precondition that a (mp, kf) pair occurs once among the live edges.  A pair with an index outside [0, n_mp)
+ * (from < 0 apart) is skipped and counted, as is a pair one of whose points has more live edges than max_keyframes.
+ * One wave walks the list; the cost is the sum of the edges of the points named, not n_pairs * n_obs.  The handle's
+ * index is invalid afterwards.  Enqueues only.                                                                         */
+int fb_covis_replace_points_dev(fb_covis *g, const fb_covis_map *map, const fb_replace_points_args *a, void *stream);
+int fb_covis_replace_points(fb_covis *g, const fb_covis_map *map, const fb_replace_points_args *a); /* host pointers; d_n_pairs
+                                                                                                       must be NULL          */
+int fb_covis_reserve_replace_points(fb_covis *g, int32_t n_mp, int32_t n_obs, int32_t n_q);
+
+typedef struct fb_loop_fuse_args {
+  int32_t cur_slot;             /* mpCurrentKF                                                                         */
+  int32_t n_features;           /* its N as the host knows it (mvpCurrentMatchedPoints.size()); 0 .. kp_stride         */
+  const int32_t *d_matched;     /* [n_features] mvpCurrentMatchedPoints as point indices, -1 = NULL                    */
+  int32_t obs_cap;              /* capacity of the edge arrays; map.n_obs + n_features <= obs_cap (FB_ERR_CAPACITY)    */
+  int32_t *obs_idx;             /* the map's obs_idx, writable (the same pointer as in map)                            */
+  int32_t *d_n_added;           /* [1] the number of new edges                                                         */
+  int32_t added_cap;
+  int32_t *d_added;             /* [added_cap][4] the new edges as rows (key frame slot, point, feature, edge)         */
+  fb_point_fuse_arrays map;
+} fb_loop_fuse_args;
+/* For i = 0 .. n_features - 1 in order with matched[i] >= 0: if kf_mp[cur][i] >= 0 as it stands at that moment, it is
+ * Replace(kf_mp[cur][i] -> matched[i]) as above; else kf_mp[cur][i] = matched[i], AddObservation(matched[i], cur, i), which
+ * returns early when the point has a live edge to cur already (MapPoint.cc:101: kf_mp is written, no edge is), and
+ * ComputeDistinctiveDescriptors(matched[i]).  The same loop point at two features follows from that.
+ * The call owns the block [map.n_obs, map.n_obs + n_features) of the edge arrays, as fb_covis_process_new_keyframe_dev does:
+ * the new edges first, in ascending i, the rest tombstones; the caller goes on with n_obs + n_features.  If kf_n[cur] !=
+ * n_features the block is all tombstones, both counts are 0, nothing else is written and one error is counted.  An entry of
+ * matched or of kf_mp[cur] >= n_mp is skipped and counted.  The handle's index is invalid afterwards.  Enqueues only.    */
+int fb_covis_loop_fuse_dev(fb_covis *g, const fb_covis_map *map, const fb_loop_fuse_args *a, void *stream);
+int fb_covis_loop_fuse(fb_covis *g, const fb_covis_map *map, const fb_loop_fuse_args *a); /* host pointers */
+int fb_covis_reserve_loop_fuse(fb_covis *g, int32_t n_mp, int32_t n_obs, int32_t n_q, int32_t n_features);
+
+/* LoopClosing::SearchAndFuse (LoopClosing.cc:616-642) with ORBmatcher::Fuse(pKF, Scw, vpPoints, th, vpReplacePoint)
+ * (ORBmatcher.cc:978-1101) on fb_covis_map.                                                                             */
+typedef struct fb_search_and_fuse_args {
+  int32_t n_set;                /* key frames (a launch parameter, as for the batched UpdateConnections); 0 .. max_keyframes */
+  const int32_t *d_set_slots;   /* [n_set] processed in the order given (fb_covis_correct_loop writes ascending kf_order,
+                                   the order of the reference's std::map<KeyFrame*, g2o::Sim3>)                        */
+  const float *d_set_Scw;       /* [n_set][12] rows 0..2 of Converter::toCvMat(CorrectedSim3[slot])                    */
+  int32_t n_loop;
+  const int32_t *d_loop_mp;     /* [n_loop] mvpLoopMapPoints as point indices                                          */
+  float th;                     /* 4 at LoopClosing.cc:628; TH_LOW is the matcher's constant                           */
+  fb_camera cam;                /* } the key-frame side that is the same for every key frame, as in fb_kf_target       */
+  fb_grid_geom grid;            /* }                                                                                   */
+  float scale_factors[FB_MAX_LEVELS];
+  float inv_level_sigma2[FB_MAX_LEVELS];
+  float log_scale_factor;
+  int32_t n_levels;
+  const fb_keypoint *kf_keys_un; /* [max_keyframes][kp_stride] mvKeysUn by slot                                        */
+  const float *mp_xw;           /* [map.n_mp][3] } the MapPoint getters of the search                                  */
+  const float *mp_normal;       /* [map.n_mp][3] }                                                                     */
+  const float *mp_min_dist;     /* [map.n_mp]    }                                                                     */
+  const float *mp_max_dist;     /* [map.n_mp]    }                                                                     */
+  int32_t obs_cap;              /* capacity of the edge arrays; map.n_obs + n_set * kp_stride <= obs_cap (FB_ERR_CAPACITY) */
+  int32_t *obs_idx;             /* the map's obs_idx, writable (the same pointer as in map)                            */
+  int32_t *d_n_fused;           /* [n_set] nFused of each Fuse                                                         */
+  int32_t *d_n_added;           /* [1] new edges of the whole call                                                     */
+  int32_t added_cap;
+  int32_t *d_added;             /* [added_cap][4] rows (key frame slot, point, feature, edge) in execution order       */
+  fb_point_fuse_arrays map;     /* d_replaced: the pairs of the whole call in execution order                          */
+} fb_search_and_fuse_args;
+/* Per key frame k, in order, on the map as the key frame before left it:
+ *  1. valid[i] = !bad(loop[i]) && loop[i] is not among the non-bad entries of kf_mp[slot] (spAlreadyFound, taken once, :994);
+ *  2. fb_fuse_sim3_search_dev with batch = 1 on the descriptors and bad flags as they stand; the key frame's grid is built
+ *     by the call in scratch from kf_keys_un, the caller keeps none;
+ *  3. the commit, serial in i (:1083-1097), for best[i] >= 0: p = kf_mp[slot][best] as it stands, adds made earlier in this
+ *     loop included; p >= 0: rep[i] = p if p is not bad, else nothing; p < 0: AddObservation(loop[i], slot, best) with its
+ *     early return, and kf_mp[slot][best] = loop[i]; each counts in nFused.  Two loop points that win the same empty feature:
+ *     the first adds, the second gets rep = the first;
+ *  4. Replace(rep[i] -> loop[i]) for i ascending with rep[i] >= 0 (:633-640), as fb_covis_replace_points_dev.
+ * New edges: key frame k owns [map.n_obs + k * kp_stride, map.n_obs + (k + 1) * kp_stride) of the edge arrays, its new
+ * edges first in the order they were made, the rest tombstones; the caller goes on with n_obs + n_set * kp_stride.
+ * A slot, a loop point or a kf_mp entry out of range is skipped and counted.  No host wait between key frames: four
+ * launches each on one stream.  The handle's index is invalid afterwards.  Enqueues only.                              */
+int fb_covis_search_and_fuse_dev(fb_covis *g, const fb_covis_map *map, const fb_search_and_fuse_args *a, void *stream);
+int fb_covis_search_and_fuse(fb_covis *g, const fb_covis_map *map, const fb_search_and_fuse_args *a); /* host pointers */
+int fb_covis_reserve_search_and_fuse(fb_covis *g, int32_t n_mp, int32_t n_obs, int32_t n_q, int32_t kp_stride, int32_t n_set,
+                                     int32_t n_loop, int32_t grid_cells);
 
 /* ======================================================================== */
 /* Frame geometry either side of the matchers (src/Frame.cc)                 */
