@@ -1633,6 +1633,12 @@ typedef struct fb_replace_points_args {
  * UpdateNormalAndDepth is not called: normal and distances stay.  The order in which one pair's edges are taken does not
  * show, by the precondition that a (mp, kf) pair occurs once among the live edges.  A pair with an index outside [0, n_mp)
  * (from < 0 apart) is skipped and counted, as is a pair one of whose points has more live edges than max_keyframes.
+ * The overflow contract (a repeated (mp, kf) edge broke the precondition), for the three calls of this section: such a
+ * pair is skipped whole -- no entry of the map, of the per-point arrays or of d_replaced is written, d_n_replaced does not
+ * count it -- one error is counted, and the pairs after it run.  Where the loop fusion or step 3 of
+ * fb_covis_search_and_fuse meets such a point at an empty feature, the step is AddObservation's early return plus one
+ * error: kf_mp[kf][feature] = the point is written (and counts in nFused), no edge is made, no row of d_added, no
+ * descriptor refresh; the features after it run.  Exactly max_keyframes live edges is no overflow.
  * One wave walks the list; the cost is the sum of the edges of the points named, not n_pairs * n_obs.  The handle's
  * index is invalid afterwards.  Enqueues only.                                                                         */
 int fb_covis_replace_points_dev(fb_covis *g, const fb_covis_map *map, const fb_replace_points_args *a, void *stream);

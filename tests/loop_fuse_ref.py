@@ -27,7 +27,17 @@ class World(R.World):
         self.visible = np.array(c["mp_visible"], np.int32)
         self.replaced = np.array(c.get("mp_replaced", np.full(self.n_mp, -1)), np.int32)
         self.replaced_rows, self.added_rows = [], []
-        self.stats = dict(moved=0, dropped=0, early_return=0, again=0)
+        self.stats = dict(moved=0, dropped=0, early_return=0, again=0, came_home=0, to_bad=0, gained_only=0, new_edge_moved=0,
+                          prior_edge_moved=0, new_edge_seen=0, dropped_ranks=[])
+        self.home = self.obs_mp.copy()                                                                 # the owner of every edge at entry
+        self.new_base = self.new_here = None                                                           # search_and_fuse: the call's block / the key frame's
+
+    def rank(self, kf):
+        return sorted(range(self.K), key=self.key).index(kf)
+
+    def holds_prior_edge(self, mp):
+        """mp has an edge that this search_and_fuse call made for an earlier key frame"""
+        return self.new_base is not None and any(self.new_base <= e < self.new_here for _, e in self.obs[mp].values())
 
     def live_edges(self):
         """sorted (mp, kf, idx) of the edge arrays"""
@@ -43,6 +53,9 @@ def replace(w, this, pMP):                                                      
         w.stats["again"] += 1
     w.mp_bad[this] = 1                                                                                 # :189
     nvisible, nfound = w.visible[this], w.found[this]
+    w.stats["to_bad"] += 1 if w.mp_bad[pMP] else 0
+    w.stats["gained_only"] += 1 if obs and all(e >= len(w.home) or w.home[e] != this for _, e in obs.values()) else 0
+    w.stats["new_edge_seen"] += 1 if obs and w.holds_prior_edge(pMP) else 0                            # IsInKeyFrame below
     w.replaced[this] = pMP                                                                             # :192
     for pKF in w.map_order(obs):                                                                       # :195
         idx, e = obs[pKF]
@@ -51,10 +64,15 @@ def replace(w, this, pMP):                                                      
             w.obs[pMP][pKF] = (idx, e)                                                                 # AddObservation
             w.obs_mp[e] = pMP
             w.stats["moved"] += 1
+            w.stats["came_home"] += 1 if e < len(w.home) and w.home[e] == pMP else 0
+            if w.new_base is not None and e >= w.new_base:
+                w.stats["new_edge_moved"] += 1
+                w.stats["prior_edge_moved"] += 1 if e < w.new_here else 0
         else:
             w.kf_mp[pKF, idx] = -1                                                                     # EraseMapPointMatch
             w.obs_kf[e] = -1
             w.stats["dropped"] += 1
+            w.stats["dropped_ranks"].append(w.rank(pKF))
     w.found[pMP] += nfound                                                                             # :210
     w.visible[pMP] += nvisible
     R.compute_distinctive_descriptors(w, pMP)                                                          # :212
@@ -151,6 +169,7 @@ def search_and_fuse(w, c, set_slots, set_scw, loop_mp, th=4.0, search=oracle_sea
             n_fused.append(0)
             continue
         N = int(min(max(w.kf_n[pKF], 0), S))
+        w.new_base, w.new_here = base, base + k * S
         spAlreadyFound = set()                                                                         # :994 GetMapPoints()
         for p in w.kf_mp[pKF, :N].tolist():
             if p >= w.n_mp:
@@ -184,6 +203,7 @@ def search_and_fuse(w, c, set_slots, set_scw, loop_mp, th=4.0, search=oracle_sea
                 else:
                     w.stats["in_kf_bad"] += 1
             else:
+                w.stats["new_edge_seen"] += 1 if w.holds_prior_edge(pMP) else 0
                 if pKF not in w.obs[pMP]:                                                              # MapPoint.cc:101
                     e = base + k * S + n_new
                     w.obs[pMP][pKF] = (bestIdx, e)

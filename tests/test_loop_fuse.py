@@ -157,3 +157,167 @@ def test_a_bad_point_in_the_key_frame_counts_and_does_nothing_else():
     w = LR.World(c)
     assert LR.search_and_fuse(w, c, [1], np.zeros((1, 12), np.float32), [0], search=_flat_search({1: [1]})) == [1]
     assert w.replaced_rows == [] and w.added_rows == [] and np.array_equal(w.kf_mp, c["kf_mp"]) and w.stats["in_kf_bad"] == 1
+
+
+# ---- more live edges than key frames: the answers by hand (the model's dict cannot hold a repeated edge) ------------------------
+def test_overflow_pairs_are_skipped_whole_and_the_next_pair_runs():
+    c, op, w = LC.overflow_replace()
+    assert op == ("replace", [0, 1, 2], [1, 0, 3])
+    assert sorted(zip(c["obs_mp"].tolist(), c["obs_kf"].tolist()))[:3] == [(0, 0), (0, 0), (0, 1)]  # three live edges at K = 2
+    assert w.errors == 2 and w.replaced_rows == [(2, 3)]
+    assert w.kf_mp.tolist() == [[0, -1, 1, 3], [0, 1, 3, -1]]                                         # rows of points 0 and 1 as they came
+    assert w.live_edges() == [(0, 0, 0), (0, 0, 1), (0, 1, 0), (1, 0, 2), (1, 1, 1), (3, 0, 3), (3, 1, 2)]
+    assert w.obs_mp.tolist() == [0, 0, 1, 1, 3, 2, 3, 0] and w.obs_kf.tolist() == [0, 1, 0, 1, 0, -1, 1, 0]
+    assert w.mp_bad.tolist() == [0, 0, 1, 0] and w.replaced.tolist() == [-1, -1, 3, -1]
+    assert w.found.tolist() == [1, 2, 3, 7] and w.visible.tolist() == [10, 20, 30, 70]
+    assert np.all(w.desc[:3] == 0xAB) and np.array_equal(w.desc[3], c["kf_desc"][0, 3])
+    # pair 2 -> 3 is the model's on the map without the extra edge
+    good = LR.World(LC.overflow_map())
+    LR.replace_points(good, [2], [3])
+    assert np.array_equal(good.kf_mp, w.kf_mp) and np.array_equal(good.desc, w.desc) and good.live_edges() == [e for e in w.live_edges() if e != (0, 0, 1)]
+
+
+def test_exactly_k_edges_is_no_overflow():
+    c, w = run(LC.exactly_k_edges())
+    assert w.errors == 0 and w.stats["moved"] == 2 and w.stats["dropped"] == 2 and w.stats["gained_only"] == 1
+    assert w.kf_mp.tolist() == [[-1, 2, -1, -1], [-1, 2, -1, -1]] and w.live_edges() == [(2, 0, 1), (2, 1, 1)]
+    assert w.mp_bad.tolist() == [1, 1, 0] and w.replaced.tolist() == [1, 2, -1] and w.found.tolist() == [1, 3, 6]
+    assert np.array_equal(w.desc[1], c["kf_desc"][0, 0]) and np.array_equal(w.desc[2], c["kf_desc"][0, 1])
+    assert w.replaced_rows == [(0, 1), (1, 2)]
+
+
+def test_overflow_in_the_loop_fusion_writes_kf_mp_and_nothing_else():
+    c, op, w = LC.overflow_loop_fuse()
+    assert op == ("loop_fuse", 1, [-1, 0, 1, -1]) and c["kf_mp"][1].tolist() == [-1, -1, -1, -1]    # both matched features are empty
+    assert [(m, k) for m, k in zip(c["obs_mp"].tolist(), c["obs_kf"].tolist()) if m == 0] == [(0, 0)] * 3   # three edges, none to cur
+    assert w.errors == 1 and w.kf_mp[1].tolist() == [-1, 0, 1, -1] and w.kf_mp[0].tolist() == [0, -1, -1, 1]
+    assert w.added_rows == [(1, 1, 2, 4)] and w.replaced_rows == []                                    # the step after the overflow ran
+    assert w.obs_mp.tolist() == [0, 1, 0, 0, 1, -1, -1, -1] and w.obs_kf.tolist() == [0, 0, 0, 0, 1, -1, -1, -1]
+    assert w.obs_idx.tolist() == [0, 3, 1, 2, 2, -1, -1, -1]
+    assert np.all(w.desc[0] == 0xAB) and np.array_equal(w.desc[1], c["kf_desc"][0, 3]) and w.mp_bad.tolist() == [0, 0]
+
+
+def test_overflow_in_search_and_fuse_is_the_early_return_plus_one_error():
+    c, slots, scw, loop, w, n_fused = LC.shared_view_overflow()
+    p = LC.SAF_OVERFLOW_POINT
+    assert int((c["obs_mp"] == p).sum()) == c["K"] + 1
+    good = LR.World(LC.shared_view_scene()[0])
+    assert LR.search_and_fuse(good, LC.shared_view_scene()[0], slots, scw, loop) == n_fused          # counted in nFused all the same
+    rows = [r for r in good.added_rows if r[1] == p]
+    assert [r[0] for r in rows] == slots and len(w.added_rows) == len(good.added_rows) - 2 and all(r[1] != p for r in w.added_rows)
+    assert all(w.kf_mp[s, i] == p for s, _, i, _ in rows) and np.array_equal(w.kf_mp, good.kf_mp)   # kf_mp is written
+    assert all(p not in r for r in w.replaced_rows) and w.errors == 2
+    assert not w.mp_bad[p] and np.array_equal(w.desc[p], c["mp_desc"][p])
+
+
+# ---- K = 1 and K = 33 ----------------------------------------------------------------------------------------------------------
+def test_one_key_frame():
+    c, w = run(LC.one_key_frame())
+    assert c["K"] == 1 and w.stats["moved"] == 1 and w.stats["dropped"] == 1 and w.errors == 0
+    assert w.kf_mp.tolist() == [[-1, 2]] and w.obs_mp.tolist() == [0, 2] and w.obs_kf.tolist() == [-1, 0]
+    assert w.mp_bad.tolist() == [1, 1, 0] and w.replaced.tolist() == [1, 2, -1] and w.found.tolist() == [1, 3, 6]
+    assert np.array_equal(w.desc[1], c["kf_desc"][0, 1]) and np.array_equal(w.desc[2], c["kf_desc"][0, 1]) and np.all(w.desc[0] == 0xAB)
+
+
+def test_the_key_frame_of_rank_32():
+    c, w = run(LC.rank_32())
+    assert c["K"] == 33 and w.rank(0) == 32 and w.rank(1) == 31 and w.rank(2) == 30                   # rank differs from slot
+    assert w.stats["dropped_ranks"] == [32] and w.stats["moved"] == 3 and w.errors == 0              # the dropped edge is the rank-32 one
+    assert w.kf_mp[0].tolist() == [-1, 2] and w.kf_mp[1].tolist() == [2, -1] and w.kf_mp[2].tolist() == [2, -1]
+    assert w.live_edges() == [(2, 0, 1), (2, 1, 0), (2, 2, 0)] and w.obs_kf.tolist() == [-1, 1, 0, 2]
+    assert w.mp_bad.tolist() == [1, 1, 0] and w.replaced.tolist() == [1, 2, -1] and w.found.tolist() == [1, 3, 6]
+    assert np.array_equal(w.desc[1], c["kf_desc"][1, 0])                                              # ranks 31, 32: a tie, the first in kf_order
+    assert any(np.array_equal(w.desc[2], c["kf_desc"][k, i]) for k, i in ((0, 1), (1, 0), (2, 0)))
+
+
+# ---- pair patterns -------------------------------------------------------------------------------------------------------------
+def test_ping_pong():
+    c, w = run(LC.ping_pong())
+    assert w.stats["came_home"] == 3 and w.stats["moved"] == 7 and w.stats["dropped"] == 1 and w.stats["to_bad"] == 2
+    assert w.kf_mp[0].tolist() == [1, -1, -1, -1] and w.kf_mp[1].tolist() == [-1, 1, -1, -1] and w.kf_mp[2].tolist() == [1, -1, -1, -1]
+    assert w.live_edges() == [(1, 0, 0), (1, 1, 1), (1, 2, 0)] and w.obs_kf.tolist() == [0, -1, 1, 2]
+    assert w.mp_bad.tolist() == [1, 1] and w.replaced.tolist() == [1, 0]                              # both marked, nobody unmarks
+    assert w.found.tolist() == [4, 7] and w.visible.tolist() == [40, 70]
+    assert w.replaced_rows == [(0, 1), (1, 0), (0, 1)]
+    # b was refreshed by the first pair only (good then; bad in the third); a was bad when it was `to`
+    assert any(np.array_equal(w.desc[1], c["kf_desc"][k, i]) for k, i in ((0, 0), (1, 1), (2, 0))) and np.all(w.desc[0] == 0xAB)
+
+
+def test_a_bad_to_is_filled_and_then_taken_as_from():
+    c, w = run(LC.bad_to_then_from())
+    assert w.stats["to_bad"] == 1 and w.stats["moved"] == 3 and w.stats["dropped"] == 0
+    assert [w.kf_mp[k, 0] for k in range(3)] == [2, 2, 2] and w.live_edges() == [(2, 0, 0), (2, 1, 0), (2, 2, 0)]
+    assert w.mp_bad.tolist() == [1, 1, 0] and w.replaced.tolist() == [1, 2, -1] and w.found.tolist() == [1, 3, 6]
+    assert np.all(w.desc[1] == 0xAB)                                                                   # its refresh was skipped
+    assert any(np.array_equal(w.desc[2], c["kf_desc"][k, 0]) for k in range(3))
+
+
+def test_bad_key_frames_do_not_describe():
+    c, w = run(LC.bad_observers())
+    assert c["kf_bad"].tolist() == [1, 1, 0] and w.stats["moved"] == 3 and w.stats["dropped"] == 0
+    assert w.kf_mp[0].tolist() == [1, 3, -1, -1] and w.kf_mp[1].tolist() == [1, 3, -1, -1] and w.kf_mp[2].tolist() == [-1, 3, -1, -1]
+    assert w.live_edges() == [(1, 0, 0), (1, 1, 0), (3, 0, 1), (3, 1, 1), (3, 2, 1)]
+    assert w.mp_bad.tolist() == [1, 0, 1, 0] and w.replaced.tolist() == [1, -1, 3, -1] and w.found.tolist() == [1, 3, 3, 7]
+    assert np.all(w.desc[1] == 0xAB)                                                                   # all observers bad: unchanged
+    assert np.array_equal(w.desc[3], c["kf_desc"][2, 1])                                              # the one good observer's
+
+
+def test_a_from_with_gained_edges_only():
+    c, w = run(LC.gained_edges_only())
+    assert w.stats["gained_only"] == 1 and w.stats["moved"] == 3 and w.stats["dropped"] == 1
+    assert w.kf_mp[0].tolist() == [2, -1, -1, -1] and w.kf_mp[1].tolist() == [-1, 2, -1, -1]
+    assert w.live_edges() == [(2, 0, 0), (2, 1, 1)] and w.obs_mp.tolist() == [2, 1, 2] and w.obs_kf.tolist() == [0, -1, 1]
+    assert w.mp_bad.tolist() == [1, 1, 0] and w.replaced.tolist() == [1, 2, -1] and w.found.tolist() == [1, 3, 6]
+    assert np.array_equal(w.desc[1], c["kf_desc"][0, 0]) and np.array_equal(w.desc[2], c["kf_desc"][0, 0])
+
+
+# ---- the logs and the device count ---------------------------------------------------------------------------------------------
+def test_the_log_cut_case_has_two_rows_in_each_log():
+    c, w = run(LC.loop_two_adds())
+    assert w.replaced_rows == [(0, 2), (1, 2)] and w.added_rows == [(1, 3, 1, 7), (1, 4, 3, 8)]
+    assert w.kf_mp[1].tolist() == [2, 3, -1, 4]
+
+
+def test_the_chain_cut_short():
+    c, op = LC.chain()
+    for n, rows in ((0, []), (1, [(0, 1)]), (2, [(0, 1), (1, 2)])):
+        w = LR.World(c)
+        LR.replace_points(w, op[1][:n], op[2][:n])
+        assert w.replaced_rows == rows and w.errors == 0
+    assert np.array_equal(LR.World(c).kf_mp, c["kf_mp"])
+
+
+# ---- SearchAndFuse on two key frames that see the same thing -------------------------------------------------------------------
+def saf_model(scene):
+    c, slots, scw, loop = scene
+    w = LR.World(c)
+    return c, w, LR.search_and_fuse(w, c, slots, scw, loop)
+
+
+def test_the_shared_view_carries_new_edges_into_the_next_key_frame():
+    c, w, n_fused = saf_model(LC.shared_view_scene())
+    print(n_fused, w.stats)
+    assert w.stats["new_edge_moved"] > 0 and w.stats["new_edge_seen"] > 0 and w.stats["prior_edge_moved"] > 0
+    assert w.stats["add"] > 0 and w.stats["rep"] > 0 and w.stats["collision"] > 0 and min(n_fused) > 0
+    S, n0 = c["S"], len(c["obs_kf"])
+    assert {r[0] for r in w.added_rows} == set(LC.SHARED_SET)                                          # both key frames add
+    assert any(r[3] < n0 + S and w.obs_mp[r[3]] != r[1] for r in w.added_rows)                        # an edge of key frame 0 changed owner
+
+
+def test_the_shared_view_with_bad_entries():
+    c, w, n_fused = saf_model(LC.shared_view_bad_entries())
+    _, _, good = saf_model(LC.shared_view_scene())
+    assert n_fused == [good[0], 0, 0, good[1]] and w.errors == 2 + 2 + 1                              # slots, the loop point twice, the entry
+    S, n0 = c["S"], len(c["obs_kf"])
+    assert np.all(w.obs_kf[n0 + S:n0 + 3 * S] == -1) and len(w.obs_kf) == n0 + 4 * S
+    assert {r[3] // S for r in w.added_rows} == {n0 // S, (n0 + 3 * S) // S}
+
+
+def test_the_shared_view_with_short_key_frames():
+    c, w, n_fused = saf_model(LC.shared_view_short())
+    _, wg, good = saf_model(LC.shared_view_scene())
+    p = LC.SHORT_KEPT
+    assert c["kf_n"][5] == 40 and c["kf_n"][2] == 40 and c["kf_mp"][5, 50] == p
+    assert sum(good) > sum(n_fused) == 2 and w.added_rows == [(5, p, 0, w.added_rows[0][3]), (2, p, 0, w.added_rows[1][3])]
+    assert all(r[2] < 40 for r in w.added_rows) and not np.any(w.kf_mp[[5, 2], 40:] != c["kf_mp"][[5, 2], 40:])
+    assert w.replaced_rows == [] and w.errors == 0

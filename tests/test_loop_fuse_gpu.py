@@ -34,21 +34,34 @@ def model():
     return out
 
 
-def run_device(c, op, n_pairs=None):
+def run_device(c, op, n_pairs=None, replaced_cap=None, added_cap=None, null_logs=False):
+    """null_logs: both caps 0 and both log pointers NULL"""
     spare = (len(op[2]) if op[0] == "loop_fuse" else 0) + GUARD
     G = CovisibilityGraph(c["K"])
     m = DeviceMap(c, obs_spare=spare)
     n_rows = len(op[1]) if op[0] == "replace" else len(op[2])
+    n_rows = 0 if null_logs else (n_rows if replaced_cap is None else replaced_cap)
     t, fuse = G.point_fuse_arrays(m, c["kf_bad"], c["kf_desc"], c["mp_desc"], c["mp_found"], c["mp_visible"], replaced_cap=n_rows, guard=GUARD)
+    if null_logs:
+        fuse.d_replaced = None
     if op[0] == "replace":
         G.replace_points(m, fuse, op[1], op[2], n_pairs=n_pairs)
         added = None
+    elif null_logs:
+        mt, n_added = torch.tensor(op[2], dtype=torch.int32, device="cuda"), G._i32(1, -1)
+        a = cabi.fill(cabi.LoopFuseArgs(), cur_slot=op[1], n_features=len(op[2]), d_matched=mt, obs_cap=m.obs_cap, obs_idx=m.t["obs_idx"],
+                      d_n_added=n_added, added_cap=0)
+        a.map = fuse
+        assert lib().fb_covis_loop_fuse_dev(G.h, C.byref(m.c), C.byref(a), None) == 0
+        m.grow(len(op[2]))
+        torch.cuda.synchronize()
+        added = (n_added, torch.full((4 * GUARD,), -5, dtype=torch.int32))
     else:
-        added = G.loop_fuse(m, fuse, op[1], op[2], guard=GUARD)
+        added = G.loop_fuse(m, fuse, op[1], op[2], added_cap=added_cap, guard=GUARD)
     return G, m, t, added, n_rows
 
 
-def check(c, w, G, m, t, added, n_rows):
+def check_map(c, w, G, m, t):
     n_mp, n0 = len(c["mp_bad"]), len(c["obs_kf"])
     assert np.array_equal(m.t["kf_mp"].cpu().numpy(), w.kf_mp)
     assert np.array_equal(m.t["mp_bad"].cpu().numpy()[:n_mp], w.mp_bad)
@@ -63,6 +76,11 @@ def check(c, w, G, m, t, added, n_rows):
         a = t[k].cpu().numpy()
         assert np.array_equal(a[:n_mp * width].reshape(np.asarray(exp).shape), exp), k
         assert np.all(a[max(n_mp, 1) * width:] == fill), k + ": guard rows"
+    assert G.error_count() == w.errors
+
+
+def check(c, w, G, m, t, added, n_rows):
+    check_map(c, w, G, m, t)
     n_rep = int(t["d_n_replaced"].cpu()[0])
     rows = t["d_replaced"].cpu().numpy()
     assert n_rep == len(w.replaced_rows) and rows[:2 * n_rep].reshape(-1, 2).tolist() == [list(r) for r in w.replaced_rows]
@@ -71,7 +89,16 @@ def check(c, w, G, m, t, added, n_rows):
         n_add, arr = int(added[0].cpu()[0]), added[1].cpu().numpy()
         assert n_add == len(w.added_rows) and arr[:4 * n_add].reshape(-1, 4).tolist() == [list(r) for r in w.added_rows]
         assert np.all(arr[4 * n_add:] == -5)
-    assert G.error_count() == w.errors
+
+
+def check_cut(c, w, G, m, t, added, replaced_cap, added_cap):
+    """the logs cut at their caps: the counts are the full ones, rows [0, cap) are the model's first, the rest keeps its fill"""
+    check_map(c, w, G, m, t)
+    rows, arr = t["d_replaced"].cpu().numpy(), added[1].cpu().numpy()
+    assert int(t["d_n_replaced"].cpu()[0]) == len(w.replaced_rows) and int(added[0].cpu()[0]) == len(w.added_rows)
+    nr, na = min(replaced_cap, len(w.replaced_rows)), min(added_cap, len(w.added_rows))
+    assert rows[:2 * nr].reshape(-1, 2).tolist() == [list(r) for r in w.replaced_rows[:nr]] and np.all(rows[2 * nr:] == -5)
+    assert arr[:4 * na].reshape(-1, 4).tolist() == [list(r) for r in w.added_rows[:na]] and np.all(arr[4 * na:] == -5)
 
 
 @pytest.mark.parametrize("name", [n for n, _ in CASES])
@@ -217,19 +244,19 @@ def test_chain_update_connections_loop_fuse_update_connections():
 
 
 # ---- SearchAndFuse ---------------------------------------------------------------------------------------------------------------
-def saf_device(c, slots, scw, loop, before=None):
+def saf_device(c, slots, scw, loop, before=None, replaced_cap=None, added_cap=None):
     from fishbirdeyevisualslam_amd import kf_problems as KP
     K, S = c["K"], c["S"]
     G = CovisibilityGraph(K)
     m = DeviceMap(c, obs_spare=len(slots) * S + GUARD)
-    t, fuse = G.point_fuse_arrays(m, c["kf_bad"], c["kf_desc"], c["mp_desc"], c["mp_found"], c["mp_visible"], replaced_cap=len(loop) * len(slots),
-                                  guard=GUARD)
+    t, fuse = G.point_fuse_arrays(m, c["kf_bad"], c["kf_desc"], c["mp_desc"], c["mp_found"], c["mp_visible"],
+                                  replaced_cap=len(loop) * len(slots) if replaced_cap is None else replaced_cap, guard=GUARD)
     cells = np.zeros((1, 64 * 48 + 1), np.int32)
     target, keep = KP.kf_target([dict(kf_kps=c["kf_keys_un"][0], kf_desc=c["kf_desc"][0])], "kf_", cells, np.zeros((1, S), np.int32))
     if before:
         before(G, m)
     out = G.search_and_fuse(m, fuse, target, slots, scw, loop, c["kf_keys_un"], c["mp_xw"], c["mp_normal"], c["mp_min_dist"], c["mp_max_dist"],
-                            guard=GUARD)
+                            added_cap=added_cap, guard=GUARD)
     return G, m, t, out
 
 
@@ -383,4 +410,192 @@ def test_chain_correct_loop_loop_fuse_search_and_fuse_update_connections():
     for s, (n, sl) in zip(slots, conn):
         new_links += len(set(sl.cpu().numpy()[:int(n.cpu()[0])].tolist()) & {0, 1})                   # the loop side: no link before
     assert new_links > 0
+    G.close()
+
+
+# ---- more live edges than key frames, the log cut, the device count, K = 1 and 33, SearchAndFuse on a shared view ----------------
+def saf_host(c, slots, scw, loop, replaced_cap=None, added_cap=None):
+    """fb_covis_search_and_fuse on host arrays -> (G, host arrays, d_n_fused, n_rep, rows, n_add, added), logs with GUARD rows"""
+    from fishbirdeyevisualslam_amd import kf_problems as KP
+    S, n_set = c["S"], len(slots)
+    h, hm = host_arrays(c, n_set * S)
+    rcap = n_set * len(loop) if replaced_cap is None else replaced_cap
+    acap = n_set * S if added_cap is None else added_cap
+    n_rep, rows = np.full(1, -1, np.int32), np.full((rcap + GUARD, 2), -5, np.int32)
+    fuse = cabi.fill(cabi.PointFuseArrays(), d_n_replaced=n_rep, replaced_cap=rcap, d_replaced=rows,
+                     **{k: h[k] for k in ("kf_mp", "mp_bad", "obs_mp", "obs_kf", "mp_found", "mp_visible", "mp_replaced", "kf_bad", "kf_desc", "mp_desc")})
+    target, keep = KP.kf_target([dict(kf_kps=c["kf_keys_un"][0], kf_desc=c["kf_desc"][0])], "kf_", np.zeros((1, 64 * 48 + 1), np.int32),
+                                np.zeros((1, S), np.int32))
+    f = {k: np.ascontiguousarray(c[k], np.float32).copy() for k in ("mp_xw", "mp_normal", "mp_min_dist", "mp_max_dist")}
+    kps = np.ascontiguousarray(c["kf_keys_un"]).copy()
+    d_fused, n_add, added = np.full(n_set, -5, np.int32), np.full(1, -1, np.int32), np.full((acap + GUARD, 4), -5, np.int32)
+    a = cabi.fill(cabi.SearchAndFuseArgs(), n_set=n_set, d_set_slots=np.array(slots, np.int32), d_set_Scw=np.ascontiguousarray(scw, np.float32),
+                  n_loop=len(loop), d_loop_mp=np.array(loop, np.int32), th=4.0, log_scale_factor=target.log_scale_factor, n_levels=target.n_levels,
+                  kf_keys_un=kps.view(np.uint8).reshape(-1), obs_cap=len(h["obs_kf"]), obs_idx=h["obs_idx"], d_n_fused=d_fused, d_n_added=n_add,
+                  added_cap=acap, d_added=added, **f)
+    a.cam, a.grid, a.scale_factors, a.inv_level_sigma2, a.map = target.cam, target.grid, target.scale_factors, target.inv_level_sigma2, fuse
+    G = CovisibilityGraph(c["K"])
+    assert lib().fb_covis_search_and_fuse(G.h, C.byref(hm), C.byref(a)) == 0
+    return G, h, d_fused, n_rep, rows, n_add, added
+
+
+def check_host(c, w, G, h, n_rep, rows, n_add, added, replaced_cap, added_cap):
+    """the host arrays against the model, the logs cut at their caps (rows past them and the guard rows keep their fill)"""
+    n_mp = len(c["mp_bad"])
+    assert np.array_equal(h["kf_mp"], w.kf_mp) and np.array_equal(h["mp_bad"], w.mp_bad) and np.array_equal(h["obs_idx"], w.obs_idx)
+    assert np.array_equal(h["obs_mp"], w.obs_mp) and np.array_equal(h["obs_kf"], w.obs_kf)
+    assert np.array_equal(h["mp_desc"].reshape(-1, 32), w.desc) and np.array_equal(h["mp_found"], w.found)
+    assert np.array_equal(h["mp_visible"], w.visible) and np.array_equal(h["mp_replaced"][:n_mp], w.replaced)
+    assert n_rep[0] == len(w.replaced_rows) and n_add[0] == len(w.added_rows)
+    nr, na = min(replaced_cap, len(w.replaced_rows)), min(added_cap, len(w.added_rows))
+    assert rows[:nr].tolist() == [list(r) for r in w.replaced_rows[:nr]] and np.all(rows[nr:] == -5)
+    assert added[:na].tolist() == [list(r) for r in w.added_rows[:na]] and np.all(added[na:] == -5)
+    assert G.error_count() == w.errors
+
+
+def test_overflow_pairs_are_skipped_whole():
+    c, op, w = LC.overflow_replace()
+    G, m, t, added, n_rows = run_device(c, op)
+    check(c, w, G, m, t, added, n_rows)
+    for k in ("kf_mp", "obs_mp", "obs_kf", "obs_idx"):                                                 # what belongs to points 0 and 1 is as it came
+        got, came = m.t[k].cpu().numpy().reshape(-1)[:c[k].size], np.asarray(c[k]).reshape(-1)
+        own = np.isin(np.asarray(c["kf_mp"] if k == "kf_mp" else c["obs_mp"]).reshape(-1), (0, 1))
+        assert np.array_equal(got[own], came[own]), k
+    G.close()
+
+
+def test_overflow_in_the_loop_fusion():
+    c, op, w = LC.overflow_loop_fuse()
+    G, m, t, added, n_rows = run_device(c, op)
+    check(c, w, G, m, t, added, n_rows)
+    G.close()
+
+
+def test_overflow_in_search_and_fuse():
+    c, slots, scw, loop, w, n_fused = LC.shared_view_overflow()
+    G, m, t, (d_n_fused, d_n_added, d_added) = saf_device(c, slots, scw, loop)
+    assert d_n_fused.cpu().numpy()[:len(slots)].tolist() == n_fused
+    check(c, w, G, m, t, (d_n_added, d_added), len(loop) * len(slots))
+    G.close()
+
+
+LOG_CUTS = {"one_row": dict(replaced_cap=1, added_cap=1), "null": dict(null_logs=True), "full": {}}
+
+
+@pytest.fixture(scope="module")
+def cut_maps():
+    return {}
+
+
+@pytest.mark.parametrize("cut", list(LOG_CUTS))
+def test_loop_fuse_logs_are_cut_at_their_caps(model, cut_maps, cut):
+    c, op = LC.loop_two_adds()
+    w = model["loop_two_adds"]
+    assert len(w.replaced_rows) == 2 and len(w.added_rows) == 2
+    G, m, t, added, n_rows = run_device(c, op, **LOG_CUTS[cut])
+    caps = dict(one_row=(1, 1), null=(0, 0), full=(4, 4))[cut]
+    check_cut(c, w, G, m, t, added, *caps)
+    cut_maps[cut] = m.bytes() + b"".join(t[k].cpu().numpy().tobytes() for k in ("mp_desc", "mp_found", "mp_visible", "mp_replaced"))
+    assert len(set(cut_maps.values())) == 1                                                            # the same map whatever the caps
+    G.close()
+
+
+@pytest.mark.parametrize("cut", list(LOG_CUTS))
+def test_loop_fuse_host_pointer_logs_are_cut_at_their_caps(model, cut):
+    c, op = LC.loop_two_adds()
+    w = model["loop_two_adds"]
+    rcap, acap = dict(one_row=(1, 1), null=(0, 0), full=(4, 4))[cut]
+    nf = len(op[2])
+    h, hm = host_arrays(c, nf)
+    n_rep, rows = np.full(1, -1, np.int32), np.full((rcap + GUARD, 2), -5, np.int32)
+    fuse = cabi.fill(cabi.PointFuseArrays(), d_n_replaced=n_rep, replaced_cap=rcap, d_replaced=None if cut == "null" else rows,
+                     **{k: h[k] for k in ("kf_mp", "mp_bad", "obs_mp", "obs_kf", "mp_found", "mp_visible", "mp_replaced", "kf_bad", "kf_desc", "mp_desc")})
+    mt, n_add, added = np.array(op[2], np.int32), np.full(1, -1, np.int32), np.full((acap + GUARD, 4), -5, np.int32)
+    a = cabi.fill(cabi.LoopFuseArgs(), cur_slot=op[1], n_features=nf, d_matched=mt, obs_cap=len(h["obs_kf"]), obs_idx=h["obs_idx"],
+                  d_n_added=n_add, added_cap=acap, d_added=None if cut == "null" else added)
+    a.map = fuse
+    G = CovisibilityGraph(c["K"])
+    assert lib().fb_covis_loop_fuse(G.h, C.byref(hm), C.byref(a)) == 0
+    check_host(c, w, G, h, n_rep, rows, n_add, added, rcap, acap)
+    G.close()
+
+
+@pytest.fixture(scope="module")
+def saf_cut():
+    """the generated scene, the model's answer, and caps one less than what the first key frame alone produces"""
+    c, slots, scw, loop = LC.search_and_fuse_scene()
+    first = LR.World(c)
+    LR.search_and_fuse(first, c, slots[:1], scw[:1], loop)
+    w = LR.World(c)
+    n_fused = LR.search_and_fuse(w, c, slots, scw, loop)
+    rcap, acap = len(first.replaced_rows) - 1, len(first.added_rows) - 1
+    assert 0 < rcap < len(w.replaced_rows) - 1 and 0 < acap < len(w.added_rows) - 1                   # later key frames produce rows too
+    return c, slots, scw, loop, w, n_fused, rcap, acap
+
+
+def test_search_and_fuse_logs_are_cut_inside_the_first_key_frame(saf_cut):
+    c, slots, scw, loop, w, n_fused, rcap, acap = saf_cut
+    G, m, t, (d_n_fused, d_n_added, d_added) = saf_device(c, slots, scw, loop, replaced_cap=rcap, added_cap=acap)
+    assert d_n_fused.cpu().numpy()[:len(slots)].tolist() == n_fused
+    check_cut(c, w, G, m, t, (d_n_added, d_added), rcap, acap)
+    G.close()
+
+
+def test_search_and_fuse_host_pointer_logs_are_cut(saf_cut):
+    c, slots, scw, loop, w, n_fused, rcap, acap = saf_cut
+    G, h, d_fused, n_rep, rows, n_add, added = saf_host(c, slots, scw, loop, rcap, acap)
+    assert d_fused.tolist() == n_fused
+    check_host(c, w, G, h, n_rep, rows, n_add, added, rcap, acap)
+    G.close()
+
+
+@pytest.mark.parametrize("count", [0, -3, 1, 2, 7])
+def test_the_device_count_on_the_chain(count):
+    c, op = LC.chain()
+    n = min(max(count, 0), 2)
+    G, m, t, added, n_rows = run_device(c, op, n_pairs=torch.tensor([count], dtype=torch.int32, device="cuda"))
+    w = LR.World(c)
+    LR.replace_points(w, op[1][:n], op[2][:n])
+    check(c, w, G, m, t, added, n_rows)
+    if n == 0:
+        assert int(t["d_n_replaced"].cpu()[0]) == 0 and m.bytes() == DeviceMap(c, obs_spare=GUARD).bytes()
+    G.close()
+
+
+SHARED = {"shared_view_scene": LC.shared_view_scene, "shared_view_bad_entries": LC.shared_view_bad_entries,
+          "shared_view_short": LC.shared_view_short}
+
+
+@pytest.fixture(scope="module")
+def shared_model():
+    out = {}
+    for name, f in SHARED.items():
+        c, slots, scw, loop = f()
+        w = LR.World(c)
+        out[name] = (w, LR.search_and_fuse(w, c, slots, scw, loop))
+    return out
+
+
+@pytest.mark.parametrize("name", list(SHARED))
+def test_search_and_fuse_on_a_shared_view_matches_the_model(shared_model, name):
+    c, slots, scw, loop = SHARED[name]()
+    w, n_fused = shared_model[name]
+    G, m, t, (d_n_fused, d_n_added, d_added) = saf_device(c, slots, scw, loop)
+    got = d_n_fused.cpu().numpy()
+    assert got[:len(slots)].tolist() == n_fused and np.all(got[len(slots):] == -5)
+    check(c, w, G, m, t, (d_n_added, d_added), len(loop) * len(slots))
+    if name == "shared_view_short":
+        arr = d_added.cpu().numpy()[:4 * len(w.added_rows)].reshape(-1, 4)
+        changed = m.t["kf_mp"].cpu().numpy() != c["kf_mp"]
+        assert np.all(arr[:, 2] < 40) and not changed[:, 40:].any()
+    G.close()
+
+
+@pytest.mark.parametrize("name", list(SHARED))
+def test_search_and_fuse_host_pointer_form_on_a_shared_view_matches_the_model(shared_model, name):
+    c, slots, scw, loop = SHARED[name]()
+    w, n_fused = shared_model[name]
+    G, h, d_fused, n_rep, rows, n_add, added = saf_host(c, slots, scw, loop)
+    assert d_fused.tolist() == n_fused
+    check_host(c, w, G, h, n_rep, rows, n_add, added, len(slots) * len(loop), len(slots) * c["S"])
     G.close()
