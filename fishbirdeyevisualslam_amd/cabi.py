@@ -378,6 +378,19 @@ class SearchAndFuseArgs(C.Structure):
                 ("added_cap", _i32), ("d_added", _vp), ("map", PointFuseArrays)]
 
 
+class LoopGroupsHeader(C.Structure):
+    _fields_ = [("n_groups", _i32), ("overflow", _i32)]
+
+
+class LoopConnectionsHeader(C.Structure):
+    _fields_ = [("total", _i32), ("overflow", _i32)]
+
+
+class LoopConnectionsArgs(C.Structure):
+    _fields_ = [("set_cap", _i32), ("d_n_set", _vp), ("d_set", _vp), ("d_n_counter", _vp), ("d_front", _vp), ("lc_cap", _i32),
+                ("d_lc_off", _vp), ("d_lc_slots", _vp), ("d_header", _vp)]
+
+
 class BirdFilterArgs(C.Structure):
     _fields_ = [("batch", _i32), ("match_stride", _i32), ("kp1_stride", _i32), ("kp2_stride", _i32),
                 ("n_matches", _vp), ("query_idx", _vp), ("train_idx", _vp), ("cam_xyz1", _vp), ("cam_xyz2", _vp),
@@ -524,6 +537,9 @@ EXPORTS = [
     "fb_covis_replace_points_dev", "fb_covis_replace_points", "fb_covis_reserve_replace_points",
     "fb_covis_loop_fuse_dev", "fb_covis_loop_fuse", "fb_covis_reserve_loop_fuse",
     "fb_covis_search_and_fuse_dev", "fb_covis_search_and_fuse", "fb_covis_reserve_search_and_fuse",
+    "fb_covis_reserve_loop_groups", "fb_covis_detect_loop_dev", "fb_covis_detect_loop", "fb_covis_loop_groups",
+    "fb_covis_loop_map_points_dev", "fb_covis_loop_map_points", "fb_covis_reserve_loop_map_points",
+    "fb_covis_loop_connections_dev", "fb_covis_loop_connections", "fb_covis_reserve_loop_connections",
     "fb_in_frustum_dev", "fb_in_frustum", "fb_undistort_keypoints_dev", "fb_undistort_keypoints", "fb_image_bounds",
     "fb_pose_opt_batch_dev", "fb_pose_opt", "fb_pose_gather_front_dev", "fb_pose_gather_bird_dev",
     "fb_frame_tail_front_dev", "fb_frame_tail_bird_dev",

@@ -602,3 +602,68 @@ class CovisibilityGraph:
         mc = m if isinstance(m, cabi.CovisMap) else m.c
         check(lib().fb_covis_local_bird_map_dev(self.h, C.byref(mc), C.byref(t.c), C.byref(a), _stream()), "fb_covis_local_bird_map_dev")
         self._keep = (m, t, a)
+
+    # ---- loop closing: consistency groups, mvpLoopMapPoints, LoopConnections ------------------------------------------------------
+    def reserve_loop_groups(self, cap_groups):
+        check(lib().fb_covis_reserve_loop_groups(self.h, int(cap_groups)), "fb_covis_reserve_loop_groups")
+        self._loop_cap = int(cap_groups)
+
+    def detect_loop(self, n_candidates, candidates, consistency_th=3, guard=0):
+        """The consistency check of LoopClosing::DetectLoop on the candidate list of fb_kfdb_query_dev (device int32[1] and
+        int32[K]) -> (n_enough int32[1], enough int32[K + guard], header int32[2 + guard] = n_groups, overflow).  Enqueues only."""
+        n_enough = self._i32(1, -5)
+        enough = torch.full((self.K + guard,), -5, dtype=torch.int32, device=self.device)
+        header = torch.full((2 + guard,), -5, dtype=torch.int32, device=self.device)
+        check(lib().fb_covis_detect_loop_dev(self.h, _p(n_candidates), _p(candidates), int(consistency_th), _p(n_enough), _p(enough),
+                                             _p(header), _stream()), "fb_covis_detect_loop_dev")
+        self._keep = (n_candidates, candidates, n_enough, enough, header)
+        return n_enough, enough, header
+
+    def loop_groups(self):
+        """mvConsistentGroups as it stands -> list of (sorted slots, consistency counter); synchronises"""
+        cap, nw = getattr(self, "_loop_cap", self.K), (self.K + 31) // 32
+        n = C.c_int32(0)
+        cons, bits = np.zeros(cap, np.int32), np.zeros((cap, nw), np.uint32)
+        check(lib().fb_covis_loop_groups(self.h, C.byref(n), C.c_void_p(cons.ctypes.data), C.c_void_p(bits.ctypes.data), _stream()),
+              "fb_covis_loop_groups")
+        out = []
+        for k in range(n.value):
+            slots = [s for s in range(self.K) if (int(bits[k, s >> 5]) >> (s & 31)) & 1]
+            out.append((slots, int(cons[k])))
+        return out
+
+    def reserve_loop_map_points(self, n_mp):
+        check(lib().fb_covis_reserve_loop_map_points(self.h, int(n_mp)), "fb_covis_reserve_loop_map_points")
+
+    def loop_map_points(self, m, matched_slot, cap=None, guard=0):
+        """mvpLoopMapPoints of the matched key frame -> (n_loop int32[1], loop_mp int32[cap + guard], overflow int32[1]).
+        Enqueues only."""
+        cap = m.n_mp if cap is None else int(cap)
+        n_loop, overflow = self._i32(1, -5), self._i32(1, -5)
+        loop_mp = torch.full((cap + guard + 1,), -5, dtype=torch.int32, device=self.device)
+        check(lib().fb_covis_loop_map_points_dev(self.h, C.byref(m.c), int(matched_slot), cap, _p(n_loop), _p(loop_mp), _p(overflow),
+                                                 _stream()), "fb_covis_loop_map_points_dev")
+        self._keep = (m, n_loop, loop_mp, overflow)
+        return n_loop, loop_mp, overflow
+
+    def reserve_loop_connections(self, n_mp, n_obs, set_cap):
+        check(lib().fb_covis_reserve_loop_connections(self.h, int(n_mp), int(n_obs), int(set_cap)), "fb_covis_reserve_loop_connections")
+
+    def loop_connections(self, m, set_slots, n_set=None, lc_cap=None, guard=0):
+        """The LoopConnections pass that ends CorrectLoop over mvpCurrentConnectedKFs = set_slots (a list or a device tensor;
+        n_set: a device int32[1] that holds its length, None = all of it) -> dict of device tensors: n_counter, front
+        [set_cap + guard], lc_off [set_cap + 1 + guard], lc_slots [lc_cap + guard], header int32[2] = total, overflow.
+        Enqueues only."""
+        slots = self._dev(set_slots).reshape(-1)
+        cap = int(slots.numel())
+        if n_set is None:
+            n_set = self._i32(1, cap)
+        lc_cap = cap * self.K if lc_cap is None else int(lc_cap)
+        out = dict(n_counter=self._i32(cap + guard, -5), front=self._i32(cap + guard, -5), lc_off=self._i32(cap + 1 + guard, -5),
+                   lc_slots=self._i32(lc_cap + guard, -5), header=self._i32(2 + guard, -5))
+        a = cabi.LoopConnectionsArgs()
+        cabi.fill(a, set_cap=cap, d_n_set=n_set, d_set=slots if cap else self._i32(1), d_n_counter=out["n_counter"], d_front=out["front"],
+                  lc_cap=lc_cap, d_lc_off=out["lc_off"], d_lc_slots=out["lc_slots"], d_header=out["header"])
+        check(lib().fb_covis_loop_connections_dev(self.h, C.byref(m.c), C.byref(a), _stream()), "fb_covis_loop_connections_dev")
+        self._keep = (m, a, slots, n_set, out)
+        return out

@@ -152,10 +152,12 @@ __global__ __launch_bounds__(256) void k_cv_tree_reset(Gr G) {
 
 // ---- UpdateConnections -------------------------------------------------------------------------------------------------
 // KFcounter of query q (KeyFrame.cc:580-598): one workgroup, the bins in LDS
+// (d_n: the list's length on the device, NULL = every row of the launch is a query)
 __global__ __launch_bounds__(CV_NT) void k_cv_counter(fb_covis_map M, Gr G, const int32_t *start, const int32_t *csr, const int32_t *slots,
-                                                      uint16_t *counter) {
+                                                      uint16_t *counter, const int32_t *d_n) {
   __shared__ int s_bin[CV_MAXK];
   const int q = blockIdx.x, K = G.K, S = M.kp_stride;
+  if (d_n && q >= *d_n) return;
   for (int b = threadIdx.x; b < K; b += CV_NT) s_bin[b] = 0;
   __syncthreads();
   const int a = slots[q];
@@ -183,16 +185,41 @@ __global__ __launch_bounds__(CV_NT) void k_cv_counter(fb_covis_map M, Gr G, cons
 // key of an ordered-vector entry: larger = earlier
 __device__ __forceinline__ uint32_t order_key(uint32_t w, int rank) { return (w << 12) | (uint32_t)rank; }
 
+// What the LoopConnections variant of k_cv_apply adds (covis_loop.inc): the list's length is on the device, and at the turn
+// of query q, before its row is replaced, bits[q] = "the row after the update has an entry" and not "member of the ordered
+// vector before it" and not "in the list", with the row's size in rowcnt[q].
+struct LoopConnOut {
+  const int32_t *d_n;
+  uint32_t *bits;       // [n_q][(K + 31) / 32], zero when the kernel starts
+  int32_t *rowcnt;      // [n_q]
+};
+
 // the counters applied to the graph one query after the other (:604-663), by one workgroup
+template <bool LC>
 __global__ __launch_bounds__(CV_NT) void k_cv_apply(Gr G, int n_q, const int32_t *slots, const uint16_t *counter, int32_t *n_counter,
-                                                    int32_t *front) {
+                                                    int32_t *front, LoopConnOut L) {
   __shared__ int s_wv[CV_NT / 64];
   __shared__ uint32_t s_mx[CV_NT / 64];
   const int tid = threadIdx.x, K = G.K, lane = tid & 63, wave = tid >> 6;
+  [[maybe_unused]] uint32_t *s_set = nullptr;   // the members of the list as a bitset, and the words of a bit row:
+  [[maybe_unused]] int nw = 0;                  // the LoopConnections instance only; the other one has neither
+  if constexpr (LC) {
+    __shared__ uint32_t s_members[CV_MAXK / 32];
+    s_set = s_members;
+    nw = (K + 31) / 32;
+    n_q = min(max(*L.d_n, 0), n_q);
+    for (int w = tid; w < nw; w += CV_NT) s_set[w] = 0;
+    __syncthreads();
+    for (int q = tid; q < n_q; q += CV_NT) {
+      const int a = slots[q];
+      if (a >= 0 && a < K) atomicOr(&s_set[a >> 5], 1u << (a & 31));
+    }
+    __syncthreads();
+  }
   for (int q = 0; q < n_q; q++) {
     const int a = slots[q];
     if (a < 0 || a >= K) {
-      if (tid == 0) { n_counter[q] = 0; front[q] = -1; }
+      if (tid == 0) { n_counter[q] = 0; front[q] = -1; if constexpr (LC) L.rowcnt[q] = 0; }
       continue;
     }
     const uint16_t *C = counter + (size_t)q * K;
@@ -211,6 +238,27 @@ __global__ __launch_bounds__(CV_NT) void k_cv_apply(Gr G, int n_q, const int32_t
     best15 = block_max_u32(best15, s_mx);
     bestAny = block_max_u32(bestAny, s_mx);
     cur = block_max_u32(cur, s_mx);
+    if constexpr (LC) {   // LoopClosing.cc:576-588 for this member; with an empty counter the row stays and is what is read
+      int mine = 0;
+      for (int base = wave * 64; base < nw * 32; base += CV_NT) {
+        const int b = base + lane;
+        bool bit = false;
+        if (b < K) {
+          const uint32_t v = rowA[b];
+          const uint32_t w = cnt ? (uint32_t)C[b] : (v & CV_W);
+          bit = w && !((v & CV_MEMBER) && (v & CV_W)) && !((s_set[b >> 5] >> (b & 31)) & 1u);
+        }
+        const unsigned long long m = __ballot(bit);
+        if (lane == 0) {
+          uint32_t *row = L.bits + (size_t)q * nw;
+          row[base >> 5] = (uint32_t)m;
+          if ((base >> 5) + 1 < nw) row[(base >> 5) + 1] = (uint32_t)(m >> 32);
+          mine += __popcll(m);
+        }
+      }
+      mine = fb::block_sum<CV_NT>(mine, s_wv);   // (its barriers also order the reads of rowA before the writes below)
+      if (tid == 0) L.rowcnt[q] = mine;
+    }
     if (cnt == 0) {   // "This should not happen": the graph stays as it is
       if (tid == 0) { n_counter[q] = 0; front[q] = cur ? G.inv[cur & 4095] : -1; }
       continue;
@@ -416,6 +464,10 @@ struct fb_covis {
   Gr G{};
   void *bird_block = nullptr;   // the bird lists (covis_bird.inc), allocated by the first bird call
   uint16_t *WB = nullptr;       // [K][K] mvpBirdConnectedKeyFrames in the format of W: weight | CV_MEMBER, members only
+  void *loop_block = nullptr;   // the consistency groups of DetectLoop (covis_loop.inc), allocated by the first such call
+  LoopGroupsOff loop_off{};
+  int loop_cap = 0;             // groups a buffer holds; 0 = max_keyframes (fb_covis_reserve_loop_groups)
+  int loop_cur = 0;             // the buffer the next fb_covis_detect_loop_dev reads as the previous groups
   uint8_t *scr = nullptr;
   ScratchState state{};   // what scr holds; written by the scratch_*() of covis_plan.h only
   int ensure() {
@@ -564,10 +616,11 @@ int fb_covis_create(int32_t max_keyframes, fb_covis **out) {
 
 int fb_covis_destroy(fb_covis *g) {
   if (!g) return FB_OK;
-  if (g->block || g->scr || g->bird_block) {
+  if (g->block || g->scr || g->bird_block || g->loop_block) {
     (void)hipDeviceSynchronize();
     if (g->block) (void)hipFree(g->block);
     if (g->bird_block) (void)hipFree(g->bird_block);
+    if (g->loop_block) (void)hipFree(g->loop_block);
     if (g->scr) (void)hipFree(g->scr);
     (void)hipGetLastError();
   }
@@ -582,6 +635,7 @@ int fb_covis_clear(fb_covis *g, void *stream) {
   FB_HIP(hipMemsetAsync(g->G.W, 0, (size_t)g->K * g->K * 2, s));
   FB_HIP(hipMemsetAsync(g->G.err, 0, 4, s));
   if (g->WB) FB_HIP(hipMemsetAsync(g->WB, 0, (size_t)g->K * g->K * 2, s));
+  if (g->loop_block) FB_HIP(hipMemsetAsync(static_cast<uint8_t *>(g->loop_block) + g->loop_off.ng, 0, 2 * 4, s));   // mvConsistentGroups.clear()
   k_cv_tree_reset<<<(g->K + 255) / 256, 256, 0, s>>>(g->G);
   FB_HIP(hipGetLastError());
   return FB_OK;
@@ -623,8 +677,8 @@ int fb_covis_update_connections_dev(fb_covis *g, const fb_covis_map *M, int32_t 
   IndexAsk ask;
   ask.n_q = n_q;
   FB_TRY(g->acquire(*M, ask, &ix, nullptr, s));
-  k_cv_counter<<<n_q, CV_NT, 0, s>>>(*M, g->G, ix.start, ix.csr, d_slots, ix.counter);
-  k_cv_apply<<<1, CV_NT, 0, s>>>(g->G, n_q, d_slots, ix.counter, d_n_counter, d_front);
+  k_cv_counter<<<n_q, CV_NT, 0, s>>>(*M, g->G, ix.start, ix.csr, d_slots, ix.counter, nullptr);
+  k_cv_apply<false><<<1, CV_NT, 0, s>>>(g->G, n_q, d_slots, ix.counter, d_n_counter, d_front, LoopConnOut{});
   FB_HIP(hipGetLastError());
   return FB_OK;
 }
@@ -797,3 +851,4 @@ int fb_covis_keyframe_culling(fb_covis *g, const fb_covis_map *H, int32_t cur_sl
 #include "covis_fuse.inc"
 #include "covis_correct.inc"
 #include "covis_bird.inc"
+#include "covis_loop.inc"

@@ -157,6 +157,42 @@ inline size_t plan_local_bird_map(size_t K, size_t n_mpb, LbOff *o) {
   return r.off;
 }
 
+// The consistency groups of LoopClosing::DetectLoop (covis_loop.inc): a block of its own, allocated by the first call, like
+// the bird lists.  Two buffers of up to cap groups (previous and current; which is which is the handle's flag): a bitset
+// over the slots and a counter per group, and the number of groups of each buffer.  Behind them the scratch of one
+// fb_covis_detect_loop_dev: per previous group the first consistent candidate, per candidate its bitset, its number of
+// pushes (then their exclusive scan) and three flags.
+inline size_t loop_words(size_t K) { return (K + 31) / 32; }
+struct LoopGroupsOff { size_t bits[2], cons[2], ng, first, cbits, cnt, any, enough, valid; };
+inline size_t plan_loop_groups(size_t K, size_t cap, LoopGroupsOff *o) {
+  Regions r;
+  const size_t nw = loop_words(K);
+  for (int b = 0; b < 2; b++) { o->bits[b] = r.take(cap * nw * 4); o->cons[b] = r.take(cap * 4); }
+  o->ng = r.take(2 * 4);
+  o->first = r.take(cap * 4); o->cbits = r.take(K * nw * 4); o->cnt = r.take(K * 4);
+  o->any = r.take(K); o->enough = r.take(K); o->valid = r.take(K);
+  return r.off;
+}
+
+// fb_covis_loop_map_points_dev: the list walked (the ordered vector and the matched key frame: at most K + 1 entries) and
+// the first-occurrence arrays of the window's point collection
+struct LoopPointsOff { size_t hdr, wslot, rowcnt, ptkey, plist; };
+inline size_t plan_loop_points(size_t K, size_t n_mp, LoopPointsOff *o) {
+  Regions r;
+  o->hdr = r.take(256); o->wslot = r.take((K + 1) * 4); o->rowcnt = r.take((K + 1) * 4);
+  o->ptkey = r.take(n_mp * 4); o->plist = r.take(n_mp * 4);
+  return r.off;
+}
+
+// fb_covis_loop_connections_dev, behind an index with set_cap counter rows: LoopConnections as one bit row per set member
+// and the rows' sizes
+struct LoopConnOff { size_t bits, rowcnt; };
+inline size_t plan_loop_connections(size_t set_cap, size_t K, LoopConnOff *o) {
+  Regions r;
+  o->bits = r.take(set_cap * loop_words(K) * 4); o->rowcnt = r.take(set_cap * 4);
+  return r.off;
+}
+
 // ---- one call -------------------------------------------------------------------------------------------------------------
 struct CallPlan { size_t head, front, bird, tail, total; };   // where each part begins (an absent part is empty)
 inline CallPlan plan_call(size_t head_bytes, size_t front_bytes, size_t bird_bytes, size_t tail_bytes) {

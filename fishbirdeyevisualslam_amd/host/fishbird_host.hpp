@@ -988,6 +988,53 @@ struct CovisibilityMap {
     localKFbird.assign(kfs.begin(), kfs.begin() + nKf);
     return std::vector<int>(pts.begin(), pts.begin() + nPts);
   }
+
+  // ---- loop closing between the device calls (LoopClosing.cc:147-228, :355-375, :571-589) ----
+  // The consistency check of DetectLoop for vpCandidateKFs as slots: mvConsistentGroups lives on the handle;
+  // -> mvpEnoughConsistentCandidates.  nGroups / overflow: the header, when wanted.
+  std::vector<int> DetectLoop(fb_covis *g, const std::vector<int> &candidates, int consistencyTh = 3, int *nGroups = nullptr,
+                              bool *overflow = nullptr) const {
+    std::vector<int32_t> cand((size_t)maxKeyFrames, -1), enough((size_t)maxKeyFrames, -1);
+    int32_t n = (int32_t)std::min(candidates.size(), cand.size()), nEnough = 0;
+    std::copy(candidates.begin(), candidates.begin() + n, cand.begin());
+    fb_loop_groups_header h;
+    memset(&h, 0, sizeof(h));
+    check(fb_covis_detect_loop(g, &n, cand.data(), consistencyTh, &nEnough, enough.data(), &h));
+    if (nGroups) *nGroups = h.n_groups;
+    if (overflow) *overflow = h.overflow != 0;
+    return std::vector<int>(enough.begin(), enough.begin() + nEnough);
+  }
+  // mvpLoopMapPoints of mpMatchedKF = matched, as point indices
+  std::vector<int> LoopMapPoints(fb_covis *g, int matched) const {
+    const fb_covis_map m = view();
+    std::vector<int32_t> pts((size_t)m.n_mp + 1, -1);
+    int32_t n = 0, overflow = 0;
+    check(fb_covis_loop_map_points(g, &m, matched, m.n_mp, &n, pts.data(), &overflow));
+    return std::vector<int>(pts.begin(), pts.begin() + n);
+  }
+  // The pass over mvpCurrentConnectedKFs = connectedKFs that ends CorrectLoop: UpdateConnections of every member, and
+  // LoopConnections[member] per list position, each in the std::set's order.  updated: (KFcounter.size(), front) per member.
+  std::vector<std::vector<int>> LoopConnections(fb_covis *g, const std::vector<int> &connectedKFs,
+                                                std::vector<std::pair<int, int>> *updated = nullptr) const {
+    const fb_covis_map m = view();
+    const int32_t n = (int32_t)connectedKFs.size();
+    std::vector<std::vector<int>> rows((size_t)n);
+    if (n == 0) return rows;
+    std::vector<int32_t> nCounter((size_t)n, 0), front((size_t)n, -1), off((size_t)n + 1, 0), slots((size_t)n * maxKeyFrames, -1);
+    fb_loop_connections_header h;
+    memset(&h, 0, sizeof(h));
+    fb_loop_connections_args a;
+    memset(&a, 0, sizeof(a));
+    a.set_cap = n; a.d_n_set = &n; a.d_set = connectedKFs.data(); a.d_n_counter = nCounter.data(); a.d_front = front.data();
+    a.lc_cap = (int32_t)slots.size(); a.d_lc_off = off.data(); a.d_lc_slots = slots.data(); a.d_header = &h;
+    check(fb_covis_loop_connections(g, &m, &a));
+    for (int j = 0; j < n; j++) rows[(size_t)j].assign(slots.begin() + off[(size_t)j], slots.begin() + off[(size_t)j + 1]);
+    if (updated) {
+      updated->clear();
+      for (int j = 0; j < n; j++) updated->push_back(std::make_pair((int)nCounter[(size_t)j], (int)front[(size_t)j]));
+    }
+    return rows;
+  }
 };
 
 class CovisibilityGraph {

@@ -1456,8 +1456,8 @@ typedef struct fb_correct_loop_args {
  * d_set_Scw, when not NULL: row k = rows 0..2 of Converter::toCvMat(CorrectedSim3[d_set_slots[k]]), s * R and t of the
  * double Sim3, each cast to float once: the Scw that SearchAndFuse projects with.  It cannot be recovered afterwards (the
  * poses are overwritten and hold [R | t / s] rounded).  NULL: not written, nothing else changes.
- * Not restated: LoopConnections (:571-589), OptimizeEssentialGraph; the loop fusion (:545-560) is fb_covis_loop_fuse_dev,
- * SearchAndFuse fb_covis_search_and_fuse_dev.  Enqueues only.                                                                              */
+ * Not restated: OptimizeEssentialGraph; the loop fusion (:545-560) is fb_covis_loop_fuse_dev, SearchAndFuse
+ * fb_covis_search_and_fuse_dev, LoopConnections (:571-589) fb_covis_loop_connections_dev.  Enqueues only.               */
 int fb_covis_correct_loop_dev(fb_covis *g, const fb_covis_map *map, const fb_covis_kf_tables *tables,
                               const fb_correct_loop_args *a, void *stream);
 int fb_covis_correct_loop(fb_covis *g, const fb_covis_map *map, const fb_covis_kf_tables *tables,
@@ -1715,6 +1715,79 @@ int fb_covis_search_and_fuse_dev(fb_covis *g, const fb_covis_map *map, const fb_
 int fb_covis_search_and_fuse(fb_covis *g, const fb_covis_map *map, const fb_search_and_fuse_args *a); /* host pointers */
 int fb_covis_reserve_search_and_fuse(fb_covis *g, int32_t n_mp, int32_t n_obs, int32_t n_q, int32_t kp_stride, int32_t n_set,
                                      int32_t n_loop, int32_t grid_cells);
+
+/* ---- loop closing between the device calls: the consistency groups of DetectLoop (LoopClosing.cc:147-153, :155-228),
+ * mvpLoopMapPoints (:355-375) and LoopConnections (:571-589).  Integer work on state the handle holds. ------------------- */
+typedef struct fb_loop_groups_header {
+  int32_t n_groups;             /* mvConsistentGroups.size() after the call (what fitted)                              */
+  int32_t overflow;             /* != 0: more groups than cap_groups; what fitted is kept, nothing is written past it  */
+} fb_loop_groups_header;
+/* mvConsistentGroups lives on the handle, in a block of its own that the first of these calls allocates: up to cap_groups
+ * groups (default max_keyframes; set ahead here), each a bitset over the slots of (max_keyframes + 31) / 32 words, bit
+ * (slot & 31) of word (slot >> 5), and its consistency counter.  A call with another capacity than the block has makes a new
+ * block: the groups are gone.  fb_covis_clear empties the groups.  fb_covis_erase_keyframe_dev does not touch them (the
+ * reference's sets keep the pointer of a bad key frame), hence the precondition: a slot named in a live group is not handed
+ * to another key frame while the groups live.                                                                            */
+int fb_covis_reserve_loop_groups(fb_covis *g, int32_t cap_groups);
+/* The consistency check that follows DetectLoopCandidates, on d_n_candidates[1] / d_candidates[] exactly as
+ * fb_kfdb_query_dev wrote them (at most max_keyframes are read).  The group of candidate i is every slot with a non-zero
+ * weight in its row -- entries below FB_COVIS_TH and non-members of the ordered vector included, as GetConnectedKeyFrames
+ * returns them -- plus the candidate.  It is consistent with previous group g iff the two share a slot.  For each g only the
+ * first consistent candidate pushes (its group, counter[g] + 1); a candidate consistent with no g pushes (its group, 0);
+ * one consistent only with groups already taken pushes nothing.  The new list is candidate-major, then g ascending; the
+ * same group may appear several times with different counters.  A candidate is enough when any consistent g has
+ * counter[g] + 1 >= consistency_th (mnCovisibilityConsistencyTh, 3), taken or not: d_enough[max_keyframes] in candidate
+ * order, d_n_enough[1]; entries past the count are left alone.  *d_n_candidates == 0 empties the groups (:147-153).  A
+ * candidate outside [0, max_keyframes) is skipped and counted (fb_covis_error_count).  The early return on
+ * mnId < mLastLoopKFid + 10 (:117-122) stays with the host, which does not call.  Enqueues only.  The two buffers swap on
+ * the host side of the handle and the call's scratch lies in the same block, so consecutive calls (and fb_covis_loop_groups,
+ * fb_covis_clear) must be on one stream or ordered by the caller with events; then they take effect in call order.       */
+int fb_covis_detect_loop_dev(fb_covis *g, const int32_t *d_n_candidates, const int32_t *d_candidates, int32_t consistency_th,
+                             int32_t *d_n_enough, int32_t *d_enough, fb_loop_groups_header *d_header, void *stream);
+int fb_covis_detect_loop(fb_covis *g, const int32_t *n_candidates, const int32_t *candidates /* [max_keyframes] */,
+                         int32_t consistency_th, int32_t *n_enough, int32_t *enough, fb_loop_groups_header *header); /* host pointers */
+/* The groups as they stand: host pointers, waits for `stream`.  consistency[cap_groups] and bits[cap_groups][words] (either
+ * may be NULL); *n entries are written.                                                                                  */
+int fb_covis_loop_groups(fb_covis *g, int32_t *n, int32_t *consistency, uint32_t *bits, void *stream);
+
+/* mvpLoopMapPoints (:355-375): GetVectorCovisibleKeyFrames() of matched_slot in the vector's order, then matched_slot;
+ * within a key frame features ascending; a point is taken at its first occurrence if it is not NULL and not bad
+ * (mnLoopPointForKF is the mark of one call).  A kf_mp entry >= n_mp is skipped and counted.  d_loop_mp[cap] holds point
+ * indices as fb_search_and_fuse_args.d_loop_mp and fb_mp_list read them, d_n_loop[1] = min(count, cap), d_overflow[1] != 0
+ * when the list did not fit (what fitted is written, nothing past cap).  The edge list of the map is not read.  Enqueues
+ * only.                                                                                                                 */
+int fb_covis_loop_map_points_dev(fb_covis *g, const fb_covis_map *map, int32_t matched_slot, int32_t cap, int32_t *d_n_loop,
+                                 int32_t *d_loop_mp, int32_t *d_overflow, void *stream);
+int fb_covis_loop_map_points(fb_covis *g, const fb_covis_map *map, int32_t matched_slot, int32_t cap, int32_t *n_loop,
+                             int32_t *loop_mp, int32_t *overflow); /* host pointers */
+/* its scratch ahead of time, behind the index the handle holds (as fb_covis_reserve_local_bird_map)                      */
+int fb_covis_reserve_loop_map_points(fb_covis *g, int32_t n_mp);
+
+typedef struct fb_loop_connections_header {
+  int32_t total;                /* entries of LoopConnections over all rows                                            */
+  int32_t overflow;             /* != 0: total > lc_cap; what fitted is written, nothing past lc_cap                   */
+} fb_loop_connections_header;
+typedef struct fb_loop_connections_args {
+  int32_t set_cap;              /* rows of the batch (a launch parameter); 0 .. max_keyframes                          */
+  const int32_t *d_n_set;       /* [1] mvpCurrentConnectedKFs.size(); min(*d_n_set, set_cap) members are processed     */
+  const int32_t *d_set;         /* [set_cap] GetVectorCovisibleKeyFrames() of the current key frame, then the key frame */
+  int32_t *d_n_counter;         /* [set_cap] } as fb_covis_update_connections_dev; rows past the list are left alone   */
+  int32_t *d_front;             /* [set_cap] }                                                                         */
+  int32_t lc_cap;
+  int32_t *d_lc_off;            /* [set_cap + 1] CSR offsets (not clamped to lc_cap); rows past the list are empty     */
+  int32_t *d_lc_slots;          /* [lc_cap] each row in ascending kf_order (a std::set<KeyFrame*>)                     */
+  fb_loop_connections_header *d_header; /* [1]                                                                         */
+} fb_loop_connections_args;
+/* The pass that ends CorrectLoop (:571-589).  On the graph it is fb_covis_update_connections_dev over the list, in list
+ * order; the caller follows with fb_covis_first_connection_dev and fb_covis_update_bird_connections_dev as documented
+ * there.  Row j of LoopConnections = GetConnectedKeyFrames() of member j after its UpdateConnections (every entry of the
+ * new row; with an empty counter the row stays and is what is read), minus vpPreviousNeighbors -- the members of its
+ * ordered vector AT ITS TURN, after the AddConnections of the members before it, each of which rebuilds the vector of a
+ * changed row from every entry -- minus the members of the list.  A slot outside [0, max_keyframes) gives an empty row and
+ * is counted.  Enqueues only.                                                                                           */
+int fb_covis_loop_connections_dev(fb_covis *g, const fb_covis_map *map, const fb_loop_connections_args *a, void *stream);
+int fb_covis_loop_connections(fb_covis *g, const fb_covis_map *map, const fb_loop_connections_args *a); /* host pointers */
+int fb_covis_reserve_loop_connections(fb_covis *g, int32_t n_mp, int32_t n_obs, int32_t set_cap);
 
 /* ======================================================================== */
 /* Frame geometry either side of the matchers (src/Frame.cc)                 */
