@@ -378,6 +378,15 @@ class SearchAndFuseArgs(C.Structure):
                 ("added_cap", _i32), ("d_added", _vp), ("map", PointFuseArrays)]
 
 
+class SearchInNeighborsArgs(C.Structure):
+    _fields_ = [("cur_slot", _i32), ("n_features", _i32), ("n_targets", _i32), ("d_n_targets", _vp), ("d_targets", _vp), ("th", _f32),
+                ("cam", Camera), ("grid", GridGeom), ("scale_factors", _f32 * FB_MAX_LEVELS), ("inv_level_sigma2", _f32 * FB_MAX_LEVELS),
+                ("log_scale_factor", _f32), ("n_levels", _i32), ("kf_keys_un", _vp), ("kf_Tcw", _vp), ("mp_xw", _vp), ("mp_normal", _vp),
+                ("mp_min_dist", _vp), ("mp_max_dist", _vp), ("mp_ref_kf", _vp), ("obs_cap", _i32), ("obs_idx", _vp), ("new_edge_cap", _i32),
+                ("d_n_fused", _vp), ("cand_cap", _i32), ("d_n_candidates", _vp), ("d_candidates", _vp), ("d_n_added", _vp),
+                ("added_cap", _i32), ("d_added", _vp), ("d_n_counter", _vp), ("d_front", _vp), ("map", PointFuseArrays)]
+
+
 class LoopGroupsHeader(C.Structure):
     _fields_ = [("n_groups", _i32), ("overflow", _i32)]
 
@@ -537,6 +546,8 @@ EXPORTS = [
     "fb_covis_replace_points_dev", "fb_covis_replace_points", "fb_covis_reserve_replace_points",
     "fb_covis_loop_fuse_dev", "fb_covis_loop_fuse", "fb_covis_reserve_loop_fuse",
     "fb_covis_search_and_fuse_dev", "fb_covis_search_and_fuse", "fb_covis_reserve_search_and_fuse",
+    "fb_covis_fuse_targets_dev", "fb_covis_fuse_targets",
+    "fb_covis_search_in_neighbors_dev", "fb_covis_search_in_neighbors", "fb_covis_reserve_search_in_neighbors",
     "fb_covis_reserve_loop_groups", "fb_covis_detect_loop_dev", "fb_covis_detect_loop", "fb_covis_loop_groups",
     "fb_covis_loop_map_points_dev", "fb_covis_loop_map_points", "fb_covis_reserve_loop_map_points",
     "fb_covis_loop_connections_dev", "fb_covis_loop_connections", "fb_covis_reserve_loop_connections",

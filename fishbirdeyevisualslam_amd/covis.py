@@ -555,6 +555,49 @@ class CovisibilityGraph:
         self._keep = (m, a, fuse, t)
         return t["d_n_fused"], t["d_n_added"], t["d_added"]
 
+    # ---- LocalMapping::SearchInNeighbors ---------------------------------------------------------------------------------------------
+    def fuse_targets(self, cur_slot, kf_bad, nn=20, nn2=5, target_cap=None, guard=0):
+        """vpTargetKFs of LocalMapping::SearchInNeighbors (:481-503) from the handle's graph, duplicates included
+        -> (d_n_targets int32[1], the uncut length; d_targets int32[target_cap]).  Enqueues only."""
+        cap = int(nn) * (1 + int(nn2)) if target_cap is None else int(target_cap)
+        bad = self._filled(kf_bad, torch.uint8, self.K)
+        n, t = self._i32(1, -1), self._i32(cap + guard, -5)
+        check(lib().fb_covis_fuse_targets_dev(self.h, int(cur_slot), int(nn), int(nn2), _p(bad), cap, _p(n), _p(t), _stream()),
+              "fb_covis_fuse_targets_dev")
+        self._keep = (bad, n, t)
+        return n, t
+
+    def reserve_search_in_neighbors(self, n_mp, n_obs, new_edge_cap, kp_stride, n_targets, cand_cap, grid_cells):
+        check(lib().fb_covis_reserve_search_in_neighbors(self.h, int(n_mp), int(n_obs), int(new_edge_cap), int(kp_stride), int(n_targets),
+                                                         int(cand_cap), int(grid_cells)), "fb_covis_reserve_search_in_neighbors")
+
+    def search_in_neighbors(self, m, fuse, refresh, target, cur_slot, n_features, n_targets, d_n_targets, d_targets, kf_keys_un, new_edge_cap,
+                            cand_cap, th=3.0, added_cap=None, guard=0):
+        """LocalMapping::SearchInNeighbors (:506-557) for the key frame in cur_slot of m (a DeviceMap with obs_spare) and the
+        target list fuse_targets left on the device; n_targets: the launch bound (the exact count or the cap).  fuse: the
+        struct of point_fuse_arrays; refresh: the struct of refresh_arrays on the same map (kf_Tcw, mp_xw, mp_ref_kf and the
+        three arrays step 5 writes are read from it; its mp_desc is not used, fuse's is); target: a cabi.KfTarget whose cam,
+        grid, scale tables and n_levels are read.  -> dict of device tensors: n_fused [n_targets + 1], n_candidates [1],
+        candidates [cand_cap], n_added [1], added rows, n_counter [1], front [1].  The edge list of m is new_edge_cap
+        longer afterwards (m.grow).  Enqueues only."""
+        kp = kf_keys_un if torch.is_tensor(kf_keys_un) else torch.from_numpy(np.ascontiguousarray(kf_keys_un).view(np.uint8).reshape(-1).copy()).to(self.device)
+        n_targets, cand_cap, new_edge_cap = int(n_targets), int(cand_cap), int(new_edge_cap)
+        cap = new_edge_cap if added_cap is None else int(added_cap)
+        t = dict(d_n_fused=self._i32(n_targets + 1 + guard, -5), d_n_candidates=self._i32(1, -1), d_candidates=self._i32(cand_cap + guard, -5),
+                 d_n_added=self._i32(1, -1), d_added=torch.full(((max(cap, 1) + guard) * 4,), -5, dtype=torch.int32, device=self.device),
+                 d_n_counter=self._i32(1, -1), d_front=self._i32(1, -7))
+        a = cabi.SearchInNeighborsArgs()
+        cabi.fill(a, cur_slot=int(cur_slot), n_features=int(n_features), n_targets=n_targets, d_n_targets=d_n_targets, d_targets=d_targets,
+                  th=float(th), log_scale_factor=target.log_scale_factor, n_levels=target.n_levels, kf_keys_un=kp, obs_cap=int(m.obs_cap),
+                  obs_idx=m.t["obs_idx"], new_edge_cap=new_edge_cap, cand_cap=cand_cap, added_cap=cap, **t)
+        for k in ("kf_Tcw", "mp_xw", "mp_normal", "mp_min_dist", "mp_max_dist", "mp_ref_kf"):
+            setattr(a, k, getattr(refresh, k))
+        a.cam, a.grid, a.scale_factors, a.inv_level_sigma2, a.map = target.cam, target.grid, target.scale_factors, target.inv_level_sigma2, fuse
+        check(lib().fb_covis_search_in_neighbors_dev(self.h, C.byref(m.c), C.byref(a), _stream()), "fb_covis_search_in_neighbors_dev")
+        m.grow(new_edge_cap)
+        self._keep = (m, a, fuse, refresh, t, kp, d_n_targets, d_targets)
+        return {k[2:]: v for k, v in t.items()}
+
     # ---- the bird side: UpdateBirdConnections and the local bird map ------------------------------------------------------------
     def reserve_local_bird_map(self, n_mpb, n_bobs):
         check(lib().fb_covis_reserve_local_bird_map(self.h, int(n_mpb), int(n_bobs)), "fb_covis_reserve_local_bird_map")

@@ -11,6 +11,7 @@
 //   LoopClosing::CorrectLoop and the map update after the global BA  covis_correct.inc
 //   KeyFrame::UpdateBirdConnections and Map::UpdateLocalBirdMap      covis_bird.inc
 //   MapPoint::Replace and the loop fusion of CorrectLoop             covis_fuse.inc
+//   LocalMapping::SearchInNeighbors                                  covis_neighbors.inc
 //
 // State: one dense row of uint16 per key frame, W[a][b] = weight (bits 0..14, 0 = no entry) | member of the ordered vector
 // (bit 15).  mvpOrderedConnectedKeyFrames is always "descending by (weight, kf_order)" over the members, so it is derived
@@ -852,3 +853,4 @@ int fb_covis_keyframe_culling(fb_covis *g, const fb_covis_map *H, int32_t cur_sl
 #include "covis_correct.inc"
 #include "covis_bird.inc"
 #include "covis_loop.inc"
+#include "covis_neighbors.inc"

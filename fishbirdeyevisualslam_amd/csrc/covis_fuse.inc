@@ -225,6 +225,27 @@ void saf_map(uint8_t *b, const SafOff &o, SafS *S) {
   S->rep = (int32_t *)(b + o.rep);
 }
 
+// What the prepare kernels of SearchAndFuse and SearchInNeighbors (covis_neighbors.inc) share.  S: the scratch of the call
+// (kps, kdesc; xw, normal, mind, maxd, desc, best), P: its arguments (the point getters and map.mp_desc).
+// feature i of key frame `slot` as the search's batch of one reads it
+template <typename Scr>
+__device__ __forceinline__ void fz_stage_feature(const Scr &S, const fb_keypoint *kf_keys_un, const uint8_t *kf_desc, int slot, int St, int i) {
+  S.kps[i] = kf_keys_un[(size_t)slot * St + i];
+  const uint4 *src = reinterpret_cast<const uint4 *>(kf_desc + ((size_t)slot * St + i) * 32);
+  uint4 *dst = reinterpret_cast<uint4 *>(S.kdesc + (size_t)i * 32);
+  dst[0] = src[0]; dst[1] = src[1];
+}
+// point mp as entry i of the search's list: its getters and its descriptor as they stand
+template <typename Scr, typename Args>
+__device__ __forceinline__ void fz_stage_point(const Scr &S, const Args &P, int mp, int i) {
+  for (int c = 0; c < 3; c++) { S.xw[i * 3 + c] = P.mp_xw[(size_t)mp * 3 + c]; S.normal[i * 3 + c] = P.mp_normal[(size_t)mp * 3 + c]; }
+  S.mind[i] = P.mp_min_dist[mp]; S.maxd[i] = P.mp_max_dist[mp];
+  const uint4 *src = reinterpret_cast<const uint4 *>(P.map.mp_desc + (size_t)mp * 32);
+  uint4 *dst = reinterpret_cast<uint4 *>(S.desc + (size_t)i * 32);
+  dst[0] = src[0]; dst[1] = src[1];
+  S.best[i] = -1;
+}
+
 // Key frame k of the set as the search reads it, spAlreadyFound (:994) and the loop points with their skip rule (:1006), from
 // the map as it stands.  One workgroup.
 __global__ __launch_bounds__(CV_NT) void k_saf_prepare(fb_covis_map M, fb_search_and_fuse_args P, int k, SafS S, int32_t *err) {
@@ -235,10 +256,7 @@ __global__ __launch_bounds__(CV_NT) void k_saf_prepare(fb_covis_map M, fb_search
   }
   const int N = min(max(M.kf_n[slot], 0), St);
   for (int i = tid; i < St; i += CV_NT) {
-    S.kps[i] = P.kf_keys_un[(size_t)slot * St + i];
-    const uint4 *src = reinterpret_cast<const uint4 *>(P.map.kf_desc + ((size_t)slot * St + i) * 32);
-    uint4 *dst = reinterpret_cast<uint4 *>(S.kdesc + (size_t)i * 32);
-    dst[0] = src[0]; dst[1] = src[1];
+    fz_stage_feature(S, P.kf_keys_un, P.map.kf_desc, slot, St, i);
     if (i < N) {
       const int p = M.kf_mp[(size_t)slot * St + i];
       if (p >= M.n_mp) atomicAdd(err, 1);
@@ -252,12 +270,7 @@ __global__ __launch_bounds__(CV_NT) void k_saf_prepare(fb_covis_map M, fb_search
     const int mp = P.d_loop_mp[i];
     if (mp < 0 || mp >= M.n_mp) { atomicAdd(err, 1); S.valid[i] = 0; continue; }
     S.valid[i] = (!M.mp_bad[mp] && ld(&S.mark[mp]) != k + 1) ? 1 : 0;
-    for (int c = 0; c < 3; c++) { S.xw[i * 3 + c] = P.mp_xw[(size_t)mp * 3 + c]; S.normal[i * 3 + c] = P.mp_normal[(size_t)mp * 3 + c]; }
-    S.mind[i] = P.mp_min_dist[mp]; S.maxd[i] = P.mp_max_dist[mp];
-    const uint4 *src = reinterpret_cast<const uint4 *>(P.map.mp_desc + (size_t)mp * 32);
-    uint4 *dst = reinterpret_cast<uint4 *>(S.desc + (size_t)i * 32);
-    dst[0] = src[0]; dst[1] = src[1];
-    S.best[i] = -1;
+    fz_stage_point(S, P, mp, i);
   }
 }
 
@@ -377,10 +390,12 @@ int check_search_and_fuse(const fb_covis *g, const fb_covis_map *M, const fb_sea
 }
 
 // the index of M, the log behind it, and the walk's arguments
+// (n_q: counter rows the index is sized with, for a call that builds it again at the same place for an UpdateConnections)
 int fz_begin(fb_covis *g, const fb_covis_map *M, const fb_point_fuse_arrays &A, size_t n_new, FzRun *R, hipStream_t s, size_t more = 0,
-             uint8_t **more_at = nullptr) {
+             uint8_t **more_at = nullptr, size_t n_q = 0) {
   FzOff fo;
   IndexAsk ask;
+  ask.n_q = n_q;
   const size_t log_bytes = plan_point_fuse(M->n_mp, M->n_obs, n_new, &fo);
   ask.tail = log_bytes + more;
   Index ix;

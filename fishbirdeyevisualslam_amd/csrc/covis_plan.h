@@ -139,6 +139,25 @@ inline size_t plan_search_and_fuse(size_t n_mp, size_t S, size_t n_loop, size_t 
   return r.off;
 }
 
+// fb_covis_search_in_neighbors_dev, behind the log: the flags and lists of the call (hdr: the window's header ints, then
+// ok, the clamped target and candidate counts and cur as the query of the closing UpdateConnections), the snapshot of cur's
+// row, one key frame's copy and one point list of `list` entries (the snapshot or the candidates), used again for every
+// Fuse, and the first-occurrence arrays of the window's point collection over `n_targets` list entries
+struct SinOff {
+  size_t hdr, snap, wslot, rowcnt, ptkey, plist, kps, kdesc, n_kf, n_list, pose, ow, cell_start, cell_items, valid, xw, normal, mind, maxd,
+      desc, best;
+};
+inline size_t plan_search_in_neighbors(size_t n_mp, size_t S, size_t n_targets, size_t list, size_t cells, SinOff *o) {
+  Regions r;
+  o->hdr = r.take(256); o->snap = r.take(S * 4); o->wslot = r.take((n_targets + 1) * 4); o->rowcnt = r.take((n_targets + 1) * 4);
+  o->ptkey = r.take(n_mp * 4); o->plist = r.take(n_mp * 4);
+  o->kps = r.take(S * 24); o->kdesc = r.take(S * 32); o->n_kf = r.take(4); o->n_list = r.take(4); o->pose = r.take(48); o->ow = r.take(12);
+  o->cell_start = r.take((cells + 1) * 4); o->cell_items = r.take(S * 4); o->valid = r.take(list);
+  o->xw = r.take(list * 12); o->normal = r.take(list * 12); o->mind = r.take(list * 4); o->maxd = r.take(list * 4);
+  o->desc = r.take(list * 32); o->best = r.take(list * 4);
+  return r.off;
+}
+
 // the bird lists of every key frame (mvpBirdConnectedKeyFrames and their weights), in the format of W: a block of its own,
 // allocated by the first bird call, so that plan_graph stays what a handle without the bird side pays
 struct BirdGraphOff { size_t WB; };

@@ -952,6 +952,54 @@ struct CovisibilityMap {
     return out;
   }
 
+  // ---- LocalMapping::SearchInNeighbors (LocalMapping.cc:478-558) ----
+  // vpTargetKFs of :481-503 for mpCurrentKeyFrame = cur from the handle's graph, in the reference's order with its duplicates
+  std::vector<int> FuseTargets(fb_covis *g, const PointTables &t, int cur, int nn = 20, int nn2 = 5) const {
+    const int32_t cap = nn * (1 + nn2);
+    std::vector<int32_t> targets((size_t)cap + 1, -1);
+    int32_t n = 0;
+    check(fb_covis_fuse_targets(g, cur, nn, nn2, t.kfBad.data(), cap, &n, targets.data()));
+    return std::vector<int>(targets.begin(), targets.begin() + std::min(n, cap));
+  }
+  struct Neighbors : Fused {                          // nFused: one per target, then the one of Fuse(cur, candidates)
+    std::vector<int> candidates;                      // vpFuseCandidates
+    int nCounter = 0, front = -1;                     // of the closing UpdateConnections, as UpdateConnections returns them
+  };
+  // :506-557 for the targets of FuseTargets: Fuse into each target, the candidates, Fuse into cur, the refresh of cur's points
+  // (mpNormal, mpMinDist, mpMaxDist, mpDesc) and UpdateConnections(cur).  The edge list grows by newEdgeCap entries (default:
+  // kpStride per Fuse call), new edges first, then tombstones.  UpdateBirdConnections stays the caller's next call.
+  Neighbors SearchInNeighbors(fb_covis *g, PointTables &t, const FuseTarget &target, int cur, const std::vector<int> &targets, float th = 3.0f,
+                              int newEdgeCap = -1) {
+    Neighbors out;
+    const size_t nT = targets.size(), grow = newEdgeCap >= 0 ? (size_t)newEdgeCap : (nT + 1) * (size_t)kpStride, nMp = mpBad.size();
+    const int32_t n0 = (int32_t)obsKf.size();
+    obsMp.resize((size_t)n0 + grow, -1); obsKf.resize((size_t)n0 + grow, -1); obsIdx.resize((size_t)n0 + grow, -1);
+    fb_covis_map m = view();
+    m.n_obs = n0;
+    fb_search_in_neighbors_args a;
+    memset(&a, 0, sizeof(a));
+    int32_t nRep = 0, nAdded = 0, nCand = 0, nTargets = (int32_t)nT, nCounter = 0, front = -1;
+    std::vector<int32_t> rows(nMp * 2 + 2, -1), added(grow * 4 + 4, -1), nFused(nT + 1, 0), cand(nMp + 1, -1), tg(targets.begin(), targets.end());
+    tg.push_back(-1);
+    a.cur_slot = cur; a.n_features = kfN[cur]; a.n_targets = nTargets; a.d_n_targets = &nTargets; a.d_targets = tg.data(); a.th = th;
+    a.cam = target.cam; a.grid = target.grid; a.log_scale_factor = target.logScaleFactor; a.n_levels = target.nLevels;
+    a.kf_keys_un = target.keysUn.data();
+    memcpy(a.scale_factors, target.scaleFactors, sizeof(a.scale_factors));
+    memcpy(a.inv_level_sigma2, target.invLevelSigma2, sizeof(a.inv_level_sigma2));
+    a.kf_Tcw = t.kfTcw.data(); a.mp_xw = t.mpXw.data(); a.mp_normal = t.mpNormal.data(); a.mp_min_dist = t.mpMinDist.data();
+    a.mp_max_dist = t.mpMaxDist.data(); a.mp_ref_kf = t.mpRefKF.data();
+    a.obs_cap = (int32_t)obsKf.size(); a.obs_idx = obsIdx.data(); a.new_edge_cap = (int32_t)grow; a.d_n_fused = nFused.data();
+    a.cand_cap = (int32_t)nMp; a.d_n_candidates = &nCand; a.d_candidates = cand.data();
+    a.d_n_added = &nAdded; a.added_cap = (int32_t)grow; a.d_added = added.data(); a.d_n_counter = &nCounter; a.d_front = &front;
+    a.map = fuseView(t, &nRep, rows);
+    check(fb_covis_search_in_neighbors(g, &m, &a));
+    collect(out, nRep, rows, nAdded, added);
+    out.nFused.assign(nFused.begin(), nFused.end());
+    out.candidates.assign(cand.begin(), cand.begin() + std::min((size_t)std::max(nCand, 0), nMp));
+    out.nCounter = nCounter; out.front = front;
+    return out;
+  }
+
  private:
   fb_point_fuse_arrays fuseView(PointTables &t, int32_t *nRep, std::vector<int32_t> &rows) {
     fb_point_fuse_arrays f;

@@ -1716,6 +1716,88 @@ int fb_covis_search_and_fuse(fb_covis *g, const fb_covis_map *map, const fb_sear
 int fb_covis_reserve_search_and_fuse(fb_covis *g, int32_t n_mp, int32_t n_obs, int32_t n_q, int32_t kp_stride, int32_t n_set,
                                      int32_t n_loop, int32_t grid_cells);
 
+/* ---- LocalMapping::SearchInNeighbors (LocalMapping.cc:478-558) with ORBmatcher::Fuse(pKF, vpMapPoints, th)
+ * (ORBmatcher.cc:826-976) on fb_covis_map, in two calls: the target list from the handle's graph, then everything else. */
+#define FB_FUSE_TARGETS_MAX 4096 /* entries of a target list that fb_covis_search_in_neighbors reads                     */
+/* The target list of :481-503 for the key frame in cur_slot: for each of GetBestCovisibilityKeyFrames(nn) of cur_slot that
+ * is not bad, the key frame is pushed and stamped, then each of its GetBestCovisibilityKeyFrames(nn2) is pushed if it is
+ * not bad, not stamped and not cur_slot.  Second neighbours are pushed without being stamped, as in the reference: a key
+ * frame reached through two first neighbours is listed twice, and again when its own turn as a first neighbour comes; a
+ * second neighbour that is an earlier first neighbour is skipped.  The stamps are this call's (mnFuseTargetForKF of another
+ * key frame's call cannot equal cur's id).  d_targets[target_cap] holds the list in that order, *d_n_targets its uncut
+ * length; if that exceeds target_cap what fits is written and one error is counted (fb_covis_error_count).
+ * nn * (1 + nn2) always suffices.  nn = 20 (monocular) and nn2 = 5 at :483, :495.  Enqueues only.                          */
+int fb_covis_fuse_targets_dev(fb_covis *g, int32_t cur_slot, int32_t nn, int32_t nn2, const uint8_t *d_kf_bad /* [max_keyframes] */,
+                              int32_t target_cap, int32_t *d_n_targets, int32_t *d_targets, void *stream);
+int fb_covis_fuse_targets(fb_covis *g, int32_t cur_slot, int32_t nn, int32_t nn2, const uint8_t *kf_bad, int32_t target_cap,
+                          int32_t *n_targets, int32_t *targets); /* host pointers */
+
+typedef struct fb_search_in_neighbors_args {
+  int32_t cur_slot;             /* mpCurrentKeyFrame                                                                   */
+  int32_t n_features;           /* its N as the host knows it; 0 .. kp_stride                                          */
+  int32_t n_targets;            /* launches of step 2 (a launch parameter); 0 .. FB_FUSE_TARGETS_MAX.  The exact count
+                                   read once from d_n_targets, or the cap: a launch past *d_n_targets returns at once   */
+  const int32_t *d_n_targets;   /* [1] } as fb_covis_fuse_targets_dev left them (the count is clamped to n_targets)      */
+  const int32_t *d_targets;     /* [n_targets] }                                                                       */
+  float th;                     /* 3, the default of Fuse at LocalMapping.cc:513, :538                                 */
+  fb_camera cam;                /* } the key-frame side that is the same for every key frame, as in fb_kf_target       */
+  fb_grid_geom grid;            /* }                                                                                   */
+  float scale_factors[FB_MAX_LEVELS];
+  float inv_level_sigma2[FB_MAX_LEVELS];
+  float log_scale_factor;
+  int32_t n_levels;
+  const fb_keypoint *kf_keys_un; /* [max_keyframes][kp_stride] mvKeysUn by slot                                        */
+  const float *kf_Tcw;          /* [max_keyframes][12]; Rcw|tcw of the search, and Ow as KeyFrame::SetPose makes it    */
+  const float *mp_xw;           /* [map.n_mp][3]                                                                       */
+  float *mp_normal;             /* [map.n_mp][3] } read by the search, written by step 5                               */
+  float *mp_min_dist;           /* [map.n_mp]    }                                                                     */
+  float *mp_max_dist;           /* [map.n_mp]    }                                                                     */
+  const int32_t *mp_ref_kf;     /* [map.n_mp] mpRefKF as a slot                                                        */
+  int32_t obs_cap;              /* capacity of the edge arrays; map.n_obs + new_edge_cap <= obs_cap (FB_ERR_CAPACITY)  */
+  int32_t *obs_idx;             /* the map's obs_idx, writable (the same pointer as in map)                            */
+  int32_t new_edge_cap;         /* edges the whole call may add                                                        */
+  int32_t *d_n_fused;           /* [n_targets + 1] nFused of each Fuse of step 2 (0 for an idle launch); the last is step 4's */
+  int32_t cand_cap;
+  int32_t *d_n_candidates;      /* [1] vpFuseCandidates.size(), uncut                                                  */
+  int32_t *d_candidates;        /* [cand_cap] vpFuseCandidates as point indices                                        */
+  int32_t *d_n_added;           /* [1] new edges of the whole call                                                     */
+  int32_t added_cap;
+  int32_t *d_added;             /* [added_cap][4] rows (key frame slot, point, feature, edge) in execution order       */
+  int32_t *d_n_counter;         /* [1] } of the closing UpdateConnections of cur_slot, as fb_covis_update_connections_dev */
+  int32_t *d_front;             /* [1] }                                                                               */
+  fb_point_fuse_arrays map;     /* d_replaced: the pairs of the whole call in execution order                          */
+} fb_search_in_neighbors_args;
+/* On one stream, without a host wait:
+ *  2. vpMapPointMatches = kf_mp[cur][0 .. n_features) is copied once.  Then per target k < *d_n_targets, in list order
+ *     (duplicates included), on the map as the target before left it: valid[i] = the snapshot's entry is not NULL, not bad
+ *     and has no live edge to the target (IsInKeyFrame is decided by edges); fb_fuse_search_dev with batch = 1 on the
+ *     descriptors, normals and distances as they stand, the pose and centre from kf_Tcw[target]; the commit (:952-972),
+ *     serial in i for best[i] >= 0, with valid[i] decided again on the live map: p = kf_mp[target][best] as it stands;
+ *     p >= 0 and not bad: Observations(p) > Observations(pMP) gives pMP->Replace(p), else p->Replace(pMP), both as
+ *     fb_covis_replace_points_dev (Observations = live edges; equality replaces p); p >= 0 and bad: nothing; p < 0:
+ *     AddObservation(pMP, target, best) and kf_mp[target][best] = pMP, without a descriptor refresh.  Each of the three
+ *     counts in nFused.
+ *  3. vpFuseCandidates: over the targets in list order, features ascending, every entry that is not NULL and not bad, at its
+ *     first occurrence, on the map as step 2 left it.  If the count exceeds cand_cap the first cand_cap are kept and fused,
+ *     and one error is counted.
+ *  4. the same Fuse with the key frame cur_slot and the candidates; its nFused is d_n_fused[n_targets].
+ *  5. every point that kf_mp[cur][0 .. n_features) holds now, if it is not bad: ComputeDistinctiveDescriptors and
+ *     UpdateNormalAndDepth as fb_covis_refresh_points_dev (mp_normal, mp_min_dist, mp_max_dist, map.mp_desc are written).
+ *  6. UpdateConnections of cur_slot as fb_covis_update_connections_dev with n_q = 1.  UpdateBirdConnections and
+ *     fb_covis_first_connection_dev stay the caller's follow-up calls, as after every other UpdateConnections.
+ * New edges: the call owns the block [map.n_obs, map.n_obs + new_edge_cap) of the edge arrays: its new edges in the order
+ * they were made, the rest tombstones; the caller goes on with n_obs + new_edge_cap.  An add that finds the block full is
+ * not made at all (no kf_mp write, no edge, not counted in nFused); one error is counted and the steps after it run.
+ * If kf_n[cur] != n_features the block is all tombstones, every count is 0, *d_front = -1, nothing else is written and one
+ * error is counted.  A target slot, a snapshot entry, a candidate or a kf_mp entry out of range is skipped and counted
+ * (a snapshot entry once per target).  The overflow contract of fb_covis_replace_points holds.  Afterwards the handle's
+ * point -> edge index is the one of the grown map (n_obs + new_edge_cap) and is valid for a reuse_index.  The scratch is
+ * sized by fb_covis_reserve_search_in_neighbors or by the call.  Enqueues only: 4 launches per target and per step 4.      */
+int fb_covis_search_in_neighbors_dev(fb_covis *g, const fb_covis_map *map, const fb_search_in_neighbors_args *a, void *stream);
+int fb_covis_search_in_neighbors(fb_covis *g, const fb_covis_map *map, const fb_search_in_neighbors_args *a); /* host pointers */
+int fb_covis_reserve_search_in_neighbors(fb_covis *g, int32_t n_mp, int32_t n_obs, int32_t new_edge_cap, int32_t kp_stride,
+                                         int32_t n_targets, int32_t cand_cap, int32_t grid_cells);
+
 /* ---- loop closing between the device calls: the consistency groups of DetectLoop (LoopClosing.cc:147-153, :155-228),
  * mvpLoopMapPoints (:355-375) and LoopConnections (:571-589).  Integer work on state the handle holds. ------------------- */
 typedef struct fb_loop_groups_header {
